@@ -19,6 +19,14 @@ resident in HBM for `value`; the PCIe-inclusive rate of the same frames is repor
 `python bench.py --gpus N` starts its own N rank processes (before anything touches the GPU) unless
 it already runs under a launcher (WORLD_SIZE set, e.g. torch.distributed.run).  Rank 0 prints ONE
 JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`, the
+roofline from the headline loop's own events).  --full adds everything else: the legs above
+(`end_to_end`, `frames_sharded`, the serial / orbit / interpreter loops), the wave statistics, the
+measured write ceiling, the cold hipRTC compile time, the CPU baseline and `parity`, the bit-exact
+check of the timed frames against the oracle (a difference makes the run exit non-zero).
+--dump-outputs DIR writes the frame the last timed step drew as .npy files; the inputs depend on the
+arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import gc
@@ -35,6 +43,7 @@ FP32_VECTOR_PEAK_TFLOPS = 157.3  # ditto
 BYTES_PER_PIXEL = 16             # one RGBA32F store per pixel: SURVEY 8(d) algorithmic bytes
 SALU_CYCLES_PER_INST = 4.33       # measured: tools/ubench_salu.hip
 VALU_CYCLES_PER_WAVE_INST = 2.0  # MI355X_MICROARCH.md: a wave64 VALU instruction occupies a SIMD-32 for 2 cycles
+DUMP_BYTES = 64 * 1000 * 1000 - (1 << 16)   # --dump-outputs: all files of all ranks together, .npy headers included
 
 
 def parse(argv=None):
@@ -67,14 +76,25 @@ def parse(argv=None):
     p.add_argument("--dist-backend", default="nccl", help="process-group backend for the timing barrier (nccl = RCCL)")
     p.add_argument("--all-ranks-on-device0", action="store_true",
                    help="rehearsal on a one-GPU box: every rank uses GPU 0 (use with --dist-backend gloo)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline: the serial / orbit / interpreter / end-to-end legs, the wave statistics, the measured "
+                        "write ceiling, the cold hipRTC compile, the CPU baseline and the bit-exact parity check against the oracle "
+                        "(a plain run times the headline loop and nothing else)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the frame of the last timed step as DIR/frame.npy (float32, H x W x RGBA; with tiling over ranks "
+                        "DIR/strips_rank<r>.npy, each rank's strips; above %d bytes a fixed, seeded sample of pixels, "
+                        "<name>_sample.npy)" % DUMP_BYTES)
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
     p.add_argument("--no-legs", "--no-ab", dest="no_legs", action="store_true",
-                   help="only the headline measurement (skips the serial / orbit / interpreter / end-to-end legs)")
+                   help="with --full: skip the serial / orbit / interpreter / end-to-end legs")
     p.add_argument("--frames-in-flight", type=int, default=4,
                    help="frames drawn concurrently, each on its own context / stream / output buffer (1 = strictly serial)")
     p.add_argument("--cpu-sample-div", type=int, default=1, help="CPU baseline renders W/div x H/div")
     p.add_argument("--launch-timeout", type=float, default=900.0, help="--gpus N self-launch: seconds before the ranks are stopped")
-    return p.parse_args(argv)
+    a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def host_cores():
@@ -145,6 +165,21 @@ def compare_frames(gpu, ref):
     return float(d[differ].max()), n
 
 
+def dump_output(out_dir, name, img, budget):
+    """--dump-outputs: one RGBA32F image as out_dir/<name>.npy (float32).  An image of more than `budget` bytes is written as a
+    fixed, seeded sample of its pixels instead (<name>_sample.npy, n x 4, in raster order): the same pixels in every run with the
+    same arguments, so two builds compare output for output."""
+    import numpy as np
+    a = np.ascontiguousarray(img, dtype=np.float32)
+    if a.nbytes > budget:
+        px = a.reshape(-1, a.shape[-1])
+        n = max(1, budget // px[0].nbytes)
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=n, replace=False))
+        a, name = px[idx], name + "_sample"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def run_rank(args):
     import torch
     import torch.distributed as dist
@@ -179,6 +214,9 @@ def run_rank(args):
             sys.stderr.write("bench.py: RCCL barrier group unavailable (%s); using gloo\n" % fallback_reason)
 
     W, H, K = args.width, args.height, args.steps
+    # a plain run times the headline loop and prints its line; everything else is --full's
+    legs_on = args.full and not args.no_legs
+    cpu_on = args.full and not args.no_cpu_baseline
     mode = args.mode
     if mode == "auto":
         mode = "tile" if (world > 1 and args.camera == "still") else "frames"
@@ -321,7 +359,7 @@ def run_rank(args):
     # what the compiler takes for this structure when the on-disk cache of compiled kernels does not have it (the first time a
     # structure is drawn on a machine): the same source through hipRTC with the cache switched off, untimed set-up
     jit_cold_ms = None
-    if rank == 0 and specialized:
+    if rank == 0 and specialized and args.full:
         old_dir = os.environ.get("RM_JIT_CACHE_DIR")
         os.environ["RM_JIT_CACHE_DIR"] = "off"
         try:
@@ -335,10 +373,16 @@ def run_rank(args):
                 os.environ["RM_JIT_CACHE_DIR"] = old_dir
     last = (strips if tile else full)[(K - 1) % F]
     checksum = float(last[..., :3].double().sum().item())                     # touches the result: nothing was skipped
+    if args.dump_outputs:
+        # what the timed path computed in its last step: the frame timed step K - 1 drew (tiled: this rank's strips of it)
+        if tile:
+            dump_output(args.dump_outputs, "strips_rank%d" % rank, last[:my_rows].cpu().numpy(), DUMP_BYTES // world)
+        elif rank == 0:
+            dump_output(args.dump_outputs, "frame", last.cpu().numpy(), DUMP_BYTES)
     # every in-flight buffer as the timed loop left it, with the uniforms of the last draw into it: `parity` (below) compares
     # ALL of them with the oracle's render of the same uniforms
     snaps = []
-    if world == 1 and not tile and not args.no_cpu_baseline:
+    if world == 1 and not tile and cpu_on:
         for i in range(F):
             snaps.append((bytes(last_uniforms(unis, i, F)), full[i].cpu().numpy()))
     frames_per_step = 1 if tile else world
@@ -348,7 +392,7 @@ def run_rank(args):
     exit_code = 0
     orbit_snap = None
     useful_occ = None
-    if not args.no_legs:
+    if legs_on:
         # strictly serial loop (one frame in flight): what ONE frame costs, and the only honest source of per-launch
         # durations (with several frames in flight an event-bracketed draw also contains time queued behind the others)
         s_el, s_draw, s_k = timed(1, headline_draw, unis)
@@ -447,7 +491,7 @@ def run_rank(args):
             o_el, _, _ = timed(F, draw_full, ounis)
             legs["orbit_camera"] = {"value": W * H * K / o_el / 1e6, "unit": "Mpixels/s",
                                     "what": "same loop, frame f of a 1024-frame orbit (yaw 2 pi f / 1024, pitch -0.25, r 5)"}
-            if not args.no_cpu_baseline:     # one sampled frame of the leg for `parity`: the last one drawn
+            if cpu_on:                       # one sampled frame of the leg for `parity`: the last one drawn
                 i_last = (K - 1) % F
                 orbit_snap = (bytes(last_uniforms(ounis, i_last, F)), full[i_last].cpu().numpy(), (args.warmup + K - 1) % 1024)
         if world == 1 and specialized:
@@ -511,7 +555,7 @@ def run_rank(args):
                                  "magnitude, see `compute`"},
             "checksum_rgb": checksum,
         }
-        if world == 1 and not args.no_legs:
+        if world == 1 and legs_on:
             # the measured HBM-write ceiling of this GPU, same run: a fill kernel with 16 B/lane stores over 1 GiB
             # (SURVEY 8(d)); the declared peak above stays the spec figure
             try:
@@ -523,7 +567,7 @@ def run_rank(args):
                 line["roofline"]["measured_write_error"] = str(e)
         line.update(legs)
         parity_ok = True
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_on:
             import numpy as np
             div = max(1, args.cpu_sample_div)
             cw, ch = W // div, H // div

@@ -164,14 +164,26 @@ def test_bench_mode_defaults():
     assert bench.parse([]).gpus == 1
 
 
+def _metric_camera_frame(oracle, W, H, max_iter):
+    """The oracle's render of bench.py's still camera (g32): what every step of a plain run draws."""
+    import numpy as np
+    from ray_marching_amd import camera, csg, renderer
+    ctl = camera.OrbitCameraController.new([0.0, 0.0, 0.0], 5.0)
+    ctl.update(camera.Orbit([35.0, -25.0]))
+    cc, words = csg.serialize(csg.scene("g32"))
+    u = oracle.Uniforms.from_buffer_copy(bytes(renderer.prepare_uniforms((float(W), float(H)), ctl.camera())))
+    return np.ascontiguousarray(oracle.render(u, (0.01, 100.0, max_iter), cc, words, W, H, threads=4), dtype=np.float32)
+
+
 @pytest.mark.gpu
-def test_bench_two_ranks_tile_one_frame_and_gather_it():
+def test_bench_two_ranks_tile_one_frame_and_gather_it(oracle, tmp_path):
     """`bench.py --gpus 2` as ONE command on a one-GPU box (both ranks on GPU 0, gloo for the timing barrier): the
     north-star layout -- frame tiled over the ranks in interleaved strips, host-side gather into one shared-memory frame --
     end to end, and the gathered frame is the single-GPU frame byte for byte."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--all-ranks-on-device0", "--dist-backend", "gloo",
-                        "--steps", "6", "--warmup", "2", "--width", "640", "--height", "360"],
+                        "--steps", "6", "--warmup", "2", "--width", "640", "--height", "360", "--full",
+                        "--dump-outputs", str(tmp_path / "tiled")],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -182,11 +194,21 @@ def test_bench_two_ranks_tile_one_frame_and_gather_it():
     assert line["roofline"]["bound"] == "hbm" and 0 < line["roofline"]["frac"] < 1 and line["roofline"]["kernel_ms"] > 0
     assert line["vs_baseline"] is None and line["unit"] == "Mpixels/s"
     assert line["config"]["barrier_backend"] == "gloo" and line["config"]["barrier_group_world_size"] == 2
+    # --dump-outputs: each rank's strips of the last timed frame; put back in place they are the oracle's frame, bit for bit
+    import numpy as np
+    from ray_marching_amd import shard
+    assert sorted(f.name for f in (tmp_path / "tiled").iterdir()) == ["strips_rank0.npy", "strips_rank1.npy"]
+    frame = np.zeros((360, 640, 4), dtype=np.float32)
+    for r in range(2):
+        strips = np.load(tmp_path / "tiled" / ("strips_rank%d.npy" % r))
+        assert strips.dtype == np.float32 and strips.shape == (shard.strip_row_count(360, shard.DEFAULT_STRIP_ROWS, r, 2), 640, 4)
+        shard.scatter_strips(frame, strips, 360, r, 2)
+    assert frame.tobytes() == _metric_camera_frame(oracle, 640, 360, 256).tobytes()
 
 
 @pytest.mark.gpu
 def test_bench_one_gpu_line_has_every_contract_key():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--cpu-sample-div", "8"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--cpu-sample-div", "8", "--full"],
                        capture_output=True, text=True, timeout=600,
                        env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert p.returncode == 0, p.stderr[-3000:]
@@ -207,3 +229,60 @@ def test_bench_one_gpu_line_has_every_contract_key():
     assert line["parity"]["vs"] == "oracle" and line["parity"]["pixels_differing"] == 0 and line["parity"]["max_abs_diff"] == 0.0
     assert line["parity"]["frames_checked"] >= 1
     assert 0.3 < line["compute"]["useful_lane_occupancy"] <= 1.0
+
+
+def test_bench_plain_run_is_the_default_and_steps_are_checked():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None and a.steps == 200 and a.warmup == 20
+    a = bench.parse(["--steps", "7", "--warmup", "0", "--full", "--dump-outputs", "out"])
+    assert a.steps == 7 and a.warmup == 0 and a.full is True and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_bench_dump_output_writes_small_frames_whole_and_samples_large_ones(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    img = np.arange(6 * 10 * 4, dtype=np.float32).reshape(6, 10, 4)
+    bench.dump_output(str(tmp_path / "a"), "frame", img, 1 << 20)
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == img.shape and (got == img).all()
+    # over the budget: a fixed, seeded sample of whole pixels, in raster order, the same in every run
+    for d in ("b", "c"):
+        bench.dump_output(str(tmp_path / d), "frame", img, 16 * 25)
+        assert not (tmp_path / d / "frame.npy").exists()
+    s1, s2 = np.load(tmp_path / "b" / "frame_sample.npy"), np.load(tmp_path / "c" / "frame_sample.npy")
+    assert s1.dtype == np.float32 and s1.shape == (25, 4) and (s1 == s2).all()
+    first = s1[:, 0].astype(np.int64)
+    assert (np.diff(first) > 0).all() and (first % 4 == 0).all()
+    assert (s1 == img.reshape(-1, 4)[first // 4]).all()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_the_frame_of_the_last_one(oracle, tmp_path):
+    """A plain run (no --full): the headline loop and its line, nothing else; --dump-outputs writes the frame the last timed
+    step drew, which must be the oracle's render of the metric camera, bit for bit."""
+    import numpy as np
+    W, H, it = 320, 180, 256
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--width", str(W),
+                        "--height", str(H), "--max-iter", str(it), "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600,
+                       env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+        assert key in line, key
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "Mpixels/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    for key in ("cpu_baseline", "parity", "compute", "one_frame_in_flight", "end_to_end", "orbit_camera", "ab_interpreter_kernel"):
+        assert key not in line, key
+    assert sorted(f.name for f in out.iterdir()) == ["frame.npy"]
+    img = np.load(out / "frame.npy")
+    assert img.dtype == np.float32 and img.shape == (H, W, 4)
+    assert img.tobytes() == _metric_camera_frame(oracle, W, H, it).tobytes()
+    assert abs(float(img[..., :3].astype(np.float64).sum()) - line["checksum_rgb"]) <= 1e-6 * max(1.0, abs(line["checksum_rgb"]))

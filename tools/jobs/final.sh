@@ -7,9 +7,9 @@ tail -2 "$out/gpu_suite.log"
 grep -q "suite rc=0" "$out/status.txt" || { cat "$out/status.txt"; exit 1; }
 RM_FUZZ_FIRST_SEED=1000 RM_FUZZ_SEEDS=${FUZZ:-200} timeout -k 10 900 python -m pytest tests/test_gpu_fuzz.py -x -q -m gpu > "$out/fuzz.log" 2>&1; echo "fuzz rc=$?" >> "$out/status.txt"
 tail -1 "$out/fuzz.log"
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench1 rc=$?" >> "$out/status.txt"
-timeout -k 10 300 python bench.py --gpus 2 --all-ranks-on-device0 --dist-backend gloo --steps 20 --warmup 5 > "$out/bench_n2.json" 2> "$out/bench_n2.err"; echo "bench2 rc=$?" >> "$out/status.txt"
-timeout -k 10 300 python bench.py > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "benchdef rc=$?" >> "$out/status.txt"
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench1 rc=$?" >> "$out/status.txt"
+timeout -k 10 300 python bench.py --gpus 2 --all-ranks-on-device0 --dist-backend gloo --steps 20 --warmup 5 --full > "$out/bench_n2.json" 2> "$out/bench_n2.err"; echo "bench2 rc=$?" >> "$out/status.txt"
+timeout -k 10 300 python bench.py --full > "$out/bench_default.json" 2> "$out/bench_default.err"; echo "benchdef rc=$?" >> "$out/status.txt"
 t() {  # label scene w h iters extra-args..
   label=$1; sc=$2; w=$3; h=$4; it=$5; shift 5
   r=$(python3 tools/time_kernel.py --scene $sc --width $w --height $h --max-iter $it --steps 30 "$@" 2>>"$out/err.log" | head -1)

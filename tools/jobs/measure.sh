@@ -5,7 +5,7 @@ mkdir -p "$out"
 timeout -k 10 600 python -m pytest tests -m gpu -x -q -k "$kexpr" > "$out/tests.log" 2>&1; echo "tests rc=$?" > "$out/status.txt"
 tail -3 "$out/tests.log"
 grep -q "tests rc=0" "$out/status.txt" || { cat "$out/status.txt"; exit 1; }
-timeout -k 10 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench rc=$?" >> "$out/status.txt"
+timeout -k 10 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench rc=$?" >> "$out/status.txt"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 timeout -k 10 200 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_BRANCH SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE \
   --output-format csv -d "$out/pmc" -- python3 bench.py --steps 20 --warmup 3 --frames-in-flight 1 --no-cpu-baseline --no-legs > "$out/pmc.log" 2>&1

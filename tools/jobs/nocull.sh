@@ -11,7 +11,7 @@ for round in 1 2; do
     echo "$1 $2x$3 | $r" | tee -a "$out/times.txt"
   done
 done
-python bench.py --steps 20 --warmup 5 > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench rc=$?" >> "$out/status.txt"
+python bench.py --steps 20 --warmup 5 --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench rc=$?" >> "$out/status.txt"
 python3 -c "
 import json; d=json.load(open('$out/bench_n1.json')); print('bench', round(d['value']), d['one_frame_in_flight'], round(d['end_to_end']['value']), round(d['orbit_camera']['value']), round(d['ab_interpreter_kernel']['value']))"
 cat "$out/status.txt"

@@ -11,6 +11,6 @@ for round in 1 2; do
     echo "$1 $2x$3 | $r" | tee -a "$out/times.txt"
   done
 done
-for i in 1 2; do python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
+for i in 1 2; do python bench.py --steps 20 --warmup 5 --no-cpu-baseline --full 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', round(d['value']), round(d['one_frame_in_flight']['value']), round(d['end_to_end']['value']), round(d['orbit_camera']['value']), round(d['ab_interpreter_kernel']['value']))" | tee -a "$out/times.txt"; done
 cat "$out/status.txt"

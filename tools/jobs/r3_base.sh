@@ -4,7 +4,7 @@
 out=$1; mkdir -p "$out"
 timeout -k 10 1000 python -m pytest tests -x -q -m gpu > "$out/gpu_suite.log" 2>&1; echo "suite rc=$?" > "$out/status.txt"
 tail -3 "$out/gpu_suite.log"
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench1 rc=$?" >> "$out/status.txt"
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench1 rc=$?" >> "$out/status.txt"
 t() { label=$1; sc=$2; w=$3; h=$4; it=$5; shift 5
   r=$(python3 tools/time_kernel.py --scene $sc --width $w --height $h --max-iter $it --steps 30 "$@" 2>>"$out/err.log" | head -1)
   echo "$label | $sc ${w}x${h}/$it | $r" | tee -a "$out/times.txt"; }

@@ -23,7 +23,7 @@ for cfg in "g32 1920 1080 256" "g8 1920 1080 128" "g8x 1920 1080 128" "g32 3840 
 import json,sys; d=json.loads(sys.stdin.readline()); print('$1 $2x$3/$4: %.0f Mpx/s  march %.3f ms  draw %.3f ms' % (d['value'], d['roofline']['kernel_ms'], d['roofline']['draw_ms']))" | tee -a "$out/configs.txt"
 done
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$out/smoke.log" 2>&1; echo "smoke rc=$?" >> "$out/status.txt"; tail -2 "$out/smoke.log"
-timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench rc=$?" >> "$out/status.txt"
+timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench rc=$?" >> "$out/status.txt"
 python3 -c "
 import json; d=json.load(open('$out/bench_n1.json'))
 print('bench', d['value'], d['parity']['pixels_differing'], d.get('one_frame_in_flight'), d['ab_interpreter_kernel']['value'], d['roofline'])"

@@ -27,5 +27,5 @@ for sc in g32 g32s; do
 RM_JIT_PRUNE_STATS=1 python3 tools/wave_stats.py --scene $sc --width 1920 --height 1080 --kernel 0 --prune --balance 3 > "$out/stats_$sc.txt" 2>&1
 head -6 "$out/stats_$sc.txt"
 done
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench1 rc=$?" >> "$out/status.txt"
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench1 rc=$?" >> "$out/status.txt"
 cat "$out/status.txt"

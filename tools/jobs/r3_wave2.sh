@@ -20,7 +20,7 @@ for round in 1 2; do
   t "interpreter" g32_balanced 1920 1080 256 --specialize 0
   t "interpreter" g32s 1920 1080 256 --specialize 0
 done
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench1 rc=$?" >> "$out/status.txt"
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full > "$out/bench_n1.json" 2> "$out/bench_n1.err"; echo "bench1 rc=$?" >> "$out/status.txt"
 python3 -c "
 import json; d=json.load(open('$out/bench_n1.json'))
 print('bench', d['value'], d['parity']['pixels_differing'], d['one_frame_in_flight'], d['ab_interpreter_kernel']['value'])"
