@@ -259,9 +259,8 @@ int ensure_materials(rm_ctx* c, hipStream_t s) {
 // (default) whichever applies if the program evaluates enough leaves for the tests to pay.
 int prune_kind(const RmDecoded& d, int option) {
     if (option == 0) return rmjit::PRUNE_NONE;
-    static const uint32_t blend_leaves = std::getenv("RM_BLEND_PRUNE_LEAVES") ? (uint32_t)std::atoi(std::getenv("RM_BLEND_PRUNE_LEAVES")) : kBlendPruneLeaves;
     if (d.unit_mode == RM_UNITS_LATTICE && (option == 1 || d.n_leaves >= kPruneLeaves)) return rmjit::PRUNE_LATTICE;
-    if (d.unit_mode == RM_UNITS_BLEND && (option == 1 || d.n_leaves >= blend_leaves)) return rmjit::PRUNE_BLEND;
+    if (d.unit_mode == RM_UNITS_BLEND && (option == 1 || d.n_leaves >= kBlendPruneLeaves)) return rmjit::PRUNE_BLEND;
     return rmjit::PRUNE_NONE;
 }
 
@@ -363,42 +362,41 @@ constexpr size_t kV5TailBytes = 16u + 144u;
 template <int WPT>
 int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hipStream_t s) {
     RmLaunch L = L_in;
-    bool cull = c->cull && L.n_rec <= 256u && !c->decoded.cull_veto;
+    const RmDecoded& d = c->decoded;
+    bool cull = c->cull && L.n_rec <= 256u && !d.cull_veto;
     if (L.n_rec == 0u && L.max_dist < L.min_dist) cull = false;  // see launch_multi_w
     L.n_cull = cull ? L.n_rec : 0u;
-    // interpreter kernels: which map_scene loop a chain program takes (RmLaunch::flags).  RM_CHAIN_MODE (diagnostics):
-    // 0 the general record loop, 1 the chain / tree loops over every record, 2 (default) over the records the wave's unit mask names / leaves
-    static const int chain_mode = std::getenv("RM_CHAIN_MODE") ? std::atoi(std::getenv("RM_CHAIN_MODE")) : 2;
-    const bool chain = c->decoded.is_chain && chain_mode > 0;
-    // ... and whether the interpreter uses the wave-level culling mask (bit 3): 2 (default) yes, wherever the program has units
-    // Measured (profiles/r03_interpreter_loops.txt): over a chain the mask names the records to fetch at all -- 64-node scene at 4K
-    // 15.5 -> 5.3 ms, metric scene 1.23 -> 0.71 ms --, and over a tree the records that are left once operands without a needed
-    // leaf are dropped with their operators (map_scene_tree_masked); but it has a fixed price per evaluation (~250 cycles) that four
-    // leaves do not repay (8-node scene 0.44 -> 0.66 ms), and in the general loop, where a skipped record is still fetched and
-    // decoded, it loses (the blended scene 4.0 -> 4.4): chains and trees of a dozen leaves or more.
-    // bit 4: tree program (every record one of the eight fast shapes): the interpreter's one-dispatch-per-record loop.  RM_CHAIN_MODE=0
-    // keeps the general loop for everything (diagnostics)
-    const bool tree = c->decoded.is_tree && chain_mode > 0;
-    static const bool tree_masks = !(std::getenv("RM_TREE_MASKS") && std::atoi(std::getenv("RM_TREE_MASKS")) == 0);  // A/B
-    const bool tree_units = tree && !chain && !c->decoded.has_extensions && !c->decoded.tree.empty() && tree_masks && lds;
-    // ... and a chain of blends (the wider interpreter: SmoothUnion is an extension): the record machine over the units the mask names
-    static const uint32_t blend_leaves = std::getenv("RM_BLEND_PRUNE_LEAVES") ? (uint32_t)std::atoi(std::getenv("RM_BLEND_PRUNE_LEAVES")) : kBlendPruneLeaves;
-    const bool blend_units = c->decoded.unit_mode == RM_UNITS_BLEND && lds && !chain && chain_mode >= 2 && c->decoded.n_leaves >= blend_leaves;
-    const bool units = blend_units ||
-                       (c->decoded.unit_mode == RM_UNITS_LATTICE && (chain || tree_units) && chain_mode >= 2 && c->decoded.n_leaves >= kPruneLeaves);
-    L.n_tree = units && tree_units ? (uint32_t)c->decoded.tree.size() : 0u;
+    // Interpreter kernels: the record loop that runs the program (RM_INFO_INTERPRETER_LOOP) and whether it runs only the units the
+    // wave's culling mask names (RmLaunch::flags bit 3).  Measured (profiles/r03_interpreter_loops.txt): over a chain the mask names
+    // the records to fetch at all -- 64-node scene at 4K 15.5 -> 5.3 ms, metric scene 1.23 -> 0.71 ms --, and over a tree the records
+    // that are left once operands without a needed leaf are dropped with their operators (map_scene_tree_masked); but it has a fixed
+    // price per evaluation (~250 cycles) that four leaves do not repay (8-node scene 0.44 -> 0.66 ms), and in the general loop, where
+    // a skipped record is still fetched and decoded, it loses (the blended scene 4.0 -> 4.4): chains and trees of a dozen leaves or
+    // more, and chains of blends (the wider interpreter: SmoothUnion is an extension) of kBlendPruneLeaves leaves or more.  The
+    // scalar-cache variant (no LDS) has no unit records at hand.
+    const bool lattice_units = d.unit_mode == RM_UNITS_LATTICE && d.n_leaves >= kPruneLeaves;
+    const bool blend_units = d.unit_mode == RM_UNITS_BLEND && d.n_leaves >= kBlendPruneLeaves && lds;
+    bool units;
+    int loop;
+    if (d.is_chain) {                             // 1 the chain loop, 2 over the records the mask names
+        units = lattice_units;
+        loop = units && lds ? 2 : 1;
+    } else if (d.is_tree && !d.has_extensions) {  // 3 the tree loop, 4 over the tree records the mask leaves
+        const bool tree_units = lds && !d.tree.empty();
+        units = blend_units || (lattice_units && tree_units);
+        loop = units && tree_units ? 4 : 3;
+    } else {                                      // 0 the general record loop, 5 over the units of a blending chain
+        units = blend_units;
+        loop = units ? 5 : 0;
+    }
+    c->last_loop = loop;
+    L.n_tree = loop == 4 ? (uint32_t)d.tree.size() : 0u;
     if (L.n_tree != 0u) L.spill_depth += 1u;  // (map_scene_tree_masked spills at every push)
-    L.flags = (cull ? 1u : 0u) | (chain ? 4u : 0u) | (units ? 8u : 0u) | (tree ? 16u : 0u);
-    // (the scalar-cache variant has no unit records at hand)
-    c->last_loop = (L.flags & 4u) ? (((L.flags & 8u) && lds) ? 2 : 1) : (tree && !c->decoded.has_extensions) ? (L.n_tree != 0u ? 4 : 3) : blend_units ? 5 : 0;
+    // bit 2: chain program, bit 4: tree program (every record one of the eight fast shapes)
+    L.flags = (cull ? 1u : 0u) | (d.is_chain ? 4u : 0u) | (units ? 8u : 0u) | (d.is_tree ? 16u : 0u);
     // programs that blend: a ray the plain miss tests cannot clear (every bound is inflated by the blend radius) gets the
-    // program run on lower bounds of its leaves along the ray.  RM_BOUND_WALK=0 (diagnostics) keeps the plain tests only.
-    static const bool bound_walk_on = !(std::getenv("RM_BOUND_WALK") && std::atoi(std::getenv("RM_BOUND_WALK")) == 0);
-    if (cull && c->decoded.bound_walk && bound_walk_on) L.flags |= 32u;
-    // diagnostics: RM_PRE_NEED_MAX=n, the largest number of pixels of a clear tile the pre-pass finishes sample-parallel (default 24;
-    // 0: only tiles that need none, 64: always)
-    static const int pre_need_max = std::getenv("RM_PRE_NEED_MAX") ? std::atoi(std::getenv("RM_PRE_NEED_MAX")) : -1;
-    if (pre_need_max >= 0 && pre_need_max <= 64) L.flags |= (uint32_t)(pre_need_max + 1) << 8;
+    // program run on lower bounds of its leaves along the ray
+    if (cull && d.bound_walk) L.flags |= 32u;
     const uint32_t n_tiles = ((L.W + 7u) / 8u) * ((L.rows + 7u) / 8u);
     if (!cull) L.n_cone = L.n_slab = 0u;
     const size_t cull_bytes = (size_t)L.n_cone * 16u + (size_t)L.n_slab * 48u;
@@ -408,7 +406,7 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
     // the material evaluation of a tagged program borrows the spill area: (distance, index) pairs + saved positions
     // (a specialised kernel with the generated material walk keeps those pairs in registers too)
     if (L.n_mrec != 0u && !(spec_fn && c->spec && c->spec->material_walk))
-        L.spill_depth = std::max(L.spill_depth, 2u * c->decoded.mat_spill_depth + 3u * c->decoded.mat_xform_depth);
+        L.spill_depth = std::max(L.spill_depth, 2u * d.mat_spill_depth + 3u * d.mat_xform_depth);
     L.wave_dwords = rmk::V5_WAVE_DWORDS - ((spec_fn && c->spec && c->spec->taps4 && L.n_mrec == 0u) ? rmk::V5_TN_DWORDS : 0u);
     const size_t shmem = (size_t)(1024u + WPT * L.wave_dwords) * 4u +
                          (size_t)L.spill_depth * 64u * WPT * 4u + cull_bytes +
@@ -447,16 +445,15 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
     // ... but never more than 24 waves of ONE launch on a CU: where a seventh workgroup would fit (kernels of at most 72 vector
     // registers and 22.8 KB of LDS), a frame drawn alone is slower with it (a tile's four waves get a seventh of the CU instead of a
     // sixth, and the launch ends with its last tiles: -4 %), while the free slot lets the next frame's launch start on the same CU
-    // (frames in flight +6 %).  RM_WG_PER_CU_CAP (A/B): another cap, 0 none.
-    static const int per_cu_cap = std::getenv("RM_WG_PER_CU_CAP") ? std::atoi(std::getenv("RM_WG_PER_CU_CAP")) : 24 / WPT;
-    if (per_cu_cap > 0 && per_cu > (uint32_t)per_cu_cap) per_cu = (uint32_t)per_cu_cap;
+    // (frames in flight +6 %).
+    if (per_cu > 24u / WPT) per_cu = 24u / WPT;
     const uint32_t n_wg = std::min<uint32_t>(n_tiles, (uint32_t)std::max(1, c->cu_count) * per_cu);
     dim3 grid(n_wg, 1, n_frames);
     if (int rc = ensure_stats(c, L, (size_t)n_wg * n_frames * WPT)) return rc;
     if (int rc = time_begin(c, s)) return rc;
     // reference-only programs run the lean interpreter (chain and tree loops only); extension node types select the wider one,
-    // which has the general record loop (RM_CHAIN_MODE=0, diagnostics: everything takes that one)
-    const bool ext = c->decoded.has_extensions || !c->decoded.is_tree || chain_mode == 0;
+    // which has the general record loop
+    const bool ext = d.has_extensions || !d.is_tree;
     c->last_specialized = spec_fn != nullptr;
     // When a wave takes new rays.  With far-primitive pruning every evaluation tests which primitives are near for ANY lane:
     // lanes at unrelated march depths (a lane refilled the moment it retires) keep most of them near, while 64 rays started
@@ -464,17 +461,15 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
     // with them.  That is worth more than the lanes that idle until the last ray of the batch is done (metric frame 0.505 ->
     // 0.482 ms, 64-node scene +7 %; profiles/r02_refill_threshold_ab.txt); without pruning nothing is gained and the idle
     // lanes cost (8-node scene -17 %, the blended scene -2 %), so those kernels keep refilling lane by lane.
-    static const bool blend_in_step = !(std::getenv("RM_BLEND_IN_STEP") && std::atoi(std::getenv("RM_BLEND_IN_STEP")) == 0);  // A/B
-    const bool pruning = spec_fn ? (c->spec && (c->spec_pruned == rmjit::PRUNE_LATTICE || (c->spec_pruned == rmjit::PRUNE_BLEND && blend_in_step)))
-                                 : ((L.flags & 8u) != 0u && lds);
+    const bool pruning = spec_fn ? (c->spec && c->spec_pruned != rmjit::PRUNE_NONE) : units && lds;
     const uint32_t refill_auto = c->refill_min_v5 != 0u ? c->refill_min_v5 : (pruning ? 64u : 1u);
     if (spec_fn) {
         uint32_t n_tiles_arg = n_tiles, refill = refill_auto;
         void* args[] = {&L, &work, &n_tiles_arg, &refill};
         hipError_t e = hipModuleLaunchKernel(spec_fn, grid.x, grid.y, grid.z, 64u * WPT, 1, 1, (unsigned)shmem, s, args, nullptr);
         if (e != hipSuccess) return fail(c, RM_ERR_DEVICE, "launch of the specialised kernel failed: %s", hipGetErrorString(e));
-    } else if (lds && !ext) {  // one lean kernel per record loop (c->last_loop: 1 .. 4 here)
-        switch (c->last_loop) {
+    } else if (lds && !ext) {  // one lean kernel per record loop (1 .. 4 here)
+        switch (loop) {
         case 1: hipLaunchKernelGGL((rmk::rm_render_v5_lean<WPT, 1>), grid, dim3(64 * WPT), shmem, s, L, work, n_tiles, refill_auto); break;
         case 2: hipLaunchKernelGGL((rmk::rm_render_v5_lean<WPT, 2>), grid, dim3(64 * WPT), shmem, s, L, work, n_tiles, refill_auto); break;
         case 3: hipLaunchKernelGGL((rmk::rm_render_v5_lean<WPT, 3>), grid, dim3(64 * WPT), shmem, s, L, work, n_tiles, refill_auto); break;
@@ -939,16 +934,14 @@ RM_EXPORT int rm_gather_strips(rm_ctx* c, uint32_t W, uint32_t H, uint32_t strip
         return RM_OK;
     }
     // This GPU's strips are equally spaced in the frame: all the full ones go in ONE pitched copy (a row of the copy = one
-    // strip, destination pitch = `stride` strips), a ragged last strip in a second one.  RM_GATHER_PER_STRIP=1: one copy per
-    // strip (A/B).
-    static const bool per_strip = std::getenv("RM_GATHER_PER_STRIP") != nullptr;
+    // strip, destination pitch = `stride` strips), a ragged last strip in a second one.
     const size_t strip_bytes = row_bytes * strip_rows;
     uint32_t n_mine = 0, n_full = 0;
     for (uint32_t sidx = first; sidx < n_strips; sidx += stride) {
         n_mine++;
         if ((sidx + 1u) * strip_rows <= H) n_full++;
     }
-    if (!per_strip && n_full >= 2u) {
+    if (n_full >= 2u) {
         HIP_TRY(c, hipMemcpy2DAsync(dst + strip_bytes * first, strip_bytes * stride, src, strip_bytes, strip_bytes, n_full,
                                     hipMemcpyDeviceToHost, s));
         if (n_mine > n_full) {  // the frame's last strip is this GPU's and is shorter

@@ -111,7 +111,7 @@ struct RmLaunch {
     const float4* bounds;      // nullptr, or one world-space bounding sphere (centre, radius) per bounded primitive:
                                // programs with transforms (their miss tests use these instead of the parameters)
     uint32_t n_cull;           // entries of the miss-ray culling table (== n_rec when culling is on)
-    uint32_t flags;            // bit 0: miss-ray culling enabled; bit 2: chain program (interpreter kernels: map_scene_chain); bit 4: tree program (map_scene_tree); bit 3: ... with the wave's unit mask (masked chain loop, map_scene_tree_masked); bit 5: miss test on lower bounds (RmDecoded::bound_walk); bits 8-14: diagnostics (RM_PRE_NEED_MAX)
+    uint32_t flags;            // bit 0: miss-ray culling enabled; bit 2: chain program (interpreter kernels: map_scene_chain); bit 4: tree program (map_scene_tree); bit 3: ... with the wave's unit mask (masked chain loop, map_scene_tree_masked); bit 5: miss test on lower bounds (RmDecoded::bound_walk)
     uint32_t n_cone, n_slab;   // v5 miss-test tables: spheres / (boxes + cylinders) of the program
     float smooth_slack;        // sum of k/4 over SmoothUnion operators: how far they can lower the tree value
     float scene_scale;         // 1 + max |centre|_1 + |size|_1 over the primitives (RmDecoded::scene_scale)

@@ -122,7 +122,7 @@ inline std::string structure_key(const std::vector<RmRecord>& rec) {
 
 inline bool can_specialise(const std::vector<RmRecord>& rec) { return !rec.empty() && rec.size() <= kMaxRecords; }
 
-// A/B knobs of the generated code (environment, read when a structure is generated; defaults are the measured best)
+// Knobs of the generated code that tests and tools set (environment, read when a structure is generated)
 inline int jit_knob(const char* name, int dflt) {
     const char* v = std::getenv(name);
     return v ? std::atoi(v) : dflt;
@@ -158,10 +158,9 @@ inline bool generate_scene_code(const std::vector<RmRecord>& rec, int prune, int
     // A scheduling barrier after every few leaves: left alone the compiler hoists the parameter loads of the whole
     // program to the top of the straight-line code (88 VGPRs for 16 leaves, 120-139 for 32: 3 waves per SIMD);
     // with the barriers 61-62 VGPRs whatever the length.  64-node scene at 4K 636 -> 682 Mpx/s, metric frame +2 %.
-    const int sched_every = T == 1 ? (std::getenv("RM_JIT_SCHED_BARRIER") ? std::atoi(std::getenv("RM_JIT_SCHED_BARRIER")) : 4)
-                                   : (std::getenv("RM_JIT_SCHED_BARRIER_TAPS") ? std::atoi(std::getenv("RM_JIT_SCHED_BARRIER_TAPS")) : 2);
+    const int sched_every = T == 1 ? 4 : 2;
     const bool sub_tests = jit_knob("RM_JIT_SUB_TESTS", 1) != 0 && T == 1;  // the local test of subtracted leaves (below)
-    const bool fence = T == 4 && jit_knob("RM_JIT_GUARD_FENCE", 1) != 0;    // see guard_fence (rm_kernel_v5.h)
+    const bool fence = T == 4;                                              // see guard_fence (rm_kernel_v5.h)
     std::vector<RmUnit> units;
     if (prune == PRUNE_LATTICE && !rm_lattice_units(rec, &units)) return false;
     if (prune == PRUNE_BLEND && !rm_blend_units(rec, &units)) return false;
@@ -576,7 +575,7 @@ inline bool generate_material_walk(const std::vector<RmRecord>& mrec, std::strin
 inline const char* kernel_name() { return "rm_render_v5_spec"; }
 
 // mrec: the program decoded with its Material tags (empty for an untagged program): the kernel then gets the material
-// phase, with the walk generated as code when jit_knob RM_JIT_MATERIAL_WALK allows (default) and possible.
+// phase, with the walk generated as code whenever possible.
 // Whether a program of this STRUCTURE can meet the miss test on lower bounds (RmDecoded::bound_walk, which also looks at
 // the parameters): only then is the test compiled into its kernel -- it costs two or three registers the others need.
 inline bool structure_allows_bound_walk(const std::vector<RmRecord>& rec) {
@@ -604,13 +603,9 @@ inline bool generate_source(const std::vector<RmRecord>& rec, const std::vector<
     prune_kind &= PRUNE_KIND_MASK;
     std::string body, taps, walk;
     if (!generate_scene_code(rec, prune_kind, 1, &body)) return false;
-    const bool walk_spec = materials && jit_knob("RM_JIT_MATERIAL_WALK", 1) != 0 && mrec.size() <= kMaxRecords && generate_material_walk(mrec, &walk);
+    const bool walk_spec = materials && mrec.size() <= kMaxRecords && generate_material_walk(mrec, &walk);
     if (walk_generated) *walk_generated = walk_spec;
-    const char* taps_knob = std::getenv("RM_JIT_TAPS4");  // A/B: RM_JIT_TAPS4=0 keeps the taps on map_scene_spec
-    // (RM_JIT_TAPS4_SMOOTH=0: programs with a SmoothUnion keep the one-position taps)
-    bool taps4 = !(taps_knob && std::atoi(taps_knob) == 0);
-    if (taps4 && rm_has_blend(rec) && jit_knob("RM_JIT_TAPS4_SMOOTH", 1) == 0) taps4 = false;
-    taps4 = taps4 && generate_scene_code(rec, prune_kind, 4, &taps);
+    const bool taps4 = generate_scene_code(rec, prune_kind, 4, &taps);
     if (taps4_generated) *taps4_generated = taps4;
     std::string s;
     // hipRTC's built-in runtime header keeps the fixed-width integer types in a namespace of its own
@@ -624,13 +619,7 @@ inline bool generate_source(const std::vector<RmRecord>& rec, const std::vector<
     if (taps4) s += "#define RM_JIT_TAPS4 1\n";
     if (walk_spec) s += "#define RM_JIT_MATERIAL_WALK 1\n";
     if (structure_allows_bound_walk(rec)) s += "#define RM_JIT_BOUND_WALK 1\n";
-    if (const char* f = std::getenv("RM_JIT_UNIT_TEST")) s += "#define RM_UNIT_TEST_FORM " + std::to_string(std::atoi(f)) + "\n";  // A/B: unit_needed
     if (!with_stats) s += "#define RM_NO_WAVE_STATS 1\n";
-    if (const char* pr = std::getenv("RM_JIT_PRIO_LONG_RAYS")) {  // experiment knob
-        s += "#define RM_PRIO_LONG_RAYS ";
-        s += std::to_string(std::atoi(pr));
-        s += "u\n";
-    }
     s += "#include \"rm_kernel_v5.h\"\n";
     s += body;
     if (taps4) s += taps;
@@ -639,7 +628,6 @@ inline bool generate_source(const std::vector<RmRecord>& rec, const std::vector<
     // The kernel of a blending chain needs 86 vector registers (the mask's prefix scans on top of the four-tap function): 5 waves per
     // SIMD.  Capped at 80 it spills nine of them and is 5 % FASTER (config 3 at 4K: 3.44 -> 3.27 ms); every other kind of kernel that
     // sits above 80 loses by the same cap (balanced tree +7 %, materials +3 %, transforms +1 %: profiles/r03_refill_threshold_and_forced_occupancy.txt).
-    // RM_JIT_WAVES_PER_EU (A/B): n forces n waves per SIMD for every kernel, 0 none.
     int waves = prune_kind == PRUNE_BLEND ? 6 : 0;
     // A CHAIN ("a op b op c ...": every record after the first a leaf fused with its operator) without blends or materials and
     // with the four-tap function takes 73 vector registers -- one more than 7 waves per SIMD allow -- and 22.5 KB of LDS per
@@ -652,9 +640,7 @@ inline bool generate_source(const std::vector<RmRecord>& rec, const std::vector<
         chain = (kind == RM_KIND_SPHERE || kind == RM_KIND_BOX || kind == RM_KIND_CYLINDER || kind == RM_KIND_PLANE) && mode != RM_MODE_PUSH;
     }
     if (chain) waves = 7;
-    const bool knob = std::getenv("RM_JIT_WAVES_PER_EU") != nullptr;
-    if (knob) waves = std::atoi(std::getenv("RM_JIT_WAVES_PER_EU"));
-    const bool probe = capped_out && !knob && waves == 0 && prune_kind == PRUNE_LATTICE && !materials && jit_knob("RM_JIT_PROBE_CAP", 1) != 0;
+    const bool probe = capped_out && waves == 0 && prune_kind == PRUNE_LATTICE && !materials && jit_knob("RM_JIT_PROBE_CAP", 1) != 0;
     auto kernel_text = [&](int w) {
         std::string k;
         if (w > 0) {
@@ -687,13 +673,8 @@ inline uint64_t fnv1a(const char* p, size_t n, uint64_t h = 1469598103934665603u
     return h;
 }
 inline const char* const* compile_options(int* n) {
-    // the flags of the offline build (build.py HIP_FLAGS) that affect code generation.  RM_JIT_OPT_LEVEL (diagnostics, read once):
-    // another -O level
-    static const char* level = [] {
-        const char* v = std::getenv("RM_JIT_OPT_LEVEL");
-        return v && std::strlen(v) == 1 && std::strchr("0123s", v[0]) ? (v[0] == '0' ? "-O0" : v[0] == '1' ? "-O1" : v[0] == '2' ? "-O2" : v[0] == 's' ? "-Os" : "-O3") : "-O3";
-    }();
-    static const char* const opts[] = {"--offload-arch=gfx950", level, "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize"};
+    // the flags of the offline build (build.py HIP_FLAGS) that affect code generation
+    static const char* const opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize"};
     *n = (int)(sizeof opts / sizeof *opts);
     return opts;
 }
@@ -916,10 +897,8 @@ public:
     // the untagged program)
     std::shared_ptr<Entry> request(const std::vector<RmRecord>& rec, const std::vector<RmRecord>& mrec, int wpt, int prune) {
         // a tagged program's kernel also depends on where its tags sit (the material walk is generated from mrec), and on the
-        // A/B knobs of the generator as the environment holds them now (so that a process may compare two settings)
-        static const char* const knobs[] = {"RM_JIT_GUARD_FENCE", "RM_JIT_MATERIAL_WALK",
-                                            "RM_JIT_PRIO_LONG_RAYS", "RM_JIT_PRUNE_STATS", "RM_JIT_SCHED_BARRIER", "RM_JIT_SCHED_BARRIER_TAPS",
-                                            "RM_JIT_SUB_TESTS", "RM_JIT_TAPS4", "RM_JIT_TAPS4_SMOOTH", "RM_JIT_WAVES_PER_EU", "RM_JIT_UNIT_TEST", "RM_JIT_UNIT_GROUPS", "RM_JIT_PROBE_CAP"};
+        // knobs of the generator as the environment holds them now (so that a process may compare two settings)
+        static const char* const knobs[] = {"RM_JIT_PRUNE_STATS", "RM_JIT_SUB_TESTS", "RM_JIT_UNIT_GROUPS", "RM_JIT_PROBE_CAP"};
         std::string knob_key;
         for (const char* name : knobs)
             if (const char* v = std::getenv(name)) knob_key += std::string("|") + name + "=" + v;

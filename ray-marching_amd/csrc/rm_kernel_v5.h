@@ -327,16 +327,10 @@ __global__ __launch_bounds__(64) void rm_selftest_wave_kernel(const float* in, f
 // whole evaluation -- 30 more scalar registers spilled, which costs the vector register that decides between 6 and 5 waves
 // per SIMD.  With the asm each test is born where it is used: s_bitcmp1_b64 + s_cbranch_scc.
 RM_DEV bool unit_needed(unsigned long long need, uint32_t u) {
-#if defined(RM_UNIT_TEST_FORM) && RM_UNIT_TEST_FORM == 2  // A/B (RM_JIT_UNIT_TEST): the plain test
-    return ((need >> u) & 1ull) != 0ull;
-#elif defined(RM_UNIT_TEST_FORM) && RM_UNIT_TEST_FORM == 0  // A/B: the whole mask through the asm (s_mov_b64 + s_and_b32 + s_cmp_eq_u64)
-    asm volatile("" : "+s"(need));
-    return ((need >> u) & 1ull) != 0ull;
-#else  // the half of the mask that holds the bit: s_mov_b32 + s_bitcmp1_b32
+    // the half of the mask that holds the bit: s_mov_b32 + s_bitcmp1_b32
     uint32_t w = (uint32_t)(need >> (u & 32u));
     asm volatile("" : "+s"(w));
     return ((w >> (u & 31u)) & 1u) != 0u;
-#endif
 }
 
 // A group of units behind one test (rm_jit.h): the 32-bit word of the mask that holds unit u, through the asm once for the group;
@@ -1141,16 +1135,6 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
             n_iter++;
             n_live += (uint32_t)__popcll(live_m);
 #endif
-#ifdef RM_PRIO_LONG_RAYS
-            // A ray that needs hundreds of steps is a serial chain of that many evaluations; at full load a wave gets a
-            // fifth of its SIMD's issue slots, so such a ray started late IS the kernel's tail.  Waves that carry one get
-            // issue priority: the chain runs at the lone-wave rate and the short rays fill in behind it.
-            if (!tapping_i) {
-                const uint32_t old_rays = (uint32_t)__popcll(__ballot(is_live && itr >= (RM_PRIO_LONG_RAYS << 10)));
-                if (old_rays != 0u) __builtin_amdgcn_s_setprio(3);
-                else __builtin_amdgcn_s_setprio(0);
-            }
-#endif
             const float sd = eval_scene(ex, ey, ez, thr, is_live, live_m);
 
             if (tapping_i) {  // n (+)= k_t * f; products with +-1 are exact (wgsl:138-143)
@@ -1284,11 +1268,8 @@ __global__ __launch_bounds__(64 * WPT) void rm_render_v5(RmLaunch L, V5Work work
 // The interpreter for reference-only programs staged in LDS -- north_star's design, and what runs while a structure compiles --
 // with its vector registers capped at 80 (6 waves per SIMD, which is also what its LDS footprint allows): left alone the
 // allocator takes 81 and a sixth of the occupancy (march kernel of the metric frame 0.83 -> 0.87 ms).
-#ifndef RM_LEAN_WAVES
-#define RM_LEAN_WAVES 6
-#endif
 template <int WPT, int LOOP>
-__global__ __launch_bounds__(64 * WPT) __attribute__((amdgpu_waves_per_eu(RM_LEAN_WAVES, 8)))
+__global__ __launch_bounds__(64 * WPT) __attribute__((amdgpu_waves_per_eu(6, 8)))
 void rm_render_v5_lean(RmLaunch L, V5Work work, uint32_t n_tiles, uint32_t refill_min) {
     rm_render_v5_body<ProgLds, true, WPT, false, false, false, LOOP>(L, work, n_tiles, refill_min);
 }
@@ -1565,8 +1546,7 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
     float tr = 0.0f, tg = 0.0f, tb = 0.0f;
     const unsigned long long need = __ballot(!known);  // pixels whose samples have to be looked at one by one
     const uint32_t n_need = (uint32_t)__popcll(need);
-    const uint32_t need_max = (L.flags >> 8) & 0x7Fu ? ((L.flags >> 8) & 0x7Fu) - 1u : 24u;  // (diagnostics: RM_PRE_NEED_MAX)
-    if (n_need <= need_max) {
+    if (n_need <= 24u) {
         // Few such pixels (a checker edge crossing the tile): their samples -- 16 n_need of them -- are spread over the 64
         // lanes, 64 per pass instead of one sample of all 64 pixels per pass; each sample's colour code goes to LDS and the
         // pixel's lane then adds its sixteen gamma values in the reference order.  Same functions, same sums.
