@@ -123,6 +123,16 @@ pub const RM_JIT_PRUNE: c_int = 0x100;
 /// `RM_STREAM_OWN`: pass as `stream` of a device-destination draw to use the context's own stream.
 pub const RM_STREAM_OWN: *mut c_void = usize::MAX as *mut c_void;
 
+// Scene queries (rm_query_points / rm_cast_rays / rm_camera_rays).
+/// `RM_NO_ID`: no primitive (an empty program, or a ray that hit no surface).
+pub const RM_NO_ID: u32 = 0xFFFF_FFFF;
+// enum rm_hit
+pub const RM_HIT_NONE: c_int = 0;
+pub const RM_HIT_SURFACE: c_int = 1;
+pub const RM_HIT_FLOOR: c_int = 2;
+// enum rm_sample
+pub const RM_SAMPLE_CENTER: c_int = 16;
+
 // Opcodes of the node types the reference only names in comments (builder.rs:8,14,16-23) and that the device
 // path implements as extensions: a CSGCommandType that gains these variants serialises them unchanged.
 //   Plane = 2, Intersection = 102, TranslationPush = 200, TranslationPop, RotationPush, RotationPop, ScalePush, ScalePop
@@ -153,6 +163,12 @@ extern "C" {
     pub fn rm_host_unregister(ptr: *mut c_void) -> c_int;
     pub fn rm_draw_batch(ctx: *mut rm_ctx, frames: *const rm_uniforms, n_frames: u32, w: u32, h: u32, out_rgba: *mut f32,
                          out_is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_query_points(ctx: *mut rm_ctx, n: u32, xyz: *const f32, out_dist: *mut f32, out_normal: *mut f32, out_ids: *mut u32,
+                           is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_cast_rays(ctx: *mut rm_ctx, n: u32, rays: *const f32, out_hit: *mut f32, out_ids: *mut u32, out_rgb: *mut f32,
+                        is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_camera_rays(ctx: *mut rm_ctx, w_frame: u32, h_frame: u32, x0: u32, y0: u32, w: u32, h: u32, sample: u32,
+                          out_rays: *mut f32, is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_sync(ctx: *mut rm_ctx) -> c_int;
     pub fn rm_sync_context(ctx: *mut rm_ctx) -> c_int;
     pub fn rm_set_option(ctx: *mut rm_ctx, key: c_int, value: i64) -> c_int;
@@ -254,6 +270,73 @@ impl RayMarchingResources {
         })?;
         Ok(rows)
     }
+
+    /// Scene query at `xyz.len() / 3` points (host memory): signed distance (`out_dist`, one per point), shading normal
+    /// (`out_normal`, three per point) and (leaf, material) (`out_ids`, two per point).  `None` skips that output.
+    pub fn query_points(&self, xyz: &[f32], out_dist: Option<&mut [f32]>, out_normal: Option<&mut [f32]>,
+                        out_ids: Option<&mut [u32]>) -> Result<(), RmError> {
+        assert!(xyz.len() % 3 == 0, "query_points: xyz holds {} floats, not a multiple of 3", xyz.len());
+        let n = xyz.len() / 3;
+        assert!(n <= u32::MAX as usize);
+        assert!(out_dist.as_ref().map_or(true, |s| s.len() >= n), "query_points: out_dist is shorter than {} points", n);
+        assert!(out_normal.as_ref().map_or(true, |s| s.len() >= 3 * n), "query_points: out_normal is shorter than {} points", n);
+        assert!(out_ids.as_ref().map_or(true, |s| s.len() >= 2 * n), "query_points: out_ids is shorter than {} points", n);
+        let dist = out_dist.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let normal = out_normal.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let ids = out_ids.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        self.check(unsafe { rm_query_points(self.ctx, n as u32, xyz.as_ptr(), dist, normal, ids, 0, std::ptr::null_mut()) })
+    }
+
+    /// Casts `rays.len() / 6` rays (ox, oy, oz, dx, dy, dz; host memory) as the draw marches them: hit records (`out_hit`,
+    /// eight per ray: t, position, normal, diffuse), (kind, steps, leaf, material) (`out_ids`, four per ray) and the colour
+    /// (`out_rgb`, three per ray).  `None` skips that output.
+    pub fn cast_rays(&self, rays: &[f32], out_hit: Option<&mut [f32]>, out_ids: Option<&mut [u32]>,
+                     out_rgb: Option<&mut [f32]>) -> Result<(), RmError> {
+        assert!(rays.len() % 6 == 0, "cast_rays: rays holds {} floats, not a multiple of 6", rays.len());
+        let n = rays.len() / 6;
+        assert!(n <= u32::MAX as usize);
+        assert!(out_hit.as_ref().map_or(true, |s| s.len() >= 8 * n), "cast_rays: out_hit is shorter than {} rays", n);
+        assert!(out_ids.as_ref().map_or(true, |s| s.len() >= 4 * n), "cast_rays: out_ids is shorter than {} rays", n);
+        assert!(out_rgb.as_ref().map_or(true, |s| s.len() >= 3 * n), "cast_rays: out_rgb is shorter than {} rays", n);
+        let hit = out_hit.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let ids = out_ids.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let rgb = out_rgb.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        self.check(unsafe { rm_cast_rays(self.ctx, n as u32, rays.as_ptr(), hit, ids, rgb, 0, std::ptr::null_mut()) })
+    }
+
+    /// The rays the draw marches for AA sample `sample` (0..15, or `RM_SAMPLE_CENTER`) of the `w` x `h` pixels at (`x0`,
+    /// `y0`) of a `width` x `height` frame, row-major, six floats each.
+    pub fn camera_rays(&self, width: u32, height: u32, x0: u32, y0: u32, w: u32, h: u32, sample: u32,
+                       out_rays: &mut [f32]) -> Result<(), RmError> {
+        assert!(out_rays.len() >= (w as usize) * (h as usize) * 6, "camera_rays: out_rays is shorter than {} rays", w as usize * h as usize);
+        self.check(unsafe { rm_camera_rays(self.ctx, width, height, x0, y0, w, h, sample, out_rays.as_mut_ptr(), 0, std::ptr::null_mut()) })
+    }
+
+    /// What lies under pixel (`x`, `y`) of a `width` x `height` frame: the ray through its centre, cast -- e.g. the node to
+    /// select when the viewport is clicked (`hit.leaf` is the `cmd_count` the builder had before it pushed that primitive).
+    pub fn pick(&self, width: u32, height: u32, x: u32, y: u32) -> Result<Hit, RmError> {
+        let mut ray = [0.0f32; 6];
+        self.camera_rays(width, height, x, y, 1, 1, RM_SAMPLE_CENTER as u32, &mut ray)?;
+        let (mut rec, mut ids, mut rgb) = ([0.0f32; 8], [0u32; 4], [0.0f32; 3]);
+        self.cast_rays(&ray, Some(&mut rec), Some(&mut ids), Some(&mut rgb))?;
+        Ok(Hit { kind: ids[0] as c_int, steps: ids[1], leaf: ids[2], material: ids[3], t: rec[0], position: [rec[1], rec[2], rec[3]],
+                 normal: [rec[4], rec[5], rec[6]], diffuse: rec[7], rgb })
+    }
+}
+
+/// One cast ray (`RayMarchingResources::pick`): `kind` is `RM_HIT_NONE`, `RM_HIT_SURFACE` or `RM_HIT_FLOOR`; `leaf` and
+/// `material` are `RM_NO_ID` unless a surface was hit.
+#[derive(Debug, Clone, Copy, PartialEq)]
+pub struct Hit {
+    pub kind: c_int,
+    pub steps: u32,
+    pub leaf: u32,
+    pub material: u32,
+    pub t: f32,
+    pub position: [f32; 3],
+    pub normal: [f32; 3],
+    pub diffuse: f32,
+    pub rgb: [f32; 3],
 }
 
 /// Output rows of strips `first`, `first + stride`, ... (`strip_rows` rows each; the frame's last strip may be ragged) of an

@@ -97,7 +97,7 @@ enum rm_status {
     RM_ERR_RANGE = -8,           /* row band / image size out of range, or max_iter > 65536 */
     RM_ERR_DEVICE = -9,          /* a HIP call failed; see rm_last_error */
     RM_ERR_NO_DEVICE = -10,      /* no usable GPU */
-    RM_ERR_ARG = -11,            /* invalid enum / option value */
+    RM_ERR_ARG = -11,            /* invalid enum / option value, or a misaligned device array of a scene query */
     RM_ERR_TRANSFORM = -12,      /* transform push / pop (extension opcodes 200-205) not nested properly, deeper than 8,
                                     or not around exactly one value */
     RM_ERR_MATERIAL = -13        /* a Material tag (extension opcode 300) names an index >= 256, or (at draw time) one
@@ -267,6 +267,42 @@ int rm_host_unregister(void* ptr);
  * written at out_rgba + f*W*H*4. */
 int rm_draw_batch(rm_ctx* ctx, const rm_uniforms* frames, uint32_t n_frames, uint32_t W, uint32_t H,
                   float* out_rgba, int out_is_device, void* stream);
+
+/* Scene queries (extension): what the scene the next rm_draw would render says at a point or along a ray -- the command
+ * buffer (validated like a draw's program), the limits, the uniforms and the material table as they are now.  Every float
+ * is bit-identical to the oracle; queries never touch the draw state (RM_OPT_TIMING, RM_INFO_*, the
+ * specialised kernel, the tile buffers).
+ *   is_device = 0: every array is host memory; the call is synchronous on the context's own stream.
+ *   is_device = 1: every array is device memory on the context's GPU; the call is asynchronous on `stream` (as rm_draw's,
+ *                  RM_STREAM_OWN included) and ordered with the context's earlier draws and uploads.  Device arrays are
+ *                  accessed a record at a time: float arrays need 4-byte alignment, out_ids of rm_query_points 8-byte,
+ *                  out_hit and out_ids of rm_cast_rays 16-byte (what any allocator returns); RM_ERR_ARG otherwise.
+ * Any output may be NULL (that work is skipped); RM_ERR_NULL when all are, or when an input is NULL with n > 0.  n = 0 (or
+ * w*h = 0) writes nothing.  Errors: the draw's status for an invalid program, RM_ERR_RANGE for max_iter > 65536, and
+ * RM_ERR_MATERIAL for a tag beyond the material table when colours are requested.
+ * leaf = command index of the primitive whose value a result carries: its 0-based position in the command stream, counting
+ * every command (operators, transform pushes / pops, Material tags).  Union / SmoothUnion take the right operand's leaf iff
+ * b < a, Subtraction iff -b > a, Intersection iff b > a; ties and NaN keep the left operand's; transforms and tags keep it. */
+#define RM_NO_ID 0xFFFFFFFFu /* no primitive (empty program, or a ray that hit no surface) */
+enum rm_hit { RM_HIT_NONE = 0, RM_HIT_SURFACE = 1, RM_HIT_FLOOR = 2 };
+enum rm_sample { RM_SAMPLE_CENTER = 16 }; /* rm_camera_rays: the ray through the pixel centre; 0..15 are fs_main's AA samples */
+/* Points.  xyz: n x 3.  out_dist: n, map_scene(p) (an empty program: limits.max_dist).  out_normal: n x 3, calculate_normal(p)
+ * (wgsl:135-144) normalised as the shading does (NaN where the tap sum is zero).  out_ids: n x 2 (leaf, material); an empty
+ * program gives (RM_NO_ID, 0). */
+int rm_query_points(rm_ctx* ctx, uint32_t n, const float* xyz, float* out_dist, float* out_normal, uint32_t* out_ids,
+                    int is_device, void* stream);
+/* Rays (ray_march, wgsl:87-131; the direction is used as given).  rays: n x 6 (ox, oy, oz, dx, dy, dz).
+ * out_hit: n x 8 (t, x, y, z, nx, ny, nz, diffuse): surface -- the march distance and position of the hit step, the shading
+ * normal, max(0.02, n.l); floor -- floor_dist, (x, -1.5, z), (0, 1, 0), 0; none -- +inf and zeros.
+ * out_ids: n x 4 (kind RM_HIT_*, steps = map_scene evaluations of the march loop, leaf, material; RM_NO_ID unless a surface).
+ * out_rgb: n x 3, the colour ray_march returns (with the context's material table). */
+int rm_cast_rays(rm_ctx* ctx, uint32_t n, const float* rays, float* out_hit, uint32_t* out_ids, float* out_rgb,
+                 int is_device, void* stream);
+/* The rays rm_draw marches for AA sample `sample` (0..15: (i, j) = (sample / 4, sample % 4), wgsl:44-53; or
+ * RM_SAMPLE_CENTER) of the pixels of the w x h block at (x0, y0) of a W x H frame, row-major.  out_rays: w*h x 6, as
+ * rm_cast_rays reads them. */
+int rm_camera_rays(rm_ctx* ctx, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                   uint32_t sample, float* out_rays, int is_device, void* stream);
 
 /* Waits for all work on the context's GPU (hipDeviceSynchronize). */
 int rm_sync(rm_ctx* ctx);

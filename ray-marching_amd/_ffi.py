@@ -41,6 +41,10 @@ RM_FORMAT_RGBA32F, RM_FORMAT_RGBA8_UNORM, RM_FORMAT_BGRA8_UNORM = 0, 1, 2
 RM_INFO_KERNEL_MS, RM_INFO_PROGRAM_COMMANDS, RM_INFO_PROGRAM_WORDS, RM_INFO_PROGRAM_DEPTH = 0, 1, 2, 3
 RM_INFO_DEVICE, RM_INFO_CU_COUNT, RM_INFO_SPECIALIZED, RM_INFO_JIT_STATE, RM_INFO_JIT_COMPILE_MS = 4, 5, 6, 7, 8
 RM_INFO_PRUNED, RM_INFO_INTERPRETER_LOOP, RM_INFO_JIT_FROM_CACHE = 9, 10, 11
+# scene queries (rm_query_points / rm_cast_rays / rm_camera_rays)
+RM_NO_ID = 0xFFFFFFFF
+RM_HIT_NONE, RM_HIT_SURFACE, RM_HIT_FLOOR = 0, 1, 2
+RM_SAMPLE_CENTER = 16
 
 _hip = None
 _host = None
@@ -121,6 +125,12 @@ def hip_lib():
         L.rm_selftest_wave.restype = C.c_int
         L.rm_read_wave_stats.argtypes = [vp, vp, u64, C.POINTER(u64)]
         L.rm_read_wave_stats.restype = C.c_int
+        L.rm_query_points.argtypes = [vp, u32, vp, vp, vp, vp, C.c_int, vp]
+        L.rm_query_points.restype = C.c_int
+        L.rm_cast_rays.argtypes = [vp, u32, vp, vp, vp, vp, C.c_int, vp]
+        L.rm_cast_rays.restype = C.c_int
+        L.rm_camera_rays.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, vp, C.c_int, vp]
+        L.rm_camera_rays.restype = C.c_int
         sz = C.c_size_t
         L.rm_jit_source.argtypes = [u32, C.POINTER(u32), u32, C.c_int, C.c_char_p, sz, C.POINTER(sz)]
         L.rm_jit_source.restype = C.c_int

@@ -19,6 +19,7 @@
 #include "rm_kernels.h"
 #include "rm_interp.h"
 #include "rm_kernel_v5.h"
+#include "rm_query.h"
 
 #define RM_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -70,6 +71,17 @@ struct rm_ctx {
     std::vector<float4> materials{make_float4(0.4f, 0.7f, 0.1f, 0.0f)};  // wgsl:105
     float4* d_materials = nullptr;  // RM_MAX_MATERIALS entries
     bool materials_dirty = true;
+    // scene queries (rm_query.h): the query program (RmDecoded::qrec), uploaded by the first query after a program change
+    // (prog_gen it belongs to in qprog_gen: draws never upload it), and the staging buffers of host-memory queries (never
+    // the draws' scratch)
+    RmRecord* d_qprog = nullptr;
+    size_t d_qprog_cap = 0;
+    uint64_t qprog_gen = ~0ull;
+    void* d_qin = nullptr;
+    size_t d_qin_bytes = 0;
+    void* d_qout = nullptr;
+    size_t d_qout_bytes = 0;
+    size_t max_lds = 0;  // LDS a workgroup may allocate on this device
     // scratch for host-destination draws and batch uniforms
     float* d_out = nullptr;
     size_t d_out_bytes = 0;
@@ -695,6 +707,7 @@ RM_EXPORT int rm_create(int device, rm_ctx** out) {
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
     if (e == hipSuccess) {
         c->cu_count = prop.multiProcessorCount;
+        c->max_lds = prop.sharedMemPerBlock;
         e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     }
     if (e == hipSuccess) e = hipEventCreate(&c->ev0);
@@ -724,6 +737,9 @@ RM_EXPORT void rm_destroy(rm_ctx* c) {
     if (c->d_bounds) (void)hipFree(c->d_bounds);
     if (c->d_mprog) (void)hipFree(c->d_mprog);
     if (c->d_materials) (void)hipFree(c->d_materials);
+    if (c->d_qprog) (void)hipFree(c->d_qprog);
+    if (c->d_qin) (void)hipFree(c->d_qin);
+    if (c->d_qout) (void)hipFree(c->d_qout);
     for (auto& st : c->staging) {
         if (st.host) (void)hipHostFree(st.host);
         if (st.done) (void)hipEventDestroy(st.done);
@@ -1007,6 +1023,215 @@ RM_EXPORT int rm_draw_batch(rm_ctx* c, const rm_uniforms* frames, uint32_t n_fra
     rc = launch(c, c->d_frames, n_frames, W, H, 0, H, c->d_out, s);
     if (rc != RM_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(out_rgba, c->d_out, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+// ---- scene queries (rm_query.h) -----------------------------------------------------------------------------------------
+namespace {
+
+// The record loop the interpreter draw runs the current program with (launch_v5_w without wave-level culling).
+int query_loop(const RmDecoded& d) {
+    if (d.is_chain) return rmk::Q_LOOP_CHAIN;
+    if (d.is_tree && !d.has_extensions) return rmk::Q_LOOP_TREE;
+    return rmk::Q_LOOP_GENERAL;
+}
+
+int grow_bytes(rm_ctx* c, void** buf, size_t* cap, size_t need) {
+    if (need <= *cap) return RM_OK;
+    if (*buf) (void)hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    HIP_TRY(c, hipMalloc(buf, need));
+    *cap = need;
+    return RM_OK;
+}
+size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
+// Device arrays of a query are read and written with vector accesses of their element size: floats 4 B, the (leaf, material)
+// pairs of rm_query_points 8 B, the hit records and id quadruples of rm_cast_rays 16 B.  A pointer off that alignment is refused.
+bool misaligned(const void* p, uintptr_t align) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & (align - 1u)) != 0u; }
+
+// What every query of the program does first, on stream `s`, exactly as a draw would: ordering with the context's earlier
+// work, the program (decoded, validated and uploaded by ensure_program), the limits and -- for colours of a tagged program --
+// the material table.  Fills the launch and the dynamic LDS of one 256-thread workgroup: four wave columns of `slots` dwords
+// per lane, the larger of what the distance loop (value stack, then 3 floats per transform level) and the leaf walk
+// ([depth] distances, [depth] (leaf, material) pairs, 3 floats per transform level) need for THIS program.
+int query_begin(rm_ctx* c, hipStream_t s, bool walk, bool rgb, rmk::QueryLaunch* Q, int* loop, size_t* shmem) {
+    order_with_previous(c, s);
+    int rc = ensure_program(c, s);
+    if (rc == RM_OK && rgb) rc = ensure_materials(c, s);
+    if (rc == RM_OK) rc = check_limits(c);
+    if (rc != RM_OK) return rc;
+    const RmDecoded& d = c->decoded;
+    // the query program of this decoding, stream-ordered like the draws' images (a query still queued on an earlier stream
+    // keeps the previous one: order_with_previous above made this stream wait for it)
+    if (c->qprog_gen != c->prog_gen) {
+        if (d.qrec.size() > c->d_qprog_cap) {
+            if (c->d_qprog) (void)hipFree(c->d_qprog);
+            c->d_qprog = nullptr;
+            c->d_qprog_cap = 0;
+            const size_t cap = std::max<size_t>(64, d.qrec.size() * 2);
+            HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_qprog), cap * sizeof(RmRecord)));
+            c->d_qprog_cap = cap;
+        }
+        if (!d.qrec.empty())
+            if (int urc = upload(c, c->d_qprog, d.qrec.data(), d.qrec.size() * sizeof(RmRecord), s)) return urc;
+        c->qprog_gen = c->prog_gen;
+    }
+    *loop = query_loop(d);
+    uint32_t slots = *loop == rmk::Q_LOOP_CHAIN ? 0u : *loop == rmk::Q_LOOP_TREE ? d.spill_depth : d.spill_depth + 3u * d.xform_depth;
+    if (walk) slots = std::max(slots, 2u * d.q_spill_depth + 3u * d.q_xform_depth);
+    *shmem = (size_t)slots * 64u * 4u * 4u;
+    const size_t cap = std::max<size_t>(c->max_lds, 64u * 1024u);
+    if (*shmem > cap) return fail(c, RM_ERR_TOO_LARGE, "the query needs %zu bytes of LDS per workgroup", *shmem);
+    Q->prog = c->d_prog;
+    Q->qprog = c->d_qprog;
+    Q->n_rec = (uint32_t)d.rec.size();
+    Q->n_qrec = (uint32_t)d.qrec.size();
+    Q->value_spill_depth = d.spill_depth;
+    Q->q_value_depth = d.q_spill_depth;
+    Q->slots = slots;
+    Q->tagged = d.has_materials ? 1u : 0u;
+    Q->min_dist = c->limits.min_dist;
+    Q->max_dist = c->limits.max_dist;
+    Q->max_iter = c->limits.max_iter;
+    Q->materials = rgb && d.has_materials ? c->d_materials : nullptr;
+    return RM_OK;
+}
+
+template <class K, class... Args>
+int query_launch(rm_ctx* c, K kernel, size_t count, size_t shmem, hipStream_t s, Args... args) {
+    if (shmem > 64u * 1024u)  // (deep programs: gfx950 gives a workgroup up to 160 KB)
+        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)((count + 255u) / 256u)), dim3(256), shmem, s, args...);
+    HIP_TRY(c, hipGetLastError());
+    return RM_OK;
+}
+
+using PointsFn = void (*)(rmk::QueryLaunch, uint32_t, const float*, float*, float*, uint32_t*);
+template <int LOOP>
+PointsFn points_kernel(bool dist, bool normal, bool ids) {
+    switch ((dist ? 1 : 0) | (normal ? 2 : 0) | (ids ? 4 : 0)) {
+    case 1: return rmk::rm_query_points_kernel<LOOP, true, false, false>;
+    case 2: return rmk::rm_query_points_kernel<LOOP, false, true, false>;
+    case 3: return rmk::rm_query_points_kernel<LOOP, true, true, false>;
+    case 4: return rmk::rm_query_points_kernel<LOOP, false, false, true>;
+    case 5: return rmk::rm_query_points_kernel<LOOP, true, false, true>;
+    case 6: return rmk::rm_query_points_kernel<LOOP, false, true, true>;
+    default: return rmk::rm_query_points_kernel<LOOP, true, true, true>;
+    }
+}
+using RaysFn = void (*)(rmk::QueryLaunch, uint32_t, const float*, float*, uint32_t*, float*);
+template <int LOOP>
+RaysFn rays_kernel(bool taps, bool walk) {
+    if (!walk) return rmk::rm_cast_rays_kernel<LOOP, true, false>;
+    return taps ? rmk::rm_cast_rays_kernel<LOOP, true, true> : rmk::rm_cast_rays_kernel<LOOP, false, true>;
+}
+
+}  // namespace
+
+RM_EXPORT int rm_query_points(rm_ctx* c, uint32_t n, const float* xyz, float* out_dist, float* out_normal, uint32_t* out_ids,
+                              int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_dist && !out_normal && !out_ids) return fail(c, RM_ERR_NULL, "rm_query_points: every output is NULL");
+    if (n == 0u) return RM_OK;
+    if (!xyz) return fail(c, RM_ERR_NULL, "rm_query_points: xyz is NULL");
+    if (is_device && (misaligned(xyz, 4) || misaligned(out_dist, 4) || misaligned(out_normal, 4) || misaligned(out_ids, 8)))
+        return fail(c, RM_ERR_ARG, "rm_query_points: device arrays need 4-byte alignment (out_ids: 8-byte)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    int rc = query_begin(c, s, out_ids != nullptr, false, &Q, &loop, &shmem);
+    if (rc != RM_OK) return rc;
+    const PointsFn k = loop == rmk::Q_LOOP_CHAIN ? points_kernel<rmk::Q_LOOP_CHAIN>(out_dist, out_normal, out_ids)
+                     : loop == rmk::Q_LOOP_TREE ? points_kernel<rmk::Q_LOOP_TREE>(out_dist, out_normal, out_ids)
+                                                : points_kernel<rmk::Q_LOOP_GENERAL>(out_dist, out_normal, out_ids);
+    if (is_device) return query_launch(c, k, n, shmem, s, Q, n, xyz, out_dist, out_normal, out_ids);
+    // host memory: staged through the context's query buffers, synchronously on its own stream
+    const size_t in_b = (size_t)n * 12u, dist_b = out_dist ? align16((size_t)n * 4u) : 0u, nrm_b = out_normal ? align16((size_t)n * 12u) : 0u,
+                 ids_b = out_ids ? (size_t)n * 8u : 0u;
+    if ((rc = grow_bytes(c, &c->d_qin, &c->d_qin_bytes, in_b)) != RM_OK) return rc;
+    if ((rc = grow_bytes(c, &c->d_qout, &c->d_qout_bytes, dist_b + nrm_b + ids_b)) != RM_OK) return rc;
+    char* o = static_cast<char*>(c->d_qout);
+    float* d_dist = out_dist ? reinterpret_cast<float*>(o) : nullptr;
+    float* d_nrm = out_normal ? reinterpret_cast<float*>(o + dist_b) : nullptr;
+    uint32_t* d_ids = out_ids ? reinterpret_cast<uint32_t*>(o + dist_b + nrm_b) : nullptr;
+    HIP_TRY(c, hipMemcpyAsync(c->d_qin, xyz, in_b, hipMemcpyHostToDevice, s));
+    if ((rc = query_launch(c, k, n, shmem, s, Q, n, static_cast<const float*>(c->d_qin), d_dist, d_nrm, d_ids)) != RM_OK) return rc;
+    if (out_dist) HIP_TRY(c, hipMemcpyAsync(out_dist, d_dist, (size_t)n * 4u, hipMemcpyDeviceToHost, s));
+    if (out_normal) HIP_TRY(c, hipMemcpyAsync(out_normal, d_nrm, (size_t)n * 12u, hipMemcpyDeviceToHost, s));
+    if (out_ids) HIP_TRY(c, hipMemcpyAsync(out_ids, d_ids, ids_b, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+RM_EXPORT int rm_cast_rays(rm_ctx* c, uint32_t n, const float* rays, float* out_hit, uint32_t* out_ids, float* out_rgb,
+                           int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_hit && !out_ids && !out_rgb) return fail(c, RM_ERR_NULL, "rm_cast_rays: every output is NULL");
+    if (n == 0u) return RM_OK;
+    if (!rays) return fail(c, RM_ERR_NULL, "rm_cast_rays: rays is NULL");
+    if (is_device && (misaligned(rays, 4) || misaligned(out_hit, 16) || misaligned(out_ids, 16) || misaligned(out_rgb, 4)))
+        return fail(c, RM_ERR_ARG, "rm_cast_rays: device arrays need 4-byte alignment (out_hit, out_ids: 16-byte)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    // the leaf walk runs for the ids, and for the colour of a tagged program (its albedo)
+    const bool taps = out_hit || out_rgb;
+    bool walk = out_ids != nullptr;
+    if (out_rgb && !walk) {
+        order_with_previous(c, s);
+        int rc = ensure_program(c, s);  // (query_begin repeats both at no cost)
+        if (rc != RM_OK) return rc;
+        walk = c->decoded.has_materials;
+    }
+    int rc = query_begin(c, s, walk, out_rgb != nullptr, &Q, &loop, &shmem);
+    if (rc != RM_OK) return rc;
+    const RaysFn k = loop == rmk::Q_LOOP_CHAIN ? rays_kernel<rmk::Q_LOOP_CHAIN>(taps, walk)
+                   : loop == rmk::Q_LOOP_TREE ? rays_kernel<rmk::Q_LOOP_TREE>(taps, walk)
+                                              : rays_kernel<rmk::Q_LOOP_GENERAL>(taps, walk);
+    if (is_device) return query_launch(c, k, n, shmem, s, Q, n, rays, out_hit, out_ids, out_rgb);
+    const size_t in_b = (size_t)n * 24u, hit_b = out_hit ? (size_t)n * 32u : 0u, ids_b = out_ids ? (size_t)n * 16u : 0u,
+                 rgb_b = out_rgb ? (size_t)n * 12u : 0u;
+    if ((rc = grow_bytes(c, &c->d_qin, &c->d_qin_bytes, in_b)) != RM_OK) return rc;
+    if ((rc = grow_bytes(c, &c->d_qout, &c->d_qout_bytes, hit_b + ids_b + rgb_b)) != RM_OK) return rc;
+    char* o = static_cast<char*>(c->d_qout);
+    float* d_hit = out_hit ? reinterpret_cast<float*>(o) : nullptr;
+    uint32_t* d_ids = out_ids ? reinterpret_cast<uint32_t*>(o + hit_b) : nullptr;
+    float* d_rgb = out_rgb ? reinterpret_cast<float*>(o + hit_b + ids_b) : nullptr;
+    HIP_TRY(c, hipMemcpyAsync(c->d_qin, rays, in_b, hipMemcpyHostToDevice, s));
+    if ((rc = query_launch(c, k, n, shmem, s, Q, n, static_cast<const float*>(c->d_qin), d_hit, d_ids, d_rgb)) != RM_OK) return rc;
+    if (out_hit) HIP_TRY(c, hipMemcpyAsync(out_hit, d_hit, hit_b, hipMemcpyDeviceToHost, s));
+    if (out_ids) HIP_TRY(c, hipMemcpyAsync(out_ids, d_ids, ids_b, hipMemcpyDeviceToHost, s));
+    if (out_rgb) HIP_TRY(c, hipMemcpyAsync(out_rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+RM_EXPORT int rm_camera_rays(rm_ctx* c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                             uint32_t sample, float* out_rays, int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    const uint64_t count = (uint64_t)w * h;
+    if (count == 0u) return RM_OK;
+    if (!out_rays) return fail(c, RM_ERR_NULL, "rm_camera_rays: out_rays is NULL");
+    if (W == 0 || H == 0 || W > kMaxDim || H > kMaxDim) return fail(c, RM_ERR_RANGE, "image size %ux%u out of range", W, H);
+    if ((uint64_t)x0 + w > W || (uint64_t)y0 + h > H)
+        return fail(c, RM_ERR_RANGE, "pixel block [%u,+%u) x [%u,+%u) outside the %ux%u image", x0, w, y0, h, W, H);
+    if (sample > RM_SAMPLE_CENTER) return fail(c, RM_ERR_RANGE, "sample %u: 0..15 or RM_SAMPLE_CENTER (16)", sample);
+    if (is_device && misaligned(out_rays, 4)) return fail(c, RM_ERR_ARG, "rm_camera_rays: out_rays needs 4-byte alignment");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    order_with_previous(c, s);
+    if (is_device) return query_launch(c, rmk::rm_camera_rays_kernel, count, 0u, s, c->uniforms, W, H, x0, y0, w, count, sample, out_rays);
+    const size_t bytes = (size_t)count * 24u;
+    if (int rc = grow_bytes(c, &c->d_qout, &c->d_qout_bytes, bytes)) return rc;
+    float* d = static_cast<float*>(c->d_qout);
+    if (int rc = query_launch(c, rmk::rm_camera_rays_kernel, count, 0u, s, c->uniforms, W, H, x0, y0, w, count, sample, d)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out_rays, d, bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     return RM_OK;
 }

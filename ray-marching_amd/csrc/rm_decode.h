@@ -85,6 +85,13 @@ struct RmDecoded {
     std::vector<RmRecord> mrec;
     uint32_t mat_spill_depth = 0;    // value-stack spill slots of mrec (each holds a distance and an index)
     uint32_t mat_xform_depth = 0;
+    // Scene queries (rm_query.h): the program decoded with its Material tags in place (what mrec is for a tagged program,
+    // what rec is for any other), with the command index of every primitive -- its position in the command stream, counting
+    // operators, transform pushes / pops and tags -- in p[6] of its record instead of the miss-test slot.  A query walks it
+    // on a stack of (distance, leaf, material) entries; nothing the draws read changes (rec, mrec, units, tree, bounds).
+    std::vector<RmRecord> qrec;
+    uint32_t q_spill_depth = 0, q_xform_depth = 0;  // value-stack spill slots and transform nesting of qrec
+    std::vector<uint32_t> rec_cmd;   // per record of rec: index of the command it starts with (a fused leaf: the leaf's)
 };
 
 // One open transform scope during decoding.
@@ -131,6 +138,7 @@ static inline int rm_decode_core(uint32_t cmd_count, const uint32_t* words, uint
     for (uint32_t i = 0; i < cmd_count; i++) {
         if (ptr >= cap_words) return RM_ERR_TRUNCATED;
         uint32_t op = words[ptr++];
+        d.rec_cmd.push_back(i);  // (every branch below that does not fail pushes exactly one record)
         RmRecord r;
         std::memset(&r, 0, sizeof r);
         uint32_t kind = RM_KIND_POP, np = 0;
@@ -436,7 +444,22 @@ static inline int rm_decode_program(uint32_t cmd_count, const uint32_t* words, u
                : op == RM_CMD_CYLINDER ? 5u : op == RM_CMD_TRANSLATION_PUSH ? 3u
                : op == RM_CMD_SMOOTH_UNION || op == RM_CMD_SCALE_PUSH ? 1u : 0u;
         }
-    if (!tagged) return rm_decode_core(cmd_count, words, cap_words, false, out);
+    // the query program: `tags` (the decoding with the tags in place) with each primitive's command index in p[6]
+    auto set_query = [](RmDecoded& d, const RmDecoded& tags) {
+        d.qrec = tags.rec;
+        for (size_t k = 0; k < d.qrec.size(); k++) {
+            const uint32_t kind = RM_OP_KIND(d.qrec[k].op);
+            if (kind == RM_KIND_SPHERE || kind == RM_KIND_BOX || kind == RM_KIND_CYLINDER || kind == RM_KIND_PLANE)
+                std::memcpy(&d.qrec[k].p[6], &tags.rec_cmd[k], 4);
+        }
+        d.q_spill_depth = tags.spill_depth;
+        d.q_xform_depth = tags.xform_depth;
+    };
+    if (!tagged) {
+        const int rc = rm_decode_core(cmd_count, words, cap_words, false, out);
+        if (rc == RM_OK) set_query(*out, *out);
+        return rc;
+    }
     RmDecoded with;
     int rc = rm_decode_core(cmd_count, words, cap_words, true, &with);  // validates everything, tags included
     if (rc != RM_OK) return rc;
@@ -463,6 +486,7 @@ static inline int rm_decode_program(uint32_t cmd_count, const uint32_t* words, u
     d.max_material = with.max_material;
     d.mat_spill_depth = with.spill_depth;
     d.mat_xform_depth = with.xform_depth;
+    set_query(d, with);
     d.mrec = std::move(with.rec);
     *out = std::move(d);
     return RM_OK;

@@ -170,6 +170,130 @@ class RayMarchingResources:
         self._check(self._L.rm_measure_write_bandwidth(self._h, nbytes, iters, C.byref(v)))
         return v.value
 
+    # -- scene queries (rm_query_points / rm_cast_rays / rm_camera_rays) ---------------------------------------------------
+    # numpy in, numpy out (host path, synchronous); a float32 torch tensor on this context's GPU in, torch tensors out on that
+    # GPU, computed on torch.cuda.current_stream() without a host round trip.
+    def _query_input(self, a, width, name):
+        """(kind, array, n): kind "torch" or "numpy"; array contiguous float32 of shape (n, width)."""
+        if type(a).__module__.split(".")[0] == "torch":
+            import torch
+            if a.device.type != "cuda" or a.device.index != self.device:
+                raise ValueError("%s is on %s; this context is on cuda:%d" % (name, a.device, self.device))
+            if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != width:
+                raise ValueError("%s must be a float32 tensor of shape (n, %d)" % (name, width))
+            return "torch", a.contiguous(), int(a.shape[0])
+        arr = np.asarray(a, dtype=np.float32)
+        if arr.shape == (width,):     # one row
+            arr = arr.reshape(1, width)
+        if arr.ndim != 2 or arr.shape[1] != width:
+            raise ValueError("%s must be an array of shape (n, %d), not %s" % (name, width, arr.shape))
+        arr = np.ascontiguousarray(arr)
+        return "numpy", arr, int(arr.shape[0])
+
+    @staticmethod
+    def _torch_stream(t):
+        import torch
+        return torch.cuda.current_stream(t.device).cuda_stream
+
+    def query_points(self, points, normals=False):
+        """Signed distance, leaf (command index of the primitive the value comes from, RM_NO_ID for an empty program) and
+        material at each point of an (n, 3) array; with normals=True also the shading normal.  Returns a dict of arrays:
+        distance (n,), leaf (n,), material (n,)[, normal (n, 3)]."""
+        kind, p, n = self._query_input(points, 3, "points")
+        if kind == "torch":
+            import torch
+            dist = torch.empty(n, dtype=torch.float32, device=p.device)
+            ids = torch.empty((n, 2), dtype=torch.int32, device=p.device)
+            nrm = torch.empty((n, 3), dtype=torch.float32, device=p.device) if normals else None
+            self.query_points_device(n, p.data_ptr(), dist.data_ptr(), nrm.data_ptr() if normals else 0, ids.data_ptr(),
+                                     stream=self._torch_stream(p))
+            out = {"distance": dist, "leaf": ids[:, 0], "material": ids[:, 1]}   # int32 views of the u32 ids (RM_NO_ID = -1)
+        else:
+            dist = np.empty(n, dtype=np.float32)
+            ids = np.empty((n, 2), dtype=np.uint32)
+            nrm = np.empty((n, 3), dtype=np.float32) if normals else None
+            self._check(self._L.rm_query_points(self._h, n, p.ctypes.data, dist.ctypes.data, nrm.ctypes.data if normals else None,
+                                                ids.ctypes.data, 0, None))
+            out = {"distance": dist, "leaf": ids[:, 0], "material": ids[:, 1]}
+        if normals:
+            out["normal"] = nrm
+        return out
+
+    def query_points_device(self, n, xyz_ptr, dist_ptr=0, normal_ptr=0, ids_ptr=0, stream=None):
+        """rm_query_points on device memory (integer addresses; 0 = not wanted), asynchronous on `stream`."""
+        self._check(self._L.rm_query_points(self._h, int(n), C.c_void_p(xyz_ptr), C.c_void_p(dist_ptr or None),
+                                            C.c_void_p(normal_ptr or None), C.c_void_p(ids_ptr or None), 1,
+                                            C.c_void_p(stream) if stream else None))
+
+    def cast_rays(self, origins, directions=None):
+        """March rays (origins (n, 3) + directions (n, 3), or one (n, 6) array as camera_rays returns) exactly as the draw
+        does.  Returns a dict: kind (RM_HIT_*), steps, leaf, material (RM_NO_ID unless a surface), t, position (n, 3),
+        normal (n, 3), diffuse, rgb (n, 3)."""
+        if directions is None:
+            kind, r, n = self._query_input(origins, 6, "rays")
+        else:
+            ko, o, n = self._query_input(origins, 3, "origins")
+            kd, d, nd = self._query_input(directions, 3, "directions")
+            if ko != kd or n != nd:
+                raise ValueError("origins and directions must be arrays of the same kind and length")
+            if ko == "torch":
+                import torch
+                kind, r = ko, torch.cat([o, d], dim=1).contiguous()
+            else:
+                kind, r = ko, np.ascontiguousarray(np.concatenate([o, d], axis=1))
+        if kind == "torch":
+            import torch
+            hit = torch.empty((n, 8), dtype=torch.float32, device=r.device)
+            ids = torch.empty((n, 4), dtype=torch.int32, device=r.device)
+            rgb = torch.empty((n, 3), dtype=torch.float32, device=r.device)
+            self.cast_rays_device(n, r.data_ptr(), hit.data_ptr(), ids.data_ptr(), rgb.data_ptr(), stream=self._torch_stream(r))
+        else:
+            hit = np.empty((n, 8), dtype=np.float32)
+            ids = np.empty((n, 4), dtype=np.uint32)
+            rgb = np.empty((n, 3), dtype=np.float32)
+            self._check(self._L.rm_cast_rays(self._h, n, r.ctypes.data, hit.ctypes.data, ids.ctypes.data, rgb.ctypes.data, 0, None))
+        return {"kind": ids[:, 0], "steps": ids[:, 1], "leaf": ids[:, 2], "material": ids[:, 3], "t": hit[:, 0],
+                "position": hit[:, 1:4], "normal": hit[:, 4:7], "diffuse": hit[:, 7], "rgb": rgb}
+
+    def cast_rays_device(self, n, rays_ptr, hit_ptr=0, ids_ptr=0, rgb_ptr=0, stream=None):
+        """rm_cast_rays on device memory (integer addresses; 0 = not wanted), asynchronous on `stream`."""
+        self._check(self._L.rm_cast_rays(self._h, int(n), C.c_void_p(rays_ptr), C.c_void_p(hit_ptr or None),
+                                         C.c_void_p(ids_ptr or None), C.c_void_p(rgb_ptr or None), 1,
+                                         C.c_void_p(stream) if stream else None))
+
+    def camera_rays(self, W, H, x0=0, y0=0, w=None, h=None, sample=_ffi.RM_SAMPLE_CENTER, out=None):
+        """The rays the draw marches for AA sample `sample` (0..15, or RM_SAMPLE_CENTER) of the pixels of the w x h block at
+        (x0, y0) of a W x H frame: (w*h, 6) float32, row-major.  out: a contiguous float32 torch tensor of exactly w*h*6
+        elements on this context's GPU, filled on torch.cuda.current_stream() (and returned) instead of a new host array --
+        the rays rm_cast_rays then reads without a host round trip."""
+        w = W - x0 if w is None else w
+        h = H - y0 if h is None else h
+        if out is not None:
+            # the library writes w*h*6 floats from out's first element on: nothing but a dense tensor of that size may receive them
+            if type(out).__module__.split(".")[0] != "torch":
+                raise ValueError("out must be a torch tensor")
+            import torch
+            if out.device.type != "cuda" or out.device.index != self.device:
+                raise ValueError("out is on %s; this context is on cuda:%d" % (out.device, self.device))
+            if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != max(w, 0) * max(h, 0) * 6:
+                raise ValueError("out must be a contiguous float32 tensor of %d elements (w*h x 6)" % (max(w, 0) * max(h, 0) * 6))
+            self.camera_rays_device(W, H, x0, y0, w, h, out.data_ptr(), sample, stream=self._torch_stream(out))
+            return out
+        rays = np.empty((max(w, 0) * max(h, 0), 6), dtype=np.float32)
+        self._check(self._L.rm_camera_rays(self._h, W, H, x0, y0, w, h, sample, rays.ctypes.data if rays.size else None, 0, None))
+        return rays
+
+    def camera_rays_device(self, W, H, x0, y0, w, h, out_ptr, sample=_ffi.RM_SAMPLE_CENTER, stream=None):
+        self._check(self._L.rm_camera_rays(self._h, W, H, x0, y0, w, h, sample, C.c_void_p(out_ptr), 1,
+                                           C.c_void_p(stream) if stream else None))
+
+    def pick(self, W, H, x, y):
+        """What is under pixel (x, y) of a W x H frame: the ray through its centre, cast.  Returns a dict of scalars (the
+        keys of cast_rays): kind, steps, leaf (the command index of the primitive hit, RM_NO_ID if none), material, t,
+        position, normal, diffuse, rgb."""
+        hit = self.cast_rays(self.camera_rays(W, H, x, y, 1, 1))
+        return {k: (v[0] if v.ndim == 1 else v[0].copy()) for k, v in hit.items()}
+
 
 class RayMarchingCallback:
     """Per-frame value object (renderer.rs:177-193) with the reference's prepare/paint split."""
