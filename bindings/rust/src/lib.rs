@@ -13,6 +13,7 @@
 //! `CSGCommandBufferBuilder`, `Camera` and `RayMarchingCallback::new(time, csg_node, viewport,
 //! camera)` untouched.
 #![allow(non_camel_case_types)]
+use std::cell::Cell;
 use std::ffi::{c_char, c_int, c_void, CStr};
 use std::fmt;
 
@@ -133,6 +134,11 @@ pub const RM_HIT_FLOOR: c_int = 2;
 // enum rm_sample
 pub const RM_SAMPLE_CENTER: c_int = 16;
 
+// Mesh export (rm_sample_grid / rm_extract_mesh / rm_read_mesh / rm_mesh_case_table).
+// enum rm_mesh: flags of rm_extract_mesh
+pub const RM_MESH_NORMALS: c_int = 1;
+pub const RM_MESH_IDS: c_int = 2;
+
 // Opcodes of the node types the reference only names in comments (builder.rs:8,14,16-23) and that the device
 // path implements as extensions: a CSGCommandType that gains these variants serialises them unchanged.
 //   Plane = 2, Intersection = 102, TranslationPush = 200, TranslationPop, RotationPush, RotationPop, ScalePush, ScalePop
@@ -169,6 +175,13 @@ extern "C" {
                         is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_camera_rays(ctx: *mut rm_ctx, w_frame: u32, h_frame: u32, x0: u32, y0: u32, w: u32, h: u32, sample: u32,
                           out_rays: *mut f32, is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_sample_grid(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, out_dist: *mut f32,
+                          is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_extract_mesh(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, level: f32,
+                           flags: u32, out_counts: *mut u64) -> c_int;
+    pub fn rm_read_mesh(ctx: *mut rm_ctx, out_vertices: *mut f32, out_triangles: *mut u32, out_normals: *mut f32,
+                        out_ids: *mut u32, is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_mesh_case_table(out: *mut u32, n_out: u32) -> c_int;
     pub fn rm_sync(ctx: *mut rm_ctx) -> c_int;
     pub fn rm_sync_context(ctx: *mut rm_ctx) -> c_int;
     pub fn rm_set_option(ctx: *mut rm_ctx, key: c_int, value: i64) -> c_int;
@@ -206,6 +219,9 @@ impl std::error::Error for RmError {}
 /// Replaces `RayMarchingResources` (renderer.rs:43-49): owns the GPU state of one device.
 pub struct RayMarchingResources {
     ctx: *mut rm_ctx,
+    /// (vertices, triangles) of the mesh the context holds since the last successful `extract_mesh`: what `read_mesh`
+    /// writes, so what its slices must hold
+    mesh: Cell<Option<(u64, u64)>>,
 }
 
 unsafe impl Send for RayMarchingResources {} // a context may move between threads; it is not Sync
@@ -219,7 +235,7 @@ impl RayMarchingResources {
             let msg = unsafe { CStr::from_ptr(rm_last_error(std::ptr::null_mut())) };
             return Err(RmError { status: rc, message: msg.to_string_lossy().into_owned() });
         }
-        Ok(Self { ctx })
+        Ok(Self { ctx, mesh: Cell::new(None) })
     }
 
     fn check(&self, rc: c_int) -> Result<(), RmError> {
@@ -321,6 +337,49 @@ impl RayMarchingResources {
         self.cast_rays(&ray, Some(&mut rec), Some(&mut ids), Some(&mut rgb))?;
         Ok(Hit { kind: ids[0] as c_int, steps: ids[1], leaf: ids[2], material: ids[3], t: rec[0], position: [rec[1], rec[2], rec[3]],
                  normal: [rec[4], rec[5], rec[6]], diffuse: rec[7], rgb })
+    }
+
+    /// `map_scene` at the `nx` x `ny` x `nz` lattice points `origin + (i, j, k) * step` (host memory, x fastest).
+    pub fn sample_grid(&self, origin: [f32; 3], step: [f32; 3], nx: u32, ny: u32, nz: u32,
+                       out_dist: &mut [f32]) -> Result<(), RmError> {
+        let n = nx as usize * ny as usize * nz as usize;
+        assert!(out_dist.len() >= n, "sample_grid: out_dist is shorter than {} points", n);
+        self.check(unsafe {
+            rm_sample_grid(self.ctx, origin.as_ptr(), step.as_ptr(), nx, ny, nz, out_dist.as_mut_ptr(), 0, std::ptr::null_mut())
+        })
+    }
+
+    /// Extracts the surface `map_scene = level` on the lattice into the context; `flags`: `RM_MESH_NORMALS`,
+    /// `RM_MESH_IDS`.  Returns (vertices, triangles); `read_mesh` copies them out.
+    pub fn extract_mesh(&self, origin: [f32; 3], step: [f32; 3], nx: u32, ny: u32, nz: u32, level: f32,
+                        flags: u32) -> Result<(u64, u64), RmError> {
+        let mut counts = [0u64; 2];
+        self.mesh.set(None);  // a failed extraction may have released the previous mesh
+        self.check(unsafe {
+            rm_extract_mesh(self.ctx, origin.as_ptr(), step.as_ptr(), nx, ny, nz, level, flags, counts.as_mut_ptr())
+        })?;
+        self.mesh.set(Some((counts[0], counts[1])));
+        Ok((counts[0], counts[1]))
+    }
+
+    /// The mesh of the last successful `extract_mesh` (of the (vertices, triangles) it returned): positions (three per
+    /// vertex), vertex indices (three per triangle), normals (three per vertex) and (leaf, material) (two per vertex).
+    /// `None` skips that output.  `RM_ERR_ARG` before any extraction, or for normals / ids it did not compute.
+    pub fn read_mesh(&self, out_vertices: Option<&mut [f32]>, out_triangles: Option<&mut [u32]>,
+                     out_normals: Option<&mut [f32]>, out_ids: Option<&mut [u32]>) -> Result<(), RmError> {
+        let (v, t) = match self.mesh.get() {
+            Some((v, t)) => (v as usize, t as usize),
+            None => return Err(RmError { status: RM_ERR_ARG, message: "read_mesh: no mesh has been extracted".to_string() }),
+        };
+        assert!(out_vertices.as_ref().map_or(true, |s| s.len() >= 3 * v), "read_mesh: out_vertices is shorter than {} vertices", v);
+        assert!(out_triangles.as_ref().map_or(true, |s| s.len() >= 3 * t), "read_mesh: out_triangles is shorter than {} triangles", t);
+        assert!(out_normals.as_ref().map_or(true, |s| s.len() >= 3 * v), "read_mesh: out_normals is shorter than {} vertices", v);
+        assert!(out_ids.as_ref().map_or(true, |s| s.len() >= 2 * v), "read_mesh: out_ids is shorter than {} vertices", v);
+        let pv = out_vertices.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pt = out_triangles.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pn = out_normals.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pi = out_ids.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        self.check(unsafe { rm_read_mesh(self.ctx, pv, pt, pn, pi, 0, std::ptr::null_mut()) })
     }
 }
 

@@ -304,6 +304,43 @@ int rm_cast_rays(rm_ctx* ctx, uint32_t n, const float* rays, float* out_hit, uin
 int rm_camera_rays(rm_ctx* ctx, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                    uint32_t sample, float* out_rays, int is_device, void* stream);
 
+/* Mesh export (extension): the scene's distance on a lattice, and its level surface as an indexed triangle mesh, from the
+ * program, limits and material table as they are at the call.  Every float is bit-identical to the
+ * oracle's map_scene at the lattice points; vertices and triangles follow from them by the rule below, so two runs give
+ * identical arrays.
+ * Lattice: origin and step are host arrays of 3 floats (finite; step > 0); point (i, j, k) is (ox + (float)i * sx,
+ * oy + (float)j * sy, oz + (float)k * sz), its linear index i + nx * (j + ny * k).
+ * Inside: d < level (NaN is outside).  One vertex on each lattice edge (p, p + e_a) whose ends differ, at
+ * t = (da - level) / (da - db) along axis a; vertices ordered by (linear index of p, axis).  Triangles: per cell (anchored
+ * at its lowest corner, ordered by linear cell index) the entries of the case table (rm_mesh_case_table), wound
+ * counter-clockwise seen from outside (the geometric normal points toward larger d).  The mesh is open where the surface
+ * meets the lattice's border. */
+enum rm_mesh { RM_MESH_NORMALS = 1, RM_MESH_IDS = 2 }; /* flags of rm_extract_mesh: per-vertex attributes to compute */
+/* map_scene at the nx x ny x nz points (1..65536 per axis, at most 2^31 in all; RM_ERR_RANGE otherwise) into out_dist,
+ * x fastest.  is_device and stream as for rm_query_points; a device out_dist needs 4-byte alignment. */
+int rm_sample_grid(rm_ctx* ctx, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
+                   float* out_dist, int is_device, void* stream);
+/* Extracts the surface d = level (finite) on the lattice (2..65536 points per axis, at most 2^28 in all; RM_ERR_RANGE
+ * otherwise) into buffers the context owns until its next rm_extract_mesh or rm_destroy; out_counts[0] = vertices,
+ * [1] = triangles.  Synchronous on the context's own stream, ordered after its earlier work.  flags: RM_MESH_NORMALS and
+ * RM_MESH_IDS add per-vertex normal and (leaf, material), exactly what rm_query_points returns at the vertex positions.
+ * Errors: those of a query for the program and limits; RM_ERR_DEVICE when device memory runs out (about 10 bytes per
+ * lattice point of scratch, plus the mesh). */
+int rm_extract_mesh(rm_ctx* ctx, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
+                    float level, uint32_t flags, uint64_t* out_counts);
+/* Copies the last extracted mesh out: out_vertices V x 3, out_triangles T x 3 (vertex indices), out_normals V x 3, out_ids
+ * V x 2 (leaf, material); any may be NULL.  RM_ERR_ARG before any extraction, or for normals / ids that extraction did not
+ * compute.  is_device and stream as for rm_query_points (device arrays: out_ids 8-byte aligned, the others 4-byte); the
+ * next rm_extract_mesh waits for a device read that is still running. */
+int rm_read_mesh(rm_ctx* ctx, float* out_vertices, uint32_t* out_triangles, float* out_normals, uint32_t* out_ids,
+                 int is_device, void* stream);
+/* The case table of rm_extract_mesh (host code; no context): 256 cases x 16 words.  out[16 * case] = triangle count (0..5),
+ * out[16 * case + 1 + 3 * t + m] = the cube edge of vertex m of triangle t, 0xFFFFFFFF after the last.  Case = sum over
+ * corners c of inside(c) << c, corner c at (c & 1, c >> 1 & 1, c >> 2 & 1); edge e runs along axis e >> 2 from the corner
+ * with 0 on it to the one with 1, bit 0 / bit 1 of e & 3 its offset on the lower / higher other axis.  RM_ERR_ARG when
+ * n_out < 4096. */
+int rm_mesh_case_table(uint32_t* out, uint32_t n_out);
+
 /* Waits for all work on the context's GPU (hipDeviceSynchronize). */
 int rm_sync(rm_ctx* ctx);
 /* HIP graphs: after its first draw of a given size and program (which allocates scratch buffers and compiles /

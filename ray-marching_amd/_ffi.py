@@ -45,6 +45,8 @@ RM_INFO_PRUNED, RM_INFO_INTERPRETER_LOOP, RM_INFO_JIT_FROM_CACHE = 9, 10, 11
 RM_NO_ID = 0xFFFFFFFF
 RM_HIT_NONE, RM_HIT_SURFACE, RM_HIT_FLOOR = 0, 1, 2
 RM_SAMPLE_CENTER = 16
+# mesh export (rm_sample_grid / rm_extract_mesh / rm_read_mesh / rm_mesh_case_table)
+RM_MESH_NORMALS, RM_MESH_IDS = 1, 2
 
 _hip = None
 _host = None
@@ -131,6 +133,15 @@ def hip_lib():
         L.rm_cast_rays.restype = C.c_int
         L.rm_camera_rays.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, vp, C.c_int, vp]
         L.rm_camera_rays.restype = C.c_int
+        f3 = C.POINTER(C.c_float)
+        L.rm_sample_grid.argtypes = [vp, f3, f3, u32, u32, u32, vp, C.c_int, vp]
+        L.rm_sample_grid.restype = C.c_int
+        L.rm_extract_mesh.argtypes = [vp, f3, f3, u32, u32, u32, C.c_float, u32, C.POINTER(u64)]
+        L.rm_extract_mesh.restype = C.c_int
+        L.rm_read_mesh.argtypes = [vp, vp, vp, vp, vp, C.c_int, vp]
+        L.rm_read_mesh.restype = C.c_int
+        L.rm_mesh_case_table.argtypes = [vp, u32]
+        L.rm_mesh_case_table.restype = C.c_int
         sz = C.c_size_t
         L.rm_jit_source.argtypes = [u32, C.POINTER(u32), u32, C.c_int, C.c_char_p, sz, C.POINTER(sz)]
         L.rm_jit_source.restype = C.c_int

@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -20,6 +21,7 @@
 #include "rm_interp.h"
 #include "rm_kernel_v5.h"
 #include "rm_query.h"
+#include "rm_mesh.h"
 
 #define RM_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -82,6 +84,14 @@ struct rm_ctx {
     void* d_qout = nullptr;
     size_t d_qout_bytes = 0;
     size_t max_lds = 0;  // LDS a workgroup may allocate on this device
+    // mesh export (rm_mesh.h): the extraction's scratch (distances, vertex bases, flags, block sums) and the last mesh
+    void* d_mscratch = nullptr;
+    size_t d_mscratch_bytes = 0;
+    void* d_mesh = nullptr;
+    size_t d_mesh_bytes = 0;
+    bool mesh_valid = false;
+    uint64_t mesh_v = 0, mesh_t = 0;
+    uint32_t mesh_flags = 0;
     // scratch for host-destination draws and batch uniforms
     float* d_out = nullptr;
     size_t d_out_bytes = 0;
@@ -740,6 +750,8 @@ RM_EXPORT void rm_destroy(rm_ctx* c) {
     if (c->d_qprog) (void)hipFree(c->d_qprog);
     if (c->d_qin) (void)hipFree(c->d_qin);
     if (c->d_qout) (void)hipFree(c->d_qout);
+    if (c->d_mscratch) (void)hipFree(c->d_mscratch);
+    if (c->d_mesh) (void)hipFree(c->d_mesh);
     for (auto& st : c->staging) {
         if (st.host) (void)hipHostFree(st.host);
         if (st.done) (void)hipEventDestroy(st.done);
@@ -1233,6 +1245,177 @@ RM_EXPORT int rm_camera_rays(rm_ctx* c, uint32_t W, uint32_t H, uint32_t x0, uin
     if (int rc = query_launch(c, rmk::rm_camera_rays_kernel, count, 0u, s, c->uniforms, W, H, x0, y0, w, count, sample, d)) return rc;
     HIP_TRY(c, hipMemcpyAsync(out_rays, d, bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+// ---- mesh export (rm_mesh.h) ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint64_t kMaxGridPoints = 1ull << 31;  // rm_sample_grid
+constexpr uint64_t kMaxMeshPoints = 1ull << 28;  // rm_extract_mesh: u32 prefix sums (<= 3 * 2^28 vertices, 5 * 2^28 triangles)
+
+// origin and step of a lattice (host arrays of 3 floats): finite, and step > 0 so that no axis is flipped (the winding)
+int check_lattice(rm_ctx* c, const char* fn, const float* origin, const float* step) {
+    if (!origin || !step) return fail(c, RM_ERR_NULL, "%s: origin or step is NULL", fn);
+    for (int a = 0; a < 3; a++) {
+        if (!std::isfinite(origin[a])) return fail(c, RM_ERR_ARG, "%s: origin[%d] = %g is not finite", fn, a, (double)origin[a]);
+        if (!std::isfinite(step[a]) || !(step[a] > 0.0f))
+            return fail(c, RM_ERR_ARG, "%s: step[%d] = %g: a step must be finite and > 0", fn, a, (double)step[a]);
+    }
+    return RM_OK;
+}
+
+using GridFn = void (*)(rmk::QueryLaunch, float, float, float, float, float, float, uint32_t, uint32_t, uint64_t, float*);
+GridFn grid_kernel(int loop) {
+    return loop == rmk::Q_LOOP_CHAIN ? rmk::rm_grid_dist_kernel<rmk::Q_LOOP_CHAIN>
+         : loop == rmk::Q_LOOP_TREE ? rmk::rm_grid_dist_kernel<rmk::Q_LOOP_TREE>
+                                    : rmk::rm_grid_dist_kernel<rmk::Q_LOOP_GENERAL>;
+}
+int launch_grid(rm_ctx* c, const rmk::QueryLaunch& Q, int loop, size_t shmem, hipStream_t s, const float* o, const float* st,
+                uint32_t nx, uint32_t ny, uint64_t n, float* out) {
+    return query_launch(c, grid_kernel(loop), n, shmem, s, Q, o[0], o[1], o[2], st[0], st[1], st[2], nx, ny, n, out);
+}
+
+// Where the arrays of a mesh of v vertices and t triangles lie in rm_ctx::d_mesh (16-byte aligned, in this order).
+struct MeshLayout {
+    size_t vertices, triangles, normals, ids, bytes;
+};
+MeshLayout mesh_layout(uint64_t v, uint64_t t, uint32_t flags) {
+    MeshLayout L{};
+    L.triangles = align16(v * 12u);
+    L.normals = L.triangles + align16(t * 12u);
+    L.ids = L.normals + ((flags & RM_MESH_NORMALS) ? align16(v * 12u) : 0u);
+    L.bytes = L.ids + ((flags & RM_MESH_IDS) ? v * 8u : 0u);
+    return L;
+}
+
+}  // namespace
+
+RM_EXPORT int rm_sample_grid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
+                             float* out_dist, int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (int rc = check_lattice(c, "rm_sample_grid", origin, step)) return rc;
+    const uint64_t n = (uint64_t)nx * ny * nz;
+    if (nx == 0 || ny == 0 || nz == 0 || nx > kMaxDim || ny > kMaxDim || nz > kMaxDim || n > kMaxGridPoints)
+        return fail(c, RM_ERR_RANGE, "rm_sample_grid: lattice %ux%ux%u: 1..65536 points per axis, at most 2^31 in all", nx, ny, nz);
+    if (!out_dist) return fail(c, RM_ERR_NULL, "rm_sample_grid: out_dist is NULL");
+    if (is_device && misaligned(out_dist, 4)) return fail(c, RM_ERR_ARG, "rm_sample_grid: out_dist needs 4-byte alignment");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);
+    if (rc != RM_OK) return rc;
+    if (is_device) return launch_grid(c, Q, loop, shmem, s, origin, step, nx, ny, n, out_dist);
+    if ((rc = grow_bytes(c, &c->d_qout, &c->d_qout_bytes, n * 4u)) != RM_OK) return rc;
+    float* d = static_cast<float*>(c->d_qout);
+    if ((rc = launch_grid(c, Q, loop, shmem, s, origin, step, nx, ny, n, d)) != RM_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out_dist, d, n * 4u, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
+                              float level, uint32_t flags, uint64_t* out_counts) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_counts) return fail(c, RM_ERR_NULL, "rm_extract_mesh: out_counts is NULL");
+    if (int rc = check_lattice(c, "rm_extract_mesh", origin, step)) return rc;
+    if (!std::isfinite(level)) return fail(c, RM_ERR_ARG, "rm_extract_mesh: level %g is not finite", (double)level);
+    if (flags & ~(uint32_t)(RM_MESH_NORMALS | RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_extract_mesh: unknown flags 0x%x", flags);
+    const uint64_t n64 = (uint64_t)nx * ny * nz;
+    if (nx < 2 || ny < 2 || nz < 2 || nx > kMaxDim || ny > kMaxDim || nz > kMaxDim || n64 > kMaxMeshPoints)
+        return fail(c, RM_ERR_RANGE, "rm_extract_mesh: lattice %ux%ux%u: 2..65536 points per axis, at most 2^28 in all", nx, ny, nz);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    const bool normals = (flags & RM_MESH_NORMALS) != 0, ids = (flags & RM_MESH_IDS) != 0;
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    int rc = query_begin(c, s, ids, false, &Q, &loop, &shmem);  // after a device read of the previous mesh, too
+    if (rc != RM_OK) return rc;
+    c->mesh_valid = false;  // its buffers change from here on
+    // scratch: distances, vertex bases (4 B per point each), flags (1 B), block sums (8 B per 2048 points), the two totals
+    const uint32_t n = (uint32_t)n64, nb = (n + rmk::kMeshBlock - 1u) / rmk::kMeshBlock;
+    const size_t dist_o = 0, vbase_o = align16((size_t)n * 4u), flags_o = vbase_o + align16((size_t)n * 4u),
+                 sums_o = flags_o + align16(n), totals_o = sums_o + align16((size_t)nb * 8u);
+    if ((rc = grow_bytes(c, &c->d_mscratch, &c->d_mscratch_bytes, totals_o + 16u)) != RM_OK) return rc;
+    char* sc = static_cast<char*>(c->d_mscratch);
+    float* dist = reinterpret_cast<float*>(sc + dist_o);
+    uint32_t* vbase = reinterpret_cast<uint32_t*>(sc + vbase_o);
+    uint8_t* fl = reinterpret_cast<uint8_t*>(sc + flags_o);
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(sc + sums_o);
+    uint32_t* totals = reinterpret_cast<uint32_t*>(sc + totals_o);
+    const rmk::MeshGrid g{origin[0], origin[1], origin[2], step[0], step[1], step[2], nx, ny, nz, n};
+    if ((rc = launch_grid(c, Q, loop, shmem, s, origin, step, nx, ny, n, dist)) != RM_OK) return rc;
+    hipLaunchKernelGGL(rmk::rm_mesh_count_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist), sums);
+    hipLaunchKernelGGL(rmk::rm_mesh_scan_kernel, dim3(1), dim3(1024), 0, s, sums, nb, totals);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t tot[2] = {0u, 0u};
+    HIP_TRY(c, hipMemcpyAsync(tot, totals, sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const uint64_t V = tot[0], T = tot[1];
+    const MeshLayout L = mesh_layout(V, T, flags);
+    if ((rc = grow_bytes(c, &c->d_mesh, &c->d_mesh_bytes, L.bytes)) != RM_OK) return rc;
+    char* m = static_cast<char*>(c->d_mesh);
+    float* verts = reinterpret_cast<float*>(m + L.vertices);
+    if (V > 0u) {
+        const unsigned long long* offs = sums;
+        hipLaunchKernelGGL(rmk::rm_mesh_vertex_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist), offs,
+                           vbase, fl, verts);
+        if (T > 0u)
+            hipLaunchKernelGGL(rmk::rm_mesh_triangle_kernel, dim3(nb), dim3(256), 0, s, g, offs, static_cast<const uint32_t*>(vbase),
+                               static_cast<const uint8_t*>(fl), reinterpret_cast<uint32_t*>(m + L.triangles));
+        HIP_TRY(c, hipGetLastError());
+        if (normals || ids) {  // the attributes: rm_query_points at the vertices, device to device
+            float* nrm = normals ? reinterpret_cast<float*>(m + L.normals) : nullptr;
+            uint32_t* idp = ids ? reinterpret_cast<uint32_t*>(m + L.ids) : nullptr;
+            const PointsFn k = loop == rmk::Q_LOOP_CHAIN ? points_kernel<rmk::Q_LOOP_CHAIN>(false, normals, ids)
+                             : loop == rmk::Q_LOOP_TREE ? points_kernel<rmk::Q_LOOP_TREE>(false, normals, ids)
+                                                        : points_kernel<rmk::Q_LOOP_GENERAL>(false, normals, ids);
+            if ((rc = query_launch(c, k, V, shmem, s, Q, (uint32_t)V, static_cast<const float*>(verts), static_cast<float*>(nullptr),
+                                   nrm, idp)) != RM_OK)
+                return rc;
+        }
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    c->mesh_valid = true;
+    c->mesh_v = V;
+    c->mesh_t = T;
+    c->mesh_flags = flags;
+    out_counts[0] = V;
+    out_counts[1] = T;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_read_mesh(rm_ctx* c, float* out_vertices, uint32_t* out_triangles, float* out_normals, uint32_t* out_ids,
+                           int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!c->mesh_valid) return fail(c, RM_ERR_ARG, "rm_read_mesh: no mesh has been extracted");
+    if (out_normals && !(c->mesh_flags & RM_MESH_NORMALS))
+        return fail(c, RM_ERR_ARG, "rm_read_mesh: the mesh was extracted without RM_MESH_NORMALS");
+    if (out_ids && !(c->mesh_flags & RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_read_mesh: the mesh was extracted without RM_MESH_IDS");
+    if (is_device && (misaligned(out_vertices, 4) || misaligned(out_triangles, 4) || misaligned(out_normals, 4) || misaligned(out_ids, 8)))
+        return fail(c, RM_ERR_ARG, "rm_read_mesh: device arrays need 4-byte alignment (out_ids: 8-byte)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    order_with_previous(c, s);  // (the next extraction waits for this stream in turn)
+    const MeshLayout L = mesh_layout(c->mesh_v, c->mesh_t, c->mesh_flags);
+    const char* m = static_cast<const char*>(c->d_mesh);
+    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const size_t vb = (size_t)c->mesh_v * 12u, tb = (size_t)c->mesh_t * 12u, ib = (size_t)c->mesh_v * 8u;
+    if (out_vertices && vb) HIP_TRY(c, hipMemcpyAsync(out_vertices, m + L.vertices, vb, kind, s));
+    if (out_triangles && tb) HIP_TRY(c, hipMemcpyAsync(out_triangles, m + L.triangles, tb, kind, s));
+    if (out_normals && vb) HIP_TRY(c, hipMemcpyAsync(out_normals, m + L.normals, vb, kind, s));
+    if (out_ids && ib) HIP_TRY(c, hipMemcpyAsync(out_ids, m + L.ids, ib, kind, s));
+    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+RM_EXPORT int rm_mesh_case_table(uint32_t* out, uint32_t n_out) {
+    if (!out) return RM_ERR_NULL;
+    if (n_out < 256u * rmk::kMeshCaseWords) return RM_ERR_ARG;
+    std::memcpy(out, rmk::kMeshCaseTable.w, sizeof rmk::kMeshCaseTable.w);
     return RM_OK;
 }
 

@@ -294,6 +294,96 @@ class RayMarchingResources:
         hit = self.cast_rays(self.camera_rays(W, H, x, y, 1, 1))
         return {k: (v[0] if v.ndim == 1 else v[0].copy()) for k, v in hit.items()}
 
+    # -- mesh export (rm_sample_grid / rm_extract_mesh / rm_read_mesh) ------------------------------------------------------
+    # A lattice is (origin, step, shape), each in (x, y, z) order: point (i, j, k) lies at origin + (i, j, k) * step (float32,
+    # one rounded product and one rounded sum per coordinate); arrays of lattice values are indexed [k, j, i].
+    @staticmethod
+    def _lattice(origin, step, shape, least):
+        # copies: the library reads 3 floats from each address, and a broadcast or strided view (extract_mesh's scalar lo)
+        # does not hold them there
+        o = np.array(origin, dtype=np.float32, copy=True).reshape(-1)
+        s = np.array(step, dtype=np.float32, copy=True).reshape(-1)
+        n = tuple(int(x) for x in np.asarray(shape).reshape(-1))
+        if o.shape != (3,) or s.shape != (3,) or len(n) != 3:
+            raise ValueError("origin, step and shape must have 3 entries each (x, y, z)")
+        if not np.all(np.isfinite(o)) or not np.all(np.isfinite(s)) or not np.all(s > 0):
+            raise ValueError("origin must be finite and step finite and > 0")
+        if min(n) < least:
+            raise ValueError("a lattice needs at least %d points per axis, not %s" % (least, n))
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        return o, s, n, fp
+
+    def sample_grid(self, origin, step, shape, out=None):
+        """map_scene at the lattice points: float32 (nz, ny, nx), bit-identical to the oracle.  out: a contiguous float32
+        torch tensor of nx*ny*nz elements on this context's GPU, filled on torch.cuda.current_stream() (and returned)."""
+        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 1)
+        if out is not None:
+            if type(out).__module__.split(".")[0] != "torch":
+                raise ValueError("out must be a torch tensor")
+            import torch
+            if out.device.type != "cuda" or out.device.index != self.device:
+                raise ValueError("out is on %s; this context is on cuda:%d" % (out.device, self.device))
+            if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != nx * ny * nz:
+                raise ValueError("out must be a contiguous float32 tensor of %d elements (nx*ny*nz)" % (nx * ny * nz))
+            self.sample_grid_device(o, s, (nx, ny, nz), out.data_ptr(), stream=self._torch_stream(out))
+            return out
+        d = np.empty((nz, ny, nx), dtype=np.float32)
+        self._check(self._L.rm_sample_grid(self._h, fp(o), fp(s), nx, ny, nz, d.ctypes.data, 0, None))
+        return d
+
+    def sample_grid_device(self, origin, step, shape, out_ptr, stream=None):
+        """rm_sample_grid into device memory (an integer address), asynchronous on `stream`."""
+        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 1)
+        self._check(self._L.rm_sample_grid(self._h, fp(o), fp(s), nx, ny, nz, C.c_void_p(out_ptr), 1,
+                                           C.c_void_p(stream) if stream else None))
+
+    def extract_mesh(self, lo, hi, resolution, level=0.0, normals=True, ids=True, device=False):
+        """The surface map_scene = level inside the box [lo, hi], on a lattice of `resolution` points per axis (an int, or
+        (nx, ny, nz)): origin lo, step (hi - lo) / (n - 1) in float32.  Returns a mesh.Mesh (numpy arrays, or torch tensors
+        on this context's GPU with device=True).  The mesh is open where the surface leaves the box."""
+        lo = np.broadcast_to(np.asarray(lo, dtype=np.float32), (3,))
+        hi = np.broadcast_to(np.asarray(hi, dtype=np.float32), (3,))
+        n = np.broadcast_to(np.asarray(resolution), (3,))
+        if not np.all(np.isfinite(lo)) or not np.all(np.isfinite(hi)) or not np.all(lo < hi):
+            raise ValueError("lo and hi must be finite with lo < hi on every axis")
+        if n.dtype.kind not in "iu" or np.any(n < 2):
+            raise ValueError("resolution must be an integer of at least 2 points per axis, not %s" % (resolution,))
+        step = (hi - lo) / (n.astype(np.float32) - np.float32(1.0))
+        return self.extract_mesh_grid(lo, step, n, level, normals, ids, device)
+
+    def extract_mesh_grid(self, origin, step, shape, level=0.0, normals=True, ids=True, device=False):
+        """extract_mesh on an exact lattice (origin, step, shape as sample_grid takes them)."""
+        from . import mesh as _mesh
+        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
+        flags = (_ffi.RM_MESH_NORMALS if normals else 0) | (_ffi.RM_MESH_IDS if ids else 0)
+        counts = (C.c_uint64 * 2)()
+        self._check(self._L.rm_extract_mesh(self._h, fp(o), fp(s), nx, ny, nz, float(level), flags, counts))
+        V, T = int(counts[0]), int(counts[1])
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
+            tris = torch.empty((T, 3), dtype=torch.int32, device=dev)       # int32 views of the u32 indices
+            nrm = torch.empty((V, 3), dtype=torch.float32, device=dev) if normals else None
+            idv = torch.empty((V, 2), dtype=torch.int32, device=dev) if ids else None
+            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
+            self._check(self._L.rm_read_mesh(self._h, ptr(verts), ptr(tris), ptr(nrm), ptr(idv), 1,
+                                             C.c_void_p(self._torch_stream(verts))))
+        else:
+            verts = np.empty((V, 3), dtype=np.float32)
+            tris = np.empty((T, 3), dtype=np.uint32)
+            nrm = np.empty((V, 3), dtype=np.float32) if normals else None
+            idv = np.empty((V, 2), dtype=np.uint32) if ids else None
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+            self._check(self._L.rm_read_mesh(self._h, ptr(verts), ptr(tris), ptr(nrm), ptr(idv), 0, None))
+        return _mesh.Mesh(verts, tris, nrm, idv[:, 0] if ids else None, idv[:, 1] if ids else None)
+
+    def read_mesh_device(self, vertices_ptr=0, triangles_ptr=0, normals_ptr=0, ids_ptr=0, stream=None):
+        """rm_read_mesh of the last extraction into device memory (integer addresses; 0 = not wanted), asynchronous."""
+        self._check(self._L.rm_read_mesh(self._h, C.c_void_p(vertices_ptr or None), C.c_void_p(triangles_ptr or None),
+                                         C.c_void_p(normals_ptr or None), C.c_void_p(ids_ptr or None), 1,
+                                         C.c_void_p(stream) if stream else None))
+
 
 class RayMarchingCallback:
     """Per-frame value object (renderer.rs:177-193) with the reference's prepare/paint split."""
