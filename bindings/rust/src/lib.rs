@@ -139,6 +139,23 @@ pub const RM_SAMPLE_CENTER: c_int = 16;
 pub const RM_MESH_NORMALS: c_int = 1;
 pub const RM_MESH_IDS: c_int = 2;
 
+// Lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit).
+// enum rm_light: indices into the parameter array; RM_LIGHT_PARAMS is its length
+pub const RM_LIGHT_POS_X: c_int = 0;
+pub const RM_LIGHT_POS_Y: c_int = 1;
+pub const RM_LIGHT_POS_Z: c_int = 2;
+pub const RM_LIGHT_SHADOW: c_int = 3;
+pub const RM_LIGHT_SHADOW_SOFTNESS: c_int = 4;
+pub const RM_LIGHT_BIAS: c_int = 5;
+pub const RM_LIGHT_SHADOW_MAX_T: c_int = 6;
+pub const RM_LIGHT_SHADOW_STEPS: c_int = 7;
+pub const RM_LIGHT_AO: c_int = 8;
+pub const RM_LIGHT_AO_STEP: c_int = 9;
+pub const RM_LIGHT_AO_FALLOFF: c_int = 10;
+pub const RM_LIGHT_AO_SCALE: c_int = 11;
+pub const RM_LIGHT_AO_TAPS: c_int = 12;
+pub const RM_LIGHT_PARAMS: c_int = 13;
+
 // Opcodes of the node types the reference only names in comments (builder.rs:8,14,16-23) and that the device
 // path implements as extensions: a CSGCommandType that gains these variants serialises them unchanged.
 //   Plane = 2, Intersection = 102, TranslationPush = 200, TranslationPop, RotationPush, RotationPop, ScalePush, ScalePop
@@ -182,6 +199,10 @@ extern "C" {
     pub fn rm_read_mesh(ctx: *mut rm_ctx, out_vertices: *mut f32, out_triangles: *mut u32, out_normals: *mut f32,
                         out_ids: *mut u32, is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_mesh_case_table(out: *mut u32, n_out: u32) -> c_int;
+    pub fn rm_lighting_defaults(out: *mut f32, n_out: u32) -> c_int;
+    pub fn rm_set_lighting(ctx: *mut rm_ctx, params: *const f32, count: u32) -> c_int;
+    pub fn rm_draw_lit(ctx: *mut rm_ctx, w: u32, h: u32, row0: u32, rows: u32, out_rgba: *mut f32, out_is_device: c_int,
+                       stream: *mut c_void) -> c_int;
     pub fn rm_sync(ctx: *mut rm_ctx) -> c_int;
     pub fn rm_sync_context(ctx: *mut rm_ctx) -> c_int;
     pub fn rm_set_option(ctx: *mut rm_ctx, key: c_int, value: i64) -> c_int;
@@ -198,6 +219,14 @@ extern "C" {
     pub fn rm_jit_log(ctx: *mut rm_ctx, buf: *mut c_char, cap: usize) -> c_int;
     pub fn rm_last_error(ctx: *mut rm_ctx) -> *const c_char;
     pub fn rm_status_string(status: c_int) -> *const c_char;
+}
+
+/// The default lighting parameters (`rm_lighting_defaults`; host code, no GPU needed).
+pub fn lighting_defaults() -> [f32; RM_LIGHT_PARAMS as usize] {
+    let mut out = [0.0f32; RM_LIGHT_PARAMS as usize];
+    let rc = unsafe { rm_lighting_defaults(out.as_mut_ptr(), RM_LIGHT_PARAMS as u32) };
+    assert_eq!(rc, RM_OK);
+    out
 }
 
 /// What the reference `unwrap()`s away (renderer.rs:24, 203, 250): a status code of `enum rm_status`
@@ -269,6 +298,19 @@ impl RayMarchingResources {
     pub fn draw(&self, width: u32, height: u32, out_rgba: &mut [f32]) -> Result<(), RmError> {
         assert!(out_rgba.len() >= (width as usize) * (height as usize) * 4);
         self.check(unsafe { rm_draw(self.ctx, width, height, 0, height, out_rgba.as_mut_ptr(), 0, std::ptr::null_mut()) })
+    }
+
+    /// All lighting parameters at once (indices `RM_LIGHT_*`; `lighting_defaults()` is the starting point).  A value
+    /// outside its range is `RM_ERR_RANGE` and changes nothing.
+    pub fn set_lighting(&self, params: &[f32; RM_LIGHT_PARAMS as usize]) -> Result<(), RmError> {
+        self.check(unsafe { rm_set_lighting(self.ctx, params.as_ptr(), RM_LIGHT_PARAMS as u32) })
+    }
+
+    /// `draw` with soft shadows and ambient occlusion into a host RGBA32F image; with
+    /// `RM_LIGHT_SHADOW` and `RM_LIGHT_AO` at 0 the image is `draw`'s bit for bit.
+    pub fn draw_lit(&self, width: u32, height: u32, out_rgba: &mut [f32]) -> Result<(), RmError> {
+        assert!(out_rgba.len() >= (width as usize) * (height as usize) * 4);
+        self.check(unsafe { rm_draw_lit(self.ctx, width, height, 0, height, out_rgba.as_mut_ptr(), 0, std::ptr::null_mut()) })
     }
 
     /// This GPU's interleaved strips of a frame tiled over `stride` GPUs (north-star layout), host destination.

@@ -341,6 +341,39 @@ int rm_read_mesh(rm_ctx* ctx, float* out_vertices, uint32_t* out_triangles, floa
  * n_out < 4096. */
 int rm_mesh_case_table(uint32_t* out, uint32_t n_out);
 
+/* Lit rendering (extension): rm_draw with soft shadows and ambient occlusion marched through the same distance field
+ * (DESIGN.md section 13 is the contract, to the last bit).  The reference has one fixed light and max(0.02, n.l)
+ * (wgsl:98-105); with RM_LIGHT_SHADOW = 0 and RM_LIGHT_AO = 0 rm_draw_lit writes rm_draw's image bit for bit.
+ * The light keeps the reference's convention: l = normalize(pos - P) is the vector whose dot product with the normal lights
+ * a surface, and shadow rays travel along +l.  The floor (wgsl:117-127) receives shadow and occlusion but is not part of
+ * map_scene, so it casts neither. */
+enum rm_light {
+    RM_LIGHT_POS_X = 0, RM_LIGHT_POS_Y = 1, RM_LIGHT_POS_Z = 2, /* P: default (2, -5, 3), wgsl:100; finite */
+    RM_LIGHT_SHADOW = 3,          /* S, strength of the shadow term: default 1; [0, 1] */
+    RM_LIGHT_SHADOW_SOFTNESS = 4, /* k, penumbra = min over the march of k h / t: default 8; > 0 */
+    RM_LIGHT_BIAS = 5,            /* b, shadow rays start at pos + n b: default 0.02; >= 0 */
+    RM_LIGHT_SHADOW_MAX_T = 6,    /* a shadow ray that travelled further is lit: default 20; > 0 */
+    RM_LIGHT_SHADOW_STEPS = 7,    /* map_scene evaluations a shadow ray may take: default 64; integral, 1..1024 */
+    RM_LIGHT_AO = 8,              /* A, strength of the occlusion term: default 1; [0, 1] */
+    RM_LIGHT_AO_STEP = 9,         /* tap i = 1.. lies at pos + n (step i): default 0.1; > 0 */
+    RM_LIGHT_AO_FALLOFF = 10,     /* weight of tap i + 1 over tap i: default 0.75; (0, 1] */
+    RM_LIGHT_AO_SCALE = 11,       /* ao = clamp(1 - scale * sum, 0, 1): default 1.5; >= 0 */
+    RM_LIGHT_AO_TAPS = 12,        /* default 5; integral, 1..16 */
+    RM_LIGHT_PARAMS = 13
+};
+/* The table above (host code; no context).  RM_ERR_NULL for a NULL out, RM_ERR_ARG when n_out < RM_LIGHT_PARAMS. */
+int rm_lighting_defaults(float* out, uint32_t n_out);
+/* All RM_LIGHT_PARAMS values at once (a new context holds the defaults); count must be RM_LIGHT_PARAMS (RM_ERR_ARG).
+ * RM_ERR_RANGE for a value outside the table (every value must be finite); a failed call changes nothing.  The
+ * parameters travel with each lit draw as kernel arguments, like limits and uniforms. */
+int rm_set_lighting(rm_ctx* ctx, const float* params, uint32_t count);
+/* rm_draw in every respect but the shading: rows, output (RM_OPT_OUTPUT_FORMAT), host / device destination, stream
+ * (RM_STREAM_OWN included) and ordering with the context's other work.  Errors are those of a scene query (program
+ * status, RM_ERR_RANGE for max_iter > 65536, RM_ERR_MATERIAL); like a query it never touches the draw state
+ * (RM_OPT_TIMING, RM_INFO_*, the specialised kernel, the tile buffers). */
+int rm_draw_lit(rm_ctx* ctx, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, float* out_rgba, int out_is_device,
+                void* stream);
+
 /* Waits for all work on the context's GPU (hipDeviceSynchronize). */
 int rm_sync(rm_ctx* ctx);
 /* HIP graphs: after its first draw of a given size and program (which allocates scratch buffers and compiles /

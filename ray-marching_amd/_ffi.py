@@ -47,6 +47,10 @@ RM_HIT_NONE, RM_HIT_SURFACE, RM_HIT_FLOOR = 0, 1, 2
 RM_SAMPLE_CENTER = 16
 # mesh export (rm_sample_grid / rm_extract_mesh / rm_read_mesh / rm_mesh_case_table)
 RM_MESH_NORMALS, RM_MESH_IDS = 1, 2
+# lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit): enum rm_light, the parameter names in index order
+RM_LIGHT_PARAMS = 13
+LIGHT_NAMES = ("pos_x", "pos_y", "pos_z", "shadow", "shadow_softness", "bias", "shadow_max_t", "shadow_steps", "ao", "ao_step",
+               "ao_falloff", "ao_scale", "ao_taps")
 
 _hip = None
 _host = None
@@ -142,6 +146,12 @@ def hip_lib():
         L.rm_read_mesh.restype = C.c_int
         L.rm_mesh_case_table.argtypes = [vp, u32]
         L.rm_mesh_case_table.restype = C.c_int
+        L.rm_lighting_defaults.argtypes = [f3, u32]
+        L.rm_lighting_defaults.restype = C.c_int
+        L.rm_set_lighting.argtypes = [vp, f3, u32]
+        L.rm_set_lighting.restype = C.c_int
+        L.rm_draw_lit.argtypes = [vp, u32, u32, u32, u32, vp, C.c_int, vp]
+        L.rm_draw_lit.restype = C.c_int
         sz = C.c_size_t
         L.rm_jit_source.argtypes = [u32, C.POINTER(u32), u32, C.c_int, C.c_char_p, sz, C.POINTER(sz)]
         L.rm_jit_source.restype = C.c_int

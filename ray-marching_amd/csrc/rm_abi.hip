@@ -22,6 +22,7 @@
 #include "rm_kernel_v5.h"
 #include "rm_query.h"
 #include "rm_mesh.h"
+#include "rm_light.h"
 
 #define RM_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -36,6 +37,9 @@ constexpr uint32_t kPruneLeaves = 12;  // RM_OPT_PRUNE = 2: programs that EVALUA
 
 constexpr uint32_t kBlendPruneLeaves = 8;  // ... and programs that blend, the rules of their chains (rm_units.h), from this many
 thread_local std::string g_create_error;
+// enum rm_light: P (wgsl:100), S, k, b, shadow max t, shadow steps, A, AO step, falloff, scale, taps
+#define RM_LIGHT_DEFAULTS {2.0f, -5.0f, 3.0f, 1.0f, 8.0f, 0.02f, 20.0f, 64.0f, 1.0f, 0.1f, 0.75f, 1.5f, 5.0f}
+const float kLightDefaults[RM_LIGHT_PARAMS] = RM_LIGHT_DEFAULTS;
 
 }  // namespace
 
@@ -84,6 +88,8 @@ struct rm_ctx {
     void* d_qout = nullptr;
     size_t d_qout_bytes = 0;
     size_t max_lds = 0;  // LDS a workgroup may allocate on this device
+    // lit rendering (rm_light.h): enum rm_light, validated by rm_set_lighting; travels with each lit draw as kernel arguments
+    float light[RM_LIGHT_PARAMS] = RM_LIGHT_DEFAULTS;
     // mesh export (rm_mesh.h): the extraction's scratch (distances, vertex bases, flags, block sums) and the last mesh
     void* d_mscratch = nullptr;
     size_t d_mscratch_bytes = 0;
@@ -1244,6 +1250,97 @@ RM_EXPORT int rm_camera_rays(rm_ctx* c, uint32_t W, uint32_t H, uint32_t x0, uin
     float* d = static_cast<float*>(c->d_qout);
     if (int rc = query_launch(c, rmk::rm_camera_rays_kernel, count, 0u, s, c->uniforms, W, H, x0, y0, w, count, sample, d)) return rc;
     HIP_TRY(c, hipMemcpyAsync(out_rays, d, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+// ---- lit rendering (rm_light.h) ------------------------------------------------------------------------------------------
+namespace {
+
+// The first parameter outside the table of enum rm_light (NaN and infinities are outside everywhere), or -1.
+int bad_light_param(const float* p) {
+    const auto integral = [](float v, float lo, float hi) { return v >= lo && v <= hi && v == std::floor(v); };
+    for (int i = 0; i < RM_LIGHT_PARAMS; i++)
+        if (!std::isfinite(p[i])) return i;
+    if (!(p[RM_LIGHT_SHADOW] >= 0.0f && p[RM_LIGHT_SHADOW] <= 1.0f)) return RM_LIGHT_SHADOW;
+    if (!(p[RM_LIGHT_SHADOW_SOFTNESS] > 0.0f)) return RM_LIGHT_SHADOW_SOFTNESS;
+    if (!(p[RM_LIGHT_BIAS] >= 0.0f)) return RM_LIGHT_BIAS;
+    if (!(p[RM_LIGHT_SHADOW_MAX_T] > 0.0f)) return RM_LIGHT_SHADOW_MAX_T;
+    if (!integral(p[RM_LIGHT_SHADOW_STEPS], 1.0f, 1024.0f)) return RM_LIGHT_SHADOW_STEPS;
+    if (!(p[RM_LIGHT_AO] >= 0.0f && p[RM_LIGHT_AO] <= 1.0f)) return RM_LIGHT_AO;
+    if (!(p[RM_LIGHT_AO_STEP] > 0.0f)) return RM_LIGHT_AO_STEP;
+    if (!(p[RM_LIGHT_AO_FALLOFF] > 0.0f && p[RM_LIGHT_AO_FALLOFF] <= 1.0f)) return RM_LIGHT_AO_FALLOFF;
+    if (!(p[RM_LIGHT_AO_SCALE] >= 0.0f)) return RM_LIGHT_AO_SCALE;
+    if (!integral(p[RM_LIGHT_AO_TAPS], 1.0f, 16.0f)) return RM_LIGHT_AO_TAPS;
+    return -1;
+}
+
+using LitFn = void (*)(rmk::QueryLaunch, rmk::LightLaunch, rmk::LitFrame);
+template <int LOOP>
+LitFn lit_kernel(bool shadow, bool ao) {
+    if (shadow) return ao ? rmk::rm_draw_lit_kernel<LOOP, true, true> : rmk::rm_draw_lit_kernel<LOOP, true, false>;
+    return ao ? rmk::rm_draw_lit_kernel<LOOP, false, true> : rmk::rm_draw_lit_kernel<LOOP, false, false>;
+}
+
+}  // namespace
+
+RM_EXPORT int rm_lighting_defaults(float* out, uint32_t n_out) {
+    if (!out) return RM_ERR_NULL;
+    if (n_out < (uint32_t)RM_LIGHT_PARAMS) return RM_ERR_ARG;
+    std::memcpy(out, kLightDefaults, sizeof kLightDefaults);
+    return RM_OK;
+}
+
+RM_EXPORT int rm_set_lighting(rm_ctx* c, const float* params, uint32_t count) {
+    if (!c) return RM_ERR_NULL;
+    if (!params) return fail(c, RM_ERR_NULL, "rm_set_lighting: params is NULL");
+    if (count != (uint32_t)RM_LIGHT_PARAMS) return fail(c, RM_ERR_ARG, "rm_set_lighting: %u parameters, not %d", count, (int)RM_LIGHT_PARAMS);
+    const int bad = bad_light_param(params);
+    if (bad >= 0) return fail(c, RM_ERR_RANGE, "rm_set_lighting: parameter %d = %g is outside its range (enum rm_light)", bad, (double)params[bad]);
+    std::memcpy(c->light, params, sizeof c->light);
+    return RM_OK;
+}
+
+RM_EXPORT int rm_draw_lit(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, float* out_rgba, int out_is_device,
+                          void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_rgba) return fail(c, RM_ERR_NULL, "rm_draw_lit: out_rgba is NULL");
+    int rc = check_dims(c, W, H, row0, rows);
+    if (rc != RM_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = out_is_device ? user_stream(c, stream) : c->stream;
+    order_with_previous(c, s);
+    rc = ensure_program(c, s);  // (query_begin repeats both at no cost)
+    if (rc != RM_OK) return rc;
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    // the leaf walk runs for the albedo of a tagged program
+    rc = query_begin(c, s, c->decoded.has_materials, true, &Q, &loop, &shmem);
+    if (rc != RM_OK) return rc;
+    const float* p = c->light;
+    rmk::LightLaunch P{p[RM_LIGHT_POS_X], p[RM_LIGHT_POS_Y], p[RM_LIGHT_POS_Z], p[RM_LIGHT_SHADOW], p[RM_LIGHT_SHADOW_SOFTNESS],
+                       p[RM_LIGHT_BIAS], p[RM_LIGHT_SHADOW_MAX_T], (uint32_t)p[RM_LIGHT_SHADOW_STEPS], p[RM_LIGHT_AO],
+                       p[RM_LIGHT_AO_STEP], p[RM_LIGHT_AO_FALLOFF], p[RM_LIGHT_AO_SCALE], (uint32_t)p[RM_LIGHT_AO_TAPS]};
+    const bool shadow = P.shadow > 0.0f, ao = P.ao > 0.0f;
+    const LitFn k = loop == rmk::Q_LOOP_CHAIN ? lit_kernel<rmk::Q_LOOP_CHAIN>(shadow, ao)
+                  : loop == rmk::Q_LOOP_TREE ? lit_kernel<rmk::Q_LOOP_TREE>(shadow, ao)
+                                             : lit_kernel<rmk::Q_LOOP_GENERAL>(shadow, ao);
+    rmk::LitFrame F;
+    F.u = c->uniforms;
+    F.W = W; F.H = H; F.row0 = row0; F.rows = rows;
+    F.format = (uint32_t)c->out_format;
+    const size_t lanes = (size_t)((W + 1u) / 2u) * ((rows + 1u) / 2u) * 64u;  // one wave per 2 x 2 block of pixels
+    if (out_is_device) {
+        F.out = out_rgba;
+        return query_launch(c, k, lanes, shmem, s, Q, P, F);
+    }
+    // host memory: staged through the context's query buffer (never the draws' scratch), synchronously on its own stream
+    const size_t bytes = (size_t)rows * W * pixel_bytes(c);
+    if ((rc = grow_bytes(c, &c->d_qout, &c->d_qout_bytes, bytes)) != RM_OK) return rc;
+    F.out = c->d_qout;
+    if ((rc = query_launch(c, k, lanes, shmem, s, Q, P, F)) != RM_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out_rgba, c->d_qout, bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     return RM_OK;
 }

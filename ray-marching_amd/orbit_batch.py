@@ -12,6 +12,8 @@ The reference has no offline mode (it only draws into an eframe window, main.rs:
 the north-star configuration asks for, built on the same rm_draw entry point the window path uses.
 
   python -m ray_marching_amd.orbit_batch --out-dir /tmp/orbit --frames 1024 --width 3840 --height 2160
+  python -m ray_marching_amd.orbit_batch --out-dir /tmp/orbit_lit --lit --shadow 1 --ao 1 --light 2 -5 3 ...    (soft shadows and
+                 ambient occlusion through rm_draw_lit; orbit.json records the lighting, an unlit job's manifest is unchanged)
   python -m torch.distributed.run --nproc-per-node 8 ... -m ray_marching_amd.orbit_batch ...    (one rank per GPU)
 """
 import argparse
@@ -115,6 +117,7 @@ def check_manifest(args):
     orbit.json, later runs refuse to mix parameters (a different frame count changes every camera)."""
     want = {"frames": args.frames, "width": args.width, "height": args.height, "scene": args.scene,
             "max_iter": args.max_iter, "format": args.format}
+    want.update(lighting_of(args) or {})      # lighting keys only for a lit job: an unlit directory resumes as before
     path = os.path.join(args.out_dir, "orbit.json")
     try:
         with open(path) as fh:
@@ -128,6 +131,13 @@ def check_manifest(args):
         os.replace(tmp, path)
     elif have != want:
         raise SystemExit("%s was written with %s; this run asks for %s" % (args.out_dir, have, want))
+
+
+def lighting_of(args):
+    """The manifest's lighting keys of a --lit job, None for an unlit one (whose manifest and frames stay as they were)."""
+    if not getattr(args, "lit", False):
+        return None
+    return {"lit": True, "shadow": float(args.shadow), "ao": float(args.ao), "light": [float(v) for v in args.light]}
 
 
 def orbit_yaw(f, n_frames):
@@ -157,6 +167,10 @@ def render_batch(args, rank=0, world=1, device=0, log=None):
     if len(words) > 255:
         res.resize_command_buffer(4 * (len(words) + 1 + 63) // 64 * 64)
     res.set_program(cc, words)
+    lit = lighting_of(args)
+    if lit:
+        res.set_lighting(pos=lit["light"], shadow=lit["shadow"], ao=lit["ao"])
+    draw = res.draw_lit_device if lit else res.draw_device
     f32 = args.format == "f32"
     res.set_output_format(_ffi.RM_FORMAT_RGBA32F if f32 else _ffi.RM_FORMAT_RGBA8_UNORM)
     dt = torch.float32 if f32 else torch.uint8
@@ -200,7 +214,7 @@ def render_batch(args, rank=0, world=1, device=0, log=None):
         ctl.set_angles(orbit_yaw(f, args.frames), -0.25, 5.0)
         res.set_uniforms(renderer.prepare_uniforms((float(W), float(H)), ctl.camera()))
         render_s.wait_event(copied[slot])          # dev[slot] was read by the copy n_slots frames ago
-        res.draw_device(W, H, dev[slot].data_ptr(), stream=render_s.cuda_stream)
+        draw(W, H, dev[slot].data_ptr(), stream=render_s.cuda_stream)
         rendered[slot].record(render_s)
         copy_s.wait_event(rendered[slot])
         with torch.cuda.stream(copy_s):
@@ -236,6 +250,11 @@ def parse(argv=None):
                    help="ppm / png: 8-bit output stage (png: zlib level 1, standard library only); f32: raw RGBA32F")
     p.add_argument("--slots", type=int, default=4, help="device / pinned-host buffer pairs in flight")
     p.add_argument("--writers", type=int, default=3, help="file-writer threads")
+    p.add_argument("--lit", action="store_true", help="soft shadows and ambient occlusion (rm_draw_lit; DESIGN.md section 13)")
+    p.add_argument("--shadow", type=float, default=1.0, metavar="S", help="with --lit: strength of the shadow term, 0..1")
+    p.add_argument("--ao", type=float, default=1.0, metavar="A", help="with --lit: strength of the occlusion term, 0..1")
+    p.add_argument("--light", type=float, nargs=3, default=[2.0, -5.0, 3.0], metavar=("X", "Y", "Z"),
+                   help="with --lit: the light's position parameter (the reference's: 2 -5 3)")
     p.add_argument("--all-ranks-on-device0", action="store_true", help="rehearsal on a one-GPU box: every rank renders on GPU 0")
     return p.parse_args(argv)
 

@@ -136,6 +136,38 @@ class RayMarchingResources:
         self._check(self._L.rm_draw_batch(self._h, arr, len(frames), W, H, C.c_void_p(out_ptr), 1,
                                           C.c_void_p(stream) if stream else None))
 
+    # -- lit rendering (rm_set_lighting / rm_draw_lit): soft shadows and ambient occlusion, DESIGN.md section 13 -------------
+    def set_lighting(self, **named):
+        """Sets the named lighting parameters (_ffi.LIGHT_NAMES; pos=(x, y, z) names the first three); the others keep
+        their current values.  A value outside its range raises RmError(RM_ERR_RANGE) and changes nothing."""
+        p = list(getattr(self, "_light", None) or lighting_defaults())
+        if "pos" in named:
+            p[0:3] = [float(v) for v in named.pop("pos")]
+        for k, v in named.items():
+            if k not in _ffi.LIGHT_NAMES:
+                raise ValueError("unknown lighting parameter %r (one of %s, or pos)" % (k, ", ".join(_ffi.LIGHT_NAMES)))
+            p[_ffi.LIGHT_NAMES.index(k)] = float(v)
+        arr = (C.c_float * _ffi.RM_LIGHT_PARAMS)(*p)
+        self._check(self._L.rm_set_lighting(self._h, arr, _ffi.RM_LIGHT_PARAMS))
+        self._light = [float(v) for v in arr]
+
+    def lighting(self):
+        """The context's lighting parameters as a dict (float32 values)."""
+        return dict(zip(_ffi.LIGHT_NAMES, getattr(self, "_light", None) or lighting_defaults()))
+
+    def draw_lit(self, W, H, row0=0, rows=None):
+        """draw() with shadows and ambient occlusion (rm_draw_lit): rows [row0,row0+rows) into a new host array."""
+        rows = H - row0 if rows is None else rows
+        out = np.empty((max(rows, 0), W, 4), dtype=self._dtype)
+        self._check(self._L.rm_draw_lit(self._h, W, H, row0, rows, out.ctypes.data_as(C.c_void_p), 0, None))
+        return out
+
+    def draw_lit_device(self, W, H, out_ptr, row0=0, rows=None, stream=None):
+        """draw_device() with shadows and ambient occlusion: asynchronous render into device memory."""
+        rows = H - row0 if rows is None else rows
+        self._check(self._L.rm_draw_lit(self._h, W, H, row0, rows, C.c_void_p(out_ptr), 1,
+                                        C.c_void_p(stream) if stream else None))
+
     def sync(self):
         self._check(self._L.rm_sync(self._h))
 
@@ -411,6 +443,15 @@ class RayMarchingCallback:
         W = int(self.viewport[0]) if width is None else width
         H = int(self.viewport[1]) if height is None else height
         return resources.draw(W, H)
+
+
+def lighting_defaults():
+    """rm_lighting_defaults: the 13 default lighting parameters in _ffi.LIGHT_NAMES order (pure host code, no GPU needed)."""
+    out = (C.c_float * _ffi.RM_LIGHT_PARAMS)()
+    rc = _ffi.hip_lib().rm_lighting_defaults(out, _ffi.RM_LIGHT_PARAMS)
+    if rc != _ffi.RM_OK:
+        raise _ffi.RmError(rc, _ffi.hip_lib().rm_status_string(rc).decode())
+    return [float(v) for v in out]
 
 
 def validate_program(cmd_count, words):
