@@ -133,6 +133,9 @@ pub const RM_HIT_SURFACE: c_int = 1;
 pub const RM_HIT_FLOOR: c_int = 2;
 // enum rm_sample
 pub const RM_SAMPLE_CENTER: c_int = 16;
+// enum rm_sampleset
+/// `rm_draw_gbuffer` only: all sixteen AA samples.
+pub const RM_SAMPLE_ALL: c_int = 17;
 
 // Mesh export (rm_sample_grid / rm_extract_mesh / rm_read_mesh / rm_mesh_case_table).
 // enum rm_mesh: flags of rm_extract_mesh
@@ -203,6 +206,11 @@ extern "C" {
     pub fn rm_set_lighting(ctx: *mut rm_ctx, params: *const f32, count: u32) -> c_int;
     pub fn rm_draw_lit(ctx: *mut rm_ctx, w: u32, h: u32, row0: u32, rows: u32, out_rgba: *mut f32, out_is_device: c_int,
                        stream: *mut c_void) -> c_int;
+    pub fn rm_draw_gbuffer(ctx: *mut rm_ctx, w: u32, h: u32, row0: u32, rows: u32, sample: u32, sel_first: u32, sel_count: u32,
+                           out_geom: *mut f32, out_ids: *mut u32, out_masks: *mut u32, is_device: c_int,
+                           stream: *mut c_void) -> c_int;
+    pub fn rm_program_subtree(cmd_count: u32, words: *const u32, n_words: u32, cmd_index: u32, out_first: *mut u32,
+                              out_count: *mut u32) -> c_int;
     pub fn rm_sync(ctx: *mut rm_ctx) -> c_int;
     pub fn rm_sync_context(ctx: *mut rm_ctx) -> c_int;
     pub fn rm_set_option(ctx: *mut rm_ctx, key: c_int, value: i64) -> c_int;
@@ -227,6 +235,16 @@ pub fn lighting_defaults() -> [f32; RM_LIGHT_PARAMS as usize] {
     let rc = unsafe { rm_lighting_defaults(out.as_mut_ptr(), RM_LIGHT_PARAMS as u32) };
     assert_eq!(rc, RM_OK);
     out
+}
+
+/// The selection of a graph node (`rm_program_subtree`; host code, no GPU needed): the range (first, count) of command
+/// indices that produce the value command `cmd_index` leaves on the stack, as `draw_gbuffer` takes it.  `Err(status)` for an
+/// invalid program (the validator's status) or an index past the end (`RM_ERR_RANGE`).
+pub fn program_subtree(cmd_count: u32, words: &[u32], cmd_index: u32) -> Result<(u32, u32), c_int> {
+    assert!(words.len() <= u32::MAX as usize);
+    let (mut first, mut count) = (0u32, 0u32);
+    let rc = unsafe { rm_program_subtree(cmd_count, words.as_ptr(), words.len() as u32, cmd_index, &mut first, &mut count) };
+    if rc == RM_OK { Ok((first, count)) } else { Err(rc) }
 }
 
 /// What the reference `unwrap()`s away (renderer.rs:24, 203, 250): a status code of `enum rm_status`
@@ -311,6 +329,26 @@ impl RayMarchingResources {
     pub fn draw_lit(&self, width: u32, height: u32, out_rgba: &mut [f32]) -> Result<(), RmError> {
         assert!(out_rgba.len() >= (width as usize) * (height as usize) * 4);
         self.check(unsafe { rm_draw_lit(self.ctx, width, height, 0, height, out_rgba.as_mut_ptr(), 0, std::ptr::null_mut()) })
+    }
+
+    /// The geometry behind rows `row0 .. row0 + rows` of a frame (host memory), per pixel: the hit
+    /// record of the nearest sample (`out_geom`, eight floats: t, position, normal, diffuse), its (kind, sample id, leaf,
+    /// material) (`out_ids`, four words) and (surface mask, floor mask, selected mask, summed steps) (`out_masks`, four
+    /// words).  `sample`: 0..15, `RM_SAMPLE_CENTER` or `RM_SAMPLE_ALL`; `select`: a (first, count) range of command indices
+    /// (`program_subtree`), (0, 0) for none.  `None` skips that output.
+    pub fn draw_gbuffer(&self, width: u32, height: u32, row0: u32, rows: u32, sample: u32, select: (u32, u32),
+                        out_geom: Option<&mut [f32]>, out_ids: Option<&mut [u32]>,
+                        out_masks: Option<&mut [u32]>) -> Result<(), RmError> {
+        let n = (width as usize) * (rows as usize);
+        assert!(out_geom.as_ref().map_or(true, |s| s.len() >= 8 * n), "draw_gbuffer: out_geom is shorter than {} pixels", n);
+        assert!(out_ids.as_ref().map_or(true, |s| s.len() >= 4 * n), "draw_gbuffer: out_ids is shorter than {} pixels", n);
+        assert!(out_masks.as_ref().map_or(true, |s| s.len() >= 4 * n), "draw_gbuffer: out_masks is shorter than {} pixels", n);
+        let geom = out_geom.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let ids = out_ids.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let masks = out_masks.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        self.check(unsafe {
+            rm_draw_gbuffer(self.ctx, width, height, row0, rows, sample, select.0, select.1, geom, ids, masks, 0, std::ptr::null_mut())
+        })
     }
 
     /// This GPU's interleaved strips of a frame tiled over `stride` GPUs (north-star layout), host destination.

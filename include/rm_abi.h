@@ -286,6 +286,9 @@ int rm_draw_batch(rm_ctx* ctx, const rm_uniforms* frames, uint32_t n_frames, uin
 #define RM_NO_ID 0xFFFFFFFFu /* no primitive (empty program, or a ray that hit no surface) */
 enum rm_hit { RM_HIT_NONE = 0, RM_HIT_SURFACE = 1, RM_HIT_FLOOR = 2 };
 enum rm_sample { RM_SAMPLE_CENTER = 16 }; /* rm_camera_rays: the ray through the pixel centre; 0..15 are fs_main's AA samples */
+/* A set of samples where rm_sample names one (rm_draw_gbuffer's `sample` takes either): all sixteen AA samples.  An enum of
+ * its own: rm_sample stays the list of values rm_camera_rays accepts. */
+enum rm_sampleset { RM_SAMPLE_ALL = 17 };
 /* Points.  xyz: n x 3.  out_dist: n, map_scene(p) (an empty program: limits.max_dist).  out_normal: n x 3, calculate_normal(p)
  * (wgsl:135-144) normalised as the shading does (NaN where the tap sum is zero).  out_ids: n x 2 (leaf, material); an empty
  * program gives (RM_NO_ID, 0). */
@@ -373,6 +376,35 @@ int rm_set_lighting(rm_ctx* ctx, const float* params, uint32_t count);
  * (RM_OPT_TIMING, RM_INFO_*, the specialised kernel, the tile buffers). */
 int rm_draw_lit(rm_ctx* ctx, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, float* out_rgba, int out_is_device,
                 void* stream);
+
+/* G-buffer draw (extension; DESIGN.md section 14 is the contract, to the last bit): the per-pixel geometry behind a frame.
+ * The record of sample s of a pixel is exactly what rm_cast_rays returns for the ray rm_camera_rays(sample = s) gives for
+ * that pixel; rm_draw_gbuffer generates the rays, marches them and reduces them per pixel in one kernel.
+ * sample: 0..15 (that AA sample), RM_SAMPLE_CENTER, or RM_SAMPLE_ALL (the sixteen AA samples); a sample's bit in the masks is
+ * its id (16 for the centre).  Each pixel of rows [row0, row0 + rows), row-major, receives
+ *   out_masks: 4 x u32 -- [0] samples with kind RM_HIT_SURFACE, [1] samples with kind RM_HIT_FLOOR, [2] surface samples whose
+ *              leaf lies in [sel_first, sel_first + sel_count), [3] the sum of the samples' steps (<= 2^20);
+ *   out_ids:   4 x u32 -- (kind, sample id, leaf, material) of the nearest sample: the one that minimises (t, sample id)
+ *              among the samples that hit a surface or the floor; (RM_HIT_NONE, RM_NO_ID, RM_NO_ID, RM_NO_ID) when none did;
+ *              on the floor leaf and material are RM_NO_ID;
+ *   out_geom:  8 x f32 -- that sample's hit record (t, x, y, z, nx, ny, nz, diffuse) as rm_cast_rays defines it; the miss
+ *              record (+inf and zeros) when no sample hit.
+ * Any output may be NULL (that work is skipped; what the others receive does not change); RM_ERR_NULL when all are.
+ * W * rows = 0 writes nothing.  is_device and stream as for rm_query_points (RM_STREAM_OWN included); device arrays need
+ * 16-byte alignment (RM_ERR_ARG).  Errors: the program's status, RM_ERR_RANGE for max_iter > 65536 or a row band outside the
+ * frame, RM_ERR_ARG for another `sample` or a selection that reaches past cmd_count.  sel_count = 0 selects nothing.
+ * RM_OPT_OUTPUT_FORMAT does not apply; like a query the call never touches the draw state (RM_OPT_TIMING, RM_INFO_*, the
+ * specialised kernel, the tile buffers). */
+int rm_draw_gbuffer(rm_ctx* ctx, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, uint32_t sample,
+                    uint32_t sel_first, uint32_t sel_count, float* out_geom, uint32_t* out_ids,
+                    uint32_t* out_masks, int is_device, void* stream);
+/* The selection of a graph node (pure host code, usable without a GPU): the contiguous range of command indices that
+ * produce the value command `cmd_index` leaves on the stack -- a primitive: itself; a binary operator: from the first
+ * command of its left operand through itself; a Material tag: from the first command of its child through itself; a
+ * transform Pop: its Push through itself; a transform Push: the range of its Pop.  The root gives [0, cmd_count).
+ * Errors: rm_validate_program's status for an invalid program, RM_ERR_RANGE for cmd_index >= cmd_count. */
+int rm_program_subtree(uint32_t cmd_count, const uint32_t* words, uint32_t n_words, uint32_t cmd_index,
+                       uint32_t* out_first, uint32_t* out_count);
 
 /* Waits for all work on the context's GPU (hipDeviceSynchronize). */
 int rm_sync(rm_ctx* ctx);

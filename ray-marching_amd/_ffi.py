@@ -45,6 +45,7 @@ RM_INFO_PRUNED, RM_INFO_INTERPRETER_LOOP, RM_INFO_JIT_FROM_CACHE = 9, 10, 11
 RM_NO_ID = 0xFFFFFFFF
 RM_HIT_NONE, RM_HIT_SURFACE, RM_HIT_FLOOR = 0, 1, 2
 RM_SAMPLE_CENTER = 16
+RM_SAMPLE_ALL = 17      # rm_draw_gbuffer only: all sixteen AA samples
 # mesh export (rm_sample_grid / rm_extract_mesh / rm_read_mesh / rm_mesh_case_table)
 RM_MESH_NORMALS, RM_MESH_IDS = 1, 2
 # lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit): enum rm_light, the parameter names in index order
@@ -152,6 +153,10 @@ def hip_lib():
         L.rm_set_lighting.restype = C.c_int
         L.rm_draw_lit.argtypes = [vp, u32, u32, u32, u32, vp, C.c_int, vp]
         L.rm_draw_lit.restype = C.c_int
+        L.rm_draw_gbuffer.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, vp, vp, vp, C.c_int, vp]
+        L.rm_draw_gbuffer.restype = C.c_int
+        L.rm_program_subtree.argtypes = [u32, C.POINTER(u32), u32, u32, C.POINTER(u32), C.POINTER(u32)]
+        L.rm_program_subtree.restype = C.c_int
         sz = C.c_size_t
         L.rm_jit_source.argtypes = [u32, C.POINTER(u32), u32, C.c_int, C.c_char_p, sz, C.POINTER(sz)]
         L.rm_jit_source.restype = C.c_int

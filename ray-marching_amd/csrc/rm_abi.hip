@@ -23,6 +23,7 @@
 #include "rm_query.h"
 #include "rm_mesh.h"
 #include "rm_light.h"
+#include "rm_gbuffer.h"
 
 #define RM_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -1341,6 +1342,115 @@ RM_EXPORT int rm_draw_lit(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, uint
     F.out = c->d_qout;
     if ((rc = query_launch(c, k, lanes, shmem, s, Q, P, F)) != RM_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(out_rgba, c->d_qout, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+// ---- G-buffer draw (rm_gbuffer.h) ----------------------------------------------------------------------------------------
+RM_EXPORT int rm_program_subtree(uint32_t cmd_count, const uint32_t* words, uint32_t n_words, uint32_t cmd_index,
+                                 uint32_t* out_first, uint32_t* out_count) {
+    RmDecoded d;
+    const int rc = rm_decode_program(cmd_count, words, n_words, &d);
+    if (rc != RM_OK) return rc;
+    if (cmd_index >= cmd_count) return RM_ERR_RANGE;
+    // the value stack of the (valid) program, holding for each value the first command of the sub-tree that produced it
+    std::vector<uint32_t> first, scopes;  // scopes: the command index of each open transform Push
+    uint32_t lo = 0u, hi = 0u, wanted_pop = cmd_index;  // cmd_index names a Push: answered at its Pop
+    bool found = false, at_pop = false;
+    for (uint32_t i = 0, q = 0; i < cmd_count && !found; i++) {
+        const uint32_t op = words[q];
+        q += 1u + (op == RM_CMD_SPHERE || op == RM_CMD_PLANE || op == RM_CMD_ROTATION_PUSH ? 4u : op == RM_CMD_BOX ? 6u
+                   : op == RM_CMD_CYLINDER ? 5u : op == RM_CMD_TRANSLATION_PUSH ? 3u
+                   : op == RM_CMD_SMOOTH_UNION || op == RM_CMD_SCALE_PUSH || op == RM_CMD_MATERIAL ? 1u : 0u);
+        uint32_t start;
+        if (op == RM_CMD_TRANSLATION_PUSH || op == RM_CMD_ROTATION_PUSH || op == RM_CMD_SCALE_PUSH) {
+            scopes.push_back(i);
+            if (i == cmd_index) at_pop = true;
+            continue;
+        } else if (op == RM_CMD_TRANSLATION_POP || op == RM_CMD_ROTATION_POP || op == RM_CMD_SCALE_POP) {
+            start = first.back() = scopes.back();  // the scope's value now spans Push .. Pop
+            scopes.pop_back();
+            if (at_pop && start == wanted_pop) found = true;
+        } else if (op == RM_CMD_MATERIAL) {
+            start = first.back();
+        } else if (op == RM_CMD_UNION || op == RM_CMD_SUBTRACTION || op == RM_CMD_INTERSECTION || op == RM_CMD_SMOOTH_UNION) {
+            first.pop_back();  // the right operand's; the left operand's first command stays: the result spans both
+            start = first.back();
+        } else {
+            first.push_back(i);
+            start = i;
+        }
+        if (i == cmd_index) found = true;
+        if (found) { lo = start; hi = i; }
+    }
+    if (!found) return RM_ERR_RANGE;  // (unreachable for a valid program: every Push has its Pop)
+    if (out_first) *out_first = lo;
+    if (out_count) *out_count = hi - lo + 1u;
+    return RM_OK;
+}
+
+namespace {
+using GBufferFn = void (*)(rmk::QueryLaunch, rmk::GBufferFrame);
+template <int LOOP>
+GBufferFn gbuffer_kernel(bool all) {
+    return all ? rmk::rm_draw_gbuffer_kernel<LOOP, true> : rmk::rm_draw_gbuffer_kernel<LOOP, false>;
+}
+}  // namespace
+
+RM_EXPORT int rm_draw_gbuffer(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, uint32_t sample, uint32_t sel_first,
+                              uint32_t sel_count, float* out_geom, uint32_t* out_ids, uint32_t* out_masks, int is_device,
+                              void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_geom && !out_ids && !out_masks) return fail(c, RM_ERR_NULL, "rm_draw_gbuffer: every output is NULL");
+    if ((uint64_t)W * rows == 0u) return RM_OK;
+    int rc = check_dims(c, W, H, row0, rows);
+    if (rc != RM_OK) return rc;
+    if (sample > (uint32_t)RM_SAMPLE_ALL)
+        return fail(c, RM_ERR_ARG, "rm_draw_gbuffer: sample %u: 0..15, RM_SAMPLE_CENTER (16) or RM_SAMPLE_ALL (17)", sample);
+    if (is_device && (misaligned(out_geom, 16) || misaligned(out_ids, 16) || misaligned(out_masks, 16)))
+        return fail(c, RM_ERR_ARG, "rm_draw_gbuffer: device arrays need 16-byte alignment");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    order_with_previous(c, s);
+    rc = ensure_program(c, s);  // (query_begin repeats both at no cost)
+    if (rc != RM_OK) return rc;
+    if ((uint64_t)sel_first + sel_count > c->cmd[0])
+        return fail(c, RM_ERR_ARG, "rm_draw_gbuffer: selection [%u,+%u) reaches past the program's %u commands", sel_first, sel_count, c->cmd[0]);
+    // the leaf walk runs for the ids, and for the selected mask of a selection that is not empty
+    const bool walk = out_ids != nullptr || (out_masks != nullptr && sel_count != 0u);
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    rc = query_begin(c, s, walk, false, &Q, &loop, &shmem);
+    if (rc != RM_OK) return rc;
+    const bool all = sample == (uint32_t)RM_SAMPLE_ALL;
+    const GBufferFn k = loop == rmk::Q_LOOP_CHAIN ? gbuffer_kernel<rmk::Q_LOOP_CHAIN>(all)
+                      : loop == rmk::Q_LOOP_TREE ? gbuffer_kernel<rmk::Q_LOOP_TREE>(all)
+                                                 : gbuffer_kernel<rmk::Q_LOOP_GENERAL>(all);
+    rmk::GBufferFrame F;
+    F.u = c->uniforms;
+    F.W = W; F.H = H; F.row0 = row0; F.rows = rows;
+    F.sample = sample;
+    F.sel_first = sel_first; F.sel_count = sel_count;
+    F.taps = out_geom != nullptr ? 1u : 0u;
+    F.walk = walk ? 1u : 0u;
+    // one wave per 2 x 2 block of pixels (all samples), or per 8 x 8 tile (one sample)
+    const size_t lanes = all ? (size_t)((W + 1u) / 2u) * ((rows + 1u) / 2u) * 64u : (size_t)((W + 7u) / 8u) * ((rows + 7u) / 8u) * 64u;
+    if (is_device) {
+        F.geom = out_geom; F.ids = out_ids; F.masks = out_masks;
+        return query_launch(c, k, lanes, shmem, s, Q, F);
+    }
+    // host memory: staged through the context's query buffer (never the draws' scratch), synchronously on its own stream
+    const size_t n = (size_t)rows * W, geom_b = out_geom ? n * 32u : 0u, ids_b = out_ids ? n * 16u : 0u, masks_b = out_masks ? n * 16u : 0u;
+    if ((rc = grow_bytes(c, &c->d_qout, &c->d_qout_bytes, geom_b + ids_b + masks_b)) != RM_OK) return rc;
+    char* o = static_cast<char*>(c->d_qout);
+    F.geom = out_geom ? reinterpret_cast<float*>(o) : nullptr;
+    F.ids = out_ids ? reinterpret_cast<uint32_t*>(o + geom_b) : nullptr;
+    F.masks = out_masks ? reinterpret_cast<uint32_t*>(o + geom_b + ids_b) : nullptr;
+    if ((rc = query_launch(c, k, lanes, shmem, s, Q, F)) != RM_OK) return rc;
+    if (out_geom) HIP_TRY(c, hipMemcpyAsync(out_geom, F.geom, geom_b, hipMemcpyDeviceToHost, s));
+    if (out_ids) HIP_TRY(c, hipMemcpyAsync(out_ids, F.ids, ids_b, hipMemcpyDeviceToHost, s));
+    if (out_masks) HIP_TRY(c, hipMemcpyAsync(out_masks, F.masks, masks_b, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     return RM_OK;
 }

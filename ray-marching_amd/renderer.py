@@ -168,6 +168,39 @@ class RayMarchingResources:
         self._check(self._L.rm_draw_lit(self._h, W, H, row0, rows, C.c_void_p(out_ptr), 1,
                                         C.c_void_p(stream) if stream else None))
 
+    # -- G-buffer draw (rm_draw_gbuffer): per-pixel depth, normals, ids and selection masks, DESIGN.md section 14 -----------
+    GBUFFER_KEYS = ("t", "position", "normal", "diffuse", "kind", "sample", "leaf", "material", "surface_mask", "floor_mask",
+                    "selected_mask", "steps")
+
+    def draw_gbuffer(self, W, H, row0=0, rows=None, sample=_ffi.RM_SAMPLE_ALL, select=None):
+        """The geometry behind rows [row0,row0+rows) of a W x H frame, per pixel (rm_draw_gbuffer).  sample: 0..15,
+        RM_SAMPLE_CENTER, or RM_SAMPLE_ALL (the sixteen AA samples).  select: (first, count), a range of command indices
+        (program_subtree gives a node's).  Returns a dict of host arrays of shape (rows, W[, 3]): t, position, normal,
+        diffuse (the hit record of the nearest sample), kind (RM_HIT_*), sample, leaf, material (of that sample; RM_NO_ID
+        where there is none), surface_mask, floor_mask, selected_mask (one bit per sample) and steps (summed over the
+        samples)."""
+        rows = H - row0 if rows is None else rows
+        first, count = (0, 0) if select is None else (int(select[0]), int(select[1]))
+        shape = (max(rows, 0), W)
+        geom = np.empty(shape + (8,), dtype=np.float32)
+        ids = np.empty(shape + (4,), dtype=np.uint32)
+        masks = np.empty(shape + (4,), dtype=np.uint32)
+        self._check(self._L.rm_draw_gbuffer(self._h, W, H, row0, rows, sample, first, count, geom.ctypes.data_as(C.c_void_p),
+                                            ids.ctypes.data_as(C.c_void_p), masks.ctypes.data_as(C.c_void_p), 0, None))
+        return {"t": geom[..., 0], "position": geom[..., 1:4], "normal": geom[..., 4:7], "diffuse": geom[..., 7],
+                "kind": ids[..., 0], "sample": ids[..., 1], "leaf": ids[..., 2], "material": ids[..., 3],
+                "surface_mask": masks[..., 0], "floor_mask": masks[..., 1], "selected_mask": masks[..., 2], "steps": masks[..., 3]}
+
+    def draw_gbuffer_device(self, W, H, geom_ptr=0, ids_ptr=0, masks_ptr=0, row0=0, rows=None, sample=_ffi.RM_SAMPLE_ALL,
+                            select=None, stream=None):
+        """rm_draw_gbuffer on device memory (integer addresses, 16-byte aligned; 0 = not wanted), asynchronous on `stream`:
+        per pixel 8 floats at geom_ptr, 4 u32 at ids_ptr, 4 u32 at masks_ptr."""
+        rows = H - row0 if rows is None else rows
+        first, count = (0, 0) if select is None else (int(select[0]), int(select[1]))
+        self._check(self._L.rm_draw_gbuffer(self._h, W, H, row0, rows, sample, first, count, C.c_void_p(geom_ptr or None),
+                                            C.c_void_p(ids_ptr or None), C.c_void_p(masks_ptr or None), 1,
+                                            C.c_void_p(stream) if stream else None))
+
     def sync(self):
         self._check(self._L.rm_sync(self._h))
 
@@ -461,6 +494,34 @@ def validate_program(cmd_count, words):
     ptr = w.ctypes.data_as(C.POINTER(C.c_uint32)) if w.size else None
     rc = _ffi.hip_lib().rm_validate_program(int(cmd_count), ptr, int(w.size), C.byref(depth))
     return rc, depth.value
+
+
+def program_subtree(cmd_count, words, index):
+    """rm_program_subtree: (first, count), the range of command indices that produce the value command `index` leaves on
+    the stack -- the selection of that graph node for draw_gbuffer (pure host code, no GPU needed)."""
+    w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32))
+    ptr = w.ctypes.data_as(C.POINTER(C.c_uint32)) if w.size else None
+    first, count = C.c_uint32(0), C.c_uint32(0)
+    rc = _ffi.hip_lib().rm_program_subtree(int(cmd_count), ptr, int(w.size), int(index), C.byref(first), C.byref(count))
+    if rc != _ffi.RM_OK:
+        raise _ffi.RmError(rc, _ffi.hip_lib().rm_status_string(rc).decode())
+    return first.value, count.value
+
+
+def selection_overlay(image, selected_mask, n_samples, colour, alpha=0.5):
+    """Highlights a selection (pure numpy): blends `colour` (r, g, b) into a copy of the RGBA32F `image` (rows, W, 4) by
+    alpha * popcount(selected_mask) / n_samples per pixel, i.e. with the image's own anti-aliasing at the selection's edge.
+    selected_mask: draw_gbuffer's, of the same rows; n_samples: 16 for RM_SAMPLE_ALL, 1 for a single sample."""
+    img = np.array(image, dtype=np.float32, copy=True)
+    m = np.asarray(selected_mask).astype(np.uint32)
+    if img.ndim != 3 or img.shape[2] != 4 or m.shape != img.shape[:2]:
+        raise ValueError("image must be (rows, W, 4) and selected_mask (rows, W)")
+    bits = np.zeros(m.shape, dtype=np.float32)
+    for b in range(17):   # sample ids 0..16
+        bits += ((m >> np.uint32(b)) & np.uint32(1)).astype(np.float32)
+    cover = (np.float32(alpha) * bits / np.float32(n_samples))[..., None]
+    img[..., :3] = img[..., :3] * (np.float32(1.0) - cover) + np.asarray(colour, dtype=np.float32)[:3] * cover
+    return img
 
 
 PROGRAM_FACTS = ("records", "cones", "slabs", "subtracted_leaves", "groups", "spill_depth", "is_chain", "prunable", "bound_walk",
