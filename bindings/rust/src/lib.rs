@@ -141,6 +141,14 @@ pub const RM_SAMPLE_ALL: c_int = 17;
 // enum rm_mesh: flags of rm_extract_mesh
 pub const RM_MESH_NORMALS: c_int = 1;
 pub const RM_MESH_IDS: c_int = 2;
+// enum rm_meshstat: indices into the statistics of rm_extract_mesh_sparse; RM_MESH_STATS is their number
+pub const RM_MESH_STAT_VERTICES: c_int = 0;
+pub const RM_MESH_STAT_TRIANGLES: c_int = 1;
+pub const RM_MESH_STAT_BRICKS: c_int = 2;
+pub const RM_MESH_STAT_BRICKS_KEPT: c_int = 3;
+pub const RM_MESH_STAT_EVALUATIONS: c_int = 4;
+pub const RM_MESH_STAT_SCRATCH_BYTES: c_int = 5;
+pub const RM_MESH_STATS: c_int = 6;
 
 // Lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit).
 // enum rm_light: indices into the parameter array; RM_LIGHT_PARAMS is its length
@@ -202,6 +210,9 @@ extern "C" {
     pub fn rm_read_mesh(ctx: *mut rm_ctx, out_vertices: *mut f32, out_triangles: *mut u32, out_normals: *mut f32,
                         out_ids: *mut u32, is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_mesh_case_table(out: *mut u32, n_out: u32) -> c_int;
+    pub fn rm_extract_mesh_sparse(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, level: f32,
+                                  flags: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_program_lipschitz(cmd_count: u32, words: *const u32, n_words: u32, out_l: *mut f64) -> c_int;
     pub fn rm_lighting_defaults(out: *mut f32, n_out: u32) -> c_int;
     pub fn rm_set_lighting(ctx: *mut rm_ctx, params: *const f32, count: u32) -> c_int;
     pub fn rm_draw_lit(ctx: *mut rm_ctx, w: u32, h: u32, row0: u32, rows: u32, out_rgba: *mut f32, out_is_device: c_int,
@@ -245,6 +256,16 @@ pub fn program_subtree(cmd_count: u32, words: &[u32], cmd_index: u32) -> Result<
     let (mut first, mut count) = (0u32, 0u32);
     let rc = unsafe { rm_program_subtree(cmd_count, words.as_ptr(), words.len() as u32, cmd_index, &mut first, &mut count) };
     if rc == RM_OK { Ok((first, count)) } else { Err(rc) }
+}
+
+/// A Lipschitz bound of a program's `map_scene` in real arithmetic (`rm_program_lipschitz`; host code, no GPU needed):
+/// `f64::INFINITY` when the program has none (a parameter that is not finite, a Scale of 0).  `Err(status)` for an invalid
+/// program.
+pub fn program_lipschitz(cmd_count: u32, words: &[u32]) -> Result<f64, c_int> {
+    assert!(words.len() <= u32::MAX as usize);
+    let mut l = 0.0f64;
+    let rc = unsafe { rm_program_lipschitz(cmd_count, words.as_ptr(), words.len() as u32, &mut l) };
+    if rc == RM_OK { Ok(l) } else { Err(rc) }
 }
 
 /// What the reference `unwrap()`s away (renderer.rs:24, 203, 250): a status code of `enum rm_status`
@@ -440,6 +461,22 @@ impl RayMarchingResources {
         })?;
         self.mesh.set(Some((counts[0], counts[1])));
         Ok((counts[0], counts[1]))
+    }
+
+    /// `extract_mesh` brick by brick (`rm_extract_mesh_sparse`): the same mesh bit for bit, evaluated only where the
+    /// surface can be, with no limit on the number of lattice points.  Fills `out_stats` (at least `RM_MESH_STATS`
+    /// entries, indexed by `RM_MESH_STAT_*`) and returns (vertices, triangles); `read_mesh` copies the mesh out.
+    pub fn extract_mesh_sparse(&self, origin: [f32; 3], step: [f32; 3], nx: u32, ny: u32, nz: u32, level: f32, flags: u32,
+                               out_stats: &mut [u64]) -> Result<(u64, u64), RmError> {
+        assert!(out_stats.len() >= RM_MESH_STATS as usize, "extract_mesh_sparse: out_stats is shorter than RM_MESH_STATS entries");
+        self.mesh.set(None);  // a failed extraction may have released the previous mesh
+        self.check(unsafe {
+            rm_extract_mesh_sparse(self.ctx, origin.as_ptr(), step.as_ptr(), nx, ny, nz, level, flags, out_stats.as_mut_ptr(),
+                                   RM_MESH_STATS as u32)
+        })?;
+        let counts = (out_stats[RM_MESH_STAT_VERTICES as usize], out_stats[RM_MESH_STAT_TRIANGLES as usize]);
+        self.mesh.set(Some(counts));
+        Ok(counts)
     }
 
     /// The mesh of the last successful `extract_mesh` (of the (vertices, triangles) it returned): positions (three per

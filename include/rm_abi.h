@@ -343,6 +343,31 @@ int rm_read_mesh(rm_ctx* ctx, float* out_vertices, uint32_t* out_triangles, floa
  * with 0 on it to the one with 1, bit 0 / bit 1 of e & 3 its offset on the lower / higher other axis.  RM_ERR_ARG when
  * n_out < 4096. */
 int rm_mesh_case_table(uint32_t* out, uint32_t n_out);
+/* Sparse extraction: the mesh of rm_extract_mesh -- the same vertices bit for bit, the same
+ * triangles, the same order, the same attributes -- computed only where the surface can be.  The lattice is cut into bricks
+ * of 8 x 8 x 8 points; one map_scene probe per brick and a Lipschitz bound of the program (rm_program_lipschitz) prove for
+ * most bricks that none of their edges crosses `level`, and only the others are evaluated.  Skipping never changes an
+ * output bit, only the statistics.  Lattice: 2..65536 points per axis and no limit on the product (beyond 2^28 points the
+ * rule of rm_extract_mesh defines the mesh with 64-bit linear indices).  out_stats[RM_MESH_STAT_*]:
+ *   VERTICES, TRIANGLES   of the mesh (what rm_extract_mesh returns in out_counts)
+ *   BRICKS, BRICKS_KEPT   bricks of the lattice, and those that were evaluated
+ *   EVALUATIONS           map_scene evaluations at brick probes and lattice points (not the attribute queries)
+ *   SCRATCH_BYTES         device memory the call used besides the arrays rm_read_mesh returns
+ * The result replaces the context's mesh like rm_extract_mesh's (rm_read_mesh reads the last extraction of either kind);
+ * synchronous on the context's own stream, ordered after its earlier work; never touches the draw state.
+ * Errors: those of rm_extract_mesh; RM_ERR_NULL for a NULL out_stats, RM_ERR_ARG for n_stats < RM_MESH_STATS, RM_ERR_RANGE
+ * when vertices or triangles would not fit a 32-bit index, RM_ERR_DEVICE when device memory runs out. */
+enum rm_meshstat { RM_MESH_STAT_VERTICES = 0, RM_MESH_STAT_TRIANGLES = 1, RM_MESH_STAT_BRICKS = 2,
+                    RM_MESH_STAT_BRICKS_KEPT = 3, RM_MESH_STAT_EVALUATIONS = 4, RM_MESH_STAT_SCRATCH_BYTES = 5,
+                    RM_MESH_STATS = 6 };
+int rm_extract_mesh_sparse(rm_ctx* ctx, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
+                           float level, uint32_t flags, uint64_t* out_stats, uint32_t n_stats);
+/* A Lipschitz bound of the program's map_scene in real arithmetic (host code; no context):
+ * |map_scene(p) - map_scene(q)| <= L |p - q| for all p, q.  Sphere, Box, Cylinder 1; Plane |n|; the operators the maximum
+ * of their operands; Translation and Scale unchanged; Rotation (w, a) times max(1, sqrt((1 - 2|a|^2)^2 + 4 w^2 |a|^2)), which
+ * is 1 for a unit quaternion.  The empty program: 0.  +infinity when there is no bound: a parameter that is not finite, or
+ * a Scale of 0.  Errors: rm_validate_program's status for an invalid program, RM_ERR_NULL for a NULL out_L. */
+int rm_program_lipschitz(uint32_t cmd_count, const uint32_t* words, uint32_t n_words, double* out_L);
 
 /* Lit rendering (extension): rm_draw with soft shadows and ambient occlusion marched through the same distance field
  * (DESIGN.md section 13 is the contract, to the last bit).  The reference has one fixed light and max(0.02, n.l)

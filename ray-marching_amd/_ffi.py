@@ -48,6 +48,10 @@ RM_SAMPLE_CENTER = 16
 RM_SAMPLE_ALL = 17      # rm_draw_gbuffer only: all sixteen AA samples
 # mesh export (rm_sample_grid / rm_extract_mesh / rm_read_mesh / rm_mesh_case_table)
 RM_MESH_NORMALS, RM_MESH_IDS = 1, 2
+# enum rm_meshstat: out_stats of rm_extract_mesh_sparse
+(RM_MESH_STAT_VERTICES, RM_MESH_STAT_TRIANGLES, RM_MESH_STAT_BRICKS, RM_MESH_STAT_BRICKS_KEPT, RM_MESH_STAT_EVALUATIONS,
+ RM_MESH_STAT_SCRATCH_BYTES, RM_MESH_STATS) = range(7)
+MESH_STAT_NAMES = ("vertices", "triangles", "bricks", "bricks_kept", "evaluations", "scratch_bytes")
 # lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit): enum rm_light, the parameter names in index order
 RM_LIGHT_PARAMS = 13
 LIGHT_NAMES = ("pos_x", "pos_y", "pos_z", "shadow", "shadow_softness", "bias", "shadow_max_t", "shadow_steps", "ao", "ao_step",
@@ -147,6 +151,10 @@ def hip_lib():
         L.rm_read_mesh.restype = C.c_int
         L.rm_mesh_case_table.argtypes = [vp, u32]
         L.rm_mesh_case_table.restype = C.c_int
+        L.rm_extract_mesh_sparse.argtypes = [vp, f3, f3, u32, u32, u32, C.c_float, u32, C.POINTER(u64), u32]
+        L.rm_extract_mesh_sparse.restype = C.c_int
+        L.rm_program_lipschitz.argtypes = [u32, C.POINTER(u32), u32, C.POINTER(C.c_double)]
+        L.rm_program_lipschitz.restype = C.c_int
         L.rm_lighting_defaults.argtypes = [f3, u32]
         L.rm_lighting_defaults.restype = C.c_int
         L.rm_set_lighting.argtypes = [vp, f3, u32]

@@ -22,6 +22,8 @@
 #include "rm_kernel_v5.h"
 #include "rm_query.h"
 #include "rm_mesh.h"
+#include "rm_mesh_bound.h"
+#include "rm_mesh_sparse.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
 
@@ -94,6 +96,8 @@ struct rm_ctx {
     // mesh export (rm_mesh.h): the extraction's scratch (distances, vertex bases, flags, block sums) and the last mesh
     void* d_mscratch = nullptr;
     size_t d_mscratch_bytes = 0;
+    void* d_mbricks = nullptr;  // sparse extraction (rm_mesh_sparse.h): the per-brick tables; d_mscratch holds the kept bricks' data
+    size_t d_mbricks_bytes = 0;
     void* d_mesh = nullptr;
     size_t d_mesh_bytes = 0;
     bool mesh_valid = false;
@@ -758,6 +762,7 @@ RM_EXPORT void rm_destroy(rm_ctx* c) {
     if (c->d_qin) (void)hipFree(c->d_qin);
     if (c->d_qout) (void)hipFree(c->d_qout);
     if (c->d_mscratch) (void)hipFree(c->d_mscratch);
+    if (c->d_mbricks) (void)hipFree(c->d_mbricks);
     if (c->d_mesh) (void)hipFree(c->d_mesh);
     for (auto& st : c->staging) {
         if (st.host) (void)hipHostFree(st.host);
@@ -1496,6 +1501,35 @@ MeshLayout mesh_layout(uint64_t v, uint64_t t, uint32_t flags) {
     return L;
 }
 
+
+// The attributes of a mesh's vertices: rm_query_points at the vertex positions, device to device.
+int mesh_attributes(rm_ctx* c, const rmk::QueryLaunch& Q, int loop, size_t shmem, hipStream_t s, uint32_t flags, uint64_t V, char* m,
+                    const MeshLayout& L) {
+    const bool normals = (flags & RM_MESH_NORMALS) != 0, ids = (flags & RM_MESH_IDS) != 0;
+    if (!(normals || ids) || V == 0u) return RM_OK;
+    float* nrm = normals ? reinterpret_cast<float*>(m + L.normals) : nullptr;
+    uint32_t* idp = ids ? reinterpret_cast<uint32_t*>(m + L.ids) : nullptr;
+    const PointsFn k = loop == rmk::Q_LOOP_CHAIN ? points_kernel<rmk::Q_LOOP_CHAIN>(false, normals, ids)
+                     : loop == rmk::Q_LOOP_TREE ? points_kernel<rmk::Q_LOOP_TREE>(false, normals, ids)
+                                                : points_kernel<rmk::Q_LOOP_GENERAL>(false, normals, ids);
+    return query_launch(c, k, V, shmem, s, Q, (uint32_t)V, reinterpret_cast<const float*>(m + L.vertices), static_cast<float*>(nullptr), nrm,
+                        idp);
+}
+
+// ---- sparse extraction (rm_mesh_sparse.h) ----
+using ProbeFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, double, double, uint32_t*, unsigned long long*);
+using SparseCountFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, const uint32_t*, const uint32_t*, float*, rmk::SparseSegMap*,
+                               uint32_t*, unsigned long long*);
+// One workgroup of `kernel` per grid entry, with the query's LDS columns behind the kernel's own LDS.
+template <class K, class... Args>
+int sparse_launch(rm_ctx* c, K kernel, uint32_t blocks, size_t shmem, hipStream_t s, Args... args) {
+    if (shmem + 4096u > 64u * 1024u)
+        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), shmem, s, args...);
+    HIP_TRY(c, hipGetLastError());
+    return RM_OK;
+}
+
 }  // namespace
 
 RM_EXPORT int rm_sample_grid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
@@ -1535,11 +1569,10 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
         return fail(c, RM_ERR_RANGE, "rm_extract_mesh: lattice %ux%ux%u: 2..65536 points per axis, at most 2^28 in all", nx, ny, nz);
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = c->stream;
-    const bool normals = (flags & RM_MESH_NORMALS) != 0, ids = (flags & RM_MESH_IDS) != 0;
     rmk::QueryLaunch Q;
     int loop = 0;
     size_t shmem = 0;
-    int rc = query_begin(c, s, ids, false, &Q, &loop, &shmem);  // after a device read of the previous mesh, too
+    int rc = query_begin(c, s, (flags & RM_MESH_IDS) != 0, false, &Q, &loop, &shmem);  // after a device read of the previous mesh, too
     if (rc != RM_OK) return rc;
     c->mesh_valid = false;  // its buffers change from here on
     // scratch: distances, vertex bases (4 B per point each), flags (1 B), block sums (8 B per 2048 points), the two totals
@@ -1574,16 +1607,7 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
             hipLaunchKernelGGL(rmk::rm_mesh_triangle_kernel, dim3(nb), dim3(256), 0, s, g, offs, static_cast<const uint32_t*>(vbase),
                                static_cast<const uint8_t*>(fl), reinterpret_cast<uint32_t*>(m + L.triangles));
         HIP_TRY(c, hipGetLastError());
-        if (normals || ids) {  // the attributes: rm_query_points at the vertices, device to device
-            float* nrm = normals ? reinterpret_cast<float*>(m + L.normals) : nullptr;
-            uint32_t* idp = ids ? reinterpret_cast<uint32_t*>(m + L.ids) : nullptr;
-            const PointsFn k = loop == rmk::Q_LOOP_CHAIN ? points_kernel<rmk::Q_LOOP_CHAIN>(false, normals, ids)
-                             : loop == rmk::Q_LOOP_TREE ? points_kernel<rmk::Q_LOOP_TREE>(false, normals, ids)
-                                                        : points_kernel<rmk::Q_LOOP_GENERAL>(false, normals, ids);
-            if ((rc = query_launch(c, k, V, shmem, s, Q, (uint32_t)V, static_cast<const float*>(verts), static_cast<float*>(nullptr),
-                                   nrm, idp)) != RM_OK)
-                return rc;
-        }
+        if ((rc = mesh_attributes(c, Q, loop, shmem, s, flags, V, m, L)) != RM_OK) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     c->mesh_valid = true;
@@ -1592,6 +1616,141 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
     c->mesh_flags = flags;
     out_counts[0] = V;
     out_counts[1] = T;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_program_lipschitz(uint32_t cmd_count, const uint32_t* words, uint32_t n_words, double* out_L) {
+    if (!out_L) return RM_ERR_NULL;
+    RmProgramBound b;
+    const int rc = rm_program_bound(cmd_count, words, n_words, 1.0, &b);
+    if (rc != RM_OK) return rc;
+    *out_L = b.L;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
+                                     float level, uint32_t flags, uint64_t* out_stats, uint32_t n_stats) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_stats) return fail(c, RM_ERR_NULL, "rm_extract_mesh_sparse: out_stats is NULL");
+    if (n_stats < (uint32_t)RM_MESH_STATS) return fail(c, RM_ERR_ARG, "rm_extract_mesh_sparse: n_stats %u < RM_MESH_STATS", n_stats);
+    if (int rc = check_lattice(c, "rm_extract_mesh_sparse", origin, step)) return rc;
+    if (!std::isfinite(level)) return fail(c, RM_ERR_ARG, "rm_extract_mesh_sparse: level %g is not finite", (double)level);
+    if (flags & ~(uint32_t)(RM_MESH_NORMALS | RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_extract_mesh_sparse: unknown flags 0x%x", flags);
+    if (nx < 2 || ny < 2 || nz < 2 || nx > kMaxDim || ny > kMaxDim || nz > kMaxDim)
+        return fail(c, RM_ERR_RANGE, "rm_extract_mesh_sparse: lattice %ux%ux%u: 2..65536 points per axis", nx, ny, nz);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    int rc = query_begin(c, s, (flags & RM_MESH_IDS) != 0, false, &Q, &loop, &shmem);  // after a device read of the previous mesh, too
+    if (rc != RM_OK) return rc;
+    if (shmem + 4096u > std::max<size_t>(c->max_lds, 64u * 1024u))
+        return fail(c, RM_ERR_TOO_LARGE, "rm_extract_mesh_sparse: the program needs %zu bytes of LDS per workgroup", shmem + 4096u);
+    c->mesh_valid = false;  // its buffers change from here on
+    // the bounds of the program, for points up to the lattice's largest coordinate (as the kernels compute it)
+    double P = 0.0;
+    const uint32_t dims[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; a++) {
+        const float last = origin[a] + (float)(dims[a] - 1u) * step[a];
+        P = std::fmax(P, std::fmax(std::fabs((double)origin[a]), std::fabs((double)last)));
+    }
+    RmProgramBound bound;
+    if ((rc = rm_program_bound(c->cmd[0], c->cmd.data() + 1, (uint32_t)c->cmd.size() - 1u, P, &bound)) != RM_OK) return rc;
+    rmk::SparseGrid g{origin[0], origin[1], origin[2], step[0], step[1], step[2], nx, ny, nz,
+                      (nx + rmk::kBrick - 1u) / rmk::kBrick, (ny + rmk::kBrick - 1u) / rmk::kBrick, (nz + rmk::kBrick - 1u) / rmk::kBrick, 0u};
+    const uint64_t nb64 = (uint64_t)g.bx * g.by * g.bz;
+    if (nb64 >= 0xFFFFFFFFull - 256u)
+        return fail(c, RM_ERR_DEVICE, "rm_extract_mesh_sparse: %llu bricks: the brick table is limited to 2^32 entries", (unsigned long long)nb64);
+    g.nb = (uint32_t)nb64;
+    // per brick: 4 B (keep flag, then the kept bricks before it); per 256 bricks a block sum; totals and the evaluation count
+    const uint32_t n_entries = g.nb + 1u, n_pblocks = (n_entries + 255u) / 256u;
+    const size_t boff_o = 0, psums_o = align16((size_t)n_entries * 4u), ptot_o = psums_o + align16((size_t)n_pblocks * 8u), evals_o = ptot_o + 16u;
+    const size_t bricks_bytes = evals_o + 16u;
+    if ((rc = grow_bytes(c, &c->d_mbricks, &c->d_mbricks_bytes, bricks_bytes)) != RM_OK) return rc;
+    char* bs = static_cast<char*>(c->d_mbricks);
+    uint32_t* boff = reinterpret_cast<uint32_t*>(bs + boff_o);
+    unsigned long long* psums = reinterpret_cast<unsigned long long*>(bs + psums_o);
+    unsigned long long* ptot = reinterpret_cast<unsigned long long*>(bs + ptot_o);
+    unsigned long long* evals = reinterpret_cast<unsigned long long*>(bs + evals_o);
+    HIP_TRY(c, hipMemsetAsync(evals, 0, 8, s));
+    const ProbeFn probe = loop == rmk::Q_LOOP_CHAIN ? rmk::rm_sparse_probe_kernel<rmk::Q_LOOP_CHAIN>
+                        : loop == rmk::Q_LOOP_TREE ? rmk::rm_sparse_probe_kernel<rmk::Q_LOOP_TREE>
+                                                   : rmk::rm_sparse_probe_kernel<rmk::Q_LOOP_GENERAL>;
+    if ((rc = sparse_launch(c, probe, n_pblocks, shmem, s, Q, g, level, bound.L, 2.0 * bound.E, boff, psums)) != RM_OK) return rc;
+    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, psums, n_pblocks, ptot);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long tot[2] = {0ull, 0ull};
+    HIP_TRY(c, hipMemcpyAsync(tot, ptot, sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const uint64_t K = tot[0];
+    uint64_t V = 0, T = 0, n_evals = g.nb;
+    size_t kept_bytes = 0;
+    MeshLayout L = mesh_layout(0, 0, flags);
+    if (K > 0u) {
+        if (K * rmk::kBrickSegs >= 0xFFFFFFFFull)
+            return fail(c, RM_ERR_DEVICE, "rm_extract_mesh_sparse: %llu bricks to evaluate: more than the segment index holds", (unsigned long long)K);
+        // per kept brick: its index, its segment map, its tile of distances, 64 segment words and their first (vertex, triangle)
+        const uint32_t n_segs = (uint32_t)(K * rmk::kBrickSegs), n_sblocks = (n_segs + rmk::kSegBlock - 1u) / rmk::kSegBlock;
+        const size_t klist_o = 0, maps_o = align16((size_t)K * 4u), tiles_o = maps_o + (size_t)K * sizeof(rmk::SparseSegMap),
+                     words_o = tiles_o + align16((size_t)K * rmk::kTilePoints * 4u), first_o = words_o + align16((size_t)n_segs * 4u),
+                     ssums_o = first_o + (size_t)n_segs * 8u, stot_o = ssums_o + align16((size_t)n_sblocks * 8u);
+        kept_bytes = stot_o + 16u;
+        if ((rc = grow_bytes(c, &c->d_mscratch, &c->d_mscratch_bytes, kept_bytes)) != RM_OK) return rc;
+        char* sc = static_cast<char*>(c->d_mscratch);
+        uint32_t* klist = reinterpret_cast<uint32_t*>(sc + klist_o);
+        rmk::SparseSegMap* maps = reinterpret_cast<rmk::SparseSegMap*>(sc + maps_o);
+        float* tiles = reinterpret_cast<float*>(sc + tiles_o);
+        uint32_t* words = reinterpret_cast<uint32_t*>(sc + words_o);
+        uint2* first = reinterpret_cast<uint2*>(sc + first_o);
+        unsigned long long* ssums = reinterpret_cast<unsigned long long*>(sc + ssums_o);
+        unsigned long long* stot = reinterpret_cast<unsigned long long*>(sc + stot_o);
+        hipLaunchKernelGGL(rmk::rm_sparse_compact_kernel, dim3(n_pblocks), dim3(256), 0, s, n_entries,
+                           static_cast<const unsigned long long*>(psums), boff, klist);
+        const SparseCountFn count = loop == rmk::Q_LOOP_CHAIN ? rmk::rm_sparse_count_kernel<rmk::Q_LOOP_CHAIN>
+                                  : loop == rmk::Q_LOOP_TREE ? rmk::rm_sparse_count_kernel<rmk::Q_LOOP_TREE>
+                                                             : rmk::rm_sparse_count_kernel<rmk::Q_LOOP_GENERAL>;
+        if ((rc = sparse_launch(c, count, (uint32_t)K, shmem, s, Q, g, level, static_cast<const uint32_t*>(boff),
+                                static_cast<const uint32_t*>(klist), tiles, maps, words, evals)) != RM_OK)
+            return rc;
+        hipLaunchKernelGGL(rmk::rm_sparse_seg_sum_kernel, dim3(n_sblocks), dim3(256), 0, s, n_segs, static_cast<const uint32_t*>(words), ssums);
+        hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, ssums, n_sblocks, stot);
+        HIP_TRY(c, hipGetLastError());
+        unsigned long long ev = 0ull;
+        HIP_TRY(c, hipMemcpyAsync(tot, stot, sizeof tot, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        V = tot[0];
+        T = tot[1];
+        n_evals += ev;
+        if (V > 0xFFFFFFFFull || T > 0xFFFFFFFFull)
+            return fail(c, RM_ERR_RANGE, "rm_extract_mesh_sparse: %llu vertices and %llu triangles do not fit 32-bit indices",
+                        (unsigned long long)V, (unsigned long long)T);
+        L = mesh_layout(V, T, flags);
+        if ((rc = grow_bytes(c, &c->d_mesh, &c->d_mesh_bytes, L.bytes)) != RM_OK) return rc;
+        char* m = static_cast<char*>(c->d_mesh);
+        if (V > 0u) {
+            hipLaunchKernelGGL(rmk::rm_sparse_seg_scan_kernel, dim3(n_sblocks), dim3(256), 0, s, n_segs, static_cast<const uint32_t*>(words),
+                               static_cast<const unsigned long long*>(ssums), first);
+            hipLaunchKernelGGL(rmk::rm_sparse_emit_kernel, dim3((uint32_t)K), dim3(256), 0, s, g, level, (uint32_t)K,
+                               static_cast<const uint32_t*>(boff), static_cast<const uint32_t*>(klist), static_cast<const float*>(tiles),
+                               static_cast<const rmk::SparseSegMap*>(maps), static_cast<const uint32_t*>(words), static_cast<const uint2*>(first),
+                               reinterpret_cast<float*>(m + L.vertices), reinterpret_cast<uint32_t*>(m + L.triangles));
+            HIP_TRY(c, hipGetLastError());
+            if ((rc = mesh_attributes(c, Q, loop, shmem, s, flags, V, m, L)) != RM_OK) return rc;
+        }
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    c->mesh_valid = true;
+    c->mesh_v = V;
+    c->mesh_t = T;
+    c->mesh_flags = flags;
+    out_stats[RM_MESH_STAT_VERTICES] = V;
+    out_stats[RM_MESH_STAT_TRIANGLES] = T;
+    out_stats[RM_MESH_STAT_BRICKS] = g.nb;
+    out_stats[RM_MESH_STAT_BRICKS_KEPT] = K;
+    out_stats[RM_MESH_STAT_EVALUATIONS] = n_evals;
+    out_stats[RM_MESH_STAT_SCRATCH_BYTES] = bricks_bytes + kept_bytes;
     return RM_OK;
 }
 

@@ -2,6 +2,7 @@
 normals, and vertex colours from a material table) and binary STL.
 
   python -m ray_marching_amd.mesh --scene g32 --lo -2.5 --hi 2.5 --res 256 out.ply
+  python -m ray_marching_amd.mesh --scene g32 --lo -2.5 --hi 2.5 --res 1024 --sparse out.ply
 
 extracts the surface of a named scene (csg.scene) on the GPU and writes it; the format follows the file's extension.
 Triangles are wound counter-clockwise seen from outside.  The mesh is open where the surface leaves the box [lo, hi]."""
@@ -20,7 +21,10 @@ def _numpy(a):
 
 class Mesh:
     """vertices (V, 3) float32; triangles (T, 3) vertex indices (uint32; int32 views as torch tensors); per vertex,
-    when extracted: normals (V, 3), leaf and material (V,) (rm_query_points at the vertex positions), else None."""
+    when extracted: normals (V, 3), leaf and material (V,) (rm_query_points at the vertex positions), else None.
+    stats: the statistics of a sparse extraction (a dict: vertices, triangles, bricks, bricks_kept, evaluations,
+    scratch_bytes), else None."""
+    stats = None
 
     def __init__(self, vertices, triangles, normals=None, leaf=None, material=None):
         self.vertices, self.triangles, self.normals, self.leaf, self.material = vertices, triangles, normals, leaf, material
@@ -31,8 +35,10 @@ class Mesh:
     def numpy(self):
         """This mesh with numpy arrays (triangles as uint32)."""
         t = _numpy(self.triangles)
-        return Mesh(_numpy(self.vertices), t.view(np.uint32) if t.dtype == np.int32 else t, _numpy(self.normals),
-                    _numpy(self.leaf), _numpy(self.material))
+        m = Mesh(_numpy(self.vertices), t.view(np.uint32) if t.dtype == np.int32 else t, _numpy(self.normals),
+                 _numpy(self.leaf), _numpy(self.material))
+        m.stats = self.stats
+        return m
 
     def is_closed(self):
         """Whether every directed edge (u, v) of the triangles occurs as often as (v, u): no border, consistent winding."""
@@ -155,6 +161,8 @@ def main(argv=None):
     ap.add_argument("--level", type=float, default=0.0)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--no-normals", action="store_true")
+    ap.add_argument("--sparse", action="store_true",
+                    help="extract brick by brick (rm_extract_mesh_sparse): the same mesh, any lattice size; prints its statistics")
     ap.add_argument("out", help="output file: .obj, .ply or .stl")
     a = ap.parse_args(argv)
     from . import csg, renderer
@@ -162,13 +170,17 @@ def main(argv=None):
     try:
         res.set_materials(MATERIALS)
         res.set_scene(csg.scene(a.scene))
-        m = res.extract_mesh(_three(a.lo, float, "--lo"), _three(a.hi, float, "--hi"), _three(a.res, int, "--res"), level=a.level,
-                             normals=not a.no_normals, ids=True)
+        extract = res.extract_mesh_sparse if a.sparse else res.extract_mesh
+        m = extract(_three(a.lo, float, "--lo"), _three(a.hi, float, "--hi"), _three(a.res, int, "--res"), level=a.level,
+                    normals=not a.no_normals, ids=True)
     finally:
         res.close()
     write(m, a.out, MATERIALS)
     print("%s: %d vertices, %d triangles, %s" % (a.out, len(m.vertices), len(m.triangles),
                                                  "closed" if m.is_closed() else "open (the surface meets the box)"))
+    if a.sparse:
+        print("sparse: %d of %d bricks kept, %d evaluations, %.1f MB of scratch"
+              % (m.stats["bricks_kept"], m.stats["bricks"], m.stats["evaluations"], m.stats["scratch_bytes"] / 1e6))
 
 
 if __name__ == "__main__":

@@ -402,10 +402,8 @@ class RayMarchingResources:
         self._check(self._L.rm_sample_grid(self._h, fp(o), fp(s), nx, ny, nz, C.c_void_p(out_ptr), 1,
                                            C.c_void_p(stream) if stream else None))
 
-    def extract_mesh(self, lo, hi, resolution, level=0.0, normals=True, ids=True, device=False):
-        """The surface map_scene = level inside the box [lo, hi], on a lattice of `resolution` points per axis (an int, or
-        (nx, ny, nz)): origin lo, step (hi - lo) / (n - 1) in float32.  Returns a mesh.Mesh (numpy arrays, or torch tensors
-        on this context's GPU with device=True).  The mesh is open where the surface leaves the box."""
+    @staticmethod
+    def _box_lattice(lo, hi, resolution):
         lo = np.broadcast_to(np.asarray(lo, dtype=np.float32), (3,))
         hi = np.broadcast_to(np.asarray(hi, dtype=np.float32), (3,))
         n = np.broadcast_to(np.asarray(resolution), (3,))
@@ -413,17 +411,43 @@ class RayMarchingResources:
             raise ValueError("lo and hi must be finite with lo < hi on every axis")
         if n.dtype.kind not in "iu" or np.any(n < 2):
             raise ValueError("resolution must be an integer of at least 2 points per axis, not %s" % (resolution,))
-        step = (hi - lo) / (n.astype(np.float32) - np.float32(1.0))
+        return lo, (hi - lo) / (n.astype(np.float32) - np.float32(1.0)), n
+
+    def extract_mesh(self, lo, hi, resolution, level=0.0, normals=True, ids=True, device=False):
+        """The surface map_scene = level inside the box [lo, hi], on a lattice of `resolution` points per axis (an int, or
+        (nx, ny, nz)): origin lo, step (hi - lo) / (n - 1) in float32.  Returns a mesh.Mesh (numpy arrays, or torch tensors
+        on this context's GPU with device=True).  The mesh is open where the surface leaves the box."""
+        lo, step, n = self._box_lattice(lo, hi, resolution)
         return self.extract_mesh_grid(lo, step, n, level, normals, ids, device)
 
     def extract_mesh_grid(self, origin, step, shape, level=0.0, normals=True, ids=True, device=False):
         """extract_mesh on an exact lattice (origin, step, shape as sample_grid takes them)."""
-        from . import mesh as _mesh
         o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
         flags = (_ffi.RM_MESH_NORMALS if normals else 0) | (_ffi.RM_MESH_IDS if ids else 0)
         counts = (C.c_uint64 * 2)()
         self._check(self._L.rm_extract_mesh(self._h, fp(o), fp(s), nx, ny, nz, float(level), flags, counts))
-        V, T = int(counts[0]), int(counts[1])
+        return self._read_mesh(int(counts[0]), int(counts[1]), normals, ids, device)
+
+    def extract_mesh_sparse(self, lo, hi, resolution, level=0.0, normals=True, ids=True, device=False):
+        """extract_mesh through rm_extract_mesh_sparse: the same mesh, bit for bit, evaluated only in the bricks of 8 x 8 x 8
+        lattice points the surface can reach -- and with no limit on the number of lattice points.  The returned Mesh
+        carries the call's statistics in mesh.stats (a dict: _ffi.MESH_STAT_NAMES)."""
+        lo, step, n = self._box_lattice(lo, hi, resolution)
+        return self.extract_mesh_grid_sparse(lo, step, n, level, normals, ids, device)
+
+    def extract_mesh_grid_sparse(self, origin, step, shape, level=0.0, normals=True, ids=True, device=False):
+        """extract_mesh_sparse on an exact lattice (origin, step, shape as sample_grid takes them)."""
+        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
+        flags = (_ffi.RM_MESH_NORMALS if normals else 0) | (_ffi.RM_MESH_IDS if ids else 0)
+        stats = (C.c_uint64 * _ffi.RM_MESH_STATS)()
+        self._check(self._L.rm_extract_mesh_sparse(self._h, fp(o), fp(s), nx, ny, nz, float(level), flags, stats, _ffi.RM_MESH_STATS))
+        m = self._read_mesh(int(stats[_ffi.RM_MESH_STAT_VERTICES]), int(stats[_ffi.RM_MESH_STAT_TRIANGLES]), normals, ids, device)
+        m.stats = {name: int(stats[k]) for k, name in enumerate(_ffi.MESH_STAT_NAMES)}
+        return m
+
+    def _read_mesh(self, V, T, normals, ids, device):
+        """rm_read_mesh of the extraction that just returned V vertices and T triangles, as a mesh.Mesh."""
+        from . import mesh as _mesh
         if device:
             import torch
             dev = torch.device("cuda", self.device)
@@ -506,6 +530,18 @@ def program_subtree(cmd_count, words, index):
     if rc != _ffi.RM_OK:
         raise _ffi.RmError(rc, _ffi.hip_lib().rm_status_string(rc).decode())
     return first.value, count.value
+
+
+def program_lipschitz(cmd_count, words):
+    """rm_program_lipschitz: L with |map_scene(p) - map_scene(q)| <= L |p - q| in real arithmetic, or inf when the program
+    has no such bound (a parameter that is not finite, a Scale of 0); pure host code, no GPU needed."""
+    w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32))
+    ptr = w.ctypes.data_as(C.POINTER(C.c_uint32)) if w.size else None
+    out = C.c_double(0.0)
+    rc = _ffi.hip_lib().rm_program_lipschitz(int(cmd_count), ptr, int(w.size), C.byref(out))
+    if rc != _ffi.RM_OK:
+        raise _ffi.RmError(rc, _ffi.hip_lib().rm_status_string(rc).decode())
+    return out.value
 
 
 def selection_overlay(image, selected_mask, n_samples, colour, alpha=0.5):

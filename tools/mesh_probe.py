@@ -6,8 +6,11 @@
   extract_mesh: g32 over [-2.5, 2.5]^3 at 512^3, host to host (the call is synchronous), without and with normals + ids;
                 vertex and triangle counts, and the bytes the count / scan / emit kernels move at least, counted from the
                 shapes (their kernel times come from a rocprofv3 --kernel-trace --stats run of this probe)
+  sparse:       rm_extract_mesh_sparse on the same lattice, host to host, alternating with the dense call in one loop
+                (median, fastest and slowest of each over --reps rounds), with its statistics; with --big also g32 at
+                1281^3 (step 2^-8) and 2561^3 (step 2^-9) from origin -2.5, which the dense call cannot hold
 
-usage: tools/mesh_probe.py [--reps N] [--res N] > profiles/r05_mesh_extraction.txt"""
+usage: tools/mesh_probe.py [--reps N] [--res N] [--big] > profiles/r08_sparse_mesh.txt"""
 import argparse
 import json
 import os
@@ -56,6 +59,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--res", type=int, default=512)
+    ap.add_argument("--big", action="store_true", help="also time the sparse extraction at 1281^3 and 2561^3")
     a = ap.parse_args()
     import torch
     dev = torch.device("cuda", 0)
@@ -90,6 +94,40 @@ def main():
     # the cells' corners once; triangles): the distances are read twice, the flags written once and read once
     out.update({"vertices": V, "triangles": T, "closed": m.is_closed(),
                 "extract_kernel_bytes": 4 * pts + 16 * blocks + (4 + 4 + 1) * pts + 12 * V + pts + 12 * T})
+    # dense and sparse by turns, so that both see the same state of the machine
+    stats = (C.c_uint64 * 6)()
+    dense = lambda: L.rm_extract_mesh(h, fo, fs, n, n, n, 0.0, 0, counts)  # noqa: E731
+    sparse = lambda: L.rm_extract_mesh_sparse(h, fo, fs, n, n, n, 0.0, 0, stats, 6)  # noqa: E731
+    for _ in range(a.warmup):
+        assert dense() == 0 and sparse() == 0
+    td, ts = [], []
+    for _ in range(a.reps):
+        for fn, t in ((dense, td), (sparse, ts)):
+            t0 = time.perf_counter()
+            fn()
+            t.append((time.perf_counter() - t0) * 1e3)
+    names = ("vertices", "triangles", "bricks", "bricks_kept", "evaluations", "scratch_bytes")
+    for label, t in (("dense", td), ("sparse", ts)):
+        out["ab_%s_host_ms" % label] = {"median": round(float(np.median(t)), 4), "min": round(min(t), 4), "max": round(max(t), 4)}
+    out["sparse_stats"] = {k: int(stats[i]) for i, k in enumerate(names)}
+    out["sparse_evaluations_per_vertex"] = round(int(stats[4]) / max(int(stats[0]), 1), 2)
+    out["sparse_matches_dense_counts"] = int(stats[0]) == V and int(stats[1]) == T
+    if a.big:
+        for big, step in ((1281, 2.0 ** -8), (2561, 2.0 ** -9)):
+            bo, bs = (C.c_float * 3)(-2.5, -2.5, -2.5), (C.c_float * 3)(step, step, step)
+            run = lambda: L.rm_extract_mesh_sparse(h, bo, bs, big, big, big, 0.0, 0, stats, 6)  # noqa: E731
+            rc = run()
+            if rc != 0:
+                out["sparse_%d" % big] = {"status": rc}
+                continue
+            t = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                run()
+                t.append((time.perf_counter() - t0) * 1e3)
+            row = {k: int(stats[i]) for i, k in enumerate(names)}
+            row.update({"host_ms": round(float(np.median(t)), 3), "evaluations_per_vertex": round(int(stats[4]) / max(int(stats[0]), 1), 2)})
+            out["sparse_%d" % big] = row
     res.close()
     print(json.dumps(out))
 
