@@ -150,6 +150,12 @@ pub const RM_MESH_STAT_EVALUATIONS: c_int = 4;
 pub const RM_MESH_STAT_SCRATCH_BYTES: c_int = 5;
 pub const RM_MESH_STATS: c_int = 6;
 
+// Slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table).
+// enum rm_slicecount: indices into the counts of rm_slice_contours; RM_SLICE_COUNTS is their number
+pub const RM_SLICE_POINTS: c_int = 0;
+pub const RM_SLICE_CONTOURS: c_int = 1;
+pub const RM_SLICE_COUNTS: c_int = 2;
+
 // Lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit).
 // enum rm_light: indices into the parameter array; RM_LIGHT_PARAMS is its length
 pub const RM_LIGHT_POS_X: c_int = 0;
@@ -212,6 +218,12 @@ extern "C" {
     pub fn rm_mesh_case_table(out: *mut u32, n_out: u32) -> c_int;
     pub fn rm_extract_mesh_sparse(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, level: f32,
                                   flags: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_slice_contours(ctx: *mut rm_ctx, axis: u32, origin_uv: *const f32, step_uv: *const f32, nu: u32, nv: u32,
+                             heights: *const f32, n_layers: u32, level: f32, flags: u32, out_counts: *mut u64,
+                             n_counts: u32) -> c_int;
+    pub fn rm_read_slices(ctx: *mut rm_ctx, out_points: *mut f32, out_contours: *mut u32, out_layer_first: *mut u32,
+                          out_normals: *mut f32, out_ids: *mut u32, is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_slice_case_table(out: *mut u32, n_out: u32) -> c_int;
     pub fn rm_program_lipschitz(cmd_count: u32, words: *const u32, n_words: u32, out_l: *mut f64) -> c_int;
     pub fn rm_lighting_defaults(out: *mut f32, n_out: u32) -> c_int;
     pub fn rm_set_lighting(ctx: *mut rm_ctx, params: *const f32, count: u32) -> c_int;
@@ -290,6 +302,9 @@ pub struct RayMarchingResources {
     /// (vertices, triangles) of the mesh the context holds since the last successful `extract_mesh`: what `read_mesh`
     /// writes, so what its slices must hold
     mesh: Cell<Option<(u64, u64)>>,
+    /// (points, contours, layers) of the slices the context holds since the last successful `slice_contours`: what
+    /// `read_slices` writes, so what its slices must hold
+    slices: Cell<Option<(u64, u64, u32)>>,
 }
 
 unsafe impl Send for RayMarchingResources {} // a context may move between threads; it is not Sync
@@ -303,7 +318,7 @@ impl RayMarchingResources {
             let msg = unsafe { CStr::from_ptr(rm_last_error(std::ptr::null_mut())) };
             return Err(RmError { status: rc, message: msg.to_string_lossy().into_owned() });
         }
-        Ok(Self { ctx, mesh: Cell::new(None) })
+        Ok(Self { ctx, mesh: Cell::new(None), slices: Cell::new(None) })
     }
 
     fn check(&self, rc: c_int) -> Result<(), RmError> {
@@ -497,6 +512,48 @@ impl RayMarchingResources {
         let pn = out_normals.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
         let pi = out_ids.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
         self.check(unsafe { rm_read_mesh(self.ctx, pv, pt, pn, pi, 0, std::ptr::null_mut()) })
+    }
+
+    /// The outlines of the solid `map_scene < level` in the planes `heights` across `axis` (0, 1, 2), as ordered contours
+    /// (`rm_slice_contours`): point (i, j) of a layer lies at `origin_uv + (i, j) * step_uv` on the in-plane axes
+    /// `(axis + 1) % 3` and `(axis + 2) % 3`.  `flags`: `RM_MESH_NORMALS`, `RM_MESH_IDS`.  Returns (points, contours);
+    /// `read_slices` copies them out.
+    pub fn slice_contours(&self, axis: u32, origin_uv: [f32; 2], step_uv: [f32; 2], nu: u32, nv: u32, heights: &[f32], level: f32,
+                          flags: u32) -> Result<(u64, u64), RmError> {
+        assert!(heights.len() <= u32::MAX as usize, "slice_contours: too many heights");
+        let mut counts = [0u64; RM_SLICE_COUNTS as usize];
+        self.slices.set(None);  // a failed call may have released the previous slices
+        self.check(unsafe {
+            rm_slice_contours(self.ctx, axis, origin_uv.as_ptr(), step_uv.as_ptr(), nu, nv, heights.as_ptr(), heights.len() as u32,
+                              level, flags, counts.as_mut_ptr(), RM_SLICE_COUNTS as u32)
+        })?;
+        let (p, c) = (counts[RM_SLICE_POINTS as usize], counts[RM_SLICE_CONTOURS as usize]);
+        self.slices.set(Some((p, c, heights.len() as u32)));
+        Ok((p, c))
+    }
+
+    /// The slices of the last successful `slice_contours`: points (world x, y, z, three per point, in contour order),
+    /// contours (first point, point count, layer, closed; four per contour), layer_first (layers + 1 entries), normals
+    /// (three per point) and (leaf, material) (two per point).  `None` skips that output.  `RM_ERR_ARG` before any
+    /// `slice_contours`, or for normals / ids it did not compute.
+    pub fn read_slices(&self, out_points: Option<&mut [f32]>, out_contours: Option<&mut [u32]>,
+                       out_layer_first: Option<&mut [u32]>, out_normals: Option<&mut [f32]>,
+                       out_ids: Option<&mut [u32]>) -> Result<(), RmError> {
+        let (p, c, l) = match self.slices.get() {
+            Some((p, c, l)) => (p as usize, c as usize, l as usize),
+            None => return Err(RmError { status: RM_ERR_ARG, message: "read_slices: nothing has been sliced".to_string() }),
+        };
+        assert!(out_points.as_ref().map_or(true, |s| s.len() >= 3 * p), "read_slices: out_points is shorter than {} points", p);
+        assert!(out_contours.as_ref().map_or(true, |s| s.len() >= 4 * c), "read_slices: out_contours is shorter than {} contours", c);
+        assert!(out_layer_first.as_ref().map_or(true, |s| s.len() >= l + 1), "read_slices: out_layer_first is shorter than {} entries", l + 1);
+        assert!(out_normals.as_ref().map_or(true, |s| s.len() >= 3 * p), "read_slices: out_normals is shorter than {} points", p);
+        assert!(out_ids.as_ref().map_or(true, |s| s.len() >= 2 * p), "read_slices: out_ids is shorter than {} points", p);
+        let pp = out_points.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pc = out_contours.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pl = out_layer_first.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pn = out_normals.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pi = out_ids.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        self.check(unsafe { rm_read_slices(self.ctx, pp, pc, pl, pn, pi, 0, std::ptr::null_mut()) })
     }
 }
 

@@ -369,6 +369,45 @@ int rm_extract_mesh_sparse(rm_ctx* ctx, const float* origin, const float* step, 
  * a Scale of 0.  Errors: rm_validate_program's status for an invalid program, RM_ERR_NULL for a NULL out_L. */
 int rm_program_lipschitz(uint32_t cmd_count, const uint32_t* words, uint32_t n_words, double* out_L);
 
+/* Slicing (extension; DESIGN.md section 16 is the contract, to the last bit): the closed outlines of the solid d < level in a
+ * stack of planes, as ordered polylines -- what a slicer or a section drawing needs, evaluated directly on a 2-D lattice
+ * per layer instead of through a triangle mesh.  From the program, limits and material table as they are at the call.
+ * Lattice: the slicing axis w = axis (0, 1 or 2), the in-plane axes u = (w + 1) % 3 and v = (w + 2) % 3 ((u, v, w) is
+ * right-handed; for y up pass axis = 1: u = z, v = x).  origin_uv and step_uv are host arrays of 2 floats (finite; step
+ * > 0), heights a host array of n_layers finite floats in any order, duplicates allowed.  Point (i, j) of layer k is
+ * (ou + (float)i * su, ov + (float)j * sv) on (u, v) and heights[k] on w; its value is rm_query_points' distance there.
+ * Inside: d < level (NaN is outside).  One vertex on each in-plane lattice edge whose ends differ, by rm_extract_mesh's rule,
+ * ordered by (layer, i + nu * j, axis).  Per cell the directed segments of the case table (rm_slice_case_table), the inside
+ * on their left seen from +w; they chain into contours: an open one (it starts and ends on the lattice's border) begins at
+ * the vertex no segment ends at, a closed one at its lowest vertex and does not repeat it.  Contours are ordered by layer
+ * (in the order of `heights`) and then by their first vertex.  So outer boundaries are counter-clockwise seen from +w and
+ * holes clockwise.  Results (rm_read_slices): points P x 3 floats (world x, y, z, in contour order), contours C x 4 u32
+ * (first point, point count, layer, closed 0/1), layer_first n_layers + 1 u32 (the contour each layer starts at; the last
+ * entry is C), and with RM_MESH_NORMALS / RM_MESH_IDS in flags normals P x 3 and ids P x 2 (leaf, material), exactly what
+ * rm_query_points returns at the points.  Two runs give identical arrays; one call over all layers gives the concatenation
+ * of one call per layer (indices shifted).
+ * nu and nv: 2..65536 with nu * nv <= 2^26; n_layers: 1..65536; RM_ERR_RANGE otherwise, or when P or C would not fit 32
+ * bits.  RM_ERR_ARG for an axis above 2, a value that is not finite, a step <= 0, unknown flags, n_counts < RM_SLICE_COUNTS.
+ * Otherwise the errors of rm_extract_mesh.  out_counts[RM_SLICE_POINTS] = P, [RM_SLICE_CONTOURS] = C.
+ * Synchronous on the context's own stream, ordered after its earlier work.  The result lives in buffers of its own until the
+ * next rm_slice_contours or rm_destroy: it does not replace the context's mesh, and like a query the call never touches
+ * the draw state (RM_OPT_TIMING, RM_INFO_*, the specialised kernel, the tile buffers). */
+enum rm_slicecount { RM_SLICE_POINTS = 0, RM_SLICE_CONTOURS = 1, RM_SLICE_COUNTS = 2 };
+int rm_slice_contours(rm_ctx* ctx, uint32_t axis, const float* origin_uv, const float* step_uv, uint32_t nu, uint32_t nv,
+                      const float* heights, uint32_t n_layers, float level, uint32_t flags, uint64_t* out_counts,
+                      uint32_t n_counts);
+/* Copies the last slices out; any output may be NULL.  RM_ERR_ARG before any rm_slice_contours, or for normals / ids that
+ * call did not compute.  is_device and stream as for rm_query_points (device arrays: out_contours 16-byte aligned, out_ids
+ * 8-byte, the others 4-byte); the next rm_slice_contours waits for a device read that is still running. */
+int rm_read_slices(rm_ctx* ctx, float* out_points, uint32_t* out_contours, uint32_t* out_layer_first, float* out_normals,
+                   uint32_t* out_ids, int is_device, void* stream);
+/* The case table of rm_slice_contours (host code; no context): 16 cases x 5 words.  out[5 * case] = segment count (0..2),
+ * then (tail edge, head edge) pairs ordered by tail edge, 0xFFFFFFFF after the last.  Case = sum over corners c of
+ * inside(c) << c, corner c at (c & 1, c >> 1) in (u, v); edge e runs along in-plane axis e >> 1 from the corner with 0 on
+ * it, e & 1 its offset on the other axis: 0 bottom, 1 top, 2 left, 3 right.  The diagonal cases 6 and 9 give one segment
+ * around each inside corner.  RM_ERR_ARG when n_out < 80. */
+int rm_slice_case_table(uint32_t* out, uint32_t n_out);
+
 /* Lit rendering (extension): rm_draw with soft shadows and ambient occlusion marched through the same distance field
  * (DESIGN.md section 13 is the contract, to the last bit).  The reference has one fixed light and max(0.02, n.l)
  * (wgsl:98-105); with RM_LIGHT_SHADOW = 0 and RM_LIGHT_AO = 0 rm_draw_lit writes rm_draw's image bit for bit.

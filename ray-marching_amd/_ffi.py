@@ -52,6 +52,8 @@ RM_MESH_NORMALS, RM_MESH_IDS = 1, 2
 (RM_MESH_STAT_VERTICES, RM_MESH_STAT_TRIANGLES, RM_MESH_STAT_BRICKS, RM_MESH_STAT_BRICKS_KEPT, RM_MESH_STAT_EVALUATIONS,
  RM_MESH_STAT_SCRATCH_BYTES, RM_MESH_STATS) = range(7)
 MESH_STAT_NAMES = ("vertices", "triangles", "bricks", "bricks_kept", "evaluations", "scratch_bytes")
+# slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table): enum rm_slicecount, the indices of out_counts
+RM_SLICE_POINTS, RM_SLICE_CONTOURS, RM_SLICE_COUNTS = 0, 1, 2
 # lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit): enum rm_light, the parameter names in index order
 RM_LIGHT_PARAMS = 13
 LIGHT_NAMES = ("pos_x", "pos_y", "pos_z", "shadow", "shadow_softness", "bias", "shadow_max_t", "shadow_steps", "ao", "ao_step",
@@ -153,6 +155,12 @@ def hip_lib():
         L.rm_mesh_case_table.restype = C.c_int
         L.rm_extract_mesh_sparse.argtypes = [vp, f3, f3, u32, u32, u32, C.c_float, u32, C.POINTER(u64), u32]
         L.rm_extract_mesh_sparse.restype = C.c_int
+        L.rm_slice_contours.argtypes = [vp, u32, f3, f3, u32, u32, f3, u32, C.c_float, u32, C.POINTER(u64), u32]
+        L.rm_slice_contours.restype = C.c_int
+        L.rm_read_slices.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]
+        L.rm_read_slices.restype = C.c_int
+        L.rm_slice_case_table.argtypes = [vp, u32]
+        L.rm_slice_case_table.restype = C.c_int
         L.rm_program_lipschitz.argtypes = [u32, C.POINTER(u32), u32, C.POINTER(C.c_double)]
         L.rm_program_lipschitz.restype = C.c_int
         L.rm_lighting_defaults.argtypes = [f3, u32]

@@ -24,6 +24,7 @@
 #include "rm_mesh.h"
 #include "rm_mesh_bound.h"
 #include "rm_mesh_sparse.h"
+#include "rm_slice.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
 
@@ -103,6 +104,21 @@ struct rm_ctx {
     bool mesh_valid = false;
     uint64_t mesh_v = 0, mesh_t = 0;
     uint32_t mesh_flags = 0;
+    // slicing (rm_slice.h): the per-vertex scratch of a batch of layers (its per-point scratch is d_mscratch), the small
+    // per-layer tables (heights, layer_first, the layers' first vertices, totals) and the last result, in buffers of its own
+    void* d_swork = nullptr;
+    size_t d_swork_bytes = 0;
+    void* d_slayers = nullptr;
+    size_t d_slayers_bytes = 0;
+    void* d_spoints = nullptr;
+    size_t d_spoints_bytes = 0;
+    void* d_scontours = nullptr;
+    size_t d_scontours_bytes = 0;
+    void* d_sattr = nullptr;
+    size_t d_sattr_bytes = 0;
+    bool slice_valid = false;
+    uint64_t slice_p = 0, slice_c = 0;
+    uint32_t slice_layers = 0, slice_flags = 0;
     // scratch for host-destination draws and batch uniforms
     float* d_out = nullptr;
     size_t d_out_bytes = 0;
@@ -764,6 +780,11 @@ RM_EXPORT void rm_destroy(rm_ctx* c) {
     if (c->d_mscratch) (void)hipFree(c->d_mscratch);
     if (c->d_mbricks) (void)hipFree(c->d_mbricks);
     if (c->d_mesh) (void)hipFree(c->d_mesh);
+    if (c->d_swork) (void)hipFree(c->d_swork);
+    if (c->d_slayers) (void)hipFree(c->d_slayers);
+    if (c->d_spoints) (void)hipFree(c->d_spoints);
+    if (c->d_scontours) (void)hipFree(c->d_scontours);
+    if (c->d_sattr) (void)hipFree(c->d_sattr);
     for (auto& st : c->staging) {
         if (st.host) (void)hipHostFree(st.host);
         if (st.done) (void)hipEventDestroy(st.done);
@@ -1782,6 +1803,243 @@ RM_EXPORT int rm_mesh_case_table(uint32_t* out, uint32_t n_out) {
     if (!out) return RM_ERR_NULL;
     if (n_out < 256u * rmk::kMeshCaseWords) return RM_ERR_ARG;
     std::memcpy(out, rmk::kMeshCaseTable.w, sizeof rmk::kMeshCaseTable.w);
+    return RM_OK;
+}
+
+// ---- slicing (rm_slice.h) ------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint64_t kMaxSlicePoints = 1ull << 26;  // lattice points of one layer
+
+using SliceDistFn = void (*)(rmk::QueryLaunch, rmk::SliceGrid, const float*, float*);
+SliceDistFn slice_dist_kernel(int loop) {
+    return loop == rmk::Q_LOOP_CHAIN ? rmk::rm_slice_dist_kernel<rmk::Q_LOOP_CHAIN>
+         : loop == rmk::Q_LOOP_TREE ? rmk::rm_slice_dist_kernel<rmk::Q_LOOP_TREE>
+                                    : rmk::rm_slice_dist_kernel<rmk::Q_LOOP_GENERAL>;
+}
+
+// grow_bytes for a result that is built batch by batch: the first `used` bytes survive the move
+int grow_keep(rm_ctx* c, void** buf, size_t* cap, size_t need, size_t used, hipStream_t s) {
+    if (need <= *cap) return RM_OK;
+    void* fresh = nullptr;
+    size_t want = need + need / 2u;
+    if (hipMalloc(&fresh, want) != hipSuccess) {
+        (void)hipGetLastError();
+        want = need;
+        HIP_TRY(c, hipMalloc(&fresh, want));
+    }
+    hipError_t e = hipSuccess;
+    if (used) {
+        e = hipMemcpyAsync(fresh, *buf, used, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(fresh);
+        HIP_TRY(c, e);
+    }
+    if (*buf) (void)hipFree(*buf);
+    *buf = fresh;
+    *cap = want;
+    return RM_OK;
+}
+
+uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1u) / per); }
+
+}  // namespace
+
+RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv, const float* step_uv, uint32_t nu, uint32_t nv,
+                                const float* heights, uint32_t n_layers, float level, uint32_t flags, uint64_t* out_counts,
+                                uint32_t n_counts) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_counts) return fail(c, RM_ERR_NULL, "rm_slice_contours: out_counts is NULL");
+    if (!origin_uv || !step_uv || !heights) return fail(c, RM_ERR_NULL, "rm_slice_contours: origin_uv, step_uv or heights is NULL");
+    if (n_counts < (uint32_t)RM_SLICE_COUNTS) return fail(c, RM_ERR_ARG, "rm_slice_contours: n_counts %u < RM_SLICE_COUNTS", n_counts);
+    if (axis > 2u) return fail(c, RM_ERR_ARG, "rm_slice_contours: axis %u is not 0, 1 or 2", axis);
+    for (int a = 0; a < 2; a++) {
+        if (!std::isfinite(origin_uv[a])) return fail(c, RM_ERR_ARG, "rm_slice_contours: origin_uv[%d] = %g is not finite", a, (double)origin_uv[a]);
+        if (!std::isfinite(step_uv[a]) || !(step_uv[a] > 0.0f))
+            return fail(c, RM_ERR_ARG, "rm_slice_contours: step_uv[%d] = %g: a step must be finite and > 0", a, (double)step_uv[a]);
+    }
+    if (!std::isfinite(level)) return fail(c, RM_ERR_ARG, "rm_slice_contours: level %g is not finite", (double)level);
+    if (flags & ~(uint32_t)(RM_MESH_NORMALS | RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_slice_contours: unknown flags 0x%x", flags);
+    const uint64_t n2_64 = (uint64_t)nu * nv;
+    if (nu < 2 || nv < 2 || nu > kMaxDim || nv > kMaxDim || n2_64 > kMaxSlicePoints || n_layers < 1 || n_layers > kMaxDim)
+        return fail(c, RM_ERR_RANGE, "rm_slice_contours: lattice %ux%u, %u layers: 2..65536 points per axis, at most 2^26 per layer, 1..65536 layers",
+                    nu, nv, n_layers);
+    for (uint32_t k = 0; k < n_layers; k++)
+        if (!std::isfinite(heights[k])) return fail(c, RM_ERR_ARG, "rm_slice_contours: heights[%u] = %g is not finite", k, (double)heights[k]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    int rc = query_begin(c, s, (flags & RM_MESH_IDS) != 0, false, &Q, &loop, &shmem);  // after a device read of the previous slices, too
+    if (rc != RM_OK) return rc;
+    c->slice_valid = false;  // its buffers change from here on
+    const uint32_t n2 = (uint32_t)n2_64, per = std::min(n_layers, std::max(1u, rmk::kSliceBatchPoints / n2));
+    const uint32_t n_max = per * n2, nb_max = blocks_of(n_max, rmk::kSliceBlock);
+    // the per-layer tables: heights, layer_first, the first vertex of each layer of a batch, two totals
+    const size_t lf_o = align16((size_t)n_layers * 4u), base_o = lf_o + align16(((size_t)n_layers + 1u) * 4u),
+                 totals_o = base_o + align16(((size_t)per + 1u) * 4u);
+    if ((rc = grow_bytes(c, &c->d_slayers, &c->d_slayers_bytes, totals_o + 16u)) != RM_OK) return rc;
+    char* lt = static_cast<char*>(c->d_slayers);
+    float* d_heights = reinterpret_cast<float*>(lt);
+    uint32_t* d_lf = reinterpret_cast<uint32_t*>(lt + lf_o);
+    uint32_t* d_base = reinterpret_cast<uint32_t*>(lt + base_o);
+    uint32_t* d_totals = reinterpret_cast<uint32_t*>(lt + totals_o);
+    HIP_TRY(c, hipMemcpyAsync(d_heights, heights, (size_t)n_layers * 4u, hipMemcpyHostToDevice, s));
+    // the per-point scratch of a batch: distances, packed vertex bases, block sums
+    const size_t packed_o = align16((size_t)n_max * 4u), sums_o = packed_o + align16((size_t)n_max * 4u);
+    if ((rc = grow_bytes(c, &c->d_mscratch, &c->d_mscratch_bytes, sums_o + align16((size_t)nb_max * 4u))) != RM_OK) return rc;
+    char* sc = static_cast<char*>(c->d_mscratch);
+    float* dist = reinterpret_cast<float*>(sc);
+    uint32_t* packed = reinterpret_cast<uint32_t*>(sc + packed_o);
+    uint32_t* sums = reinterpret_cast<uint32_t*>(sc + sums_o);
+    std::vector<uint32_t> base(per + 1u);
+    uint64_t P = 0, Cn = 0;
+    for (uint32_t k0 = 0; k0 < n_layers; k0 += per) {
+        const uint32_t nl = std::min(per, n_layers - k0), n = nl * n2, nb = blocks_of(n, rmk::kSliceBlock), pb = blocks_of(n, 256u);
+        const rmk::SliceGrid g{origin_uv[0], origin_uv[1], step_uv[0], step_uv[1], nu, nv, n2, axis, k0, n};
+        if ((rc = query_launch(c, slice_dist_kernel(loop), n, shmem, s, Q, g, static_cast<const float*>(d_heights), dist)) != RM_OK) return rc;
+        hipLaunchKernelGGL(rmk::rm_slice_count_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist), sums);
+        hipLaunchKernelGGL(rmk::rm_slice_scan_kernel, dim3(1), dim3(1024), 0, s, sums, nb, d_totals);
+        hipLaunchKernelGGL(rmk::rm_slice_pack_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist),
+                           static_cast<const uint32_t*>(sums), packed);
+        hipLaunchKernelGGL(rmk::rm_slice_layer_base_kernel, dim3(blocks_of(nl + 1u, 256u)), dim3(256), 0, s,
+                           static_cast<const uint32_t*>(packed), n2, nl, static_cast<const uint32_t*>(d_totals), d_base);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(base.data(), d_base, ((size_t)nl + 1u) * 4u, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        const uint32_t V = base[nl];
+        if (P + V > 0xFFFFFFFFull) return fail(c, RM_ERR_RANGE, "rm_slice_contours: more than 2^32 - 1 points");
+        if (V == 0u) {
+            hipLaunchKernelGGL(rmk::rm_slice_layer_first_kernel, dim3(blocks_of(nl + 1u, 256u)), dim3(256), 0, s,
+                               static_cast<const uint32_t*>(d_base), nl, 0u, static_cast<const uint32_t*>(nullptr), 0u, (uint32_t)Cn, d_lf + k0);
+            HIP_TRY(c, hipGetLastError());
+            continue;
+        }
+        // ranking rounds: 2^rounds >= the vertices of the fullest layer >= the longest chain
+        uint32_t v_layer = 0, rounds = 0;
+        for (uint32_t l = 0; l < nl; l++) v_layer = std::max(v_layer, base[l + 1u] - base[l]);
+        while ((1ull << rounds) < v_layer) rounds++;
+        // the per-vertex scratch: next, prev, two (8-byte) ranking states, start, their block sums, and per contour (at most
+        // V / 2: a chain has two vertices or more) length and first point
+        const uint32_t vb = blocks_of(V, 256u), vsb = blocks_of(V, rmk::kSliceBlock), c_max = V / 2u + 1u;
+        const size_t prev_o = align16((size_t)V * 4u), st0_o = prev_o + align16((size_t)V * 4u), st1_o = st0_o + align16((size_t)V * 8u),
+                     start_o = st1_o + align16((size_t)V * 8u), vsums_o = start_o + align16((size_t)V * 4u),
+                     len_o = vsums_o + align16((size_t)vsb * 4u), fp_o = len_o + align16((size_t)c_max * 4u),
+                     work_bytes = fp_o + align16((size_t)c_max * 4u);
+        if ((rc = grow_bytes(c, &c->d_swork, &c->d_swork_bytes, work_bytes)) != RM_OK) return rc;
+        char* wk = static_cast<char*>(c->d_swork);
+        uint32_t* next = reinterpret_cast<uint32_t*>(wk);
+        uint32_t* prev = reinterpret_cast<uint32_t*>(wk + prev_o);
+        uint2* st_a = reinterpret_cast<uint2*>(wk + st0_o);
+        uint2* st_b = reinterpret_cast<uint2*>(wk + st1_o);
+        uint32_t* start = reinterpret_cast<uint32_t*>(wk + start_o);
+        uint32_t* vsums = reinterpret_cast<uint32_t*>(wk + vsums_o);
+        uint32_t* length = reinterpret_cast<uint32_t*>(wk + len_o);
+        uint32_t* first_point = reinterpret_cast<uint32_t*>(wk + fp_o);
+        if ((rc = grow_keep(c, &c->d_spoints, &c->d_spoints_bytes, (size_t)(P + V) * 12u, (size_t)P * 12u, s)) != RM_OK) return rc;
+        HIP_TRY(c, hipMemsetAsync(wk, 0xFF, st0_o, s));  // next and prev: kSliceNil
+        hipLaunchKernelGGL(rmk::rm_slice_link_kernel, dim3(pb), dim3(256), 0, s, g, static_cast<const uint32_t*>(packed), next, prev);
+        hipLaunchKernelGGL(rmk::rm_slice_low_init_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint32_t*>(next), V, st_a);
+        for (uint32_t r = 0; r < rounds; r++) {
+            hipLaunchKernelGGL(rmk::rm_slice_low_round_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint2*>(st_a), V, st_b);
+            std::swap(st_a, st_b);
+        }
+        hipLaunchKernelGGL(rmk::rm_slice_cut_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint2*>(st_a),
+                           static_cast<const uint32_t*>(prev), V, start, st_b);
+        std::swap(st_a, st_b);
+        for (uint32_t r = 0; r < rounds; r++) {
+            hipLaunchKernelGGL(rmk::rm_slice_rank_round_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint2*>(st_a), V, st_b);
+            std::swap(st_a, st_b);
+        }
+        hipLaunchKernelGGL(rmk::rm_slice_start_count_kernel, dim3(vsb), dim3(256), 0, s, static_cast<const uint32_t*>(start), V, vsums);
+        hipLaunchKernelGGL(rmk::rm_slice_scan_kernel, dim3(1), dim3(1024), 0, s, vsums, vsb, d_totals + 1);
+        hipLaunchKernelGGL(rmk::rm_slice_start_scan_kernel, dim3(vsb), dim3(256), 0, s, start, V, static_cast<const uint32_t*>(vsums));
+        HIP_TRY(c, hipGetLastError());
+        uint32_t Cb = 0;
+        HIP_TRY(c, hipMemcpyAsync(&Cb, d_totals + 1, 4u, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (Cb > c_max) return fail(c, RM_ERR_DEVICE, "rm_slice_contours: %u contours from %u vertices", Cb, V);
+        if (Cn + Cb > 0xFFFFFFFFull) return fail(c, RM_ERR_RANGE, "rm_slice_contours: more than 2^32 - 1 contours");
+        if ((rc = grow_keep(c, &c->d_scontours, &c->d_scontours_bytes, (size_t)(Cn + Cb) * 16u, (size_t)Cn * 16u, s)) != RM_OK) return rc;
+        const uint32_t cb = blocks_of(Cb, rmk::kSliceBlock);
+        hipLaunchKernelGGL(rmk::rm_slice_length_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint2*>(st_a),
+                           static_cast<const uint32_t*>(next), static_cast<const uint32_t*>(start), V, length);
+        hipLaunchKernelGGL(rmk::rm_slice_length_count_kernel, dim3(cb), dim3(256), 0, s, static_cast<const uint32_t*>(length), Cb, vsums);
+        hipLaunchKernelGGL(rmk::rm_slice_scan_kernel, dim3(1), dim3(1024), 0, s, vsums, cb, d_totals + 2);
+        hipLaunchKernelGGL(rmk::rm_slice_length_scan_kernel, dim3(cb), dim3(256), 0, s, static_cast<const uint32_t*>(length), Cb,
+                           static_cast<const uint32_t*>(vsums), first_point);
+        hipLaunchKernelGGL(rmk::rm_slice_layer_first_kernel, dim3(blocks_of(nl + 1u, 256u)), dim3(256), 0, s,
+                           static_cast<const uint32_t*>(d_base), nl, V, static_cast<const uint32_t*>(start), Cb, (uint32_t)Cn, d_lf + k0);
+        hipLaunchKernelGGL(rmk::rm_slice_emit_kernel, dim3(pb), dim3(256), 0, s, g, level, static_cast<const float*>(dist),
+                           static_cast<const float*>(d_heights), static_cast<const uint32_t*>(packed), static_cast<const uint2*>(st_a),
+                           static_cast<const uint32_t*>(start), static_cast<const uint32_t*>(length),
+                           static_cast<const uint32_t*>(first_point), (uint32_t)P, (uint32_t)Cn, static_cast<float*>(c->d_spoints),
+                           static_cast<uint4*>(c->d_scontours));
+        HIP_TRY(c, hipGetLastError());
+        P += V;
+        Cn += Cb;
+    }
+    // the attributes of the points: rm_query_points at their positions, device to device
+    const bool normals = (flags & RM_MESH_NORMALS) != 0, ids = (flags & RM_MESH_IDS) != 0;
+    if ((normals || ids) && P > 0u) {
+        const size_t ids_o = normals ? align16((size_t)P * 12u) : 0u;
+        if ((rc = grow_bytes(c, &c->d_sattr, &c->d_sattr_bytes, ids_o + (ids ? (size_t)P * 8u : 0u))) != RM_OK) return rc;
+        char* at = static_cast<char*>(c->d_sattr);
+        float* nrm = normals ? reinterpret_cast<float*>(at) : nullptr;
+        uint32_t* idp = ids ? reinterpret_cast<uint32_t*>(at + ids_o) : nullptr;
+        const PointsFn k = loop == rmk::Q_LOOP_CHAIN ? points_kernel<rmk::Q_LOOP_CHAIN>(false, normals, ids)
+                         : loop == rmk::Q_LOOP_TREE ? points_kernel<rmk::Q_LOOP_TREE>(false, normals, ids)
+                                                    : points_kernel<rmk::Q_LOOP_GENERAL>(false, normals, ids);
+        if ((rc = query_launch(c, k, P, shmem, s, Q, (uint32_t)P, static_cast<const float*>(c->d_spoints), static_cast<float*>(nullptr), nrm,
+                               idp)) != RM_OK)
+            return rc;
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    c->slice_valid = true;
+    c->slice_p = P;
+    c->slice_c = Cn;
+    c->slice_layers = n_layers;
+    c->slice_flags = flags;
+    out_counts[RM_SLICE_POINTS] = P;
+    out_counts[RM_SLICE_CONTOURS] = Cn;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_read_slices(rm_ctx* c, float* out_points, uint32_t* out_contours, uint32_t* out_layer_first, float* out_normals,
+                             uint32_t* out_ids, int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!c->slice_valid) return fail(c, RM_ERR_ARG, "rm_read_slices: nothing has been sliced");
+    if (out_normals && !(c->slice_flags & RM_MESH_NORMALS))
+        return fail(c, RM_ERR_ARG, "rm_read_slices: the slices were computed without RM_MESH_NORMALS");
+    if (out_ids && !(c->slice_flags & RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_read_slices: the slices were computed without RM_MESH_IDS");
+    if (is_device && (misaligned(out_points, 4) || misaligned(out_contours, 16) || misaligned(out_layer_first, 4) ||
+                      misaligned(out_normals, 4) || misaligned(out_ids, 8)))
+        return fail(c, RM_ERR_ARG, "rm_read_slices: device arrays need 4-byte alignment (out_contours: 16-byte, out_ids: 8-byte)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    order_with_previous(c, s);  // (the next slice call waits for this stream in turn)
+    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const size_t pb = (size_t)c->slice_p * 12u, cb = (size_t)c->slice_c * 16u, ib = (size_t)c->slice_p * 8u;
+    const bool normals = (c->slice_flags & RM_MESH_NORMALS) != 0;
+    const char* at = static_cast<const char*>(c->d_sattr);
+    const char* lt = static_cast<const char*>(c->d_slayers);
+    if (out_points && pb) HIP_TRY(c, hipMemcpyAsync(out_points, c->d_spoints, pb, kind, s));
+    if (out_contours && cb) HIP_TRY(c, hipMemcpyAsync(out_contours, c->d_scontours, cb, kind, s));
+    if (out_layer_first)
+        HIP_TRY(c, hipMemcpyAsync(out_layer_first, lt + align16((size_t)c->slice_layers * 4u), ((size_t)c->slice_layers + 1u) * 4u, kind, s));
+    if (out_normals && pb) HIP_TRY(c, hipMemcpyAsync(out_normals, at, pb, kind, s));
+    if (out_ids && ib) HIP_TRY(c, hipMemcpyAsync(out_ids, at + (normals ? align16(pb) : 0u), ib, kind, s));
+    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+RM_EXPORT int rm_slice_case_table(uint32_t* out, uint32_t n_out) {
+    if (!out) return RM_ERR_NULL;
+    if (n_out < 16u * rmk::kSliceCaseWords) return RM_ERR_ARG;
+    std::memcpy(out, rmk::kSliceCaseTable.w, sizeof rmk::kSliceCaseTable.w);
     return RM_OK;
 }
 

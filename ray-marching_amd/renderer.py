@@ -473,6 +473,119 @@ class RayMarchingResources:
                                          C.c_void_p(normals_ptr or None), C.c_void_p(ids_ptr or None), 1,
                                          C.c_void_p(stream) if stream else None))
 
+    # -- slicing (rm_slice_contours / rm_read_slices) ------------------------------------------------------------------------
+    # The slicing axis w is 0, 1 or 2 (x, y, z); the in-plane axes are u = (w + 1) % 3 and v = (w + 2) % 3.
+    @staticmethod
+    def _slice_axis(axis):
+        if isinstance(axis, str) and axis in ("x", "y", "z"):
+            return "xyz".index(axis)
+        if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not 0 <= int(axis) <= 2:
+            raise ValueError("axis must be 0, 1, 2 or 'x', 'y', 'z', not %r" % (axis,))
+        return int(axis)
+
+    @staticmethod
+    def _slice_lattice(axis, origin_uv, step_uv, shape_uv, heights, level):
+        axis = RayMarchingResources._slice_axis(axis)
+        # copies: the library reads 2 floats from each address, and a broadcast or strided view does not hold them there
+        o = np.array(origin_uv, dtype=np.float32, copy=True).reshape(-1)
+        s = np.array(step_uv, dtype=np.float32, copy=True).reshape(-1)
+        n = tuple(int(x) for x in np.asarray(shape_uv).reshape(-1))
+        if o.shape != (2,) or s.shape != (2,) or len(n) != 2:
+            raise ValueError("origin_uv, step_uv and shape_uv must have 2 entries each (u, v)")
+        if not np.all(np.isfinite(o)) or not np.all(np.isfinite(s)) or not np.all(s > 0):
+            raise ValueError("origin_uv must be finite and step_uv finite and > 0")
+        if min(n) < 2:
+            raise ValueError("a layer's lattice needs at least 2 points per axis, not %s" % (n,))
+        h = np.array(heights, dtype=np.float32, copy=True).reshape(-1)
+        if h.size < 1 or not np.all(np.isfinite(h)):
+            raise ValueError("heights must be at least one finite value")
+        if not np.isfinite(np.float32(level)):
+            raise ValueError("level must be finite, not %r" % (level,))
+        return axis, o, s, n, h
+
+    @staticmethod
+    def _layer_heights(lo_w, hi_w, layer_height):
+        """Mid-layer heights lo_w + ((float)k + 0.5f) * h in float32, k = 0, 1, ... while below hi_w."""
+        h = np.float32(layer_height)
+        if not np.isfinite(h) or not h > 0:
+            raise ValueError("layer_height must be finite and > 0, not %r" % (layer_height,))
+        lo_w, hi_w = np.float32(lo_w), np.float32(hi_w)
+        count = int(np.ceil((np.float64(hi_w) - np.float64(lo_w)) / np.float64(h))) + 2
+        if count > (1 << 16) + 2:
+            raise ValueError("layer_height %g gives more than 65536 layers between %g and %g" % (h, lo_w, hi_w))
+        z = lo_w + (np.arange(count, dtype=np.float64).astype(np.float32) + np.float32(0.5)) * h
+        below = z < hi_w
+        z = z if below.all() else z[:int(np.argmin(below))]
+        if z.size < 1:
+            raise ValueError("no layer of height %g fits between %g and %g" % (h, lo_w, hi_w))
+        return z
+
+    def slice_contours(self, lo, hi, resolution, heights=None, layer_height=None, axis=1, level=0.0, normals=False, ids=False,
+                       device=False):
+        """The outlines of the solid map_scene < level in planes across `axis` (0, 1, 2 or "x", "y", "z"; default y, the up
+        axis of the floor) inside the box [lo, hi]: a slicer.Slices.  resolution: lattice points per in-plane axis (an int,
+        or (nu, nv)), over the box's extents on u = (axis + 1) % 3 and v = (axis + 2) % 3 as in extract_mesh.  Give either
+        `heights` (any order, duplicates allowed) or `layer_height`: mid-layer heights lo_w + (k + 0.5) * layer_height in
+        float32 while below hi_w.  Outer boundaries come counter-clockwise seen from +axis, holes clockwise; a contour is
+        open where the outline leaves the box."""
+        if (heights is None) == (layer_height is None):
+            raise ValueError("give either heights or layer_height")
+        lo3, extent, _ = self._box_lattice(lo, hi, 2)       # validates the box; with 2 points per axis the step is hi - lo
+        hi3 = np.broadcast_to(np.asarray(hi, dtype=np.float32), (3,))
+        axis = self._slice_axis(axis)
+        u, v = (axis + 1) % 3, (axis + 2) % 3
+        n = np.broadcast_to(np.asarray(resolution), (2,))
+        if n.dtype.kind not in "iu" or np.any(n < 2):
+            raise ValueError("resolution must be an integer of at least 2 points per in-plane axis, not %s" % (resolution,))
+        lo_uv = lo3[[u, v]]
+        step = extent[[u, v]] / (n.astype(np.float32) - np.float32(1.0))
+        if heights is None:
+            heights = self._layer_heights(lo3[axis], hi3[axis], layer_height)
+        return self.slice_contours_grid(axis, lo_uv, step, n, heights, level, normals, ids, device)
+
+    def slice_contours_grid(self, axis, origin_uv, step_uv, shape_uv, heights, level=0.0, normals=False, ids=False, device=False):
+        """slice_contours on an exact lattice: point (i, j) of layer k lies at origin_uv + (i, j) * step_uv on the in-plane
+        axes (float32, one rounded product and one rounded sum per coordinate) and at heights[k] on `axis`."""
+        axis, o, s, (nu, nv), h = self._slice_lattice(axis, origin_uv, step_uv, shape_uv, heights, level)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        flags = (_ffi.RM_MESH_NORMALS if normals else 0) | (_ffi.RM_MESH_IDS if ids else 0)
+        counts = (C.c_uint64 * _ffi.RM_SLICE_COUNTS)()
+        self._check(self._L.rm_slice_contours(self._h, axis, fp(o), fp(s), nu, nv, fp(h), len(h), float(level), flags, counts,
+                                              _ffi.RM_SLICE_COUNTS))
+        return self._read_slices(int(counts[_ffi.RM_SLICE_POINTS]), int(counts[_ffi.RM_SLICE_CONTOURS]), axis, h, (o, s, (nu, nv)),
+                                 normals, ids, device)
+
+    def _read_slices(self, P, Cn, axis, heights, lattice, normals, ids, device):
+        """rm_read_slices of the call that just returned P points and Cn contours, as a slicer.Slices."""
+        from . import slicer as _slicer
+        nl = len(heights)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            pts = torch.empty((P, 3), dtype=torch.float32, device=dev)
+            con = torch.empty((Cn, 4), dtype=torch.int32, device=dev)       # int32 views of the u32 records
+            lf = torch.empty(nl + 1, dtype=torch.int32, device=dev)
+            nrm = torch.empty((P, 3), dtype=torch.float32, device=dev) if normals else None
+            idv = torch.empty((P, 2), dtype=torch.int32, device=dev) if ids else None
+            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
+            self._check(self._L.rm_read_slices(self._h, ptr(pts), ptr(con), ptr(lf), ptr(nrm), ptr(idv), 1,
+                                               C.c_void_p(self._torch_stream(pts))))
+        else:
+            pts = np.empty((P, 3), dtype=np.float32)
+            con = np.empty((Cn, 4), dtype=np.uint32)
+            lf = np.empty(nl + 1, dtype=np.uint32)
+            nrm = np.empty((P, 3), dtype=np.float32) if normals else None
+            idv = np.empty((P, 2), dtype=np.uint32) if ids else None
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+            self._check(self._L.rm_read_slices(self._h, ptr(pts), ptr(con), ptr(lf), ptr(nrm), ptr(idv), 0, None))
+        return _slicer.Slices(pts, con, lf, heights, axis, nrm, idv[:, 0] if ids else None, idv[:, 1] if ids else None, lattice)
+
+    def read_slices_device(self, points_ptr=0, contours_ptr=0, layer_first_ptr=0, normals_ptr=0, ids_ptr=0, stream=None):
+        """rm_read_slices of the last slice call into device memory (integer addresses; 0 = not wanted), asynchronous."""
+        self._check(self._L.rm_read_slices(self._h, C.c_void_p(points_ptr or None), C.c_void_p(contours_ptr or None),
+                                           C.c_void_p(layer_first_ptr or None), C.c_void_p(normals_ptr or None),
+                                           C.c_void_p(ids_ptr or None), 1, C.c_void_p(stream) if stream else None))
+
 
 class RayMarchingCallback:
     """Per-frame value object (renderer.rs:177-193) with the reference's prepare/paint split."""

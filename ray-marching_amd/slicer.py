@@ -1,0 +1,194 @@
+"""Slices from RayMarchingResources.slice_contours -- the outlines of the solid in a stack of parallel planes, as ordered
+polylines -- and their files: SVG (section drawings) and an ASCII layer file in the style of the Common Layer Interface.
+
+  python -m ray_marching_amd.slicer --scene g8 --axis y --lo -2 --hi 2 --res 1024 --layer-height 0.05 out.svg
+
+slices a named scene (csg.scene) on the GPU and writes the layers; the format follows the file's extension (.svg, .cli).
+Seen from the positive end of the slicing axis, outer boundaries run counter-clockwise and holes clockwise.  A contour is
+open where the outline leaves the box [lo, hi]."""
+import argparse
+import sys
+
+import numpy as np
+
+
+def _numpy(a):
+    if a is None or isinstance(a, np.ndarray):
+        return a
+    return a.cpu().numpy()     # a torch tensor (device=True)
+
+
+def _unsigned(a):
+    return a.view(np.uint32) if a is not None and a.dtype == np.int32 else a
+
+
+class Slices:
+    """points (P, 3) float32, world x, y, z in contour order; contours (C, 4) (first point, point count, layer, closed 0/1);
+    layer_first (n_layers + 1,): the contour each layer starts at, the last entry is C (uint32; int32 views as torch
+    tensors); heights (n_layers,) float32 as given to the call; axis: the slicing axis w (0, 1, 2) -- the in-plane axes are
+    u = (w + 1) % 3 and v = (w + 2) % 3; per point, when computed: normals (P, 3), leaf and material (P,) (rm_query_points
+    at the points), else None.  lattice: (origin_uv, step_uv, (nu, nv)) of the layers, or None."""
+
+    def __init__(self, points, contours, layer_first, heights, axis, normals=None, leaf=None, material=None, lattice=None):
+        self.points, self.contours, self.layer_first = points, contours, layer_first
+        self.heights, self.axis = np.asarray(heights, dtype=np.float32), int(axis)
+        self.normals, self.leaf, self.material, self.lattice = normals, leaf, material, lattice
+
+    def __repr__(self):
+        return "Slices(%d layers, %d contours, %d points)" % (len(self.heights), len(self.contours), len(self.points))
+
+    def numpy(self):
+        """These slices with numpy arrays (contours and layer_first as uint32)."""
+        return Slices(_numpy(self.points), _unsigned(_numpy(self.contours)), _unsigned(_numpy(self.layer_first)), self.heights,
+                      self.axis, _numpy(self.normals), _unsigned(_numpy(self.leaf)), _unsigned(_numpy(self.material)), self.lattice)
+
+    @property
+    def in_plane_axes(self):
+        return (self.axis + 1) % 3, (self.axis + 2) % 3
+
+    def contour(self, c):
+        """((n, 2) float32 in-plane points (u, v) in order, closed).  A closed contour does not repeat its first point."""
+        s = self.numpy()
+        first, count, _, closed = (int(x) for x in s.contours[c])
+        return s.points[first:first + count][:, list(self.in_plane_axes)], bool(closed)
+
+    def layer(self, k):
+        """The contours of layer k, in order: a list of ((n, 2) points, closed)."""
+        s = self.numpy()
+        return [s.contour(c) for c in range(int(s.layer_first[k]), int(s.layer_first[k + 1]))]
+
+    def area(self, k):
+        """The area of layer k's solid: the float64 shoelace sum over its closed contours (holes run clockwise and subtract)."""
+        total = 0.0
+        for uv, closed in self.layer(k):
+            if closed:
+                total += shoelace(uv)
+        return total
+
+
+def shoelace(uv):
+    """Signed area of the closed polygon through (n, 2) points, float64: positive for counter-clockwise."""
+    p = np.asarray(uv, dtype=np.float64)
+    x, y = p[:, 0], p[:, 1]
+    return 0.5 * float(np.sum(x * np.roll(y, -1) - np.roll(x, -1) * y))
+
+
+def _extent(s):
+    """(u0, v0, u1, v1): the layers' lattice, or the bounding box of the points when the slices carry none."""
+    if s.lattice is not None:
+        (ou, ov), (su, sv), (nu, nv) = s.lattice
+        return float(ou), float(ov), float(ou) + (nu - 1) * float(su), float(ov) + (nv - 1) * float(sv)
+    if len(s.points) == 0:
+        return 0.0, 0.0, 1.0, 1.0
+    uv = s.points[:, list(s.in_plane_axes)].astype(np.float64)
+    return float(uv[:, 0].min()), float(uv[:, 1].min()), float(uv[:, 0].max()), float(uv[:, 1].max())
+
+
+def write_svg(slices, path):
+    """SVG: one <g id="layer-k" data-height="..."> per layer holding one <path fill-rule="evenodd"> with all the layer's
+    contours -- "M u v L u v ... Z" for a closed one, without the Z for an open one --, inside one <g> that flips v so the
+    drawing is seen from the positive end of the slicing axis.  The viewBox is the layers' lattice.  Coordinates are
+    written with %.9g: every float32 round-trips."""
+    s = slices.numpy()
+    u0, v0, u1, v1 = _extent(s)
+    w, h = max(u1 - u0, 1e-30), max(v1 - v0, 1e-30)
+    stroke = 0.002 * max(w, h)
+    with open(path, "w") as f:
+        f.write('<?xml version="1.0" encoding="UTF-8"?>\n')
+        f.write('<svg xmlns="http://www.w3.org/2000/svg" viewBox="%.9g %.9g %.9g %.9g">\n' % (u0, -v1, w, h))
+        f.write('<g transform="scale(1,-1)" fill="#9aba4a" fill-opacity="0.25" stroke="#203000" stroke-width="%.9g">\n' % stroke)
+        for k in range(len(s.heights)):
+            f.write('<g id="layer-%d" data-height="%.9g">\n' % (k, s.heights[k]))
+            d = []
+            for uv, closed in s.layer(k):
+                pts = uv.tolist()
+                d.append("M %.9g %.9g" % tuple(pts[0]) + "".join(" L %.9g %.9g" % tuple(p) for p in pts[1:]) + (" Z" if closed else ""))
+            if d:
+                f.write('<path fill-rule="evenodd" d="%s"/>\n' % " ".join(d))
+            f.write("</g>\n")
+        f.write("</g>\n</svg>\n")
+
+
+def write_cli(slices, path):
+    """An ASCII layer file in the style of the Common Layer Interface.  Exactly this is written: the header lines
+    $$HEADERSTART, $$ASCII, $$UNITS/1, $$VERSION/200, $$LABEL/1,ray-marching_amd, $$LAYERS/<number of layers>, $$HEADEREND;
+    then $$GEOMETRYSTART, per layer "$$LAYER/<height>" followed by one "$$POLYLINE/1,<dir>,<n>,u1,v1,...,un,vn" per contour,
+    and $$GEOMETRYEND.  dir is 1 for a counter-clockwise contour, 0 for a clockwise one and 2 for an open one; a closed
+    polyline repeats its first point as its last (n counts it); coordinates are in-plane (u, v), written with %.9g.  No
+    specification of the format was at hand: the file is unverified against a third-party reader."""
+    s = slices.numpy()
+    with open(path, "w") as f:
+        f.write("$$HEADERSTART\n$$ASCII\n$$UNITS/1\n$$VERSION/200\n$$LABEL/1,ray-marching_amd\n$$LAYERS/%d\n$$HEADEREND\n" % len(s.heights))
+        f.write("$$GEOMETRYSTART\n")
+        for k in range(len(s.heights)):
+            f.write("$$LAYER/%.9g\n" % s.heights[k])
+            for uv, closed in s.layer(k):
+                direction = (1 if shoelace(uv) > 0 else 0) if closed else 2
+                pts = uv.tolist() + ([uv[0].tolist()] if closed else [])
+                f.write("$$POLYLINE/1,%d,%d,%s\n" % (direction, len(pts), ",".join("%.9g,%.9g" % tuple(p) for p in pts)))
+        f.write("$$GEOMETRYEND\n")
+
+
+def write(slices, path):
+    """write_svg / write_cli by the extension of `path`."""
+    ext = path.lower().rsplit(".", 1)[-1]
+    if ext == "svg":
+        write_svg(slices, path)
+    elif ext == "cli":
+        write_cli(slices, path)
+    else:
+        raise ValueError("unknown slice format .%s (svg or cli)" % ext)
+
+
+def _values(text, kind, name, counts):
+    """'v' or comma-separated values -> a list of one of the lengths in `counts` (a single value is repeated)."""
+    try:
+        v = [kind(x) for x in text.split(",")]
+    except ValueError:
+        raise SystemExit("%s: %r is not a number or a comma-separated list" % (name, text))
+    if len(v) == 1:
+        return v * max(counts)
+    if len(v) not in counts:
+        raise SystemExit("%s takes %s comma-separated values, not %r" % (name, " or ".join(str(c) for c in (1,) + tuple(counts)), text))
+    return v
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m ray_marching_amd.slicer", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--scene", default="g32", help="a csg.scene name (g1, g8, g32, g32_balanced, mat_mix, ...)")
+    ap.add_argument("--axis", default="y", help="the slicing axis: x, y or z (default y: the floor's up axis)")
+    ap.add_argument("--lo", default="-3", help="lower box corner: one value for all axes, or x,y,z")
+    ap.add_argument("--hi", default="3", help="upper box corner: one value, or x,y,z")
+    ap.add_argument("--res", default="1024", help="lattice points per in-plane axis: n, or nu,nv")
+    ap.add_argument("--layer-height", type=float, default=None, help="slice mid-layer every this much from lo to hi on the axis")
+    ap.add_argument("--heights", default=None, help="comma-separated heights on the axis, instead of --layer-height")
+    ap.add_argument("--level", type=float, default=0.0)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("out", help="output file: .svg or .cli")
+    a = ap.parse_args(argv)
+    if a.axis not in ("x", "y", "z"):
+        raise SystemExit("--axis takes x, y or z, not %r" % a.axis)
+    if (a.heights is None) == (a.layer_height is None):
+        raise SystemExit("give either --layer-height or --heights")
+    heights = None
+    if a.heights is not None:
+        try:
+            heights = [float(x) for x in a.heights.split(",")]
+        except ValueError:
+            raise SystemExit("--heights: %r is not a comma-separated list of numbers" % a.heights)
+    from . import csg, renderer
+    res = renderer.RayMarchingResources(a.device)
+    try:
+        res.set_scene(csg.scene(a.scene))
+        s = res.slice_contours(_values(a.lo, float, "--lo", (3,)), _values(a.hi, float, "--hi", (3,)), _values(a.res, int, "--res", (2,)),
+                               heights=heights, layer_height=a.layer_height, axis=a.axis, level=a.level)
+    finally:
+        res.close()
+    write(s, a.out)
+    closed = int(np.count_nonzero(s.contours[:, 3])) if len(s.contours) else 0
+    print("%s: %d layers, %d contours (%d closed, %d open), %d points"
+          % (a.out, len(s.heights), len(s.contours), closed, len(s.contours) - closed, len(s.points)))
+
+
+if __name__ == "__main__":
+    sys.exit(main())
