@@ -1,6 +1,7 @@
 """Mesh export on the GPU (rm_sample_grid / rm_extract_mesh / rm_read_mesh) against the oracle and the numpy restatement
 of the contract (tests/mesh_ref.py), bit for bit: lattice distances for every scene, vertices and triangles on the chain,
-tree and general record loops, case coverage, a lattice of many scan blocks, the per-vertex attributes, topology, errors,
+tree and general record loops, case coverage, a lattice of many scan blocks, the per-vertex attributes, topology, lattices
+far from the origin with steps down to the coordinates' ulp (and the distances there against a binary64 evaluation), errors,
 and isolation from the draws."""
 import ctypes as C
 
@@ -8,7 +9,10 @@ import numpy as np
 import pytest
 
 import mesh_ref as R
+import scene_f64
 import scenes
+import sparse_ref
+import test_mesh_bound_cpu as B
 from oracle import rm_oracle_np as onp
 from ray_marching_amd import _ffi, renderer
 
@@ -125,6 +129,34 @@ def test_extract_mesh_vs_restatement(res, oracle, name):
     m2 = res.extract_mesh((-3.0, -3.0, -3.0), (3.0, 3.0, 3.0), 64, normals=False, ids=False)
     assert same(m2.vertices, v) and same(m2.triangles, t)
     check_mesh(res, cc, w, origin, step, shape, level=0.05, dist=dist)
+
+
+# ---- far from the origin, and steps near the coordinates' ulp --------------------------------------------------------------------
+def far_cases():
+    return dict(list(B.far_lattices().items()) + [("72 step 2^-15 (near ulp)", B.near_ulp_lattice())])
+
+
+@pytest.mark.parametrize("label", list(far_cases()))
+def test_far_from_the_origin_and_fine_steps(res, label):
+    """Coordinates of magnitude 800 with steps of 200 ulps down to half an ulp (lattice points that share a coordinate):
+    rm_sample_grid is the oracle bit for bit, every distance is within rm_program_bound's E of the binary64 value (DESIGN.md
+    section 15 "The evaluation error", on the kernel's own evaluation), and the mesh is the restatement's."""
+    cc, w = B.far_program()
+    origin, step, shape = far_cases()[label]
+    res.set_limits(LIM)
+    res.set_program(cc, w)
+    dist = oracle_grid(cc, w, origin, step, shape)
+    d = res.sample_grid(origin, step, shape)
+    assert same(d, dist), label
+    L, E = B.program_bound(cc, w, sparse_ref.lattice_P(origin, step, shape))
+    p = R.lattice_points(origin, step, shape)
+    assert np.abs(p).max() <= sparse_ref.lattice_P(origin, step, shape)
+    err = np.abs(d.ravel().astype(np.float64) - scene_f64.map_scene(cc, w, LIM[1], p))
+    print("%s: largest |gpu - f64| %.3g, E %.3g, ratio %.4f" % (label, float(err.max()), E, float(err.max() / E)))
+    assert np.all(np.isfinite(err)) and np.all(err <= E), (label, float(err.max()), E)
+    assert len(R.extract(dist, origin, step, 0.0)[1]) > 0, "the restatement finds no surface: the lattice misses it"
+    for level in (0.0, 0.03):
+        check_mesh(res, cc, w, origin, step, shape, level=level, dist=dist)
 
 
 @pytest.mark.parametrize("name", ["g32", "g32_balanced", "xform_mix"])

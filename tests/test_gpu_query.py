@@ -1,10 +1,13 @@
 """Scene queries on the GPU (rm_query_points / rm_cast_rays / rm_camera_rays) against the oracle, bit for bit: distances,
 materials, leaves, normals, ray casts, frames composed from cast sample rays against rm_draw, picking, the device / torch
-path, the largest program the command buffer holds, and isolation from the draw state."""
+path, the largest program the command buffer holds, isolation from the draw state, and the distances against a binary64
+evaluation within the error bound sparse mesh extraction relies on."""
 import numpy as np
 import pytest
 
+import scene_f64
 import scenes
+import test_mesh_bound_cpu as B
 from oracle import rm_oracle_np as onp
 from ray_marching_amd import _ffi, renderer
 
@@ -130,6 +133,40 @@ def test_points_vs_oracle(res, oracle, name):
     assert same(res.query_points(nsub, normals=True)["normal"], oracle_taps_normal(cc, w, F(LIM[1]), nsub)), name
     # without the normals (the distance + ids kernel): the same bits; every other combination: test_every_output_combination
     assert same(res.query_points(p)["distance"], q["distance"])
+
+
+def real_value_programs(oracle):
+    """The named scenes and four random programs: two with scaled plane normals and off-unit quaternions, the one with the
+    largest error against its bound in tests/test_mesh_bound_cpu.py, and the first."""
+    out = {name: oracle.serialize(*ALL_SCENES[name]()) for name in sorted(ALL_SCENES)}
+    progs = B.random_programs(oracle)
+    picks = [p for p in progs if "scaled" in p[0]][:2] + [p for p in progs if p[0] in ("seed 31000", "seed 31034")]
+    assert len(picks) == 4
+    out.update({label: (cc, w) for label, cc, w in picks})
+    return out
+
+
+@pytest.mark.parametrize("k", range(len(ALL_SCENES) + 4))
+def test_sampled_distances_are_within_E_of_the_real_value(res, oracle, k):
+    """|rm_query_points(p) - f(p)| <= E(1000) with f the binary64 evaluation (tests/scene_f64.py) and E rm_program_bound's error
+    term: DESIGN.md section 15 "The evaluation error" on the kernel's own arithmetic, square root included."""
+    progs = real_value_programs(oracle)
+    label = list(progs)[k]
+    cc, w = progs[label]
+    L, E = B.program_bound(cc, w, 1000.0)
+    assert np.isfinite(E), label
+    p = np.random.default_rng(1000 + k).uniform(-1000.0, 1000.0, (20000, 3)).astype(F)
+    res.set_limits(LIM)
+    res.set_program(cc, w)
+    res.set_materials(np.full((8, 3), 0.5, dtype=np.float32))                 # the random programs' tags name indices up to 7
+    try:
+        d = res.query_points(p)["distance"]
+    finally:
+        res.set_materials(scenes.MATERIAL_TABLE)
+    err = np.abs(d.astype(np.float64) - scene_f64.map_scene(cc, w, LIM[1], p))
+    print("%s: largest |gpu - f64| %.3g, E(1000) %.3g, ratio %.4f" % (label, float(err.max()), E, float(err.max() / E)))
+    assert np.all(np.isfinite(err)), label
+    assert np.all(err <= E), (label, float(err.max()), E)
 
 
 @pytest.mark.parametrize("name", sorted(ALL_SCENES))

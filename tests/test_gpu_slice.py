@@ -1,7 +1,8 @@
 """Slicing on the GPU (rm_slice_contours / rm_read_slices) against the numpy restatement of the contract
 (tests/slice_ref.py), bit for bit: every mesh scene on every axis, odd lattices, unsorted and duplicated heights, levels,
 case coverage, open contours, chains longer than 4096 points over more than one batch, consistency with the mesh, the
-per-point attributes, orientation, errors, device reads, and isolation from the draws and the mesh."""
+per-point attributes, orientation, lattice planes far from the origin with steps down to the coordinates' ulp, errors, device
+reads, and isolation from the draws and the mesh."""
 import ctypes as C
 
 import numpy as np
@@ -10,6 +11,7 @@ import pytest
 import mesh_ref as MR
 import scenes
 import slice_ref as R
+import test_mesh_bound_cpu as B
 from oracle import rm_oracle_np as onp
 from ray_marching_amd import _ffi, renderer
 
@@ -122,6 +124,37 @@ def test_empty_program_gives_no_contours(res):
     # ... but a level above max_dist makes every point inside: still no crossing
     s = res.slice_contours_grid(1, (-1.0, -1.0), (0.1, 0.1), (21, 23), [0.0], level=1000.0)
     assert len(s.points) == 0 and same(s.layer_first, np.zeros(2, np.uint32))
+
+
+# ---- far from the origin, and steps near the coordinates' ulp --------------------------------------------------------------------
+def far_cases():
+    return dict(list(B.far_lattices().items()) + [("72 step 2^-15 (near ulp)", B.near_ulp_lattice())])
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+@pytest.mark.parametrize("label", list(far_cases()))
+def test_far_lattice_planes(res, label, axis):
+    """Planes of the far lattices of tests/test_mesh_bound_cpu.py: coordinates of magnitude 800, steps of 200 ulps down to half an
+    ulp, where neighbouring lattice points share a coordinate (a cell of zero width: its two sides carry the same distances, so
+    no contour crosses between them and the interpolation never divides by the width)."""
+    cc, w = B.far_program()
+    origin3, step3, shape3 = far_cases()[label]
+    u, v = R.in_plane_axes(axis)
+    origin, step, shape = (origin3[u], origin3[v]), (step3[u], step3[v]), (shape3[u], shape3[v])
+    along = R.axis_coords(origin3[axis], step3[axis], shape3[axis])
+    n = shape3[axis]
+    heights = [along[n // 2], along[n // 5], along[n // 2 + 1], along[n - 3]]
+    if "ulp" in label:
+        cu = R.axis_coords(origin3[0], step3[0], shape3[0])
+        assert len(np.unique(cu)) < 0.6 * len(cu)                              # coincident lattice coordinates along x
+    res.set_limits(LIM)
+    res.set_program(cc, w)
+    layers = oracle_layers(cc, w, axis, origin, step, shape, heights)
+    n_points = 0
+    for level in (0.0, 0.03):
+        s = check_slices(res, axis, origin, step, shape, heights, level, layers)
+        n_points += len(s.points)
+    assert n_points > 0, "no plane meets the surface: the lattice misses it"
 
 
 # ---- case coverage ---------------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """Sparse mesh extraction on the GPU (rm_extract_mesh_sparse): its arrays against the numpy restatement
 of the mesh contract (tests/mesh_ref.py on the oracle's lattice) and against the dense extraction, bit for bit; odd shapes;
-programs without a usable bound; random programs; a lattice beyond the dense limit; that culling really culls; errors and
-isolation."""
+programs without a usable bound; random programs; a lattice beyond the dense limit; that culling really culls; which bricks
+are kept, against the numpy model of the skipping rule (tests/sparse_ref.py), exactly; lattices far from the origin with steps
+down to the coordinates' ulp; errors and isolation."""
 import ctypes as C
 
 import numpy as np
@@ -9,7 +10,9 @@ import pytest
 
 import mesh_ref as R
 import scenes
+import sparse_ref
 import test_gpu_fuzz
+import test_mesh_bound_cpu as B
 from oracle import rm_oracle_np as onp
 from ray_marching_amd import _ffi, renderer
 
@@ -182,6 +185,79 @@ def test_fuzz_against_the_restatement(res, oracle, seed):
                          res.extract_mesh_grid(origin, step, shape, level=level))
     finally:
         res.set_materials(scenes.MATERIAL_TABLE)
+
+
+# ---- which bricks are kept -------------------------------------------------------------------------------------------------------
+def fuzz_program(oracle, seed):
+    """The program of test_fuzz_against_the_restatement's seed."""
+    rng = np.random.default_rng(7000 + seed)
+    t = scenes._Tab()
+    root = test_gpu_fuzz.random_tree(rng, t, int(rng.integers(1, 5)), allow_plane=bool(rng.random() < 0.4), tags=True)
+    return oracle.serialize(t.nodes, root)
+
+
+def kept_cases():
+    far = [("far " + label, 0.0) for label in B.far_lattices()]
+    return far + [(name, level) for name in ("g32", "xform_mix") for level in (0.0, 0.05)] + [("fuzz 7", 0.0), ("fuzz 10", 0.03)]
+
+
+@pytest.mark.parametrize("what, level", kept_cases())
+def test_kept_bricks_equal_the_model(res, oracle, what, level):
+    """BRICKS_KEPT and EVALUATIONS are those of tests/sparse_ref.py, exactly: the probe's distance is the oracle's bit for bit, the
+    lattice coordinates are single binary32 operations, and the radius, the margin and the two comparisons are IEEE binary64
+    operations (correctly rounded sqrt, no contraction) in one fixed order on both sides, so there is nothing to tolerate.  Fails
+    when the probe ignores 2 E, drops `2 E <= L r / 2`, sizes a border tile's radius like a full tile's, or when P is formed
+    differently (E scales with P)."""
+    if what.startswith("far "):
+        cc, w = B.far_program()
+        origin, step, shape = B.far_lattices()[what[4:]]
+    else:
+        cc, w = fuzz_program(oracle, int(what[5:])) if what.startswith("fuzz ") else oracle.serialize(*ALL_SCENES[what]())
+        origin, step, shape = cube(72)
+    res.set_limits(LIM)
+    res.set_program(cc, w)
+    res.set_materials(np.full((8, 3), 0.5, dtype=np.float32))                 # the fuzz programs' tags name indices up to 7
+    try:
+        m = res.extract_mesh_grid_sparse(origin, step, shape, level=level, normals=False, ids=False)
+    finally:
+        res.set_materials(scenes.MATERIAL_TABLE)
+    L, E = B.program_bound(cc, w, sparse_ref.lattice_P(origin, step, shape))
+    assert np.isfinite(L) and np.isfinite(E)
+    keep, evaluations = sparse_ref.brick_model(cc, w, origin, step, shape, level, L, E, max_dist=LIM[1])
+    s = check_stats(m, shape)
+    print("%s level %g: L = %.9g, E = %.3g; kept %d of %d bricks (model %d), %d evaluations (model %d)"
+          % (what, level, L, E, s["bricks_kept"], s["bricks"], int(np.count_nonzero(keep)), s["evaluations"], evaluations))
+    assert s["bricks"] == keep.size
+    assert s["bricks_kept"] == int(np.count_nonzero(keep))
+    assert s["evaluations"] == evaluations
+
+
+# ---- far from the origin, and steps near the coordinates' ulp --------------------------------------------------------------------
+def far_cases():
+    return dict(list(B.far_lattices().items()) + [("72 step 2^-15 (near ulp)", B.near_ulp_lattice())])
+
+
+@pytest.mark.parametrize("label", list(far_cases()))
+def test_far_from_the_origin_and_fine_steps(res, label):
+    """Coordinates of magnitude 800 with steps of 200 ulps down to half an ulp (lattice points that share a coordinate): the sparse
+    mesh is the restatement's on the oracle's lattice, and the dense mesh is the sparse one, attributes included."""
+    cc, w = B.far_program()
+    origin, step, shape = far_cases()[label]
+    res.set_limits(LIM)
+    res.set_program(cc, w)
+    dist = oracle_grid(cc, w, origin, step, shape)
+    if "ulp" in label:
+        xs = R.axis_coords(origin, step, shape)[0]
+        assert len(np.unique(xs)) < 0.6 * len(xs)                              # coincident lattice coordinates
+    assert len(R.extract(dist, origin, step, 0.0)[1]) > 0, "the restatement finds no surface: the lattice misses it"
+    for level in (0.0, 0.03):
+        m = check_vs_restatement(res, cc, w, origin, step, shape, level, dist)
+        dense = res.extract_mesh_grid(origin, step, shape, level=level)
+        sparse = res.extract_mesh_grid_sparse(origin, step, shape, level=level)
+        assert same(sparse.vertices, m.vertices) and same(sparse.triangles, m.triangles)
+        assert same_mesh(sparse, dense), (label, level)
+        if "2^-8" in label or "ulp" in label:                                  # 2 E > L r / 2: nothing may be skipped
+            assert sparse.stats["bricks_kept"] == sparse.stats["bricks"]
 
 
 # ---- beyond the dense limit ---------------------------------------------------------------------------------------------------
