@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -11,9 +12,11 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "rm_abi.h"
+#include "rm_abi_layout.h"
 #include "rm_decode.h"
 #include "rm_jit.h"
 #include "rm_device.h"
@@ -45,6 +48,59 @@ thread_local std::string g_create_error;
 #define RM_LIGHT_DEFAULTS {2.0f, -5.0f, 3.0f, 1.0f, 8.0f, 0.02f, 20.0f, 64.0f, 1.0f, 0.1f, 0.75f, 1.5f, 5.0f}
 const float kLightDefaults[RM_LIGHT_PARAMS] = RM_LIGHT_DEFAULTS;
 
+int fail(rm_ctx* c, int status, const char* fmt, ...);
+
+#define HIP_TRY(ctx, expr)                                                                         \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess)                                                                      \
+            return fail(ctx, RM_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                        __FILE__, __LINE__);                                                       \
+    } while (0)
+
+// An array of T in device memory, owned: freed when the context, or the call that made it, goes away.  It only ever grows
+// (scratch is allocated outside of any timed or captured region the first time a size is seen; later calls of the same size
+// allocate nothing).
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;  // in elements
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    template <class U>
+    U* as() const { return reinterpret_cast<U*>(p); }  // (the byte buffers: what they hold depends on the call)
+    // Room for `need` elements; contents are lost when the buffer moves (the old one goes first: never both at once).
+    int reserve(rm_ctx* c, size_t need, const char* what = "scratch") {
+        if (need <= cap) return RM_OK;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), need * sizeof(T));
+        if (e != hipSuccess) return fail(c, RM_ERR_DEVICE, "hipMalloc(%s) failed: %s", what, hipGetErrorString(e));
+        cap = need;
+        return RM_OK;
+    }
+    // reserve() for a result that is built batch by batch: the first `used` elements survive the move
+    int grow_keep(rm_ctx* c, size_t need, size_t used, hipStream_t s) {
+        if (need <= cap) return RM_OK;
+        DevBuf fresh;
+        if (hipMalloc(reinterpret_cast<void**>(&fresh.p), (need + need / 2u) * sizeof(T)) == hipSuccess) {
+            fresh.cap = need + need / 2u;
+        } else {
+            (void)hipGetLastError();
+            if (int rc = fresh.reserve(c, need)) return rc;
+        }
+        if (used) {
+            HIP_TRY(c, hipMemcpyAsync(fresh.p, p, used * sizeof(T), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(c, hipStreamSynchronize(s));
+        }
+        *this = std::move(fresh);  // (the old buffer goes with `fresh`)
+        return RM_OK;
+    }
+};
+
 }  // namespace
 
 struct rm_ctx {
@@ -71,59 +127,38 @@ struct rm_ctx {
     int cmd_status = RM_OK;
     // decoded program, device copy
     RmDecoded decoded;
-    RmRecord* d_prog = nullptr;
-    size_t d_prog_cap = 0;
-    float4* d_bounds = nullptr;  // world-space bounding spheres of a program with transforms (RmDecoded::bounds)
-    size_t d_bounds_cap = 0;
+    DevBuf<RmRecord> d_prog;
+    DevBuf<float4> d_bounds;  // world-space bounding spheres of a program with transforms (RmDecoded::bounds)
     // materials (extension): the tagged decoding of the program and the albedo table
-    RmRecord* d_mprog = nullptr;
-    size_t d_mprog_cap = 0;
+    DevBuf<RmRecord> d_mprog;
     std::vector<float4> materials{make_float4(0.4f, 0.7f, 0.1f, 0.0f)};  // wgsl:105
-    float4* d_materials = nullptr;  // RM_MAX_MATERIALS entries
+    DevBuf<float4> d_materials;  // RM_MAX_MATERIALS entries
     bool materials_dirty = true;
     // scene queries (rm_query.h): the query program (RmDecoded::qrec), uploaded by the first query after a program change
     // (prog_gen it belongs to in qprog_gen: draws never upload it), and the staging buffers of host-memory queries (never
     // the draws' scratch)
-    RmRecord* d_qprog = nullptr;
-    size_t d_qprog_cap = 0;
+    DevBuf<RmRecord> d_qprog;
     uint64_t qprog_gen = ~0ull;
-    void* d_qin = nullptr;
-    size_t d_qin_bytes = 0;
-    void* d_qout = nullptr;
-    size_t d_qout_bytes = 0;
+    DevBuf<char> d_qin, d_qout;
     size_t max_lds = 0;  // LDS a workgroup may allocate on this device
     // lit rendering (rm_light.h): enum rm_light, validated by rm_set_lighting; travels with each lit draw as kernel arguments
     float light[RM_LIGHT_PARAMS] = RM_LIGHT_DEFAULTS;
     // mesh export (rm_mesh.h): the extraction's scratch (distances, vertex bases, flags, block sums) and the last mesh
-    void* d_mscratch = nullptr;
-    size_t d_mscratch_bytes = 0;
-    void* d_mbricks = nullptr;  // sparse extraction (rm_mesh_sparse.h): the per-brick tables; d_mscratch holds the kept bricks' data
-    size_t d_mbricks_bytes = 0;
-    void* d_mesh = nullptr;
-    size_t d_mesh_bytes = 0;
+    DevBuf<char> d_mscratch;
+    DevBuf<char> d_mbricks;  // sparse extraction (rm_mesh_sparse.h): the per-brick tables; d_mscratch holds the kept bricks' data
+    DevBuf<char> d_mesh;
     bool mesh_valid = false;
     uint64_t mesh_v = 0, mesh_t = 0;
     uint32_t mesh_flags = 0;
     // slicing (rm_slice.h): the per-vertex scratch of a batch of layers (its per-point scratch is d_mscratch), the small
     // per-layer tables (heights, layer_first, the layers' first vertices, totals) and the last result, in buffers of its own
-    void* d_swork = nullptr;
-    size_t d_swork_bytes = 0;
-    void* d_slayers = nullptr;
-    size_t d_slayers_bytes = 0;
-    void* d_spoints = nullptr;
-    size_t d_spoints_bytes = 0;
-    void* d_scontours = nullptr;
-    size_t d_scontours_bytes = 0;
-    void* d_sattr = nullptr;
-    size_t d_sattr_bytes = 0;
+    DevBuf<char> d_swork, d_slayers, d_spoints, d_scontours, d_sattr;
     bool slice_valid = false;
     uint64_t slice_p = 0, slice_c = 0;
     uint32_t slice_layers = 0, slice_flags = 0;
     // scratch for host-destination draws and batch uniforms
-    float* d_out = nullptr;
-    size_t d_out_bytes = 0;
-    rm_uniforms* d_frames = nullptr;
-    size_t d_frames_cap = 0;
+    DevBuf<char> d_out;
+    DevBuf<rm_uniforms> d_frames;
     // options / info
     int kernel = RM_KERNEL_DEFAULT;
     uint32_t refill_min_v5 = 0;  // 0: by what the kernel does with coherent rays (launch_v5_w)
@@ -132,16 +167,12 @@ struct rm_ctx {
                       // 3 (default) longest tiles of the previous draw of the same shape first
     int waves_per_tile = 0;  // 0: by the size of the launch (launch_v5)
     bool wave_stats = false;
-    unsigned long long* d_stats = nullptr;
-    size_t d_stats_bytes = 0, stats_valid_bytes = 0;
-    uint32_t* d_cost = nullptr;   // per-tile cost estimates / dispatch order of the balance pre-pass
-    uint32_t* d_order = nullptr;
-    uint32_t* d_counters = nullptr;  // v5: {work-list length, cursor} per frame
-    uint32_t* d_measured = nullptr;  // v5, RM_OPT_BALANCE = 3: per-tile durations of the previous draw of the same shape
-    size_t d_measured_cap = 0;
-    uint64_t measured_shape = 0;     // hash of (W, rows, strips, frames) the measurements belong to; 0 = none yet
-    size_t d_counters_cap = 0;
-    size_t d_tiles_cap = 0;
+    DevBuf<unsigned long long> d_stats;
+    size_t stats_valid_bytes = 0;
+    DevBuf<uint32_t> d_cost, d_order;  // per-tile cost estimates / dispatch order of the balance pre-pass
+    DevBuf<uint32_t> d_counters;       // v5: {work-list length, cursor} per frame
+    DevBuf<uint32_t> d_measured;       // v5, RM_OPT_BALANCE = 3: per-tile durations of the previous draw of the same shape
+    uint64_t measured_shape = 0;       // hash of (W, rows, strips, frames) the measurements belong to; 0 = none yet
     bool timing = false;
     double last_kernel_ms = 0.0;
     // structure specialisation (rm_jit.h): 0 off, 1 compile in the background and switch over when
@@ -177,14 +208,6 @@ int fail(rm_ctx* c, int status, const char* fmt, ...) {
     else g_create_error = buf;
     return status;
 }
-
-#define HIP_TRY(ctx, expr)                                                                         \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(ctx, RM_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                                       \
-    } while (0)
 
 // Host data -> device scratch of the context, ordered on the stream the next draw is issued on (what
 // queue.write_buffer is to wgpu, renderer.rs:213-239): a draw of the previous program that is still queued or
@@ -230,60 +253,19 @@ int ensure_program(rm_ctx* c, hipStream_t s) {
     std::vector<RmRecord> image = d.rec;
     image.insert(image.end(), d.units.begin(), d.units.end());
     image.insert(image.end(), d.tree.begin(), d.tree.end());  // ... and the operand masks of a tree program's records (RmDecoded::tree)
-    if (image.size() > c->d_prog_cap) {
-        if (c->d_prog) (void)hipFree(c->d_prog);
-        c->d_prog = nullptr;
-        c->d_prog_cap = 0;
-        size_t cap = std::max<size_t>(64, image.size() * 2);
-        hipError_t e = hipMalloc(&c->d_prog, cap * sizeof(RmRecord));
-        if (e != hipSuccess) {
-            c->cmd_dirty = true;
-            return fail(c, RM_ERR_DEVICE, "hipMalloc(program) failed: %s", hipGetErrorString(e));
-        }
-        c->d_prog_cap = cap;
-    }
-    if (!image.empty()) {
-        if (int urc = upload(c, c->d_prog, image.data(), image.size() * sizeof(RmRecord), s)) {
-            c->cmd_dirty = true;
-            return urc;
-        }
-    }
-    if (!d.bounds.empty()) {
-        const size_t n = d.bounds.size() / 4u;
-        if (n > c->d_bounds_cap) {
-            if (c->d_bounds) (void)hipFree(c->d_bounds);
-            c->d_bounds = nullptr;
-            c->d_bounds_cap = 0;
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_bounds), std::max<size_t>(64, 2 * n) * sizeof(float4));
-            if (e != hipSuccess) {
-                c->cmd_dirty = true;
-                return fail(c, RM_ERR_DEVICE, "hipMalloc(bounds) failed: %s", hipGetErrorString(e));
-            }
-            c->d_bounds_cap = std::max<size_t>(64, 2 * n);
-        }
-        if (int urc = upload(c, c->d_bounds, d.bounds.data(), d.bounds.size() * sizeof(float), s)) {
-            c->cmd_dirty = true;
-            return urc;
-        }
-    }
-    if (!d.mrec.empty()) {
-        if (d.mrec.size() > c->d_mprog_cap) {
-            if (c->d_mprog) (void)hipFree(c->d_mprog);
-            c->d_mprog = nullptr;
-            c->d_mprog_cap = 0;
-            const size_t cap = std::max<size_t>(64, d.mrec.size() * 2);
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->d_mprog), cap * sizeof(RmRecord));
-            if (e != hipSuccess) {
-                c->cmd_dirty = true;
-                return fail(c, RM_ERR_DEVICE, "hipMalloc(material program) failed: %s", hipGetErrorString(e));
-            }
-            c->d_mprog_cap = cap;
-        }
-        if (int urc = upload(c, c->d_mprog, d.mrec.data(), d.mrec.size() * sizeof(RmRecord), s)) {
-            c->cmd_dirty = true;
-            return urc;
-        }
-    }
+    // device copies: room for twice what is needed (an edited scene grows record by record), then the stream-ordered upload;
+    // a program that did not arrive is decoded and sent again by the next draw
+    auto put = [&](auto& buf, const char* what, size_t n, const void* src, size_t bytes) {
+        int prc = n <= buf.cap ? RM_OK : buf.reserve(c, std::max<size_t>(64, 2 * n), what);
+        if (prc == RM_OK && bytes) prc = upload(c, buf.p, src, bytes, s);
+        if (prc != RM_OK) c->cmd_dirty = true;
+        return prc;
+    };
+    if (int prc = put(c->d_prog, "program", image.size(), image.data(), image.size() * sizeof(RmRecord))) return prc;
+    if (!d.bounds.empty())
+        if (int prc = put(c->d_bounds, "bounds", d.bounds.size() / 4u, d.bounds.data(), d.bounds.size() * sizeof(float))) return prc;
+    if (!d.mrec.empty())
+        if (int prc = put(c->d_mprog, "material program", d.mrec.size(), d.mrec.data(), d.mrec.size() * sizeof(RmRecord))) return prc;
     c->decoded = std::move(d);
     c->prog_gen++;
     c->cmd_status = RM_OK;
@@ -296,9 +278,9 @@ int ensure_materials(rm_ctx* c, hipStream_t s) {
     if (c->decoded.max_material >= c->materials.size())
         return fail(c, RM_ERR_MATERIAL, "the program tags a surface with material %u, the material table has %zu entries "
                     "(rm_set_materials)", c->decoded.max_material, c->materials.size());
-    if (!c->d_materials) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_materials), RM_MAX_MATERIALS * sizeof(float4)));
+    if (int rc = c->d_materials.reserve(c, RM_MAX_MATERIALS, "materials")) return rc;
     if (c->materials_dirty) {
-        if (int rc = upload(c, c->d_materials, c->materials.data(), c->materials.size() * sizeof(float4), s)) return rc;
+        if (int rc = upload(c, c->d_materials.p, c->materials.data(), c->materials.size() * sizeof(float4), s)) return rc;
         c->materials_dirty = false;
     }
     return RM_OK;
@@ -386,22 +368,9 @@ hipFunction_t specialised_kernel(rm_ctx* c, int wpt) {
     return static_cast<hipFunction_t>(l.function);
 }
 
-// Device scratch that only ever grows (allocated outside of any timed or captured region the first
-// time a size is seen; later draws of the same size allocate nothing).
-template <class T>
-int grow_device(rm_ctx* c, T** buf, size_t* cap, size_t need_elems) {
-    if (need_elems <= *cap) return RM_OK;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(buf), need_elems * sizeof(T)));
-    *cap = need_elems;
-    return RM_OK;
-}
-int ensure_tile_buffers(rm_ctx* c, size_t n_tiles_total);
 int ensure_stats(rm_ctx* c, RmLaunch& L, size_t n_waves);
 
-int finish_launch(rm_ctx* c, hipStream_t s);
+int finish_launch(rm_ctx* c);
 int time_begin(rm_ctx* c, hipStream_t s);
 int time_end(rm_ctx* c, hipStream_t s);
 
@@ -463,31 +432,32 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
                          (L.n_mrec != 0u ? 1024u : 0u);
     if (shmem > 64u * 1024u) return fail(c, RM_ERR_TOO_LARGE, "program needs %zu bytes of LDS per tile", shmem);
     // pre-pass buffers: cost + work list per tile, {count, cursor} per frame
-    if (int rc = ensure_tile_buffers(c, (size_t)n_tiles * n_frames)) return rc;
-    if (int rc = grow_device(c, &c->d_counters, &c->d_counters_cap, (size_t)n_frames * 4u)) return rc;
+    if (int rc = c->d_cost.reserve(c, (size_t)n_tiles * n_frames)) return rc;
+    if (int rc = c->d_order.reserve(c, (size_t)n_tiles * n_frames)) return rc;
+    if (int rc = c->d_counters.reserve(c, (size_t)n_frames * 4u)) return rc;
     const uint32_t pre_tiles_per_group = rmk::V5_PRE_TILES * rmk::V5_PRE_TILES_PER_WAVE;
     hipLaunchKernelGGL(rmk::rm_tile_pre_v5, dim3((n_tiles + pre_tiles_per_group - 1u) / pre_tiles_per_group, 1, n_frames),
-                       dim3(64u * rmk::V5_PRE_TILES), 16u + cull_bytes + (size_t)(L.n_cone + L.n_slab) * 8u, s, L, c->d_cost, n_tiles);
+                       dim3(64u * rmk::V5_PRE_TILES), 16u + cull_bytes + (size_t)(L.n_cone + L.n_slab) * 8u, s, L, c->d_cost.p, n_tiles);
     // RM_OPT_BALANCE = 3: the march kernel records how long every tile took; the next draw of the same shape
     // dispatches the longest first (consecutive frames of an interactive view or an orbit look alike)
     const uint32_t* prev = nullptr;
     uint32_t* measured = nullptr;
     if (c->balance == 3) {
         const size_t need = (size_t)n_tiles * n_frames;
-        if (need > c->d_measured_cap) {
-            if (int rc = grow_device(c, &c->d_measured, &c->d_measured_cap, need)) return rc;
+        if (need > c->d_measured.cap) {
+            if (int rc = c->d_measured.reserve(c, need)) return rc;
             c->measured_shape = 0;
         }
         const uint64_t shape = ((uint64_t)L.W << 40) ^ ((uint64_t)L.rows << 20) ^ ((uint64_t)L.strip_rows << 12) ^
                                ((uint64_t)L.strip_first << 6) ^ (uint64_t)L.strip_stride ^ ((uint64_t)n_frames << 52) ^ 1ull;
-        if (c->measured_shape == shape) prev = c->d_measured;
-        else HIP_TRY(c, hipMemsetAsync(c->d_measured, 0, need * sizeof(uint32_t), s));
+        if (c->measured_shape == shape) prev = c->d_measured.p;
+        else HIP_TRY(c, hipMemsetAsync(c->d_measured.p, 0, need * sizeof(uint32_t), s));
         c->measured_shape = shape;
-        measured = c->d_measured;
+        measured = c->d_measured.p;
     }
-    hipLaunchKernelGGL(rmk::rm_tile_sort_v5, dim3(n_frames), dim3(1024), 0, s, L, c->d_cost, c->d_order, c->d_counters,
+    hipLaunchKernelGGL(rmk::rm_tile_sort_v5, dim3(n_frames), dim3(1024), 0, s, L, c->d_cost.p, c->d_order.p, c->d_counters.p,
                        n_tiles, (uint32_t)c->balance, prev);
-    rmk::V5Work work{c->d_order, c->d_counters, measured};
+    rmk::V5Work work{c->d_order.p, c->d_counters.p, measured};
     // persistent grid: about as many workgroups as fit the chip (LDS, 32 waves per CU), never more than tiles
     uint32_t per_cu = (uint32_t)std::min<size_t>(32u / WPT, (160u * 1024u) / shmem);
     if (per_cu < 1u) per_cu = 1u;
@@ -532,7 +502,7 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
     else
         hipLaunchKernelGGL((rmk::rm_render_v5<rmk::ProgSmem, false, WPT, true>), grid, dim3(64 * WPT), shmem, s, L, work, n_tiles, refill_auto);
     if (int rc = time_end(c, s)) return rc;
-    return finish_launch(c, s);
+    return finish_launch(c);
 }
 
 int launch_v5(rm_ctx* c, const RmLaunch& L, bool lds, uint32_t n_frames, hipStream_t s) {
@@ -566,7 +536,7 @@ int launch(rm_ctx* c, const rm_uniforms* frames_dev, uint32_t n_frames, uint32_t
            uint32_t rows, float* d_out, hipStream_t s, StripSpec strips = StripSpec()) {
     RmLaunch L;
     L.strip_rows = strips.rows; L.strip_first = strips.first; L.strip_stride = strips.stride;
-    L.prog = c->d_prog;
+    L.prog = c->d_prog.p;
     L.n_rec = (uint32_t)c->decoded.rec.size();
     L.n_grp = (uint32_t)c->decoded.units.size();
     L.n_tree = 0u;  // (set by launch_v5_w when the interpreter runs the masked tree loop)
@@ -574,11 +544,11 @@ int launch(rm_ctx* c, const rm_uniforms* frames_dev, uint32_t n_frames, uint32_t
     L.unit_kmax = c->decoded.unit_kmax;
     L.value_spill_depth = c->decoded.spill_depth;
     L.spill_depth = c->decoded.spill_depth + 3u * c->decoded.xform_depth;  // saved positions follow the value stack
-    L.bounds = c->decoded.has_xforms ? c->d_bounds : nullptr;
-    L.mprog = c->d_mprog;
+    L.bounds = c->decoded.has_xforms ? c->d_bounds.p : nullptr;
+    L.mprog = c->d_mprog.p;
     L.n_mrec = (uint32_t)c->decoded.mrec.size();
     L.mat_value_depth = c->decoded.mat_spill_depth;
-    L.materials = c->d_materials;
+    L.materials = c->d_materials.p;
     L.n_cull = 0;
     L.flags = 0;
     L.n_cone = c->decoded.n_sphere;
@@ -611,22 +581,14 @@ int launch(rm_ctx* c, const rm_uniforms* frames_dev, uint32_t n_frames, uint32_t
         hipLaunchKernelGGL(rmk::rm_render_pixel, grid, dim3(256), shmem, s, L);
     }
     if (int rc = time_end(c, s)) return rc;
-    return finish_launch(c, s);
+    return finish_launch(c);
 }
 
-int ensure_tile_buffers(rm_ctx* c, size_t n_tiles_total) {
-    size_t cap = c->d_tiles_cap;
-    if (int rc = grow_device(c, &c->d_cost, &cap, n_tiles_total)) return rc;
-    if (int rc = grow_device(c, &c->d_order, &c->d_tiles_cap, n_tiles_total)) return rc;
-    return RM_OK;
-}
 int ensure_stats(rm_ctx* c, RmLaunch& L, size_t n_waves) {
     if (!c->wave_stats) return RM_OK;
-    size_t cap = c->d_stats_bytes / sizeof(unsigned long long);  // in u64 elements
-    if (int rc = grow_device(c, &c->d_stats, &cap, n_waves * 4u)) return rc;
-    c->d_stats_bytes = cap * sizeof(unsigned long long);
+    if (int rc = c->d_stats.reserve(c, n_waves * 4u)) return rc;
     c->stats_valid_bytes = n_waves * 4u * sizeof(unsigned long long);
-    L.stats = c->d_stats;
+    L.stats = c->d_stats.p;
     return RM_OK;
 }
 
@@ -649,7 +611,7 @@ int time_end(rm_ctx* c, hipStream_t s) {
     return RM_OK;
 }
 
-int finish_launch(rm_ctx* c, hipStream_t s) {
+int finish_launch(rm_ctx* c) {
     HIP_TRY(c, hipGetLastError());
     return RM_OK;
 }
@@ -709,13 +671,62 @@ void order_with_previous(rm_ctx* c, hipStream_t s) {
 
 size_t pixel_bytes(const rm_ctx* c) { return c->out_format == RM_FORMAT_RGBA32F ? 16u : 4u; }
 
-int ensure_out(rm_ctx* c, size_t bytes) {
-    if (bytes <= c->d_out_bytes) return RM_OK;
-    if (c->d_out) (void)hipFree(c->d_out);
-    c->d_out = nullptr;
-    c->d_out_bytes = 0;
-    HIP_TRY(c, hipMalloc(&c->d_out, bytes));
-    c->d_out_bytes = bytes;
+// The stream an entry point works on: results for host memory are staged and copied on the context's own stream.
+hipStream_t dest_stream(const rm_ctx* c, int is_device, void* stream) { return is_device ? user_stream(c, stream) : c->stream; }
+
+// The outputs of an entry point whose destination is device memory (the kernel writes the caller's arrays, asynchronously on
+// the caller's stream) or host memory: then the kernel writes one of the context's staging buffers -- d_out for the draws,
+// d_qout for the queries (never the draws' scratch) --, and finish() copies every output back and waits for the stream.  add()
+// the outputs, reserve(), launch with dev(i), finish().  An output the caller passed as NULL stays NULL for the kernel.
+struct Outputs {
+    rm_ctx* c;
+    bool to_host;
+    DevBuf<char>& staging;
+    struct Out { void* user; size_t offset, bytes; } out[3] = {};
+    int n = 0;
+    size_t total = 0;
+    Outputs(rm_ctx* c, int is_device, DevBuf<char>& staging) : c(c), to_host(!is_device), staging(staging) {}
+    void add(void* user, size_t bytes) {
+        assert(n < 3);
+        out[n++] = Out{user, total, bytes};
+        if (user) total += rml::align16(bytes);
+    }
+    int reserve() { return to_host ? staging.reserve(c, total) : RM_OK; }
+    template <class T>
+    T* dev(int i) const { return static_cast<T*>(to_host && out[i].user ? staging.p + out[i].offset : out[i].user); }
+    int finish(hipStream_t s) const {
+        if (!to_host) return RM_OK;
+        for (int i = 0; i < n; i++)
+            if (out[i].user) HIP_TRY(c, hipMemcpyAsync(out[i].user, staging.p + out[i].offset, out[i].bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        return RM_OK;
+    }
+};
+
+// What rm_draw, rm_draw_strips and rm_draw_batch do before they launch, on the stream *s they draw on.
+int draw_begin(rm_ctx* c, int out_is_device, void* stream, hipStream_t* s) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    *s = dest_stream(c, out_is_device, stream);
+    order_with_previous(c, *s);
+    int rc = ensure_program(c, *s);
+    if (rc == RM_OK) rc = ensure_materials(c, *s);
+    if (rc == RM_OK) rc = check_limits(c);
+    return rc;
+}
+
+// ... and after: the launch into the caller's device memory, or into d_out and from there to the caller's host memory.
+int draw_launch(rm_ctx* c, const rm_uniforms* frames_dev, uint32_t n_frames, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                float* out_rgba, int out_is_device, hipStream_t s, StripSpec strips = StripSpec()) {
+    Outputs o(c, out_is_device, c->d_out);
+    o.add(out_rgba, (size_t)n_frames * rows * W * pixel_bytes(c));
+    int rc = o.reserve();
+    if (rc == RM_OK) rc = launch(c, frames_dev, n_frames, W, H, row0, rows, o.dev<float>(0), s, strips);
+    return rc == RM_OK ? o.finish(s) : rc;
+}
+
+int check_strips(rm_ctx* c, const char* fn, uint32_t strip_rows, uint32_t first, uint32_t stride) {
+    if (strip_rows == 0u || (strip_rows % 8u) != 0u || stride == 0u || first >= stride)
+        return fail(c, RM_ERR_ARG, "%s: strip_rows %u must be a positive multiple of 8, first %u < stride %u", fn, strip_rows, first, stride);
     return RM_OK;
 }
 
@@ -763,28 +774,6 @@ RM_EXPORT void rm_destroy(rm_ctx* c) {
     if (!c) return;
     if (c->device >= 0) (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->d_prog) (void)hipFree(c->d_prog);
-    if (c->d_out) (void)hipFree(c->d_out);
-    if (c->d_frames) (void)hipFree(c->d_frames);
-    if (c->d_stats) (void)hipFree(c->d_stats);
-    if (c->d_cost) (void)hipFree(c->d_cost);
-    if (c->d_order) (void)hipFree(c->d_order);
-    if (c->d_counters) (void)hipFree(c->d_counters);
-    if (c->d_measured) (void)hipFree(c->d_measured);
-    if (c->d_bounds) (void)hipFree(c->d_bounds);
-    if (c->d_mprog) (void)hipFree(c->d_mprog);
-    if (c->d_materials) (void)hipFree(c->d_materials);
-    if (c->d_qprog) (void)hipFree(c->d_qprog);
-    if (c->d_qin) (void)hipFree(c->d_qin);
-    if (c->d_qout) (void)hipFree(c->d_qout);
-    if (c->d_mscratch) (void)hipFree(c->d_mscratch);
-    if (c->d_mbricks) (void)hipFree(c->d_mbricks);
-    if (c->d_mesh) (void)hipFree(c->d_mesh);
-    if (c->d_swork) (void)hipFree(c->d_swork);
-    if (c->d_slayers) (void)hipFree(c->d_slayers);
-    if (c->d_spoints) (void)hipFree(c->d_spoints);
-    if (c->d_scontours) (void)hipFree(c->d_scontours);
-    if (c->d_sattr) (void)hipFree(c->d_sattr);
     for (auto& st : c->staging) {
         if (st.host) (void)hipHostFree(st.host);
         if (st.done) (void)hipEventDestroy(st.done);
@@ -794,6 +783,8 @@ RM_EXPORT void rm_destroy(rm_ctx* c) {
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev_order) (void)hipEventDestroy(c->ev_order);
     if (c->stream) (void)hipStreamDestroy(c->stream);
+    // the device buffers go with the context, after the stream on purpose: it was synchronised above, hipFree waits for the
+    // device, and no buffer refers to the stream or to an event
     delete c;
 }
 
@@ -909,34 +900,9 @@ RM_EXPORT int rm_draw(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, uint32_t
     if (!out_rgba) return fail(c, RM_ERR_NULL, "rm_draw: out_rgba is NULL");
     int rc = check_dims(c, W, H, row0, rows);
     if (rc != RM_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = out_is_device ? user_stream(c, stream) : c->stream;
-    order_with_previous(c, s);
-    rc = ensure_program(c, s);
-    if (rc == RM_OK) rc = ensure_materials(c, s);
-    if (rc != RM_OK) return rc;
-    rc = check_limits(c);
-    if (rc != RM_OK) return rc;
-    const size_t bytes = (size_t)rows * W * pixel_bytes(c);
-    if (out_is_device) return launch(c, nullptr, 1, W, H, row0, rows, out_rgba, s);
-    rc = ensure_out(c, bytes);
-    if (rc != RM_OK) return rc;
-    rc = launch(c, nullptr, 1, W, H, row0, rows, c->d_out, s);
-    if (rc != RM_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out_rgba, c->d_out, bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
-}
-
-// Output rows of the strips first, first+stride, ... (strip_rows rows each) of an H-row image.
-static uint32_t strip_row_count(uint32_t H, uint32_t strip_rows, uint32_t first, uint32_t stride) {
-    const uint32_t n_strips = (H + strip_rows - 1u) / strip_rows;
-    uint32_t rows = 0;
-    for (uint32_t sidx = first; sidx < n_strips; sidx += stride) {
-        const uint32_t r0 = sidx * strip_rows;
-        rows += H - r0 < strip_rows ? H - r0 : strip_rows;
-    }
-    return rows;
+    hipStream_t s;
+    if ((rc = draw_begin(c, out_is_device, stream, &s)) != RM_OK) return rc;
+    return draw_launch(c, nullptr, 1, W, H, row0, rows, out_rgba, out_is_device, s);
 }
 
 RM_EXPORT int rm_draw_strips(rm_ctx* c, uint32_t W, uint32_t H, uint32_t strip_rows, uint32_t first, uint32_t stride,
@@ -945,31 +911,16 @@ RM_EXPORT int rm_draw_strips(rm_ctx* c, uint32_t W, uint32_t H, uint32_t strip_r
     if (!out_rows) return fail(c, RM_ERR_NULL, "rm_draw_strips: out_rows is NULL");
     int rc = check_dims(c, W, H, 0, H);
     if (rc != RM_OK) return rc;
-    if (strip_rows == 0u || (strip_rows % 8u) != 0u || stride == 0u || first >= stride)
-        return fail(c, RM_ERR_ARG, "rm_draw_strips: strip_rows %u must be a positive multiple of 8, first %u < stride %u",
-                    strip_rows, first, stride);
-    const uint32_t rows = strip_row_count(H, strip_rows, first, stride);
+    if ((rc = check_strips(c, "rm_draw_strips", strip_rows, first, stride)) != RM_OK) return rc;
+    const uint32_t rows = rml::strip_row_count(H, strip_rows, first, stride);
     *out_rows = rows;
     if (rows == 0u) return RM_OK;  // more ranks than strips: nothing to do for this one
     if (!out_rgba) return fail(c, RM_ERR_NULL, "rm_draw_strips: out_rgba is NULL");
-    HIP_TRY(c, hipSetDevice(c->device));
-    order_with_previous(c, out_is_device ? user_stream(c, stream) : c->stream);
-    rc = ensure_program(c, out_is_device ? user_stream(c, stream) : c->stream);
-    if (rc == RM_OK) rc = ensure_materials(c, out_is_device ? user_stream(c, stream) : c->stream);
-    if (rc != RM_OK) return rc;
-    rc = check_limits(c);
-    if (rc != RM_OK) return rc;
+    hipStream_t s;
+    if ((rc = draw_begin(c, out_is_device, stream, &s)) != RM_OK) return rc;
     StripSpec sp;
     sp.rows = strip_rows; sp.first = first; sp.stride = stride;
-    const size_t bytes = (size_t)rows * W * pixel_bytes(c);
-    if (out_is_device) return launch(c, nullptr, 1, W, H, 0, rows, out_rgba, user_stream(c, stream), sp);
-    rc = ensure_out(c, bytes);
-    if (rc != RM_OK) return rc;
-    rc = launch(c, nullptr, 1, W, H, 0, rows, c->d_out, c->stream, sp);
-    if (rc != RM_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out_rgba, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return RM_OK;
+    return draw_launch(c, nullptr, 1, W, H, 0, rows, out_rgba, out_is_device, s, sp);
 }
 
 // The final host-side gather of a tiled frame (north-star): this GPU's strips go from the compact device
@@ -979,9 +930,7 @@ RM_EXPORT int rm_gather_strips(rm_ctx* c, uint32_t W, uint32_t H, uint32_t strip
     if (!c) return RM_ERR_NULL;
     int rc = check_dims(c, W, H, 0, H);
     if (rc != RM_OK) return rc;
-    if (strip_rows == 0u || (strip_rows % 8u) != 0u || stride == 0u || first >= stride)
-        return fail(c, RM_ERR_ARG, "rm_gather_strips: strip_rows %u must be a positive multiple of 8, first %u < stride %u",
-                    strip_rows, first, stride);
+    if ((rc = check_strips(c, "rm_gather_strips", strip_rows, first, stride)) != RM_OK) return rc;
     const uint32_t n_strips = (H + strip_rows - 1u) / strip_rows;
     if (first >= n_strips) return RM_OK;  // this GPU has no strip
     if (!strips_device || !host_image) return fail(c, RM_ERR_NULL, "rm_gather_strips: NULL buffer");
@@ -1044,32 +993,12 @@ RM_EXPORT int rm_draw_batch(rm_ctx* c, const rm_uniforms* frames, uint32_t n_fra
     if (n_frames == 0 || n_frames > 65535u) return fail(c, RM_ERR_RANGE, "rm_draw_batch: n_frames %u not in [1,65535]", n_frames);
     int rc = check_dims(c, W, H, 0, H);
     if (rc != RM_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = out_is_device ? user_stream(c, stream) : c->stream;
-    order_with_previous(c, s);
-    rc = ensure_program(c, s);
-    if (rc == RM_OK) rc = ensure_materials(c, s);
+    hipStream_t s;
+    if ((rc = draw_begin(c, out_is_device, stream, &s)) != RM_OK) return rc;
+    if ((rc = c->d_frames.reserve(c, n_frames)) != RM_OK) return rc;
+    rc = upload(c, c->d_frames.p, frames, (size_t)n_frames * sizeof(rm_uniforms), s);
     if (rc != RM_OK) return rc;
-    rc = check_limits(c);
-    if (rc != RM_OK) return rc;
-    if (n_frames > c->d_frames_cap) {
-        if (c->d_frames) (void)hipFree(c->d_frames);
-        c->d_frames = nullptr;
-        c->d_frames_cap = 0;
-        HIP_TRY(c, hipMalloc(&c->d_frames, (size_t)n_frames * sizeof(rm_uniforms)));
-        c->d_frames_cap = n_frames;
-    }
-    rc = upload(c, c->d_frames, frames, (size_t)n_frames * sizeof(rm_uniforms), s);
-    if (rc != RM_OK) return rc;
-    const size_t bytes = (size_t)n_frames * H * W * pixel_bytes(c);
-    if (out_is_device) return launch(c, c->d_frames, n_frames, W, H, 0, H, out_rgba, s);
-    rc = ensure_out(c, bytes);
-    if (rc != RM_OK) return rc;
-    rc = launch(c, c->d_frames, n_frames, W, H, 0, H, c->d_out, s);
-    if (rc != RM_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out_rgba, c->d_out, bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+    return draw_launch(c, c->d_frames.p, n_frames, W, H, 0, H, out_rgba, out_is_device, s);
 }
 
 // ---- scene queries (rm_query.h) -----------------------------------------------------------------------------------------
@@ -1082,16 +1011,15 @@ int query_loop(const RmDecoded& d) {
     return rmk::Q_LOOP_GENERAL;
 }
 
-int grow_bytes(rm_ctx* c, void** buf, size_t* cap, size_t need) {
-    if (need <= *cap) return RM_OK;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    HIP_TRY(c, hipMalloc(buf, need));
-    *cap = need;
-    return RM_OK;
+// A record loop as a compile-time constant: f(std::integral_constant<int, LOOP>) for the run-time `loop`, so that every kernel
+// template with a LOOP parameter is chosen in one place.
+template <class F>
+auto with_loop(int loop, F&& f) {
+    if (loop == rmk::Q_LOOP_CHAIN) return f(std::integral_constant<int, rmk::Q_LOOP_CHAIN>());
+    if (loop == rmk::Q_LOOP_TREE) return f(std::integral_constant<int, rmk::Q_LOOP_TREE>());
+    return f(std::integral_constant<int, rmk::Q_LOOP_GENERAL>());
 }
-size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
+
 // Device arrays of a query are read and written with vector accesses of their element size: floats 4 B, the (leaf, material)
 // pairs of rm_query_points 8 B, the hit records and id quadruples of rm_cast_rays 16 B.  A pointer off that alignment is refused.
 bool misaligned(const void* p, uintptr_t align) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & (align - 1u)) != 0u; }
@@ -1111,16 +1039,10 @@ int query_begin(rm_ctx* c, hipStream_t s, bool walk, bool rgb, rmk::QueryLaunch*
     // the query program of this decoding, stream-ordered like the draws' images (a query still queued on an earlier stream
     // keeps the previous one: order_with_previous above made this stream wait for it)
     if (c->qprog_gen != c->prog_gen) {
-        if (d.qrec.size() > c->d_qprog_cap) {
-            if (c->d_qprog) (void)hipFree(c->d_qprog);
-            c->d_qprog = nullptr;
-            c->d_qprog_cap = 0;
-            const size_t cap = std::max<size_t>(64, d.qrec.size() * 2);
-            HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_qprog), cap * sizeof(RmRecord)));
-            c->d_qprog_cap = cap;
-        }
+        if (d.qrec.size() > c->d_qprog.cap)
+            if ((rc = c->d_qprog.reserve(c, std::max<size_t>(64, d.qrec.size() * 2), "query program")) != RM_OK) return rc;
         if (!d.qrec.empty())
-            if (int urc = upload(c, c->d_qprog, d.qrec.data(), d.qrec.size() * sizeof(RmRecord), s)) return urc;
+            if (int urc = upload(c, c->d_qprog.p, d.qrec.data(), d.qrec.size() * sizeof(RmRecord), s)) return urc;
         c->qprog_gen = c->prog_gen;
     }
     *loop = query_loop(d);
@@ -1129,8 +1051,8 @@ int query_begin(rm_ctx* c, hipStream_t s, bool walk, bool rgb, rmk::QueryLaunch*
     *shmem = (size_t)slots * 64u * 4u * 4u;
     const size_t cap = std::max<size_t>(c->max_lds, 64u * 1024u);
     if (*shmem > cap) return fail(c, RM_ERR_TOO_LARGE, "the query needs %zu bytes of LDS per workgroup", *shmem);
-    Q->prog = c->d_prog;
-    Q->qprog = c->d_qprog;
+    Q->prog = c->d_prog.p;
+    Q->qprog = c->d_qprog.p;
     Q->n_rec = (uint32_t)d.rec.size();
     Q->n_qrec = (uint32_t)d.qrec.size();
     Q->value_spill_depth = d.spill_depth;
@@ -1140,7 +1062,7 @@ int query_begin(rm_ctx* c, hipStream_t s, bool walk, bool rgb, rmk::QueryLaunch*
     Q->min_dist = c->limits.min_dist;
     Q->max_dist = c->limits.max_dist;
     Q->max_iter = c->limits.max_iter;
-    Q->materials = rgb && d.has_materials ? c->d_materials : nullptr;
+    Q->materials = rgb && d.has_materials ? c->d_materials.p : nullptr;
     return RM_OK;
 }
 
@@ -1154,23 +1076,39 @@ int query_launch(rm_ctx* c, K kernel, size_t count, size_t shmem, hipStream_t s,
 }
 
 using PointsFn = void (*)(rmk::QueryLaunch, uint32_t, const float*, float*, float*, uint32_t*);
-template <int LOOP>
-PointsFn points_kernel(bool dist, bool normal, bool ids) {
-    switch ((dist ? 1 : 0) | (normal ? 2 : 0) | (ids ? 4 : 0)) {
-    case 1: return rmk::rm_query_points_kernel<LOOP, true, false, false>;
-    case 2: return rmk::rm_query_points_kernel<LOOP, false, true, false>;
-    case 3: return rmk::rm_query_points_kernel<LOOP, true, true, false>;
-    case 4: return rmk::rm_query_points_kernel<LOOP, false, false, true>;
-    case 5: return rmk::rm_query_points_kernel<LOOP, true, false, true>;
-    case 6: return rmk::rm_query_points_kernel<LOOP, false, true, true>;
-    default: return rmk::rm_query_points_kernel<LOOP, true, true, true>;
-    }
+PointsFn points_kernel(int loop, bool dist, bool normal, bool ids) {
+    return with_loop(loop, [&](auto tag) -> PointsFn {
+        constexpr int LOOP = decltype(tag)::value;
+        switch ((dist ? 1 : 0) | (normal ? 2 : 0) | (ids ? 4 : 0)) {
+        case 1: return rmk::rm_query_points_kernel<LOOP, true, false, false>;
+        case 2: return rmk::rm_query_points_kernel<LOOP, false, true, false>;
+        case 3: return rmk::rm_query_points_kernel<LOOP, true, true, false>;
+        case 4: return rmk::rm_query_points_kernel<LOOP, false, false, true>;
+        case 5: return rmk::rm_query_points_kernel<LOOP, true, false, true>;
+        case 6: return rmk::rm_query_points_kernel<LOOP, false, true, true>;
+        default: return rmk::rm_query_points_kernel<LOOP, true, true, true>;
+        }
+    });
 }
 using RaysFn = void (*)(rmk::QueryLaunch, uint32_t, const float*, float*, uint32_t*, float*);
-template <int LOOP>
-RaysFn rays_kernel(bool taps, bool walk) {
-    if (!walk) return rmk::rm_cast_rays_kernel<LOOP, true, false>;
-    return taps ? rmk::rm_cast_rays_kernel<LOOP, true, true> : rmk::rm_cast_rays_kernel<LOOP, false, true>;
+RaysFn rays_kernel(int loop, bool taps, bool walk) {
+    return with_loop(loop, [&](auto tag) -> RaysFn {
+        constexpr int LOOP = decltype(tag)::value;
+        if (!walk) return rmk::rm_cast_rays_kernel<LOOP, true, false>;
+        return taps ? rmk::rm_cast_rays_kernel<LOOP, true, true> : rmk::rm_cast_rays_kernel<LOOP, false, true>;
+    });
+}
+
+// The input array of a query with outputs `o`: the caller's device array, or -- host memory: staged through the context's query
+// buffers, synchronously on its own stream -- its copy in d_qin.  Reserves the outputs' staging on the way.
+int query_input(rm_ctx* c, Outputs& o, const float* in, size_t bytes, hipStream_t s, const float** dev) {
+    *dev = in;
+    if (!o.to_host) return RM_OK;
+    if (int rc = c->d_qin.reserve(c, bytes)) return rc;
+    if (int rc = o.reserve()) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_qin.p, in, bytes, hipMemcpyHostToDevice, s));
+    *dev = c->d_qin.as<const float>();
+    return RM_OK;
 }
 
 }  // namespace
@@ -1184,32 +1122,21 @@ RM_EXPORT int rm_query_points(rm_ctx* c, uint32_t n, const float* xyz, float* ou
     if (is_device && (misaligned(xyz, 4) || misaligned(out_dist, 4) || misaligned(out_normal, 4) || misaligned(out_ids, 8)))
         return fail(c, RM_ERR_ARG, "rm_query_points: device arrays need 4-byte alignment (out_ids: 8-byte)");
     HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    const hipStream_t s = dest_stream(c, is_device, stream);
     rmk::QueryLaunch Q;
     int loop = 0;
     size_t shmem = 0;
     int rc = query_begin(c, s, out_ids != nullptr, false, &Q, &loop, &shmem);
     if (rc != RM_OK) return rc;
-    const PointsFn k = loop == rmk::Q_LOOP_CHAIN ? points_kernel<rmk::Q_LOOP_CHAIN>(out_dist, out_normal, out_ids)
-                     : loop == rmk::Q_LOOP_TREE ? points_kernel<rmk::Q_LOOP_TREE>(out_dist, out_normal, out_ids)
-                                                : points_kernel<rmk::Q_LOOP_GENERAL>(out_dist, out_normal, out_ids);
-    if (is_device) return query_launch(c, k, n, shmem, s, Q, n, xyz, out_dist, out_normal, out_ids);
-    // host memory: staged through the context's query buffers, synchronously on its own stream
-    const size_t in_b = (size_t)n * 12u, dist_b = out_dist ? align16((size_t)n * 4u) : 0u, nrm_b = out_normal ? align16((size_t)n * 12u) : 0u,
-                 ids_b = out_ids ? (size_t)n * 8u : 0u;
-    if ((rc = grow_bytes(c, &c->d_qin, &c->d_qin_bytes, in_b)) != RM_OK) return rc;
-    if ((rc = grow_bytes(c, &c->d_qout, &c->d_qout_bytes, dist_b + nrm_b + ids_b)) != RM_OK) return rc;
-    char* o = static_cast<char*>(c->d_qout);
-    float* d_dist = out_dist ? reinterpret_cast<float*>(o) : nullptr;
-    float* d_nrm = out_normal ? reinterpret_cast<float*>(o + dist_b) : nullptr;
-    uint32_t* d_ids = out_ids ? reinterpret_cast<uint32_t*>(o + dist_b + nrm_b) : nullptr;
-    HIP_TRY(c, hipMemcpyAsync(c->d_qin, xyz, in_b, hipMemcpyHostToDevice, s));
-    if ((rc = query_launch(c, k, n, shmem, s, Q, n, static_cast<const float*>(c->d_qin), d_dist, d_nrm, d_ids)) != RM_OK) return rc;
-    if (out_dist) HIP_TRY(c, hipMemcpyAsync(out_dist, d_dist, (size_t)n * 4u, hipMemcpyDeviceToHost, s));
-    if (out_normal) HIP_TRY(c, hipMemcpyAsync(out_normal, d_nrm, (size_t)n * 12u, hipMemcpyDeviceToHost, s));
-    if (out_ids) HIP_TRY(c, hipMemcpyAsync(out_ids, d_ids, ids_b, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+    Outputs o(c, is_device, c->d_qout);
+    o.add(out_dist, (size_t)n * 4u);
+    o.add(out_normal, (size_t)n * 12u);
+    o.add(out_ids, (size_t)n * 8u);
+    const float* d_xyz = nullptr;
+    if ((rc = query_input(c, o, xyz, (size_t)n * 12u, s, &d_xyz)) != RM_OK) return rc;
+    rc = query_launch(c, points_kernel(loop, out_dist, out_normal, out_ids), n, shmem, s, Q, n, d_xyz, o.dev<float>(0), o.dev<float>(1),
+                      o.dev<uint32_t>(2));
+    return rc == RM_OK ? o.finish(s) : rc;
 }
 
 RM_EXPORT int rm_cast_rays(rm_ctx* c, uint32_t n, const float* rays, float* out_hit, uint32_t* out_ids, float* out_rgb,
@@ -1221,7 +1148,7 @@ RM_EXPORT int rm_cast_rays(rm_ctx* c, uint32_t n, const float* rays, float* out_
     if (is_device && (misaligned(rays, 4) || misaligned(out_hit, 16) || misaligned(out_ids, 16) || misaligned(out_rgb, 4)))
         return fail(c, RM_ERR_ARG, "rm_cast_rays: device arrays need 4-byte alignment (out_hit, out_ids: 16-byte)");
     HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    const hipStream_t s = dest_stream(c, is_device, stream);
     rmk::QueryLaunch Q;
     int loop = 0;
     size_t shmem = 0;
@@ -1236,25 +1163,14 @@ RM_EXPORT int rm_cast_rays(rm_ctx* c, uint32_t n, const float* rays, float* out_
     }
     int rc = query_begin(c, s, walk, out_rgb != nullptr, &Q, &loop, &shmem);
     if (rc != RM_OK) return rc;
-    const RaysFn k = loop == rmk::Q_LOOP_CHAIN ? rays_kernel<rmk::Q_LOOP_CHAIN>(taps, walk)
-                   : loop == rmk::Q_LOOP_TREE ? rays_kernel<rmk::Q_LOOP_TREE>(taps, walk)
-                                              : rays_kernel<rmk::Q_LOOP_GENERAL>(taps, walk);
-    if (is_device) return query_launch(c, k, n, shmem, s, Q, n, rays, out_hit, out_ids, out_rgb);
-    const size_t in_b = (size_t)n * 24u, hit_b = out_hit ? (size_t)n * 32u : 0u, ids_b = out_ids ? (size_t)n * 16u : 0u,
-                 rgb_b = out_rgb ? (size_t)n * 12u : 0u;
-    if ((rc = grow_bytes(c, &c->d_qin, &c->d_qin_bytes, in_b)) != RM_OK) return rc;
-    if ((rc = grow_bytes(c, &c->d_qout, &c->d_qout_bytes, hit_b + ids_b + rgb_b)) != RM_OK) return rc;
-    char* o = static_cast<char*>(c->d_qout);
-    float* d_hit = out_hit ? reinterpret_cast<float*>(o) : nullptr;
-    uint32_t* d_ids = out_ids ? reinterpret_cast<uint32_t*>(o + hit_b) : nullptr;
-    float* d_rgb = out_rgb ? reinterpret_cast<float*>(o + hit_b + ids_b) : nullptr;
-    HIP_TRY(c, hipMemcpyAsync(c->d_qin, rays, in_b, hipMemcpyHostToDevice, s));
-    if ((rc = query_launch(c, k, n, shmem, s, Q, n, static_cast<const float*>(c->d_qin), d_hit, d_ids, d_rgb)) != RM_OK) return rc;
-    if (out_hit) HIP_TRY(c, hipMemcpyAsync(out_hit, d_hit, hit_b, hipMemcpyDeviceToHost, s));
-    if (out_ids) HIP_TRY(c, hipMemcpyAsync(out_ids, d_ids, ids_b, hipMemcpyDeviceToHost, s));
-    if (out_rgb) HIP_TRY(c, hipMemcpyAsync(out_rgb, d_rgb, rgb_b, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+    Outputs o(c, is_device, c->d_qout);
+    o.add(out_hit, (size_t)n * 32u);
+    o.add(out_ids, (size_t)n * 16u);
+    o.add(out_rgb, (size_t)n * 12u);
+    const float* d_rays = nullptr;
+    if ((rc = query_input(c, o, rays, (size_t)n * 24u, s, &d_rays)) != RM_OK) return rc;
+    rc = query_launch(c, rays_kernel(loop, taps, walk), n, shmem, s, Q, n, d_rays, o.dev<float>(0), o.dev<uint32_t>(1), o.dev<float>(2));
+    return rc == RM_OK ? o.finish(s) : rc;
 }
 
 RM_EXPORT int rm_camera_rays(rm_ctx* c, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
@@ -1269,16 +1185,13 @@ RM_EXPORT int rm_camera_rays(rm_ctx* c, uint32_t W, uint32_t H, uint32_t x0, uin
     if (sample > RM_SAMPLE_CENTER) return fail(c, RM_ERR_RANGE, "sample %u: 0..15 or RM_SAMPLE_CENTER (16)", sample);
     if (is_device && misaligned(out_rays, 4)) return fail(c, RM_ERR_ARG, "rm_camera_rays: out_rays needs 4-byte alignment");
     HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    const hipStream_t s = dest_stream(c, is_device, stream);
     order_with_previous(c, s);
-    if (is_device) return query_launch(c, rmk::rm_camera_rays_kernel, count, 0u, s, c->uniforms, W, H, x0, y0, w, count, sample, out_rays);
-    const size_t bytes = (size_t)count * 24u;
-    if (int rc = grow_bytes(c, &c->d_qout, &c->d_qout_bytes, bytes)) return rc;
-    float* d = static_cast<float*>(c->d_qout);
-    if (int rc = query_launch(c, rmk::rm_camera_rays_kernel, count, 0u, s, c->uniforms, W, H, x0, y0, w, count, sample, d)) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out_rays, d, bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+    Outputs o(c, is_device, c->d_qout);
+    o.add(out_rays, (size_t)count * 24u);
+    int rc = o.reserve();
+    if (rc == RM_OK) rc = query_launch(c, rmk::rm_camera_rays_kernel, count, 0u, s, c->uniforms, W, H, x0, y0, w, count, sample, o.dev<float>(0));
+    return rc == RM_OK ? o.finish(s) : rc;
 }
 
 // ---- lit rendering (rm_light.h) ------------------------------------------------------------------------------------------
@@ -1303,10 +1216,12 @@ int bad_light_param(const float* p) {
 }
 
 using LitFn = void (*)(rmk::QueryLaunch, rmk::LightLaunch, rmk::LitFrame);
-template <int LOOP>
-LitFn lit_kernel(bool shadow, bool ao) {
-    if (shadow) return ao ? rmk::rm_draw_lit_kernel<LOOP, true, true> : rmk::rm_draw_lit_kernel<LOOP, true, false>;
-    return ao ? rmk::rm_draw_lit_kernel<LOOP, false, true> : rmk::rm_draw_lit_kernel<LOOP, false, false>;
+LitFn lit_kernel(int loop, bool shadow, bool ao) {
+    return with_loop(loop, [&](auto tag) -> LitFn {
+        constexpr int LOOP = decltype(tag)::value;
+        if (shadow) return ao ? rmk::rm_draw_lit_kernel<LOOP, true, true> : rmk::rm_draw_lit_kernel<LOOP, true, false>;
+        return ao ? rmk::rm_draw_lit_kernel<LOOP, false, true> : rmk::rm_draw_lit_kernel<LOOP, false, false>;
+    });
 }
 
 }  // namespace
@@ -1335,7 +1250,7 @@ RM_EXPORT int rm_draw_lit(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, uint
     int rc = check_dims(c, W, H, row0, rows);
     if (rc != RM_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = out_is_device ? user_stream(c, stream) : c->stream;
+    const hipStream_t s = dest_stream(c, out_is_device, stream);
     order_with_previous(c, s);
     rc = ensure_program(c, s);  // (query_begin repeats both at no cost)
     if (rc != RM_OK) return rc;
@@ -1350,26 +1265,18 @@ RM_EXPORT int rm_draw_lit(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, uint
                        p[RM_LIGHT_BIAS], p[RM_LIGHT_SHADOW_MAX_T], (uint32_t)p[RM_LIGHT_SHADOW_STEPS], p[RM_LIGHT_AO],
                        p[RM_LIGHT_AO_STEP], p[RM_LIGHT_AO_FALLOFF], p[RM_LIGHT_AO_SCALE], (uint32_t)p[RM_LIGHT_AO_TAPS]};
     const bool shadow = P.shadow > 0.0f, ao = P.ao > 0.0f;
-    const LitFn k = loop == rmk::Q_LOOP_CHAIN ? lit_kernel<rmk::Q_LOOP_CHAIN>(shadow, ao)
-                  : loop == rmk::Q_LOOP_TREE ? lit_kernel<rmk::Q_LOOP_TREE>(shadow, ao)
-                                             : lit_kernel<rmk::Q_LOOP_GENERAL>(shadow, ao);
     rmk::LitFrame F;
     F.u = c->uniforms;
     F.W = W; F.H = H; F.row0 = row0; F.rows = rows;
     F.format = (uint32_t)c->out_format;
     const size_t lanes = (size_t)((W + 1u) / 2u) * ((rows + 1u) / 2u) * 64u;  // one wave per 2 x 2 block of pixels
-    if (out_is_device) {
-        F.out = out_rgba;
-        return query_launch(c, k, lanes, shmem, s, Q, P, F);
-    }
     // host memory: staged through the context's query buffer (never the draws' scratch), synchronously on its own stream
-    const size_t bytes = (size_t)rows * W * pixel_bytes(c);
-    if ((rc = grow_bytes(c, &c->d_qout, &c->d_qout_bytes, bytes)) != RM_OK) return rc;
-    F.out = c->d_qout;
-    if ((rc = query_launch(c, k, lanes, shmem, s, Q, P, F)) != RM_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out_rgba, c->d_qout, bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+    Outputs o(c, out_is_device, c->d_qout);
+    o.add(out_rgba, (size_t)rows * W * pixel_bytes(c));
+    if ((rc = o.reserve()) != RM_OK) return rc;
+    F.out = o.dev<void>(0);
+    rc = query_launch(c, lit_kernel(loop, shadow, ao), lanes, shmem, s, Q, P, F);
+    return rc == RM_OK ? o.finish(s) : rc;
 }
 
 // ---- G-buffer draw (rm_gbuffer.h) ----------------------------------------------------------------------------------------
@@ -1417,9 +1324,11 @@ RM_EXPORT int rm_program_subtree(uint32_t cmd_count, const uint32_t* words, uint
 
 namespace {
 using GBufferFn = void (*)(rmk::QueryLaunch, rmk::GBufferFrame);
-template <int LOOP>
-GBufferFn gbuffer_kernel(bool all) {
-    return all ? rmk::rm_draw_gbuffer_kernel<LOOP, true> : rmk::rm_draw_gbuffer_kernel<LOOP, false>;
+GBufferFn gbuffer_kernel(int loop, bool all) {
+    return with_loop(loop, [&](auto tag) -> GBufferFn {
+        constexpr int LOOP = decltype(tag)::value;
+        return all ? rmk::rm_draw_gbuffer_kernel<LOOP, true> : rmk::rm_draw_gbuffer_kernel<LOOP, false>;
+    });
 }
 }  // namespace
 
@@ -1436,7 +1345,7 @@ RM_EXPORT int rm_draw_gbuffer(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, 
     if (is_device && (misaligned(out_geom, 16) || misaligned(out_ids, 16) || misaligned(out_masks, 16)))
         return fail(c, RM_ERR_ARG, "rm_draw_gbuffer: device arrays need 16-byte alignment");
     HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    const hipStream_t s = dest_stream(c, is_device, stream);
     order_with_previous(c, s);
     rc = ensure_program(c, s);  // (query_begin repeats both at no cost)
     if (rc != RM_OK) return rc;
@@ -1450,9 +1359,6 @@ RM_EXPORT int rm_draw_gbuffer(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, 
     rc = query_begin(c, s, walk, false, &Q, &loop, &shmem);
     if (rc != RM_OK) return rc;
     const bool all = sample == (uint32_t)RM_SAMPLE_ALL;
-    const GBufferFn k = loop == rmk::Q_LOOP_CHAIN ? gbuffer_kernel<rmk::Q_LOOP_CHAIN>(all)
-                      : loop == rmk::Q_LOOP_TREE ? gbuffer_kernel<rmk::Q_LOOP_TREE>(all)
-                                                 : gbuffer_kernel<rmk::Q_LOOP_GENERAL>(all);
     rmk::GBufferFrame F;
     F.u = c->uniforms;
     F.W = W; F.H = H; F.row0 = row0; F.rows = rows;
@@ -1462,23 +1368,16 @@ RM_EXPORT int rm_draw_gbuffer(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, 
     F.walk = walk ? 1u : 0u;
     // one wave per 2 x 2 block of pixels (all samples), or per 8 x 8 tile (one sample)
     const size_t lanes = all ? (size_t)((W + 1u) / 2u) * ((rows + 1u) / 2u) * 64u : (size_t)((W + 7u) / 8u) * ((rows + 7u) / 8u) * 64u;
-    if (is_device) {
-        F.geom = out_geom; F.ids = out_ids; F.masks = out_masks;
-        return query_launch(c, k, lanes, shmem, s, Q, F);
-    }
     // host memory: staged through the context's query buffer (never the draws' scratch), synchronously on its own stream
-    const size_t n = (size_t)rows * W, geom_b = out_geom ? n * 32u : 0u, ids_b = out_ids ? n * 16u : 0u, masks_b = out_masks ? n * 16u : 0u;
-    if ((rc = grow_bytes(c, &c->d_qout, &c->d_qout_bytes, geom_b + ids_b + masks_b)) != RM_OK) return rc;
-    char* o = static_cast<char*>(c->d_qout);
-    F.geom = out_geom ? reinterpret_cast<float*>(o) : nullptr;
-    F.ids = out_ids ? reinterpret_cast<uint32_t*>(o + geom_b) : nullptr;
-    F.masks = out_masks ? reinterpret_cast<uint32_t*>(o + geom_b + ids_b) : nullptr;
-    if ((rc = query_launch(c, k, lanes, shmem, s, Q, F)) != RM_OK) return rc;
-    if (out_geom) HIP_TRY(c, hipMemcpyAsync(out_geom, F.geom, geom_b, hipMemcpyDeviceToHost, s));
-    if (out_ids) HIP_TRY(c, hipMemcpyAsync(out_ids, F.ids, ids_b, hipMemcpyDeviceToHost, s));
-    if (out_masks) HIP_TRY(c, hipMemcpyAsync(out_masks, F.masks, masks_b, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+    const size_t n = (size_t)rows * W;
+    Outputs o(c, is_device, c->d_qout);
+    o.add(out_geom, n * 32u);
+    o.add(out_ids, n * 16u);
+    o.add(out_masks, n * 16u);
+    if ((rc = o.reserve()) != RM_OK) return rc;
+    F.geom = o.dev<float>(0); F.ids = o.dev<uint32_t>(1); F.masks = o.dev<uint32_t>(2);
+    rc = query_launch(c, gbuffer_kernel(loop, all), lanes, shmem, s, Q, F);
+    return rc == RM_OK ? o.finish(s) : rc;
 }
 
 // ---- mesh export (rm_mesh.h) ---------------------------------------------------------------------------------------------
@@ -1500,47 +1399,47 @@ int check_lattice(rm_ctx* c, const char* fn, const float* origin, const float* s
 
 using GridFn = void (*)(rmk::QueryLaunch, float, float, float, float, float, float, uint32_t, uint32_t, uint64_t, float*);
 GridFn grid_kernel(int loop) {
-    return loop == rmk::Q_LOOP_CHAIN ? rmk::rm_grid_dist_kernel<rmk::Q_LOOP_CHAIN>
-         : loop == rmk::Q_LOOP_TREE ? rmk::rm_grid_dist_kernel<rmk::Q_LOOP_TREE>
-                                    : rmk::rm_grid_dist_kernel<rmk::Q_LOOP_GENERAL>;
+    return with_loop(loop, [](auto tag) -> GridFn { return rmk::rm_grid_dist_kernel<decltype(tag)::value>; });
 }
 int launch_grid(rm_ctx* c, const rmk::QueryLaunch& Q, int loop, size_t shmem, hipStream_t s, const float* o, const float* st,
                 uint32_t nx, uint32_t ny, uint64_t n, float* out) {
     return query_launch(c, grid_kernel(loop), n, shmem, s, Q, o[0], o[1], o[2], st[0], st[1], st[2], nx, ny, n, out);
 }
 
-// Where the arrays of a mesh of v vertices and t triangles lie in rm_ctx::d_mesh (16-byte aligned, in this order).
-struct MeshLayout {
-    size_t vertices, triangles, normals, ids, bytes;
-};
-MeshLayout mesh_layout(uint64_t v, uint64_t t, uint32_t flags) {
-    MeshLayout L{};
-    L.triangles = align16(v * 12u);
-    L.normals = L.triangles + align16(t * 12u);
-    L.ids = L.normals + ((flags & RM_MESH_NORMALS) ? align16(v * 12u) : 0u);
-    L.bytes = L.ids + ((flags & RM_MESH_IDS) ? v * 8u : 0u);
-    return L;
+// level and flags of the iso-surface entry points (rm_extract_mesh, rm_extract_mesh_sparse, rm_slice_contours)
+int check_iso(rm_ctx* c, const char* fn, float level, uint32_t flags) {
+    if (!std::isfinite(level)) return fail(c, RM_ERR_ARG, "%s: level %g is not finite", fn, (double)level);
+    if (flags & ~(uint32_t)(RM_MESH_NORMALS | RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "%s: unknown flags 0x%x", fn, flags);
+    return RM_OK;
 }
 
+// Where the arrays of a mesh of v vertices and t triangles lie in rm_ctx::d_mesh.
+rml::MeshLayout mesh_layout(uint64_t v, uint64_t t, uint32_t flags) {
+    return rml::MeshLayout(v, t, (flags & RM_MESH_NORMALS) != 0, (flags & RM_MESH_IDS) != 0);
+}
 
-// The attributes of a mesh's vertices: rm_query_points at the vertex positions, device to device.
-int mesh_attributes(rm_ctx* c, const rmk::QueryLaunch& Q, int loop, size_t shmem, hipStream_t s, uint32_t flags, uint64_t V, char* m,
-                    const MeshLayout& L) {
+// The attributes (regions of the buffer at `base`) of n points: rm_query_points at their positions, device to device.
+int point_attributes(rm_ctx* c, const rmk::QueryLaunch& Q, int loop, size_t shmem, hipStream_t s, uint32_t flags, uint64_t n,
+                     const float* points, char* base, const rml::Region<float>& nrm, const rml::Region<uint32_t>& idp) {
     const bool normals = (flags & RM_MESH_NORMALS) != 0, ids = (flags & RM_MESH_IDS) != 0;
-    if (!(normals || ids) || V == 0u) return RM_OK;
-    float* nrm = normals ? reinterpret_cast<float*>(m + L.normals) : nullptr;
-    uint32_t* idp = ids ? reinterpret_cast<uint32_t*>(m + L.ids) : nullptr;
-    const PointsFn k = loop == rmk::Q_LOOP_CHAIN ? points_kernel<rmk::Q_LOOP_CHAIN>(false, normals, ids)
-                     : loop == rmk::Q_LOOP_TREE ? points_kernel<rmk::Q_LOOP_TREE>(false, normals, ids)
-                                                : points_kernel<rmk::Q_LOOP_GENERAL>(false, normals, ids);
-    return query_launch(c, k, V, shmem, s, Q, (uint32_t)V, reinterpret_cast<const float*>(m + L.vertices), static_cast<float*>(nullptr), nrm,
-                        idp);
+    if (!(normals || ids) || n == 0u) return RM_OK;
+    return query_launch(c, points_kernel(loop, false, normals, ids), n, shmem, s, Q, (uint32_t)n, points, static_cast<float*>(nullptr),
+                        normals ? nrm.at(base) : nullptr, ids ? idp.at(base) : nullptr);
 }
 
 // ---- sparse extraction (rm_mesh_sparse.h) ----
 using ProbeFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, double, double, uint32_t*, unsigned long long*);
+ProbeFn sparse_probe_kernel(int loop) {
+    return with_loop(loop, [](auto tag) -> ProbeFn { return rmk::rm_sparse_probe_kernel<decltype(tag)::value>; });
+}
 using SparseCountFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, const uint32_t*, const uint32_t*, float*, rmk::SparseSegMap*,
                                uint32_t*, unsigned long long*);
+SparseCountFn sparse_count_kernel(int loop) {
+    return with_loop(loop, [](auto tag) -> SparseCountFn { return rmk::rm_sparse_count_kernel<decltype(tag)::value>; });
+}
+// The regions of the kept bricks' scratch round up to 16 bytes like all others; the segment maps and the segments' first
+// (vertex, triangle) pairs always were whole multiples of 16, so RM_MESH_STAT_SCRATCH_BYTES is what it was.
+static_assert(sizeof(rmk::SparseSegMap) % 16u == 0u && (rmk::kBrickSegs * sizeof(uint2)) % 16u == 0u, "sparse scratch layout");
 // One workgroup of `kernel` per grid entry, with the query's LDS columns behind the kernel's own LDS.
 template <class K, class... Args>
 int sparse_launch(rm_ctx* c, K kernel, uint32_t blocks, size_t shmem, hipStream_t s, Args... args) {
@@ -1563,19 +1462,17 @@ RM_EXPORT int rm_sample_grid(rm_ctx* c, const float* origin, const float* step, 
     if (!out_dist) return fail(c, RM_ERR_NULL, "rm_sample_grid: out_dist is NULL");
     if (is_device && misaligned(out_dist, 4)) return fail(c, RM_ERR_ARG, "rm_sample_grid: out_dist needs 4-byte alignment");
     HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    const hipStream_t s = dest_stream(c, is_device, stream);
     rmk::QueryLaunch Q;
     int loop = 0;
     size_t shmem = 0;
     int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);
     if (rc != RM_OK) return rc;
-    if (is_device) return launch_grid(c, Q, loop, shmem, s, origin, step, nx, ny, n, out_dist);
-    if ((rc = grow_bytes(c, &c->d_qout, &c->d_qout_bytes, n * 4u)) != RM_OK) return rc;
-    float* d = static_cast<float*>(c->d_qout);
-    if ((rc = launch_grid(c, Q, loop, shmem, s, origin, step, nx, ny, n, d)) != RM_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(out_dist, d, n * 4u, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+    Outputs o(c, is_device, c->d_qout);
+    o.add(out_dist, n * 4u);
+    if ((rc = o.reserve()) != RM_OK) return rc;
+    rc = launch_grid(c, Q, loop, shmem, s, origin, step, nx, ny, n, o.dev<float>(0));
+    return rc == RM_OK ? o.finish(s) : rc;
 }
 
 RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
@@ -1583,8 +1480,7 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
     if (!c) return RM_ERR_NULL;
     if (!out_counts) return fail(c, RM_ERR_NULL, "rm_extract_mesh: out_counts is NULL");
     if (int rc = check_lattice(c, "rm_extract_mesh", origin, step)) return rc;
-    if (!std::isfinite(level)) return fail(c, RM_ERR_ARG, "rm_extract_mesh: level %g is not finite", (double)level);
-    if (flags & ~(uint32_t)(RM_MESH_NORMALS | RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_extract_mesh: unknown flags 0x%x", flags);
+    if (int rc = check_iso(c, "rm_extract_mesh", level, flags)) return rc;
     const uint64_t n64 = (uint64_t)nx * ny * nz;
     if (nx < 2 || ny < 2 || nz < 2 || nx > kMaxDim || ny > kMaxDim || nz > kMaxDim || n64 > kMaxMeshPoints)
         return fail(c, RM_ERR_RANGE, "rm_extract_mesh: lattice %ux%ux%u: 2..65536 points per axis, at most 2^28 in all", nx, ny, nz);
@@ -1596,17 +1492,15 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
     int rc = query_begin(c, s, (flags & RM_MESH_IDS) != 0, false, &Q, &loop, &shmem);  // after a device read of the previous mesh, too
     if (rc != RM_OK) return rc;
     c->mesh_valid = false;  // its buffers change from here on
-    // scratch: distances, vertex bases (4 B per point each), flags (1 B), block sums (8 B per 2048 points), the two totals
     const uint32_t n = (uint32_t)n64, nb = (n + rmk::kMeshBlock - 1u) / rmk::kMeshBlock;
-    const size_t dist_o = 0, vbase_o = align16((size_t)n * 4u), flags_o = vbase_o + align16((size_t)n * 4u),
-                 sums_o = flags_o + align16(n), totals_o = sums_o + align16((size_t)nb * 8u);
-    if ((rc = grow_bytes(c, &c->d_mscratch, &c->d_mscratch_bytes, totals_o + 16u)) != RM_OK) return rc;
-    char* sc = static_cast<char*>(c->d_mscratch);
-    float* dist = reinterpret_cast<float*>(sc + dist_o);
-    uint32_t* vbase = reinterpret_cast<uint32_t*>(sc + vbase_o);
-    uint8_t* fl = reinterpret_cast<uint8_t*>(sc + flags_o);
-    unsigned long long* sums = reinterpret_cast<unsigned long long*>(sc + sums_o);
-    uint32_t* totals = reinterpret_cast<uint32_t*>(sc + totals_o);
+    const rml::DenseMeshScratch S(n, nb);
+    if ((rc = c->d_mscratch.reserve(c, S.bytes)) != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    float* dist = S.dist.at(sc);
+    uint32_t* vbase = S.vbase.at(sc);
+    uint8_t* fl = S.flags.at(sc);
+    unsigned long long* sums = S.sums.at(sc);
+    uint32_t* totals = S.totals.at(sc);
     const rmk::MeshGrid g{origin[0], origin[1], origin[2], step[0], step[1], step[2], nx, ny, nz, n};
     if ((rc = launch_grid(c, Q, loop, shmem, s, origin, step, nx, ny, n, dist)) != RM_OK) return rc;
     hipLaunchKernelGGL(rmk::rm_mesh_count_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist), sums);
@@ -1616,19 +1510,19 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
     HIP_TRY(c, hipMemcpyAsync(tot, totals, sizeof tot, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     const uint64_t V = tot[0], T = tot[1];
-    const MeshLayout L = mesh_layout(V, T, flags);
-    if ((rc = grow_bytes(c, &c->d_mesh, &c->d_mesh_bytes, L.bytes)) != RM_OK) return rc;
-    char* m = static_cast<char*>(c->d_mesh);
-    float* verts = reinterpret_cast<float*>(m + L.vertices);
+    const rml::MeshLayout L = mesh_layout(V, T, flags);
+    if ((rc = c->d_mesh.reserve(c, L.bytes)) != RM_OK) return rc;
+    char* m = c->d_mesh.p;
+    float* verts = L.vertices.at(m);
     if (V > 0u) {
         const unsigned long long* offs = sums;
         hipLaunchKernelGGL(rmk::rm_mesh_vertex_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist), offs,
                            vbase, fl, verts);
         if (T > 0u)
             hipLaunchKernelGGL(rmk::rm_mesh_triangle_kernel, dim3(nb), dim3(256), 0, s, g, offs, static_cast<const uint32_t*>(vbase),
-                               static_cast<const uint8_t*>(fl), reinterpret_cast<uint32_t*>(m + L.triangles));
+                               static_cast<const uint8_t*>(fl), L.triangles.at(m));
         HIP_TRY(c, hipGetLastError());
-        if ((rc = mesh_attributes(c, Q, loop, shmem, s, flags, V, m, L)) != RM_OK) return rc;
+        if ((rc = point_attributes(c, Q, loop, shmem, s, flags, V, verts, m, L.normals, L.ids)) != RM_OK) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     c->mesh_valid = true;
@@ -1655,8 +1549,7 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
     if (!out_stats) return fail(c, RM_ERR_NULL, "rm_extract_mesh_sparse: out_stats is NULL");
     if (n_stats < (uint32_t)RM_MESH_STATS) return fail(c, RM_ERR_ARG, "rm_extract_mesh_sparse: n_stats %u < RM_MESH_STATS", n_stats);
     if (int rc = check_lattice(c, "rm_extract_mesh_sparse", origin, step)) return rc;
-    if (!std::isfinite(level)) return fail(c, RM_ERR_ARG, "rm_extract_mesh_sparse: level %g is not finite", (double)level);
-    if (flags & ~(uint32_t)(RM_MESH_NORMALS | RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_extract_mesh_sparse: unknown flags 0x%x", flags);
+    if (int rc = check_iso(c, "rm_extract_mesh_sparse", level, flags)) return rc;
     if (nx < 2 || ny < 2 || nz < 2 || nx > kMaxDim || ny > kMaxDim || nz > kMaxDim)
         return fail(c, RM_ERR_RANGE, "rm_extract_mesh_sparse: lattice %ux%ux%u: 2..65536 points per axis", nx, ny, nz);
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1686,19 +1579,15 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
     g.nb = (uint32_t)nb64;
     // per brick: 4 B (keep flag, then the kept bricks before it); per 256 bricks a block sum; totals and the evaluation count
     const uint32_t n_entries = g.nb + 1u, n_pblocks = (n_entries + 255u) / 256u;
-    const size_t boff_o = 0, psums_o = align16((size_t)n_entries * 4u), ptot_o = psums_o + align16((size_t)n_pblocks * 8u), evals_o = ptot_o + 16u;
-    const size_t bricks_bytes = evals_o + 16u;
-    if ((rc = grow_bytes(c, &c->d_mbricks, &c->d_mbricks_bytes, bricks_bytes)) != RM_OK) return rc;
-    char* bs = static_cast<char*>(c->d_mbricks);
-    uint32_t* boff = reinterpret_cast<uint32_t*>(bs + boff_o);
-    unsigned long long* psums = reinterpret_cast<unsigned long long*>(bs + psums_o);
-    unsigned long long* ptot = reinterpret_cast<unsigned long long*>(bs + ptot_o);
-    unsigned long long* evals = reinterpret_cast<unsigned long long*>(bs + evals_o);
+    const rml::SparseBrickTables B(n_entries, n_pblocks);
+    if ((rc = c->d_mbricks.reserve(c, B.bytes)) != RM_OK) return rc;
+    char* bs = c->d_mbricks.p;
+    uint32_t* boff = B.boff.at(bs);
+    unsigned long long* psums = B.psums.at(bs);
+    unsigned long long* ptot = B.ptot.at(bs);
+    unsigned long long* evals = B.evals.at(bs);
     HIP_TRY(c, hipMemsetAsync(evals, 0, 8, s));
-    const ProbeFn probe = loop == rmk::Q_LOOP_CHAIN ? rmk::rm_sparse_probe_kernel<rmk::Q_LOOP_CHAIN>
-                        : loop == rmk::Q_LOOP_TREE ? rmk::rm_sparse_probe_kernel<rmk::Q_LOOP_TREE>
-                                                   : rmk::rm_sparse_probe_kernel<rmk::Q_LOOP_GENERAL>;
-    if ((rc = sparse_launch(c, probe, n_pblocks, shmem, s, Q, g, level, bound.L, 2.0 * bound.E, boff, psums)) != RM_OK) return rc;
+    if ((rc = sparse_launch(c, sparse_probe_kernel(loop), n_pblocks, shmem, s, Q, g, level, bound.L, 2.0 * bound.E, boff, psums)) != RM_OK) return rc;
     hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, psums, n_pblocks, ptot);
     HIP_TRY(c, hipGetLastError());
     unsigned long long tot[2] = {0ull, 0ull};
@@ -1707,31 +1596,26 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
     const uint64_t K = tot[0];
     uint64_t V = 0, T = 0, n_evals = g.nb;
     size_t kept_bytes = 0;
-    MeshLayout L = mesh_layout(0, 0, flags);
+    rml::MeshLayout L = mesh_layout(0, 0, flags);
     if (K > 0u) {
         if (K * rmk::kBrickSegs >= 0xFFFFFFFFull)
             return fail(c, RM_ERR_DEVICE, "rm_extract_mesh_sparse: %llu bricks to evaluate: more than the segment index holds", (unsigned long long)K);
         // per kept brick: its index, its segment map, its tile of distances, 64 segment words and their first (vertex, triangle)
         const uint32_t n_segs = (uint32_t)(K * rmk::kBrickSegs), n_sblocks = (n_segs + rmk::kSegBlock - 1u) / rmk::kSegBlock;
-        const size_t klist_o = 0, maps_o = align16((size_t)K * 4u), tiles_o = maps_o + (size_t)K * sizeof(rmk::SparseSegMap),
-                     words_o = tiles_o + align16((size_t)K * rmk::kTilePoints * 4u), first_o = words_o + align16((size_t)n_segs * 4u),
-                     ssums_o = first_o + (size_t)n_segs * 8u, stot_o = ssums_o + align16((size_t)n_sblocks * 8u);
-        kept_bytes = stot_o + 16u;
-        if ((rc = grow_bytes(c, &c->d_mscratch, &c->d_mscratch_bytes, kept_bytes)) != RM_OK) return rc;
-        char* sc = static_cast<char*>(c->d_mscratch);
-        uint32_t* klist = reinterpret_cast<uint32_t*>(sc + klist_o);
-        rmk::SparseSegMap* maps = reinterpret_cast<rmk::SparseSegMap*>(sc + maps_o);
-        float* tiles = reinterpret_cast<float*>(sc + tiles_o);
-        uint32_t* words = reinterpret_cast<uint32_t*>(sc + words_o);
-        uint2* first = reinterpret_cast<uint2*>(sc + first_o);
-        unsigned long long* ssums = reinterpret_cast<unsigned long long*>(sc + ssums_o);
-        unsigned long long* stot = reinterpret_cast<unsigned long long*>(sc + stot_o);
+        const rml::SparseKeptScratch<rmk::SparseSegMap, uint2> S(K, rmk::kTilePoints, n_segs, n_sblocks);
+        kept_bytes = S.bytes;
+        if ((rc = c->d_mscratch.reserve(c, kept_bytes)) != RM_OK) return rc;
+        char* sc = c->d_mscratch.p;
+        uint32_t* klist = S.klist.at(sc);
+        rmk::SparseSegMap* maps = S.maps.at(sc);
+        float* tiles = S.tiles.at(sc);
+        uint32_t* words = S.words.at(sc);
+        uint2* first = S.first.at(sc);
+        unsigned long long* ssums = S.ssums.at(sc);
+        unsigned long long* stot = S.stot.at(sc);
         hipLaunchKernelGGL(rmk::rm_sparse_compact_kernel, dim3(n_pblocks), dim3(256), 0, s, n_entries,
                            static_cast<const unsigned long long*>(psums), boff, klist);
-        const SparseCountFn count = loop == rmk::Q_LOOP_CHAIN ? rmk::rm_sparse_count_kernel<rmk::Q_LOOP_CHAIN>
-                                  : loop == rmk::Q_LOOP_TREE ? rmk::rm_sparse_count_kernel<rmk::Q_LOOP_TREE>
-                                                             : rmk::rm_sparse_count_kernel<rmk::Q_LOOP_GENERAL>;
-        if ((rc = sparse_launch(c, count, (uint32_t)K, shmem, s, Q, g, level, static_cast<const uint32_t*>(boff),
+        if ((rc = sparse_launch(c, sparse_count_kernel(loop), (uint32_t)K, shmem, s, Q, g, level, static_cast<const uint32_t*>(boff),
                                 static_cast<const uint32_t*>(klist), tiles, maps, words, evals)) != RM_OK)
             return rc;
         hipLaunchKernelGGL(rmk::rm_sparse_seg_sum_kernel, dim3(n_sblocks), dim3(256), 0, s, n_segs, static_cast<const uint32_t*>(words), ssums);
@@ -1748,17 +1632,17 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
             return fail(c, RM_ERR_RANGE, "rm_extract_mesh_sparse: %llu vertices and %llu triangles do not fit 32-bit indices",
                         (unsigned long long)V, (unsigned long long)T);
         L = mesh_layout(V, T, flags);
-        if ((rc = grow_bytes(c, &c->d_mesh, &c->d_mesh_bytes, L.bytes)) != RM_OK) return rc;
-        char* m = static_cast<char*>(c->d_mesh);
+        if ((rc = c->d_mesh.reserve(c, L.bytes)) != RM_OK) return rc;
+        char* m = c->d_mesh.p;
         if (V > 0u) {
             hipLaunchKernelGGL(rmk::rm_sparse_seg_scan_kernel, dim3(n_sblocks), dim3(256), 0, s, n_segs, static_cast<const uint32_t*>(words),
                                static_cast<const unsigned long long*>(ssums), first);
             hipLaunchKernelGGL(rmk::rm_sparse_emit_kernel, dim3((uint32_t)K), dim3(256), 0, s, g, level, (uint32_t)K,
                                static_cast<const uint32_t*>(boff), static_cast<const uint32_t*>(klist), static_cast<const float*>(tiles),
                                static_cast<const rmk::SparseSegMap*>(maps), static_cast<const uint32_t*>(words), static_cast<const uint2*>(first),
-                               reinterpret_cast<float*>(m + L.vertices), reinterpret_cast<uint32_t*>(m + L.triangles));
+                               L.vertices.at(m), L.triangles.at(m));
             HIP_TRY(c, hipGetLastError());
-            if ((rc = mesh_attributes(c, Q, loop, shmem, s, flags, V, m, L)) != RM_OK) return rc;
+            if ((rc = point_attributes(c, Q, loop, shmem, s, flags, V, L.vertices.at(m), m, L.normals, L.ids)) != RM_OK) return rc;
         }
         HIP_TRY(c, hipStreamSynchronize(s));
     }
@@ -1771,7 +1655,7 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
     out_stats[RM_MESH_STAT_BRICKS] = g.nb;
     out_stats[RM_MESH_STAT_BRICKS_KEPT] = K;
     out_stats[RM_MESH_STAT_EVALUATIONS] = n_evals;
-    out_stats[RM_MESH_STAT_SCRATCH_BYTES] = bricks_bytes + kept_bytes;
+    out_stats[RM_MESH_STAT_SCRATCH_BYTES] = B.bytes + kept_bytes;
     return RM_OK;
 }
 
@@ -1785,16 +1669,15 @@ RM_EXPORT int rm_read_mesh(rm_ctx* c, float* out_vertices, uint32_t* out_triangl
     if (is_device && (misaligned(out_vertices, 4) || misaligned(out_triangles, 4) || misaligned(out_normals, 4) || misaligned(out_ids, 8)))
         return fail(c, RM_ERR_ARG, "rm_read_mesh: device arrays need 4-byte alignment (out_ids: 8-byte)");
     HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    const hipStream_t s = dest_stream(c, is_device, stream);
     order_with_previous(c, s);  // (the next extraction waits for this stream in turn)
-    const MeshLayout L = mesh_layout(c->mesh_v, c->mesh_t, c->mesh_flags);
-    const char* m = static_cast<const char*>(c->d_mesh);
+    const rml::MeshLayout L = mesh_layout(c->mesh_v, c->mesh_t, c->mesh_flags);
+    const char* m = c->d_mesh.p;
     const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const size_t vb = (size_t)c->mesh_v * 12u, tb = (size_t)c->mesh_t * 12u, ib = (size_t)c->mesh_v * 8u;
-    if (out_vertices && vb) HIP_TRY(c, hipMemcpyAsync(out_vertices, m + L.vertices, vb, kind, s));
-    if (out_triangles && tb) HIP_TRY(c, hipMemcpyAsync(out_triangles, m + L.triangles, tb, kind, s));
-    if (out_normals && vb) HIP_TRY(c, hipMemcpyAsync(out_normals, m + L.normals, vb, kind, s));
-    if (out_ids && ib) HIP_TRY(c, hipMemcpyAsync(out_ids, m + L.ids, ib, kind, s));
+    if (out_vertices && L.vertices.bytes) HIP_TRY(c, hipMemcpyAsync(out_vertices, L.vertices.at(m), L.vertices.bytes, kind, s));
+    if (out_triangles && L.triangles.bytes) HIP_TRY(c, hipMemcpyAsync(out_triangles, L.triangles.at(m), L.triangles.bytes, kind, s));
+    if (out_normals && L.normals.bytes) HIP_TRY(c, hipMemcpyAsync(out_normals, L.normals.at(m), L.normals.bytes, kind, s));
+    if (out_ids && L.ids.bytes) HIP_TRY(c, hipMemcpyAsync(out_ids, L.ids.at(m), L.ids.bytes, kind, s));
     if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
     return RM_OK;
 }
@@ -1813,34 +1696,7 @@ constexpr uint64_t kMaxSlicePoints = 1ull << 26;  // lattice points of one layer
 
 using SliceDistFn = void (*)(rmk::QueryLaunch, rmk::SliceGrid, const float*, float*);
 SliceDistFn slice_dist_kernel(int loop) {
-    return loop == rmk::Q_LOOP_CHAIN ? rmk::rm_slice_dist_kernel<rmk::Q_LOOP_CHAIN>
-         : loop == rmk::Q_LOOP_TREE ? rmk::rm_slice_dist_kernel<rmk::Q_LOOP_TREE>
-                                    : rmk::rm_slice_dist_kernel<rmk::Q_LOOP_GENERAL>;
-}
-
-// grow_bytes for a result that is built batch by batch: the first `used` bytes survive the move
-int grow_keep(rm_ctx* c, void** buf, size_t* cap, size_t need, size_t used, hipStream_t s) {
-    if (need <= *cap) return RM_OK;
-    void* fresh = nullptr;
-    size_t want = need + need / 2u;
-    if (hipMalloc(&fresh, want) != hipSuccess) {
-        (void)hipGetLastError();
-        want = need;
-        HIP_TRY(c, hipMalloc(&fresh, want));
-    }
-    hipError_t e = hipSuccess;
-    if (used) {
-        e = hipMemcpyAsync(fresh, *buf, used, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    if (e != hipSuccess) {
-        (void)hipFree(fresh);
-        HIP_TRY(c, e);
-    }
-    if (*buf) (void)hipFree(*buf);
-    *buf = fresh;
-    *cap = want;
-    return RM_OK;
+    return with_loop(loop, [](auto tag) -> SliceDistFn { return rmk::rm_slice_dist_kernel<decltype(tag)::value>; });
 }
 
 uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1u) / per); }
@@ -1860,8 +1716,7 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
         if (!std::isfinite(step_uv[a]) || !(step_uv[a] > 0.0f))
             return fail(c, RM_ERR_ARG, "rm_slice_contours: step_uv[%d] = %g: a step must be finite and > 0", a, (double)step_uv[a]);
     }
-    if (!std::isfinite(level)) return fail(c, RM_ERR_ARG, "rm_slice_contours: level %g is not finite", (double)level);
-    if (flags & ~(uint32_t)(RM_MESH_NORMALS | RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_slice_contours: unknown flags 0x%x", flags);
+    if (int rc = check_iso(c, "rm_slice_contours", level, flags)) return rc;
     const uint64_t n2_64 = (uint64_t)nu * nv;
     if (nu < 2 || nv < 2 || nu > kMaxDim || nv > kMaxDim || n2_64 > kMaxSlicePoints || n_layers < 1 || n_layers > kMaxDim)
         return fail(c, RM_ERR_RANGE, "rm_slice_contours: lattice %ux%u, %u layers: 2..65536 points per axis, at most 2^26 per layer, 1..65536 layers",
@@ -1878,23 +1733,20 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
     c->slice_valid = false;  // its buffers change from here on
     const uint32_t n2 = (uint32_t)n2_64, per = std::min(n_layers, std::max(1u, rmk::kSliceBatchPoints / n2));
     const uint32_t n_max = per * n2, nb_max = blocks_of(n_max, rmk::kSliceBlock);
-    // the per-layer tables: heights, layer_first, the first vertex of each layer of a batch, two totals
-    const size_t lf_o = align16((size_t)n_layers * 4u), base_o = lf_o + align16(((size_t)n_layers + 1u) * 4u),
-                 totals_o = base_o + align16(((size_t)per + 1u) * 4u);
-    if ((rc = grow_bytes(c, &c->d_slayers, &c->d_slayers_bytes, totals_o + 16u)) != RM_OK) return rc;
-    char* lt = static_cast<char*>(c->d_slayers);
-    float* d_heights = reinterpret_cast<float*>(lt);
-    uint32_t* d_lf = reinterpret_cast<uint32_t*>(lt + lf_o);
-    uint32_t* d_base = reinterpret_cast<uint32_t*>(lt + base_o);
-    uint32_t* d_totals = reinterpret_cast<uint32_t*>(lt + totals_o);
+    const rml::SliceLayerTables T(n_layers, per);
+    if ((rc = c->d_slayers.reserve(c, T.bytes)) != RM_OK) return rc;
+    char* lt = c->d_slayers.p;
+    float* d_heights = T.heights.at(lt);
+    uint32_t* d_lf = T.layer_first.at(lt);
+    uint32_t* d_base = T.base.at(lt);
+    uint32_t* d_totals = T.totals.at(lt);
     HIP_TRY(c, hipMemcpyAsync(d_heights, heights, (size_t)n_layers * 4u, hipMemcpyHostToDevice, s));
-    // the per-point scratch of a batch: distances, packed vertex bases, block sums
-    const size_t packed_o = align16((size_t)n_max * 4u), sums_o = packed_o + align16((size_t)n_max * 4u);
-    if ((rc = grow_bytes(c, &c->d_mscratch, &c->d_mscratch_bytes, sums_o + align16((size_t)nb_max * 4u))) != RM_OK) return rc;
-    char* sc = static_cast<char*>(c->d_mscratch);
-    float* dist = reinterpret_cast<float*>(sc);
-    uint32_t* packed = reinterpret_cast<uint32_t*>(sc + packed_o);
-    uint32_t* sums = reinterpret_cast<uint32_t*>(sc + sums_o);
+    const rml::SlicePointScratch S(n_max, nb_max);
+    if ((rc = c->d_mscratch.reserve(c, S.bytes)) != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    float* dist = S.dist.at(sc);
+    uint32_t* packed = S.packed.at(sc);
+    uint32_t* sums = S.sums.at(sc);
     std::vector<uint32_t> base(per + 1u);
     uint64_t P = 0, Cn = 0;
     for (uint32_t k0 = 0; k0 < n_layers; k0 += per) {
@@ -1922,25 +1774,21 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
         uint32_t v_layer = 0, rounds = 0;
         for (uint32_t l = 0; l < nl; l++) v_layer = std::max(v_layer, base[l + 1u] - base[l]);
         while ((1ull << rounds) < v_layer) rounds++;
-        // the per-vertex scratch: next, prev, two (8-byte) ranking states, start, their block sums, and per contour (at most
-        // V / 2: a chain has two vertices or more) length and first point
+        // per contour: at most V / 2 (a chain has two vertices or more)
         const uint32_t vb = blocks_of(V, 256u), vsb = blocks_of(V, rmk::kSliceBlock), c_max = V / 2u + 1u;
-        const size_t prev_o = align16((size_t)V * 4u), st0_o = prev_o + align16((size_t)V * 4u), st1_o = st0_o + align16((size_t)V * 8u),
-                     start_o = st1_o + align16((size_t)V * 8u), vsums_o = start_o + align16((size_t)V * 4u),
-                     len_o = vsums_o + align16((size_t)vsb * 4u), fp_o = len_o + align16((size_t)c_max * 4u),
-                     work_bytes = fp_o + align16((size_t)c_max * 4u);
-        if ((rc = grow_bytes(c, &c->d_swork, &c->d_swork_bytes, work_bytes)) != RM_OK) return rc;
-        char* wk = static_cast<char*>(c->d_swork);
-        uint32_t* next = reinterpret_cast<uint32_t*>(wk);
-        uint32_t* prev = reinterpret_cast<uint32_t*>(wk + prev_o);
-        uint2* st_a = reinterpret_cast<uint2*>(wk + st0_o);
-        uint2* st_b = reinterpret_cast<uint2*>(wk + st1_o);
-        uint32_t* start = reinterpret_cast<uint32_t*>(wk + start_o);
-        uint32_t* vsums = reinterpret_cast<uint32_t*>(wk + vsums_o);
-        uint32_t* length = reinterpret_cast<uint32_t*>(wk + len_o);
-        uint32_t* first_point = reinterpret_cast<uint32_t*>(wk + fp_o);
-        if ((rc = grow_keep(c, &c->d_spoints, &c->d_spoints_bytes, (size_t)(P + V) * 12u, (size_t)P * 12u, s)) != RM_OK) return rc;
-        HIP_TRY(c, hipMemsetAsync(wk, 0xFF, st0_o, s));  // next and prev: kSliceNil
+        const rml::SliceVertexScratch<uint2> Wk(V, vsb, c_max);
+        if ((rc = c->d_swork.reserve(c, Wk.bytes)) != RM_OK) return rc;
+        char* wk = c->d_swork.p;
+        uint32_t* next = Wk.next.at(wk);
+        uint32_t* prev = Wk.prev.at(wk);
+        uint2* st_a = Wk.state0.at(wk);
+        uint2* st_b = Wk.state1.at(wk);
+        uint32_t* start = Wk.start.at(wk);
+        uint32_t* vsums = Wk.vsums.at(wk);
+        uint32_t* length = Wk.length.at(wk);
+        uint32_t* first_point = Wk.first_point.at(wk);
+        if ((rc = c->d_spoints.grow_keep(c, (size_t)(P + V) * 12u, (size_t)P * 12u, s)) != RM_OK) return rc;
+        HIP_TRY(c, hipMemsetAsync(wk, 0xFF, Wk.state0.offset, s));  // next and prev: kSliceNil
         hipLaunchKernelGGL(rmk::rm_slice_link_kernel, dim3(pb), dim3(256), 0, s, g, static_cast<const uint32_t*>(packed), next, prev);
         hipLaunchKernelGGL(rmk::rm_slice_low_init_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint32_t*>(next), V, st_a);
         for (uint32_t r = 0; r < rounds; r++) {
@@ -1963,7 +1811,7 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
         HIP_TRY(c, hipStreamSynchronize(s));
         if (Cb > c_max) return fail(c, RM_ERR_DEVICE, "rm_slice_contours: %u contours from %u vertices", Cb, V);
         if (Cn + Cb > 0xFFFFFFFFull) return fail(c, RM_ERR_RANGE, "rm_slice_contours: more than 2^32 - 1 contours");
-        if ((rc = grow_keep(c, &c->d_scontours, &c->d_scontours_bytes, (size_t)(Cn + Cb) * 16u, (size_t)Cn * 16u, s)) != RM_OK) return rc;
+        if ((rc = c->d_scontours.grow_keep(c, (size_t)(Cn + Cb) * 16u, (size_t)Cn * 16u, s)) != RM_OK) return rc;
         const uint32_t cb = blocks_of(Cb, rmk::kSliceBlock);
         hipLaunchKernelGGL(rmk::rm_slice_length_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint2*>(st_a),
                            static_cast<const uint32_t*>(next), static_cast<const uint32_t*>(start), V, length);
@@ -1976,26 +1824,17 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
         hipLaunchKernelGGL(rmk::rm_slice_emit_kernel, dim3(pb), dim3(256), 0, s, g, level, static_cast<const float*>(dist),
                            static_cast<const float*>(d_heights), static_cast<const uint32_t*>(packed), static_cast<const uint2*>(st_a),
                            static_cast<const uint32_t*>(start), static_cast<const uint32_t*>(length),
-                           static_cast<const uint32_t*>(first_point), (uint32_t)P, (uint32_t)Cn, static_cast<float*>(c->d_spoints),
-                           static_cast<uint4*>(c->d_scontours));
+                           static_cast<const uint32_t*>(first_point), (uint32_t)P, (uint32_t)Cn, c->d_spoints.as<float>(),
+                           c->d_scontours.as<uint4>());
         HIP_TRY(c, hipGetLastError());
         P += V;
         Cn += Cb;
     }
     // the attributes of the points: rm_query_points at their positions, device to device
-    const bool normals = (flags & RM_MESH_NORMALS) != 0, ids = (flags & RM_MESH_IDS) != 0;
-    if ((normals || ids) && P > 0u) {
-        const size_t ids_o = normals ? align16((size_t)P * 12u) : 0u;
-        if ((rc = grow_bytes(c, &c->d_sattr, &c->d_sattr_bytes, ids_o + (ids ? (size_t)P * 8u : 0u))) != RM_OK) return rc;
-        char* at = static_cast<char*>(c->d_sattr);
-        float* nrm = normals ? reinterpret_cast<float*>(at) : nullptr;
-        uint32_t* idp = ids ? reinterpret_cast<uint32_t*>(at + ids_o) : nullptr;
-        const PointsFn k = loop == rmk::Q_LOOP_CHAIN ? points_kernel<rmk::Q_LOOP_CHAIN>(false, normals, ids)
-                         : loop == rmk::Q_LOOP_TREE ? points_kernel<rmk::Q_LOOP_TREE>(false, normals, ids)
-                                                    : points_kernel<rmk::Q_LOOP_GENERAL>(false, normals, ids);
-        if ((rc = query_launch(c, k, P, shmem, s, Q, (uint32_t)P, static_cast<const float*>(c->d_spoints), static_cast<float*>(nullptr), nrm,
-                               idp)) != RM_OK)
-            return rc;
+    const rml::SliceAttributes A(P, (flags & RM_MESH_NORMALS) != 0, (flags & RM_MESH_IDS) != 0);
+    if (P > 0u) {
+        if ((rc = c->d_sattr.reserve(c, A.bytes)) != RM_OK) return rc;
+        if ((rc = point_attributes(c, Q, loop, shmem, s, flags, P, c->d_spoints.as<const float>(), c->d_sattr.p, A.normals, A.ids)) != RM_OK) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     c->slice_valid = true;
@@ -2019,19 +1858,18 @@ RM_EXPORT int rm_read_slices(rm_ctx* c, float* out_points, uint32_t* out_contour
                       misaligned(out_normals, 4) || misaligned(out_ids, 8)))
         return fail(c, RM_ERR_ARG, "rm_read_slices: device arrays need 4-byte alignment (out_contours: 16-byte, out_ids: 8-byte)");
     HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = is_device ? user_stream(c, stream) : c->stream;
+    const hipStream_t s = dest_stream(c, is_device, stream);
     order_with_previous(c, s);  // (the next slice call waits for this stream in turn)
     const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const size_t pb = (size_t)c->slice_p * 12u, cb = (size_t)c->slice_c * 16u, ib = (size_t)c->slice_p * 8u;
-    const bool normals = (c->slice_flags & RM_MESH_NORMALS) != 0;
-    const char* at = static_cast<const char*>(c->d_sattr);
-    const char* lt = static_cast<const char*>(c->d_slayers);
-    if (out_points && pb) HIP_TRY(c, hipMemcpyAsync(out_points, c->d_spoints, pb, kind, s));
-    if (out_contours && cb) HIP_TRY(c, hipMemcpyAsync(out_contours, c->d_scontours, cb, kind, s));
-    if (out_layer_first)
-        HIP_TRY(c, hipMemcpyAsync(out_layer_first, lt + align16((size_t)c->slice_layers * 4u), ((size_t)c->slice_layers + 1u) * 4u, kind, s));
-    if (out_normals && pb) HIP_TRY(c, hipMemcpyAsync(out_normals, at, pb, kind, s));
-    if (out_ids && ib) HIP_TRY(c, hipMemcpyAsync(out_ids, at + (normals ? align16(pb) : 0u), ib, kind, s));
+    const size_t pb = (size_t)c->slice_p * 12u, cb = (size_t)c->slice_c * 16u;
+    const rml::SliceLayerTables T(c->slice_layers);
+    const rml::SliceAttributes A(c->slice_p, (c->slice_flags & RM_MESH_NORMALS) != 0, (c->slice_flags & RM_MESH_IDS) != 0);
+    const char* at = c->d_sattr.p;
+    if (out_points && pb) HIP_TRY(c, hipMemcpyAsync(out_points, c->d_spoints.p, pb, kind, s));
+    if (out_contours && cb) HIP_TRY(c, hipMemcpyAsync(out_contours, c->d_scontours.p, cb, kind, s));
+    if (out_layer_first) HIP_TRY(c, hipMemcpyAsync(out_layer_first, T.layer_first.at(c->d_slayers.p), T.layer_first.bytes, kind, s));
+    if (out_normals && A.normals.bytes) HIP_TRY(c, hipMemcpyAsync(out_normals, A.normals.at(at), A.normals.bytes, kind, s));
+    if (out_ids && A.ids.bytes) HIP_TRY(c, hipMemcpyAsync(out_ids, A.ids.at(at), A.ids.bytes, kind, s));
     if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
     return RM_OK;
 }
@@ -2148,7 +1986,7 @@ RM_EXPORT int rm_read_wave_stats(rm_ctx* c, void* dst, uint64_t cap_bytes, uint6
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipDeviceSynchronize());
     const uint64_t n = c->stats_valid_bytes < cap_bytes ? c->stats_valid_bytes : cap_bytes;
-    if (n) HIP_TRY(c, hipMemcpy(dst, c->d_stats, n, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(c, hipMemcpy(dst, c->d_stats.p, n, hipMemcpyDeviceToHost));
     *out_bytes = n;
     return RM_OK;
 }
@@ -2157,20 +1995,18 @@ RM_EXPORT int rm_selftest_sqrt(rm_ctx* c, uint64_t* out_mismatches, uint32_t* ou
     if (!c) return RM_ERR_NULL;
     if (!out_mismatches || !out_first_bad_bits) return fail(c, RM_ERR_NULL, "rm_selftest_sqrt: NULL argument");
     HIP_TRY(c, hipSetDevice(c->device));
-    unsigned long long* d_bad = nullptr;
-    uint32_t* d_first = nullptr;
-    HIP_TRY(c, hipMalloc(&d_bad, 8));
-    HIP_TRY(c, hipMalloc(&d_first, 4));
-    HIP_TRY(c, hipMemset(d_bad, 0, 8));
-    HIP_TRY(c, hipMemset(d_first, 0xFF, 4));
+    DevBuf<unsigned long long> d_bad;
+    DevBuf<uint32_t> d_first;
+    if (int rc = d_bad.reserve(c, 1)) return rc;
+    if (int rc = d_first.reserve(c, 1)) return rc;
+    HIP_TRY(c, hipMemset(d_bad.p, 0, 8));
+    HIP_TRY(c, hipMemset(d_first.p, 0xFF, 4));
     hipLaunchKernelGGL(rmk::rm_selftest_sqrt_kernel, dim3(std::max(1, c->cu_count) * 16), dim3(256), 0, c->stream, 0u,
-                       (uint64_t)1 << 32, d_bad, d_first);
+                       (uint64_t)1 << 32, d_bad.p, d_first.p);
     hipError_t e = hipStreamSynchronize(c->stream);
     unsigned long long bad = 0;
-    if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_first_bad_bits, d_first, 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
-    (void)hipFree(d_first);
+    if (e == hipSuccess) e = hipMemcpy(&bad, d_bad.p, 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_first_bad_bits, d_first.p, 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(c, RM_ERR_DEVICE, "rm_selftest_sqrt: %s", hipGetErrorString(e));
     *out_mismatches = bad;
     return RM_OK;
@@ -2180,18 +2016,17 @@ RM_EXPORT int rm_selftest_ops(rm_ctx* c, const float* a, const float* b, float* 
     if (!c) return RM_ERR_NULL;
     if (!a || !b || !out || n == 0u) return fail(c, RM_ERR_NULL, "rm_selftest_ops: NULL argument");
     HIP_TRY(c, hipSetDevice(c->device));
-    float *da = nullptr, *db = nullptr, *dout = nullptr;
-    HIP_TRY(c, hipMalloc(&da, (size_t)n * 4));
-    HIP_TRY(c, hipMalloc(&db, (size_t)n * 4));
-    HIP_TRY(c, hipMalloc(&dout, (size_t)n * 32));
-    hipError_t e = hipMemcpy(da, a, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(db, b, (size_t)n * 4, hipMemcpyHostToDevice);
+    DevBuf<float> da, db, dout;
+    if (int rc = da.reserve(c, n)) return rc;
+    if (int rc = db.reserve(c, n)) return rc;
+    if (int rc = dout.reserve(c, (size_t)n * 8)) return rc;
+    hipError_t e = hipMemcpy(da.p, a, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(db.p, b, (size_t)n * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(rmk::rm_selftest_ops_kernel, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, da, db, dout, n);
+        hipLaunchKernelGGL(rmk::rm_selftest_ops_kernel, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, da.p, db.p, dout.p, n);
         e = hipStreamSynchronize(c->stream);
     }
-    if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 32, hipMemcpyDeviceToHost);
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
+    if (e == hipSuccess) e = hipMemcpy(out, dout.p, (size_t)n * 32, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(c, RM_ERR_DEVICE, "rm_selftest_ops: %s", hipGetErrorString(e));
     return RM_OK;
 }
@@ -2201,16 +2036,15 @@ RM_EXPORT int rm_selftest_wave(rm_ctx* c, const float* in, uint32_t n_waves, flo
     if (!in || !out || n_waves == 0u || n_waves > 65535u) return fail(c, RM_ERR_NULL, "rm_selftest_wave: bad argument");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)n_waves * 64u;
-    float *din = nullptr, *dout = nullptr;
-    HIP_TRY(c, hipMalloc(&din, n * 4));
-    HIP_TRY(c, hipMalloc(&dout, n * 8));
-    hipError_t e = hipMemcpy(din, in, n * 4, hipMemcpyHostToDevice);
+    DevBuf<float> din, dout;
+    if (int rc = din.reserve(c, n)) return rc;
+    if (int rc = dout.reserve(c, n * 2)) return rc;
+    hipError_t e = hipMemcpy(din.p, in, n * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(rmk::rm_selftest_wave_kernel, dim3(n_waves), dim3(64), 0, c->stream, din, dout, n_waves);
+        hipLaunchKernelGGL(rmk::rm_selftest_wave_kernel, dim3(n_waves), dim3(64), 0, c->stream, din.p, dout.p, n_waves);
         e = hipStreamSynchronize(c->stream);
     }
-    if (e == hipSuccess) e = hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(din); (void)hipFree(dout);
+    if (e == hipSuccess) e = hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(c, RM_ERR_DEVICE, "rm_selftest_wave: %s", hipGetErrorString(e));
     return RM_OK;
 }
@@ -2220,19 +2054,18 @@ RM_EXPORT int rm_measure_write_bandwidth(rm_ctx* c, uint64_t bytes, int iters, d
     if (!out_gbps) return fail(c, RM_ERR_NULL, "rm_measure_write_bandwidth: out is NULL");
     if (bytes < 4096 || (bytes & 15u) || iters < 1 || iters > 1000) return fail(c, RM_ERR_ARG, "bad bytes/iters");
     HIP_TRY(c, hipSetDevice(c->device));
-    float4* buf = nullptr;
-    HIP_TRY(c, hipMalloc(&buf, bytes));
+    DevBuf<float4> buf;
+    if (int rc = buf.reserve(c, bytes / 16u)) return rc;
     const size_t n_vec = bytes / 16u;
     const int grid = std::max(1, c->cu_count) * 8;
-    hipLaunchKernelGGL(rmk::rm_fill, dim3(grid), dim3(256), 0, c->stream, buf, n_vec, 0.0f);  // warm-up
+    hipLaunchKernelGGL(rmk::rm_fill, dim3(grid), dim3(256), 0, c->stream, buf.p, n_vec, 0.0f);  // warm-up
     hipError_t e = hipEventRecord(c->ev0, c->stream);
     for (int i = 0; i < iters && e == hipSuccess; i++)
-        hipLaunchKernelGGL(rmk::rm_fill, dim3(grid), dim3(256), 0, c->stream, buf, n_vec, (float)i);
+        hipLaunchKernelGGL(rmk::rm_fill, dim3(grid), dim3(256), 0, c->stream, buf.p, n_vec, (float)i);
     if (e == hipSuccess) e = hipEventRecord(c->ev1, c->stream);
     if (e == hipSuccess) e = hipEventSynchronize(c->ev1);
     float ms = 0.f;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    (void)hipFree(buf);
     if (e != hipSuccess) return fail(c, RM_ERR_DEVICE, "write-bandwidth calibration failed: %s", hipGetErrorString(e));
     *out_gbps = (double)bytes * iters / (ms * 1e-3) / 1e9;
     return RM_OK;

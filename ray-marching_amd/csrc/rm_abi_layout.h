@@ -1,0 +1,154 @@
+// rm_abi_layout.h -- where the typed arrays of rm_abi.hip's device allocations lie.  Pure host arithmetic (no HIP), so that
+// tests/cpp/abi_layout_check.cpp can check every layout on the CPU.  A layout is declared first (sizes only), gives the bytes to
+// reserve, and its regions are resolved against the buffer's base pointer afterwards; the entry points that read a result
+// (rm_read_mesh, rm_read_slices) use the declarations of the ones that wrote it.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace rml {
+
+constexpr size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
+
+// `bytes` bytes at `offset` of an allocation, holding an array of T.
+template <class T>
+struct Region {
+    size_t offset = 0, bytes = 0;
+    T* at(void* base) const { return reinterpret_cast<T*>(static_cast<char*>(base) + offset); }
+    const T* at(const void* base) const { return reinterpret_cast<const T*>(static_cast<const char*>(base) + offset); }
+};
+
+// Hands out the regions of one allocation in declaration order.  Every region starts on a 16-byte boundary (device arrays
+// are read and written with vector accesses of up to 16 bytes), so the total is a multiple of 16 as well.
+struct Carver {
+    size_t total = 0;
+    template <class T>
+    Region<T> take(size_t count) {
+        const Region<T> r{total, count * sizeof(T)};
+        total += align16(r.bytes);
+        return r;
+    }
+};
+
+// The layouts below declare their regions as members, in the order in which they lie: each constructor takes them from the
+// Carver declared first (members are initialised in declaration order), `bytes` is the total to reserve.
+
+// rm_extract_mesh's scratch for a lattice of n points in nb blocks: distances, vertex bases (4 B per point each), flags (1 B),
+// block sums (8 B per block), the two totals.
+struct DenseMeshScratch {
+    Carver a;
+    Region<float> dist;
+    Region<uint32_t> vbase;
+    Region<uint8_t> flags;
+    Region<unsigned long long> sums;
+    Region<uint32_t> totals;
+    size_t bytes;
+    DenseMeshScratch(uint32_t n, uint32_t nb)
+        : dist(a.take<float>(n)), vbase(a.take<uint32_t>(n)), flags(a.take<uint8_t>(n)), sums(a.take<unsigned long long>(nb)),
+          totals(a.take<uint32_t>(4)), bytes(a.total) {}
+};
+
+// rm_extract_mesh_sparse, per brick: 4 B (keep flag, then the kept bricks before it); per 256 bricks a block sum; totals and
+// the evaluation count.
+struct SparseBrickTables {
+    Carver a;
+    Region<uint32_t> boff;
+    Region<unsigned long long> psums, ptot, evals;
+    size_t bytes;
+    SparseBrickTables(uint32_t n_entries, uint32_t n_pblocks)
+        : boff(a.take<uint32_t>(n_entries)), psums(a.take<unsigned long long>(n_pblocks)), ptot(a.take<unsigned long long>(2)),
+          evals(a.take<unsigned long long>(2)), bytes(a.total) {}
+};
+
+// ... and per kept brick: its index, its segment map, its tile of distances, its segment words and their first (vertex,
+// triangle).  SegMap and Pair are the kernels' types (rmk::SparseSegMap, uint2).
+template <class SegMap, class Pair>
+struct SparseKeptScratch {
+    Carver a;
+    Region<uint32_t> klist;
+    Region<SegMap> maps;
+    Region<float> tiles;
+    Region<uint32_t> words;
+    Region<Pair> first;
+    Region<unsigned long long> ssums, stot;
+    size_t bytes;
+    SparseKeptScratch(uint64_t K, uint32_t tile_points, uint32_t n_segs, uint32_t n_sblocks)
+        : klist(a.take<uint32_t>(K)), maps(a.take<SegMap>(K)), tiles(a.take<float>(K * tile_points)), words(a.take<uint32_t>(n_segs)),
+          first(a.take<Pair>(n_segs)), ssums(a.take<unsigned long long>(n_sblocks)), stot(a.take<unsigned long long>(2)),
+          bytes(a.total) {}
+};
+
+// rm_slice_contours' per-layer tables: heights, layer_first, the first vertex of each layer of a batch of `per`, totals.
+// (heights and layer_first lie before anything `per` sizes: rm_read_slices finds layer_first without it.)
+struct SliceLayerTables {
+    Carver a;
+    Region<float> heights;
+    Region<uint32_t> layer_first, base, totals;
+    size_t bytes;
+    explicit SliceLayerTables(uint32_t n_layers, uint32_t per = 0)
+        : heights(a.take<float>(n_layers)), layer_first(a.take<uint32_t>((size_t)n_layers + 1u)),
+          base(a.take<uint32_t>((size_t)per + 1u)), totals(a.take<uint32_t>(4)), bytes(a.total) {}
+};
+
+// ... the per-point scratch of a batch of n_max points in nb_max blocks: distances, packed vertex bases, block sums.
+struct SlicePointScratch {
+    Carver a;
+    Region<float> dist;
+    Region<uint32_t> packed, sums;
+    size_t bytes;
+    SlicePointScratch(uint32_t n_max, uint32_t nb_max)
+        : dist(a.take<float>(n_max)), packed(a.take<uint32_t>(n_max)), sums(a.take<uint32_t>(nb_max)), bytes(a.total) {}
+};
+
+// ... and the per-vertex scratch of a batch of V vertices: next, prev, two (8-byte) ranking states, start, their block sums
+// (vsb blocks), and per contour (at most c_max) length and first point.  Pair is the kernels' uint2.
+template <class Pair>
+struct SliceVertexScratch {
+    Carver a;
+    Region<uint32_t> next, prev;
+    Region<Pair> state0, state1;
+    Region<uint32_t> start, vsums, length, first_point;
+    size_t bytes;
+    SliceVertexScratch(uint32_t V, uint32_t vsb, uint32_t c_max)
+        : next(a.take<uint32_t>(V)), prev(a.take<uint32_t>(V)), state0(a.take<Pair>(V)), state1(a.take<Pair>(V)),
+          start(a.take<uint32_t>(V)), vsums(a.take<uint32_t>(vsb)), length(a.take<uint32_t>(c_max)),
+          first_point(a.take<uint32_t>(c_max)), bytes(a.total) {}
+};
+
+// rm_slice_contours' attributes of its P points, in a buffer of their own: normals (3 floats) and (leaf, material) pairs, each
+// only if asked for.
+struct SliceAttributes {
+    Carver a;
+    Region<float> normals;
+    Region<uint32_t> ids;
+    size_t bytes;
+    SliceAttributes(uint64_t P, bool with_normals, bool with_ids)
+        : normals(a.take<float>(with_normals ? P * 3u : 0u)), ids(a.take<uint32_t>(with_ids ? P * 2u : 0u)), bytes(a.total) {}
+};
+
+// Where the arrays of a mesh of V vertices and T triangles lie in the mesh buffer; the attributes as above.
+struct MeshLayout {
+    Carver a;
+    Region<float> vertices;
+    Region<uint32_t> triangles;
+    Region<float> normals;
+    Region<uint32_t> ids;
+    size_t bytes;
+    MeshLayout(uint64_t V, uint64_t T, bool with_normals, bool with_ids)
+        : vertices(a.take<float>(V * 3u)), triangles(a.take<uint32_t>(T * 3u)), normals(a.take<float>(with_normals ? V * 3u : 0u)),
+          ids(a.take<uint32_t>(with_ids ? V * 2u : 0u)), bytes(a.total) {}
+};
+
+// Output rows of the strips first, first+stride, ... (strip_rows rows each) of an H-row image.
+inline uint32_t strip_row_count(uint32_t H, uint32_t strip_rows, uint32_t first, uint32_t stride) {
+    const uint32_t n_strips = (H + strip_rows - 1u) / strip_rows;
+    uint32_t rows = 0;
+    for (uint32_t sidx = first; sidx < n_strips; sidx += stride) {
+        const uint32_t r0 = sidx * strip_rows;
+        rows += H - r0 < strip_rows ? H - r0 : strip_rows;
+    }
+    return rows;
+}
+
+}  // namespace rml

@@ -68,3 +68,23 @@ def test_elf_reader_of_the_specialiser_survives_damaged_code_objects(tmp_path):
     run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
     assert "elf reader fuzz ok" in run.stdout
+
+
+def test_scratch_layouts_of_the_host_abi_match_the_hand_written_offsets(tmp_path):
+    """tests/cpp/abi_layout_check.cpp: rm_abi_layout.h -- where the typed arrays of the host ABI's device allocations lie (dense
+    and sparse mesh scratch, the three slicing layouts, the slice attributes, the mesh result) -- against the chained align16
+    offsets written out by hand: regions in declaration order, 16-byte aligned, disjoint and inside the total, at the shapes
+    where a count is no multiple of 4 or crosses a scan block; and strip_row_count against a direct loop over the rows."""
+    cxx = os.environ.get("CXX", "g++")
+    if not shutil.which(cxx):
+        pytest.skip("no C++ compiler")
+    exe = tmp_path / "abi_layout_check"
+    build = subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
+                            "-fno-sanitize-recover=undefined", "-I", os.path.join(ROOT, "include"),
+                            "-I", os.path.join(ROOT, "ray-marching_amd", "csrc"), "-o", str(exe),
+                            os.path.join(ROOT, "tests", "cpp", "abi_layout_check.cpp")], capture_output=True, text=True, timeout=300)
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
+    assert "abi layout ok" in run.stdout
