@@ -503,6 +503,25 @@ int rm_selftest_ops(rm_ctx* ctx, const float* a, const float* b, float* out, uin
  * NaN): out[i] = the largest value of input i's wave (by bit pattern: a NaN wins), out[64 n_waves + i] = the minimum over the
  * inputs of the LOWER lanes of its wave (+inf for lane 0; a NaN is skipped).  tests/test_gpu_arithmetic.py compares with numpy. */
 int rm_selftest_wave(rm_ctx* ctx, const float* in, uint32_t n_waves, float* out);
+/* The culling decisions of the march on inputs the caller chooses (tests/test_gpu_cull_bounds.py compares them with binary64
+ * geometry): the device functions of a draw, on the context's current program, limits and options, with the launch a draw would
+ * fill and the tables staged as the kernels stage them.  Host arrays only; they wait for the result.
+ * rm_selftest_cull_rays: half-lines from origin[3] along dirs[3 n] (any length).  out_flags[i]: bit 0 the miss-test tables clear
+ *   the ray, bit 1 the tables were usable (culling on, nothing vetoed), bit 2 the miss test on lower bounds applies to the
+ *   program, bit 3 it clears the ray, bits 8.. the veto word of the tables; out_bound[i]: the lower bound that test computes
+ *   (NaN when it does not apply).
+ * rm_selftest_cull_pixels: pixels xy[2 n] of a W x H frame under the context's uniforms, as the pre-pass sees them.  out[8 i + ..]:
+ *   0..2 the centre direction and 3 the radius rho of the cone of the pixel's sixteen sample directions (NaN: no usable cone),
+ *   4 the lower bound over the cone (NaN when that test does not apply), 5 flags as the bits of an integer (bit 0 the tables
+ *   clear the pixel, bit 1 the tables were usable, bit 2 the test on lower bounds applies, bit 3 it clears the pixel), 6..7 zero.
+ * rm_selftest_cull_waves: n_waves waves of 64 positions, pos[(3 w + k) * 64 + lane] (k = x, y, z), thresholds thr[64 w + lane]
+ *   and live-lane masks live[w] (not 0); camera position origin[3].  out_masks[w]: the units wave-level culling keeps -- the
+ *   threshold rule (lattice programs; extra_margin unused) or the rules of a blending chain (thr unused), by the program;
+ *   RM_ERR_ARG when the program has no units. */
+int rm_selftest_cull_rays(rm_ctx* ctx, const float* origin, const float* dirs, uint32_t n, uint32_t* out_flags, float* out_bound);
+int rm_selftest_cull_pixels(rm_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* xy, uint32_t n, float* out);
+int rm_selftest_cull_waves(rm_ctx* ctx, const float* origin, const float* pos, const float* thr, const uint64_t* live, uint32_t n_waves,
+                           float extra_margin, uint64_t* out_masks);
 
 /* Diagnostics: per-wave records of the last draw made with RM_OPT_WAVE_STATS = 1, four u64 per
  * wave in dispatch order: [0] start, [1] end (100 MHz s_memrealtime ticks), [2] tile id << 32 |

@@ -136,6 +136,12 @@ def hip_lib():
         L.rm_selftest_ops.restype = C.c_int
         L.rm_selftest_wave.argtypes = [vp, vp, u32, vp]
         L.rm_selftest_wave.restype = C.c_int
+        L.rm_selftest_cull_rays.argtypes = [vp, vp, vp, u32, vp, vp]
+        L.rm_selftest_cull_rays.restype = C.c_int
+        L.rm_selftest_cull_pixels.argtypes = [vp, u32, u32, vp, u32, vp]
+        L.rm_selftest_cull_pixels.restype = C.c_int
+        L.rm_selftest_cull_waves.argtypes = [vp, vp, vp, vp, vp, u32, C.c_float, vp]
+        L.rm_selftest_cull_waves.restype = C.c_int
         L.rm_read_wave_stats.argtypes = [vp, vp, u64, C.POINTER(u64)]
         L.rm_read_wave_stats.restype = C.c_int
         L.rm_query_points.argtypes = [vp, u32, vp, vp, vp, vp, C.c_int, vp]

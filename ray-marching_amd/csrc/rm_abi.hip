@@ -377,9 +377,11 @@ int time_end(rm_ctx* c, hipStream_t s);
 // LDS behind the program copy of a march workgroup: {pool cursor, tile slot, veto, pad} + the 16 AA sample offsets (+ pad)
 constexpr size_t kV5TailBytes = 16u + 144u;
 
-template <int WPT>
-int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hipStream_t s) {
-    RmLaunch L = L_in;
+// What a march launch decides before it launches: whether the miss tests run, which record loop an interpreter kernel takes and
+// whether it culls per wave -- written into L (n_cull, n_tree, spill_depth, flags, n_cone, n_slab).  The culling self-tests
+// (rm_selftest_cull_*) fill their launch through it too, so that they see the fields a frame would see.
+struct V5Plan { bool units; int loop; };
+V5Plan plan_v5(rm_ctx* c, RmLaunch& L, bool lds) {
     const RmDecoded& d = c->decoded;
     bool cull = c->cull && L.n_rec <= 256u && !d.cull_veto;
     if (L.n_rec == 0u && L.max_dist < L.min_dist) cull = false;  // see launch_multi_w
@@ -407,7 +409,6 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
         units = blend_units;
         loop = units ? 5 : 0;
     }
-    c->last_loop = loop;
     L.n_tree = loop == 4 ? (uint32_t)d.tree.size() : 0u;
     if (L.n_tree != 0u) L.spill_depth += 1u;  // (map_scene_tree_masked spills at every push)
     // bit 2: chain program, bit 4: tree program (every record one of the eight fast shapes)
@@ -415,8 +416,19 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
     // programs that blend: a ray the plain miss tests cannot clear (every bound is inflated by the blend radius) gets the
     // program run on lower bounds of its leaves along the ray
     if (cull && d.bound_walk) L.flags |= 32u;
-    const uint32_t n_tiles = ((L.W + 7u) / 8u) * ((L.rows + 7u) / 8u);
     if (!cull) L.n_cone = L.n_slab = 0u;
+    return V5Plan{units, loop};
+}
+
+template <int WPT>
+int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hipStream_t s) {
+    RmLaunch L = L_in;
+    const RmDecoded& d = c->decoded;
+    const V5Plan plan = plan_v5(c, L, lds);
+    const bool units = plan.units;
+    const int loop = plan.loop;
+    c->last_loop = loop;
+    const uint32_t n_tiles = ((L.W + 7u) / 8u) * ((L.rows + 7u) / 8u);
     const size_t cull_bytes = (size_t)L.n_cone * 16u + (size_t)L.n_slab * 48u;
     // structure-specialised kernel (values live in registers: no LDS spill stack)
     hipFunction_t spec_fn = lds ? specialised_kernel(c, WPT) : nullptr;
@@ -532,8 +544,10 @@ int launch_v5(rm_ctx* c, const RmLaunch& L, bool lds, uint32_t n_frames, hipStre
 
 struct StripSpec { uint32_t rows = 0, first = 0, stride = 0; };
 
-int launch(rm_ctx* c, const rm_uniforms* frames_dev, uint32_t n_frames, uint32_t W, uint32_t H, uint32_t row0,
-           uint32_t rows, float* d_out, hipStream_t s, StripSpec strips = StripSpec()) {
+// The launch of the context's current program, limits, uniforms and output format for a W x H frame (rows [row0, row0 + rows),
+// or strips): everything but what the kernel variant decides (plan_v5).
+RmLaunch fill_launch(rm_ctx* c, const rm_uniforms* frames_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, float* d_out,
+                     StripSpec strips) {
     RmLaunch L;
     L.strip_rows = strips.rows; L.strip_first = strips.first; L.strip_stride = strips.stride;
     L.prog = c->d_prog.p;
@@ -561,12 +575,18 @@ int launch(rm_ctx* c, const rm_uniforms* frames_dev, uint32_t n_frames, uint32_t
     L.W = W; L.H = H; L.row0 = row0; L.rows = rows;
     L.out = d_out;
     L.out_format = (uint32_t)c->out_format;
-    if (c->out_format != RM_FORMAT_RGBA32F && !(c->kernel == RM_KERNEL_DEFAULT || c->kernel == RM_KERNEL_V5 || c->kernel == RM_KERNEL_V5_LDS))
-        return fail(c, RM_ERR_ARG, "kernel variant %d writes RGBA32F only (8-bit output formats need the default kernels)", c->kernel);
     L.frames = frames_dev;
     L.order = nullptr;
     L.stats = nullptr;
     L.u = c->uniforms;
+    return L;
+}
+
+int launch(rm_ctx* c, const rm_uniforms* frames_dev, uint32_t n_frames, uint32_t W, uint32_t H, uint32_t row0,
+           uint32_t rows, float* d_out, hipStream_t s, StripSpec strips = StripSpec()) {
+    RmLaunch L = fill_launch(c, frames_dev, W, H, row0, rows, d_out, strips);
+    if (c->out_format != RM_FORMAT_RGBA32F && !(c->kernel == RM_KERNEL_DEFAULT || c->kernel == RM_KERNEL_V5 || c->kernel == RM_KERNEL_V5_LDS))
+        return fail(c, RM_ERR_ARG, "kernel variant %d writes RGBA32F only (8-bit output formats need the default kernels)", c->kernel);
     int kernel = c->kernel == RM_KERNEL_DEFAULT ? RM_KERNEL_V5_LDS : c->kernel;
     if (kernel == RM_KERNEL_V5 || kernel == RM_KERNEL_V5_LDS) return launch_v5(c, L, kernel == RM_KERNEL_V5_LDS, n_frames, s);
     if (kernel != RM_KERNEL_PIXEL) return fail(c, RM_ERR_ARG, "kernel variant %d is not available", kernel);
@@ -2046,6 +2066,101 @@ RM_EXPORT int rm_selftest_wave(rm_ctx* c, const float* in, uint32_t n_waves, flo
     }
     if (e == hipSuccess) e = hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(c, RM_ERR_DEVICE, "rm_selftest_wave: %s", hipGetErrorString(e));
+    return RM_OK;
+}
+
+// ---- self-tests of the culling decisions (rm_kernel_v5.h rm_selftest_cull_*_kernel) -----------------------------------------
+namespace {
+// What a draw does before it launches, and the launch it would fill for a W x H frame of the context's program with the default
+// march kernel: rm_selftest_cull_* hand their kernels the same flags, table sizes, bounds, slack, scale and unit table.
+int cull_probe_begin(rm_ctx* c, const char* fn, uint32_t W, uint32_t H, RmLaunch* L) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    order_with_previous(c, c->stream);
+    int rc = ensure_program(c, c->stream);
+    if (rc == RM_OK) rc = check_limits(c);
+    if (rc != RM_OK) return rc;
+    if (W == 0u || H == 0u || W > kMaxDim || H > kMaxDim) return fail(c, RM_ERR_RANGE, "%s: image size %ux%u out of range", fn, W, H);
+    *L = fill_launch(c, nullptr, W, H, 0u, H, nullptr, StripSpec());
+    (void)plan_v5(c, *L, true);
+    return RM_OK;
+}
+// host array -> a device buffer of this call
+template <class T>
+int probe_put(rm_ctx* c, DevBuf<T>& buf, const void* src, size_t n) {
+    if (int rc = buf.reserve(c, n)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(buf.p, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    return RM_OK;
+}
+int probe_finish(rm_ctx* c, const char* fn) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, RM_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
+    return RM_OK;
+}
+}  // namespace
+
+RM_EXPORT int rm_selftest_cull_rays(rm_ctx* c, const float* origin, const float* dirs, uint32_t n, uint32_t* out_flags, float* out_bound) {
+    if (!c) return RM_ERR_NULL;
+    if (!origin || !dirs || !out_flags || !out_bound) return fail(c, RM_ERR_NULL, "rm_selftest_cull_rays: NULL argument");
+    if (n == 0u || n > (1u << 20)) return fail(c, RM_ERR_ARG, "rm_selftest_cull_rays: n = %u, must be 1 .. 2^20", n);
+    RmLaunch L;
+    if (int rc = cull_probe_begin(c, "rm_selftest_cull_rays", 8u, 8u, &L)) return rc;
+    DevBuf<float> d_dirs, d_bound;
+    DevBuf<uint32_t> d_flags;
+    if (int rc = probe_put(c, d_dirs, dirs, (size_t)n * 3u)) return rc;
+    if (int rc = d_flags.reserve(c, n)) return rc;
+    if (int rc = d_bound.reserve(c, n)) return rc;
+    const size_t shmem = 16u + (size_t)L.n_cone * 16u + (size_t)L.n_slab * 48u;
+    const rmk::V4 ro{origin[0], origin[1], origin[2], 1.0f};
+    hipLaunchKernelGGL(rmk::rm_selftest_cull_rays_kernel, dim3((n + 63u) / 64u), dim3(64), shmem, c->stream, L, ro, d_dirs.p, n, d_flags.p, d_bound.p);
+    if (int rc = probe_finish(c, "rm_selftest_cull_rays")) return rc;
+    HIP_TRY(c, hipMemcpy(out_flags, d_flags.p, (size_t)n * 4u, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(out_bound, d_bound.p, (size_t)n * 4u, hipMemcpyDeviceToHost));
+    return RM_OK;
+}
+
+RM_EXPORT int rm_selftest_cull_pixels(rm_ctx* c, uint32_t W, uint32_t H, const uint32_t* xy, uint32_t n, float* out) {
+    if (!c) return RM_ERR_NULL;
+    if (!xy || !out) return fail(c, RM_ERR_NULL, "rm_selftest_cull_pixels: NULL argument");
+    if (n == 0u || n > (1u << 20)) return fail(c, RM_ERR_ARG, "rm_selftest_cull_pixels: n = %u, must be 1 .. 2^20", n);
+    RmLaunch L;
+    if (int rc = cull_probe_begin(c, "rm_selftest_cull_pixels", W, H, &L)) return rc;
+    for (uint32_t i = 0; i < n; i++)
+        if (xy[2u * i] >= W || xy[2u * i + 1u] >= H)
+            return fail(c, RM_ERR_RANGE, "rm_selftest_cull_pixels: pixel %u = (%u, %u) outside the %ux%u image", i, xy[2u * i], xy[2u * i + 1u], W, H);
+    DevBuf<uint32_t> d_xy;
+    DevBuf<float> d_out;
+    if (int rc = probe_put(c, d_xy, xy, (size_t)n * 2u)) return rc;
+    if (int rc = d_out.reserve(c, (size_t)n * 8u)) return rc;
+    const size_t shmem = 16u + (size_t)L.n_cone * 16u + (size_t)L.n_slab * 48u + (size_t)(L.n_cone + L.n_slab) * 8u;
+    hipLaunchKernelGGL(rmk::rm_selftest_cull_pixels_kernel, dim3((n + 63u) / 64u), dim3(64), shmem, c->stream, L, d_xy.p, n, d_out.p);
+    if (int rc = probe_finish(c, "rm_selftest_cull_pixels")) return rc;
+    HIP_TRY(c, hipMemcpy(out, d_out.p, (size_t)n * 32u, hipMemcpyDeviceToHost));
+    return RM_OK;
+}
+
+RM_EXPORT int rm_selftest_cull_waves(rm_ctx* c, const float* origin, const float* pos, const float* thr, const uint64_t* live, uint32_t n_waves,
+                                     float extra_margin, uint64_t* out_masks) {
+    if (!c) return RM_ERR_NULL;
+    if (!origin || !pos || !thr || !live || !out_masks) return fail(c, RM_ERR_NULL, "rm_selftest_cull_waves: NULL argument");
+    if (n_waves == 0u || n_waves > 65535u) return fail(c, RM_ERR_ARG, "rm_selftest_cull_waves: n_waves = %u, must be 1 .. 65535", n_waves);
+    for (uint32_t w = 0; w < n_waves; w++)
+        if (live[w] == 0u) return fail(c, RM_ERR_ARG, "rm_selftest_cull_waves: wave %u has no live lane", w);
+    RmLaunch L;
+    if (int rc = cull_probe_begin(c, "rm_selftest_cull_waves", 8u, 8u, &L)) return rc;
+    if (L.unit_mode == RM_UNITS_NONE || L.n_grp == 0u || L.n_grp > 64u)
+        return fail(c, RM_ERR_ARG, "rm_selftest_cull_waves: the program has no units of wave-level culling");
+    DevBuf<float> d_pos, d_thr;
+    DevBuf<unsigned long long> d_live, d_out;
+    if (int rc = probe_put(c, d_pos, pos, (size_t)n_waves * 192u)) return rc;
+    if (int rc = probe_put(c, d_thr, thr, (size_t)n_waves * 64u)) return rc;
+    if (int rc = probe_put(c, d_live, live, (size_t)n_waves)) return rc;
+    if (int rc = d_out.reserve(c, n_waves)) return rc;
+    const rmk::V4 ro{origin[0], origin[1], origin[2], 1.0f};
+    hipLaunchKernelGGL(rmk::rm_selftest_cull_waves_kernel, dim3(n_waves), dim3(64), (size_t)L.n_grp * 32u, c->stream, L, ro, d_pos.p, d_thr.p,
+                       d_live.p, extra_margin, d_out.p);
+    if (int rc = probe_finish(c, "rm_selftest_cull_waves")) return rc;
+    HIP_TRY(c, hipMemcpy(out_masks, d_out.p, (size_t)n_waves * 8u, hipMemcpyDeviceToHost));
     return RM_OK;
 }
 

@@ -73,7 +73,8 @@ struct RmDecoded {
     float unit_kmax = 0.0f;
     // Space transformations (extension): deepest nesting, and -- because a transformed primitive's parameters no longer
     // say where it is -- one world-space bounding sphere (x, y, z, radius) per bounded primitive for the miss tests.
-    // cull_veto: some transform is not a similarity (non-unit quaternion, scale not positive and finite): no culling.
+    // cull_veto: some transform is not a similarity (non-unit quaternion, scale not positive and finite), or a box or cylinder
+    // has a NaN size (it is unbounded): no culling.
     uint32_t xform_depth = 0;
     bool has_xforms = false, cull_veto = false;
     std::vector<float> bounds;  // 4 floats per cone slot; empty unless has_xforms
@@ -212,6 +213,12 @@ static inline int rm_decode_core(uint32_t cmd_count, const uint32_t* words, uint
                 // pruning threshold of a sphere, pre-multiplied (see spec_sphere_far): radius * 1.000005, rounded up
                 if (kind == RM_KIND_SPHERE) r.p[4] = std::nextafterf((float)((double)r.p[3] * 1.000005), INFINITY);
             }
+            // A NaN size of a box or a cylinder drops out of the leaf's maxima: the leaf is an infinite slab or column, which no
+            // table entry and no bound along a ray describes (they read max(NaN, 0) = 0, a flat leaf).  A sphere of NaN radius has
+            // the value NaN everywhere, which every operator drops: it needs no veto.
+            if (kind == RM_KIND_BOX || kind == RM_KIND_CYLINDER)
+                for (uint32_t k = 3; k < np; k++)
+                    if (r.p[k] != r.p[k]) d.cull_veto = true;
             // slot in the kernels' per-kind miss-test tables: cones for spheres, slabs for boxes and cylinders; in a
             // program with transforms every bounded primitive is a cone around its world-space bounding sphere
             uint32_t slot = 0u;
@@ -234,8 +241,13 @@ static inline int rm_decode_core(uint32_t cmd_count, const uint32_t* words, uint
                         const double cx[3] = {a[1] * c[2] - a[2] * c[1], a[2] * c[0] - a[0] * c[2], a[0] * c[1] - a[1] * c[0]};
                         const double t[3] = {2.0 * cx[0], 2.0 * cx[1], 2.0 * cx[2]};
                         const double u[3] = {a[1] * t[2] - a[2] * t[1], a[2] * t[0] - a[0] * t[2], a[0] * t[1] - a[1] * t[0]};
+                        // |q|^2 = 1 + e, |e| < 1e-4 (else cull_veto): the map is (1 - |q|^2) I + |q|^2 R, lengths change by at most
+                        // 2 |e|; and it is not the inverse of the map the evaluation applies (the conjugate's): a point taken
+                        // there and back moves by up to 4 |e| |q|^2 of its distance from the scope's origin -- a leaf far from it
+                        // by more than its own size
+                        const double e = std::fabs(w * w + a[0] * a[0] + a[1] * a[1] + a[2] * a[2] - 1.0);
+                        rho = (rho + 4.0004 * e * std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2])) * (1.0 + 1.0e-3);
                         for (int m = 0; m < 3; m++) c[m] = c[m] + w * t[m] + u[m];
-                        rho *= 1.0 + 1.0e-3;  // |q| within 5e-5 of 1 (else cull_veto): lengths change by < 1e-4
                     }
                 }
                 const double mag = std::fabs(c[0]) + std::fabs(c[1]) + std::fabs(c[2]) + rho;

@@ -601,9 +601,9 @@ RM_DEV bool ray_misses_scene_v5(const CullTables& T, float dx, float dy, float d
 // beyond T = |m| + R + max(c_i, 0) a leaf of bounding radius R around m is farther than max(c_i, 0) anyway, so
 //     c_i(pixel) >= c_i(centre ray) - rho (|m| + R + max(c_i, 0)),
 // the same inflation the plain pixel test applies to its cones and slabs.
+// ray_bound_v5: the bound L itself (the self-test rm_selftest_cull_rays reads it); ray_misses_by_bounds_v5: the verdict.
 template <bool CONE, class LoadRecord>
-RM_DEV bool ray_misses_by_bounds_v5(const LoadRecord& load, uint32_t n_rec, const V4& ro, float dx, float dy, float dz, float min_dist,
-                                    float scale, float rho = 0.0f) {
+RM_DEV float ray_bound_v5(const LoadRecord& load, uint32_t n_rec, const V4& ro, float dx, float dy, float dz, float scale, float rho = 0.0f) {
     if (!CONE) unit_dir(dx, dy, dz);
     const float tiny = 1.0e-18f;  // |d_i| is clamped away from 0: 1 / |d_i| times a coordinate (< 1e12, RmDecoded::bound_walk) stays finite
     const float ax = fmax_(__builtin_fabsf(dx), tiny), ay = fmax_(__builtin_fabsf(dy), tiny), az = fmax_(__builtin_fabsf(dz), tiny);
@@ -684,6 +684,12 @@ RM_DEV bool ray_misses_by_bounds_v5(const LoadRecord& load, uint32_t n_rec, cons
             acc = fmax_(v, -3.0e38f);  // NaN (k = inf) -> -3e38
         }
     }
+    return acc;
+}
+template <bool CONE, class LoadRecord>
+RM_DEV bool ray_misses_by_bounds_v5(const LoadRecord& load, uint32_t n_rec, const V4& ro, float dx, float dy, float dz, float min_dist,
+                                    float scale, float rho = 0.0f) {
+    const float acc = ray_bound_v5<CONE>(load, n_rec, ro, dx, dy, dz, scale, rho);
     const float margin = fmax_(min_dist, 0.0f) * 1.01f + 1.0e-4f * scale;
     return acc > margin;  // NaN -> false
 }
@@ -1364,6 +1370,28 @@ RM_DEV bool pixel_misses_scene_v5(const CullTables& T, const float2* aux, const 
     return clear;
 }
 
+// The pixel test's own table, behind the miss-test tables: per cone / slab entry (|m|, |m| + bounding radius of the inflated
+// box), both rounded up.  Whole workgroup, after the barrier behind cull_build_v5.
+RM_DEV void pixel_aux_build_v5(const float4* t_cone, const float4* t_slab, uint32_t n_cone, uint32_t n_slab, float2* t_aux, uint32_t tid,
+                               uint32_t n_threads) {
+    const float up = 1.0f + 1.0e-6f;
+    for (uint32_t k = tid; k < n_cone + n_slab; k += n_threads) {
+        float4 m;
+        float radius = 0.0f;
+        if (k < n_cone) {
+            m = t_cone[k];
+        } else {
+            const uint32_t j = k - n_cone;
+            m = t_slab[3u * j + 2u];
+            const float4 a = t_slab[3u * j], b = t_slab[3u * j + 1u];
+            const float hx = b.x - a.x, hy = b.y - a.y, hz = b.z - a.z;  // full extents of the inflated box
+            radius = 0.5f * __builtin_sqrtf(hx * hx + hy * hy + hz * hz) * up;
+        }
+        const float len = __builtin_sqrtf(m.x * m.x + m.y * m.y + m.z * m.z) * up;
+        t_aux[k] = make_float2(len, (len + radius) * up);
+    }
+}
+
 __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, uint32_t* cost, uint32_t n_tiles) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     uint32_t* s_veto = smem;
@@ -1387,24 +1415,7 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
         for (uint32_t k = tid; k < L.n_rec; k += 64u * V5_PRE_TILES)
             cull_build_v5(L.prog[k], ro, L.min_dist, L.smooth_slack, t_cone, t_slab, s_veto, L.bounds);
     __syncthreads();
-    if (tables) {
-        const float up = 1.0f + 1.0e-6f;
-        for (uint32_t k = tid; k < L.n_cone + L.n_slab; k += 64u * V5_PRE_TILES) {
-            float4 m;
-            float radius = 0.0f;
-            if (k < L.n_cone) {
-                m = t_cone[k];
-            } else {
-                const uint32_t j = k - L.n_cone;
-                m = t_slab[3u * j + 2u];
-                const float4 a = t_slab[3u * j], b = t_slab[3u * j + 1u];
-                const float hx = b.x - a.x, hy = b.y - a.y, hz = b.z - a.z;  // full extents of the inflated box
-                radius = 0.5f * __builtin_sqrtf(hx * hx + hy * hy + hz * hz) * up;
-            }
-            const float len = __builtin_sqrtf(m.x * m.x + m.y * m.y + m.z * m.z) * up;
-            t_aux[k] = make_float2(len, (len + radius) * up);
-        }
-    }
+    if (tables) pixel_aux_build_v5(t_cone, t_slab, L.n_cone, L.n_slab, t_aux, tid, 64u * V5_PRE_TILES);
     __syncthreads();
     const uint32_t tiles_x = (L.W + 7u) / 8u;
   auto do_tile = [&](uint32_t tile) {  // (whole wave; no barrier inside)
@@ -1696,6 +1707,127 @@ __global__ __launch_bounds__(1024) void rm_tile_sort_v5(RmLaunch L, const uint32
             else if (v != 0u) o[atomicAdd(&base[bucket(v)], 1u)] = i;
         }
     }
+}
+#endif
+
+// ---- Self-tests of the culling decisions (rm_selftest_cull_*; tests/test_gpu_cull_bounds.py) ------------------------------------
+// The device functions above on inputs the caller chooses, with the launch a draw of the context's program would get and the
+// tables staged in LDS the way rm_render_v5_body and rm_tile_pre_v5 stage them.  (They stand here, not next to
+// rm_selftest_wave_kernel: they need the functions defined since.)
+#if !defined(RM_JIT_TU)
+// LDS: {veto, 3 x pad}, cone[n_cone], slab[3 n_slab], aux[n_cone + n_slab] (the pixel probe).  One wave per workgroup.
+// Rays: out_flags[i] bit 0 the verdict of ray_misses_scene_v5 (false without culling), bit 1 the tables were usable (culling on, no
+// veto), bit 2 the walk on lower bounds applies, bit 3 its verdict, bits 8.. the veto word; out_bound[i] the walk's bound (NaN
+// when it does not apply).
+__global__ __launch_bounds__(64) void rm_selftest_cull_rays_kernel(RmLaunch L, V4 ro, const float* dirs, uint32_t n, uint32_t* out_flags,
+                                                                   float* out_bound) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    uint32_t* s_veto = smem;
+    float4* t_cone = reinterpret_cast<float4*>(smem + 4u);
+    float4* t_slab = t_cone + L.n_cone;
+    const CullTables cullt{t_cone, t_slab, s_veto, L.n_cone, L.n_slab};
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0u) *s_veto = 0u;
+    __syncthreads();
+    const bool tables = (L.flags & 1u) != 0u;
+    if (tables)
+        for (uint32_t k = tid; k < L.n_rec; k += 64u) cull_build_v5(L.prog[k], ro, L.min_dist, L.smooth_slack, t_cone, t_slab, s_veto, L.bounds);
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 64u + tid, j = i < n ? i : n - 1u;
+    const float gx = dirs[3u * j], gy = dirs[3u * j + 1u], gz = dirs[3u * j + 2u];
+    const uint32_t veto = *s_veto;
+    const bool clear = tables && ray_misses_scene_v5(cullt, gx, gy, gz);
+    const float prune_scale = L.scene_scale + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));
+    const float bound_scale = prune_scale + L.smooth_slack;  // (as rm_render_v5_body adds them up)
+    const bool walk = tables && (L.flags & 32u) && (veto & 1u) == 0u && bound_scale < 1.0e12f;
+    float acc = __uint_as_float(0x7FC00000u);
+    bool by_bounds = false;
+    if (walk) {
+        auto load_record = [&](uint32_t r, uint32_t& op, float (&p)[7]) {
+            const RmRecord& rec = L.prog[r];  // wave-uniform address: scalar loads
+            op = rec.op;
+#pragma unroll
+            for (int k = 0; k < 7; k++) p[k] = rec.p[k];
+        };
+        acc = ray_bound_v5<false>(load_record, L.n_rec, ro, gx, gy, gz, bound_scale);
+        by_bounds = ray_misses_by_bounds_v5<false>(load_record, L.n_rec, ro, gx, gy, gz, L.min_dist, bound_scale);
+    }
+    if (i < n) {
+        out_flags[i] = (clear ? 1u : 0u) | ((tables && veto == 0u) ? 2u : 0u) | (walk ? 4u : 0u) | (by_bounds ? 8u : 0u) | (veto << 8);
+        out_bound[i] = acc;
+    }
+}
+// Pixels of a W x H frame (L.W, L.H) under the context's uniforms: out[8 i + 0..3] the cone (c, rho) of pixel_misses_scene_v5
+// (rho = NaN: not usable), [4] the CONE walk's bound (NaN when it does not apply), [5] flags as an integer: bit 0 the verdict of
+// pixel_misses_scene_v5, bit 1 the tables were usable, bit 2 the CONE walk applies, bit 3 its verdict; [6], [7] zero.
+__global__ __launch_bounds__(64) void rm_selftest_cull_pixels_kernel(RmLaunch L, const uint32_t* xy, uint32_t n, float* out) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    uint32_t* s_veto = smem;
+    float4* t_cone = reinterpret_cast<float4*>(smem + 4u);
+    float4* t_slab = t_cone + L.n_cone;
+    float2* t_aux = reinterpret_cast<float2*>(t_slab + 3u * L.n_slab);
+    __shared__ float s_off[32];
+    const CullTables cullt{t_cone, t_slab, s_veto, L.n_cone, L.n_slab};
+    const uint32_t tid = threadIdx.x;
+    const rm_uniforms u = L.u;
+    const V4 ro = matvec(u.inv_view, 0.0f, 0.0f, 0.0f, 1.0f);
+    const bool tables = (L.flags & 1u) != 0u;
+    if (tid == 0u) *s_veto = 0u;
+    if (tid < 16u) sample_offset(u, tid >> 2, tid & 3u, s_off[2u * tid], s_off[2u * tid + 1u]);
+    __syncthreads();
+    if (tables)
+        for (uint32_t k = tid; k < L.n_rec; k += 64u) cull_build_v5(L.prog[k], ro, L.min_dist, L.smooth_slack, t_cone, t_slab, s_veto, L.bounds);
+    __syncthreads();
+    if (tables) pixel_aux_build_v5(t_cone, t_slab, L.n_cone, L.n_slab, t_aux, tid, 64u);
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 64u + tid, j = i < n ? i : n - 1u;
+    const float sx = screen_x(xy[2u * j], L.W), sy = screen_y(rm_global_row(L, xy[2u * j + 1u]), L.H);
+    float mp[16], mv[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) { mp[k] = u.inv_proj[k]; mv[k] = u.inv_view[k]; }
+    const float nan = __uint_as_float(0x7FC00000u);
+    float cone[4] = {nan, nan, nan, nan}, corner[4][3], acc = nan;
+    bool clear = false, walk = false, by_bounds = false;
+    const uint32_t veto = *s_veto;
+    if (tables) {
+        clear = pixel_misses_scene_v5(cullt, t_aux, mp, mv, s_off, ro, sx, sy, cone, corner);
+        const float bound_scale = (L.scene_scale + L.smooth_slack) + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));  // (as rm_tile_pre_v5)
+        walk = (L.flags & 32u) && (veto & 1u) == 0u && bound_scale < 1.0e12f && cone[3] == cone[3];
+        if (__ballot(walk) != 0ull) {
+            auto load_record = [&](uint32_t r, uint32_t& op, float (&p)[7]) {
+                const RmRecord& rec = L.prog[r];
+                op = rec.op;
+#pragma unroll
+                for (int k = 0; k < 7; k++) p[k] = rec.p[k];
+            };
+            const float b = ray_bound_v5<true>(load_record, L.n_rec, ro, cone[0], cone[1], cone[2], bound_scale, cone[3]);
+            const bool v = ray_misses_by_bounds_v5<true>(load_record, L.n_rec, ro, cone[0], cone[1], cone[2], L.min_dist, bound_scale, cone[3]);
+            if (walk) { acc = b; by_bounds = v; }
+        }
+    }
+    if (i < n) {
+        float* o = out + 8u * (size_t)i;
+        o[0] = cone[0]; o[1] = cone[1]; o[2] = cone[2]; o[3] = cone[3]; o[4] = acc;
+        o[5] = __uint_as_float((clear ? 1u : 0u) | ((tables && veto == 0u) ? 2u : 0u) | (walk ? 4u : 0u) | (by_bounds ? 8u : 0u));
+        o[6] = 0.0f; o[7] = 0.0f;
+    }
+}
+// Waves: pos[(3 w + k) * 64 + lane] coordinate k of wave w's lane, thr[64 w + lane], live[w] the mask of its live lanes (not 0);
+// out[w] the mask of wave_cull_lattice or wave_cull_blend, by the program's unit_mode (not RM_UNITS_NONE).  LDS: the unit table.
+__global__ __launch_bounds__(64) void rm_selftest_cull_waves_kernel(RmLaunch L, V4 ro, const float* pos, const float* thr, const unsigned long long* live,
+                                                                    float extra_margin, unsigned long long* out) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    const uint32_t lane = threadIdx.x, w = blockIdx.x;
+    stage_units(smem, L.prog + L.n_rec, L.n_grp, lane, 64u);
+    __syncthreads();
+    const float x = pos[(3u * w) * 64u + lane], y = pos[(3u * w + 1u) * 64u + lane], z = pos[(3u * w + 2u) * 64u + lane];
+    const unsigned long long live_mask = live[w];
+    const bool is_live = ((live_mask >> lane) & 1ull) != 0ull;
+    const float prune_scale = L.scene_scale + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));
+    unsigned long long need;
+    if (L.unit_mode == RM_UNITS_LATTICE) need = wave_cull_lattice(smem, L.n_grp, x, y, z, thr[64u * w + lane], is_live, live_mask);
+    else need = wave_cull_blend(smem, L.n_grp, L.unit_kmax, x, y, z, extra_margin, prune_scale, is_live, live_mask);
+    if (lane == 0u) out[w] = need;
 }
 #endif
 
