@@ -149,6 +149,50 @@ pub const RM_MESH_STAT_BRICKS_KEPT: c_int = 3;
 pub const RM_MESH_STAT_EVALUATIONS: c_int = 4;
 pub const RM_MESH_STAT_SCRATCH_BYTES: c_int = 5;
 pub const RM_MESH_STATS: c_int = 6;
+// enum rm_moment: indices into the moments of rm_mass_moments; RM_MOMENTS is their number
+pub const RM_MOMENT_COUNT: c_int = 0;
+pub const RM_MOMENT_X: c_int = 1;
+pub const RM_MOMENT_Y: c_int = 2;
+pub const RM_MOMENT_Z: c_int = 3;
+pub const RM_MOMENT_XX: c_int = 4;
+pub const RM_MOMENT_YY: c_int = 5;
+pub const RM_MOMENT_ZZ: c_int = 6;
+pub const RM_MOMENT_XY: c_int = 7;
+pub const RM_MOMENT_YZ: c_int = 8;
+pub const RM_MOMENT_XZ: c_int = 9;
+pub const RM_MOMENT_MIN_X: c_int = 10;
+pub const RM_MOMENT_MIN_Y: c_int = 11;
+pub const RM_MOMENT_MIN_Z: c_int = 12;
+pub const RM_MOMENT_MAX_X: c_int = 13;
+pub const RM_MOMENT_MAX_Y: c_int = 14;
+pub const RM_MOMENT_MAX_Z: c_int = 15;
+pub const RM_MOMENTS: c_int = 16;
+// enum rm_massstat: indices into the statistics of rm_mass_moments; RM_MASS_STATS is their number
+pub const RM_MASS_STAT_BRICKS: c_int = 0;
+pub const RM_MASS_STAT_BRICKS_KEPT: c_int = 1;
+pub const RM_MASS_STAT_BRICKS_INSIDE: c_int = 2;
+pub const RM_MASS_STAT_EVALUATIONS: c_int = 3;
+pub const RM_MASS_STAT_SCRATCH_BYTES: c_int = 4;
+pub const RM_MASS_STATS: c_int = 5;
+// enum rm_massprop: indices into the output of rm_mass_from_moments; RM_MASS_PROPS is their number
+pub const RM_MASS_VOLUME: c_int = 0;
+pub const RM_MASS_MASS: c_int = 1;
+pub const RM_MASS_CX: c_int = 2;
+pub const RM_MASS_CY: c_int = 3;
+pub const RM_MASS_CZ: c_int = 4;
+pub const RM_MASS_IXX: c_int = 5;
+pub const RM_MASS_IYY: c_int = 6;
+pub const RM_MASS_IZZ: c_int = 7;
+pub const RM_MASS_IXY: c_int = 8;
+pub const RM_MASS_IYZ: c_int = 9;
+pub const RM_MASS_IXZ: c_int = 10;
+pub const RM_MASS_LO_X: c_int = 11;
+pub const RM_MASS_LO_Y: c_int = 12;
+pub const RM_MASS_LO_Z: c_int = 13;
+pub const RM_MASS_HI_X: c_int = 14;
+pub const RM_MASS_HI_Y: c_int = 15;
+pub const RM_MASS_HI_Z: c_int = 16;
+pub const RM_MASS_PROPS: c_int = 17;
 
 // Slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table).
 // enum rm_slicecount: indices into the counts of rm_slice_contours; RM_SLICE_COUNTS is their number
@@ -218,6 +262,10 @@ extern "C" {
     pub fn rm_mesh_case_table(out: *mut u32, n_out: u32) -> c_int;
     pub fn rm_extract_mesh_sparse(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, level: f32,
                                   flags: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_mass_moments(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, level: f32,
+                           out_moments: *mut u64, n_moments: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_mass_from_moments(moments: *const u64, n_moments: u32, origin: *const f32, step: *const f32, density: f64,
+                                out: *mut f64, n_out: u32) -> c_int;
     pub fn rm_slice_contours(ctx: *mut rm_ctx, axis: u32, origin_uv: *const f32, step_uv: *const f32, nu: u32, nv: u32,
                              heights: *const f32, n_layers: u32, level: f32, flags: u32, out_counts: *mut u64,
                              n_counts: u32) -> c_int;
@@ -282,6 +330,19 @@ pub fn program_lipschitz(cmd_count: u32, words: &[u32]) -> Result<f64, c_int> {
     let mut l = 0.0f64;
     let rc = unsafe { rm_program_lipschitz(cmd_count, words.as_ptr(), words.len() as u32, &mut l) };
     if rc == RM_OK { Ok(l) } else { Err(rc) }
+}
+
+/// Volume, mass, centre of mass, inertia about it and bounding box (`out`, at least `RM_MASS_PROPS` entries indexed by
+/// `RM_MASS_*`) from the moments of `mass_moments` on the lattice (`origin`, `step`), by the midpoint rule
+/// (`rm_mass_from_moments`; host code, no GPU needed).  `Err(status)` for a density or step that is not finite or a step <= 0.
+pub fn mass_from_moments(moments: &[u64], origin: [f32; 3], step: [f32; 3], density: f64, out: &mut [f64]) -> Result<(), c_int> {
+    assert!(moments.len() >= RM_MOMENTS as usize, "mass_from_moments: moments is shorter than RM_MOMENTS entries");
+    assert!(out.len() >= RM_MASS_PROPS as usize, "mass_from_moments: out is shorter than RM_MASS_PROPS entries");
+    let rc = unsafe {
+        rm_mass_from_moments(moments.as_ptr(), RM_MOMENTS as u32, origin.as_ptr(), step.as_ptr(), density, out.as_mut_ptr(),
+                             RM_MASS_PROPS as u32)
+    };
+    if rc == RM_OK { Ok(()) } else { Err(rc) }
 }
 
 /// What the reference `unwrap()`s away (renderer.rs:24, 203, 250): a status code of `enum rm_status`
@@ -496,6 +557,19 @@ impl RayMarchingResources {
         let counts = (out_stats[RM_MESH_STAT_VERTICES as usize], out_stats[RM_MESH_STAT_TRIANGLES as usize]);
         self.mesh.set(Some(counts));
         Ok(counts)
+    }
+
+    /// The integer moments of the solid `map_scene < level` on the lattice (`rm_mass_moments`; 2..4096 points per axis): fills
+    /// `out_moments` (at least `RM_MOMENTS` entries, indexed by `RM_MOMENT_*`) and `out_stats` (at least `RM_MASS_STATS`,
+    /// indexed by `RM_MASS_STAT_*`).  Exact integers: every run gives the same words.  Leaves the context's mesh and slices alone.
+    pub fn mass_moments(&self, origin: [f32; 3], step: [f32; 3], nx: u32, ny: u32, nz: u32, level: f32, out_moments: &mut [u64],
+                        out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(out_moments.len() >= RM_MOMENTS as usize, "mass_moments: out_moments is shorter than RM_MOMENTS entries");
+        assert!(out_stats.len() >= RM_MASS_STATS as usize, "mass_moments: out_stats is shorter than RM_MASS_STATS entries");
+        self.check(unsafe {
+            rm_mass_moments(self.ctx, origin.as_ptr(), step.as_ptr(), nx, ny, nz, level, out_moments.as_mut_ptr(), RM_MOMENTS as u32,
+                            out_stats.as_mut_ptr(), RM_MASS_STATS as u32)
+        })
     }
 
     /// The mesh of the last successful `extract_mesh` (of the (vertices, triangles) it returned): positions (three per

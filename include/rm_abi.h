@@ -369,6 +369,58 @@ int rm_extract_mesh_sparse(rm_ctx* ctx, const float* origin, const float* step, 
  * a Scale of 0.  Errors: rm_validate_program's status for an invalid program, RM_ERR_NULL for a NULL out_L. */
 int rm_program_lipschitz(uint32_t cmd_count, const uint32_t* words, uint32_t n_words, double* out_L);
 
+/* Mass properties (extension; DESIGN.md section 17 is the contract, to the last bit): integer moments of the solid d < level
+ * on a lattice, and volume, centre of mass, inertia tensor and bounding box from them.
+ * Lattice, values and "inside" are rm_extract_mesh's: point (i, j, k) lies at o + (float)i * s per axis, its value is what
+ * rm_query_points returns there for the program and limits at the call (the empty program: max_dist), and it is inside iff
+ * d < level (NaN is outside).  out_moments[RM_MOMENT_*], over the inside points (i, j, k):
+ *   COUNT                 their number N
+ *   X, Y, Z               sum i, sum j, sum k
+ *   XX, YY, ZZ            sum i^2, sum j^2, sum k^2
+ *   XY, YZ, XZ            sum i j, sum j k, sum i k
+ *   MIN_*, MAX_*          the smallest and the largest inside index per axis; for an empty solid 0xFFFFFFFF and 0
+ * All are integers and integer addition is associative, so the words do not depend on any order: two runs, and any correct
+ * implementation, give identical words.  Lattice: 2..4096 points per axis (RM_ERR_RANGE otherwise) and no limit on the
+ * product.  With that limit no sum overflows: N <= 4096^3 = 2^36 and every term (an index below 2^12, or a product of two)
+ * is below 2^24, so every sum is below 2^60.
+ * Bricks: section 15's rule, unchanged and on the same tile, decides which bricks of 8 x 8 x 8 points are evaluated
+ * (BRICKS_KEPT is rm_extract_mesh_sparse's for the same lattice and level).  A brick's own points are a subset of its tile, so
+ * a brick proven clear lies wholly on the side of its probe: inside (probe < level) it contributes the closed-form moments of
+ * its index box and no evaluation, outside nothing.  out_stats[RM_MASS_STAT_*]:
+ *   BRICKS, BRICKS_KEPT   bricks of the lattice, and those that were evaluated point by point
+ *   BRICKS_INSIDE         bricks proven wholly inside
+ *   EVALUATIONS           map_scene evaluations: one probe per brick and the kept bricks' own points
+ *   SCRATCH_BYTES         device memory the call used
+ * Synchronous on the context's own stream, ordered after its earlier work; never touches the draw state and replaces neither
+ * the context's mesh nor its slices.  Errors: RM_ERR_NULL for a NULL output, RM_ERR_ARG for n_moments < RM_MOMENTS,
+ * n_stats < RM_MASS_STATS, a level, origin or step that is not finite or a step <= 0; RM_ERR_TOO_LARGE and RM_ERR_DEVICE as
+ * for rm_extract_mesh_sparse; otherwise those of a query for the program and limits. */
+enum rm_moment { RM_MOMENT_COUNT = 0, RM_MOMENT_X = 1, RM_MOMENT_Y = 2, RM_MOMENT_Z = 3, RM_MOMENT_XX = 4, RM_MOMENT_YY = 5,
+                 RM_MOMENT_ZZ = 6, RM_MOMENT_XY = 7, RM_MOMENT_YZ = 8, RM_MOMENT_XZ = 9, RM_MOMENT_MIN_X = 10,
+                 RM_MOMENT_MIN_Y = 11, RM_MOMENT_MIN_Z = 12, RM_MOMENT_MAX_X = 13, RM_MOMENT_MAX_Y = 14, RM_MOMENT_MAX_Z = 15,
+                 RM_MOMENTS = 16 };
+enum rm_massstat { RM_MASS_STAT_BRICKS = 0, RM_MASS_STAT_BRICKS_KEPT = 1, RM_MASS_STAT_BRICKS_INSIDE = 2,
+                   RM_MASS_STAT_EVALUATIONS = 3, RM_MASS_STAT_SCRATCH_BYTES = 4, RM_MASS_STATS = 5 };
+int rm_mass_moments(rm_ctx* ctx, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                    uint64_t* out_moments, uint32_t n_moments, uint64_t* out_stats, uint32_t n_stats);
+/* Volume, mass, centre of mass, inertia tensor about the centre of mass and bounding box from the moments of rm_mass_moments
+ * on the lattice (origin, step) (host code; no context), by the midpoint rule: each inside point stands for a cell of volume
+ * dV = sx sy sz centred on it.  All arithmetic is binary64.  out[RM_MASS_*]:
+ *   VOLUME = N dV, MASS = density VOLUME, C_a = o_a + s_a S_a / N
+ *   central second moments from exact integers: D_ab = N S_ab - S_a S_b (128-bit), mu_ab = s_a s_b D_ab / N^2, plus
+ *   s_a^2 / 12 on the diagonal for the cell's own extent; IXX = MASS (mu_yy + mu_zz), ..., IXY = -MASS mu_xy, ...
+ *   LO_a = o_a + min_a s_a, HI_a = o_a + max_a s_a (the outermost inside points, not their cells' faces)
+ * N = 0: volume, mass, centre and inertia 0, LO = +infinity, HI = -infinity.  This is a first-order quadrature of the solid
+ * (volume error at most surface area x sqrt(3) max(step)) and exact as a statement about the lattice.
+ * Errors: RM_ERR_NULL for a NULL pointer, RM_ERR_ARG for n_moments < RM_MOMENTS, n_out < RM_MASS_PROPS, a density, origin or
+ * step that is not finite, or a step <= 0. */
+enum rm_massprop { RM_MASS_VOLUME = 0, RM_MASS_MASS = 1, RM_MASS_CX = 2, RM_MASS_CY = 3, RM_MASS_CZ = 4, RM_MASS_IXX = 5,
+                   RM_MASS_IYY = 6, RM_MASS_IZZ = 7, RM_MASS_IXY = 8, RM_MASS_IYZ = 9, RM_MASS_IXZ = 10, RM_MASS_LO_X = 11,
+                   RM_MASS_LO_Y = 12, RM_MASS_LO_Z = 13, RM_MASS_HI_X = 14, RM_MASS_HI_Y = 15, RM_MASS_HI_Z = 16,
+                   RM_MASS_PROPS = 17 };
+int rm_mass_from_moments(const uint64_t* moments, uint32_t n_moments, const float* origin, const float* step, double density,
+                         double* out, uint32_t n_out);
+
 /* Slicing (extension; DESIGN.md section 16 is the contract, to the last bit): the closed outlines of the solid d < level in a
  * stack of planes, as ordered polylines -- what a slicer or a section drawing needs, evaluated directly on a 2-D lattice
  * per layer instead of through a triangle mesh.  From the program, limits and material table as they are at the call.

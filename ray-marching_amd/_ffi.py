@@ -52,6 +52,15 @@ RM_MESH_NORMALS, RM_MESH_IDS = 1, 2
 (RM_MESH_STAT_VERTICES, RM_MESH_STAT_TRIANGLES, RM_MESH_STAT_BRICKS, RM_MESH_STAT_BRICKS_KEPT, RM_MESH_STAT_EVALUATIONS,
  RM_MESH_STAT_SCRATCH_BYTES, RM_MESH_STATS) = range(7)
 MESH_STAT_NAMES = ("vertices", "triangles", "bricks", "bricks_kept", "evaluations", "scratch_bytes")
+# mass properties (rm_mass_moments / rm_mass_from_moments): enum rm_moment, enum rm_massstat, enum rm_massprop
+(RM_MOMENT_COUNT, RM_MOMENT_X, RM_MOMENT_Y, RM_MOMENT_Z, RM_MOMENT_XX, RM_MOMENT_YY, RM_MOMENT_ZZ, RM_MOMENT_XY, RM_MOMENT_YZ,
+ RM_MOMENT_XZ, RM_MOMENT_MIN_X, RM_MOMENT_MIN_Y, RM_MOMENT_MIN_Z, RM_MOMENT_MAX_X, RM_MOMENT_MAX_Y, RM_MOMENT_MAX_Z,
+ RM_MOMENTS) = range(17)
+(RM_MASS_STAT_BRICKS, RM_MASS_STAT_BRICKS_KEPT, RM_MASS_STAT_BRICKS_INSIDE, RM_MASS_STAT_EVALUATIONS, RM_MASS_STAT_SCRATCH_BYTES,
+ RM_MASS_STATS) = range(6)
+MASS_STAT_NAMES = ("bricks", "bricks_kept", "bricks_inside", "evaluations", "scratch_bytes")
+(RM_MASS_VOLUME, RM_MASS_MASS, RM_MASS_CX, RM_MASS_CY, RM_MASS_CZ, RM_MASS_IXX, RM_MASS_IYY, RM_MASS_IZZ, RM_MASS_IXY, RM_MASS_IYZ,
+ RM_MASS_IXZ, RM_MASS_LO_X, RM_MASS_LO_Y, RM_MASS_LO_Z, RM_MASS_HI_X, RM_MASS_HI_Y, RM_MASS_HI_Z, RM_MASS_PROPS) = range(18)
 # slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table): enum rm_slicecount, the indices of out_counts
 RM_SLICE_POINTS, RM_SLICE_CONTOURS, RM_SLICE_COUNTS = 0, 1, 2
 # lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit): enum rm_light, the parameter names in index order
@@ -161,6 +170,10 @@ def hip_lib():
         L.rm_mesh_case_table.restype = C.c_int
         L.rm_extract_mesh_sparse.argtypes = [vp, f3, f3, u32, u32, u32, C.c_float, u32, C.POINTER(u64), u32]
         L.rm_extract_mesh_sparse.restype = C.c_int
+        L.rm_mass_moments.argtypes = [vp, f3, f3, u32, u32, u32, C.c_float, C.POINTER(u64), u32, C.POINTER(u64), u32]
+        L.rm_mass_moments.restype = C.c_int
+        L.rm_mass_from_moments.argtypes = [C.POINTER(u64), u32, f3, f3, C.c_double, C.POINTER(C.c_double), u32]
+        L.rm_mass_from_moments.restype = C.c_int
         L.rm_slice_contours.argtypes = [vp, u32, f3, f3, u32, u32, f3, u32, C.c_float, u32, C.POINTER(u64), u32]
         L.rm_slice_contours.restype = C.c_int
         L.rm_read_slices.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]

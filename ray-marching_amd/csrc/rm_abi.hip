@@ -27,6 +27,7 @@
 #include "rm_mesh.h"
 #include "rm_mesh_bound.h"
 #include "rm_mesh_sparse.h"
+#include "rm_mass.h"
 #include "rm_slice.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
@@ -1460,6 +1461,16 @@ SparseCountFn sparse_count_kernel(int loop) {
 // The regions of the kept bricks' scratch round up to 16 bytes like all others; the segment maps and the segments' first
 // (vertex, triangle) pairs always were whole multiples of 16, so RM_MESH_STAT_SCRATCH_BYTES is what it was.
 static_assert(sizeof(rmk::SparseSegMap) % 16u == 0u && (rmk::kBrickSegs * sizeof(uint2)) % 16u == 0u, "sparse scratch layout");
+using MassProbeFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, double, double, uint32_t*, unsigned long long*, unsigned long long*);
+MassProbeFn mass_probe_kernel(int loop) {
+    return with_loop(loop, [](auto tag) -> MassProbeFn { return rmk::rm_mass_probe_kernel<decltype(tag)::value>; });
+}
+using MassCountFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, const uint32_t*, unsigned long long*, unsigned long long*);
+MassCountFn mass_count_kernel(int loop) {
+    return with_loop(loop, [](auto tag) -> MassCountFn { return rmk::rm_mass_count_kernel<decltype(tag)::value>; });
+}
+static_assert(rmk::kMoments == (uint32_t)RM_MOMENTS, "a row holds the moments of enum rm_moment");
+constexpr uint32_t kMaxMassDim = 4096u;  // rm_mass_moments: every sum below 2^60 (rm_abi.h)
 // One workgroup of `kernel` per grid entry, with the query's LDS columns behind the kernel's own LDS.
 template <class K, class... Args>
 int sparse_launch(rm_ctx* c, K kernel, uint32_t blocks, size_t shmem, hipStream_t s, Args... args) {
@@ -1676,6 +1687,136 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
     out_stats[RM_MESH_STAT_BRICKS_KEPT] = K;
     out_stats[RM_MESH_STAT_EVALUATIONS] = n_evals;
     out_stats[RM_MESH_STAT_SCRATCH_BYTES] = B.bytes + kept_bytes;
+    return RM_OK;
+}
+
+// ---- mass properties (rm_mass.h) ----
+RM_EXPORT int rm_mass_moments(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                              uint64_t* out_moments, uint32_t n_moments, uint64_t* out_stats, uint32_t n_stats) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_moments || !out_stats) return fail(c, RM_ERR_NULL, "rm_mass_moments: out_moments or out_stats is NULL");
+    if (n_moments < (uint32_t)RM_MOMENTS) return fail(c, RM_ERR_ARG, "rm_mass_moments: n_moments %u < RM_MOMENTS", n_moments);
+    if (n_stats < (uint32_t)RM_MASS_STATS) return fail(c, RM_ERR_ARG, "rm_mass_moments: n_stats %u < RM_MASS_STATS", n_stats);
+    if (int rc = check_lattice(c, "rm_mass_moments", origin, step)) return rc;
+    if (int rc = check_iso(c, "rm_mass_moments", level, 0u)) return rc;
+    if (nx < 2 || ny < 2 || nz < 2 || nx > kMaxMassDim || ny > kMaxMassDim || nz > kMaxMassDim)
+        return fail(c, RM_ERR_RANGE, "rm_mass_moments: lattice %ux%ux%u: 2..4096 points per axis", nx, ny, nz);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);
+    if (rc != RM_OK) return rc;
+    if (shmem + 4096u > std::max<size_t>(c->max_lds, 64u * 1024u))
+        return fail(c, RM_ERR_TOO_LARGE, "rm_mass_moments: the program needs %zu bytes of LDS per workgroup", shmem + 4096u);
+    // the bounds of the program, for points up to the lattice's largest coordinate (as the kernels compute it)
+    double P = 0.0;
+    const uint32_t dims[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; a++) {
+        const float last = origin[a] + (float)(dims[a] - 1u) * step[a];
+        P = std::fmax(P, std::fmax(std::fabs((double)origin[a]), std::fabs((double)last)));
+    }
+    RmProgramBound bound;
+    if ((rc = rm_program_bound(c->cmd[0], c->cmd.data() + 1, (uint32_t)c->cmd.size() - 1u, P, &bound)) != RM_OK) return rc;
+    rmk::SparseGrid g{origin[0], origin[1], origin[2], step[0], step[1], step[2], nx, ny, nz,
+                      (nx + rmk::kBrick - 1u) / rmk::kBrick, (ny + rmk::kBrick - 1u) / rmk::kBrick, (nz + rmk::kBrick - 1u) / rmk::kBrick, 0u};
+    const uint64_t nb64 = (uint64_t)g.bx * g.by * g.bz;  // (<= 2^27 with 4096 points per axis)
+    if (nb64 >= 0xFFFFFFFFull - 256u)
+        return fail(c, RM_ERR_DEVICE, "rm_mass_moments: %llu bricks: the brick table is limited to 2^32 entries", (unsigned long long)nb64);
+    g.nb = (uint32_t)nb64;
+    // the mesh's scratch buffers (neither holds a result): the brick tables, then the kept bricks' rows
+    const uint32_t n_entries = g.nb + 1u, n_pblocks = (n_entries + 255u) / 256u;
+    const rml::MassBrickTables B(n_entries, n_pblocks);
+    if ((rc = c->d_mbricks.reserve(c, B.bytes)) != RM_OK) return rc;
+    char* bs = c->d_mbricks.p;
+    uint32_t* boff = B.boff.at(bs);
+    unsigned long long* psums = B.psums.at(bs);
+    unsigned long long* ptot = B.ptot.at(bs);
+    unsigned long long* evals = B.evals.at(bs);
+    unsigned long long* prows = B.prows.at(bs);
+    unsigned long long* result = B.result.at(bs);
+    HIP_TRY(c, hipMemsetAsync(evals, 0, 8, s));
+    if ((rc = sparse_launch(c, mass_probe_kernel(loop), n_pblocks, shmem, s, Q, g, level, bound.L, 2.0 * bound.E, boff, psums, prows)) != RM_OK)
+        return rc;
+    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, psums, n_pblocks, ptot);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long tot[2] = {0ull, 0ull};
+    HIP_TRY(c, hipMemcpyAsync(tot, ptot, sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const uint64_t K = tot[0], n_inside = tot[1];
+    size_t kept_bytes = 0;
+    const unsigned long long* krows = nullptr;
+    if (K > 0u) {
+        const rml::MassKeptScratch S(K);
+        kept_bytes = S.bytes;
+        if ((rc = c->d_mscratch.reserve(c, kept_bytes)) != RM_OK) return rc;
+        char* sc = c->d_mscratch.p;
+        uint32_t* klist = S.klist.at(sc);
+        hipLaunchKernelGGL(rmk::rm_sparse_compact_kernel, dim3(n_pblocks), dim3(256), 0, s, n_entries,
+                           static_cast<const unsigned long long*>(psums), boff, klist);
+        if ((rc = sparse_launch(c, mass_count_kernel(loop), (uint32_t)K, shmem, s, Q, g, level, static_cast<const uint32_t*>(klist),
+                                S.krows.at(sc), evals)) != RM_OK)
+            return rc;
+        krows = S.krows.at(sc);
+    }
+    hipLaunchKernelGGL(rmk::rm_mass_reduce_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned long long*>(prows), n_pblocks, krows,
+                       (uint32_t)K, result);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long mom[RM_MOMENTS], ev = 0ull;
+    HIP_TRY(c, hipMemcpyAsync(mom, result, sizeof mom, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (int m = 0; m < RM_MOMENTS; m++) out_moments[m] = mom[m];
+    out_stats[RM_MASS_STAT_BRICKS] = g.nb;
+    out_stats[RM_MASS_STAT_BRICKS_KEPT] = K;
+    out_stats[RM_MASS_STAT_BRICKS_INSIDE] = n_inside;
+    out_stats[RM_MASS_STAT_EVALUATIONS] = g.nb + ev;
+    out_stats[RM_MASS_STAT_SCRATCH_BYTES] = B.bytes + kept_bytes;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_mass_from_moments(const uint64_t* moments, uint32_t n_moments, const float* origin, const float* step, double density,
+                                   double* out, uint32_t n_out) {
+    if (!moments || !origin || !step || !out) return RM_ERR_NULL;
+    if (n_moments < (uint32_t)RM_MOMENTS || n_out < (uint32_t)RM_MASS_PROPS) return RM_ERR_ARG;
+    if (!std::isfinite(density)) return RM_ERR_ARG;
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(origin[a]) || !std::isfinite(step[a]) || !(step[a] > 0.0f)) return RM_ERR_ARG;
+    const double o[3] = {origin[0], origin[1], origin[2]}, st[3] = {step[0], step[1], step[2]};
+    for (int p = 0; p < RM_MASS_PROPS; p++) out[p] = 0.0;
+    const uint64_t N = moments[RM_MOMENT_COUNT];
+    if (N == 0u) {
+        for (int a = 0; a < 3; a++) {
+            out[RM_MASS_LO_X + a] = HUGE_VAL;
+            out[RM_MASS_HI_X + a] = -HUGE_VAL;
+        }
+        return RM_OK;
+    }
+    const double n = (double)N, dV = st[0] * st[1] * st[2], volume = n * dV, mass = density * volume;
+    out[RM_MASS_VOLUME] = volume;
+    out[RM_MASS_MASS] = mass;
+    for (int a = 0; a < 3; a++) {
+        out[RM_MASS_CX + a] = o[a] + st[a] * ((double)moments[RM_MOMENT_X + a] / n);
+        out[RM_MASS_LO_X + a] = o[a] + (double)moments[RM_MOMENT_MIN_X + a] * st[a];
+        out[RM_MASS_HI_X + a] = o[a] + (double)moments[RM_MOMENT_MAX_X + a] * st[a];
+    }
+#if !defined(__HIP_DEVICE_COMPILE__)
+    // central second moments from exact integers: D_ab = N S_ab - S_a S_b, |D_ab| <= 2^96
+    using i128 = __int128;
+    const auto central = [&](int a, int b, int ab) {
+        const i128 D = (i128)N * (i128)moments[ab] - (i128)moments[RM_MOMENT_X + a] * (i128)moments[RM_MOMENT_X + b];
+        return st[a] * st[b] * ((double)D / (n * n));
+    };
+    const double mxx = central(0, 0, RM_MOMENT_XX) + st[0] * st[0] / 12.0, myy = central(1, 1, RM_MOMENT_YY) + st[1] * st[1] / 12.0,
+                 mzz = central(2, 2, RM_MOMENT_ZZ) + st[2] * st[2] / 12.0;  // (+ the cell's own extent)
+    out[RM_MASS_IXX] = mass * (myy + mzz);
+    out[RM_MASS_IYY] = mass * (mxx + mzz);
+    out[RM_MASS_IZZ] = mass * (mxx + myy);
+    out[RM_MASS_IXY] = 0.0 - mass * central(0, 1, RM_MOMENT_XY);
+    out[RM_MASS_IYZ] = 0.0 - mass * central(1, 2, RM_MOMENT_YZ);
+    out[RM_MASS_IXZ] = 0.0 - mass * central(0, 2, RM_MOMENT_XZ);
+#endif
     return RM_OK;
 }
 

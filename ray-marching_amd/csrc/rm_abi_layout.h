@@ -79,6 +79,28 @@ struct SparseKeptScratch {
           bytes(a.total) {}
 };
 
+// rm_mass_moments, per brick: 4 B as above; per 256 bricks a block sum and one row of 16 moments (128 B); totals, the
+// evaluation count and the result row.
+struct MassBrickTables {
+    Carver a;
+    Region<uint32_t> boff;
+    Region<unsigned long long> psums, ptot, evals, prows, result;
+    size_t bytes;
+    MassBrickTables(uint32_t n_entries, uint32_t n_pblocks)
+        : boff(a.take<uint32_t>(n_entries)), psums(a.take<unsigned long long>(n_pblocks)), ptot(a.take<unsigned long long>(2)),
+          evals(a.take<unsigned long long>(2)), prows(a.take<unsigned long long>((size_t)n_pblocks * 16u)),
+          result(a.take<unsigned long long>(16)), bytes(a.total) {}
+};
+
+// ... and per kept brick: its index and its row of 16 moments.
+struct MassKeptScratch {
+    Carver a;
+    Region<uint32_t> klist;
+    Region<unsigned long long> krows;
+    size_t bytes;
+    explicit MassKeptScratch(uint64_t K) : klist(a.take<uint32_t>(K)), krows(a.take<unsigned long long>(K * 16u)), bytes(a.total) {}
+};
+
 // rm_slice_contours' per-layer tables: heights, layer_first, the first vertex of each layer of a batch of `per`, totals.
 // (heights and layer_first lie before anything `per` sizes: rm_read_slices finds layer_first without it.)
 struct SliceLayerTables {

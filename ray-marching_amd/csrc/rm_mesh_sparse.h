@@ -56,6 +56,29 @@ RM_DEV SparseBrick sparse_brick(const SparseGrid& g, uint32_t b) {
 // ---- probe ------------------------------------------------------------------------------------------------------------------
 // keep[b] (as a u32, scanned in place later) for the bricks [0, nb) and 0 for the extra entry nb; block sums of 256 entries.
 // margin_scale = L, err2 = 2 E: both +inf when the program has no bound.
+// The decision for brick b (< g.nb): true when it is kept; v is map_scene at the tile's centre.  Shared by the mesh's probe and
+// the mass probe (rm_mass.h), so that both keep the same bricks.
+template <int LOOP>
+RM_DEV bool sparse_probe_brick(const QueryLaunch& Q, float* spill, const SparseGrid& g, const SparseBrick& B, float level, double L,
+                               double err2, float& v) {
+    // Lattice coordinates are monotone in the index (one rounded product, one rounded sum, step > 0), so every point of
+    // the tile lies in the box of its first and last point as they are computed
+    const float x0 = grid_coord(g.ox, B.i0, g.sx), x1 = grid_coord(g.ox, B.i0 + B.ex - 1u, g.sx);
+    const float y0 = grid_coord(g.oy, B.j0, g.sy), y1 = grid_coord(g.oy, B.j0 + B.ey - 1u, g.sy);
+    const float z0 = grid_coord(g.oz, B.k0, g.sz), z1 = grid_coord(g.oz, B.k0 + B.ez - 1u, g.sz);
+    const float cx = x0 + (x1 - x0) * 0.5f, cy = y0 + (y1 - y0) * 0.5f, cz = z0 + (z1 - z0) * 0.5f;  // any point serves
+    v = query_distance<LOOP>(Q, spill, cx, cy, cz);
+    // the radius about the probe as it was computed, in binary64 (differences of binary32 numbers: exact or 2^-53 off)
+    const double hx = fmax((double)x1 - (double)cx, (double)cx - (double)x0), hy = fmax((double)y1 - (double)cy, (double)cy - (double)y0),
+                 hz = fmax((double)z1 - (double)cz, (double)cz - (double)z0);
+    const double r = sqrt(hx * hx + hy * hy + hz * hz), reach = L * r;
+    const double margin = (reach + err2) * (1.0 + 1.0e-9);
+    // skipped only when proven clear: a NaN probe, an infinite bound, or an error term that is not small against
+    // L * radius (steps near the coordinates' ulp) all keep the brick
+    const bool clear = fabs((double)v - (double)level) > margin && err2 <= 0.5 * reach;
+    return !clear;
+}
+
 template <int LOOP>
 __global__ __launch_bounds__(256) void rm_sparse_probe_kernel(QueryLaunch Q, SparseGrid g, float level, double L, double err2,
                                                               uint32_t* __restrict__ keep, unsigned long long* __restrict__ block_sums) {
@@ -63,24 +86,8 @@ __global__ __launch_bounds__(256) void rm_sparse_probe_kernel(QueryLaunch Q, Spa
     const uint32_t b = blockIdx.x * 256u + threadIdx.x;
     uint32_t k = 0u;
     if (b < g.nb) {
-        float* spill = query_spill(Q.slots);
-        const SparseBrick B = sparse_brick(g, b);
-        // Lattice coordinates are monotone in the index (one rounded product, one rounded sum, step > 0), so every point of
-        // the tile lies in the box of its first and last point as they are computed
-        const float x0 = grid_coord(g.ox, B.i0, g.sx), x1 = grid_coord(g.ox, B.i0 + B.ex - 1u, g.sx);
-        const float y0 = grid_coord(g.oy, B.j0, g.sy), y1 = grid_coord(g.oy, B.j0 + B.ey - 1u, g.sy);
-        const float z0 = grid_coord(g.oz, B.k0, g.sz), z1 = grid_coord(g.oz, B.k0 + B.ez - 1u, g.sz);
-        const float cx = x0 + (x1 - x0) * 0.5f, cy = y0 + (y1 - y0) * 0.5f, cz = z0 + (z1 - z0) * 0.5f;  // any point serves
-        const float v = query_distance<LOOP>(Q, spill, cx, cy, cz);
-        // the radius about the probe as it was computed, in binary64 (differences of binary32 numbers: exact or 2^-53 off)
-        const double hx = fmax((double)x1 - (double)cx, (double)cx - (double)x0), hy = fmax((double)y1 - (double)cy, (double)cy - (double)y0),
-                     hz = fmax((double)z1 - (double)cz, (double)cz - (double)z0);
-        const double r = sqrt(hx * hx + hy * hy + hz * hz), reach = L * r;
-        const double margin = (reach + err2) * (1.0 + 1.0e-9);
-        // skipped only when proven clear: a NaN probe, an infinite bound, or an error term that is not small against
-        // L * radius (steps near the coordinates' ulp) all keep the brick
-        const bool clear = fabs((double)v - (double)level) > margin && err2 <= 0.5 * reach;
-        k = clear ? 0u : 1u;
+        float v;
+        k = sparse_probe_brick<LOOP>(Q, query_spill(Q.slots), g, sparse_brick(g, b), level, L, err2, v) ? 1u : 0u;
     }
     if (b <= g.nb) keep[b] = k;
     unsigned long long total;

@@ -445,6 +445,29 @@ class RayMarchingResources:
         m.stats = {name: int(stats[k]) for k, name in enumerate(_ffi.MESH_STAT_NAMES)}
         return m
 
+    # -- mass properties (rm_mass_moments / rm_mass_from_moments) -------------------------------------------------------------
+    def mass_moments(self, origin, step, shape, level=0.0):
+        """The integer moments of the solid map_scene < level on an exact lattice (origin, step, shape as sample_grid takes them;
+        2..4096 points per axis): a MassMoments with .moments (uint64[16], _ffi.RM_MOMENT_*: count, sums of i, j, k, of their
+        squares and products, smallest and largest inside index per axis) and .stats (a dict: _ffi.MASS_STAT_NAMES).  Exact:
+        every implementation and every run gives the same words."""
+        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
+        mom = np.zeros(_ffi.RM_MOMENTS, dtype=np.uint64)
+        stats = (C.c_uint64 * _ffi.RM_MASS_STATS)()
+        self._check(self._L.rm_mass_moments(self._h, fp(o), fp(s), nx, ny, nz, float(level), mom.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                            _ffi.RM_MOMENTS, stats, _ffi.RM_MASS_STATS))
+        return MassMoments(mom, {name: int(stats[k]) for k, name in enumerate(_ffi.MASS_STAT_NAMES)}, o, s, (nx, ny, nz))
+
+    def mass_properties(self, lo, hi, resolution, level=0.0, density=1.0):
+        """Volume, mass, centre of mass, inertia tensor (about the centre of mass) and bounding box of the solid map_scene < level
+        inside the box [lo, hi], on the lattice extract_mesh_sparse builds from (lo, hi, resolution): a dict (mass_from_moments)
+        that also carries "moments" and "stats".  A first-order quadrature: each inside lattice point stands for its cell."""
+        lo, step, n = self._box_lattice(lo, hi, resolution)
+        m = self.mass_moments(lo, step, n, level)
+        props = mass_from_moments(m.moments, m.origin, m.step, density)
+        props["moments"], props["stats"] = m.moments, m.stats
+        return props
+
     def _read_mesh(self, V, T, normals, ids, device):
         """rm_read_mesh of the extraction that just returned V vertices and T triangles, as a mesh.Mesh."""
         from . import mesh as _mesh
@@ -613,6 +636,48 @@ class RayMarchingCallback:
         W = int(self.viewport[0]) if width is None else width
         H = int(self.viewport[1]) if height is None else height
         return resources.draw(W, H)
+
+
+class MassMoments:
+    """moments: uint64[16] (_ffi.RM_MOMENT_*); stats: a dict (bricks, bricks_kept, bricks_inside, evaluations, scratch_bytes);
+    origin, step (float32[3]) and shape of the lattice they belong to."""
+
+    def __init__(self, moments, stats, origin, step, shape):
+        self.moments, self.stats, self.origin, self.step, self.shape = moments, stats, origin, step, shape
+
+    def __repr__(self):
+        return "MassMoments(%d inside points of %s)" % (int(self.moments[0]), "x".join(map(str, self.shape)))
+
+    def properties(self, density=1.0):
+        return mass_from_moments(self.moments, self.origin, self.step, density)
+
+
+MASS_PROP_NAMES = ("volume", "mass", "cx", "cy", "cz", "ixx", "iyy", "izz", "ixy", "iyz", "ixz", "lo_x", "lo_y", "lo_z", "hi_x", "hi_y",
+                   "hi_z")
+
+
+def mass_from_moments(moments, origin, step, density=1.0, raw=False):
+    """rm_mass_from_moments (host code, no GPU): the moments of mass_moments on the lattice (origin, step) -> a dict with volume,
+    mass, centroid (3), inertia (3 x 3, about the centroid), bbox_lo and bbox_hi (3 each: the outermost inside points), all float64
+    by the midpoint rule.  raw=True: the float64[17] array in _ffi.RM_MASS_* order instead."""
+    m = np.ascontiguousarray(moments, dtype=np.uint64).reshape(-1)
+    o = np.array(origin, dtype=np.float32, copy=True).reshape(-1)
+    s = np.array(step, dtype=np.float32, copy=True).reshape(-1)
+    if o.shape != (3,) or s.shape != (3,):
+        raise ValueError("origin and step must have 3 entries each (x, y, z)")
+    out = np.zeros(_ffi.RM_MASS_PROPS, dtype=np.float64)
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    rc = _ffi.hip_lib().rm_mass_from_moments(m.ctypes.data_as(C.POINTER(C.c_uint64)), len(m), fp(o), fp(s), float(density),
+                                             out.ctypes.data_as(C.POINTER(C.c_double)), len(out))
+    if rc != _ffi.RM_OK:
+        raise _ffi.RmError(rc, "rm_mass_from_moments: " + _ffi.hip_lib().rm_status_string(rc).decode())
+    if raw:
+        return out
+    ixx, iyy, izz, ixy, iyz, ixz = (float(x) for x in out[_ffi.RM_MASS_IXX:_ffi.RM_MASS_IXZ + 1])
+    return {"volume": float(out[_ffi.RM_MASS_VOLUME]), "mass": float(out[_ffi.RM_MASS_MASS]),
+            "centroid": out[_ffi.RM_MASS_CX:_ffi.RM_MASS_CZ + 1].copy(),
+            "inertia": np.array([[ixx, ixy, ixz], [ixy, iyy, iyz], [ixz, iyz, izz]]),
+            "bbox_lo": out[_ffi.RM_MASS_LO_X:_ffi.RM_MASS_LO_Z + 1].copy(), "bbox_hi": out[_ffi.RM_MASS_HI_X:_ffi.RM_MASS_HI_Z + 1].copy()}
 
 
 def lighting_defaults():
