@@ -292,6 +292,7 @@ extern "C" {
     pub fn rm_selftest_wave(ctx: *mut rm_ctx, input: *const f32, n_waves: u32, out: *mut f32) -> c_int;
     pub fn rm_selftest_cull_rays(ctx: *mut rm_ctx, origin: *const f32, dirs: *const f32, n: u32, out_flags: *mut u32, out_bound: *mut f32) -> c_int;
     pub fn rm_selftest_cull_pixels(ctx: *mut rm_ctx, w: u32, h: u32, xy: *const u32, n: u32, out: *mut f32) -> c_int;
+    pub fn rm_selftest_cull_tiles(ctx: *mut rm_ctx, w: u32, h: u32, xy: *const u32, n: u32, out: *mut f32) -> c_int;
     pub fn rm_selftest_cull_waves(ctx: *mut rm_ctx, origin: *const f32, pos: *const f32, thr: *const f32, live: *const u64, n_waves: u32,
                                   extra_margin: f32, out_masks: *mut u64) -> c_int;
     pub fn rm_read_wave_stats(ctx: *mut rm_ctx, dst: *mut c_void, cap_bytes: u64, out_bytes: *mut u64) -> c_int;

@@ -566,12 +566,19 @@ int rm_selftest_wave(rm_ctx* ctx, const float* in, uint32_t n_waves, float* out)
  *   0..2 the centre direction and 3 the radius rho of the cone of the pixel's sixteen sample directions (NaN: no usable cone),
  *   4 the lower bound over the cone (NaN when that test does not apply), 5 flags as the bits of an integer (bit 0 the tables
  *   clear the pixel, bit 1 the tables were usable, bit 2 the test on lower bounds applies, bit 3 it clears the pixel), 6..7 zero.
+ * rm_selftest_cull_tiles: 8 x 8 tiles xy[2 n] = (tile_x, tile_y) of a W x H frame under the context's uniforms, as the pre-pass
+ *   classifies a whole tile from the rectangle of its 32 x 32 sample positions.  out[8 i + ..]: 0..2 the centre direction and 3 the
+ *   radius rho of the cone of those directions (NaN: no usable cone), 4 the checker bit of a one-cell tile (else 0), 5 flags as
+ *   the bits of an integer (bit 0 the tables clear the tile, bit 1 every sample is sky, bit 2 every sample falls in one checker
+ *   cell, bit 3 the tables were usable), 6..7 zero.  The pre-pass settles a tile with bit 0 and bit 1 or 2 without looking at
+ *   its pixels.
  * rm_selftest_cull_waves: n_waves waves of 64 positions, pos[(3 w + k) * 64 + lane] (k = x, y, z), thresholds thr[64 w + lane]
  *   and live-lane masks live[w] (not 0); camera position origin[3].  out_masks[w]: the units wave-level culling keeps -- the
  *   threshold rule (lattice programs; extra_margin unused) or the rules of a blending chain (thr unused), by the program;
  *   RM_ERR_ARG when the program has no units. */
 int rm_selftest_cull_rays(rm_ctx* ctx, const float* origin, const float* dirs, uint32_t n, uint32_t* out_flags, float* out_bound);
 int rm_selftest_cull_pixels(rm_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* xy, uint32_t n, float* out);
+int rm_selftest_cull_tiles(rm_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* xy, uint32_t n, float* out);
 int rm_selftest_cull_waves(rm_ctx* ctx, const float* origin, const float* pos, const float* thr, const uint64_t* live, uint32_t n_waves,
                            float extra_margin, uint64_t* out_masks);
 

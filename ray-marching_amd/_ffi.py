@@ -149,6 +149,8 @@ def hip_lib():
         L.rm_selftest_cull_rays.restype = C.c_int
         L.rm_selftest_cull_pixels.argtypes = [vp, u32, u32, vp, u32, vp]
         L.rm_selftest_cull_pixels.restype = C.c_int
+        L.rm_selftest_cull_tiles.argtypes = [vp, u32, u32, vp, u32, vp]
+        L.rm_selftest_cull_tiles.restype = C.c_int
         L.rm_selftest_cull_waves.argtypes = [vp, vp, vp, vp, vp, u32, C.c_float, vp]
         L.rm_selftest_cull_waves.restype = C.c_int
         L.rm_read_wave_stats.argtypes = [vp, vp, u64, C.POINTER(u64)]

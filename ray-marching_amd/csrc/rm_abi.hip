@@ -448,8 +448,7 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
     if (int rc = c->d_cost.reserve(c, (size_t)n_tiles * n_frames)) return rc;
     if (int rc = c->d_order.reserve(c, (size_t)n_tiles * n_frames)) return rc;
     if (int rc = c->d_counters.reserve(c, (size_t)n_frames * 4u)) return rc;
-    const uint32_t pre_tiles_per_group = rmk::V5_PRE_TILES * rmk::V5_PRE_TILES_PER_WAVE;
-    hipLaunchKernelGGL(rmk::rm_tile_pre_v5, dim3((n_tiles + pre_tiles_per_group - 1u) / pre_tiles_per_group, 1, n_frames),
+    hipLaunchKernelGGL(rmk::rm_tile_pre_v5, dim3((n_tiles + rmk::V5_PRE_BLOCK - 1u) / rmk::V5_PRE_BLOCK, 1, n_frames),
                        dim3(64u * rmk::V5_PRE_TILES), 16u + cull_bytes + (size_t)(L.n_cone + L.n_slab) * 8u, s, L, c->d_cost.p, n_tiles);
     // RM_OPT_BALANCE = 3: the march kernel records how long every tile took; the next draw of the same shape
     // dispatches the longest first (consecutive frames of an interactive view or an orbit look alike)
@@ -2276,6 +2275,28 @@ RM_EXPORT int rm_selftest_cull_pixels(rm_ctx* c, uint32_t W, uint32_t H, const u
     const size_t shmem = 16u + (size_t)L.n_cone * 16u + (size_t)L.n_slab * 48u + (size_t)(L.n_cone + L.n_slab) * 8u;
     hipLaunchKernelGGL(rmk::rm_selftest_cull_pixels_kernel, dim3((n + 63u) / 64u), dim3(64), shmem, c->stream, L, d_xy.p, n, d_out.p);
     if (int rc = probe_finish(c, "rm_selftest_cull_pixels")) return rc;
+    HIP_TRY(c, hipMemcpy(out, d_out.p, (size_t)n * 32u, hipMemcpyDeviceToHost));
+    return RM_OK;
+}
+
+RM_EXPORT int rm_selftest_cull_tiles(rm_ctx* c, uint32_t W, uint32_t H, const uint32_t* xy, uint32_t n, float* out) {
+    if (!c) return RM_ERR_NULL;
+    if (!xy || !out) return fail(c, RM_ERR_NULL, "rm_selftest_cull_tiles: NULL argument");
+    if (n == 0u || n > (1u << 20)) return fail(c, RM_ERR_ARG, "rm_selftest_cull_tiles: n = %u, must be 1 .. 2^20", n);
+    RmLaunch L;
+    if (int rc = cull_probe_begin(c, "rm_selftest_cull_tiles", W, H, &L)) return rc;
+    const uint32_t tiles_x = (W + 7u) / 8u, tiles_y = (H + 7u) / 8u;
+    for (uint32_t i = 0; i < n; i++)
+        if (xy[2u * i] >= tiles_x || xy[2u * i + 1u] >= tiles_y)
+            return fail(c, RM_ERR_RANGE, "rm_selftest_cull_tiles: tile %u = (%u, %u) outside the %ux%u tiles of the image", i, xy[2u * i], xy[2u * i + 1u],
+                        tiles_x, tiles_y);
+    DevBuf<uint32_t> d_xy;
+    DevBuf<float> d_out;
+    if (int rc = probe_put(c, d_xy, xy, (size_t)n * 2u)) return rc;
+    if (int rc = d_out.reserve(c, (size_t)n * 8u)) return rc;
+    const size_t shmem = 16u + (size_t)L.n_cone * 16u + (size_t)L.n_slab * 48u + (size_t)(L.n_cone + L.n_slab) * 8u;
+    hipLaunchKernelGGL(rmk::rm_selftest_cull_tiles_kernel, dim3((n + 63u) / 64u), dim3(64), shmem, c->stream, L, d_xy.p, n, d_out.p);
+    if (int rc = probe_finish(c, "rm_selftest_cull_tiles")) return rc;
     HIP_TRY(c, hipMemcpy(out, d_out.p, (size_t)n * 32u, hipMemcpyDeviceToHost));
     return RM_OK;
 }

@@ -1281,9 +1281,12 @@ void rm_render_v5_lean(RmLaunch L, V5Work work, uint32_t n_tiles, uint32_t refil
 }
 
 // ---------------------------------------------------------------------------------------------
-// Pre-pass: one WAVE per tile, lane = pixel, four tiles per workgroup.
+// Pre-pass: a workgroup of four waves owns a block of V5_PRE_BLOCK consecutive tiles.  It builds the
+// tables once, settles what it can per TILE (lane = tile), and its waves then claim the block's tiles
+// from a counter: a settled tile is filled with its constant, every other tile gets the per-pixel
+// test (one wave per tile, lane = pixel).
 //
-// Each lane decides whether ALL 16 AA rays of its pixel provably miss the scene, with one test per
+// Per pixel, each lane decides whether ALL 16 AA rays of its pixel provably miss the scene, with one test per
 // primitive instead of sixteen.  The 16 sample points are an affine 4x4 grid on the screen and
 // pt_world.xyz - ro.xyz is affine in the screen position (two mat-vecs, wgsl:56-61), so the 16 ray
 // directions lie in the convex cone spanned by the four extreme samples (i, j in {0, 3}).  With the
@@ -1299,28 +1302,56 @@ void rm_render_v5_lean(RmLaunch L, V5Work work, uint32_t n_tiles, uint32_t refil
 // inflated by a further D rho, every ray of the pixel misses the box.  rho carries 0.1 % + 2e-6 of
 // slack for the rounding of e_i and c.
 //
+// Per tile, the same three proofs (clear of the tables, sky, one checker cell) run on the rectangle of
+// the tile's 32 x 32 sample positions; none of them needs the rectangle to be one pixel's grid.  What
+// has to be re-examined is that a tile's samples are NOT one affine grid: every pixel centre
+// screen_x(px), screen_y(py) and every sum centre + offset is rounded on its own.  The proofs never
+// use the grid, though, only that every sample position lies in the rectangle spanned by the four
+// extreme ones, and that holds exactly, with no slack: a correctly rounded operation is monotone in
+// each operand, so screen_x is non-decreasing in px, screen_y non-increasing in py, and
+// fl(centre + offset) is monotone in both; the sample offsets are monotone in (i, j).  Hence every
+// x the march computes in the tile lies in [fl(screen_x(8 tx) + min offset), fl(screen_x(8 tx + 7) +
+// max offset)], both ends being values the march computes itself (for an edge tile the far end belongs
+// to a pixel outside the frame: a superset), and likewise for y, provided the tile's eight rows are
+// consecutive rows of the frame (strips of a height that is no multiple of 8 break that: no tile
+// verdicts then).  The remaining error is that of the two mat-vecs and the normalisation between a
+// position and its direction.  It is absolute -- some 1e-7 of `mag`, whatever the rectangle's size --
+// and it is what the 2e-6 in rho, the 1e-5 mag of the sky rule and the E = 4e-6 mag of the cell rule
+// were sized for: they cover an interior sample and a corner of a tile as they cover those of a pixel,
+// and the relative 0.1 % of rho only grows with the rectangle.  So the constants stand as they are,
+// and the bounds bx, by of |x|, |y| that `mag` is built from are taken over the tile's rectangle.
+// At rho >= 0.05 (frames of a few dozen pixels) a tile has no usable cone and nothing is settled per tile.
+//
+// A tile is settled per tile iff the tables clear its cone (the lower-bound walk of a blending program
+// stays per pixel) and its samples are all sky or all in one cell.  It gets the constant the per-pixel
+// path would have written -- zeros, or the sum of sixteen equal gamma values over 16 -- and cost 0.
+//
 // cost = number of pixels that are not provably clear (0..64).  A tile with cost 0 is finished
 // here: its wave sums the 16 gamma-corrected floor colours of every pixel in the reference's order
 // (wgsl:44-45, 68-69, 73-75) and writes it.  Tiles with cost > 0 go on the work list; the march
-// kernel repeats the (sharper) test per ray.  ~60 % of the tiles of the metric frame end here.
+// kernel repeats the (sharper) test per ray.  76 % of the tiles of the metric frame end here, 60.5 % of
+// all tiles settled per tile (tools/prepass_tile_classes.py; tests/test_gpu_prepass_tiles.py).
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t V5_PRE_TILES = 4u;  // waves per pre-pass workgroup, one tile at a time each
-// Tiles each of those waves walks through: one.  (Four -- to spread the workgroup's prologue: records fetched, tables built, three
-// barriers -- made the kernel slower, 60 -> 75 us: it is bound by its work, and expensive tiles are neighbours.)
-constexpr uint32_t V5_PRE_TILES_PER_WAVE = 1u;
+// Tiles per workgroup.  The waves claim them one by one (expensive tiles are neighbours: handing each wave a fixed four made the
+// kernel slower, 60 -> 75 us).  The block size also fixes how full the one classifying wave is (lane = tile: 32 of its 64 lanes,
+// while the other three waves wait at the barrier) and how often the prologue is paid.  16 and 64 both measured slower than 32 on
+// the headline (profiles/r11_prepass_tile_classes_ab.txt); why was not profiled.
+constexpr uint32_t V5_PRE_BLOCK = 32u;
+static_assert(V5_PRE_BLOCK >= 1u && V5_PRE_BLOCK <= 64u, "one wave classifies the block, lane = tile");
 
 #if !defined(RM_JIT_TU)  // not part of a specialised translation unit (rm_jit.h)
-// cone_out: (unit centre direction, rho) of the pixel's sixteen sample directions; rho = NaN when the cone is not usable.
-// corner[c]: pt_world.xyz - ro.xyz of corner sample c (samples (0,0), (3,0), (0,3), (3,3)), as gen_ray computes it before its
-// normalisation; the caller's sky / floor tests reuse them.  m_proj / m_view: the matrices (in vector registers), off: the
-// table of the sixteen sample offsets.
-RM_DEV bool pixel_misses_scene_v5(const CullTables& T, const float2* aux, const float* m_proj, const float* m_view, const float* off,
-                                  const V4& ro, float sx, float sy, float (&cone_out)[4], float (&corner)[4][3]) {
+// The cone of a rectangle of sample positions.  px[a] + ox[a], py[b] + oy[b] (a, b in {0, 1}; added as gen_ray adds a pixel centre
+// and a sample offset) are its extreme positions; corner c is (a, b) = (c & 1, c >> 1).  cone_out: (unit centre direction, rho) of
+// the directions through the rectangle; rho = NaN when the cone is not usable.  corner[c]: pt_world.xyz - ro.xyz of corner c,
+// as gen_ray computes it before its normalisation; the caller's sky / floor tests reuse them.  m_proj / m_view: the matrices (in
+// vector registers).  Returns whether the cone is usable.
+RM_DEV bool rect_cone_v5(const float* m_proj, const float* m_view, const V4& ro, const float (&px)[2], const float (&py)[2], const float (&ox)[2],
+                         const float (&oy)[2], float (&cone_out)[4], float (&corner)[4][3]) {
     float cx = 0.0f, cy = 0.0f, cz = 0.0f, ex[4], ey[4], ez[4];
 #pragma unroll
     for (uint32_t c = 0; c < 4u; c++) {
-        const uint32_t s = ((c & 1u) * 3u) * 4u + (c >> 1) * 3u;  // sample (i, j) = table entry 4 i + j
-        gen_ray_unnormalized_at(m_proj, m_view, ro, sx, sy, off[2u * s], off[2u * s + 1u], ex[c], ey[c], ez[c]);  // unit_dir normalises
+        gen_ray_unnormalized_at(m_proj, m_view, ro, px[c & 1u], py[c >> 1], ox[c & 1u], oy[c >> 1], ex[c], ey[c], ez[c]);  // unit_dir normalises
         corner[c][0] = ex[c]; corner[c][1] = ey[c]; corner[c][2] = ez[c];
         unit_dir(ex[c], ey[c], ez[c]);
         cx += ex[c]; cy += ey[c]; cz += ez[c];
@@ -1340,6 +1371,11 @@ RM_DEV bool pixel_misses_scene_v5(const CullTables& T, const float2* aux, const 
     for (uint32_t c = 0; c < 4u; c++) cone_ok = cone_ok && (ex[c] - cx) * (ex[c] - cx) < 1.0f && (ey[c] - cy) * (ey[c] - cy) < 1.0f && (ez[c] - cz) * (ez[c] - cz) < 1.0f;
     cone_out[0] = cx; cone_out[1] = cy; cone_out[2] = cz;
     cone_out[3] = cone_ok ? rho : __uint_as_float(0x7FC00000u);
+    return cone_ok;
+}
+// Whether the tables clear every direction of a cone of rect_cone_v5 (cone_ok: what it returned).
+RM_DEV bool cone_misses_tables_v5(const CullTables& T, const float2* aux, const float (&cone)[4], bool cone_ok) {
+    const float cx = cone[0], cy = cone[1], cz = cone[2], rho = cone[3];
     bool clear = cone_ok && *T.veto == 0u;  // a Plane (veto bit 1) leaves the tables unusable, not the cone
     for (uint32_t k = 0; k < T.n_cone; k++) {
         const float4 a = T.cone[k];  // wave-uniform address: LDS broadcast
@@ -1369,6 +1405,14 @@ RM_DEV bool pixel_misses_scene_v5(const CullTables& T, const float2* aux, const 
     }
     return clear;
 }
+// One pixel: the rectangle is its 4 x 4 grid of samples, spanned by samples (0,0), (3,0), (0,3), (3,3) (table entry 4 i + j of
+// off, the table of the sixteen sample offsets).
+RM_DEV bool pixel_misses_scene_v5(const CullTables& T, const float2* aux, const float* m_proj, const float* m_view, const float* off,
+                                  const V4& ro, float sx, float sy, float (&cone_out)[4], float (&corner)[4][3]) {
+    const float px[2] = {sx, sx}, py[2] = {sy, sy}, ox[2] = {off[0], off[24]}, oy[2] = {off[1], off[7]};
+    const bool cone_ok = rect_cone_v5(m_proj, m_view, ro, px, py, ox, oy, cone_out, corner);
+    return cone_misses_tables_v5(T, aux, cone_out, cone_ok);
+}
 
 // The pixel test's own table, behind the miss-test tables: per cone / slab entry (|m|, |m| + bounding radius of the inflated
 // box), both rounded up.  Whole workgroup, after the barrier behind cull_build_v5.
@@ -1392,6 +1436,111 @@ RM_DEV void pixel_aux_build_v5(const float4* t_cone, const float4* t_slab, uint3
     }
 }
 
+// The colour rules of a rectangle of sample positions whose rays all miss the scene.  corner[c]: pt_world.xyz - ro.xyz of its four
+// extreme samples (rect_cone_v5); bx, by: upper bounds of |x|, |y| over the rectangle's positions.
+//
+// Sky: a sample whose ray points away from the floor plane (t <= 0 in wgsl:120-121) is black, and the sum of sixteen zeros is
+// zero.  pt_world.y - ro.y is affine in the sample's screen position, so its sign over the rectangle is decided at the four
+// corner samples up to rounding; with the camera above the plane (-1.5 - ro.y < 0), "all four corners point up by more than the
+// rounding can move any sample" means dy > 0, t < 0 for all of them.  The margin is 1e-5 of `mag`, the sum of the absolute
+// values of every term the two mat-vecs add up for the y component (each of the ~30 roundings on the way is <= 6e-8 of a
+// partial sum, hence of mag; interior and corner values each move by that, the affine argument needs twice it).  Anything
+// non-finite fails the comparison.
+RM_DEV bool rect_sky_v5(const rm_uniforms& u, const V4& ro, const float (&corner)[4][3], float bx, float by, float& mag) {
+    float lo = __uint_as_float(0x7F800000u);
+#pragma unroll
+    for (uint32_t c = 0; c < 4u; c++) {
+        lo = corner[c][1] < lo ? corner[c][1] : lo;
+        if (!(corner[c][1] == corner[c][1])) lo = corner[c][1];  // a NaN sticks and makes the test below false
+    }
+    mag = __builtin_fabsf(ro.y);
+#pragma unroll
+    for (int k = 0; k < 4; k++)  // |inv_view row y| . (|inv_proj| (|x|, |y|, 1, 1))
+        mag += __builtin_fabsf(u.inv_view[1 + 4 * k]) * (((__builtin_fabsf(u.inv_proj[k]) * bx + __builtin_fabsf(u.inv_proj[k + 4]) * by) +
+                                                          __builtin_fabsf(u.inv_proj[k + 8])) + __builtin_fabsf(u.inv_proj[k + 12]));
+    return (-1.5f - ro.y) < 0.0f && lo > 1.0e-5f * mag;
+}
+// Floor, one checker cell for the whole rectangle.  With every sample ray pointing down (t > 0) the floor point of a sample is
+// fx = o.x + C ex / ey, C = -1.5 - o.y (the normalisation cancels), a linear-fractional function of the sample's screen
+// position: monotone along every segment where ey keeps its sign, so over the rectangle it stays between its values at the four
+// corner samples.  If the interval those span -- widened by everything rounding can do to a sample's own fx: the mat-vec errors
+// E (4e-6 of `mag`, per component) pushed through |C| / |ey| (E_x + |ex| E_y / |ey|), once for the corners and once for the
+// sample, the approximate reciprocal used here and the five roundings of the sample's own chain -- rounds to ONE integer after
+// the +0.5 of wgsl:124 (rint is monotone), and the same holds for z, all samples carry the same checker bit `code`, and each
+// pixel is the sum of sixteen equal gamma values.  mag: as rect_sky_v5 left it.
+RM_DEV bool rect_cell_v5(const rm_uniforms& u, const V4& ro, const float (&corner)[4][3], float bx, float by, float mag, int& code) {
+    const float Cf = -1.5f - ro.y;  // as shade_floor computes it
+    float ex[4], eyc[4], ez[4], ey_hi = -__uint_as_float(0x7F800000u), ax_hi = 0.0f, az_hi = 0.0f;
+#pragma unroll
+    for (uint32_t c = 0; c < 4u; c++) {
+        ex[c] = corner[c][0]; eyc[c] = corner[c][1]; ez[c] = corner[c][2];
+        ey_hi = eyc[c] > ey_hi ? eyc[c] : ey_hi;
+        if (!(eyc[c] == eyc[c])) ey_hi = eyc[c];
+        ax_hi = fmax_(ax_hi, __builtin_fabsf(ex[c]));
+        az_hi = fmax_(az_hi, __builtin_fabsf(ez[c]));
+    }
+    float mag_x = __builtin_fabsf(ro.x), mag_z = __builtin_fabsf(ro.z);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float pvk = ((__builtin_fabsf(u.inv_proj[k]) * bx + __builtin_fabsf(u.inv_proj[k + 4]) * by) + __builtin_fabsf(u.inv_proj[k + 8])) +
+                          __builtin_fabsf(u.inv_proj[k + 12]);
+        mag_x += __builtin_fabsf(u.inv_view[0 + 4 * k]) * pvk;
+        mag_z += __builtin_fabsf(u.inv_view[2 + 4 * k]) * pvk;
+    }
+    const float Ey = 4.0e-6f * mag, Ex = 4.0e-6f * mag_x, Ez = 4.0e-6f * mag_z;
+    const float my = -ey_hi - 2.0f * Ey;  // every sample's |ey| is at least this
+    bool uniform = Cf < -1.0e-20f && my > 0.0f && ey_hi < -4.0f * Ey;
+    const float inv_my = __builtin_amdgcn_rcpf(my) * 1.00001f, absC = -Cf;
+    float gx_lo = __uint_as_float(0x7F800000u), gx_hi = -gx_lo, gz_lo = gx_lo, gz_hi = -gx_lo;
+#pragma unroll
+    for (uint32_t c = 0; c < 4u; c++) {
+        const float r = __builtin_amdgcn_rcpf(eyc[c]);
+        const float gx = ex[c] * r, gz = ez[c] * r;
+        gx_lo = fmin_(gx_lo, gx); gx_hi = fmax_(gx_hi, gx);
+        gz_lo = fmin_(gz_lo, gz); gz_hi = fmax_(gz_hi, gz);
+        uniform = uniform && gx == gx && gz == gz;  // (v_min / v_max drop a NaN)
+    }
+    // C < 0: the interval of fx - o.x is [C gx_hi, C gx_lo]
+    const float dx_lo = Cf * gx_hi, dx_hi = Cf * gx_lo, dz_lo = Cf * gz_hi, dz_hi = Cf * gz_lo;
+    const float dev_x = fmax_(__builtin_fabsf(dx_lo), __builtin_fabsf(dx_hi)), dev_z = fmax_(__builtin_fabsf(dz_lo), __builtin_fabsf(dz_hi));
+    const float del_x = 4.0f * (absC * inv_my) * (Ex + ((ax_hi + Ex) * inv_my) * Ey) + 2.0e-5f * ((1.0f + __builtin_fabsf(ro.x)) + dev_x);
+    const float del_z = 4.0f * (absC * inv_my) * (Ez + ((az_hi + Ez) * inv_my) * Ey) + 2.0e-5f * ((1.0f + __builtin_fabsf(ro.z)) + dev_z);
+    const float nx = __builtin_rintf(((ro.x + dx_lo) - del_x) + 0.5f), nz = __builtin_rintf(((ro.z + dz_lo) - del_z) + 0.5f);
+    uniform = uniform && nx == __builtin_rintf(((ro.x + dx_hi) + del_x) + 0.5f) && nz == __builtin_rintf(((ro.z + dz_hi) + del_z) + 0.5f);
+    code = (__float2int_rz(nx) ^ __float2int_rz(nz)) & 1;  // as shade_floor: saturating, wgsl:124-126
+    return uniform;
+}
+
+// Verdict bits of a tile (tile_verdict_v5): the tables clear it / all its samples are sky / all are in one checker cell, whose
+// bit is V5_TILE_CODE.  Settled here: CLEAR and (SKY or CELL).
+constexpr uint32_t V5_TILE_CLEAR = 1u, V5_TILE_SKY = 2u, V5_TILE_CELL = 4u, V5_TILE_CODE = 8u;
+// One lane, one tile (tile_x, tile_y) of eight consecutive frame rows from strip-local row 8 tile_y on (see the header above).
+// tables: the miss-test tables are staged; all_miss: no ray can hit anything (max_iter = 0).  off: the sixteen sample offsets.
+RM_DEV uint32_t tile_verdict_v5(const RmLaunch& L, const rm_uniforms& u, const V4& ro, const CullTables& T, const float2* aux, const float* off,
+                                bool tables, bool all_miss, uint32_t tile_x, uint32_t tile_y, float (&cone)[4]) {
+    const uint32_t row = rm_global_row(L, tile_y * 8u);
+    const float px[2] = {screen_x(tile_x * 8u, L.W), screen_x(tile_x * 8u + 7u, L.W)};
+    const float py[2] = {screen_y(row, L.H), screen_y(row + 7u, L.H)};
+    // samples 0 and 3 carry the extreme offsets, in an order the viewport's signs decide
+    const float ox[2] = {fmin_(off[0], off[24]), fmax_(off[0], off[24])}, oy[2] = {fmax_(off[1], off[7]), fmin_(off[1], off[7])};
+    float corner[4][3];
+    const bool cone_ok = rect_cone_v5(u.inv_proj, u.inv_view, ro, px, py, ox, oy, cone, corner);
+    bool clear = cone_ok && all_miss;
+    if (!all_miss && tables) clear = cone_misses_tables_v5(T, aux, cone, cone_ok);
+    float bx = 0.0f, by = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 2; a++) {
+        bx = fmax_(bx, __builtin_fabsf(px[a] + ox[a]));
+        by = fmax_(by, __builtin_fabsf(py[a] + oy[a]));
+    }
+    float mag;
+    int code = 0;
+    const bool sky = rect_sky_v5(u, ro, corner, bx, by, mag);
+    const bool cell = !sky && rect_cell_v5(u, ro, corner, bx, by, mag, code);
+    // (a NaN offset or position: v_min / v_max drop it, but it reaches the corners and fails the cone)
+    return (clear ? V5_TILE_CLEAR : 0u) | (sky ? V5_TILE_SKY : 0u) | (cell ? V5_TILE_CELL | (code ? V5_TILE_CODE : 0u) : 0u);
+}
+
 __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, uint32_t* cost, uint32_t n_tiles) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     uint32_t* s_veto = smem;
@@ -1408,7 +1557,9 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
     __shared__ float s_sxy[V5_PRE_TILES][128];          // per wave: pixel centres, sample codes and the list of the pixels that
     __shared__ uint8_t s_code[V5_PRE_TILES][64 * 16];   // need them, for the sample-parallel finish of a clear tile (below)
     __shared__ uint8_t s_list[V5_PRE_TILES][64];
-    if (tid == 0u) *s_veto = 0u;
+    __shared__ uint8_t s_verdict[V5_PRE_BLOCK];  // per tile of the block: tile_verdict_v5 if it settles the tile, else 0
+    __shared__ uint32_t s_claim;                 // next tile of the block to hand out
+    if (tid == 0u) { *s_veto = 0u; s_claim = 0u; }
     if (tid < 16u) sample_offset(u, tid >> 2, tid & 3u, s_off[2u * tid], s_off[2u * tid + 1u]);
     __syncthreads();
     if (tables)
@@ -1460,85 +1611,21 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
     const uint32_t pending = (uint32_t)__popcll(__ballot(!clear));
     if (lane == 0u) cost[(size_t)blockIdx.z * n_tiles + tile] = pending;  // 0 = finished here
     if (pending != 0u) return;
-    bool known = false;   // this pixel's sixteen samples provably share one colour code ...
-    int known_code = -1;  // ... -1 black (sky), 0 / 1 the checker bit
-    // Sky: a sample whose ray points away from the floor plane (t <= 0 in wgsl:120-121) is black, and the sum of sixteen
-    // zeros is zero.  pt_world.y - ro.y is affine in the sample's screen offset, so its sign over the 4 x 4 grid is decided at
-    // the four corner samples up to rounding; with the camera above the plane (-1.5 - ro.y < 0), "all four corners point up by
-    // more than the rounding can move any of the sixteen" means dy > 0, t < 0 for all of them.  The margin is 1e-5 of `mag`,
-    // the sum of the absolute values of every term the two mat-vecs add up for the y component (each of the ~30 roundings
-    // on the way is <= 6e-8 of a partial sum, hence of mag; interior and corner values each move by that, the affine
-    // argument needs twice it).  A tile whose 64 pixels are all such writes zeros and skips the loop below (about half of
-    // the clear tiles of the metric frame).  Anything non-finite fails the comparison and takes the loop.
-    {
-        float lo = __uint_as_float(0x7F800000u);
-#pragma unroll
-        for (uint32_t c = 0; c < 4u; c++) {
-            lo = corner[c][1] < lo ? corner[c][1] : lo;
-            if (!(corner[c][1] == corner[c][1])) lo = corner[c][1];  // a NaN sticks and makes the test below false
-        }
-        const float bx = __builtin_fabsf(sx) + __builtin_fabsf(s_off[0]), by = __builtin_fabsf(sy) + __builtin_fabsf(s_off[1]);  // sample (0, 0) has the largest offsets
-        float mag = __builtin_fabsf(ro.y);
-#pragma unroll
-        for (int k = 0; k < 4; k++)  // |inv_view row y| . (|inv_proj| (|x|, |y|, 1, 1))
-            mag += __builtin_fabsf(u.inv_view[1 + 4 * k]) * (((__builtin_fabsf(u.inv_proj[k]) * bx + __builtin_fabsf(u.inv_proj[k + 4]) * by) +
-                                                              __builtin_fabsf(u.inv_proj[k + 8])) + __builtin_fabsf(u.inv_proj[k + 12]));
-        const bool sky = (-1.5f - ro.y) < 0.0f && lo > 1.0e-5f * mag;
-        if (__ballot(!sky) == 0ull) {
-            if (tx < L.W && ty < L.rows) store_pixel(L, blockIdx.z, (size_t)ty * L.W + tx, 0.0f, 0.0f, 0.0f);  // 0 / 16 = 0 (wgsl:73-75)
-            return;
-        }
-        // Floor, one checker cell per pixel.  With every sample ray pointing down (t > 0) the floor point of a sample is
-        // fx = o.x + C ex / ey, C = -1.5 - o.y (the normalisation cancels), a linear-fractional function of the sample's screen
-        // position: monotone along every segment where ey keeps its sign, so over the pixel's rectangle of samples it stays between
-        // its values at the four corner samples.  If the interval those span -- widened by everything rounding can do to a
-        // sample's own fx: the mat-vec errors E (4e-6 of `mag`, per component) pushed through |C| / |ey| (E_x + |ex| E_y / |ey|),
-        // once for the corners and once for the sample, the approximate reciprocal used here and the five roundings of the
-        // sample's own chain -- rounds to ONE integer after the +0.5 of wgsl:124 (rint is monotone), and the same holds for z,
-        // all sixteen samples carry the same checker bit, and the pixel is the sum of sixteen equal gamma values: a constant
-        // per bit, accumulated below exactly as the loop would.  A tile whose 64 pixels are each sky or such a pixel skips the
-        // loop: what remains for it are the pixels a cell edge crosses, the horizon and the far floor.
-        const float Cf = -1.5f - ro.y;  // as shade_floor computes it
-        float ex[4], eyc[4], ez[4], ey_hi = -__uint_as_float(0x7F800000u), ax_hi = 0.0f, az_hi = 0.0f;
-#pragma unroll
-        for (uint32_t c = 0; c < 4u; c++) {
-            ex[c] = corner[c][0]; eyc[c] = corner[c][1]; ez[c] = corner[c][2];
-            ey_hi = eyc[c] > ey_hi ? eyc[c] : ey_hi;
-            if (!(eyc[c] == eyc[c])) ey_hi = eyc[c];
-            ax_hi = fmax_(ax_hi, __builtin_fabsf(ex[c]));
-            az_hi = fmax_(az_hi, __builtin_fabsf(ez[c]));
-        }
-        float mag_x = __builtin_fabsf(ro.x), mag_z = __builtin_fabsf(ro.z);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const float pvk = ((__builtin_fabsf(u.inv_proj[k]) * bx + __builtin_fabsf(u.inv_proj[k + 4]) * by) + __builtin_fabsf(u.inv_proj[k + 8])) +
-                              __builtin_fabsf(u.inv_proj[k + 12]);
-            mag_x += __builtin_fabsf(u.inv_view[0 + 4 * k]) * pvk;
-            mag_z += __builtin_fabsf(u.inv_view[2 + 4 * k]) * pvk;
-        }
-        const float Ey = 4.0e-6f * mag, Ex = 4.0e-6f * mag_x, Ez = 4.0e-6f * mag_z;
-        const float my = -ey_hi - 2.0f * Ey;  // every sample's |ey| is at least this
-        bool uniform = Cf < -1.0e-20f && my > 0.0f && ey_hi < -4.0f * Ey;
-        const float inv_my = __builtin_amdgcn_rcpf(my) * 1.00001f, absC = -Cf;
-        float gx_lo = __uint_as_float(0x7F800000u), gx_hi = -gx_lo, gz_lo = gx_lo, gz_hi = -gx_lo;
-#pragma unroll
-        for (uint32_t c = 0; c < 4u; c++) {
-            const float r = __builtin_amdgcn_rcpf(eyc[c]);
-            const float gx = ex[c] * r, gz = ez[c] * r;
-            gx_lo = fmin_(gx_lo, gx); gx_hi = fmax_(gx_hi, gx);
-            gz_lo = fmin_(gz_lo, gz); gz_hi = fmax_(gz_hi, gz);
-            uniform = uniform && gx == gx && gz == gz;  // (v_min / v_max drop a NaN)
-        }
-        // C < 0: the interval of fx - o.x is [C gx_hi, C gx_lo]
-        const float dx_lo = Cf * gx_hi, dx_hi = Cf * gx_lo, dz_lo = Cf * gz_hi, dz_hi = Cf * gz_lo;
-        const float dev_x = fmax_(__builtin_fabsf(dx_lo), __builtin_fabsf(dx_hi)), dev_z = fmax_(__builtin_fabsf(dz_lo), __builtin_fabsf(dz_hi));
-        const float del_x = 4.0f * (absC * inv_my) * (Ex + ((ax_hi + Ex) * inv_my) * Ey) + 2.0e-5f * ((1.0f + __builtin_fabsf(ro.x)) + dev_x);
-        const float del_z = 4.0f * (absC * inv_my) * (Ez + ((az_hi + Ez) * inv_my) * Ey) + 2.0e-5f * ((1.0f + __builtin_fabsf(ro.z)) + dev_z);
-        const float nx = __builtin_rintf(((ro.x + dx_lo) - del_x) + 0.5f), nz = __builtin_rintf(((ro.z + dz_lo) - del_z) + 0.5f);
-        uniform = uniform && nx == __builtin_rintf(((ro.x + dx_hi) + del_x) + 0.5f) && nz == __builtin_rintf(((ro.z + dz_hi) + del_z) + 0.5f);
-        known = sky || uniform;
-        known_code = sky ? -1 : ((__float2int_rz(nx) ^ __float2int_rz(nz)) & 1);  // as shade_floor: saturating, wgsl:124-126
+    // this pixel's sixteen samples provably share one colour code (rect_sky_v5 / rect_cell_v5 on the pixel's 4 x 4 grid):
+    // -1 black (sky), 0 / 1 the checker bit.  A tile whose 64 pixels are all sky writes zeros and skips the loop below; one whose
+    // pixels are each sky or one cell skips the sample rays: what remains for it are the pixels a cell edge crosses, the horizon
+    // and the far floor.
+    const float bx = __builtin_fabsf(sx) + __builtin_fabsf(s_off[0]), by = __builtin_fabsf(sy) + __builtin_fabsf(s_off[1]);  // sample (0, 0) has the largest offsets
+    float mag;
+    const bool sky = rect_sky_v5(u, ro, corner, bx, by, mag);
+    if (__ballot(!sky) == 0ull) {
+        if (tx < L.W && ty < L.rows) store_pixel(L, blockIdx.z, (size_t)ty * L.W + tx, 0.0f, 0.0f, 0.0f);  // 0 / 16 = 0 (wgsl:73-75)
+        return;
     }
+    int cell_code;
+    const bool uniform = rect_cell_v5(u, ro, corner, bx, by, mag, cell_code);
+    const bool known = sky || uniform;
+    const int known_code = sky ? -1 : cell_code;
     // The sample loop.  Everything that does not depend on the pixel is taken out of it: the sample offsets (two divisions each)
     // come from the table, the matrices sit in vector registers, and the gamma-corrected colour of a sample is one of three
     // values -- black, or the checker colour for bit 0 / 1 (wgsl:127) -- whose square roots are taken once, by the same
@@ -1600,10 +1687,44 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
         store_pixel(L, blockIdx.z, (size_t)ty * L.W + tx, tr / 16.0f, tg / 16.0f, tb / 16.0f);  // wgsl:73-75
     }
   };
-    const uint32_t first_tile = (blockIdx.x * V5_PRE_TILES + wave) * V5_PRE_TILES_PER_WAVE;
-    for (uint32_t t = 0; t < V5_PRE_TILES_PER_WAVE && first_tile + t < n_tiles; t++) {
-        do_tile(first_tile + t);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the wave's LDS scratch is reused by its next tile
+    // Tile verdicts, lane = tile; without tables nothing is known unless no ray can hit (do_tile decides the same way), and
+    // a tile's rows must be consecutive frame rows
+    const uint32_t first_tile = blockIdx.x * V5_PRE_BLOCK;
+    if (tid < V5_PRE_BLOCK) {
+        uint32_t v = 0u;
+        if ((tables || L.max_iter == 0u) && L.strip_rows % 8u == 0u) {
+            const uint32_t tile = first_tile + tid < n_tiles ? first_tile + tid : n_tiles - 1u;
+            float cone[4];
+            v = tile_verdict_v5(L, u, ro, cullt, t_aux, s_off, tables, L.max_iter == 0u, tile % tiles_x, tile / tiles_x, cone);
+            if (!(v & V5_TILE_CLEAR) || !(v & (V5_TILE_SKY | V5_TILE_CELL))) v = 0u;
+        }
+        s_verdict[tid] = (uint8_t)v;
+    }
+    __syncthreads();
+    for (;;) {
+        uint32_t t = 0u;
+        if (lane == 0u) t = atomicAdd(&s_claim, 1u);
+        t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+        if (t >= V5_PRE_BLOCK || first_tile + t >= n_tiles) break;
+        const uint32_t tile = first_tile + t, v = s_verdict[t];
+        if (v == 0u) {
+            do_tile(tile);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the wave's LDS scratch is reused by its next tile
+            continue;
+        }
+        // settled: one constant for the tile's 64 pixels, added up as do_tile's sample loop adds a pixel's sixteen equal values
+        float tr = 0.0f, tb = 0.0f;
+        if (v & V5_TILE_CELL) {
+            const float g = 0.2f * (float)((v & V5_TILE_CODE) ? 1 : 0);
+            const float rg = __builtin_sqrtf(0.1f + g), b = __builtin_sqrtf(0.2f + g);
+            for (uint32_t s = 0; s < 16u; s++) {
+                tr += rg;
+                tb += b;
+            }
+        }
+        const uint32_t tx = (tile % tiles_x) * 8u + (lane & 7u), ty = (tile / tiles_x) * 8u + (lane >> 3);
+        if (lane == 0u) cost[(size_t)blockIdx.z * n_tiles + tile] = 0u;
+        if (tx < L.W && ty < L.rows) store_pixel(L, blockIdx.z, (size_t)ty * L.W + tx, tr / 16.0f, tr / 16.0f, tb / 16.0f);  // wgsl:73-75
     }
 }
 #endif
@@ -1809,6 +1930,42 @@ __global__ __launch_bounds__(64) void rm_selftest_cull_pixels_kernel(RmLaunch L,
         float* o = out + 8u * (size_t)i;
         o[0] = cone[0]; o[1] = cone[1]; o[2] = cone[2]; o[3] = cone[3]; o[4] = acc;
         o[5] = __uint_as_float((clear ? 1u : 0u) | ((tables && veto == 0u) ? 2u : 0u) | (walk ? 4u : 0u) | (by_bounds ? 8u : 0u));
+        o[6] = 0.0f; o[7] = 0.0f;
+    }
+}
+// Tiles xy[2 i] = (tile_x, tile_y) of a W x H frame (L.W, L.H) under the context's uniforms, as the pre-pass classifies them, lane
+// = tile: out[8 i + 0..3] the cone (c, rho) of the tile's 32 x 32 sample directions (rho = NaN: not usable), [4] the checker bit
+// of a one-cell tile (else 0), [5] flags as an integer: bit 0 the tables clear the tile, bit 1 all its samples are sky, bit 2 all
+// are in one checker cell, bit 3 the tables were usable; [6], [7] zero.
+__global__ __launch_bounds__(64) void rm_selftest_cull_tiles_kernel(RmLaunch L, const uint32_t* xy, uint32_t n, float* out) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    uint32_t* s_veto = smem;
+    float4* t_cone = reinterpret_cast<float4*>(smem + 4u);
+    float4* t_slab = t_cone + L.n_cone;
+    float2* t_aux = reinterpret_cast<float2*>(t_slab + 3u * L.n_slab);
+    __shared__ float s_off[32];
+    const CullTables cullt{t_cone, t_slab, s_veto, L.n_cone, L.n_slab};
+    const uint32_t tid = threadIdx.x;
+    const rm_uniforms u = L.u;
+    const V4 ro = matvec(u.inv_view, 0.0f, 0.0f, 0.0f, 1.0f);
+    const bool tables = (L.flags & 1u) != 0u;
+    if (tid == 0u) *s_veto = 0u;
+    if (tid < 16u) sample_offset(u, tid >> 2, tid & 3u, s_off[2u * tid], s_off[2u * tid + 1u]);
+    __syncthreads();
+    if (tables)
+        for (uint32_t k = tid; k < L.n_rec; k += 64u) cull_build_v5(L.prog[k], ro, L.min_dist, L.smooth_slack, t_cone, t_slab, s_veto, L.bounds);
+    __syncthreads();
+    if (tables) pixel_aux_build_v5(t_cone, t_slab, L.n_cone, L.n_slab, t_aux, tid, 64u);
+    __syncthreads();
+    const uint32_t i = blockIdx.x * 64u + tid, j = i < n ? i : n - 1u;
+    float cone[4];
+    const uint32_t v = tile_verdict_v5(L, u, ro, cullt, t_aux, s_off, tables, L.max_iter == 0u, xy[2u * j], xy[2u * j + 1u], cone);
+    if (i < n) {
+        float* o = out + 8u * (size_t)i;
+        o[0] = cone[0]; o[1] = cone[1]; o[2] = cone[2]; o[3] = cone[3];
+        o[4] = (v & V5_TILE_CODE) ? 1.0f : 0.0f;
+        o[5] = __uint_as_float(((v & V5_TILE_CLEAR) ? 1u : 0u) | ((v & V5_TILE_SKY) ? 2u : 0u) | ((v & V5_TILE_CELL) ? 4u : 0u) |
+                               ((tables && *s_veto == 0u) ? 8u : 0u));
         o[6] = 0.0f; o[7] = 0.0f;
     }
 }
