@@ -1300,7 +1300,7 @@ void rm_render_v5_lean(RmLaunch L, V5Work work, uint32_t n_tiles, uint32_t refil
 // that fails: a point P of any of the pixel's rays inside the (margin-inflated) box has |P| <= D =
 // |m| + radius, and the centre ray passes within D rho of it, so if the centre ray misses the box
 // inflated by a further D rho, every ray of the pixel misses the box.  rho carries 0.1 % + 2e-6 of
-// slack for the rounding of e_i and c.
+// slack for the rounding of e_i and c, and the frame's cone_noise_v5 for that of the mat-vecs (below).
 //
 // Per tile, the same three proofs (clear of the tables, sky, one checker cell) run on the rectangle of
 // the tile's 32 x 32 sample positions; none of them needs the rectangle to be one pixel's grid.  What
@@ -1321,6 +1321,13 @@ void rm_render_v5_lean(RmLaunch L, V5Work work, uint32_t n_tiles, uint32_t refil
 // and the relative 0.1 % of rho only grows with the rectangle.  So the constants stand as they are,
 // and the bounds bx, by of |x|, |y| that `mag` is built from are taken over the tile's rectangle.
 // At rho >= 0.05 (frames of a few dozen pixels) a tile has no usable cone and nothing is settled per tile.
+// The 2e-6 of rho covers the normalisations, NOT the mat-vecs: their error is absolute in the un-normalised direction, up to
+// 1e-6 of `mag` per component (13 roundings of 2^-24 on the way from a position to pt_world - ro, each of a partial sum that
+// `mag` bounds), and for the reference camera near the origin that is a few 1e-6 -- but `mag` grows with the camera's distance
+// from the origin and with entries of the matrices that cancel (1e5 and -1e5 in one row of inv_proj quantise pt_view to 2^-7,
+// several sample pitches: the samples between the corners then leave the corners' cone by 3e-3).  cone_noise_v5 bounds that error
+// once per frame and rect_cone_v5 adds it to rho, twice (the corners' own and the sample's) over the shortest corner: a block
+// whose noise is not small against a rectangle's directions gets no cone.
 //
 // A tile is settled per tile iff the tables clear its cone (the lower-bound walk of a blending program
 // stays per pixel) and its samples are all sky or all in one cell.  It gets the constant the per-pixel
@@ -1345,15 +1352,17 @@ static_assert(V5_PRE_BLOCK >= 1u && V5_PRE_BLOCK <= 64u, "one wave classifies th
 // and a sample offset) are its extreme positions; corner c is (a, b) = (c & 1, c >> 1).  cone_out: (unit centre direction, rho) of
 // the directions through the rectangle; rho = NaN when the cone is not usable.  corner[c]: pt_world.xyz - ro.xyz of corner c,
 // as gen_ray computes it before its normalisation; the caller's sky / floor tests reuse them.  m_proj / m_view: the matrices (in
-// vector registers).  Returns whether the cone is usable.
+// vector registers).  noise: cone_noise_v5 of the frame.  Returns whether the cone is usable.
 RM_DEV bool rect_cone_v5(const float* m_proj, const float* m_view, const V4& ro, const float (&px)[2], const float (&py)[2], const float (&ox)[2],
-                         const float (&oy)[2], float (&cone_out)[4], float (&corner)[4][3]) {
-    float cx = 0.0f, cy = 0.0f, cz = 0.0f, ex[4], ey[4], ez[4];
+                         const float (&oy)[2], float noise, float (&cone_out)[4], float (&corner)[4][3]) {
+    float cx = 0.0f, cy = 0.0f, cz = 0.0f, ex[4], ey[4], ez[4], inv_hi = 0.0f;
 #pragma unroll
     for (uint32_t c = 0; c < 4u; c++) {
-        gen_ray_unnormalized_at(m_proj, m_view, ro, px[c & 1u], py[c >> 1], ox[c & 1u], oy[c >> 1], ex[c], ey[c], ez[c]);  // unit_dir normalises
+        gen_ray_unnormalized_at(m_proj, m_view, ro, px[c & 1u], py[c >> 1], ox[c & 1u], oy[c >> 1], ex[c], ey[c], ez[c]);
         corner[c][0] = ex[c]; corner[c][1] = ey[c]; corner[c][2] = ez[c];
-        unit_dir(ex[c], ey[c], ez[c]);
+        const float inv = __builtin_amdgcn_rsqf(__builtin_fmaf(ez[c], ez[c], __builtin_fmaf(ey[c], ey[c], ex[c] * ex[c])));  // (as unit_dir)
+        ex[c] *= inv; ey[c] *= inv; ez[c] *= inv;
+        inv_hi = fmax_(inv_hi, inv);  // 1 / the shortest corner; every sample is at least 0.998 of that long (rho < 0.05)
         cx += ex[c]; cy += ey[c]; cz += ez[c];
     }
     unit_dir(cx, cy, cz);
@@ -1363,7 +1372,7 @@ RM_DEV bool rect_cone_v5(const float* m_proj, const float* m_view, const V4& ro,
         const float ax = ex[c] - cx, ay = ey[c] - cy, az = ez[c] - cz;
         rho2 = fmax_(rho2, __builtin_fmaf(az, az, __builtin_fmaf(ay, ay, ax * ax)));
     }
-    const float rho = __builtin_sqrtf(rho2) * 1.001f + 2.0e-6f;
+    const float rho = __builtin_fmaf(2.2f * noise, inv_hi, __builtin_sqrtf(rho2) * 1.001f + 2.0e-6f);
     // NaN anywhere above (zero / non-finite directions) makes this false; v_max drops a NaN operand, so
     // the corners are checked one by one as well
     bool cone_ok = rho < 0.05f;
@@ -1372,6 +1381,20 @@ RM_DEV bool rect_cone_v5(const float* m_proj, const float* m_view, const V4& ro,
     cone_out[0] = cx; cone_out[1] = cy; cone_out[2] = cz;
     cone_out[3] = cone_ok ? rho : __uint_as_float(0x7FC00000u);
     return cone_ok;
+}
+// How far rounding can move a sample's pt_world.xyz - ro.xyz from the affine image of its screen position (Euclidean; the same
+// for every sample of a W x H frame): 1e-6 of the sum over the three components of |ro| + |inv_view row| . (|inv_proj| (|x|, |y|, 1,
+// 1)), with |x|, |y| bounded for every position a tile's rectangle can have (its far corner may lie 7 pixels outside the frame).
+RM_DEV float cone_noise_v5(const rm_uniforms& u, const V4& ro, uint32_t W, uint32_t H) {
+    const float bx = (1.0f + 16.0f / (float)W) + 0.75f / __builtin_fabsf(u.viewport_extent[0]);
+    const float by = (1.0f + 16.0f / (float)H) + 0.75f / __builtin_fabsf(u.viewport_extent[1]);
+    float mag = (__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z);
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+        mag += ((__builtin_fabsf(u.inv_view[4 * k]) + __builtin_fabsf(u.inv_view[1 + 4 * k])) + __builtin_fabsf(u.inv_view[2 + 4 * k])) *
+               (((__builtin_fabsf(u.inv_proj[k]) * bx + __builtin_fabsf(u.inv_proj[k + 4]) * by) + __builtin_fabsf(u.inv_proj[k + 8])) +
+                __builtin_fabsf(u.inv_proj[k + 12]));
+    return 1.0e-6f * mag;  // (anything non-finite ends up in rho and fails the cone)
 }
 // Whether the tables clear every direction of a cone of rect_cone_v5 (cone_ok: what it returned).
 RM_DEV bool cone_misses_tables_v5(const CullTables& T, const float2* aux, const float (&cone)[4], bool cone_ok) {
@@ -1408,9 +1431,9 @@ RM_DEV bool cone_misses_tables_v5(const CullTables& T, const float2* aux, const 
 // One pixel: the rectangle is its 4 x 4 grid of samples, spanned by samples (0,0), (3,0), (0,3), (3,3) (table entry 4 i + j of
 // off, the table of the sixteen sample offsets).
 RM_DEV bool pixel_misses_scene_v5(const CullTables& T, const float2* aux, const float* m_proj, const float* m_view, const float* off,
-                                  const V4& ro, float sx, float sy, float (&cone_out)[4], float (&corner)[4][3]) {
+                                  const V4& ro, float sx, float sy, float noise, float (&cone_out)[4], float (&corner)[4][3]) {
     const float px[2] = {sx, sx}, py[2] = {sy, sy}, ox[2] = {off[0], off[24]}, oy[2] = {off[1], off[7]};
-    const bool cone_ok = rect_cone_v5(m_proj, m_view, ro, px, py, ox, oy, cone_out, corner);
+    const bool cone_ok = rect_cone_v5(m_proj, m_view, ro, px, py, ox, oy, noise, cone_out, corner);
     return cone_misses_tables_v5(T, aux, cone_out, cone_ok);
 }
 
@@ -1524,7 +1547,7 @@ RM_DEV uint32_t tile_verdict_v5(const RmLaunch& L, const rm_uniforms& u, const V
     // samples 0 and 3 carry the extreme offsets, in an order the viewport's signs decide
     const float ox[2] = {fmin_(off[0], off[24]), fmax_(off[0], off[24])}, oy[2] = {fmax_(off[1], off[7]), fmin_(off[1], off[7])};
     float corner[4][3];
-    const bool cone_ok = rect_cone_v5(u.inv_proj, u.inv_view, ro, px, py, ox, oy, cone, corner);
+    const bool cone_ok = rect_cone_v5(u.inv_proj, u.inv_view, ro, px, py, ox, oy, cone_noise_v5(u, ro, L.W, L.H), cone, corner);
     bool clear = cone_ok && all_miss;
     if (!all_miss && tables) clear = cone_misses_tables_v5(T, aux, cone, cone_ok);
     float bx = 0.0f, by = 0.0f;
@@ -1538,6 +1561,13 @@ RM_DEV uint32_t tile_verdict_v5(const RmLaunch& L, const rm_uniforms& u, const V
     const bool sky = rect_sky_v5(u, ro, corner, bx, by, mag);
     const bool cell = !sky && rect_cell_v5(u, ro, corner, bx, by, mag, code);
     // (a NaN offset or position: v_min / v_max drop it, but it reaches the corners and fails the cone)
+    // A block that maps the tile's 8 x 8 pixels onto ONE direction (a singular inv_proj: all zeros sends every sample to -ro) is no
+    // camera: the four corners coincide, the rules above would hold trivially, and nothing is settled per tile -- the per-pixel
+    // path draws such a frame.
+    bool spread = false;
+#pragma unroll
+    for (uint32_t c = 1; c < 4u; c++) spread = spread || corner[c][0] != corner[0][0] || corner[c][1] != corner[0][1] || corner[c][2] != corner[0][2];
+    if (!spread) return 0u;
     return (clear ? V5_TILE_CLEAR : 0u) | (sky ? V5_TILE_SKY : 0u) | (cell ? V5_TILE_CELL | (code ? V5_TILE_CODE : 0u) : 0u);
 }
 
@@ -1569,6 +1599,7 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
     if (tables) pixel_aux_build_v5(t_cone, t_slab, L.n_cone, L.n_slab, t_aux, tid, 64u * V5_PRE_TILES);
     __syncthreads();
     const uint32_t tiles_x = (L.W + 7u) / 8u;
+    const float cone_noise = cone_noise_v5(u, ro, L.W, L.H);
   auto do_tile = [&](uint32_t tile) {  // (whole wave; no barrier inside)
     const uint32_t tile_x = tile % tiles_x, tile_y = tile / tiles_x;
     const uint32_t tx = tile_x * 8u + (lane & 7u), ty = tile_y * 8u + (lane >> 3);
@@ -1593,7 +1624,7 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
         }
     } else {
         float cone[4];
-        clear = pixel_misses_scene_v5(cullt, t_aux, mp, mv, s_off, ro, sx, sy, cone, corner);
+        clear = pixel_misses_scene_v5(cullt, t_aux, mp, mv, s_off, ro, sx, sy, cone_noise, cone, corner);
         // a program that blends: the pixels the inflated bounds could not clear get the program run on lower bounds of its
         // leaves over the pixel's cone ("Miss test on lower bounds"; the march kernel repeats it per ray for what is left)
         const float bound_scale = (L.scene_scale + L.smooth_slack) + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));
@@ -1906,12 +1937,12 @@ __global__ __launch_bounds__(64) void rm_selftest_cull_pixels_kernel(RmLaunch L,
     float mp[16], mv[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) { mp[k] = u.inv_proj[k]; mv[k] = u.inv_view[k]; }
-    const float nan = __uint_as_float(0x7FC00000u);
+    const float nan = __uint_as_float(0x7FC00000u), cone_noise = cone_noise_v5(u, ro, L.W, L.H);
     float cone[4] = {nan, nan, nan, nan}, corner[4][3], acc = nan;
     bool clear = false, walk = false, by_bounds = false;
     const uint32_t veto = *s_veto;
     if (tables) {
-        clear = pixel_misses_scene_v5(cullt, t_aux, mp, mv, s_off, ro, sx, sy, cone, corner);
+        clear = pixel_misses_scene_v5(cullt, t_aux, mp, mv, s_off, ro, sx, sy, cone_noise, cone, corner);
         const float bound_scale = (L.scene_scale + L.smooth_slack) + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));  // (as rm_tile_pre_v5)
         walk = (L.flags & 32u) && (veto & 1u) == 0u && bound_scale < 1.0e12f && cone[3] == cone[3];
         if (__ballot(walk) != 0ull) {

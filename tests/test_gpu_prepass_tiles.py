@@ -10,10 +10,9 @@ import hashlib
 import numpy as np
 import pytest
 
-import cull_ref as R
 import gbuffer_ref
 import scenes
-from oracle import rm_oracle_np as onp
+from prepass_ref import CELL, CLEAR, SKY, check_tiles, floor_codes, pick_tiles, program as _program, udict, with_frame_corners
 from ray_marching_amd import _ffi, renderer, shard
 from test_cull_tables_cpu import decode
 from test_gpu_cull_bounds import MIN_DISTS, _ptr, set_case, table_zones
@@ -22,7 +21,6 @@ from test_gpu_parity import assert_same, orbit_frame_uniforms, setup
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-CLEAR, SKY, CELL, USABLE = 1, 2, 4, 8
 
 
 @pytest.fixture(scope="module")
@@ -38,75 +36,6 @@ def probe_tiles(res, W, H, txy):
     out = np.zeros((len(txy), 8), dtype=F)
     res._check(res._L.rm_selftest_cull_tiles(res._h, W, H, _ptr(txy), len(txy), _ptr(out)))
     return out
-
-
-def udict(u):
-    return {"viewport_extent": list(u.viewport_extent), "inv_proj": list(u.inv_proj), "inv_view": list(u.inv_view)}
-
-
-def floor_codes(ro, d):
-    """The colour code of a miss ray as the oracle's ray_march decides it (rm_oracle_np.py, the miss branch): -1 black, else
-    the checker bit.  d: (dx, dy, dz) binary32 arrays."""
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        fd = (F(-1.5) - ro[1]) / d[1]
-        on = fd > 0
-        fx, fz = ro[0] + d[0] * fd, ro[2] + d[2] * fd
-        ix, iz = onp.f2i(np.rint(fx + F(0.5))), onp.f2i(np.rint(fz + F(0.5)))
-    return np.where(on, (ix ^ iz) & 1, -1)
-
-
-def tile_samples(ud, W, H, txy):
-    """Every sample ray of the tiles' pixels inside the frame: ro (3,), directions (n, 3) binary32, tile index (n,)."""
-    lane = np.arange(64)
-    px = (txy[:, 0, None] * 8 + (lane & 7)[None, :]).ravel()
-    py = (txy[:, 1, None] * 8 + (lane >> 3)[None, :]).ravel()
-    owner = np.repeat(np.arange(len(txy)), 64)
-    keep = (px < W) & (py < H)
-    px, py, owner = px[keep].astype(np.uint32), py[keep].astype(np.uint32), owner[keep]
-    dirs, ro = [], None
-    for s in range(16):
-        ro, d = gbuffer_ref.camera_rays(px, py, s, ud, W, H)
-        dirs.append(np.stack(d, axis=1))
-    return np.array(ro, dtype=F)[:3], np.concatenate(dirs), np.tile(owner, 16)
-
-
-def pick_tiles(ud, W, H, zones, rng, n_each=70, n_random=90):
-    """Tiles on silhouettes, on the horizon and on cell edges -- the centre rays of their four corner pixels disagree about a
-    zone, about sky / floor or about the checker bit -- and random ones."""
-    tiles_x, tiles_y = (W + 7) // 8, (H + 7) // 8
-    tx, ty = np.meshgrid(np.arange(tiles_x), np.arange(tiles_y))
-    tx, ty = tx.ravel(), ty.ravel()
-    meets, codes = [], []
-    for cx, cy in ((0, 0), (7, 0), (0, 7), (7, 7)):
-        px, py = np.minimum(tx * 8 + cx, W - 1).astype(np.uint32), np.minimum(ty * 8 + cy, H - 1).astype(np.uint32)
-        ro, d = gbuffer_ref.camera_rays(px, py, _ffi.RM_SAMPLE_CENTER, ud, W, H)
-        ro = np.array(ro, dtype=F)[:3]
-        d64 = np.stack(d, axis=1).astype(np.float64)
-        m = np.zeros(len(px), dtype=bool)
-        for z in zones:
-            m |= R.meets_zone(z, ro.astype(np.float64), d64)
-        meets.append(m)
-        codes.append(floor_codes(ro, d))
-    meets, codes = np.array(meets), np.array(codes)
-    silhouette = np.flatnonzero(meets.any(axis=0) != meets.all(axis=0))
-    sky = codes < 0
-    horizon = np.flatnonzero(sky.any(axis=0) != sky.all(axis=0))
-    edge = np.flatnonzero(~sky.any(axis=0) & (codes.min(axis=0) != codes.max(axis=0)))
-    parts = [rng.permutation(k)[:n_each] for k in (silhouette, horizon, edge)] + [rng.integers(0, len(tx), n_random)]
-    pick = np.unique(np.concatenate(parts))
-    return np.stack([tx[pick], ty[pick]], axis=1)
-
-
-def _plane_program(oracle):
-    t = scenes._Tab()
-    ground = t.plane((0.0, 2.0, 0.0), 2.4)
-    return oracle.serialize(t.nodes, t.op(scenes.UNION, t.op(scenes.UNION, t.sphere((-0.7, 0.0, 0.0), 0.8), t.box((0.9, -0.4, 0.2), (0.5, 0.8, 0.5))), ground))
-
-
-def _program(oracle, name):
-    if name == "plane":
-        return _plane_program(oracle)
-    return oracle.serialize(*{**scenes.SCENES, **scenes.EXT_SCENES}[name]())
 
 
 def _camera(oracle, name, W, H):
@@ -126,57 +55,36 @@ CASES = [("g32", "still", 1920, 1080, 3), ("g32", "orbit100", 1920, 1080, 2), ("
 _RESULTS = {}
 
 
-def run_case(res, oracle, case):
-    """One probe call and its assertions; returns how often each flag was seen set and unset."""
-    if case in _RESULTS:
-        return _RESULTS[case]
-    prog, cam, W, H, k = case
-    min_dist = MIN_DISTS[k]
-    cc, w = _program(oracle, prog)
+def probe_case(res, oracle, name, prog, u, W, H, min_dist, seed, frame_corners=False, cone_expected=None, n_each=70, n_random=90):
+    """One probe call under the prepared uniform block u and its assertions (prepass_ref.check_tiles); returns how often each flag
+    was seen set and unset.  prog: a scene's name or (cmd_count, words)."""
+    cc, w = _program(oracle, prog) if isinstance(prog, str) else prog
     w = np.asarray(w, dtype=np.uint32)
     d = decode(cc, w)
     set_case(res, cc, w, min_dist)
-    u = _camera(oracle, cam, W, H)
     res.set_uniforms(_ffi.Uniforms.from_buffer_copy(bytes(u)))
     ud = udict(u)
-    ro0, _ = gbuffer_ref.camera_rays(np.zeros(1, np.uint32), np.zeros(1, np.uint32), 0, ud, W, H)
-    ro64 = np.array(ro0, dtype=F)[:3].astype(np.float64)
-    zones = table_zones(d, ro64, min_dist)
-    txy = pick_tiles(ud, W, H, zones, np.random.default_rng(61000 + CASES.index(case)))
+    ro64 = np.array([ud["inv_view"][12 + k] for k in range(3)], dtype=F).astype(np.float64)
+    vetoed = bool(d["cull_veto"])
+    zones = [] if vetoed else table_zones(d, ro64, min_dist)
+    txy = pick_tiles(ud, W, H, zones, np.random.default_rng(seed), n_each=n_each, n_random=n_random)
+    if frame_corners:
+        txy = with_frame_corners(txy, W, H)
     out = probe_tiles(res, W, H, txy)
-    flags = out[:, 5].view(np.uint32)
-    clear, sky, cell, usable = (flags & CLEAR) != 0, (flags & SKY) != 0, (flags & CELL) != 0, (flags & USABLE) != 0
-    code = out[:, 4].astype(np.int64)
-    c, rho = out[:, :3].astype(np.float64), out[:, 3].astype(np.float64)
-    ro, e, owner = tile_samples(ud, W, H, txy)
-    assert np.all(ro == np.array(ro0, dtype=F)[:3])
-    name = "%s / %s / %dx%d / min_dist %g" % (prog, cam, W, H, min_dist)
-    assert not np.any(clear & ~usable), name
-    assert not np.any(clear & np.isnan(rho)), name
-    assert not np.any(sky & cell), name
-    if W < 100:
-        assert np.isnan(rho).all() and not clear.any(), "%s: a tile of a tiny frame has no usable cone" % name
-    else:
-        assert not np.isnan(rho).any(), name
-        gap = rho[owner] - np.linalg.norm(e.astype(np.float64) - c[owner], axis=1)
-        assert gap.min() >= 0.0, "%s: a sample direction lies %.3g outside its tile's cone" % (name, -gap.min())
-    sel = clear[owner]
-    if sel.any():
-        for z in zones:
-            hit = R.meets_zone(z, ro64, e[sel].astype(np.float64))
-            assert not hit.any(), "%s: tile %s is reported clear but one of its samples meets the zone %s" % (
-                name, txy[owner[sel][np.argmax(hit)]].tolist(), z)
-    codes = floor_codes(ro, (e[:, 0], e[:, 1], e[:, 2]))
-    bad = sky[owner] & (codes != -1)
-    assert not bad.any(), "%s: tile %s is reported sky but a sample has floor code %d" % (name, txy[owner[np.argmax(bad)]].tolist(), codes[np.argmax(bad)])
-    bad = cell[owner] & (codes != code[owner])
-    assert not bad.any(), "%s: tile %s is reported cell %d but a sample has floor code %d" % (
-        name, txy[owner[np.argmax(bad)]].tolist(), code[owner[np.argmax(bad)]], codes[np.argmax(bad)])
-    stats = {"clear": (int(clear.sum()), int((~clear).sum())), "sky": (int(sky.sum()), int((~sky).sum())), "cell": (int(cell.sum()), int((~cell).sum())),
-             "code": (int((cell & (code == 1)).sum()), int((cell & (code == 0)).sum())), "settled": int((clear & (sky | cell)).sum()), "tiles": len(txy)}
+    stats = check_tiles(name, ud, W, H, txy, out, zones, check_zones=not vetoed, cone_expected=cone_expected)
     print("%s: %s" % (name, stats))
-    _RESULTS[case] = stats
     return stats
+
+
+def run_case(res, oracle, case):
+    """One of CASES; cached."""
+    if case in _RESULTS:
+        return _RESULTS[case]
+    prog, cam, W, H, k = case
+    name = "%s / %s / %dx%d / min_dist %g" % (prog, cam, W, H, MIN_DISTS[k])
+    _RESULTS[case] = probe_case(res, oracle, name, prog, _camera(oracle, cam, W, H), W, H, MIN_DISTS[k], 61000 + CASES.index(case),
+                                cone_expected=W >= 100)
+    return _RESULTS[case]
 
 
 @pytest.mark.parametrize("case", CASES, ids=["%s-%s-%dx%d" % c[:4] for c in CASES])
