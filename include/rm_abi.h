@@ -551,6 +551,15 @@ int rm_measure_write_bandwidth(rm_ctx* ctx, uint64_t bytes, int iters, double* o
  * generic sqrt(a), a / b, (float) i32(round(a)) -- compared on the host with the oracle's definitions. */
 int rm_selftest_sqrt(rm_ctx* ctx, uint64_t* out_mismatches, uint32_t* out_first_bad_bits);
 int rm_selftest_ops(rm_ctx* ctx, const float* a, const float* b, float* out, uint32_t n);
+/* rm_selftest_div: the kernels' short division by one denominator (v_rcp_f32 refined by two FMA; per numerator a multiply, two
+ * FMA and a sign transfer; a range guard in front) against the generic one.  (a) On EVERY b with the sign bit clear: where the
+ * guard accepts b, the refined reciprocal equals 1.0f / b bit for bit.  (b) On the caller's pairs (a[i], b[i]), i < n (host
+ * arrays; may be NULL with n = 0), and on n_seeded pairs generated on the device from `seed`: where the guard accepts the pair
+ * the short quotient equals a / b bit for bit, signed zeros included.  out[8]: 0 reciprocal mismatches, 1 the lowest
+ * mismatching b (bit pattern; all ones: none), 2 the b in [2^-48, 2^44] the guard rejects, 3 those of them whose significand
+ * is not one of the top four, 4 quotient mismatches, 5 the lowest mismatching pair (bits of a << 32 | bits of b; all ones:
+ * none), 6 the caller's pairs the guard sent to the generic form, 7 the seeded ones.  0, 3 and 4 must come back 0. */
+int rm_selftest_div(rm_ctx* ctx, const float* a, const float* b, uint32_t n, uint32_t seed, uint32_t n_seeded, uint64_t* out);
 /* The two cross-lane primitives of wave-level culling (DPP row operations), one wave per 64 inputs (non-negative floats, +inf,
  * NaN): out[i] = the largest value of input i's wave (by bit pattern: a NaN wins), out[64 n_waves + i] = the minimum over the
  * inputs of the LOWER lanes of its wave (+inf for lane 0; a NaN is skipped).  tests/test_gpu_arithmetic.py compares with numpy. */

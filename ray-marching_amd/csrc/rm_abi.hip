@@ -2172,6 +2172,29 @@ RM_EXPORT int rm_selftest_sqrt(rm_ctx* c, uint64_t* out_mismatches, uint32_t* ou
     return RM_OK;
 }
 
+RM_EXPORT int rm_selftest_div(rm_ctx* c, const float* a, const float* b, uint32_t n, uint32_t seed, uint32_t n_seeded, uint64_t* out) {
+    if (!c) return RM_ERR_NULL;
+    if (!out || (n != 0u && (!a || !b))) return fail(c, RM_ERR_NULL, "rm_selftest_div: NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<float> da, db;
+    DevBuf<unsigned long long> d_out;
+    if (int rc = da.reserve(c, n ? n : 1u)) return rc;
+    if (int rc = db.reserve(c, n ? n : 1u)) return rc;
+    if (int rc = d_out.reserve(c, 8)) return rc;
+    unsigned long long init[8] = {0, ~0ull, 0, 0, 0, ~0ull, 0, 0};
+    hipError_t e = hipMemcpy(d_out.p, init, sizeof init, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(da.p, a, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(db.p, b, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(rmk::rm_selftest_div_kernel, dim3(std::max(1, c->cu_count) * 16), dim3(256), 0, c->stream, da.p, db.p, n, seed,
+                           n_seeded, d_out.p);
+        e = hipStreamSynchronize(c->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, d_out.p, 64, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(c, RM_ERR_DEVICE, "rm_selftest_div: %s", hipGetErrorString(e));
+    return RM_OK;
+}
+
 RM_EXPORT int rm_selftest_ops(rm_ctx* c, const float* a, const float* b, float* out, uint32_t n) {
     if (!c) return RM_ERR_NULL;
     if (!a || !b || !out || n == 0u) return fail(c, RM_ERR_NULL, "rm_selftest_ops: NULL argument");

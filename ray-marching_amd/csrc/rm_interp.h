@@ -3,8 +3,8 @@
 // and the arithmetic self-tests.  Device code only (gfx950, wave64).
 //
 // Bit-exactness: every value goes through exactly the operation sequence of the arithmetic
-// contract; only the correctly-rounded sqrt is computed by a shorter (still exact) sequence:
-// see sqrt_rn_fast.
+// contract; only the correctly-rounded sqrt and the divisions of a normalisation are computed by
+// shorter (still exact) sequences: see sqrt_rn_fast and div_rn_fast.
 #pragma once
 #include "rm_kernels.h"
 
@@ -71,6 +71,95 @@ RM_DEV float sqrt_sel(float x, SqrtGuard& guard) {
     } else {
         return __builtin_sqrtf(x);
     }
+}
+
+// Correctly rounded division by one denominator b for several numerators, in v_rcp_f32 + 2 FMA once and a multiply, two FMA
+// and a v_bfi_b32 per numerator -- instead of the generic v_div_scale x2, v_rcp, five FMA, v_div_fmas, v_div_fixup per quotient.
+//   r0 = rcp(b); r = fma(fma(-b, r0, 1), r0, r0):  r = RN(1/b) for every r0 within one ulp of 1/b unless the significand of b
+//     is all ones (Markstein; tools/probe_div_model.cpp repeats it over every significand, rm_selftest_div over every b on
+//     the GPU the library runs on).
+//   q = a r; q' = fma(fma(-q, b, a), r, q):  q' = RN(a/b) given r = RN(1/b) while neither q nor the remainder under- or
+//     overflows (DESIGN.md section 2 "Short division": an error bound plus exhaustion over the quotients near a rounding
+//     boundary).  A zero numerator gives q' = +0 whatever its sign (fma(+0, r, -0) = +0), so q' takes the sign of q.
+// Outside those conditions the results are garbage: a DivGuard collects what decides it from the operands and the caller
+// redoes the divisions with the generic form when any lane of the wave is outside (normalize3 below).  The proven range:
+//   radicand s of b = sqrt(s) in [2^-96, 2^88] (inside sqrt_rn_fast's range), i.e. b in [2^-48, 2^44];  the significand of b
+//   not among the top four (all ones is Markstein's exception, the three below it are margin);  every numerator zero or
+//   2^-79 <= |a| < 2^78, which keeps |q| in (2^-124, 2^127) and the remainder, a multiple of ulp(q) ulp(b) >= 2^-126, zero
+//   or normal.  NaN and infinite operands fall outside by their bit patterns.
+struct DivGuard {
+    uint32_t d_hi = 0u;                 // max over (bits(b) - bits(2^-48)): below the range wraps to the top
+    uint32_t m_hi = 0u;                 // max over the significand fields of b
+    uint32_t a_lo = 0xFFFFFFFFu, a_hi = 0u;  // min over (bits(|a|) - 1): zero wraps to the top; max over bits(|a|)
+    static constexpr uint32_t kBLo = 0x27800000u, kBSpan = 0x2E000000u;  // 2^-48; bits(2^44) - bits(2^-48)
+    static constexpr uint32_t kSLo = 0x0F800000u;                        // 2^-96
+    static constexpr uint32_t kMant = 0x7FFFFCu;
+    static constexpr uint32_t kALo = 0x18000000u, kAHi = 0x66800000u;    // 2^-79, 2^78
+    RM_DEV void denominator(float b) {
+        d_hi = max(d_hi, __float_as_uint(b) - kBLo);
+        m_hi = max(m_hi, __float_as_uint(b) & 0x7FFFFFu);
+    }
+    // b is sqrt_rn_fast(s), garbage when s is outside that function's range: the range test looks at s.  Half the distance of
+    // bits(s) from bits(2^-96) is the distance of bits(b) from bits(2^-48), up to the rounding of the root.
+    RM_DEV void root_of(float s, float b) {
+        d_hi = max(d_hi, (__float_as_uint(s) - kSLo) >> 1);
+        m_hi = max(m_hi, __float_as_uint(b) & 0x7FFFFFu);
+    }
+    RM_DEV void numerator(float a) {
+        const uint32_t ua = __float_as_uint(a) & 0x7FFFFFFFu;
+        a_lo = min(a_lo, ua - 1u);
+        a_hi = max(a_hi, ua);
+    }
+    RM_DEV bool bad() const { return d_hi > kBSpan || m_hi >= kMant || a_lo < kALo - 1u || a_hi >= kAHi; }
+    RM_DEV bool any_bad() const {  // any lane of the wave, combined on the scalar side like SqrtGuard::any_bad
+        return (__builtin_amdgcn_ballot_w64(d_hi > kBSpan) | __builtin_amdgcn_ballot_w64(m_hi >= kMant) |
+                __builtin_amdgcn_ballot_w64(a_lo < kALo - 1u) | __builtin_amdgcn_ballot_w64(a_hi >= kAHi)) != 0ull;
+    }
+};
+RM_DEV float rcp_rn_fast(float b) {
+    const float r0 = __builtin_amdgcn_rcpf(b);
+    return __builtin_fmaf(__builtin_fmaf(-b, r0, 1.0f), r0, r0);
+}
+RM_DEV float div_rn_fast(float a, float b, float r) {  // r = rcp_rn_fast(b)
+    const float q = a * r;
+    const float q1 = __builtin_fmaf(__builtin_fmaf(-q, b, a), r, q);
+    return __uint_as_float((__float_as_uint(q1) & 0x7FFFFFFFu) | (__float_as_uint(q) & 0x80000000u));  // v_bfi_b32
+}
+
+// (x, y, z) / sqrt(s), s the sum of squares the caller formed in the contract's order (wgsl:62, 98-103): one exact root,
+// one exact reciprocal, three short quotients; a wave with any lane outside the DivGuard's range takes the generic form.
+template <bool FAST>
+RM_DEV void normalize3(float s, float& x, float& y, float& z) {
+    if constexpr (FAST) {
+        const float b = sqrt_rn_fast<false>(s);
+        DivGuard g;
+        g.root_of(s, b);
+        g.numerator(x); g.numerator(y); g.numerator(z);
+        if (!g.any_bad()) {
+            const float r = rcp_rn_fast(b);
+            x = div_rn_fast(x, b, r); y = div_rn_fast(y, b, r); z = div_rn_fast(z, b, r);
+            return;
+        }
+    }
+    const float len = __builtin_sqrtf(s);
+    x = x / len; y = y / len; z = z / len;
+}
+// gen_ray_at and shade_hit (rm_kernels.h) with the normalisations switched: the same values, bit for bit.
+template <bool FAST>
+RM_DEV void gen_ray_at(const float* m_proj, const float* m_view, const V4& ro, float sx, float sy, float ox, float oy,
+                       float& dx, float& dy, float& dz) {
+    V4 pv = matvec(m_proj, sx + ox, sy + oy, -1.0f, 1.0f);
+    V4 pw = matvec(m_view, pv.x, pv.y, pv.z, pv.w);
+    dx = pw.x - ro.x; dy = pw.y - ro.y; dz = pw.z - ro.z;
+    const float ew = pw.w - ro.w;
+    normalize3<FAST>(((dx * dx + dy * dy) + dz * dz) + ew * ew, dx, dy, dz);
+}
+template <bool FAST>
+RM_DEV float shade_hit(float nx, float ny, float nz, float px, float py, float pz) {
+    normalize3<FAST>((nx * nx + ny * ny) + nz * nz, nx, ny, nz);
+    float lx = px - 2.0f, ly = py - (-5.0f), lz = pz - 3.0f;  // pos - light_position
+    normalize3<FAST>((lx * lx + ly * ly) + lz * lz, lx, ly, lz);
+    return fmax_(0.02f, (nx * lx + ny * ly) + nz * lz);
 }
 
 template <bool FAST>
@@ -570,6 +659,88 @@ __global__ __launch_bounds__(256) void rm_selftest_sqrt_kernel(uint32_t first, u
         }
     }
     if (bad) atomicAdd(mismatches, bad);
+}
+#endif
+
+// The short division (rcp_rn_fast / div_rn_fast behind a DivGuard) against the generic one.
+// (a) Exhaustive over every b with the sign bit clear (NaN and infinity among them): where the guard accepts b the refined
+//     reciprocal must equal the generic 1.0f / b bit for bit; b in [2^-48, 2^44] the guard rejects are counted, and those of
+//     them whose significand is not among the top four (there must be none).
+// (b) Pairs: the caller's (a[i], b[i]), then n_seeded pairs made from (seed, index) by selftest_div_pair, which
+//     tests/test_gpu_normalise.py restates in numpy.  Where the guard accepts the pair the short quotient must equal a / b bit
+//     for bit (signed zeros included; NaN matches NaN); pairs it rejects are counted, caller's and seeded apart.
+// out: 0 reciprocal mismatches, 1 the lowest mismatching b (bits), 2 rejected b in range, 3 of those outside the top four
+// significands, 4 quotient mismatches, 5 the lowest mismatching pair (bits of a << 32 | bits of b), 6 / 7 the caller's / the
+// seeded pairs on the slow path.
+RM_DEV uint32_t selftest_div_mix(uint32_t x) {  // murmur3's finaliser
+    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+    return x;
+}
+RM_DEV void selftest_div_pair(uint32_t seed, uint32_t j, uint32_t& a_bits, uint32_t& b_bits) {
+    const uint32_t h1 = selftest_div_mix(seed ^ (3u * j) * 0x9E3779B9u), h2 = selftest_div_mix(seed ^ (3u * j + 1u) * 0x9E3779B9u),
+                   h3 = selftest_div_mix(seed ^ (3u * j + 2u) * 0x9E3779B9u);
+    const uint32_t mode = j & 3u;
+    if (mode == 0u) {  // raw bit patterns: mostly outside the guard's range, NaN and infinity among them
+        a_bits = h1;
+        b_bits = h2 & 0x7FFFFFFFu;
+        return;
+    }
+    // b = 2^[-20, 20] * [1, 2); |a| = a random significand 0..3 / 0..39 / 0..109 binades below b's (clamped at the denormals)
+    const uint32_t eb = 107u + (h3 & 0xFFu) % 41u;
+    const uint32_t drop = ((h3 >> 8) & 0xFFu) % (mode == 1u ? 4u : mode == 2u ? 40u : 110u);
+    const uint32_t ea = eb > drop ? eb - drop : 0u;
+    b_bits = (eb << 23) | (h2 & 0x7FFFFFu);
+    a_bits = (h1 & 0x80000000u) | (ea << 23) | (h1 & 0x7FFFFFu);
+    if (((h3 >> 16) & 31u) == 0u) a_bits &= 0x80000000u;   // a zero of either sign
+    if (((h3 >> 21) & 63u) == 0u) b_bits |= 0x7FFFFCu;     // one of the top four significands
+}
+#if !defined(RM_JIT_TU)  // not part of a specialised translation unit (rm_jit.h)
+__global__ __launch_bounds__(256) void rm_selftest_div_kernel(const float* a, const float* b, uint32_t n, uint32_t seed, uint32_t n_seeded,
+                                                              unsigned long long* out) {
+    const uint64_t stride = (uint64_t)gridDim.x * 256u, first = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    unsigned long long bad_r = 0, rejected = 0, rejected_other = 0, bad_q = 0, slow_given = 0, slow_seeded = 0;
+    for (uint64_t i = first; i < ((uint64_t)1 << 31); i += stride) {
+        const uint32_t bits = (uint32_t)i;
+        const float x = __uint_as_float(bits);
+        DivGuard g;
+        g.denominator(x);
+        if (g.bad()) {
+            if (bits >= DivGuard::kBLo && bits <= DivGuard::kBLo + DivGuard::kBSpan) {
+                rejected++;
+                if ((bits & 0x7FFFFFu) < DivGuard::kMant) rejected_other++;
+            }
+        } else if (__float_as_uint(rcp_rn_fast(x)) != __float_as_uint(1.0f / x)) {
+            bad_r++;
+            atomicMin(&out[1], (unsigned long long)bits);
+        }
+    }
+    for (uint64_t i = first; i < (uint64_t)n + n_seeded; i += stride) {
+        uint32_t ua, ub;
+        if (i < n) {
+            ua = __float_as_uint(a[i]); ub = __float_as_uint(b[i]);
+        } else {
+            selftest_div_pair(seed, (uint32_t)(i - n), ua, ub);
+        }
+        const float x = __uint_as_float(ua), y = __uint_as_float(ub);
+        DivGuard g;
+        g.denominator(y);
+        g.numerator(x);
+        if (g.bad()) {
+            if (i < n) slow_given++; else slow_seeded++;
+            continue;
+        }
+        const float got = div_rn_fast(x, y, rcp_rn_fast(y)), want = x / y;
+        if (__float_as_uint(got) != __float_as_uint(want) && !(got != got && want != want)) {
+            bad_q++;
+            atomicMin(&out[5], ((unsigned long long)ua << 32) | ub);
+        }
+    }
+    if (bad_r) atomicAdd(&out[0], bad_r);
+    if (rejected) atomicAdd(&out[2], rejected);
+    if (rejected_other) atomicAdd(&out[3], rejected_other);
+    if (bad_q) atomicAdd(&out[4], bad_q);
+    if (slow_given) atomicAdd(&out[6], slow_given);
+    if (slow_seeded) atomicAdd(&out[7], slow_seeded);
 }
 #endif
 

@@ -980,7 +980,7 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
                         const uint32_t bpx = 2u * (blk & 3u) + (ln & 1u), bpy = 2u * (blk >> 2) + ((ln >> 1) & 1u), s = ln >> 2;
                         const uint32_t r = s * 64u + bpy * 8u + bpx;
                         float gx, gy, gz;
-                        gen_ray_at(u.inv_proj, u.inv_view, ro, wxy[bpx], wxy[8u + bpy], s_off[2u * s], s_off[2u * s + 1u], gx, gy, gz);
+                        gen_ray_at<true>(u.inv_proj, u.inv_view, ro, wxy[bpx], wxy[8u + bpy], s_off[2u * s], s_off[2u * s + 1u], gx, gy, gz);
                         const bool finite_d = __builtin_fabsf(gx) < inf_f && __builtin_fabsf(gy) < inf_f && __builtin_fabsf(gz) < inf_f;
                         // The miss tests are optional (a ray they do not clear is marched and ends as the same miss): in a tile
                         // the scene covers completely they clear nothing -- 92 % of the rays that reach this kernel are marched --
@@ -1053,7 +1053,7 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
 #endif
                 if (lane < tap_n) {
                     const uint32_t r = hq_rid[e] & 1023u;
-                    res[r] = shade_hit(tn[lane], tn[64u + lane], tn[128u + lane], hx, hy, hz);  // wgsl:98-103
+                    res[r] = shade_hit<true>(tn[lane], tn[64u + lane], tn[128u + lane], hx, hy, hz);  // wgsl:98-103
                     rmat[r] = (uint8_t)m;
                 }
                 tap_t = TAP_IDLE;
@@ -1093,7 +1093,7 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
                 // (the hit position is read again rather than kept in three registers through the four-tap function, whose
                 // pressure is the kernel's peak: the acquire keeps the compiler from forwarding the earlier loads)
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                if (live4) res[hq_rid[e] & 1023u] = shade_hit(nx, ny, nz, hq_v[e], hq_v[V5_HQ + e], hq_v[2u * V5_HQ + e]);  // wgsl:98-103
+                if (live4) res[hq_rid[e] & 1023u] = shade_hit<true>(nx, ny, nz, hq_v[e], hq_v[V5_HQ + e], hq_v[2u * V5_HQ + e]);  // wgsl:98-103
                 tap_t = TAP_IDLE;
             }
             continue;
@@ -1152,7 +1152,7 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
                 const float ny = tap_t == 0u ? vy : tn[64u + lane] + vy;
                 const float nz = tap_t == 0u ? vz : tn[128u + lane] + vz;
                 if (++tap_t == 4u && !tagged) {
-                    if (is_live) res[hq_rid[he] & 1023u] = shade_hit(nx, ny, nz, hq_v[he], hq_v[V5_HQ + he], hq_v[2u * V5_HQ + he]);  // wgsl:98-103
+                    if (is_live) res[hq_rid[he] & 1023u] = shade_hit<true>(nx, ny, nz, hq_v[he], hq_v[V5_HQ + he], hq_v[2u * V5_HQ + he]);  // wgsl:98-103
                     tap_t = TAP_IDLE;
                     break;
                 }
@@ -1689,7 +1689,7 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
             const uint32_t item = base + lane, q = item >> 4, s = item & 15u;
             const uint32_t pl = w_list[q < n_need ? q : 0u];
             float dx, dy, dz;
-            gen_ray_at(mp, mv, ro, w_sxy[pl], w_sxy[64u + pl], s_off[2u * s], s_off[2u * s + 1u], dx, dy, dz);
+            gen_ray_at<true>(mp, mv, ro, w_sxy[pl], w_sxy[64u + pl], s_off[2u * s], s_off[2u * s + 1u], dx, dy, dz);
             const int c = shade_floor(ro.y, ro.x, ro.z, dx, dy, dz);  // wgsl:117-130
             if (q < n_need) w_code[pl * 16u + s] = (uint8_t)(c + 1);
         }
@@ -1705,7 +1705,7 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
     } else {
         for (uint32_t s = 0; s < 16u; s++) {  // reference order: wgsl:44-45, 68-69
             float dx, dy, dz;
-            gen_ray_at(mp, mv, ro, sx, sy, s_off[2u * s], s_off[2u * s + 1u], dx, dy, dz);
+            gen_ray_at<true>(mp, mv, ro, sx, sy, s_off[2u * s], s_off[2u * s + 1u], dx, dy, dz);
             const int c = shade_floor(ro.y, ro.x, ro.z, dx, dy, dz);  // wgsl:117-130
             float rg, b;
             gamma_of(c, rg, b);
