@@ -290,6 +290,7 @@ extern "C" {
     pub fn rm_selftest_sqrt(ctx: *mut rm_ctx, out_mismatches: *mut u64, out_first_bad_bits: *mut u32) -> c_int;
     pub fn rm_selftest_ops(ctx: *mut rm_ctx, a: *const f32, b: *const f32, out: *mut f32, n: u32) -> c_int;
     pub fn rm_selftest_div(ctx: *mut rm_ctx, a: *const f32, b: *const f32, n: u32, seed: u32, n_seeded: u32, out: *mut u64) -> c_int;
+    pub fn rm_selftest_normalise(ctx: *mut rm_ctx, input: *const f32, n: u32, mode: c_int, out: *mut u32) -> c_int;
     pub fn rm_selftest_wave(ctx: *mut rm_ctx, input: *const f32, n_waves: u32, out: *mut f32) -> c_int;
     pub fn rm_selftest_cull_rays(ctx: *mut rm_ctx, origin: *const f32, dirs: *const f32, n: u32, out_flags: *mut u32, out_bound: *mut f32) -> c_int;
     pub fn rm_selftest_cull_pixels(ctx: *mut rm_ctx, w: u32, h: u32, xy: *const u32, n: u32, out: *mut f32) -> c_int;

@@ -560,6 +560,18 @@ int rm_selftest_ops(rm_ctx* ctx, const float* a, const float* b, float* out, uin
  * is not one of the top four, 4 quotient mismatches, 5 the lowest mismatching pair (bits of a << 32 | bits of b; all ones:
  * none), 6 the caller's pairs the guard sent to the generic form, 7 the seeded ones.  0, 3 and 4 must come back 0. */
 int rm_selftest_div(rm_ctx* ctx, const float* a, const float* b, uint32_t n, uint32_t seed, uint32_t n_seeded, uint64_t* out);
+/* rm_selftest_normalise: the normalisations of the march kernels as those kernels call them -- the device functions themselves,
+ * not restatements -- on records the caller chooses.  in[8 n] (host array): one record of 8 floats per lane, 64 consecutive
+ * records per wave, so the caller decides which lanes share a wave's fall-back to the generic form; n a multiple of 64, at most
+ * 2^24 (RM_ERR_ARG otherwise).  mode 0: (x, y, z) = in[8 i + 0..2], divided by the root of (x x + y y) + z z (normalize3);
+ * mode 1: (dx, dy, dz, ew) = in[8 i + 0..3], the ray form: (dx, dy, dz) divided by the root of ((dx dx + dy dy) + dz dz) + ew ew;
+ * mode 2: the tap sum n = in[8 i + 0..2] and the hit position pos = in[8 i + 4..6] through shade_hit:
+ * max(0.02, normalize(n) . normalize(pos - (2, -5, 3))).  Unused fields are ignored.
+ * out[8 n] (host array, 32-bit words; floats as their bit patterns): out[8 i + 0..2] the result of the short form as the
+ * kernels run it (whole-wave fall-back included; mode 2: word 0 alone, 1..2 zero), 3..5 the same call in its generic form
+ * (mode 2: word 3 alone), 6 the range guard's verdict for lane i alone (1: outside the short form's range; mode 2: bit 0 the
+ * normal, bit 1 the light vector), 7 zero.  tests/test_gpu_normalise_direct.py compares all of it with numpy. */
+int rm_selftest_normalise(rm_ctx* ctx, const float* in, uint32_t n, int mode, uint32_t* out);
 /* The two cross-lane primitives of wave-level culling (DPP row operations), one wave per 64 inputs (non-negative floats, +inf,
  * NaN): out[i] = the largest value of input i's wave (by bit pattern: a NaN wins), out[64 n_waves + i] = the minimum over the
  * inputs of the LOWER lanes of its wave (+inf for lane 0; a NaN is skipped).  tests/test_gpu_arithmetic.py compares with numpy. */

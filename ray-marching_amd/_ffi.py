@@ -145,6 +145,8 @@ def hip_lib():
         L.rm_selftest_ops.restype = C.c_int
         L.rm_selftest_div.argtypes = [vp, vp, vp, u32, u32, u32, C.POINTER(u64)]
         L.rm_selftest_div.restype = C.c_int
+        L.rm_selftest_normalise.argtypes = [vp, vp, u32, C.c_int, vp]
+        L.rm_selftest_normalise.restype = C.c_int
         L.rm_selftest_wave.argtypes = [vp, vp, u32, vp]
         L.rm_selftest_wave.restype = C.c_int
         L.rm_selftest_cull_rays.argtypes = [vp, vp, vp, u32, vp, vp]

@@ -2195,6 +2195,27 @@ RM_EXPORT int rm_selftest_div(rm_ctx* c, const float* a, const float* b, uint32_
     return RM_OK;
 }
 
+RM_EXPORT int rm_selftest_normalise(rm_ctx* c, const float* in, uint32_t n, int mode, uint32_t* out) {
+    if (!c) return RM_ERR_NULL;
+    if (!in || !out) return fail(c, RM_ERR_NULL, "rm_selftest_normalise: NULL argument");
+    if (n == 0u || (n & 63u) != 0u || n > (1u << 24) || mode < 0 || mode > 2)
+        return fail(c, RM_ERR_ARG, "rm_selftest_normalise: n must be a multiple of 64 in [64, 2^24] and mode 0, 1 or 2");
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<float> din;
+    DevBuf<uint32_t> dout;
+    if (int rc = din.reserve(c, (size_t)n * 8)) return rc;
+    if (int rc = dout.reserve(c, (size_t)n * 8)) return rc;
+    hipError_t e = hipMemcpy(din.p, in, (size_t)n * 32, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(rmk::rm_selftest_normalise_kernel, dim3(n / 256u + (n % 256u ? 1u : 0u)), dim3(256), 0, c->stream, din.p, n,
+                           (uint32_t)mode, dout.p);
+        e = hipStreamSynchronize(c->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, dout.p, (size_t)n * 32, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(c, RM_ERR_DEVICE, "rm_selftest_normalise: %s", hipGetErrorString(e));
+    return RM_OK;
+}
+
 RM_EXPORT int rm_selftest_ops(rm_ctx* c, const float* a, const float* b, float* out, uint32_t n) {
     if (!c) return RM_ERR_NULL;
     if (!a || !b || !out || n == 0u) return fail(c, RM_ERR_NULL, "rm_selftest_ops: NULL argument");

@@ -128,13 +128,19 @@ RM_DEV float div_rn_fast(float a, float b, float r) {  // r = rcp_rn_fast(b)
 
 // (x, y, z) / sqrt(s), s the sum of squares the caller formed in the contract's order (wgsl:62, 98-103): one exact root,
 // one exact reciprocal, three short quotients; a wave with any lane outside the DivGuard's range takes the generic form.
+// The guard of one normalisation: the radicand s, its short root b and the three numerators (rm_selftest_normalise reads a
+// lane's verdict from the same function).
+RM_DEV DivGuard normalize3_guard(float s, float b, float x, float y, float z) {
+    DivGuard g;
+    g.root_of(s, b);
+    g.numerator(x); g.numerator(y); g.numerator(z);
+    return g;
+}
 template <bool FAST>
 RM_DEV void normalize3(float s, float& x, float& y, float& z) {
     if constexpr (FAST) {
         const float b = sqrt_rn_fast<false>(s);
-        DivGuard g;
-        g.root_of(s, b);
-        g.numerator(x); g.numerator(y); g.numerator(z);
+        const DivGuard g = normalize3_guard(s, b, x, y, z);
         if (!g.any_bad()) {
             const float r = rcp_rn_fast(b);
             x = div_rn_fast(x, b, r); y = div_rn_fast(y, b, r); z = div_rn_fast(z, b, r);
@@ -145,14 +151,18 @@ RM_DEV void normalize3(float s, float& x, float& y, float& z) {
     x = x / len; y = y / len; z = z / len;
 }
 // gen_ray_at and shade_hit (rm_kernels.h) with the normalisations switched: the same values, bit for bit.
+// wgsl:62's vec4 normalize of pt_world - ro_world, of which only xyz is used: four squares in the radicand, three quotients.
+template <bool FAST>
+RM_DEV void normalize_ray(float& dx, float& dy, float& dz, float ew) {
+    normalize3<FAST>(((dx * dx + dy * dy) + dz * dz) + ew * ew, dx, dy, dz);
+}
 template <bool FAST>
 RM_DEV void gen_ray_at(const float* m_proj, const float* m_view, const V4& ro, float sx, float sy, float ox, float oy,
                        float& dx, float& dy, float& dz) {
     V4 pv = matvec(m_proj, sx + ox, sy + oy, -1.0f, 1.0f);
     V4 pw = matvec(m_view, pv.x, pv.y, pv.z, pv.w);
     dx = pw.x - ro.x; dy = pw.y - ro.y; dz = pw.z - ro.z;
-    const float ew = pw.w - ro.w;
-    normalize3<FAST>(((dx * dx + dy * dy) + dz * dz) + ew * ew, dx, dy, dz);
+    normalize_ray<FAST>(dx, dy, dz, pw.w - ro.w);
 }
 template <bool FAST>
 RM_DEV float shade_hit(float nx, float ny, float nz, float px, float py, float pz) {
@@ -741,6 +751,47 @@ __global__ __launch_bounds__(256) void rm_selftest_div_kernel(const float* a, co
     if (bad_q) atomicAdd(&out[4], bad_q);
     if (slow_given) atomicAdd(&out[6], slow_given);
     if (slow_seeded) atomicAdd(&out[7], slow_seeded);
+}
+#endif
+
+// The normalisations the march kernels perform -- normalize3, the ray's four-term form, shade_hit -- as those kernels call
+// them, on records the caller chooses: in[8 i + ..], one record per lane and 64 consecutive records per wave (n is a multiple of
+// 64), so that the caller decides which lanes share a wave's fallback.  mode 0: (x, y, z) = in[0..2] through
+// normalize3((x x + y y) + z z, ..); mode 1: (dx, dy, dz, ew) = in[0..3] through normalize_ray; mode 2: the tap sum in[0..2]
+// and the position in[4..6] through shade_hit.  out[8 i + ..]: 0..2 the result with FAST = true (mode 2: 0 alone), 3..5 with
+// FAST = false (mode 2: 3 alone), 6 the DivGuard's verdict for this lane alone (1: outside; mode 2: bit 0 the normal, bit 1 the
+// light vector), the rest zero.
+#if !defined(RM_JIT_TU)  // not part of a specialised translation unit (rm_jit.h)
+__global__ __launch_bounds__(256) void rm_selftest_normalise_kernel(const float* in, uint32_t n, uint32_t mode, uint32_t* out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;  // whole waves: n is a multiple of 64
+    const float* r = in + (size_t)i * 8u;
+    uint32_t* o = out + (size_t)i * 8u;
+    float fx = r[0], fy = r[1], fz = r[2], gx = fx, gy = fy, gz = fz;
+    uint32_t verdict;
+    if (mode == 2u) {
+        const float px = r[4], py = r[5], pz = r[6];
+        const float lx = px - 2.0f, ly = py - (-5.0f), lz = pz - 3.0f, sn = (fx * fx + fy * fy) + fz * fz, sl = (lx * lx + ly * ly) + lz * lz;
+        verdict = (normalize3_guard(sn, sqrt_rn_fast<false>(sn), fx, fy, fz).bad() ? 1u : 0u) |
+                  (normalize3_guard(sl, sqrt_rn_fast<false>(sl), lx, ly, lz).bad() ? 2u : 0u);
+        fx = shade_hit<true>(fx, fy, fz, px, py, pz);
+        gx = shade_hit<false>(gx, gy, gz, px, py, pz);
+        fy = fz = gy = gz = 0.0f;
+    } else {
+        const float ew = mode == 1u ? r[3] : 0.0f;
+        const float s = mode == 1u ? ((fx * fx + fy * fy) + fz * fz) + ew * ew : (fx * fx + fy * fy) + fz * fz;
+        verdict = normalize3_guard(s, sqrt_rn_fast<false>(s), fx, fy, fz).bad() ? 1u : 0u;
+        if (mode == 1u) {
+            normalize_ray<true>(fx, fy, fz, ew);
+            normalize_ray<false>(gx, gy, gz, ew);
+        } else {
+            normalize3<true>(s, fx, fy, fz);
+            normalize3<false>(s, gx, gy, gz);
+        }
+    }
+    o[0] = __float_as_uint(fx); o[1] = __float_as_uint(fy); o[2] = __float_as_uint(fz);
+    o[3] = __float_as_uint(gx); o[4] = __float_as_uint(gy); o[5] = __float_as_uint(gz);
+    o[6] = verdict; o[7] = 0u;
 }
 #endif
 
