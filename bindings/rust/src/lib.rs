@@ -217,6 +217,25 @@ pub const RM_LIGHT_AO_SCALE: c_int = 11;
 pub const RM_LIGHT_AO_TAPS: c_int = 12;
 pub const RM_LIGHT_PARAMS: c_int = 13;
 
+// Ray traversal (rm_trace_defaults / rm_trace_rays).
+// enum rm_trace: indices into the parameter array; RM_TRACE_PARAMS is its length
+pub const RM_TRACE_T_MIN: c_int = 0;
+pub const RM_TRACE_T_MAX: c_int = 1;
+pub const RM_TRACE_MIN_STEP: c_int = 2;
+pub const RM_TRACE_STEP_SCALE: c_int = 3;
+pub const RM_TRACE_LEVEL: c_int = 4;
+pub const RM_TRACE_MAX_STEPS: c_int = 5;
+pub const RM_TRACE_PARAMS: c_int = 6;
+// enum rm_tracekind: the kind of an event
+pub const RM_TRACE_ENTER: c_int = 1;
+pub const RM_TRACE_EXIT: c_int = 2;
+// enum rm_traceflag: bits of a ray's flags word
+pub const RM_TRACE_START_INSIDE: c_int = 1;
+pub const RM_TRACE_END_INSIDE: c_int = 2;
+pub const RM_TRACE_OUT_OF_STEPS: c_int = 4;
+// enum rm_tracelimit
+pub const RM_TRACE_MAX_EVENTS: c_int = 64;
+
 // Opcodes of the node types the reference only names in comments (builder.rs:8,14,16-23) and that the device
 // path implements as extensions: a CSGCommandType that gains these variants serialises them unchanged.
 //   Plane = 2, Intersection = 102, TranslationPush = 200, TranslationPop, RotationPush, RotationPop, ScalePush, ScalePop
@@ -253,6 +272,10 @@ extern "C" {
                         is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_camera_rays(ctx: *mut rm_ctx, w_frame: u32, h_frame: u32, x0: u32, y0: u32, w: u32, h: u32, sample: u32,
                           out_rays: *mut f32, is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_trace_defaults(out: *mut f32, n_out: u32) -> c_int;
+    pub fn rm_trace_rays(ctx: *mut rm_ctx, n: u32, rays: *const f32, params: *const f32, n_params: u32, max_events: u32, flags: u32,
+                         out_events: *mut f32, out_event_ids: *mut u32, out_counts: *mut u32, out_spans: *mut f32,
+                         is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_sample_grid(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, out_dist: *mut f32,
                           is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_extract_mesh(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, level: f32,
@@ -311,6 +334,14 @@ extern "C" {
 pub fn lighting_defaults() -> [f32; RM_LIGHT_PARAMS as usize] {
     let mut out = [0.0f32; RM_LIGHT_PARAMS as usize];
     let rc = unsafe { rm_lighting_defaults(out.as_mut_ptr(), RM_LIGHT_PARAMS as u32) };
+    assert_eq!(rc, RM_OK);
+    out
+}
+
+/// The default traversal parameters (`rm_trace_defaults`; host code, no GPU needed), indexed by `RM_TRACE_*`.
+pub fn trace_defaults() -> [f32; RM_TRACE_PARAMS as usize] {
+    let mut out = [0.0f32; RM_TRACE_PARAMS as usize];
+    let rc = unsafe { rm_trace_defaults(out.as_mut_ptr(), RM_TRACE_PARAMS as u32) };
     assert_eq!(rc, RM_OK);
     out
 }
@@ -502,6 +533,35 @@ impl RayMarchingResources {
         let ids = out_ids.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
         let rgb = out_rgb.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
         self.check(unsafe { rm_cast_rays(self.ctx, n as u32, rays.as_ptr(), hit, ids, rgb, 0, std::ptr::null_mut()) })
+    }
+
+    /// Every crossing of the level set along `rays.len() / 6` rays (host memory) over [T_MIN, T_MAX], in order (DESIGN.md
+    /// section 18): `params` indexed by `RM_TRACE_*` (`trace_defaults()` is the starting point), `max_events` slots per ray
+    /// (1..`RM_TRACE_MAX_EVENTS`), `flags` `RM_MESH_NORMALS` / `RM_MESH_IDS`.  Per slot: `out_events` (eight floats: t,
+    /// position, normal, width) and `out_event_ids` (four words: kind, step, leaf, material); per ray: `out_counts` (four
+    /// words: events found, steps, flags, events stored) and `out_spans` (four floats: final t, length inside, first and
+    /// final distance).  `None` skips that output.
+    pub fn trace_rays(&self, rays: &[f32], params: &[f32; RM_TRACE_PARAMS as usize], max_events: u32, flags: u32,
+                      out_events: Option<&mut [f32]>, out_event_ids: Option<&mut [u32]>, out_counts: Option<&mut [u32]>,
+                      out_spans: Option<&mut [f32]>) -> Result<(), RmError> {
+        assert!(rays.len() % 6 == 0, "trace_rays: rays holds {} floats, not a multiple of 6", rays.len());
+        let n = rays.len() / 6;
+        assert!(n <= u32::MAX as usize);
+        // (the library rejects a max_events outside 1..RM_TRACE_MAX_EVENTS before it writes; the slices are sized for the
+        // value as given)
+        let slots = n * max_events as usize;
+        assert!(out_events.as_ref().map_or(true, |s| s.len() >= 8 * slots), "trace_rays: out_events is shorter than {} slots", slots);
+        assert!(out_event_ids.as_ref().map_or(true, |s| s.len() >= 4 * slots), "trace_rays: out_event_ids is shorter than {} slots", slots);
+        assert!(out_counts.as_ref().map_or(true, |s| s.len() >= 4 * n), "trace_rays: out_counts is shorter than {} rays", n);
+        assert!(out_spans.as_ref().map_or(true, |s| s.len() >= 4 * n), "trace_rays: out_spans is shorter than {} rays", n);
+        let events = out_events.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let event_ids = out_event_ids.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let counts = out_counts.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let spans = out_spans.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        self.check(unsafe {
+            rm_trace_rays(self.ctx, n as u32, rays.as_ptr(), params.as_ptr(), RM_TRACE_PARAMS as u32, max_events, flags, events,
+                          event_ids, counts, spans, 0, std::ptr::null_mut())
+        })
     }
 
     /// The rays the draw marches for AA sample `sample` (0..15, or `RM_SAMPLE_CENTER`) of the `w` x `h` pixels at (`x0`,

@@ -307,6 +307,55 @@ int rm_cast_rays(rm_ctx* ctx, uint32_t n, const float* rays, float* out_hit, uin
 int rm_camera_rays(rm_ctx* ctx, uint32_t W, uint32_t H, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                    uint32_t sample, float* out_rays, int is_device, void* stream);
 
+/* Ray traversal (extension): every crossing of the level set along a ray over [T_MIN, T_MAX], in
+ * order -- where rm_cast_rays stops at the first surface.  A ray is (o, d), d used as given.  D(t) is what rm_query_points
+ * returns at (ox + dx t, oy + dy t, oz + dz t) (one rounded product and one rounded sum per coordinate); inside(t) is
+ * D(t) < LEVEL (NaN is outside, as in rm_extract_mesh).  Every operation is one binary32 operation in the order written;
+ * fmin / fmax: NaN loses.
+ *   t = T_MIN; da = D(t); in = da < LEVEL; steps = 1; events = 0; length = 0; t_enter = t
+ *   while t < T_MAX and steps < MAX_STEPS:
+ *       h  = fmax(|da - LEVEL| * STEP_SCALE, MIN_STEP);  tn = fmin(t + h, T_MAX)
+ *       db = D(tn); steps += 1; inb = db < LEVEL
+ *       if inb != in:
+ *           tc = fmin(t + (tn - t) * ((da - LEVEL) / (da - db)), tn)      (rm_extract_mesh's vertex rule on [t, tn])
+ *           event number `events` (stored while events < max_events): t = tc, position o + d tc, width tn - t,
+ *                                                                     kind ENTER if inb else EXIT, step = steps
+ *           events += 1;  if inb: t_enter = tc  else: length = length + (tc - t_enter)
+ *       t = tn; da = db; in = inb
+ *   if in: length = length + (t - t_enter)
+ * With STEP_SCALE <= 1 / max(1, L), L from rm_program_lipschitz, no step can pass the level set in real arithmetic: what can
+ * be missed is a pair of crossings closer than MIN_STEP, and each event lies within its width of a true crossing.  The call
+ * accepts any scale in (0, 1]. */
+enum rm_trace {
+    RM_TRACE_T_MIN = 0,      /* default 0; finite */
+    RM_TRACE_T_MAX = 1,      /* default 100; finite, >= T_MIN */
+    RM_TRACE_MIN_STEP = 2,   /* default 0.001; finite, > 0 */
+    RM_TRACE_STEP_SCALE = 3, /* default 1; (0, 1] */
+    RM_TRACE_LEVEL = 4,      /* default 0; finite */
+    RM_TRACE_MAX_STEPS = 5,  /* map_scene evaluations a ray may take: default 1024; integral, 1..65536 */
+    RM_TRACE_PARAMS = 6
+};
+enum rm_tracekind { RM_TRACE_ENTER = 1, RM_TRACE_EXIT = 2 };
+enum rm_traceflag { RM_TRACE_START_INSIDE = 1, RM_TRACE_END_INSIDE = 2, RM_TRACE_OUT_OF_STEPS = 4 }; /* OUT_OF_STEPS: ended with t < T_MAX */
+enum rm_tracelimit { RM_TRACE_MAX_EVENTS = 64 };
+/* The table above (host code; no context).  RM_ERR_NULL for a NULL out, RM_ERR_ARG when n_out < RM_TRACE_PARAMS. */
+int rm_trace_defaults(float* out, uint32_t n_out);
+/* rays: n x 6 as rm_cast_rays reads them.  params: RM_TRACE_PARAMS floats in host memory (n_params must be RM_TRACE_PARAMS:
+ * RM_ERR_ARG; a value outside its range: RM_ERR_RANGE).  max_events K: 1..RM_TRACE_MAX_EVENTS (RM_ERR_RANGE).  flags:
+ * RM_MESH_NORMALS / RM_MESH_IDS, the attributes to compute per stored event (others: RM_ERR_ARG).
+ *   out_counts:    n x 4 u32 (events found -- counting past K --, steps, flags RM_TRACE_*, events stored = min(events, K))
+ *   out_spans:     n x 4 f32 (the final t, length inside the solid over the interval marched, D(T_MIN), the final D)
+ *   out_events:    n x K x 8 f32 (t, x, y, z, nx, ny, nz, width); an unfilled slot is (+inf, 0, ..., 0)
+ *   out_event_ids: n x K x 4 u32 (kind RM_TRACE_ENTER / RM_TRACE_EXIT, step, leaf, material); unfilled (0, 0, RM_NO_ID, RM_NO_ID)
+ * The normal and (leaf, material) of an event are what rm_query_points returns at its (x, y, z) when asked for in flags,
+ * zeros / RM_NO_ID otherwise.  Any output may be NULL (that work is skipped; with both event arrays NULL no attribute work
+ * runs); what one array receives does not depend on the others.  is_device, stream, ordering, statuses and the draw state as
+ * for rm_cast_rays; every device output needs 16-byte alignment, rays 4-byte.  n = 0 writes nothing; a failed call launches
+ * nothing. */
+int rm_trace_rays(rm_ctx* ctx, uint32_t n, const float* rays, const float* params, uint32_t n_params, uint32_t max_events,
+                  uint32_t flags, float* out_events, uint32_t* out_event_ids, uint32_t* out_counts, float* out_spans,
+                  int is_device, void* stream);
+
 /* Mesh export (extension): the scene's distance on a lattice, and its level surface as an indexed triangle mesh, from the
  * program, limits and material table as they are at the call.  Every float is bit-identical to the
  * oracle's map_scene at the lattice points; vertices and triangles follow from them by the rule below, so two runs give

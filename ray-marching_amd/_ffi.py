@@ -67,6 +67,13 @@ RM_SLICE_POINTS, RM_SLICE_CONTOURS, RM_SLICE_COUNTS = 0, 1, 2
 RM_LIGHT_PARAMS = 13
 LIGHT_NAMES = ("pos_x", "pos_y", "pos_z", "shadow", "shadow_softness", "bias", "shadow_max_t", "shadow_steps", "ao", "ao_step",
                "ao_falloff", "ao_scale", "ao_taps")
+# ray traversal (rm_trace_defaults / rm_trace_rays): enum rm_trace, the parameter names in index order; event kinds; ray flags
+(RM_TRACE_T_MIN, RM_TRACE_T_MAX, RM_TRACE_MIN_STEP, RM_TRACE_STEP_SCALE, RM_TRACE_LEVEL, RM_TRACE_MAX_STEPS,
+ RM_TRACE_PARAMS) = range(7)
+TRACE_PARAM_NAMES = ("t_min", "t_max", "min_step", "step_scale", "level", "max_steps")
+RM_TRACE_ENTER, RM_TRACE_EXIT = 1, 2
+RM_TRACE_START_INSIDE, RM_TRACE_END_INSIDE, RM_TRACE_OUT_OF_STEPS = 1, 2, 4
+RM_TRACE_MAX_EVENTS = 64
 
 _hip = None
 _host = None
@@ -166,6 +173,10 @@ def hip_lib():
         L.rm_camera_rays.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, vp, C.c_int, vp]
         L.rm_camera_rays.restype = C.c_int
         f3 = C.POINTER(C.c_float)
+        L.rm_trace_defaults.argtypes = [f3, u32]
+        L.rm_trace_defaults.restype = C.c_int
+        L.rm_trace_rays.argtypes = [vp, u32, vp, f3, u32, u32, u32, vp, vp, vp, vp, C.c_int, vp]
+        L.rm_trace_rays.restype = C.c_int
         L.rm_sample_grid.argtypes = [vp, f3, f3, u32, u32, u32, vp, C.c_int, vp]
         L.rm_sample_grid.restype = C.c_int
         L.rm_extract_mesh.argtypes = [vp, f3, f3, u32, u32, u32, C.c_float, u32, C.POINTER(u64)]

@@ -24,6 +24,7 @@
 #include "rm_interp.h"
 #include "rm_kernel_v5.h"
 #include "rm_query.h"
+#include "rm_trace.h"
 #include "rm_mesh.h"
 #include "rm_mesh_bound.h"
 #include "rm_mesh_sparse.h"
@@ -141,6 +142,7 @@ struct rm_ctx {
     DevBuf<RmRecord> d_qprog;
     uint64_t qprog_gen = ~0ull;
     DevBuf<char> d_qin, d_qout;
+    DevBuf<char> d_tscratch;  // ray traversal (rm_trace.h): the attribute pass's scratch (rml::TraceScratch)
     size_t max_lds = 0;  // LDS a workgroup may allocate on this device
     // lit rendering (rm_light.h): enum rm_light, validated by rm_set_lighting; travels with each lit draw as kernel arguments
     float light[RM_LIGHT_PARAMS] = RM_LIGHT_DEFAULTS;
@@ -702,12 +704,12 @@ struct Outputs {
     rm_ctx* c;
     bool to_host;
     DevBuf<char>& staging;
-    struct Out { void* user; size_t offset, bytes; } out[3] = {};
+    struct Out { void* user; size_t offset, bytes; } out[4] = {};
     int n = 0;
     size_t total = 0;
     Outputs(rm_ctx* c, int is_device, DevBuf<char>& staging) : c(c), to_host(!is_device), staging(staging) {}
     void add(void* user, size_t bytes) {
-        assert(n < 3);
+        assert(n < 4);
         out[n++] = Out{user, total, bytes};
         if (user) total += rml::align16(bytes);
     }
@@ -1044,6 +1046,14 @@ auto with_loop(int loop, F&& f) {
 // pairs of rm_query_points 8 B, the hit records and id quadruples of rm_cast_rays 16 B.  A pointer off that alignment is refused.
 bool misaligned(const void* p, uintptr_t align) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & (align - 1u)) != 0u; }
 
+// LDS dwords per lane of a wave's column: what the distance loop needs (value stack, then 3 floats per transform level) and,
+// with the leaf walk, the larger of that and the walk's ([depth] distances, [depth] pairs, 3 floats per transform level).
+uint32_t query_slots(const RmDecoded& d, int loop, bool walk) {
+    uint32_t slots = loop == rmk::Q_LOOP_CHAIN ? 0u : loop == rmk::Q_LOOP_TREE ? d.spill_depth : d.spill_depth + 3u * d.xform_depth;
+    if (walk) slots = std::max(slots, 2u * d.q_spill_depth + 3u * d.q_xform_depth);
+    return slots;
+}
+
 // What every query of the program does first, on stream `s`, exactly as a draw would: ordering with the context's earlier
 // work, the program (decoded, validated and uploaded by ensure_program), the limits and -- for colours of a tagged program --
 // the material table.  Fills the launch and the dynamic LDS of one 256-thread workgroup: four wave columns of `slots` dwords
@@ -1066,8 +1076,7 @@ int query_begin(rm_ctx* c, hipStream_t s, bool walk, bool rgb, rmk::QueryLaunch*
         c->qprog_gen = c->prog_gen;
     }
     *loop = query_loop(d);
-    uint32_t slots = *loop == rmk::Q_LOOP_CHAIN ? 0u : *loop == rmk::Q_LOOP_TREE ? d.spill_depth : d.spill_depth + 3u * d.xform_depth;
-    if (walk) slots = std::max(slots, 2u * d.q_spill_depth + 3u * d.q_xform_depth);
+    const uint32_t slots = query_slots(d, *loop, walk);
     *shmem = (size_t)slots * 64u * 4u * 4u;
     const size_t cap = std::max<size_t>(c->max_lds, 64u * 1024u);
     if (*shmem > cap) return fail(c, RM_ERR_TOO_LARGE, "the query needs %zu bytes of LDS per workgroup", *shmem);
@@ -1086,13 +1095,19 @@ int query_begin(rm_ctx* c, hipStream_t s, bool walk, bool rgb, rmk::QueryLaunch*
     return RM_OK;
 }
 
+// `blocks` 256-thread workgroups of a query kernel ...
 template <class K, class... Args>
-int query_launch(rm_ctx* c, K kernel, size_t count, size_t shmem, hipStream_t s, Args... args) {
+int query_launch_blocks(rm_ctx* c, K kernel, uint32_t blocks, size_t shmem, hipStream_t s, Args... args) {
     if (shmem > 64u * 1024u)  // (deep programs: gfx950 gives a workgroup up to 160 KB)
         HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)((count + 255u) / 256u)), dim3(256), shmem, s, args...);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), shmem, s, args...);
     HIP_TRY(c, hipGetLastError());
     return RM_OK;
+}
+// ... and as many as give `count` items one lane each.
+template <class K, class... Args>
+int query_launch(rm_ctx* c, K kernel, size_t count, size_t shmem, hipStream_t s, Args... args) {
+    return query_launch_blocks(c, kernel, (uint32_t)((count + 255u) / 256u), shmem, s, args...);
 }
 
 using PointsFn = void (*)(rmk::QueryLaunch, uint32_t, const float*, float*, float*, uint32_t*);
@@ -1211,6 +1226,117 @@ RM_EXPORT int rm_camera_rays(rm_ctx* c, uint32_t W, uint32_t H, uint32_t x0, uin
     o.add(out_rays, (size_t)count * 24u);
     int rc = o.reserve();
     if (rc == RM_OK) rc = query_launch(c, rmk::rm_camera_rays_kernel, count, 0u, s, c->uniforms, W, H, x0, y0, w, count, sample, o.dev<float>(0));
+    return rc == RM_OK ? o.finish(s) : rc;
+}
+
+// ---- ray traversal (rm_trace.h) ------------------------------------------------------------------------------------------
+namespace {
+
+// enum rm_trace: T_MIN, T_MAX, MIN_STEP, STEP_SCALE, LEVEL, MAX_STEPS
+const float kTraceDefaults[RM_TRACE_PARAMS] = {0.0f, 100.0f, 0.001f, 1.0f, 0.0f, 1024.0f};
+
+// The first parameter outside the table of enum rm_trace (NaN and infinities are outside everywhere), or -1.
+int bad_trace_param(const float* p) {
+    for (int i = 0; i < RM_TRACE_PARAMS; i++)
+        if (!std::isfinite(p[i])) return i;
+    if (!(p[RM_TRACE_T_MAX] >= p[RM_TRACE_T_MIN])) return RM_TRACE_T_MAX;
+    if (!(p[RM_TRACE_MIN_STEP] > 0.0f)) return RM_TRACE_MIN_STEP;
+    if (!(p[RM_TRACE_STEP_SCALE] > 0.0f && p[RM_TRACE_STEP_SCALE] <= 1.0f)) return RM_TRACE_STEP_SCALE;
+    const float ms = p[RM_TRACE_MAX_STEPS];
+    if (!(ms >= 1.0f && ms <= (float)kMaxIter && ms == std::floor(ms))) return RM_TRACE_MAX_STEPS;
+    return -1;
+}
+
+using TraceMarchFn = void (*)(rmk::QueryLaunch, rmk::TraceLaunch, uint32_t, const float*, float*, uint32_t*, uint32_t*, float*,
+                              uint32_t*, unsigned long long*);
+TraceMarchFn trace_march_kernel(int loop) {
+    return with_loop(loop, [&](auto tag) -> TraceMarchFn { return rmk::rm_trace_march_kernel<decltype(tag)::value>; });
+}
+using TraceAttrFn = void (*)(rmk::QueryLaunch, uint32_t, const uint32_t*, const uint2*, const float*, float*, uint32_t*);
+TraceAttrFn trace_attr_kernel(int loop, bool normals, bool ids) {
+    return with_loop(loop, [&](auto tag) -> TraceAttrFn {
+        constexpr int LOOP = decltype(tag)::value;
+        if (normals) return ids ? rmk::rm_trace_attr_kernel<LOOP, true, true> : rmk::rm_trace_attr_kernel<LOOP, true, false>;
+        return rmk::rm_trace_attr_kernel<LOOP, false, true>;
+    });
+}
+
+}  // namespace
+
+RM_EXPORT int rm_trace_defaults(float* out, uint32_t n_out) {
+    if (!out) return RM_ERR_NULL;
+    if (n_out < (uint32_t)RM_TRACE_PARAMS) return RM_ERR_ARG;
+    std::memcpy(out, kTraceDefaults, sizeof kTraceDefaults);
+    return RM_OK;
+}
+
+RM_EXPORT int rm_trace_rays(rm_ctx* c, uint32_t n, const float* rays, const float* params, uint32_t n_params, uint32_t max_events,
+                            uint32_t flags, float* out_events, uint32_t* out_event_ids, uint32_t* out_counts, float* out_spans,
+                            int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_events && !out_event_ids && !out_counts && !out_spans) return fail(c, RM_ERR_NULL, "rm_trace_rays: every output is NULL");
+    if (n_params != (uint32_t)RM_TRACE_PARAMS)
+        return fail(c, RM_ERR_ARG, "rm_trace_rays: %u parameters, not %d", n_params, (int)RM_TRACE_PARAMS);
+    if (flags & ~(uint32_t)(RM_MESH_NORMALS | RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_trace_rays: unknown flags 0x%x", flags);
+    if (max_events == 0u || max_events > (uint32_t)RM_TRACE_MAX_EVENTS)
+        return fail(c, RM_ERR_RANGE, "rm_trace_rays: max_events %u not in [1,%d]", max_events, (int)RM_TRACE_MAX_EVENTS);
+    if (params) {
+        const int bad = bad_trace_param(params);
+        if (bad >= 0)
+            return fail(c, RM_ERR_RANGE, "rm_trace_rays: parameter %d = %g is outside its range (enum rm_trace)", bad, (double)params[bad]);
+    }
+    if (n == 0u) return RM_OK;
+    if (!rays || !params) return fail(c, RM_ERR_NULL, "rm_trace_rays: %s is NULL", rays ? "params" : "rays");
+    if (is_device && (misaligned(rays, 4) || misaligned(out_events, 16) || misaligned(out_event_ids, 16) || misaligned(out_counts, 16) ||
+                      misaligned(out_spans, 16)))
+        return fail(c, RM_ERR_ARG, "rm_trace_rays: device arrays need 16-byte alignment (rays: 4-byte)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = dest_stream(c, is_device, stream);
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);  // the march: the distance loop's columns
+    if (rc != RM_OK) return rc;
+    const size_t cap = std::max<size_t>(c->max_lds, 64u * 1024u);
+    if (shmem + 64u > cap) return fail(c, RM_ERR_TOO_LARGE, "the query needs %zu bytes of LDS per workgroup", shmem + 64u);
+    // the attribute pass runs for what the caller both asked for and takes; with the ids its columns hold the walk's layout
+    const bool normals = (flags & RM_MESH_NORMALS) && out_events, ids = (flags & RM_MESH_IDS) && out_event_ids, attr = normals || ids;
+    rmk::QueryLaunch QA = Q;
+    QA.slots = query_slots(c->decoded, loop, ids);
+    const size_t shmem_attr = (size_t)QA.slots * 64u * 4u * 4u;
+    if (attr && shmem_attr > cap) return fail(c, RM_ERR_TOO_LARGE, "the query needs %zu bytes of LDS per workgroup", shmem_attr);
+    const uint32_t K = max_events, nb = (uint32_t)(((uint64_t)n + 255u) / 256u);
+    const rmk::TraceLaunch T{params[RM_TRACE_T_MIN], params[RM_TRACE_T_MAX], params[RM_TRACE_MIN_STEP], params[RM_TRACE_STEP_SCALE],
+                             params[RM_TRACE_LEVEL], (uint32_t)params[RM_TRACE_MAX_STEPS], K};
+    const rml::TraceScratch<uint2> L(n, nb, K, attr && !out_events);
+    if (attr)
+        if ((rc = c->d_tscratch.reserve(c, L.bytes, "traversal scratch")) != RM_OK) return rc;
+    Outputs o(c, is_device, c->d_qout);
+    o.add(out_events, (size_t)n * K * 32u);
+    o.add(out_event_ids, (size_t)n * K * 16u);
+    o.add(out_counts, (size_t)n * 16u);
+    o.add(out_spans, (size_t)n * 16u);
+    const float* d_rays = nullptr;
+    if ((rc = query_input(c, o, rays, (size_t)n * 24u, s, &d_rays)) != RM_OK) return rc;
+    void* base = c->d_tscratch.p;
+    // the event records the march writes and the attribute pass reads the positions from: the caller's, else the scratch copy
+    float* d_events = out_events ? o.dev<float>(0) : attr ? L.events.at(base) : nullptr;
+    rc = query_launch(c, trace_march_kernel(loop), n, shmem, s, Q, T, n, d_rays, d_events, o.dev<uint32_t>(1), o.dev<uint32_t>(2),
+                      o.dev<float>(3), attr ? L.stored.at(base) : nullptr, attr ? L.sums.at(base) : nullptr);
+    if (rc == RM_OK && attr) {
+        hipLaunchKernelGGL(rmk::rm_mesh_scan_kernel, dim3(1), dim3(1024), 0, s, L.sums.at(base), nb, L.totals.at(base));
+        HIP_TRY(c, hipGetLastError());
+        rc = query_launch(c, rmk::rm_trace_list_kernel, n, 0u, s, n, static_cast<const uint32_t*>(L.stored.at(base)),
+                          static_cast<const unsigned long long*>(L.sums.at(base)), L.list.at(base));
+        // one lane per stored event; how many there are only the device knows, so a fixed number of workgroups strides over them
+        const uint64_t most = ((uint64_t)n * K + 255u) / 256u;
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>(most, (uint64_t)std::max(c->cu_count, 1) * 8u);
+        if (rc == RM_OK)
+            rc = query_launch_blocks(c, trace_attr_kernel(loop, normals, ids), blocks, shmem_attr, s, QA, K,
+                                     static_cast<const uint32_t*>(L.totals.at(base)), static_cast<const uint2*>(L.list.at(base)),
+                                     static_cast<const float*>(d_events), normals ? o.dev<float>(0) : nullptr,
+                                     ids ? o.dev<uint32_t>(1) : nullptr);
+    }
     return rc == RM_OK ? o.finish(s) : rc;
 }
 

@@ -149,6 +149,24 @@ struct SliceAttributes {
         : normals(a.take<float>(with_normals ? P * 3u : 0u)), ids(a.take<uint32_t>(with_ids ? P * 2u : 0u)), bytes(a.total) {}
 };
 
+// rm_trace_rays' scratch of the attribute pass over n rays (nb workgroups of 256) with K event slots each: the stored count
+// per ray, the workgroups' sums (scanned in place into offsets), the total (2 of 4 words), the compact (ray, slot) list -- K
+// entries per ray at most -- and, only when the caller takes no event records, a copy of them for the positions.  Pair is the
+// kernels' uint2.
+template <class Pair>
+struct TraceScratch {
+    Carver a;
+    Region<uint32_t> stored;
+    Region<unsigned long long> sums;
+    Region<uint32_t> totals;
+    Region<Pair> list;
+    Region<float> events;
+    size_t bytes;
+    TraceScratch(uint32_t n, uint32_t nb, uint32_t K, bool own_events)
+        : stored(a.take<uint32_t>(n)), sums(a.take<unsigned long long>(nb)), totals(a.take<uint32_t>(4)),
+          list(a.take<Pair>((size_t)n * K)), events(a.take<float>(own_events ? (size_t)n * K * 8u : 0u)), bytes(a.total) {}
+};
+
 // Where the arrays of a mesh of V vertices and T triangles lie in the mesh buffer; the attributes as above.
 struct MeshLayout {
     Carver a;

@@ -53,6 +53,8 @@ class RayMarchingResources:
     def write_buffer(self, buffer, offset, data):
         """Queue::write_buffer (renderer.rs:213,230,235); data: bytes-like."""
         b = bytes(data)
+        if buffer == _ffi.RM_BUF_COMMANDS:
+            self._program = None      # (no longer what set_program gave: trace_rays cannot bound its step from it)
         self._check(self._L.rm_write_buffer(self._h, buffer, offset, b, len(b)))
 
     def set_limits(self, limits):
@@ -66,7 +68,9 @@ class RayMarchingResources:
         w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32))
         n = int(w.size)
         ptr = w.ctypes.data_as(C.POINTER(C.c_uint32)) if n else None
+        self._program = None
         self._check(self._L.rm_set_program(self._h, int(cmd_count), ptr, n))
+        self._program = (int(cmd_count), w.copy())
 
     def set_materials(self, rgb):
         """Material table (extension): (n, 3) albedo values, n in [1, 256]; entry i colours the surfaces tagged Material(i)."""
@@ -290,22 +294,24 @@ class RayMarchingResources:
                                             C.c_void_p(normal_ptr or None), C.c_void_p(ids_ptr or None), 1,
                                             C.c_void_p(stream) if stream else None))
 
+    def _rays_input(self, origins, directions):
+        """_query_input for rays: origins (n, 3) + directions (n, 3), or one (n, 6) array as camera_rays returns."""
+        if directions is None:
+            return self._query_input(origins, 6, "rays")
+        ko, o, n = self._query_input(origins, 3, "origins")
+        kd, d, nd = self._query_input(directions, 3, "directions")
+        if ko != kd or n != nd:
+            raise ValueError("origins and directions must be arrays of the same kind and length")
+        if ko == "torch":
+            import torch
+            return ko, torch.cat([o, d], dim=1).contiguous(), n
+        return ko, np.ascontiguousarray(np.concatenate([o, d], axis=1)), n
+
     def cast_rays(self, origins, directions=None):
         """March rays (origins (n, 3) + directions (n, 3), or one (n, 6) array as camera_rays returns) exactly as the draw
         does.  Returns a dict: kind (RM_HIT_*), steps, leaf, material (RM_NO_ID unless a surface), t, position (n, 3),
         normal (n, 3), diffuse, rgb (n, 3)."""
-        if directions is None:
-            kind, r, n = self._query_input(origins, 6, "rays")
-        else:
-            ko, o, n = self._query_input(origins, 3, "origins")
-            kd, d, nd = self._query_input(directions, 3, "directions")
-            if ko != kd or n != nd:
-                raise ValueError("origins and directions must be arrays of the same kind and length")
-            if ko == "torch":
-                import torch
-                kind, r = ko, torch.cat([o, d], dim=1).contiguous()
-            else:
-                kind, r = ko, np.ascontiguousarray(np.concatenate([o, d], axis=1))
+        kind, r, n = self._rays_input(origins, directions)
         if kind == "torch":
             import torch
             hit = torch.empty((n, 8), dtype=torch.float32, device=r.device)
@@ -325,6 +331,72 @@ class RayMarchingResources:
         self._check(self._L.rm_cast_rays(self._h, int(n), C.c_void_p(rays_ptr), C.c_void_p(hit_ptr or None),
                                          C.c_void_p(ids_ptr or None), C.c_void_p(rgb_ptr or None), 1,
                                          C.c_void_p(stream) if stream else None))
+
+    # -- ray traversal (rm_trace_rays): every entry and exit of the solid along a ray, DESIGN.md section 18 -------------------
+    @staticmethod
+    def trace_defaults():
+        """The default traversal parameters as a dict (_ffi.TRACE_PARAM_NAMES; pure host code)."""
+        return dict(zip(_ffi.TRACE_PARAM_NAMES, trace_defaults()))
+
+    def _trace_params(self, named):
+        p = trace_defaults()
+        for i, k in enumerate(_ffi.TRACE_PARAM_NAMES):
+            if named.get(k) is not None:
+                p[i] = float(named[k])
+        if named.get("step_scale") is None:
+            # a step of |d - level| / max(1, L) cannot pass the level set (L: the program's Lipschitz bound)
+            prog = getattr(self, "_program", None)
+            if prog is None:
+                raise ValueError("step_scale=None needs the program as set_program / set_scene gave it; pass a step_scale")
+            L = program_lipschitz(*prog)
+            if not np.isfinite(L):
+                raise ValueError("the program has no finite Lipschitz bound (rm_program_lipschitz): pass a step_scale, "
+                                 "which then carries no guarantee")
+            p[_ffi.RM_TRACE_STEP_SCALE] = float(np.float32(1.0 / max(1.0, L)))
+        return (C.c_float * _ffi.RM_TRACE_PARAMS)(*p)
+
+    def trace_rays(self, origins, directions=None, *, t_min=None, t_max=None, min_step=None, step_scale=None, level=None,
+                   max_steps=None, max_events=8, normals=False, ids=True):
+        """Every crossing of the level set along each ray over [t_min, t_max], in order (rays as for cast_rays; parameters
+        left at None take trace_defaults(); step_scale=None: 1 / max(1, program_lipschitz), ValueError when that bound is
+        infinite).  Returns a dict.  Per ray: events (found, counting past max_events), steps, flags (RM_TRACE_START_INSIDE /
+        END_INSIDE / OUT_OF_STEPS), stored, t_end, length (inside the solid), d_start, d_end.  Per event slot (n, max_events):
+        t (+inf when unfilled), position, normal (zeros unless normals=True), width, kind (RM_TRACE_ENTER / EXIT; 0 when
+        unfilled), step, leaf, material (RM_NO_ID unless ids=True)."""
+        params = self._trace_params(dict(t_min=t_min, t_max=t_max, min_step=min_step, step_scale=step_scale, level=level,
+                                         max_steps=max_steps))
+        kind, r, n = self._rays_input(origins, directions)
+        K = int(max_events)
+        flags = (_ffi.RM_MESH_NORMALS if normals else 0) | (_ffi.RM_MESH_IDS if ids else 0)
+        if kind == "torch":
+            import torch
+            ev = torch.empty((n, K, 8), dtype=torch.float32, device=r.device)
+            eid = torch.empty((n, K, 4), dtype=torch.int32, device=r.device)
+            cnt = torch.empty((n, 4), dtype=torch.int32, device=r.device)
+            sp = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+            self.trace_rays_device(n, r.data_ptr(), params, K, flags, ev.data_ptr(), eid.data_ptr(), cnt.data_ptr(), sp.data_ptr(),
+                                   stream=self._torch_stream(r))
+        else:
+            ev = np.empty((n, K, 8), dtype=np.float32)
+            eid = np.empty((n, K, 4), dtype=np.uint32)
+            cnt = np.empty((n, 4), dtype=np.uint32)
+            sp = np.empty((n, 4), dtype=np.float32)
+            self._check(self._L.rm_trace_rays(self._h, n, r.ctypes.data, params, _ffi.RM_TRACE_PARAMS, K, flags, ev.ctypes.data,
+                                              eid.ctypes.data, cnt.ctypes.data, sp.ctypes.data, 0, None))
+        return {"events": cnt[:, 0], "steps": cnt[:, 1], "flags": cnt[:, 2], "stored": cnt[:, 3], "t_end": sp[:, 0],
+                "length": sp[:, 1], "d_start": sp[:, 2], "d_end": sp[:, 3], "t": ev[:, :, 0], "position": ev[:, :, 1:4],
+                "normal": ev[:, :, 4:7], "width": ev[:, :, 7], "kind": eid[:, :, 0], "step": eid[:, :, 1], "leaf": eid[:, :, 2],
+                "material": eid[:, :, 3]}
+
+    def trace_rays_device(self, n, rays_ptr, params, max_events, flags=0, events_ptr=0, event_ids_ptr=0, counts_ptr=0, spans_ptr=0,
+                          stream=None):
+        """rm_trace_rays on device memory (integer addresses; 0 = not wanted), asynchronous on `stream`.  params: the six
+        values in _ffi.TRACE_PARAM_NAMES order."""
+        p = params if isinstance(params, C.Array) else (C.c_float * _ffi.RM_TRACE_PARAMS)(*[float(v) for v in params])
+        self._check(self._L.rm_trace_rays(self._h, int(n), C.c_void_p(rays_ptr), p, len(p), int(max_events), int(flags),
+                                          C.c_void_p(events_ptr or None), C.c_void_p(event_ids_ptr or None),
+                                          C.c_void_p(counts_ptr or None), C.c_void_p(spans_ptr or None), 1,
+                                          C.c_void_p(stream) if stream else None))
 
     def camera_rays(self, W, H, x0=0, y0=0, w=None, h=None, sample=_ffi.RM_SAMPLE_CENTER, out=None):
         """The rays the draw marches for AA sample `sample` (0..15, or RM_SAMPLE_CENTER) of the pixels of the w x h block at
@@ -684,6 +756,15 @@ def lighting_defaults():
     """rm_lighting_defaults: the 13 default lighting parameters in _ffi.LIGHT_NAMES order (pure host code, no GPU needed)."""
     out = (C.c_float * _ffi.RM_LIGHT_PARAMS)()
     rc = _ffi.hip_lib().rm_lighting_defaults(out, _ffi.RM_LIGHT_PARAMS)
+    if rc != _ffi.RM_OK:
+        raise _ffi.RmError(rc, _ffi.hip_lib().rm_status_string(rc).decode())
+    return [float(v) for v in out]
+
+
+def trace_defaults():
+    """rm_trace_defaults: the 6 default traversal parameters in _ffi.TRACE_PARAM_NAMES order (pure host code, no GPU needed)."""
+    out = (C.c_float * _ffi.RM_TRACE_PARAMS)()
+    rc = _ffi.hip_lib().rm_trace_defaults(out, _ffi.RM_TRACE_PARAMS)
     if rc != _ffi.RM_OK:
         raise _ffi.RmError(rc, _ffi.hip_lib().rm_status_string(rc).decode())
     return [float(v) for v in out]
