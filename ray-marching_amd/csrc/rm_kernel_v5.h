@@ -103,8 +103,9 @@ constexpr float kPruneAbs = 4.0e-6f;
 //        L_u = |p* - c| - R - rho  <=  value_u(p_l)  <=  |p* - c| + rho - r_in = H_u      (triangle inequality)
 // LATTICE programs (threshold rule above): unit u is far for lane l when |p* - c| - R - |p_l - p*| > thr_l; for the whole wave
 //   when |p* - c| - R > S = max over live lanes (|p_l - p*| + thr_l) -- one reduction (the first form took rho and T = max thr_l
-//   separately: L_u > T).  A CPU simulation of the metric frame (tools/sim/wave_cull_sim.py) has the rho + T form evaluate 4.5 of
-//   16 leaves per step where the per-lane pair tests evaluate 5.5 and a per-lane, per-leaf test 4.2.
+//   separately: L_u > T), with |p_l - p*| in the L1 norm (wave_cull_lattice below).  A CPU simulation of the metric frame
+//   (tools/sim/wave_cull_sim.py; batches of 2x2 pixels x 16 samples) has the rho + T form evaluate 3.62 of 16 leaves per step, S with the
+//   L2 norm 3.60, with the L1 norm 3.63, where the per-lane pair tests evaluate 4.54 and a per-lane, per-leaf test 3.09.
 // Programs that BLEND, top-level chain (rm_units.h).  With a_hi(u) = min over the Union / SmoothUnion units j < u of H_j
 //   (the accumulator a unit meets is at most the smallest leaf blended in so far) and a_lo(u) = min_j L_j - kmax (a chain
 //   of blends never falls more than the largest k below its smallest leaf: rm_decode.h [*]; Subtraction and Intersection
@@ -117,7 +118,7 @@ constexpr float kPruneAbs = 4.0e-6f;
 //   skipped (and any opaque unit, behind which nothing is known) POISONS the rules -- every unit behind it is evaluated.
 //   Same simulation, config 3: 4.4 of 16 units per step against 7.2 for the per-lane rule of the first half of this round.
 // All comparisons fail on a NaN (the unit is evaluated); m is the margin of the threshold rule at p*, with rho added.
-// Cost: ~50 vector instructions per evaluation for a lattice program, ~100 for a blending one, whatever the number of units.
+// Cost: ~30 vector instructions per evaluation for a lattice program, ~100 for a blending one, whatever the number of units.
 #define RM_DPP(old, src, ctrl) ((uint32_t)__builtin_amdgcn_update_dpp((int)(old), (int)(src), (ctrl), 0xF, 0xF, false))
 // largest value over the wave, wave-uniform (all 64 lanes must be active; lanes without a value pass 0).  Four DPP steps
 // leave every row of 16 lanes with its maximum (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror), two
@@ -211,8 +212,27 @@ RM_DEV unsigned long long wave_cull_lattice(const uint32_t* lunits, uint32_t n_u
     const float py = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), first));
     const float pz = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(z), first));
     const float ex = x - px, ey = y - py, ez = z - pz;
-    const float e2 = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
-    const float sl = (__builtin_amdgcn_sqrtf(e2) * 1.00001f + 1.0e-30f) + thr;  // v_sqrt_f32 is within an ulp
+    // The reach is taken in the L1 norm: |p_l - p*|_2 <= |p_l - p*|_1, so the triangle inequality holds a fortiori, and the sum
+    // of three magnitudes is two additions (|.| is a source modifier) where the L2 norm is three multiply-adds and a v_sqrt_f32,
+    // the one transcendental of a march step the arithmetic contract does not ask for (nothing overlaps one: DESIGN.md section 5).
+    // The price is a larger S -- 3.63 leaves of 16 evaluated per step on the metric frame instead of 3.60 (tools/sim/wave_cull_sim.py;
+    // 3.28 instead of 3.20 by the GPU's counters, profiles/r14_lattice_reach_ab.txt).
+    // Slack, with u = 2^-24 (every operation below is rounded to nearest; a difference or a sum that lands among the denormals is
+    // exact, and nothing is squared: no underflow, which is what the L2 form's "+ 1e-30f" was for -- ex * ex vanishes below 1e-19):
+    //   x - px            a rounded difference is at least (1 - u) times the exact one:  |x - px| <= |ex| / (1 - u)
+    //   the two additions a rounded sum is at least (1 - u) times the exact one:         |ex| + |ey| + |ez| <= l1 / (1 - u)^2
+    //                     together |p_l - p*|_1 <= l1 / (1 - u)^3 < l1 (1 + 1.8e-7): the factor 1.00001f of the multiply-add covers it
+    //                     fifty times over (the figure is the L2 form's, kept so that the two reaches differ by the norm alone);
+    //   S * 1.000005f     the single rounding of the multiply-add (sl >= (1 - u) (l1 * 1.00001f + thr)), this product's own, and
+    //                     the rounding of s = S + R below (thr >= 0 or NaN, R >= 0 or +inf: both are relative to a sum of non-negative
+    //                     terms): 3 u = 1.8e-7 of 5e-6;
+    //   1.000004f         on the squares, 2e-6 on the lengths: the three differences c - p* (u each), the three roundings of
+    //                     the fused sum of their squares (d2 is below 1 + 3e-7 times the exact one), s * s and the product with
+    //                     the constant (u each): 5e-7 of 4e-6 on the squares.
+    // A NaN or an infinite coordinate, or a NaN or +inf threshold, of a live lane gives sl = +inf or NaN: both win the unsigned
+    // maximum over every finite reach, S is not finite and no comparison below holds.  A dead lane passes 0, whatever it holds.
+    const float l1 = (__builtin_fabsf(ex) + __builtin_fabsf(ey)) + __builtin_fabsf(ez);
+    const float sl = __builtin_fmaf(l1, 1.00001f, thr);
     const float S = __uint_as_float(wave_max_u32(is_live ? __float_as_uint(sl) : 0u)) * 1.000005f;
     // far: |p* - c| - R > S, decided on the squares (every term is >= 0; a NaN or an infinity makes it false)
     const uint32_t lane = threadIdx.x & 63u;

@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
-"""CPU simulation (numpy, statistics only): how many leaves does a wave of 64 rays marching in step have to evaluate per
-iteration under different far tests?  A wave = the 64 pixels of an 8x8 tile at one AA sample (what the march kernel's ray pool
-hands a wave), all rays advanced together, rays that end leave their lane idle.
+"""CPU simulation (numpy, binary64, statistics only): how many leaves does a wave of 64 rays marching in step have to evaluate per
+iteration under different far tests?  A wave = one BATCH of the march kernel's ray pool: the sixteen AA samples of a 2x2 block of
+pixels (lane: sample lane >> 2, pixel lane & 3 of the block), all rays advanced together, rays that end leave their lane idle.
+The first march step is shared (every ray evaluates the scene at the camera: the kernel takes it once per frame), so a batch
+starts at dist = f0 with threshold 2 |f0| and that evaluation is not counted.  Thresholds are 2 |F| without float margins.
   exact      a leaf is evaluated iff v_leaf <= thr for ANY live lane (per-lane, per-leaf test; the ideal of the threshold rule)
-  pairs      the shipped tests: bounding sphere per pair of consecutive leaves, then a test per box
-  ball       one test per leaf for the whole wave: |p* - c| - R - rho > max thr, p* a live lane's position, rho the wave's radius
-usage: wave_cull_sim.py [scene] [W H] [n_tiles]"""
+  pairs      rounds 1 and 2: bounding sphere per pair of consecutive leaves, then a test per box
+  rho + T    one test per leaf for the whole wave, two reductions: |p* - c| - R - rho > max thr, p* the first live lane's
+             position, rho the wave's radius about it
+  one reduction, |p* - c| - R > S = max over live lanes (|p_l - p*| + thr_l), with |.| the
+    L2       Euclidean norm (shipped until round 14: three multiply-adds and a square root per lane)
+    L1       sum of the magnitudes (shipped: two additions)
+    Linf     sqrt(3) times the largest magnitude
+usage: wave_cull_sim.py [scene] [W H] [n_batches]"""
 import os
 import sys
 
@@ -96,23 +103,25 @@ PR = np.array([max(np.linalg.norm(C[a] - PC[g]) + RB[a], np.linalg.norm(C[b] - P
 
 rng = np.random.default_rng(1)
 tiles_x, tiles_y = W // 8, H // 8
-stat = {"iters": 0, "live": 0, "exact": 0, "pairs": 0, "ball": 0, "ball2": 0, "lane": 0}
+RULES = ("exact", "pairs", "rho+T", "L2", "L1", "Linf")
+stat = dict.fromkeys(("iters", "live", "lane") + RULES, 0)
+F0 = float(fold(leaf_values(ro[None]))[0])                 # the shared first step
 done_tiles = 0
 attempts = 0
-while done_tiles < NT and attempts < 40 * NT:
+lane = np.arange(64)
+while done_tiles < NT and attempts < 40 * NT and MIN_D <= F0 <= MAX_D:
     attempts += 1
-    tx, ty = int(rng.integers(tiles_x)), int(rng.integers(tiles_y))
-    s = int(rng.integers(16))
-    px = (tx * 8 + np.arange(64) % 8).astype(float)
-    py = (ty * 8 + np.arange(64) // 8).astype(float)
-    d = rays(px, py, s)
-    # keep rays that hit (the marched population is ~92 % hits); march all first to classify
-    sc = np.zeros(64)
+    tx, ty, blk = int(rng.integers(tiles_x)), int(rng.integers(tiles_y)), int(rng.integers(16))
+    px = (tx * 8 + 2 * (blk & 3) + (lane & 1)).astype(float)
+    py = (ty * 8 + 2 * (blk >> 2) + ((lane >> 1) & 1)).astype(float)
+    d = np.concatenate([rays(px[4 * s:4 * s + 4], py[4 * s:4 * s + 4], s) for s in range(16)])
+    # keep batches that are marched at all (the marched population is ~92 % hits); march first to classify
+    sc = np.full(64, F0)
     live = np.ones(64, bool)
     hit = np.zeros(64, bool)
     hist = []
-    thr = np.full(64, np.inf)
-    for it in range(MAX_ITER):
+    thr = np.full(64, 2 * abs(F0))
+    for it in range(1, MAX_ITER):
         if not live.any():
             break
         p = ro[None] + d * sc[:, None]
@@ -129,17 +138,14 @@ while done_tiles < NT and attempts < 40 * NT:
     if hit.sum() < 8:
         continue
     done_tiles += 1
-    keep = hit            # lanes of rays that are marched at all
     for live, p, v, thr in hist:
-        l = live & keep
-        if not l.any():
-            continue
+        l = live
         stat["iters"] += 1
         stat["live"] += l.sum()
         near = (v[l] <= thr[l][:, None])                 # (n_live, N)
         stat["lane"] += near.sum() / l.sum()
         stat["exact"] += near.any(axis=0).sum()
-        # shipped: pair spheres then boxes individually
+        # rounds 1 and 2: pair spheres, then boxes individually
         dp = np.linalg.norm(p[l][:, None, :] - PC[None], axis=2) - PR[None]
         pnear = (dp <= thr[l][:, None]).any(axis=0)
         cnt = 0
@@ -153,22 +159,22 @@ while done_tiles < NT and attempts < 40 * NT:
         if N % 2:
             cnt += int(near[:, N - 1].any())
         stat["pairs"] += cnt
-        # ball: reference = first live lane
-        pl = p[l]
-        pstar = pl[0]
-        rho = np.linalg.norm(pl - pstar[None], axis=1).max()
-        T = thr[l].max()
-        lb = np.linalg.norm(C - pstar[None], axis=1) - RB - rho
-        stat["ball"] += (lb <= T).sum()
-        # ball around the centroid (smaller rho)
-        pc = pl.mean(axis=0)
-        rho2 = np.linalg.norm(pl - pc[None], axis=1).max()
-        lb2 = np.linalg.norm(C - pc[None], axis=1) - RB - rho2
-        stat["ball2"] += (lb2 <= T).sum()
-it = stat["iters"]
-print("%s %dx%d: %d tiles, %d wave-iterations, lane occupancy %.2f" % (scene, W, H, done_tiles, it, stat["live"] / (64.0 * it)))
-print("leaves of %d evaluated per wave-iteration:  per-lane average %.2f | exact union %.2f | shipped pair+box tests %.2f | ball (a lane's position) %.2f | ball (centroid) %.2f"
-      % (N, stat["lane"] / it, stat["exact"] / it, stat["pairs"] / it, stat["ball"] / it, stat["ball2"] / it))
+        # the wave rules: reference = first live lane
+        pl, tl = p[l], thr[l]
+        e = np.abs(pl - pl[0][None])
+        gap = np.linalg.norm(C - pl[0][None], axis=1) - RB
+        l2 = np.sqrt((e * e).sum(axis=1))
+        stat["rho+T"] += (gap - l2.max() <= tl.max()).sum()
+        stat["L2"] += (gap <= (l2 + tl).max()).sum()
+        stat["L1"] += (gap <= (e.sum(axis=1) + tl).max()).sum()
+        stat["Linf"] += (gap <= (np.sqrt(3.0) * e.max(axis=1) + tl).max()).sum()
+it = max(stat["iters"], 1)
+print("%s %dx%d: %d batches (2x2 pixels x 16 samples), %d wave-iterations after the shared first step (f0 = %.4f), lane occupancy %.2f" % (
+    scene, W, H, done_tiles, stat["iters"], F0, stat["live"] / (64.0 * it)))
+print("leaves of %d evaluated per wave-iteration: per-lane average %.2f" % (N, stat["lane"] / it))
+for rule, label in (("exact", "exact per-lane union (ideal)"), ("pairs", "pair + box tests per lane (rounds 1, 2)"), ("rho+T", "rho + T, two reductions"),
+                    ("L2", "L2 reach, one reduction"), ("L1", "L1 reach, one reduction (shipped)"), ("Linf", "sqrt(3) Linf reach, one reduction")):
+    print("  %-42s %.2f" % (label, stat[rule] / it))
 
 # ---- programs that blend: the local rule, per lane and through the wave's ball -----------------------------------------
 if any(isinstance(c[2], tuple) for c in chain):
