@@ -17,6 +17,7 @@
 
 #include "rm_abi.h"
 #include "rm_abi_layout.h"
+#include "rm_lds_layout.h"
 #include "rm_decode.h"
 #include "rm_jit.h"
 #include "rm_device.h"
@@ -377,9 +378,6 @@ int finish_launch(rm_ctx* c);
 int time_begin(rm_ctx* c, hipStream_t s);
 int time_end(rm_ctx* c, hipStream_t s);
 
-// LDS behind the program copy of a march workgroup: {pool cursor, tile slot, veto, pad} + the 16 AA sample offsets (+ pad)
-constexpr size_t kV5TailBytes = 16u + 144u;
-
 // What a march launch decides before it launches: whether the miss tests run, which record loop an interpreter kernel takes and
 // whether it culls per wave -- written into L (n_cull, n_tree, spill_depth, flags, n_cone, n_slab).  The culling self-tests
 // (rm_selftest_cull_*) fill their launch through it too, so that they see the fields a frame would see.
@@ -432,7 +430,6 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
     const int loop = plan.loop;
     c->last_loop = loop;
     const uint32_t n_tiles = ((L.W + 7u) / 8u) * ((L.rows + 7u) / 8u);
-    const size_t cull_bytes = (size_t)L.n_cone * 16u + (size_t)L.n_slab * 48u;
     // structure-specialised kernel (values live in registers: no LDS spill stack)
     hipFunction_t spec_fn = lds ? specialised_kernel(c, WPT) : nullptr;
     if (spec_fn) { L.spill_depth = 0u; L.n_tree = 0u; }
@@ -440,18 +437,15 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
     // (a specialised kernel with the generated material walk keeps those pairs in registers too)
     if (L.n_mrec != 0u && !(spec_fn && c->spec && c->spec->material_walk))
         L.spill_depth = std::max(L.spill_depth, 2u * d.mat_spill_depth + 3u * d.mat_xform_depth);
-    L.wave_dwords = rmk::V5_WAVE_DWORDS - ((spec_fn && c->spec && c->spec->taps4 && L.n_mrec == 0u) ? rmk::V5_TN_DWORDS : 0u);
-    const size_t shmem = (size_t)(1024u + WPT * L.wave_dwords) * 4u +
-                         (size_t)L.spill_depth * 64u * WPT * 4u + cull_bytes +
-                         (lds ? (size_t)(L.n_rec + L.n_grp + L.n_tree) * sizeof(RmRecord) : 0u) + kV5TailBytes +
-                         (L.n_mrec != 0u ? 1024u : 0u);
-    if (shmem > 64u * 1024u) return fail(c, RM_ERR_TOO_LARGE, "program needs %zu bytes of LDS per tile", shmem);
+    L.wave_dwords = rml::V5_WAVE_DWORDS - ((spec_fn && c->spec && c->spec->taps4 && L.n_mrec == 0u) ? rml::V5_TN_DWORDS : 0u);
+    const size_t shmem = rml::MarchLds(WPT, L.wave_dwords, L.spill_depth, L.n_cone, L.n_slab, lds, L.n_rec, L.n_grp, L.n_tree, L.n_mrec != 0u).bytes;
+    if (shmem > rml::kLdsLaunchLimit) return fail(c, RM_ERR_TOO_LARGE, "program needs %zu bytes of LDS per tile", shmem);
     // pre-pass buffers: cost + work list per tile, {count, cursor} per frame
     if (int rc = c->d_cost.reserve(c, (size_t)n_tiles * n_frames)) return rc;
     if (int rc = c->d_order.reserve(c, (size_t)n_tiles * n_frames)) return rc;
     if (int rc = c->d_counters.reserve(c, (size_t)n_frames * 4u)) return rc;
     hipLaunchKernelGGL(rmk::rm_tile_pre_v5, dim3((n_tiles + rmk::V5_PRE_BLOCK - 1u) / rmk::V5_PRE_BLOCK, 1, n_frames),
-                       dim3(64u * rmk::V5_PRE_TILES), 16u + cull_bytes + (size_t)(L.n_cone + L.n_slab) * 8u, s, L, c->d_cost.p, n_tiles);
+                       dim3(64u * rmk::V5_PRE_TILES), rml::CullLds(L.n_cone, L.n_slab, true).bytes, s, L, c->d_cost.p, n_tiles);
     // RM_OPT_BALANCE = 3: the march kernel records how long every tile took; the next draw of the same shape
     // dispatches the longest first (consecutive frames of an interactive view or an orbit look alike)
     const uint32_t* prev = nullptr;
@@ -525,22 +519,17 @@ int launch_v5(rm_ctx* c, const RmLaunch& L, bool lds, uint32_t n_frames, hipStre
     // launch has fewer tiles than the chip has room for -- one GPU's share of a frame tiled over eight (DESIGN.md section 7:
     // 144 rows of 1080p: 0.095 -> 0.084 ms per frame; the whole frame: 0.546 -> 0.613).
     const size_t launch_tiles = (size_t)((L.W + 7u) / 8u) * ((L.rows + 7u) / 8u) * n_frames;
-    int wpt = c->waves_per_tile != 0 ? c->waves_per_tile : (launch_tiles <= 6000u ? 8 : 4);
-    const size_t cull_bytes = L.n_rec <= 256u ? (size_t)L.n_cone * 16u + (size_t)L.n_slab * 48u : 0u;  // tables exist up to 256 records
-    const size_t prog_bytes = (size_t)(L.n_rec + L.n_grp + c->decoded.tree.size()) * sizeof(RmRecord);  // (the tree table: at most 4 KB, when the interpreter uses it)
-    const size_t depth = std::max<size_t>(L.spill_depth + (c->decoded.tree.empty() ? 0u : 1u), L.n_mrec != 0u ? 2u * c->decoded.mat_spill_depth + 3u * c->decoded.mat_xform_depth : 0u);
-    const size_t per_wave = rmk::V5_WAVE_DWORDS * 4u + depth * 256u;
-    const size_t fixed = 4096u + cull_bytes + kV5TailBytes + (L.n_mrec != 0u ? 1024u : 0u);
+    const int wpt = c->waves_per_tile != 0 ? c->waves_per_tile : (launch_tiles <= 6000u ? 8 : 4);
     // A long program (rm_resize_command_buffer admits 64 KB of commands, ~2 700 leaves = 85 KB of records) does not fit
     // a workgroup's LDS next to the ray buffers: it is then read through the scalar cache instead (ProgSmem).
-    if (lds && fixed + prog_bytes + per_wave > 60u * 1024u) lds = false;
-    const size_t fixed_all = fixed + (lds ? prog_bytes : 0u);
-    while (wpt > 1 && fixed_all + (size_t)wpt * per_wave > 48u * 1024u) wpt /= 2;
-    switch (wpt) {
-    case 1: return launch_v5_w<1>(c, L, lds, n_frames, s);
-    case 2: return launch_v5_w<2>(c, L, lds, n_frames, s);
-    case 8: return launch_v5_w<8>(c, L, lds, n_frames, s);
-    default: return launch_v5_w<4>(c, L, lds, n_frames, s);
+    const RmDecoded& d = c->decoded;
+    const rml::MarchChoice m = rml::choose_march(lds, (uint32_t)wpt, L.spill_depth, L.n_mrec != 0u ? 2u * d.mat_spill_depth + 3u * d.mat_xform_depth : 0u,
+                                                 L.n_mrec != 0u, L.n_cone, L.n_slab, L.n_rec, L.n_grp, (uint32_t)d.tree.size());
+    switch (m.wpt) {
+    case 1: return launch_v5_w<1>(c, L, m.prog_in_lds, n_frames, s);
+    case 2: return launch_v5_w<2>(c, L, m.prog_in_lds, n_frames, s);
+    case 8: return launch_v5_w<8>(c, L, m.prog_in_lds, n_frames, s);
+    default: return launch_v5_w<4>(c, L, m.prog_in_lds, n_frames, s);
     }
 }
 
@@ -598,8 +587,8 @@ int launch(rm_ctx* c, const rm_uniforms* frames_dev, uint32_t n_frames, uint32_t
     if (int rc = time_begin(c, s)) return rc;
     {
         dim3 grid((W + 15u) / 16u, (rows + 15u) / 16u, n_frames);
-        size_t shmem = (size_t)L.n_rec * sizeof(RmRecord) + (size_t)L.spill_depth * 256u * sizeof(float);
-        if (shmem > 64u * 1024u) return fail(c, RM_ERR_TOO_LARGE, "program needs %zu bytes of LDS per workgroup", shmem);
+        const size_t shmem = rml::PixelLds(L.n_rec, L.spill_depth).bytes;
+        if (shmem > rml::kLdsLaunchLimit) return fail(c, RM_ERR_TOO_LARGE, "program needs %zu bytes of LDS per workgroup", shmem);
         hipLaunchKernelGGL(rmk::rm_render_pixel, grid, dim3(256), shmem, s, L);
     }
     if (int rc = time_end(c, s)) return rc;
@@ -2420,7 +2409,7 @@ RM_EXPORT int rm_selftest_cull_rays(rm_ctx* c, const float* origin, const float*
     if (int rc = probe_put(c, d_dirs, dirs, (size_t)n * 3u)) return rc;
     if (int rc = d_flags.reserve(c, n)) return rc;
     if (int rc = d_bound.reserve(c, n)) return rc;
-    const size_t shmem = 16u + (size_t)L.n_cone * 16u + (size_t)L.n_slab * 48u;
+    const size_t shmem = rml::CullLds(L.n_cone, L.n_slab, false).bytes;
     const rmk::V4 ro{origin[0], origin[1], origin[2], 1.0f};
     hipLaunchKernelGGL(rmk::rm_selftest_cull_rays_kernel, dim3((n + 63u) / 64u), dim3(64), shmem, c->stream, L, ro, d_dirs.p, n, d_flags.p, d_bound.p);
     if (int rc = probe_finish(c, "rm_selftest_cull_rays")) return rc;
@@ -2442,7 +2431,7 @@ RM_EXPORT int rm_selftest_cull_pixels(rm_ctx* c, uint32_t W, uint32_t H, const u
     DevBuf<float> d_out;
     if (int rc = probe_put(c, d_xy, xy, (size_t)n * 2u)) return rc;
     if (int rc = d_out.reserve(c, (size_t)n * 8u)) return rc;
-    const size_t shmem = 16u + (size_t)L.n_cone * 16u + (size_t)L.n_slab * 48u + (size_t)(L.n_cone + L.n_slab) * 8u;
+    const size_t shmem = rml::CullLds(L.n_cone, L.n_slab, true).bytes;
     hipLaunchKernelGGL(rmk::rm_selftest_cull_pixels_kernel, dim3((n + 63u) / 64u), dim3(64), shmem, c->stream, L, d_xy.p, n, d_out.p);
     if (int rc = probe_finish(c, "rm_selftest_cull_pixels")) return rc;
     HIP_TRY(c, hipMemcpy(out, d_out.p, (size_t)n * 32u, hipMemcpyDeviceToHost));
@@ -2464,7 +2453,7 @@ RM_EXPORT int rm_selftest_cull_tiles(rm_ctx* c, uint32_t W, uint32_t H, const ui
     DevBuf<float> d_out;
     if (int rc = probe_put(c, d_xy, xy, (size_t)n * 2u)) return rc;
     if (int rc = d_out.reserve(c, (size_t)n * 8u)) return rc;
-    const size_t shmem = 16u + (size_t)L.n_cone * 16u + (size_t)L.n_slab * 48u + (size_t)(L.n_cone + L.n_slab) * 8u;
+    const size_t shmem = rml::CullLds(L.n_cone, L.n_slab, true).bytes;
     hipLaunchKernelGGL(rmk::rm_selftest_cull_tiles_kernel, dim3((n + 63u) / 64u), dim3(64), shmem, c->stream, L, d_xy.p, n, d_out.p);
     if (int rc = probe_finish(c, "rm_selftest_cull_tiles")) return rc;
     HIP_TRY(c, hipMemcpy(out, d_out.p, (size_t)n * 32u, hipMemcpyDeviceToHost));

@@ -28,6 +28,7 @@
 // that scale).
 #pragma once
 #include "rm_interp.h"
+#include "rm_lds_layout.h"
 
 namespace rmk {
 
@@ -481,15 +482,11 @@ RM_DEV void spec_smooth_union4(LdsF r, const float (&a)[4], const float (&b)[4],
     }
 }
 
-constexpr uint32_t V5_RQ = 64u;   // ready buffer entries per wave (refilled only when empty)
-constexpr uint32_t V5_SQ = 64u;   // miss buffer entries per wave
-constexpr uint32_t V5_HQ = 128u;  // hit buffer entries per wave (64 are taken whenever 64 are waiting)
-// per wave: the three buffers, the screen coordinates of the tile's 8 columns and 8 rows, and LAST the partial normals of a tap phase
-// that takes its four taps one at a time or is followed by a material phase -- a generated kernel with the four-tap function and no
-// materials leaves those 768 bytes away (RmLaunch::wave_dwords): 25.6 -> 22.5 KB per workgroup for the metric scene, 7 instead of 6
-// workgroups per CU
-constexpr uint32_t V5_TN_DWORDS = 3u * 64u;
-constexpr uint32_t V5_WAVE_DWORDS = 4u * (V5_RQ + V5_SQ + V5_HQ) + 16u + V5_TN_DWORDS;
+// sizes of a march wave's ready / miss / hit buffers and of the tile's ray pool: rm_lds_layout.h
+using rml::V5_RQ; using rml::V5_SQ; using rml::V5_HQ; using rml::V5_POOL;
+// typed pointer to a byte offset of the workgroup's dynamic LDS (offsets: the layouts of rm_lds_layout.h)
+template <class T>
+RM_DEV T* lds_at(uint32_t* smem, uint32_t byte_offset) { return reinterpret_cast<T*>(reinterpret_cast<char*>(smem) + byte_offset); }
 
 // Miss-test tables of a program, built per workgroup in LDS from the decoded records (the
 // decoder stores each primitive's slot within its kind in RmRecord::p[6]):
@@ -505,6 +502,18 @@ struct CullTables {
     const uint32_t* veto;
     uint32_t n_cone, n_slab;
 };
+
+// Scale of the coordinates a ray from `ro` meets: what the margins of "Pruning" are multiples of ...
+RM_DEV float prune_scale_v5(const RmLaunch& L, const V4& ro) {
+    return L.scene_scale + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));
+}
+// ... and, with the blends' slack, what the bounds of "Miss test on lower bounds" are computed from.  The three terms are added
+// up in two orders, which round differently: the march kernel (and the self-test of its ray test) starts from its prune_scale,
+// the pre-pass (and the self-test of its pixel test) from the program's two terms.  Each verdict is pinned with its own sum.
+RM_DEV float bound_scale_march_v5(const RmLaunch& L, const V4& ro) { return prune_scale_v5(L, ro) + L.smooth_slack; }
+RM_DEV float bound_scale_prepass_v5(const RmLaunch& L, const V4& ro) {
+    return (L.scene_scale + L.smooth_slack) + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));
+}
 
 // `slack`: how far SmoothUnion operators can pull the tree value below the minimum over its leaves
 // (each lowers min(a,b) by at most k/4; nested operators add up).  0 for reference-only programs.
@@ -763,31 +772,35 @@ struct FalseTag { static constexpr bool value = false; };
 // all none of the other loops' code and registers (the lean kernel with all four kept 176 scalar registers spilled in vector lanes)
 template <class Prog, bool PROG_IN_LDS, int WPT, bool EXT, bool SPEC, bool MAT = false, int LOOP = 0>
 RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_tiles, uint32_t refill_min) {
-    constexpr uint32_t POOL = 1024u;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u, wave = tid >> 6;
-    // ---- LDS carve-up (all offsets multiples of 16 bytes) ----
-    float* res = reinterpret_cast<float*>(smem);                       // [1024] result code per ray (tile)
-    uint32_t* wbase = smem + POOL + wave * L.wave_dwords;             // this wave's buffers
-    uint32_t* rq_rid = wbase;                                          // ready rays (SoA): id, direction
-    float* rq_d = reinterpret_cast<float*>(wbase + V5_RQ);             // [3][V5_RQ]
-    uint32_t* sq_rid = wbase + 4u * V5_RQ;                             // rays that ended without a hit: id, direction
-    float* sq_v = reinterpret_cast<float*>(sq_rid + V5_SQ);            // [3][V5_SQ]
-    uint32_t* hq_rid = sq_rid + 4u * V5_SQ;                            // hits waiting for their normal: id, position
-    float* hq_v = reinterpret_cast<float*>(hq_rid + V5_HQ);            // [3][V5_HQ]
-    float* wxy = hq_v + 3u * V5_HQ;                                    // [16] pt_screen.x of the tile's 8 columns, .y of its 8 rows (wgsl:41-43)
-    float* tn = wxy + 16u;                                             // [3][64] partial normals of the running tap phase (absent when L.wave_dwords says so)
-    uint32_t* after = smem + POOL + WPT * L.wave_dwords;
+    // ---- LDS carve-up: rml::MarchLds (rm_lds_layout.h), from which the launch is sized.  Everything fixed at compile time is
+    // taken from it; the offsets that depend on the launch are the same sums, written out on L's fields: through the
+    // layout object (by value, inlined) the tree interpreters and the scalar-cache kernels came out with one or two more
+    // scalar registers spilled (profiles/r15_lds_layout_kernel_resources.txt).  tests/cpp/lds_layout_check.cpp holds these sums
+    // against the layout over every size a launch can have. ----
+    typedef rml::MarchWaveLds WL;
+    float* res = reinterpret_cast<float*>(smem);                       // [V5_POOL] result code per ray (tile)
+    uint32_t* wbase = smem + V5_POOL + wave * L.wave_dwords;           // this wave's buffers
+    uint32_t* rq_rid = wbase + WL::rq_rid / 4u;                        // ready rays (SoA): id, direction
+    float* rq_d = reinterpret_cast<float*>(wbase + WL::rq_d / 4u);     // [3][V5_RQ]
+    uint32_t* sq_rid = wbase + WL::sq_rid / 4u;                        // rays that ended without a hit: id, direction
+    float* sq_v = reinterpret_cast<float*>(wbase + WL::sq_v / 4u);     // [3][V5_SQ]
+    uint32_t* hq_rid = wbase + WL::hq_rid / 4u;                        // hits waiting for their normal: id, position
+    float* hq_v = reinterpret_cast<float*>(wbase + WL::hq_v / 4u);     // [3][V5_HQ]
+    float* wxy = reinterpret_cast<float*>(wbase + WL::wxy / 4u);       // [16] pt_screen.x of the tile's 8 columns, .y of its 8 rows (wgsl:41-43)
+    float* tn = reinterpret_cast<float*>(wbase + WL::tn / 4u);         // [3][64] partial normals of the running tap phase (absent when L.wave_dwords says so)
+    uint32_t* after = smem + V5_POOL + WPT * L.wave_dwords;            // MarchLds::spill
     float* spill = reinterpret_cast<float*>(after) + wave * (L.spill_depth * 64u) + lane;  // [WPT][depth][64]
     float4* t_cone = reinterpret_cast<float4*>(after + WPT * L.spill_depth * 64u);         // [n_cone]
-    float4* t_slab = t_cone + L.n_cone;                                                     // [2 * n_slab]
-    uint32_t* lprog = reinterpret_cast<uint32_t*>(t_slab + 3u * L.n_slab);
-    uint32_t* s_next = lprog + (PROG_IN_LDS ? (L.n_rec + L.n_grp + L.n_tree) * 8u : 0u);  // shared pool cursor
+    float4* t_slab = t_cone + L.n_cone;                                                     // [3 * n_slab]
+    uint32_t* lprog = reinterpret_cast<uint32_t*>(t_slab + 3u * L.n_slab);                  // PROG_IN_LDS: records, unit table, tree table
+    uint32_t* s_next = lprog + (PROG_IN_LDS ? (L.n_rec + L.n_grp + L.n_tree) * 8u : 0u);  // MarchLds::ctl: shared pool cursor
     uint32_t* s_tile = s_next + 1;                                     // work-list slot of the current tile
     uint32_t* s_veto = s_next + 2;
-    float* s_off = reinterpret_cast<float*>(s_next + 4);               // [16][2] screen offsets of the AA samples (wgsl:47-53)
-    uint8_t* rmat = reinterpret_cast<uint8_t*>(s_next + 36);           // MAT, tagged program: [1024] material per ray
+    float* s_off = reinterpret_cast<float*>(s_next + rml::kMarchCtlBytes / 4u);  // [16][2] screen offsets of the AA samples (wgsl:47-53)
+    uint8_t* rmat = reinterpret_cast<uint8_t*>(s_next) + rml::kMarchCtlBytes + rml::kMarchOffBytes;  // MAT, tagged program: [V5_POOL] material per ray
     const bool tagged = MAT && L.n_mrec != 0u;                         // wave-uniform
     constexpr uint32_t TAP_IDLE = MAT ? 5u : 4u;                       // tap_t: 0..3 normal taps, 4 (MAT) material, else idle
     const CullTables cullt{t_cone, t_slab, s_veto, L.n_cone, L.n_slab};
@@ -800,6 +813,8 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
     const uint32_t n_active = counters[0];
 
     const V4 ro = matvec(u.inv_view, 0.0f, 0.0f, 0.0f, 1.0f);  // wgsl:39-40
+    // (prune_scale_v5 and bound_scale_march_v5, written out: called here, even with their operands by value, they moved the
+    // scalar spill counts of these kernels, some up)
     const float prune_scale = L.scene_scale + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));  // "Pruning"
     const float eps = 0.0001f;                                    // wgsl:136
     if (PROG_IN_LDS) {
@@ -809,6 +824,8 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
         stage_units(lprog + 8u * L.n_rec, L.prog + L.n_rec, L.n_grp, tid, 64u * WPT);  // (7 of a unit record's 8 dwords: it fits the same space)
         if constexpr (!SPEC) stage_tree(lprog + 8u * (L.n_rec + L.n_grp), L.prog + L.n_rec + L.n_grp, L.n_tree, tid, 64u * WPT);
     }
+    // (the steps of stage_cull_tables, written out: the program's copy shares the first barrier, the tile loop's first barrier
+    // closes the table build, and there are no aux rows)
     if (tid == 0u) *s_veto = 0u;
     if (tid < 16u) sample_offset(u, tid >> 2, tid & 3u, s_off[2u * tid], s_off[2u * tid + 1u]);  // two divisions per sample, once
     __syncthreads();
@@ -989,7 +1006,7 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
                         uint32_t base = 0u;
                         if (lane == 0u) base = atomicAdd(s_next, 64u);
                         base = __builtin_amdgcn_readfirstlane(base);
-                        if (base >= POOL) { pool_open = false; continue; }
+                        if (base >= V5_POOL) { pool_open = false; continue; }
                         n_prod++;
                         // batch -> block of the 4x4 blocks of the tile: the corners first, then the centre (see test_rays below)
                         const uint32_t blk = (uint32_t)(0xEDB87421A965FC30ull >> (4u * (base >> 6))) & 15u;
@@ -1591,13 +1608,34 @@ RM_DEV uint32_t tile_verdict_v5(const RmLaunch& L, const rm_uniforms& u, const V
     return (clear ? V5_TILE_CLEAR : 0u) | (sky ? V5_TILE_SKY : 0u) | (cell ? V5_TILE_CELL | (code ? V5_TILE_CODE : 0u) : 0u);
 }
 
+// The miss-test tables of the launch's program for rays from `ro`, staged in the workgroup's dynamic LDS (rml::CullLds) by all
+// its n_threads threads; ends with a barrier.  The pre-pass and the culling self-tests stage them through this one function.
+//   off   nullptr, or [16][2]: the screen offsets of the AA samples under `u` are computed alongside
+//   aux   nullptr, or where to return the rows [n_cone + n_slab] (|m|, |m| + bounding radius) of the pixel and tile tests
+RM_DEV CullTables stage_cull_tables(const RmLaunch& L, const V4& ro, uint32_t* smem, const rm_uniforms* u, float* off, const float2** aux,
+                                    uint32_t tid, uint32_t n_threads) {
+    const rml::CullLds lds(L.n_cone, L.n_slab, aux != nullptr);
+    uint32_t* s_veto = lds_at<uint32_t>(smem, lds.veto);
+    float4* t_cone = lds_at<float4>(smem, lds.cone);
+    float4* t_slab = lds_at<float4>(smem, lds.slab);
+    const bool tables = (L.flags & 1u) != 0u;
+    if (tid == 0u) *s_veto = 0u;
+    if (off && tid < 16u) sample_offset(*u, tid >> 2, tid & 3u, off[2u * tid], off[2u * tid + 1u]);
+    __syncthreads();
+    if (tables)
+        for (uint32_t k = tid; k < L.n_rec; k += n_threads) cull_build_v5(L.prog[k], ro, L.min_dist, L.smooth_slack, t_cone, t_slab, s_veto, L.bounds);
+    __syncthreads();
+    if (aux) {
+        float2* t_aux = lds_at<float2>(smem, lds.aux);
+        if (tables) pixel_aux_build_v5(t_cone, t_slab, L.n_cone, L.n_slab, t_aux, tid, n_threads);
+        __syncthreads();
+        *aux = t_aux;
+    }
+    return CullTables{t_cone, t_slab, s_veto, L.n_cone, L.n_slab};
+}
+
 __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, uint32_t* cost, uint32_t n_tiles) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    uint32_t* s_veto = smem;
-    float4* t_cone = reinterpret_cast<float4*>(smem + 4u);
-    float4* t_slab = t_cone + L.n_cone;
-    float2* t_aux = reinterpret_cast<float2*>(t_slab + 3u * L.n_slab);  // [n_cone + n_slab] (|m|, |m| + bounding radius)
-    const CullTables cullt{t_cone, t_slab, s_veto, L.n_cone, L.n_slab};
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     rm_uniforms u = L.u;
     if (L.frames) u = L.frames[blockIdx.z];
@@ -1609,15 +1647,10 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
     __shared__ uint8_t s_list[V5_PRE_TILES][64];
     __shared__ uint8_t s_verdict[V5_PRE_BLOCK];  // per tile of the block: tile_verdict_v5 if it settles the tile, else 0
     __shared__ uint32_t s_claim;                 // next tile of the block to hand out
-    if (tid == 0u) { *s_veto = 0u; s_claim = 0u; }
-    if (tid < 16u) sample_offset(u, tid >> 2, tid & 3u, s_off[2u * tid], s_off[2u * tid + 1u]);
-    __syncthreads();
-    if (tables)
-        for (uint32_t k = tid; k < L.n_rec; k += 64u * V5_PRE_TILES)
-            cull_build_v5(L.prog[k], ro, L.min_dist, L.smooth_slack, t_cone, t_slab, s_veto, L.bounds);
-    __syncthreads();
-    if (tables) pixel_aux_build_v5(t_cone, t_slab, L.n_cone, L.n_slab, t_aux, tid, 64u * V5_PRE_TILES);
-    __syncthreads();
+    if (tid == 0u) s_claim = 0u;
+    const float2* t_aux;
+    const CullTables cullt = stage_cull_tables(L, ro, smem, &u, s_off, &t_aux, tid, 64u * V5_PRE_TILES);
+    const uint32_t* s_veto = cullt.veto;
     const uint32_t tiles_x = (L.W + 7u) / 8u;
     const float cone_noise = cone_noise_v5(u, ro, L.W, L.H);
   auto do_tile = [&](uint32_t tile) {  // (whole wave; no barrier inside)
@@ -1647,14 +1680,10 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
         clear = pixel_misses_scene_v5(cullt, t_aux, mp, mv, s_off, ro, sx, sy, cone_noise, cone, corner);
         // a program that blends: the pixels the inflated bounds could not clear get the program run on lower bounds of its
         // leaves over the pixel's cone ("Miss test on lower bounds"; the march kernel repeats it per ray for what is left)
-        const float bound_scale = (L.scene_scale + L.smooth_slack) + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));
+        const float bound_scale = bound_scale_prepass_v5(L, ro);
         if ((L.flags & 32u) && (*s_veto & 1u) == 0u && bound_scale < 1.0e12f && __ballot(!clear && cone[3] == cone[3]) != 0ull) {
-            auto load_record = [&](uint32_t i, uint32_t& op, float (&p)[7]) {
-                const RmRecord& r = L.prog[i];  // wave-uniform address: scalar loads
-                op = r.op;
-#pragma unroll
-                for (int k = 0; k < 7; k++) p[k] = r.p[k];
-            };
+            const ProgSmem prog{L.prog};  // wave-uniform addresses: scalar loads
+            auto load_record = [&](uint32_t i, uint32_t& op, float (&p)[7]) { prog.load(i, op, p); };
             const bool by_bounds = ray_misses_by_bounds_v5<true>(load_record, L.n_rec, ro, cone[0], cone[1], cone[2], L.min_dist, bound_scale, cone[3]);
             clear = clear || (cone[3] == cone[3] && by_bounds);
         }
@@ -1884,43 +1913,30 @@ __global__ __launch_bounds__(1024) void rm_tile_sort_v5(RmLaunch L, const uint32
 
 // ---- Self-tests of the culling decisions (rm_selftest_cull_*; tests/test_gpu_cull_bounds.py) ------------------------------------
 // The device functions above on inputs the caller chooses, with the launch a draw of the context's program would get and the
-// tables staged in LDS the way rm_render_v5_body and rm_tile_pre_v5 stage them.  (They stand here, not next to
+// tables staged in LDS by the function that stages them for rm_tile_pre_v5, stage_cull_tables.  (They stand here, not next to
 // rm_selftest_wave_kernel: they need the functions defined since.)
 #if !defined(RM_JIT_TU)
-// LDS: {veto, 3 x pad}, cone[n_cone], slab[3 n_slab], aux[n_cone + n_slab] (the pixel probe).  One wave per workgroup.
+// LDS: rml::CullLds, with the aux rows for the pixel and tile probes.  One wave per workgroup.
 // Rays: out_flags[i] bit 0 the verdict of ray_misses_scene_v5 (false without culling), bit 1 the tables were usable (culling on, no
 // veto), bit 2 the walk on lower bounds applies, bit 3 its verdict, bits 8.. the veto word; out_bound[i] the walk's bound (NaN
 // when it does not apply).
 __global__ __launch_bounds__(64) void rm_selftest_cull_rays_kernel(RmLaunch L, V4 ro, const float* dirs, uint32_t n, uint32_t* out_flags,
                                                                    float* out_bound) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    uint32_t* s_veto = smem;
-    float4* t_cone = reinterpret_cast<float4*>(smem + 4u);
-    float4* t_slab = t_cone + L.n_cone;
-    const CullTables cullt{t_cone, t_slab, s_veto, L.n_cone, L.n_slab};
     const uint32_t tid = threadIdx.x;
-    if (tid == 0u) *s_veto = 0u;
-    __syncthreads();
     const bool tables = (L.flags & 1u) != 0u;
-    if (tables)
-        for (uint32_t k = tid; k < L.n_rec; k += 64u) cull_build_v5(L.prog[k], ro, L.min_dist, L.smooth_slack, t_cone, t_slab, s_veto, L.bounds);
-    __syncthreads();
+    const CullTables cullt = stage_cull_tables(L, ro, smem, nullptr, nullptr, nullptr, tid, 64u);
     const uint32_t i = blockIdx.x * 64u + tid, j = i < n ? i : n - 1u;
     const float gx = dirs[3u * j], gy = dirs[3u * j + 1u], gz = dirs[3u * j + 2u];
-    const uint32_t veto = *s_veto;
+    const uint32_t veto = *cullt.veto;
     const bool clear = tables && ray_misses_scene_v5(cullt, gx, gy, gz);
-    const float prune_scale = L.scene_scale + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));
-    const float bound_scale = prune_scale + L.smooth_slack;  // (as rm_render_v5_body adds them up)
+    const float bound_scale = bound_scale_march_v5(L, ro);
     const bool walk = tables && (L.flags & 32u) && (veto & 1u) == 0u && bound_scale < 1.0e12f;
     float acc = __uint_as_float(0x7FC00000u);
     bool by_bounds = false;
     if (walk) {
-        auto load_record = [&](uint32_t r, uint32_t& op, float (&p)[7]) {
-            const RmRecord& rec = L.prog[r];  // wave-uniform address: scalar loads
-            op = rec.op;
-#pragma unroll
-            for (int k = 0; k < 7; k++) p[k] = rec.p[k];
-        };
+        const ProgSmem prog{L.prog};  // wave-uniform addresses: scalar loads
+        auto load_record = [&](uint32_t r, uint32_t& op, float (&p)[7]) { prog.load(r, op, p); };
         acc = ray_bound_v5<false>(load_record, L.n_rec, ro, gx, gy, gz, bound_scale);
         by_bounds = ray_misses_by_bounds_v5<false>(load_record, L.n_rec, ro, gx, gy, gz, L.min_dist, bound_scale);
     }
@@ -1934,24 +1950,13 @@ __global__ __launch_bounds__(64) void rm_selftest_cull_rays_kernel(RmLaunch L, V
 // pixel_misses_scene_v5, bit 1 the tables were usable, bit 2 the CONE walk applies, bit 3 its verdict; [6], [7] zero.
 __global__ __launch_bounds__(64) void rm_selftest_cull_pixels_kernel(RmLaunch L, const uint32_t* xy, uint32_t n, float* out) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    uint32_t* s_veto = smem;
-    float4* t_cone = reinterpret_cast<float4*>(smem + 4u);
-    float4* t_slab = t_cone + L.n_cone;
-    float2* t_aux = reinterpret_cast<float2*>(t_slab + 3u * L.n_slab);
     __shared__ float s_off[32];
-    const CullTables cullt{t_cone, t_slab, s_veto, L.n_cone, L.n_slab};
     const uint32_t tid = threadIdx.x;
     const rm_uniforms u = L.u;
     const V4 ro = matvec(u.inv_view, 0.0f, 0.0f, 0.0f, 1.0f);
     const bool tables = (L.flags & 1u) != 0u;
-    if (tid == 0u) *s_veto = 0u;
-    if (tid < 16u) sample_offset(u, tid >> 2, tid & 3u, s_off[2u * tid], s_off[2u * tid + 1u]);
-    __syncthreads();
-    if (tables)
-        for (uint32_t k = tid; k < L.n_rec; k += 64u) cull_build_v5(L.prog[k], ro, L.min_dist, L.smooth_slack, t_cone, t_slab, s_veto, L.bounds);
-    __syncthreads();
-    if (tables) pixel_aux_build_v5(t_cone, t_slab, L.n_cone, L.n_slab, t_aux, tid, 64u);
-    __syncthreads();
+    const float2* t_aux;
+    const CullTables cullt = stage_cull_tables(L, ro, smem, &u, s_off, &t_aux, tid, 64u);
     const uint32_t i = blockIdx.x * 64u + tid, j = i < n ? i : n - 1u;
     const float sx = screen_x(xy[2u * j], L.W), sy = screen_y(rm_global_row(L, xy[2u * j + 1u]), L.H);
     float mp[16], mv[16];
@@ -1960,18 +1965,14 @@ __global__ __launch_bounds__(64) void rm_selftest_cull_pixels_kernel(RmLaunch L,
     const float nan = __uint_as_float(0x7FC00000u), cone_noise = cone_noise_v5(u, ro, L.W, L.H);
     float cone[4] = {nan, nan, nan, nan}, corner[4][3], acc = nan;
     bool clear = false, walk = false, by_bounds = false;
-    const uint32_t veto = *s_veto;
+    const uint32_t veto = *cullt.veto;
     if (tables) {
         clear = pixel_misses_scene_v5(cullt, t_aux, mp, mv, s_off, ro, sx, sy, cone_noise, cone, corner);
-        const float bound_scale = (L.scene_scale + L.smooth_slack) + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));  // (as rm_tile_pre_v5)
+        const float bound_scale = bound_scale_prepass_v5(L, ro);
         walk = (L.flags & 32u) && (veto & 1u) == 0u && bound_scale < 1.0e12f && cone[3] == cone[3];
         if (__ballot(walk) != 0ull) {
-            auto load_record = [&](uint32_t r, uint32_t& op, float (&p)[7]) {
-                const RmRecord& rec = L.prog[r];
-                op = rec.op;
-#pragma unroll
-                for (int k = 0; k < 7; k++) p[k] = rec.p[k];
-            };
+            const ProgSmem prog{L.prog};
+            auto load_record = [&](uint32_t r, uint32_t& op, float (&p)[7]) { prog.load(r, op, p); };
             const float b = ray_bound_v5<true>(load_record, L.n_rec, ro, cone[0], cone[1], cone[2], bound_scale, cone[3]);
             const bool v = ray_misses_by_bounds_v5<true>(load_record, L.n_rec, ro, cone[0], cone[1], cone[2], L.min_dist, bound_scale, cone[3]);
             if (walk) { acc = b; by_bounds = v; }
@@ -1990,24 +1991,13 @@ __global__ __launch_bounds__(64) void rm_selftest_cull_pixels_kernel(RmLaunch L,
 // are in one checker cell, bit 3 the tables were usable; [6], [7] zero.
 __global__ __launch_bounds__(64) void rm_selftest_cull_tiles_kernel(RmLaunch L, const uint32_t* xy, uint32_t n, float* out) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    uint32_t* s_veto = smem;
-    float4* t_cone = reinterpret_cast<float4*>(smem + 4u);
-    float4* t_slab = t_cone + L.n_cone;
-    float2* t_aux = reinterpret_cast<float2*>(t_slab + 3u * L.n_slab);
     __shared__ float s_off[32];
-    const CullTables cullt{t_cone, t_slab, s_veto, L.n_cone, L.n_slab};
     const uint32_t tid = threadIdx.x;
     const rm_uniforms u = L.u;
     const V4 ro = matvec(u.inv_view, 0.0f, 0.0f, 0.0f, 1.0f);
     const bool tables = (L.flags & 1u) != 0u;
-    if (tid == 0u) *s_veto = 0u;
-    if (tid < 16u) sample_offset(u, tid >> 2, tid & 3u, s_off[2u * tid], s_off[2u * tid + 1u]);
-    __syncthreads();
-    if (tables)
-        for (uint32_t k = tid; k < L.n_rec; k += 64u) cull_build_v5(L.prog[k], ro, L.min_dist, L.smooth_slack, t_cone, t_slab, s_veto, L.bounds);
-    __syncthreads();
-    if (tables) pixel_aux_build_v5(t_cone, t_slab, L.n_cone, L.n_slab, t_aux, tid, 64u);
-    __syncthreads();
+    const float2* t_aux;
+    const CullTables cullt = stage_cull_tables(L, ro, smem, &u, s_off, &t_aux, tid, 64u);
     const uint32_t i = blockIdx.x * 64u + tid, j = i < n ? i : n - 1u;
     float cone[4];
     const uint32_t v = tile_verdict_v5(L, u, ro, cullt, t_aux, s_off, tables, L.max_iter == 0u, xy[2u * j], xy[2u * j + 1u], cone);
@@ -2016,7 +2006,7 @@ __global__ __launch_bounds__(64) void rm_selftest_cull_tiles_kernel(RmLaunch L, 
         o[0] = cone[0]; o[1] = cone[1]; o[2] = cone[2]; o[3] = cone[3];
         o[4] = (v & V5_TILE_CODE) ? 1.0f : 0.0f;
         o[5] = __uint_as_float(((v & V5_TILE_CLEAR) ? 1u : 0u) | ((v & V5_TILE_SKY) ? 2u : 0u) | ((v & V5_TILE_CELL) ? 4u : 0u) |
-                               ((tables && *s_veto == 0u) ? 8u : 0u));
+                               ((tables && *cullt.veto == 0u) ? 8u : 0u));
         o[6] = 0.0f; o[7] = 0.0f;
     }
 }
@@ -2031,7 +2021,7 @@ __global__ __launch_bounds__(64) void rm_selftest_cull_waves_kernel(RmLaunch L, 
     const float x = pos[(3u * w) * 64u + lane], y = pos[(3u * w + 1u) * 64u + lane], z = pos[(3u * w + 2u) * 64u + lane];
     const unsigned long long live_mask = live[w];
     const bool is_live = ((live_mask >> lane) & 1ull) != 0ull;
-    const float prune_scale = L.scene_scale + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));
+    const float prune_scale = prune_scale_v5(L, ro);
     unsigned long long need;
     if (L.unit_mode == RM_UNITS_LATTICE) need = wave_cull_lattice(smem, L.n_grp, x, y, z, thr[64u * w + lane], is_live, live_mask);
     else need = wave_cull_blend(smem, L.n_grp, L.unit_kmax, x, y, z, extra_margin, prune_scale, is_live, live_mask);

@@ -10,6 +10,7 @@
 #endif
 
 #include "rm_device.h"
+#include "rm_lds_layout.h"
 
 #define RM_DEV __device__ __forceinline__
 
@@ -208,14 +209,15 @@ RM_DEV float map_scene(const Prog& prog, uint32_t n_rec, const SpillLds& st, flo
 __global__ __launch_bounds__(256) void rm_render_pixel(RmLaunch L) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const uint32_t tid = threadIdx.x;
-    const uint32_t prog_dwords = L.n_rec * 8u;
+    const rml::PixelLds lds(L.n_rec, L.spill_depth);
+    uint32_t* lprog = smem + lds.prog / 4u;
     {
         const uint32_t* src = reinterpret_cast<const uint32_t*>(L.prog);
-        for (uint32_t k = tid; k < prog_dwords; k += 256u) smem[k] = src[k];
+        for (uint32_t k = tid; k < L.n_rec * 8u; k += 256u) lprog[k] = src[k];
     }
     __syncthreads();
-    ProgLds prog{smem};
-    SpillLds st{reinterpret_cast<float*>(smem + prog_dwords) + tid, 256u};
+    ProgLds prog{lprog};
+    SpillLds st{reinterpret_cast<float*>(smem + lds.spill / 4u) + tid, 256u};
 
     rm_uniforms u = L.u;
     if (L.frames) u = L.frames[blockIdx.z];  // wave-uniform: stays in SGPRs

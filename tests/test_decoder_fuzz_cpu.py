@@ -88,3 +88,35 @@ def test_scratch_layouts_of_the_host_abi_match_the_hand_written_offsets(tmp_path
                          env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
     assert "abi layout ok" in run.stdout
+
+
+def test_lds_layouts_match_the_hand_written_offsets_and_the_boundary_frames_straddle_their_edges(tmp_path, oracle):
+    """tests/cpp/lds_layout_check.cpp: rm_lds_layout.h -- where the arrays of the kernels' dynamic LDS lie (the miss-test tables
+    of the pre-pass and the culling self-tests, the march workgroup, kernel v1) -- against the sums the host and the kernels
+    wrote out before it existed, which the march kernel still writes out for its launch-dependent offsets: regions in order,
+    16-byte aligned, disjoint, ending at the total; the choice of waves per tile and program placement against launch_v5's
+    former formulas, and never below the launch that follows.  The programs of test_gpu_parity.LAYOUT_BOUNDARY_FRAMES go
+    through the decoder and the chooser: each must come out with the waves per tile the list gives it, so that consecutive
+    entries do straddle an edge of the layout."""
+    cxx = os.environ.get("CXX", "g++")
+    if not shutil.which(cxx):
+        pytest.skip("no C++ compiler")
+    import scenes
+    from test_gpu_parity import LAYOUT_BOUNDARY_FRAMES
+    for (n0, wpt0, _), (n1, wpt1, _) in zip(LAYOUT_BOUNDARY_FRAMES[0::2], LAYOUT_BOUNDARY_FRAMES[1::2]):
+        assert n1 == n0 + 1 and wpt1 < wpt0
+    progs = tmp_path / "boundary_programs.txt"
+    with open(progs, "w") as f:
+        for n, wpt, in_lds in LAYOUT_BOUNDARY_FRAMES:
+            cc, w = oracle.serialize(*scenes.right_deep(n))
+            f.write("%d %d %d %d %d %s\n" % (n, wpt, in_lds, cc, len(w), " ".join(str(int(x)) for x in w)))
+    exe = tmp_path / "lds_layout_check"
+    build = subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
+                            "-fno-sanitize-recover=undefined", "-I", os.path.join(ROOT, "include"),
+                            "-I", os.path.join(ROOT, "ray-marching_amd", "csrc"), "-o", str(exe),
+                            os.path.join(ROOT, "tests", "cpp", "lds_layout_check.cpp")], capture_output=True, text=True, timeout=300)
+    assert build.returncode == 0, build.stderr[-3000:]
+    run = subprocess.run([str(exe), str(progs)], capture_output=True, text=True, timeout=600,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert run.returncode == 0, (run.stdout + run.stderr)[-3000:]
+    assert "lds layout ok" in run.stdout and "%d programs)" % len(LAYOUT_BOUNDARY_FRAMES) in run.stdout

@@ -112,6 +112,34 @@ def test_deep_stack_programs(res, oracle, kernel):
         assert_same(res.draw(W, H), oracle.render(u, lim, cc, w, W, H, threads=4))
 
 
+# scenes.right_deep(n) drawn as a 24 x 16 frame (six tiles: the launch starts from eight waves per tile), as (n, waves per tile,
+# program in LDS): the last n before and the first n after each decision of rml::choose_march (rm_lds_layout.h) such a program
+# reaches -- eight waves to four, four to two.  The decoder admits a value stack of 32, and right_deep(32) fits a two-wave
+# workgroup with 13 KB to spare: two waves to one, LDS to scalar cache and the 64 KB launch limit lie beyond every right_deep(n)
+# that decodes, so no frame stands at them.  tests/test_decoder_fuzz_cpu.py hands these programs to tests/cpp/lds_layout_check.cpp,
+# which holds each entry against the layout: a change of a buffer size that moves an edge fails there.
+LAYOUT_BOUNDARY_FRAMES = [(3, 8, 1), (4, 4, 1), (22, 4, 1), (23, 2, 1)]
+
+
+def test_frames_at_the_lds_layout_decision_boundaries(res, oracle):
+    """The interpreter draws every entry of LAYOUT_BOUNDARY_FRAMES as the oracle does; the entries of at most 16 leaves again
+    under the generated kernel, whose workgroup has no spill columns."""
+    W, H = 24, 16
+    lim = (0.01, 100.0, 48)
+    res.resize_command_buffer(4096)
+    res.set_option(_ffi.RM_OPT_WAVES_PER_TILE, 0)
+    for specialize in (0, 2):
+        for n, _wpt, _in_lds in LAYOUT_BOUNDARY_FRAMES:
+            if specialize == 2 and n > 16:
+                continue
+            cc, w, u = oracle_case(oracle, scenes.right_deep(n), W, H, None)
+            setup(res, cc=cc, words=w, u=_ffi.Uniforms.from_buffer_copy(bytes(u)), limits=lim, kernel=_ffi.RM_KERNEL_V5_LDS)
+            res.set_option(_ffi.RM_OPT_SPECIALIZE, specialize)
+            assert_same(res.draw(W, H), oracle.render(u, lim, cc, w, W, H, threads=4))
+            assert res.info(_ffi.RM_INFO_SPECIALIZED) == (1 if specialize else 0), n
+    res.set_option(_ffi.RM_OPT_SPECIALIZE, 0)
+
+
 @pytest.mark.parametrize("kernel", [_ffi.RM_KERNEL_V5, _ffi.RM_KERNEL_V5_LDS], ids=["v5", "v5_lds"])
 def test_interpreter_record_loops(res, oracle, kernel):
     """Which record loop the interpreter kernels take (RM_INFO_INTERPRETER_LOOP) and that each renders the oracle's image:
