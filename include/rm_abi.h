@@ -640,8 +640,9 @@ int rm_selftest_wave(rm_ctx* ctx, const float* in, uint32_t n_waves, float* out)
  *   classifies a whole tile from the rectangle of its 32 x 32 sample positions.  out[8 i + ..]: 0..2 the centre direction and 3 the
  *   radius rho of the cone of those directions (NaN: no usable cone), 4 the checker bit of a one-cell tile (else 0), 5 flags as
  *   the bits of an integer (bit 0 the tables clear the tile, bit 1 every sample is sky, bit 2 every sample falls in one checker
- *   cell, bit 3 the tables were usable), 6..7 zero.  The pre-pass settles a tile with bit 0 and bit 1 or 2 without looking at
- *   its pixels.
+ *   cell, bit 3 the tables were usable), 6 the tile's primitive mask as the bits of an integer (bit k: the tile's cone does not
+ *   clear miss-test entry k, spheres first, then boxes; all ones when the mask is not in use), 7 the number of those entries,
+ *   likewise.  The pre-pass settles a tile with bit 0 and bit 1 or 2 without looking at its pixels.
  * rm_selftest_cull_waves: n_waves waves of 64 positions, pos[(3 w + k) * 64 + lane] (k = x, y, z), thresholds thr[64 w + lane]
  *   and live-lane masks live[w] (not 0); camera position origin[3].  out_masks[w]: the units wave-level culling keeps -- the
  *   threshold rule (lattice programs; extra_margin unused) or the rules of a blending chain (thr unused), by the program;

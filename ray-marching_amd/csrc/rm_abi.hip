@@ -174,6 +174,7 @@ struct rm_ctx {
     DevBuf<unsigned long long> d_stats;
     size_t stats_valid_bytes = 0;
     DevBuf<uint32_t> d_cost, d_order;  // per-tile cost estimates / dispatch order of the balance pre-pass
+    DevBuf<uint32_t> d_masks;          // per-tile primitive masks of the pre-pass, for the march kernel's ray tests
     DevBuf<uint32_t> d_counters;       // v5: {work-list length, cursor} per frame
     DevBuf<uint32_t> d_measured;       // v5, RM_OPT_BALANCE = 3: per-tile durations of the previous draw of the same shape
     uint64_t measured_shape = 0;       // hash of (W, rows, strips, frames) the measurements belong to; 0 = none yet
@@ -443,9 +444,10 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
     // pre-pass buffers: cost + work list per tile, {count, cursor} per frame
     if (int rc = c->d_cost.reserve(c, (size_t)n_tiles * n_frames)) return rc;
     if (int rc = c->d_order.reserve(c, (size_t)n_tiles * n_frames)) return rc;
+    if (int rc = c->d_masks.reserve(c, (size_t)n_tiles * n_frames)) return rc;
     if (int rc = c->d_counters.reserve(c, (size_t)n_frames * 4u)) return rc;
     hipLaunchKernelGGL(rmk::rm_tile_pre_v5, dim3((n_tiles + rmk::V5_PRE_BLOCK - 1u) / rmk::V5_PRE_BLOCK, 1, n_frames),
-                       dim3(64u * rmk::V5_PRE_TILES), rml::CullLds(L.n_cone, L.n_slab, true).bytes, s, L, c->d_cost.p, n_tiles);
+                       dim3(64u * rmk::V5_PRE_TILES), rml::CullLds(L.n_cone, L.n_slab, true).bytes, s, L, c->d_cost.p, c->d_masks.p, n_tiles);
     // RM_OPT_BALANCE = 3: the march kernel records how long every tile took; the next draw of the same shape
     // dispatches the longest first (consecutive frames of an interactive view or an orbit look alike)
     const uint32_t* prev = nullptr;
@@ -465,7 +467,7 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
     }
     hipLaunchKernelGGL(rmk::rm_tile_sort_v5, dim3(n_frames), dim3(1024), 0, s, L, c->d_cost.p, c->d_order.p, c->d_counters.p,
                        n_tiles, (uint32_t)c->balance, prev);
-    rmk::V5Work work{c->d_order.p, c->d_counters.p, measured};
+    rmk::V5Work work{c->d_order.p, c->d_counters.p, measured, c->d_masks.p};
     // persistent grid: about as many workgroups as fit the chip (LDS, 32 waves per CU), never more than tiles
     uint32_t per_cu = (uint32_t)std::min<size_t>(32u / WPT, (160u * 1024u) / shmem);
     if (per_cu < 1u) per_cu = 1u;

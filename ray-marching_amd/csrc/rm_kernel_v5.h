@@ -577,33 +577,62 @@ RM_DEV void cull_build_v5(const RmRecord& rec, const V4& ro, float min_dist, flo
     if (!finite || !(slack < inf)) atomicOr(veto, 1u);  // bit 0: non-finite data, nothing may be culled by any test
 }
 
-// true iff the half-line o + t d (t >= 0) provably stays clear of every primitive's margin zone.
-RM_DEV bool ray_misses_scene_v5(const CullTables& T, float dx, float dy, float dz) {
+// Per-tile primitive mask (the pre-pass's tile_touch_mask_v5 makes it, one word per tile): bit k set for cone entry k, bit
+// n_cone + k for slab entry k, iff the tile's cone does not provably clear that entry -- the tile test has proven that every
+// sample ray of the tile clears each entry whose bit is 0, so a ray or a pixel of the tile tests the set bits only.  All ones:
+// nothing is known about the tile (more than 32 entries, tables or cone unusable, rows not consecutive) and every entry is tested,
+// by the loops over the whole tables.  A mask in use belongs to a program of at most 32 entries and never has a bit at or above
+// n_cone + n_slab, so it is never all ones unless all 32 entries are touched -- and then both ways test the same entries.
+// (Walking the set bits with s_ff1 costs nothing per cleared entry; a bit test per entry inside the old loops gave +0.6 % of
+// headline where this form gives +2 %: profiles/r16_tile_masks_ab.txt.)
+constexpr uint32_t V5_MASK_ALL = 0xFFFFFFFFu;
+// the cone / slab bits of a mask in use (n_cone + n_slab <= 32)
+RM_DEV uint32_t mask_cone_bits(uint32_t mask, uint32_t n_cone) { return n_cone >= 32u ? mask : mask & ((1u << n_cone) - 1u); }
+RM_DEV uint32_t mask_slab_bits(uint32_t mask, uint32_t n_cone) { return n_cone >= 32u ? 0u : mask >> n_cone; }
+
+// One entry of the ray test.  Cone k: the ray clears it iff m.d - s < 0 (NaN -> not clear).
+RM_DEV void ray_cone_entry_v5(const CullTables& T, uint32_t k, float dx, float dy, float dz, bool& clear) {
+    const float4 a = T.cone[k];  // wave-uniform address: LDS broadcast
+    const float t = __builtin_fmaf(a.z, dz, __builtin_fmaf(a.y, dy, __builtin_fmaf(a.x, dx, -a.w)));
+    clear = clear && (t < 0.0f);
+}
+// Slab k, (ix, iy, iz) = 1 / d; returns true when no lane of the wave is clear any more.
+RM_DEV bool ray_slab_entry_v5(const CullTables& T, uint32_t k, float dx, float dy, float dz, float ix, float iy, float iz, bool& clear) {
+    const float4 c = T.slab[3u * k + 2u];
+    const float t = __builtin_fmaf(c.z, dz, __builtin_fmaf(c.y, dy, __builtin_fmaf(c.x, dx, -c.w)));
+    if (__ballot(clear && !(t < 0.0f)) == 0ull) return false;  // every still-clear ray misses the bounding sphere
+    const float4 a = T.slab[3u * k], b = T.slab[3u * k + 1u];
+    const float x1 = a.x * ix, x2 = b.x * ix, y1 = a.y * iy, y2 = b.y * iy, z1 = a.z * iz, z2 = b.z * iz;
+    const float tn = fmax_(fmin_(x1, x2), fmax_(fmin_(y1, y2), fmin_(z1, z2)));
+    const float tf = fmin_(fmax_(x1, x2), fmin_(fmax_(y1, y2), fmax_(z1, z2)));
+    clear = clear && !(tf >= fmax_(tn, 0.0f));  // a dropped NaN only widens the interval
+    return __ballot(clear) == 0ull;
+}
+// 1/d with |d_i| clamped away from 0 so that no 0 * inf = NaN can appear in the slab test
+RM_DEV float slab_rcp_v5(float d) { return __builtin_amdgcn_rcpf(__builtin_copysignf(fmax_(__builtin_fabsf(d), 1.0e-30f), d)); }
+
+// true iff the half-line o + t d (t >= 0) provably stays clear of every primitive's margin zone.  mask (wave-uniform): the
+// primitive mask of the ray's tile, V5_MASK_ALL for a ray of no tile.
+RM_DEV bool ray_misses_scene_v5(const CullTables& T, uint32_t mask, float dx, float dy, float dz) {
     bool clear = *T.veto == 0u;  // no primitives (empty scene): every ray misses (wgsl:189-191)
     unit_dir(dx, dy, dz);        // the tests are about the half-line, whatever the length of d (see unit_dir)
+    if (mask != V5_MASK_ALL) {  // a mask in use (at most 32 entries): its set bits in ascending order, 1.7 of 13 on the metric frame
+        for (uint32_t m = mask_cone_bits(mask, T.n_cone); m != 0u; m &= m - 1u) ray_cone_entry_v5(T, (uint32_t)__builtin_ctz(m), dx, dy, dz, clear);
+        const uint32_t ms = mask_slab_bits(mask, T.n_cone);
+        if (ms == 0u || __ballot(clear) == 0ull) return clear;
+        const float ix = slab_rcp_v5(dx), iy = slab_rcp_v5(dy), iz = slab_rcp_v5(dz);
+        for (uint32_t m = ms; m != 0u; m &= m - 1u)
+            if (ray_slab_entry_v5(T, (uint32_t)__builtin_ctz(m), dx, dy, dz, ix, iy, iz, clear)) return false;
+        return clear;
+    }
     for (uint32_t k = 0; k < T.n_cone; k++) {
-        const float4 a = T.cone[k];  // wave-uniform address: LDS broadcast
-        const float t = __builtin_fmaf(a.z, dz, __builtin_fmaf(a.y, dy, __builtin_fmaf(a.x, dx, -a.w)));
-        clear = clear && (t < 0.0f);  // NaN -> not clear
+        ray_cone_entry_v5(T, k, dx, dy, dz, clear);
         if ((k & 3u) == 3u && __ballot(clear) == 0ull) return false;
     }
     if (T.n_slab == 0u || __ballot(clear) == 0ull) return clear;
-    // 1/d with |d_i| clamped away from 0 so that no 0 * inf = NaN can appear in the slab test
-    const float tiny = 1.0e-30f;
-    const float ix = __builtin_amdgcn_rcpf(__builtin_copysignf(fmax_(__builtin_fabsf(dx), tiny), dx));
-    const float iy = __builtin_amdgcn_rcpf(__builtin_copysignf(fmax_(__builtin_fabsf(dy), tiny), dy));
-    const float iz = __builtin_amdgcn_rcpf(__builtin_copysignf(fmax_(__builtin_fabsf(dz), tiny), dz));
-    for (uint32_t k = 0; k < T.n_slab; k++) {
-        const float4 c = T.slab[3u * k + 2u];
-        const float t = __builtin_fmaf(c.z, dz, __builtin_fmaf(c.y, dy, __builtin_fmaf(c.x, dx, -c.w)));
-        if (__ballot(clear && !(t < 0.0f)) == 0ull) continue;  // every still-clear ray misses the bounding sphere
-        const float4 a = T.slab[3u * k], b = T.slab[3u * k + 1u];
-        const float x1 = a.x * ix, x2 = b.x * ix, y1 = a.y * iy, y2 = b.y * iy, z1 = a.z * iz, z2 = b.z * iz;
-        const float tn = fmax_(fmin_(x1, x2), fmax_(fmin_(y1, y2), fmin_(z1, z2)));
-        const float tf = fmin_(fmax_(x1, x2), fmin_(fmax_(y1, y2), fmax_(z1, z2)));
-        clear = clear && !(tf >= fmax_(tn, 0.0f));  // a dropped NaN only widens the interval
-        if (__ballot(clear) == 0ull) return false;
-    }
+    const float ix = slab_rcp_v5(dx), iy = slab_rcp_v5(dy), iz = slab_rcp_v5(dz);
+    for (uint32_t k = 0; k < T.n_slab; k++)
+        if (ray_slab_entry_v5(T, k, dx, dy, dz, ix, iy, iz, clear)) return false;
     return clear;
 }
 
@@ -730,6 +759,7 @@ struct V5Work {
                             //                 bits of f0 = map_scene(ro) (the shared first march step), unused}
     uint32_t* measured;     // nullptr, or [n_frames][n_tiles]: how long each marched tile took (10 ns ticks), written here
                             // and read by the NEXT draw's rm_tile_sort_v5 (RM_OPT_BALANCE = 3: longest tiles first)
+    const uint32_t* masks;  // [n_frames][n_tiles] primitive mask of every tile (rm_tile_pre_v5; V5_MASK_ALL: nothing known)
 };
 
 // (Round 3 tried to drop the sort kernel -- the pre-pass appending every tile that needs marching to one of four lists by the
@@ -801,6 +831,8 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
     uint32_t* s_veto = s_next + 2;
     float* s_off = reinterpret_cast<float*>(s_next + rml::kMarchCtlBytes / 4u);  // [16][2] screen offsets of the AA samples (wgsl:47-53)
     uint8_t* rmat = reinterpret_cast<uint8_t*>(s_next) + rml::kMarchCtlBytes + rml::kMarchOffBytes;  // MAT, tagged program: [V5_POOL] material per ray
+    // MarchLds::pad: primitive mask of the current tile (a kernel without MAT never meets a tagged program: a fixed offset from s_next)
+    uint32_t* s_mask = reinterpret_cast<uint32_t*>(rmat + (MAT && L.n_mrec != 0u ? V5_POOL : 0u));
     const bool tagged = MAT && L.n_mrec != 0u;                         // wave-uniform
     constexpr uint32_t TAP_IDLE = MAT ? 5u : 4u;                       // tap_t: 0..3 normal taps, 4 (MAT) material, else idle
     const CullTables cullt{t_cone, t_slab, s_veto, L.n_cone, L.n_slab};
@@ -964,6 +996,9 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
         wxy[lane] = lane < 8u ? screen_x(tx < L.W ? tx : L.W - 1u, L.W)                                // edge tiles clamp
                               : screen_y(rm_global_row(L, ty < L.rows ? ty : L.rows - 1u), L.H);
     }
+    // the tile's primitive mask, for the ray tests of the produce rounds: every wave stores the same word and reads it behind
+    // its own fence (kept in LDS, not in a scalar register that would live through the march loop)
+    if (lane == 0u) *s_mask = work.masks[(size_t)blockIdx.z * n_tiles + tile];
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 
     // lane state of a marching ray: evaluation point = ro + d * sc
@@ -1024,7 +1059,7 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
                         // so once the batches of the tile's four CORNER blocks (the first four of the pool) went through without
                         // a single ray cleared, the rest of the tile's batches skip them.
                         const bool test_rays = (L.flags & 1u) != 0u && __builtin_amdgcn_readfirstlane(s_next[3]) < 4u;
-                        bool culled = L.max_iter == 0u || (start == START_DONE && finite_d) || (test_rays && ray_misses_scene_v5(cullt, gx, gy, gz));
+                        bool culled = L.max_iter == 0u || (start == START_DONE && finite_d) || (test_rays && ray_misses_scene_v5(cullt, __builtin_amdgcn_readfirstlane(*s_mask), gx, gy, gz));
 #if !defined(RM_JIT_TU) || defined(RM_JIT_BOUND_WALK)  // a generated kernel carries it only if its program's structure can use it
                         if (test_rays && (L.flags & 32u) && (*s_veto & 1u) == 0u && bound_scale < 1.0e12f && __ballot(!culled) != 0ull)  // "Miss test on lower bounds"
                             culled = culled || ray_misses_by_bounds_v5<false>(load_record, L.n_rec, ro, gx, gy, gz, L.min_dist, bound_scale);
@@ -1433,45 +1468,100 @@ RM_DEV float cone_noise_v5(const rm_uniforms& u, const V4& ro, uint32_t W, uint3
                 __builtin_fabsf(u.inv_proj[k + 12]));
     return 1.0e-6f * mag;  // (anything non-finite ends up in rho and fails the cone)
 }
-// Whether the tables clear every direction of a cone of rect_cone_v5 (cone_ok: what it returned).
-RM_DEV bool cone_misses_tables_v5(const CullTables& T, const float2* aux, const float (&cone)[4], bool cone_ok) {
+// One entry of the cone test, cone (c, rho) of rect_cone_v5.  Cone entry k: every direction of the cone clears it iff
+// m.c + |m| rho < s (NaN -> not clear).
+RM_DEV bool cone_clears_cone_entry_v5(const CullTables& T, const float2* aux, uint32_t k, float cx, float cy, float cz, float rho) {
+    const float4 a = T.cone[k];  // wave-uniform address: LDS broadcast
+    const float t = __builtin_fmaf(aux[k].x, rho, __builtin_fmaf(a.z, cz, __builtin_fmaf(a.y, cy, a.x * cx)));
+    return t < a.w;
+}
+// Slab entry k, its bounding sphere: as a cone entry.
+RM_DEV bool cone_clears_slab_sphere_v5(const CullTables& T, const float2* aux, uint32_t k, float cx, float cy, float cz, float rho) {
+    const float4 c = T.slab[3u * k + 2u];
+    const float t = __builtin_fmaf(aux[T.n_cone + k].x, rho, __builtin_fmaf(c.z, cz, __builtin_fmaf(c.y, cy, c.x * cx)));
+    return t < c.w;
+}
+// Slab entry k, its box inflated by D rho against the centre ray; (ix, iy, iz) = 1 / c (slab_rcp_v5).
+RM_DEV bool cone_clears_slab_box_v5(const CullTables& T, const float2* aux, uint32_t k, float rho, float ix, float iy, float iz) {
+    const float infl = aux[T.n_cone + k].y * rho;  // (|m|, D) both rounded up
+    const float4 a = T.slab[3u * k], b = T.slab[3u * k + 1u];
+    const float x1 = (a.x - infl) * ix, x2 = (b.x + infl) * ix, y1 = (a.y - infl) * iy, y2 = (b.y + infl) * iy;
+    const float z1 = (a.z - infl) * iz, z2 = (b.z + infl) * iz;
+    const float tn = fmax_(fmin_(x1, x2), fmax_(fmin_(y1, y2), fmin_(z1, z2)));
+    const float tf = fmin_(fmax_(x1, x2), fmin_(fmax_(y1, y2), fmax_(z1, z2)));
+    // infl must be a number for the comparison to mean anything (a dropped NaN would shrink the box)
+    return infl < __uint_as_float(0x7F800000u) && !(tf >= fmax_(tn, 0.0f));
+}
+// Whether the tables clear every direction of a cone of rect_cone_v5 (cone_ok: what it returned).  mask (wave-uniform): the
+// primitive mask of the tile the cone's rectangle lies in; V5_MASK_ALL tests every entry.
+RM_DEV bool cone_misses_tables_v5(const CullTables& T, const float2* aux, const float (&cone)[4], bool cone_ok, uint32_t mask) {
     const float cx = cone[0], cy = cone[1], cz = cone[2], rho = cone[3];
     bool clear = cone_ok && *T.veto == 0u;  // a Plane (veto bit 1) leaves the tables unusable, not the cone
+    if (mask != V5_MASK_ALL) {  // a mask in use: its set bits in ascending order; none: the pixel is clear without a table read
+        for (uint32_t m = mask_cone_bits(mask, T.n_cone); m != 0u; m &= m - 1u)
+            clear = clear && cone_clears_cone_entry_v5(T, aux, (uint32_t)__builtin_ctz(m), cx, cy, cz, rho);
+        const uint32_t ms = mask_slab_bits(mask, T.n_cone);
+        if (ms == 0u || __ballot(clear) == 0ull) return clear;
+        const float ix = slab_rcp_v5(cx), iy = slab_rcp_v5(cy), iz = slab_rcp_v5(cz);
+        for (uint32_t m = ms; m != 0u; m &= m - 1u) {
+            const uint32_t k = (uint32_t)__builtin_ctz(m);
+            if (__ballot(clear && !cone_clears_slab_sphere_v5(T, aux, k, cx, cy, cz, rho)) == 0ull) continue;
+            clear = clear && cone_clears_slab_box_v5(T, aux, k, rho, ix, iy, iz);
+            if (__ballot(clear) == 0ull) return false;
+        }
+        return clear;
+    }
     for (uint32_t k = 0; k < T.n_cone; k++) {
-        const float4 a = T.cone[k];  // wave-uniform address: LDS broadcast
-        const float t = __builtin_fmaf(aux[k].x, rho, __builtin_fmaf(a.z, cz, __builtin_fmaf(a.y, cy, a.x * cx)));
-        clear = clear && (t < a.w);  // NaN -> not clear
+        clear = clear && cone_clears_cone_entry_v5(T, aux, k, cx, cy, cz, rho);
         if ((k & 3u) == 3u && __ballot(clear) == 0ull) return false;
     }
     if (T.n_slab == 0u || __ballot(clear) == 0ull) return clear;
-    const float tiny = 1.0e-30f;
-    const float ix = __builtin_amdgcn_rcpf(__builtin_copysignf(fmax_(__builtin_fabsf(cx), tiny), cx));
-    const float iy = __builtin_amdgcn_rcpf(__builtin_copysignf(fmax_(__builtin_fabsf(cy), tiny), cy));
-    const float iz = __builtin_amdgcn_rcpf(__builtin_copysignf(fmax_(__builtin_fabsf(cz), tiny), cz));
+    const float ix = slab_rcp_v5(cx), iy = slab_rcp_v5(cy), iz = slab_rcp_v5(cz);
     for (uint32_t k = 0; k < T.n_slab; k++) {
-        const float4 c = T.slab[3u * k + 2u];
-        const float2 x = aux[T.n_cone + k];  // (|m|, D) both rounded up
-        const float t = __builtin_fmaf(x.x, rho, __builtin_fmaf(c.z, cz, __builtin_fmaf(c.y, cy, c.x * cx)));
-        if (__ballot(clear && !(t < c.w)) == 0ull) continue;  // every still-clear pixel clears the bounding sphere
-        const float infl = x.y * rho;
-        const float4 a = T.slab[3u * k], b = T.slab[3u * k + 1u];
-        const float x1 = (a.x - infl) * ix, x2 = (b.x + infl) * ix, y1 = (a.y - infl) * iy, y2 = (b.y + infl) * iy;
-        const float z1 = (a.z - infl) * iz, z2 = (b.z + infl) * iz;
-        const float tn = fmax_(fmin_(x1, x2), fmax_(fmin_(y1, y2), fmin_(z1, z2)));
-        const float tf = fmin_(fmax_(x1, x2), fmin_(fmax_(y1, y2), fmax_(z1, z2)));
-        // infl must be a number for the comparison to mean anything (a dropped NaN would shrink the box)
-        clear = clear && infl < __uint_as_float(0x7F800000u) && !(tf >= fmax_(tn, 0.0f));
+        if (__ballot(clear && !cone_clears_slab_sphere_v5(T, aux, k, cx, cy, cz, rho)) == 0ull) continue;  // every still-clear pixel clears the bounding sphere
+        clear = clear && cone_clears_slab_box_v5(T, aux, k, rho, ix, iy, iz);
         if (__ballot(clear) == 0ull) return false;
     }
     return clear;
 }
+// The same test entry by entry, lane = tile, for a program of at most 32 entries: `mask` gets bit k for cone entry k and bit
+// n_cone + k for slab entry k iff the lane's cone does not provably clear the entry -- neither its bounding sphere nor, for a
+// slab, its inflated box.  Returns what cone_misses_tables_v5(.., V5_MASK_ALL) returns in the same wave, bit for bit, and that
+// is mask == 0 whenever cone_ok holds and nothing is vetoed: that function runs the box test of a slab for the whole wave as
+// soon as ONE still-clear lane fails the sphere test, and a lane that is still clear then takes the box's verdict alone (it can
+// be the stricter one: the box grows by D rho per axis, sqrt(3) D rho at its corners) -- so does its bit here.
+RM_DEV bool tile_touch_mask_v5(const CullTables& T, const float2* aux, const float (&cone)[4], bool cone_ok, uint32_t& mask) {
+    const float cx = cone[0], cy = cone[1], cz = cone[2], rho = cone[3];
+    bool clear = cone_ok && *T.veto == 0u;
+    uint32_t touched = 0u;
+    for (uint32_t k = 0; k < T.n_cone; k++) {
+        const bool ok = cone_clears_cone_entry_v5(T, aux, k, cx, cy, cz, rho);
+        clear = clear && ok;
+        touched |= ok ? 0u : 1u << k;
+    }
+    if (T.n_slab != 0u) {
+        const float ix = slab_rcp_v5(cx), iy = slab_rcp_v5(cy), iz = slab_rcp_v5(cz);
+        for (uint32_t k = 0; k < T.n_slab; k++) {
+            const bool sphere_ok = cone_clears_slab_sphere_v5(T, aux, k, cx, cy, cz, rho);
+            if (__ballot(!sphere_ok) == 0ull) continue;
+            const bool wave_ran_box = __ballot(clear && !sphere_ok) != 0ull;
+            const bool box_decides = clear && wave_ran_box;
+            const bool box_ok = cone_clears_slab_box_v5(T, aux, k, rho, ix, iy, iz);
+            const bool ok = box_decides ? box_ok : (sphere_ok || box_ok);
+            clear = clear && ok;
+            touched |= ok ? 0u : 1u << (T.n_cone + k);
+        }
+    }
+    mask = touched;
+    return clear;
+}
 // One pixel: the rectangle is its 4 x 4 grid of samples, spanned by samples (0,0), (3,0), (0,3), (3,3) (table entry 4 i + j of
-// off, the table of the sixteen sample offsets).
+// off, the table of the sixteen sample offsets).  mask: the primitive mask of the pixel's tile (V5_MASK_ALL: test every entry).
 RM_DEV bool pixel_misses_scene_v5(const CullTables& T, const float2* aux, const float* m_proj, const float* m_view, const float* off,
-                                  const V4& ro, float sx, float sy, float noise, float (&cone_out)[4], float (&corner)[4][3]) {
+                                  const V4& ro, float sx, float sy, float noise, uint32_t mask, float (&cone_out)[4], float (&corner)[4][3]) {
     const float px[2] = {sx, sx}, py[2] = {sy, sy}, ox[2] = {off[0], off[24]}, oy[2] = {off[1], off[7]};
     const bool cone_ok = rect_cone_v5(m_proj, m_view, ro, px, py, ox, oy, noise, cone_out, corner);
-    return cone_misses_tables_v5(T, aux, cone_out, cone_ok);
+    return cone_misses_tables_v5(T, aux, cone_out, cone_ok, mask);
 }
 
 // The pixel test's own table, behind the miss-test tables: per cone / slab entry (|m|, |m| + bounding radius of the inflated
@@ -1576,8 +1666,10 @@ RM_DEV bool rect_cell_v5(const rm_uniforms& u, const V4& ro, const float (&corne
 constexpr uint32_t V5_TILE_CLEAR = 1u, V5_TILE_SKY = 2u, V5_TILE_CELL = 4u, V5_TILE_CODE = 8u;
 // One lane, one tile (tile_x, tile_y) of eight consecutive frame rows from strip-local row 8 tile_y on (see the header above).
 // tables: the miss-test tables are staged; all_miss: no ray can hit anything (max_iter = 0).  off: the sixteen sample offsets.
+// mask: the tile's primitive mask (tile_touch_mask_v5) where it is exact information -- the tables were consulted and are
+// usable, the cone is, the program has at most 32 entries --, else V5_MASK_ALL.
 RM_DEV uint32_t tile_verdict_v5(const RmLaunch& L, const rm_uniforms& u, const V4& ro, const CullTables& T, const float2* aux, const float* off,
-                                bool tables, bool all_miss, uint32_t tile_x, uint32_t tile_y, float (&cone)[4]) {
+                                bool tables, bool all_miss, uint32_t tile_x, uint32_t tile_y, float (&cone)[4], uint32_t& mask) {
     const uint32_t row = rm_global_row(L, tile_y * 8u);
     const float px[2] = {screen_x(tile_x * 8u, L.W), screen_x(tile_x * 8u + 7u, L.W)};
     const float py[2] = {screen_y(row, L.H), screen_y(row + 7u, L.H)};
@@ -1586,7 +1678,16 @@ RM_DEV uint32_t tile_verdict_v5(const RmLaunch& L, const rm_uniforms& u, const V
     float corner[4][3];
     const bool cone_ok = rect_cone_v5(u.inv_proj, u.inv_view, ro, px, py, ox, oy, cone_noise_v5(u, ro, L.W, L.H), cone, corner);
     bool clear = cone_ok && all_miss;
-    if (!all_miss && tables) clear = cone_misses_tables_v5(T, aux, cone, cone_ok);
+    mask = V5_MASK_ALL;
+    if (!all_miss && tables) {
+        if (T.n_cone + T.n_slab <= 32u) {  // (wave-uniform)
+            uint32_t touched;
+            clear = tile_touch_mask_v5(T, aux, cone, cone_ok, touched);
+            if (cone_ok && *T.veto == 0u) mask = touched;
+        } else {
+            clear = cone_misses_tables_v5(T, aux, cone, cone_ok, V5_MASK_ALL);
+        }
+    }
     float bx = 0.0f, by = 0.0f;
 #pragma unroll
     for (int a = 0; a < 2; a++) {
@@ -1604,7 +1705,10 @@ RM_DEV uint32_t tile_verdict_v5(const RmLaunch& L, const rm_uniforms& u, const V
     bool spread = false;
 #pragma unroll
     for (uint32_t c = 1; c < 4u; c++) spread = spread || corner[c][0] != corner[0][0] || corner[c][1] != corner[0][1] || corner[c][2] != corner[0][2];
-    if (!spread) return 0u;
+    if (!spread) {
+        mask = V5_MASK_ALL;
+        return 0u;
+    }
     return (clear ? V5_TILE_CLEAR : 0u) | (sky ? V5_TILE_SKY : 0u) | (cell ? V5_TILE_CELL | (code ? V5_TILE_CODE : 0u) : 0u);
 }
 
@@ -1634,7 +1738,7 @@ RM_DEV CullTables stage_cull_tables(const RmLaunch& L, const V4& ro, uint32_t* s
     return CullTables{t_cone, t_slab, s_veto, L.n_cone, L.n_slab};
 }
 
-__global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, uint32_t* cost, uint32_t n_tiles) {
+__global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, uint32_t* cost, uint32_t* masks, uint32_t n_tiles) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     rm_uniforms u = L.u;
@@ -1646,6 +1750,7 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
     __shared__ uint8_t s_code[V5_PRE_TILES][64 * 16];   // need them, for the sample-parallel finish of a clear tile (below)
     __shared__ uint8_t s_list[V5_PRE_TILES][64];
     __shared__ uint8_t s_verdict[V5_PRE_BLOCK];  // per tile of the block: tile_verdict_v5 if it settles the tile, else 0
+    __shared__ uint32_t s_mask[V5_PRE_BLOCK];    // per tile of the block: its primitive mask (also written to masks[], for the march kernel)
     __shared__ uint32_t s_claim;                 // next tile of the block to hand out
     if (tid == 0u) s_claim = 0u;
     const float2* t_aux;
@@ -1653,7 +1758,7 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
     const uint32_t* s_veto = cullt.veto;
     const uint32_t tiles_x = (L.W + 7u) / 8u;
     const float cone_noise = cone_noise_v5(u, ro, L.W, L.H);
-  auto do_tile = [&](uint32_t tile) {  // (whole wave; no barrier inside)
+  auto do_tile = [&](uint32_t tile, uint32_t tile_mask) {  // (whole wave; no barrier inside; tile_mask wave-uniform)
     const uint32_t tile_x = tile % tiles_x, tile_y = tile / tiles_x;
     const uint32_t tx = tile_x * 8u + (lane & 7u), ty = tile_y * 8u + (lane >> 3);
     const uint32_t px = tx < L.W ? tx : L.W - 1u, ry = ty < L.rows ? ty : L.rows - 1u;
@@ -1677,7 +1782,7 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
         }
     } else {
         float cone[4];
-        clear = pixel_misses_scene_v5(cullt, t_aux, mp, mv, s_off, ro, sx, sy, cone_noise, cone, corner);
+        clear = pixel_misses_scene_v5(cullt, t_aux, mp, mv, s_off, ro, sx, sy, cone_noise, tile_mask, cone, corner);
         // a program that blends: the pixels the inflated bounds could not clear get the program run on lower bounds of its
         // leaves over the pixel's cone ("Miss test on lower bounds"; the march kernel repeats it per ray for what is left)
         const float bound_scale = bound_scale_prepass_v5(L, ro);
@@ -1771,14 +1876,16 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
     // a tile's rows must be consecutive frame rows
     const uint32_t first_tile = blockIdx.x * V5_PRE_BLOCK;
     if (tid < V5_PRE_BLOCK) {
-        uint32_t v = 0u;
+        uint32_t v = 0u, mask = V5_MASK_ALL;
         if ((tables || L.max_iter == 0u) && L.strip_rows % 8u == 0u) {
             const uint32_t tile = first_tile + tid < n_tiles ? first_tile + tid : n_tiles - 1u;
             float cone[4];
-            v = tile_verdict_v5(L, u, ro, cullt, t_aux, s_off, tables, L.max_iter == 0u, tile % tiles_x, tile / tiles_x, cone);
+            v = tile_verdict_v5(L, u, ro, cullt, t_aux, s_off, tables, L.max_iter == 0u, tile % tiles_x, tile / tiles_x, cone, mask);
             if (!(v & V5_TILE_CLEAR) || !(v & (V5_TILE_SKY | V5_TILE_CELL))) v = 0u;
         }
         s_verdict[tid] = (uint8_t)v;
+        s_mask[tid] = mask;
+        if (first_tile + tid < n_tiles) masks[(size_t)blockIdx.z * n_tiles + first_tile + tid] = mask;
     }
     __syncthreads();
     for (;;) {
@@ -1788,7 +1895,7 @@ __global__ __launch_bounds__(64 * V5_PRE_TILES) void rm_tile_pre_v5(RmLaunch L, 
         if (t >= V5_PRE_BLOCK || first_tile + t >= n_tiles) break;
         const uint32_t tile = first_tile + t, v = s_verdict[t];
         if (v == 0u) {
-            do_tile(tile);
+            do_tile(tile, (uint32_t)__builtin_amdgcn_readfirstlane((int)s_mask[t]));
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the wave's LDS scratch is reused by its next tile
             continue;
         }
@@ -1929,7 +2036,7 @@ __global__ __launch_bounds__(64) void rm_selftest_cull_rays_kernel(RmLaunch L, V
     const uint32_t i = blockIdx.x * 64u + tid, j = i < n ? i : n - 1u;
     const float gx = dirs[3u * j], gy = dirs[3u * j + 1u], gz = dirs[3u * j + 2u];
     const uint32_t veto = *cullt.veto;
-    const bool clear = tables && ray_misses_scene_v5(cullt, gx, gy, gz);
+    const bool clear = tables && ray_misses_scene_v5(cullt, V5_MASK_ALL, gx, gy, gz);
     const float bound_scale = bound_scale_march_v5(L, ro);
     const bool walk = tables && (L.flags & 32u) && (veto & 1u) == 0u && bound_scale < 1.0e12f;
     float acc = __uint_as_float(0x7FC00000u);
@@ -1967,7 +2074,7 @@ __global__ __launch_bounds__(64) void rm_selftest_cull_pixels_kernel(RmLaunch L,
     bool clear = false, walk = false, by_bounds = false;
     const uint32_t veto = *cullt.veto;
     if (tables) {
-        clear = pixel_misses_scene_v5(cullt, t_aux, mp, mv, s_off, ro, sx, sy, cone_noise, cone, corner);
+        clear = pixel_misses_scene_v5(cullt, t_aux, mp, mv, s_off, ro, sx, sy, cone_noise, V5_MASK_ALL, cone, corner);
         const float bound_scale = bound_scale_prepass_v5(L, ro);
         walk = (L.flags & 32u) && (veto & 1u) == 0u && bound_scale < 1.0e12f && cone[3] == cone[3];
         if (__ballot(walk) != 0ull) {
@@ -1988,7 +2095,8 @@ __global__ __launch_bounds__(64) void rm_selftest_cull_pixels_kernel(RmLaunch L,
 // Tiles xy[2 i] = (tile_x, tile_y) of a W x H frame (L.W, L.H) under the context's uniforms, as the pre-pass classifies them, lane
 // = tile: out[8 i + 0..3] the cone (c, rho) of the tile's 32 x 32 sample directions (rho = NaN: not usable), [4] the checker bit
 // of a one-cell tile (else 0), [5] flags as an integer: bit 0 the tables clear the tile, bit 1 all its samples are sky, bit 2 all
-// are in one checker cell, bit 3 the tables were usable; [6], [7] zero.
+// are in one checker cell, bit 3 the tables were usable; [6] the tile's primitive mask as an integer (V5_MASK_ALL when it is
+// not in use), [7] the number of table entries n_cone + n_slab as an integer.
 __global__ __launch_bounds__(64) void rm_selftest_cull_tiles_kernel(RmLaunch L, const uint32_t* xy, uint32_t n, float* out) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     __shared__ float s_off[32];
@@ -2000,14 +2108,16 @@ __global__ __launch_bounds__(64) void rm_selftest_cull_tiles_kernel(RmLaunch L, 
     const CullTables cullt = stage_cull_tables(L, ro, smem, &u, s_off, &t_aux, tid, 64u);
     const uint32_t i = blockIdx.x * 64u + tid, j = i < n ? i : n - 1u;
     float cone[4];
-    const uint32_t v = tile_verdict_v5(L, u, ro, cullt, t_aux, s_off, tables, L.max_iter == 0u, xy[2u * j], xy[2u * j + 1u], cone);
+    uint32_t mask;
+    const uint32_t v = tile_verdict_v5(L, u, ro, cullt, t_aux, s_off, tables, L.max_iter == 0u, xy[2u * j], xy[2u * j + 1u], cone, mask);
+    if (L.strip_rows % 8u != 0u) mask = V5_MASK_ALL;  // (as rm_tile_pre_v5: no verdicts on tiles whose rows are not consecutive)
     if (i < n) {
         float* o = out + 8u * (size_t)i;
         o[0] = cone[0]; o[1] = cone[1]; o[2] = cone[2]; o[3] = cone[3];
         o[4] = (v & V5_TILE_CODE) ? 1.0f : 0.0f;
         o[5] = __uint_as_float(((v & V5_TILE_CLEAR) ? 1u : 0u) | ((v & V5_TILE_SKY) ? 2u : 0u) | ((v & V5_TILE_CELL) ? 4u : 0u) |
                                ((tables && *cullt.veto == 0u) ? 8u : 0u));
-        o[6] = 0.0f; o[7] = 0.0f;
+        o[6] = __uint_as_float(mask); o[7] = __uint_as_float(L.n_cone + L.n_slab);
     }
 }
 // Waves: pos[(3 w + k) * 64 + lane] coordinate k of wave w's lane, thr[64 w + lane], live[w] the mask of its live lanes (not 0);

@@ -55,7 +55,8 @@ static_assert(MarchWaveLds::bytes == 4u * V5_WAVE_DWORDS, "a wave's buffers");
 
 // pool, per-wave buffers [wpt], spill columns [wpt][spill_depth][64], the miss-test tables, the staged program (records, unit
 // table, tree table: prog_in_lds kernels only), {pool cursor, tile slot, veto, flag}, the 16 AA sample offsets, one
-// material byte per ray of a tagged program, 16 B unused.  Every region starts on a multiple of 16 bytes.
+// material byte per ray of a tagged program, then `pad`: the current tile's primitive mask (one word) and 12 B unused.  Every
+// region starts on a multiple of 16 bytes.
 // (The march kernel takes the compile-time parts from here -- MarchWaveLds, the two sizes below -- and writes the sums that
 // depend on the launch out on RmLaunch's fields, see the comment there; lds_layout_check.cpp compares the two.)
 constexpr uint32_t kMarchCtlBytes = 16u, kMarchOffBytes = 16u * 2u * 4u;
