@@ -654,8 +654,9 @@ int rm_selftest_cull_waves(rm_ctx* ctx, const float* origin, const float* pos, c
                            float extra_margin, uint64_t* out_masks);
 
 /* Diagnostics: per-wave records of the last draw made with RM_OPT_WAVE_STATS = 1, four u64 per
- * wave in dispatch order: [0] start, [1] end (100 MHz s_memrealtime ticks), [2] tile id << 32 |
- * map_scene iterations, [3] refills << 32 | sum over iterations of live lanes. */
+ * wave in dispatch order (frame, workgroup, wave of the workgroup): [0] start, [1] end (100 MHz s_memrealtime ticks),
+ * [2] tiles the wave's workgroup took from the work list << 32 | map_scene iterations, [3] refills << 32 | sum over
+ * iterations of live lanes. */
 int rm_read_wave_stats(rm_ctx* ctx, void* dst, uint64_t cap_bytes, uint64_t* out_bytes);
 
 /* Message for the last error on this context (ctx may be NULL: last rm_create error). */

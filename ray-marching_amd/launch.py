@@ -129,11 +129,22 @@ def init_timing_group(backend="nccl", local_rank=0, timeout_s=120.0):
     if backend != "nccl":
         return None, "gloo", "cpu", world, None
     ok, why, group = 1, None, None
+
+    def every_rank_ok():
+        flag = torch.tensor([ok], dtype=torch.int32)
+        dist.all_reduce(flag, op=dist.ReduceOp.MIN)    # over gloo: every rank learns whether every rank got this far
+        return int(flag.item()) == 1
+
+    # First what a rank knows without its peers.  The ranks agree on it BEFORE any of them enters RCCL: communicator set-up
+    # waits for every peer to connect, and that wait has no limit -- one rank staying out would leave the others there for
+    # good, and itself in the agreement below until gloo's timeout.
+    if os.environ.get("RM_BENCH_FORCE_NCCL_FAILURE"):
+        ok, why = 0, "RuntimeError: RM_BENCH_FORCE_NCCL_FAILURE is set"
+    elif not (dist.is_nccl_available() and torch.cuda.is_available()):
+        ok, why = 0, "RuntimeError: RCCL or a GPU is not available in this process"
+    if not every_rank_ok():
+        return None, "gloo", "cpu", world, why or "another rank could not bring RCCL up"
     try:
-        if os.environ.get("RM_BENCH_FORCE_NCCL_FAILURE"):
-            raise RuntimeError("RM_BENCH_FORCE_NCCL_FAILURE is set")
-        if not (dist.is_nccl_available() and torch.cuda.is_available()):
-            raise RuntimeError("RCCL or a GPU is not available in this process")
         group = dist.new_group(backend="nccl", timeout=datetime.timedelta(seconds=timeout_s))
         t = torch.ones(1, device=torch.device("cuda", local_rank))
         dist.all_reduce(t, group=group)
@@ -142,9 +153,7 @@ def init_timing_group(backend="nccl", local_rank=0, timeout_s=120.0):
             raise RuntimeError("probe all-reduce returned %r, expected %d" % (t.item(), world))
     except Exception as e:  # noqa: BLE001 -- whatever went wrong, the barrier must not cost the run
         ok, why = 0, "%s: %s" % (type(e).__name__, e)
-    flag = torch.tensor([ok], dtype=torch.int32)
-    dist.all_reduce(flag, op=dist.ReduceOp.MIN)    # over gloo: every rank learns whether every rank got RCCL up
-    if int(flag.item()) == 1:
+    if every_rank_ok():                            # ... and then whether every rank got RCCL up
         return group, "nccl", "cuda", dist.get_world_size(group), None
     if group is not None and ok:
         why = "another rank could not bring RCCL up"
