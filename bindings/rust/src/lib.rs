@@ -194,6 +194,31 @@ pub const RM_MASS_HI_Y: c_int = 15;
 pub const RM_MASS_HI_Z: c_int = 16;
 pub const RM_MASS_PROPS: c_int = 17;
 
+// Solid topology (rm_label_solid / rm_label_occupancy / rm_read_topology).
+/// `RM_TOPO_CAVITY_BIT`: a cavity point of the label volume holds this bit | its cavity's number.
+pub const RM_TOPO_CAVITY_BIT: u32 = 0x8000_0000;
+/// `RM_TOPO_EXTERIOR`: a point of the exterior in the label volume.
+pub const RM_TOPO_EXTERIOR: u32 = 0xFFFF_FFFF;
+// enum rm_topocount: indices into the counts of a labelling call; RM_TOPO_COUNTS is their number
+pub const RM_TOPO_BODIES: c_int = 0;
+pub const RM_TOPO_CAVITIES: c_int = 1;
+pub const RM_TOPO_POINTS: c_int = 2;
+pub const RM_TOPO_EDGES: c_int = 3;
+pub const RM_TOPO_FACES: c_int = 4;
+pub const RM_TOPO_CELLS: c_int = 5;
+pub const RM_TOPO_EULER: c_int = 6;
+pub const RM_TOPO_TUNNELS: c_int = 7;
+pub const RM_TOPO_EXTERIOR_POINTS: c_int = 8;
+pub const RM_TOPO_COUNTS: c_int = 9;
+// enum rm_topostat: indices into the statistics of a labelling call; RM_TOPO_STATS is their number
+pub const RM_TOPO_STAT_BRICKS: c_int = 0;
+pub const RM_TOPO_STAT_BRICKS_KEPT: c_int = 1;
+pub const RM_TOPO_STAT_BRICKS_INSIDE: c_int = 2;
+pub const RM_TOPO_STAT_EVALUATIONS: c_int = 3;
+pub const RM_TOPO_STAT_MERGE_PASSES: c_int = 4;
+pub const RM_TOPO_STAT_SCRATCH_BYTES: c_int = 5;
+pub const RM_TOPO_STATS: c_int = 6;
+
 // Slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table).
 // enum rm_slicecount: indices into the counts of rm_slice_contours; RM_SLICE_COUNTS is their number
 pub const RM_SLICE_POINTS: c_int = 0;
@@ -289,6 +314,12 @@ extern "C" {
                            out_moments: *mut u64, n_moments: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
     pub fn rm_mass_from_moments(moments: *const u64, n_moments: u32, origin: *const f32, step: *const f32, density: f64,
                                 out: *mut f64, n_out: u32) -> c_int;
+    pub fn rm_label_solid(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, level: f32,
+                          out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_label_occupancy(ctx: *mut rm_ctx, nx: u32, ny: u32, nz: u32, occupancy: *const c_void, is_device: c_int,
+                              stream: *mut c_void, out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_read_topology(ctx: *mut rm_ctx, out_body_moments: *mut u64, out_cavity_moments: *mut u64, out_labels: *mut u32,
+                            is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_slice_contours(ctx: *mut rm_ctx, axis: u32, origin_uv: *const f32, step_uv: *const f32, nu: u32, nv: u32,
                              heights: *const f32, n_layers: u32, level: f32, flags: u32, out_counts: *mut u64,
                              n_counts: u32) -> c_int;
@@ -404,6 +435,8 @@ pub struct RayMarchingResources {
     /// (points, contours, layers) of the slices the context holds since the last successful `slice_contours`: what
     /// `read_slices` writes, so what its slices must hold
     slices: Cell<Option<(u64, u64, u32)>>,
+    /// (bodies, cavities, lattice points) of the last successful labelling call: what `read_topology` writes
+    topology: Cell<Option<(u64, u64, u64)>>,
 }
 
 unsafe impl Send for RayMarchingResources {} // a context may move between threads; it is not Sync
@@ -417,7 +450,7 @@ impl RayMarchingResources {
             let msg = unsafe { CStr::from_ptr(rm_last_error(std::ptr::null_mut())) };
             return Err(RmError { status: rc, message: msg.to_string_lossy().into_owned() });
         }
-        Ok(Self { ctx, mesh: Cell::new(None), slices: Cell::new(None) })
+        Ok(Self { ctx, mesh: Cell::new(None), slices: Cell::new(None), topology: Cell::new(None) })
     }
 
     fn check(&self, rc: c_int) -> Result<(), RmError> {
@@ -633,6 +666,61 @@ impl RayMarchingResources {
             rm_mass_moments(self.ctx, origin.as_ptr(), step.as_ptr(), nx, ny, nz, level, out_moments.as_mut_ptr(), RM_MOMENTS as u32,
                             out_stats.as_mut_ptr(), RM_MASS_STATS as u32)
         })
+    }
+
+    /// Bodies (6-adjacency), cavities (voids under 26-adjacency that do not reach the lattice's border) and tunnels of the solid
+    /// `map_scene < level` on the lattice (`rm_label_solid`; 2..1024 points per axis, at most 2^28 in all): fills `out_counts`
+    /// (at least `RM_TOPO_COUNTS` entries, indexed by `RM_TOPO_*`; EULER and TUNNELS are two's-complement `i64`) and `out_stats`
+    /// (at least `RM_TOPO_STATS`, indexed by `RM_TOPO_STAT_*`).  Exact integers: every run gives the same words.  `read_topology`
+    /// copies the rows and the label volume out.  Leaves the context's mesh and slices alone.
+    pub fn label_solid(&self, origin: [f32; 3], step: [f32; 3], nx: u32, ny: u32, nz: u32, level: f32, out_counts: &mut [u64],
+                       out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(out_counts.len() >= RM_TOPO_COUNTS as usize, "label_solid: out_counts is shorter than RM_TOPO_COUNTS entries");
+        assert!(out_stats.len() >= RM_TOPO_STATS as usize, "label_solid: out_stats is shorter than RM_TOPO_STATS entries");
+        self.topology.set(None);  // a failed call may have released the previous labelling
+        self.check(unsafe {
+            rm_label_solid(self.ctx, origin.as_ptr(), step.as_ptr(), nx, ny, nz, level, out_counts.as_mut_ptr(), RM_TOPO_COUNTS as u32,
+                           out_stats.as_mut_ptr(), RM_TOPO_STATS as u32)
+        })?;
+        self.topology.set(Some((out_counts[RM_TOPO_BODIES as usize], out_counts[RM_TOPO_CAVITIES as usize],
+                                nx as u64 * ny as u64 * nz as u64)));
+        Ok(())
+    }
+
+    /// `label_solid` of a caller's occupancy in host memory (`rm_label_occupancy`): one byte per point, x fastest, nonzero =
+    /// inside.  The brick statistics are 0.
+    pub fn label_occupancy(&self, nx: u32, ny: u32, nz: u32, occupancy: &[u8], out_counts: &mut [u64],
+                           out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(occupancy.len() as u64 >= nx as u64 * ny as u64 * nz as u64, "label_occupancy: occupancy is shorter than nx * ny * nz bytes");
+        assert!(out_counts.len() >= RM_TOPO_COUNTS as usize, "label_occupancy: out_counts is shorter than RM_TOPO_COUNTS entries");
+        assert!(out_stats.len() >= RM_TOPO_STATS as usize, "label_occupancy: out_stats is shorter than RM_TOPO_STATS entries");
+        self.topology.set(None);  // a failed call may have released the previous labelling
+        self.check(unsafe {
+            rm_label_occupancy(self.ctx, nx, ny, nz, occupancy.as_ptr() as *const c_void, 0, std::ptr::null_mut(),
+                               out_counts.as_mut_ptr(), RM_TOPO_COUNTS as u32, out_stats.as_mut_ptr(), RM_TOPO_STATS as u32)
+        })?;
+        self.topology.set(Some((out_counts[RM_TOPO_BODIES as usize], out_counts[RM_TOPO_CAVITIES as usize],
+                                nx as u64 * ny as u64 * nz as u64)));
+        Ok(())
+    }
+
+    /// The result of the last successful labelling call: the bodies' rows and the cavities' rows (`RM_MOMENTS` words each, in
+    /// body and cavity order) and the label volume (one word per lattice point: a body's number, `RM_TOPO_CAVITY_BIT` | a
+    /// cavity's number, or `RM_TOPO_EXTERIOR`).  `None` skips that output.  `RM_ERR_ARG` before any labelling.
+    pub fn read_topology(&self, out_body_moments: Option<&mut [u64]>, out_cavity_moments: Option<&mut [u64]>,
+                         out_labels: Option<&mut [u32]>) -> Result<(), RmError> {
+        let (b, c, n) = match self.topology.get() {
+            Some((b, c, n)) => (b as usize, c as usize, n as usize),
+            None => return Err(RmError { status: RM_ERR_ARG, message: "read_topology: nothing has been labelled".to_string() }),
+        };
+        let m = RM_MOMENTS as usize;
+        assert!(out_body_moments.as_ref().map_or(true, |s| s.len() >= m * b), "read_topology: out_body_moments is shorter than {} rows", b);
+        assert!(out_cavity_moments.as_ref().map_or(true, |s| s.len() >= m * c), "read_topology: out_cavity_moments is shorter than {} rows", c);
+        assert!(out_labels.as_ref().map_or(true, |s| s.len() >= n), "read_topology: out_labels is shorter than {} points", n);
+        let pb = out_body_moments.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pc = out_cavity_moments.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pl = out_labels.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        self.check(unsafe { rm_read_topology(self.ctx, pb, pc, pl, 0, std::ptr::null_mut()) })
     }
 
     /// The mesh of the last successful `extract_mesh` (of the (vertices, triangles) it returned): positions (three per

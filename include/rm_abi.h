@@ -470,6 +470,58 @@ enum rm_massprop { RM_MASS_VOLUME = 0, RM_MASS_MASS = 1, RM_MASS_CX = 2, RM_MASS
 int rm_mass_from_moments(const uint64_t* moments, uint32_t n_moments, const float* origin, const float* step, double density,
                          double* out, uint32_t n_out);
 
+/* Solid topology (extension; DESIGN.md section 19 is the contract, to the last bit): is the part one piece, does it enclose
+ * voids, does it have through-holes -- and the moments of every piece.
+ * Lattice, values and "inside" are rm_mass_moments': point (i, j, k) lies at o + (float)i * s per axis, its value is what
+ * rm_query_points returns there (the empty program: max_dist), inside iff d < level (NaN is outside), linear index
+ * i + nx * (j + ny * k).  2..1024 points per axis and at most 2^28 in all (RM_ERR_RANGE otherwise).
+ * Adjacency (the complementary pair): BODIES are the connected components of the inside points under 6-adjacency (face
+ * neighbours), VOIDS those of the outside points under 26-adjacency (face, edge and corner neighbours).  The lattice counts as
+ * surrounded by one layer of outside points: every void with a point on the lattice's border belongs to THE EXTERIOR, every
+ * other void is a CAVITY.  Two cubes that touch along an edge or at a corner are two bodies, and the gap joins the voids.
+ * Canonical numbers: a component's label is the smallest linear index among its points; bodies are numbered 0..B-1 and
+ * cavities 0..C-1 in ascending order of it.  out_counts[RM_TOPO_*]:
+ *   BODIES, CAVITIES      B and C
+ *   POINTS                V, the inside points (RM_MOMENT_COUNT of rm_mass_moments on the same lattice and level)
+ *   EDGES, FACES, CELLS   E, F, K: the pairs of face-adjacent inside points, the unit squares whose four corners are inside,
+ *                         the unit cubes whose eight corners are
+ *   EULER                 V - E + F - K, a two's-complement int64
+ *   TUNNELS               B + C - EULER, a two's-complement int64: the first Betti number of the cubical complex (through-holes
+ *                         and handles, summed over the bodies)
+ *   EXTERIOR_POINTS       the outside points of the exterior
+ * Per body, and per cavity over its (outside) points, a row of the sixteen RM_MOMENT_* words; rm_mass_from_moments turns a row
+ * into that component's volume, centre, inertia and box, and the body rows combine entry by entry (sum 0-9, minimum 10-12,
+ * maximum 13-15) into rm_mass_moments' words.  The label volume: one u32 per point, x fastest -- an inside point holds its
+ * body's number, a cavity point RM_TOPO_CAVITY_BIT | its cavity's number, an exterior point RM_TOPO_EXTERIOR.
+ * Every output is an integer that no order of execution changes: two runs, and any correct implementation, give identical
+ * words.  out_stats[RM_TOPO_STAT_*]: BRICKS, BRICKS_KEPT, BRICKS_INSIDE, EVALUATIONS as rm_mass_moments reports them for the
+ * same lattice and level (0 for rm_label_occupancy); MERGE_PASSES, the merge passes over the union-find that ran (1 unless a
+ * verification found a pair of neighbours with different roots; after 8 the call fails with RM_ERR_DEVICE); SCRATCH_BYTES,
+ * the device memory the call used besides the label volume and the rows.
+ * rm_label_occupancy labels the caller's occupancy instead: one byte per point, x fastest, nonzero = inside; in host memory, or
+ * (is_device) in device memory, read after the work queued on `stream` (RM_STREAM_OWN: the context's).
+ * Both are synchronous on the context's own stream, ordered after its earlier work; they never touch the draw state, and the
+ * result lives in buffers of its own until the next labelling call or rm_destroy: it replaces neither the context's mesh nor
+ * its slices.  Errors (every check precedes the first launch, and a failed call leaves the outputs untouched): RM_ERR_NULL for
+ * a NULL output or occupancy; RM_ERR_ARG for n_counts < RM_TOPO_COUNTS, n_stats < RM_TOPO_STATS, a level, origin or step that
+ * is not finite or a step <= 0; RM_ERR_RANGE for the lattice; RM_ERR_DEVICE when device memory runs out (about 10 bytes per
+ * point, and 128 per component once B and C are known); otherwise those of a query for the program and limits. */
+#define RM_TOPO_CAVITY_BIT 0x80000000u /* label volume: this bit | the cavity's number */
+#define RM_TOPO_EXTERIOR 0xFFFFFFFFu   /* label volume: a point of the exterior */
+enum rm_topocount { RM_TOPO_BODIES = 0, RM_TOPO_CAVITIES = 1, RM_TOPO_POINTS = 2, RM_TOPO_EDGES = 3, RM_TOPO_FACES = 4,
+                    RM_TOPO_CELLS = 5, RM_TOPO_EULER = 6, RM_TOPO_TUNNELS = 7, RM_TOPO_EXTERIOR_POINTS = 8, RM_TOPO_COUNTS = 9 };
+enum rm_topostat { RM_TOPO_STAT_BRICKS = 0, RM_TOPO_STAT_BRICKS_KEPT = 1, RM_TOPO_STAT_BRICKS_INSIDE = 2,
+                   RM_TOPO_STAT_EVALUATIONS = 3, RM_TOPO_STAT_MERGE_PASSES = 4, RM_TOPO_STAT_SCRATCH_BYTES = 5, RM_TOPO_STATS = 6 };
+int rm_label_solid(rm_ctx* ctx, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                   uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats);
+int rm_label_occupancy(rm_ctx* ctx, uint32_t nx, uint32_t ny, uint32_t nz, const void* occupancy, int is_device, void* stream,
+                       uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats);
+/* Copies the last labelling out: out_body_moments B x 16 u64, out_cavity_moments C x 16 u64, out_labels nx * ny * nz u32; any
+ * may be NULL.  RM_ERR_ARG before any labelling.  is_device and stream as for rm_query_points (device arrays: the moments
+ * 8-byte aligned, the labels 4-byte); the next labelling call waits for a device read that is still running. */
+int rm_read_topology(rm_ctx* ctx, uint64_t* out_body_moments, uint64_t* out_cavity_moments, uint32_t* out_labels,
+                     int is_device, void* stream);
+
 /* Slicing (extension; DESIGN.md section 16 is the contract, to the last bit): the closed outlines of the solid d < level in a
  * stack of planes, as ordered polylines -- what a slicer or a section drawing needs, evaluated directly on a 2-D lattice
  * per layer instead of through a triangle mesh.  From the program, limits and material table as they are at the call.

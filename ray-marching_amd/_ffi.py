@@ -61,6 +61,14 @@ MESH_STAT_NAMES = ("vertices", "triangles", "bricks", "bricks_kept", "evaluation
 MASS_STAT_NAMES = ("bricks", "bricks_kept", "bricks_inside", "evaluations", "scratch_bytes")
 (RM_MASS_VOLUME, RM_MASS_MASS, RM_MASS_CX, RM_MASS_CY, RM_MASS_CZ, RM_MASS_IXX, RM_MASS_IYY, RM_MASS_IZZ, RM_MASS_IXY, RM_MASS_IYZ,
  RM_MASS_IXZ, RM_MASS_LO_X, RM_MASS_LO_Y, RM_MASS_LO_Z, RM_MASS_HI_X, RM_MASS_HI_Y, RM_MASS_HI_Z, RM_MASS_PROPS) = range(18)
+# solid topology (rm_label_solid / rm_label_occupancy / rm_read_topology): enum rm_topocount, enum rm_topostat, the label marks
+(RM_TOPO_BODIES, RM_TOPO_CAVITIES, RM_TOPO_POINTS, RM_TOPO_EDGES, RM_TOPO_FACES, RM_TOPO_CELLS, RM_TOPO_EULER, RM_TOPO_TUNNELS,
+ RM_TOPO_EXTERIOR_POINTS, RM_TOPO_COUNTS) = range(10)
+TOPO_COUNT_NAMES = ("bodies", "cavities", "points", "edges", "faces", "cells", "euler", "tunnels", "exterior_points")
+(RM_TOPO_STAT_BRICKS, RM_TOPO_STAT_BRICKS_KEPT, RM_TOPO_STAT_BRICKS_INSIDE, RM_TOPO_STAT_EVALUATIONS, RM_TOPO_STAT_MERGE_PASSES,
+ RM_TOPO_STAT_SCRATCH_BYTES, RM_TOPO_STATS) = range(7)
+TOPO_STAT_NAMES = ("bricks", "bricks_kept", "bricks_inside", "evaluations", "merge_passes", "scratch_bytes")
+RM_TOPO_CAVITY_BIT, RM_TOPO_EXTERIOR = 0x80000000, 0xFFFFFFFF
 # slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table): enum rm_slicecount, the indices of out_counts
 RM_SLICE_POINTS, RM_SLICE_CONTOURS, RM_SLICE_COUNTS = 0, 1, 2
 # lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit): enum rm_light, the parameter names in index order
@@ -191,6 +199,12 @@ def hip_lib():
         L.rm_mass_moments.restype = C.c_int
         L.rm_mass_from_moments.argtypes = [C.POINTER(u64), u32, f3, f3, C.c_double, C.POINTER(C.c_double), u32]
         L.rm_mass_from_moments.restype = C.c_int
+        L.rm_label_solid.argtypes = [vp, f3, f3, u32, u32, u32, C.c_float, C.POINTER(u64), u32, C.POINTER(u64), u32]
+        L.rm_label_solid.restype = C.c_int
+        L.rm_label_occupancy.argtypes = [vp, u32, u32, u32, vp, C.c_int, vp, C.POINTER(u64), u32, C.POINTER(u64), u32]
+        L.rm_label_occupancy.restype = C.c_int
+        L.rm_read_topology.argtypes = [vp, vp, vp, vp, C.c_int, vp]
+        L.rm_read_topology.restype = C.c_int
         L.rm_slice_contours.argtypes = [vp, u32, f3, f3, u32, u32, f3, u32, C.c_float, u32, C.POINTER(u64), u32]
         L.rm_slice_contours.restype = C.c_int
         L.rm_read_slices.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]

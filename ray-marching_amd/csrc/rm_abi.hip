@@ -30,6 +30,7 @@
 #include "rm_mesh_bound.h"
 #include "rm_mesh_sparse.h"
 #include "rm_mass.h"
+#include "rm_topology.h"
 #include "rm_slice.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
@@ -160,6 +161,11 @@ struct rm_ctx {
     bool slice_valid = false;
     uint64_t slice_p = 0, slice_c = 0;
     uint32_t slice_layers = 0, slice_flags = 0;
+    // solid topology (rm_topology.h): the label volume and the components' rows of the last labelling, in buffers of their own
+    // (its scratch is d_mscratch)
+    DevBuf<char> d_tlabels, d_trows;
+    bool topo_valid = false;
+    uint64_t topo_n = 0, topo_b = 0, topo_c = 0;
     // scratch for host-destination draws and batch uniforms
     DevBuf<char> d_out;
     DevBuf<rm_uniforms> d_frames;
@@ -1587,6 +1593,19 @@ MassCountFn mass_count_kernel(int loop) {
 }
 static_assert(rmk::kMoments == (uint32_t)RM_MOMENTS, "a row holds the moments of enum rm_moment");
 constexpr uint32_t kMaxMassDim = 4096u;  // rm_mass_moments: every sum below 2^60 (rm_abi.h)
+using TopoProbeFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, double, double, uint8_t*, unsigned long long*);
+TopoProbeFn topo_probe_kernel(int loop) {
+    return with_loop(loop, [](auto tag) -> TopoProbeFn { return rmk::rm_topo_probe_kernel<decltype(tag)::value>; });
+}
+using TopoOccupancyFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, const uint8_t*, uint8_t*, unsigned long long*);
+TopoOccupancyFn topo_occupancy_kernel(int loop) {
+    return with_loop(loop, [](auto tag) -> TopoOccupancyFn { return rmk::rm_topo_occupancy_kernel<decltype(tag)::value>; });
+}
+constexpr uint32_t kMaxTopoDim = 1024u;        // rm_label_solid: labels are linear indices with the two top bits free ...
+constexpr uint64_t kMaxTopoPoints = 1ull << 28;  // ... and every moment stays far below 2^60
+constexpr uint32_t kMaxMergePasses = 8u;
+static_assert(rmk::kTopoFold == 256u, "TopoScratch folds the bricks' rows by the probe's blocks of 256");
+static_assert(rmk::kTopoExterior == RM_TOPO_EXTERIOR && rmk::kTopoCavityBit == RM_TOPO_CAVITY_BIT, "the label volume's marks");
 // One workgroup of `kernel` per grid entry, with the query's LDS columns behind the kernel's own LDS.
 template <class K, class... Args>
 int sparse_launch(rm_ctx* c, K kernel, uint32_t blocks, size_t shmem, hipStream_t s, Args... args) {
@@ -1933,6 +1952,225 @@ RM_EXPORT int rm_mass_from_moments(const uint64_t* moments, uint32_t n_moments, 
     out[RM_MASS_IYZ] = 0.0 - mass * central(1, 2, RM_MOMENT_YZ);
     out[RM_MASS_IXZ] = 0.0 - mass * central(0, 2, RM_MOMENT_XZ);
 #endif
+    return RM_OK;
+}
+
+// ---- solid topology (rm_topology.h) ----
+namespace {
+
+struct TopoGrid {
+    rmk::SparseGrid g;
+    uint32_t n, n_pblocks, n_rblocks;
+};
+TopoGrid topo_grid(const float* o, const float* st, uint32_t nx, uint32_t ny, uint32_t nz) {
+    TopoGrid t;
+    t.g = rmk::SparseGrid{o[0], o[1], o[2], st[0], st[1], st[2], nx, ny, nz,
+                          (nx + rmk::kBrick - 1u) / rmk::kBrick, (ny + rmk::kBrick - 1u) / rmk::kBrick, (nz + rmk::kBrick - 1u) / rmk::kBrick, 0u};
+    t.g.nb = t.g.bx * t.g.by * t.g.bz;  // (<= 2^21 with 1024 points per axis)
+    t.n = nx * ny * nz;                 // (<= 2^28)
+    t.n_pblocks = (t.g.nb + 255u) / 256u;
+    t.n_rblocks = (t.n + rmk::kTopoRankBlock - 1u) / rmk::kTopoRankBlock;
+    return t;
+}
+bool topo_lattice_ok(uint32_t nx, uint32_t ny, uint32_t nz) {
+    return nx >= 2 && ny >= 2 && nz >= 2 && nx <= kMaxTopoDim && ny <= kMaxTopoDim && nz <= kMaxTopoDim &&
+           (uint64_t)nx * ny * nz <= kMaxTopoPoints;
+}
+
+// From the occupancy in T.occ on: local labelling; merge, flatten and verify until no pair of neighbours has two roots; the
+// exterior; the numbering; the rows, the counts and the label volume.  counts: RM_TOPO_COUNTS words.
+int label_lattice(rm_ctx* c, const char* fn, hipStream_t s, const TopoGrid& G, const rml::TopoScratch& T, uint64_t* counts,
+                  uint64_t* merge_passes) {
+    const rmk::SparseGrid& g = G.g;
+    char* sc = c->d_mscratch.p;
+    uint32_t* parent = T.parent.at(sc);
+    const uint8_t* occ = T.occ.at(sc);
+    uint8_t* ext = T.ext.at(sc);
+    unsigned long long* rows = T.rows.at(sc);
+    unsigned long long* rsums = T.rsums.at(sc);
+    unsigned long long* rtot = T.rtot.at(sc);
+    unsigned long long* result = T.result.at(sc);
+    int rc = c->d_tlabels.reserve(c, (size_t)G.n * 4u, "label volume");
+    if (rc != RM_OK) return rc;
+    uint32_t* labels = c->d_tlabels.as<uint32_t>();
+    const uint32_t point_blocks = (G.n + 255u) / 256u;
+    unsigned long long row[RM_MOMENTS];
+    // the bricks' rows -> result: 256 rows to a workgroup, then the mass reducer over the folded ones
+    unsigned long long* folded = T.folded.at(sc);
+    const auto reduce_rows = [&] {
+        hipLaunchKernelGGL(rmk::rm_topo_fold_kernel, dim3(G.n_pblocks), dim3(256), 0, s, static_cast<const unsigned long long*>(rows), g.nb, folded);
+        hipLaunchKernelGGL(rmk::rm_mass_reduce_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned long long*>(folded), G.n_pblocks,
+                           static_cast<const unsigned long long*>(nullptr), 0u, result);
+    };
+    hipLaunchKernelGGL(rmk::rm_topo_local_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, parent);
+    // A bounded host loop over a convergent process: one pass unites everything unless a union was lost, which the verification
+    // after the kernel boundary (every write visible) would find.
+    uint32_t passes = 0;
+    for (;;) {
+        passes++;
+        hipLaunchKernelGGL(rmk::rm_topo_merge_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, parent);
+        hipLaunchKernelGGL(rmk::rm_topo_flatten_kernel, dim3(point_blocks), dim3(256), 0, s, G.n, parent);
+        hipLaunchKernelGGL(rmk::rm_topo_verify_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, static_cast<const uint32_t*>(parent), rows);
+        reduce_rows();
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(row, result, sizeof row, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (row[4] == 0ull) break;
+        if (passes == kMaxMergePasses)
+            return fail(c, RM_ERR_DEVICE, "%s: %llu pairs of neighbours still have different roots after %u merge passes", fn, row[4], passes);
+    }
+    HIP_TRY(c, hipMemsetAsync(ext, 0, G.n, s));
+    hipLaunchKernelGGL(rmk::rm_topo_exterior_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, static_cast<const uint32_t*>(parent), ext);
+    hipLaunchKernelGGL(rmk::rm_topo_root_sum_kernel, dim3(G.n_rblocks), dim3(256), 0, s, G.n, occ, static_cast<const uint32_t*>(parent),
+                       static_cast<const uint8_t*>(ext), rsums);
+    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, rsums, G.n_rblocks, rtot);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long tot[2] = {0ull, 0ull};
+    HIP_TRY(c, hipMemcpyAsync(tot, rtot, sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const uint64_t B = tot[0], C = tot[1];
+    const rml::TopoRows R(B, C);
+    if (R.bytes > 0u) {
+        if ((rc = c->d_trows.reserve(c, R.bytes, "component rows")) != RM_OK) return rc;
+        hipLaunchKernelGGL(rmk::rm_topo_rows_init_kernel, dim3((uint32_t)(((B + C) * rmk::kMoments + 255u) / 256u)), dim3(256), 0, s,
+                           (uint32_t)(B + C), R.bodies.at(c->d_trows.p));
+    }
+    hipLaunchKernelGGL(rmk::rm_topo_rank_kernel, dim3(G.n_rblocks), dim3(256), 0, s, G.n, occ, static_cast<const uint32_t*>(parent),
+                       static_cast<const uint8_t*>(ext), static_cast<const unsigned long long*>(rsums), labels);
+    hipLaunchKernelGGL(rmk::rm_topo_rows_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, static_cast<const uint32_t*>(parent), labels, (uint32_t)B,
+                       R.bodies.at(c->d_trows.p), rows);
+    reduce_rows();
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(row, result, sizeof row, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const uint64_t V = row[0], E = row[1], F = row[2], K = row[3];
+    const int64_t euler = (int64_t)V - (int64_t)E + (int64_t)F - (int64_t)K;
+    counts[RM_TOPO_BODIES] = B;
+    counts[RM_TOPO_CAVITIES] = C;
+    counts[RM_TOPO_POINTS] = V;
+    counts[RM_TOPO_EDGES] = E;
+    counts[RM_TOPO_FACES] = F;
+    counts[RM_TOPO_CELLS] = K;
+    counts[RM_TOPO_EULER] = (uint64_t)euler;
+    counts[RM_TOPO_TUNNELS] = (uint64_t)((int64_t)B + (int64_t)C - euler);
+    counts[RM_TOPO_EXTERIOR_POINTS] = row[4];
+    *merge_passes = passes;
+    c->topo_valid = true;
+    c->topo_n = G.n;
+    c->topo_b = B;
+    c->topo_c = C;
+    return RM_OK;
+}
+
+}  // namespace
+
+RM_EXPORT int rm_label_solid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                             uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_counts || !out_stats) return fail(c, RM_ERR_NULL, "rm_label_solid: out_counts or out_stats is NULL");
+    if (n_counts < (uint32_t)RM_TOPO_COUNTS) return fail(c, RM_ERR_ARG, "rm_label_solid: n_counts %u < RM_TOPO_COUNTS", n_counts);
+    if (n_stats < (uint32_t)RM_TOPO_STATS) return fail(c, RM_ERR_ARG, "rm_label_solid: n_stats %u < RM_TOPO_STATS", n_stats);
+    if (int rc = check_lattice(c, "rm_label_solid", origin, step)) return rc;
+    if (int rc = check_iso(c, "rm_label_solid", level, 0u)) return rc;
+    if (!topo_lattice_ok(nx, ny, nz))
+        return fail(c, RM_ERR_RANGE, "rm_label_solid: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", nx, ny, nz);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);  // after a device read of the previous labelling, too
+    if (rc != RM_OK) return rc;
+    if (shmem + 4096u > std::max<size_t>(c->max_lds, 64u * 1024u))
+        return fail(c, RM_ERR_TOO_LARGE, "rm_label_solid: the program needs %zu bytes of LDS per workgroup", shmem + 4096u);
+    // the bounds of the program, for points up to the lattice's largest coordinate (as the kernels compute it)
+    double P = 0.0;
+    const uint32_t dims[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; a++) {
+        const float last = origin[a] + (float)(dims[a] - 1u) * step[a];
+        P = std::fmax(P, std::fmax(std::fabs((double)origin[a]), std::fabs((double)last)));
+    }
+    RmProgramBound bound;
+    if ((rc = rm_program_bound(c->cmd[0], c->cmd.data() + 1, (uint32_t)c->cmd.size() - 1u, P, &bound)) != RM_OK) return rc;
+    const TopoGrid G = topo_grid(origin, step, nx, ny, nz);
+    const rml::TopoScratch T(G.n, G.g.nb, G.n_pblocks, G.n_rblocks);
+    if ((rc = c->d_mscratch.reserve(c, T.bytes)) != RM_OK) return rc;
+    c->topo_valid = false;  // its buffers change from here on
+    char* sc = c->d_mscratch.p;
+    unsigned long long* evals = T.evals.at(sc);
+    HIP_TRY(c, hipMemsetAsync(evals, 0, 8, s));
+    if ((rc = sparse_launch(c, topo_probe_kernel(loop), G.n_pblocks, shmem, s, Q, G.g, level, bound.L, 2.0 * bound.E, T.cls.at(sc),
+                            T.psums.at(sc))) != RM_OK)
+        return rc;
+    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, T.psums.at(sc), G.n_pblocks, T.ptot.at(sc));
+    if ((rc = sparse_launch(c, topo_occupancy_kernel(loop), G.g.nb, shmem, s, Q, G.g, level, static_cast<const uint8_t*>(T.cls.at(sc)),
+                            T.occ.at(sc), evals)) != RM_OK)
+        return rc;
+    uint64_t counts[RM_TOPO_COUNTS], passes = 0;
+    if ((rc = label_lattice(c, "rm_label_solid", s, G, T, counts, &passes)) != RM_OK) return rc;
+    unsigned long long tot[2] = {0ull, 0ull}, ev = 0ull;
+    HIP_TRY(c, hipMemcpyAsync(tot, T.ptot.at(sc), sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (int k = 0; k < RM_TOPO_COUNTS; k++) out_counts[k] = counts[k];
+    out_stats[RM_TOPO_STAT_BRICKS] = G.g.nb;
+    out_stats[RM_TOPO_STAT_BRICKS_KEPT] = tot[0];
+    out_stats[RM_TOPO_STAT_BRICKS_INSIDE] = tot[1];
+    out_stats[RM_TOPO_STAT_EVALUATIONS] = G.g.nb + ev;
+    out_stats[RM_TOPO_STAT_MERGE_PASSES] = passes;
+    out_stats[RM_TOPO_STAT_SCRATCH_BYTES] = T.bytes;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_label_occupancy(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz, const void* occupancy, int is_device, void* stream,
+                                 uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
+    if (!c) return RM_ERR_NULL;
+    if (!occupancy || !out_counts || !out_stats) return fail(c, RM_ERR_NULL, "rm_label_occupancy: occupancy, out_counts or out_stats is NULL");
+    if (n_counts < (uint32_t)RM_TOPO_COUNTS) return fail(c, RM_ERR_ARG, "rm_label_occupancy: n_counts %u < RM_TOPO_COUNTS", n_counts);
+    if (n_stats < (uint32_t)RM_TOPO_STATS) return fail(c, RM_ERR_ARG, "rm_label_occupancy: n_stats %u < RM_TOPO_STATS", n_stats);
+    if (!topo_lattice_ok(nx, ny, nz))
+        return fail(c, RM_ERR_RANGE, "rm_label_occupancy: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", nx, ny, nz);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    order_with_previous(c, s);  // after a device read of the previous labelling, too
+    const float zero[3] = {0.0f, 0.0f, 0.0f}, one[3] = {1.0f, 1.0f, 1.0f};
+    const TopoGrid G = topo_grid(zero, one, nx, ny, nz);
+    const rml::TopoScratch T(G.n, G.g.nb, G.n_pblocks, G.n_rblocks);
+    int rc = c->d_mscratch.reserve(c, T.bytes);
+    if (rc != RM_OK) return rc;
+    c->topo_valid = false;  // its buffers change from here on
+    char* sc = c->d_mscratch.p;
+    if (is_device) {
+        // the caller's array is ready when the work queued on its stream is done; the call is synchronous anyway
+        const hipStream_t su = user_stream(c, stream);
+        if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
+    }
+    HIP_TRY(c, hipMemcpyAsync(T.occ.at(sc), occupancy, G.n, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    uint64_t counts[RM_TOPO_COUNTS], passes = 0;
+    if ((rc = label_lattice(c, "rm_label_occupancy", s, G, T, counts, &passes)) != RM_OK) return rc;
+    for (int k = 0; k < RM_TOPO_COUNTS; k++) out_counts[k] = counts[k];
+    for (int k = 0; k < RM_TOPO_STATS; k++) out_stats[k] = 0u;
+    out_stats[RM_TOPO_STAT_MERGE_PASSES] = passes;
+    out_stats[RM_TOPO_STAT_SCRATCH_BYTES] = T.bytes;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_read_topology(rm_ctx* c, uint64_t* out_body_moments, uint64_t* out_cavity_moments, uint32_t* out_labels, int is_device,
+                               void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!c->topo_valid) return fail(c, RM_ERR_ARG, "rm_read_topology: nothing has been labelled");
+    if (is_device && (misaligned(out_body_moments, 8) || misaligned(out_cavity_moments, 8) || misaligned(out_labels, 4)))
+        return fail(c, RM_ERR_ARG, "rm_read_topology: device arrays need 8-byte alignment (out_labels: 4-byte)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = dest_stream(c, is_device, stream);
+    order_with_previous(c, s);  // (the next labelling call waits for this stream in turn)
+    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const rml::TopoRows R(c->topo_b, c->topo_c);
+    const char* rows = c->d_trows.p;
+    if (out_body_moments && R.bodies.bytes) HIP_TRY(c, hipMemcpyAsync(out_body_moments, R.bodies.at(rows), R.bodies.bytes, kind, s));
+    if (out_cavity_moments && R.cavities.bytes) HIP_TRY(c, hipMemcpyAsync(out_cavity_moments, R.cavities.at(rows), R.cavities.bytes, kind, s));
+    if (out_labels) HIP_TRY(c, hipMemcpyAsync(out_labels, c->d_tlabels.p, (size_t)c->topo_n * 4u, kind, s));
+    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
     return RM_OK;
 }
 

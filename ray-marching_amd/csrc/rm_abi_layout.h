@@ -101,6 +101,33 @@ struct MassKeptScratch {
     explicit MassKeptScratch(uint64_t K) : klist(a.take<uint32_t>(K)), krows(a.take<unsigned long long>(K * 16u)), bytes(a.total) {}
 };
 
+// rm_label_solid / rm_label_occupancy, for a lattice of n points in nb bricks: per point its parent (4 B), its occupancy and its
+// root's exterior mark (1 B each); per brick its class (1 B) and one row of 16 words (128 B: the verify and the count pass, one
+// after the other); per 256 bricks those rows folded into one and the probe's block sum, per 2048 points the numbering's;
+// totals, the evaluation count and the reduced row.
+struct TopoScratch {
+    Carver a;
+    Region<uint32_t> parent;
+    Region<uint8_t> occ, ext, cls;
+    Region<unsigned long long> rows, folded, psums, rsums, ptot, rtot, evals, result;
+    size_t bytes;
+    TopoScratch(uint32_t n, uint32_t nb, uint32_t n_pblocks, uint32_t n_rblocks)
+        : parent(a.take<uint32_t>(n)), occ(a.take<uint8_t>(n)), ext(a.take<uint8_t>(n)), cls(a.take<uint8_t>(nb)),
+          rows(a.take<unsigned long long>((size_t)nb * 16u)), folded(a.take<unsigned long long>((size_t)n_pblocks * 16u)),
+          psums(a.take<unsigned long long>(n_pblocks)), rsums(a.take<unsigned long long>(n_rblocks)),
+          ptot(a.take<unsigned long long>(2)), rtot(a.take<unsigned long long>(2)), evals(a.take<unsigned long long>(2)),
+          result(a.take<unsigned long long>(16)), bytes(a.total) {}
+};
+
+// ... and the result: the label volume (4 B per point) in a buffer of its own, and the bodies' rows, then the cavities' (16
+// words each), in another, allocated once B and C are known.
+struct TopoRows {
+    Carver a;
+    Region<unsigned long long> bodies, cavities;
+    size_t bytes;
+    TopoRows(uint64_t B, uint64_t C) : bodies(a.take<unsigned long long>(B * 16u)), cavities(a.take<unsigned long long>(C * 16u)), bytes(a.total) {}
+};
+
 // rm_slice_contours' per-layer tables: heights, layer_first, the first vertex of each layer of a batch of `per`, totals.
 // (heights and layer_first lie before anything `per` sizes: rm_read_slices finds layer_first without it.)
 struct SliceLayerTables {

@@ -540,6 +540,68 @@ class RayMarchingResources:
         props["moments"], props["stats"] = m.moments, m.stats
         return props
 
+    # -- solid topology (rm_label_solid / rm_label_occupancy / rm_read_topology) -----------------------------------------------
+    def label_solid(self, lo, hi, resolution, level=0.0):
+        """Bodies, cavities and tunnels of the solid map_scene < level inside the box [lo, hi], on the lattice extract_mesh
+        builds from (lo, hi, resolution) (2..1024 points per axis, at most 2^28 in all): a Topology."""
+        lo, step, n = self._box_lattice(lo, hi, resolution)
+        return self.label_solid_grid(lo, step, n, level)
+
+    def label_solid_grid(self, origin, step, shape, level=0.0):
+        """label_solid on an exact lattice (origin, step, shape as sample_grid takes them)."""
+        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
+        counts = (C.c_uint64 * _ffi.RM_TOPO_COUNTS)()
+        stats = (C.c_uint64 * _ffi.RM_TOPO_STATS)()
+        self._check(self._L.rm_label_solid(self._h, fp(o), fp(s), nx, ny, nz, float(level), counts, _ffi.RM_TOPO_COUNTS, stats,
+                                           _ffi.RM_TOPO_STATS))
+        return self._read_topology(counts, stats, o, s, (nx, ny, nz))
+
+    def label_occupancy(self, occupancy):
+        """rm_label_occupancy: the topology of a caller's occupancy, indexed [k, j, i] (shape (nz, ny, nx); nonzero = inside): a
+        numpy array of a one-byte type (bool, uint8, int8), or such a contiguous torch tensor on this context's GPU, read after
+        the work queued on torch.cuda.current_stream().  The Topology's lattice is the unit lattice at the origin."""
+        if type(occupancy).__module__.split(".")[0] == "torch":
+            t = occupancy
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("occupancy is on %s; this context is on cuda:%d" % (t.device, self.device))
+            if t.element_size() != 1 or t.dim() != 3 or not t.is_contiguous():
+                raise ValueError("occupancy must be a contiguous 3-D tensor of a one-byte type")
+            nz, ny, nx = (int(x) for x in t.shape)
+            ptr, is_device, stream, keep = C.c_void_p(t.data_ptr()), 1, C.c_void_p(self._torch_stream(t)), t
+        else:
+            a = np.asarray(occupancy)
+            if a.ndim != 3 or a.dtype.itemsize != 1:
+                raise ValueError("occupancy must be a 3-D array of a one-byte type, indexed [k, j, i]")
+            keep = np.ascontiguousarray(a)
+            nz, ny, nx = keep.shape
+            ptr, is_device, stream = C.c_void_p(keep.ctypes.data), 0, None
+        if min(nx, ny, nz) < 2:
+            raise ValueError("a lattice needs at least 2 points per axis, not %s" % ((nx, ny, nz),))
+        counts = (C.c_uint64 * _ffi.RM_TOPO_COUNTS)()
+        stats = (C.c_uint64 * _ffi.RM_TOPO_STATS)()
+        self._check(self._L.rm_label_occupancy(self._h, nx, ny, nz, ptr, is_device, stream, counts, _ffi.RM_TOPO_COUNTS, stats,
+                                               _ffi.RM_TOPO_STATS))
+        del keep
+        return self._read_topology(counts, stats, np.zeros(3, dtype=np.float32), np.ones(3, dtype=np.float32), (nx, ny, nz))
+
+    def _read_topology(self, counts, stats, origin, step, shape):
+        """The Topology of the labelling call that just returned: its counts and statistics, and both row tables read back."""
+        cd = {name: int(counts[k]) for k, name in enumerate(_ffi.TOPO_COUNT_NAMES)}
+        for name in ("euler", "tunnels"):                                    # two's-complement int64
+            cd[name] -= (cd[name] >> 63) << 64
+        sd = {name: int(stats[k]) for k, name in enumerate(_ffi.TOPO_STAT_NAMES)}
+        body = np.zeros((cd["bodies"], _ffi.RM_MOMENTS), dtype=np.uint64)
+        cav = np.zeros((cd["cavities"], _ffi.RM_MOMENTS), dtype=np.uint64)
+        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+        if body.size or cav.size:
+            self._check(self._L.rm_read_topology(self._h, ptr(body), ptr(cav), None, 0, None))
+        return Topology(self, cd, sd, body, cav, origin, step, shape)
+
+    def read_topology_device(self, body_moments_ptr=0, cavity_moments_ptr=0, labels_ptr=0, stream=None):
+        """rm_read_topology of the last labelling call into device memory (integer addresses; 0 = not wanted), asynchronous."""
+        self._check(self._L.rm_read_topology(self._h, C.c_void_p(body_moments_ptr or None), C.c_void_p(cavity_moments_ptr or None),
+                                             C.c_void_p(labels_ptr or None), 1, C.c_void_p(stream) if stream else None))
+
     def _read_mesh(self, V, T, normals, ids, device):
         """rm_read_mesh of the extraction that just returned V vertices and T triangles, as a mesh.Mesh."""
         from . import mesh as _mesh
@@ -722,6 +784,39 @@ class MassMoments:
 
     def properties(self, density=1.0):
         return mass_from_moments(self.moments, self.origin, self.step, density)
+
+
+class Topology:
+    """The result of label_solid / label_occupancy.  bodies, cavities, euler, tunnels: ints; counts and stats: dicts
+    (_ffi.TOPO_COUNT_NAMES, _ffi.TOPO_STAT_NAMES); body_moments (B, 16) and cavity_moments (C, 16): uint64 rows of the
+    _ffi.RM_MOMENT_* words, in body and cavity order; origin, step (float32[3]) and shape of the lattice."""
+
+    def __init__(self, resources, counts, stats, body_moments, cavity_moments, origin, step, shape):
+        self._res = resources
+        self.counts, self.stats = counts, stats
+        self.bodies, self.cavities, self.euler, self.tunnels = counts["bodies"], counts["cavities"], counts["euler"], counts["tunnels"]
+        self.body_moments, self.cavity_moments = body_moments, cavity_moments
+        self.origin, self.step, self.shape = origin, step, shape
+
+    def __repr__(self):
+        return "Topology(%d bodies, %d cavities, %d tunnels, euler %d on %s)" % (self.bodies, self.cavities, self.tunnels, self.euler,
+                                                                               "x".join(map(str, self.shape)))
+
+    def body_properties(self, density=1.0):
+        """mass_from_moments of every body's row: a list of dicts."""
+        return [mass_from_moments(row, self.origin, self.step, density) for row in self.body_moments]
+
+    def cavity_properties(self):
+        """mass_from_moments (density 1) of every cavity's row, over the cavity's outside points."""
+        return [mass_from_moments(row, self.origin, self.step, 1.0) for row in self.cavity_moments]
+
+    def labels(self):
+        """The label volume, uint32 (nz, ny, nx): a body's number, _ffi.RM_TOPO_CAVITY_BIT | a cavity's number, or
+        _ffi.RM_TOPO_EXTERIOR.  Read on demand, and only while this is the context's last labelling."""
+        nx, ny, nz = self.shape
+        out = np.empty((nz, ny, nx), dtype=np.uint32)
+        self._res._check(self._res._L.rm_read_topology(self._res._h, None, None, out.ctypes.data, 0, None))
+        return out
 
 
 MASS_PROP_NAMES = ("volume", "mass", "cx", "cy", "cz", "ixx", "iyy", "izz", "ixy", "iyz", "ixz", "lo_x", "lo_y", "lo_z", "hi_x", "hi_y",
