@@ -219,6 +219,34 @@ pub const RM_TOPO_STAT_MERGE_PASSES: c_int = 4;
 pub const RM_TOPO_STAT_SCRATCH_BYTES: c_int = 5;
 pub const RM_TOPO_STATS: c_int = 6;
 
+// Distance transform (rm_distance_solid / rm_distance_occupancy / rm_distance_features / rm_read_distance).
+/// `RM_DIST_INSIDE_BIT`: ORed into the squared distance of an inside point of the distance volume.
+pub const RM_DIST_INSIDE_BIT: u32 = 0x8000_0000;
+/// `RM_DIST_NONE`: the squared distance of an outside point when the solid is empty.
+pub const RM_DIST_NONE: u32 = 0x7FFF_FFFF;
+/// `RM_DIST_SKIP`: as a squared radius of `distance_features`, leaves that half out.
+pub const RM_DIST_SKIP: u32 = 0xFFFF_FFFF;
+// enum rm_distcount: indices into the counts of a distance call; RM_DIST_COUNTS is their number
+pub const RM_DIST_POINTS: c_int = 0;
+pub const RM_DIST_MAX_INSIDE: c_int = 1;
+pub const RM_DIST_ARGMAX_INSIDE: c_int = 2;
+pub const RM_DIST_MAX_OUTSIDE: c_int = 3;
+pub const RM_DIST_ARGMAX_OUTSIDE: c_int = 4;
+pub const RM_DIST_COUNTS: c_int = 5;
+// enum rm_distfeature: indices into the counts of rm_distance_features; RM_DIST_FEATURE_COUNTS is their number
+pub const RM_DIST_CORE: c_int = 0;
+pub const RM_DIST_THIN: c_int = 1;
+pub const RM_DIST_GAP_CORE: c_int = 2;
+pub const RM_DIST_NARROW: c_int = 3;
+pub const RM_DIST_FEATURE_COUNTS: c_int = 4;
+// enum rm_diststat: indices into the statistics of a distance call; RM_DIST_STATS is their number
+pub const RM_DIST_STAT_BRICKS: c_int = 0;
+pub const RM_DIST_STAT_BRICKS_KEPT: c_int = 1;
+pub const RM_DIST_STAT_BRICKS_INSIDE: c_int = 2;
+pub const RM_DIST_STAT_EVALUATIONS: c_int = 3;
+pub const RM_DIST_STAT_SCRATCH_BYTES: c_int = 4;
+pub const RM_DIST_STATS: c_int = 5;
+
 // Slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table).
 // enum rm_slicecount: indices into the counts of rm_slice_contours; RM_SLICE_COUNTS is their number
 pub const RM_SLICE_POINTS: c_int = 0;
@@ -320,6 +348,12 @@ extern "C" {
                               stream: *mut c_void, out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
     pub fn rm_read_topology(ctx: *mut rm_ctx, out_body_moments: *mut u64, out_cavity_moments: *mut u64, out_labels: *mut u32,
                             is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_distance_solid(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, level: f32,
+                             out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_distance_occupancy(ctx: *mut rm_ctx, nx: u32, ny: u32, nz: u32, occupancy: *const c_void, is_device: c_int,
+                                 stream: *mut c_void, out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_distance_features(ctx: *mut rm_ctx, r2_wall: u32, r2_gap: u32, out_counts: *mut u64, n_counts: u32) -> c_int;
+    pub fn rm_read_distance(ctx: *mut rm_ctx, out_d2: *mut u32, out_mask: *mut c_void, is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_slice_contours(ctx: *mut rm_ctx, axis: u32, origin_uv: *const f32, step_uv: *const f32, nu: u32, nv: u32,
                              heights: *const f32, n_layers: u32, level: f32, flags: u32, out_counts: *mut u64,
                              n_counts: u32) -> c_int;
@@ -437,6 +471,8 @@ pub struct RayMarchingResources {
     slices: Cell<Option<(u64, u64, u32)>>,
     /// (bodies, cavities, lattice points) of the last successful labelling call: what `read_topology` writes
     topology: Cell<Option<(u64, u64, u64)>>,
+    /// (lattice points, whether a features call has made a mask) of the last successful distance call: what `read_distance` writes
+    distance: Cell<Option<(u64, bool)>>,
 }
 
 unsafe impl Send for RayMarchingResources {} // a context may move between threads; it is not Sync
@@ -450,7 +486,7 @@ impl RayMarchingResources {
             let msg = unsafe { CStr::from_ptr(rm_last_error(std::ptr::null_mut())) };
             return Err(RmError { status: rc, message: msg.to_string_lossy().into_owned() });
         }
-        Ok(Self { ctx, mesh: Cell::new(None), slices: Cell::new(None), topology: Cell::new(None) })
+        Ok(Self { ctx, mesh: Cell::new(None), slices: Cell::new(None), topology: Cell::new(None), distance: Cell::new(None) })
     }
 
     fn check(&self, rc: c_int) -> Result<(), RmError> {
@@ -721,6 +757,79 @@ impl RayMarchingResources {
         let pc = out_cavity_moments.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
         let pl = out_labels.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
         self.check(unsafe { rm_read_topology(self.ctx, pb, pc, pl, 0, std::ptr::null_mut()) })
+    }
+
+    /// The exact squared Euclidean distance transform of the solid `map_scene < level` on the lattice (`rm_distance_solid`;
+    /// 2..1024 points per axis, at most 2^28 in all), in index units: fills `out_counts` (at least `RM_DIST_COUNTS` entries,
+    /// indexed by `RM_DIST_*`: the inside points, the largest inside and outside squared distance and where) and `out_stats`
+    /// (at least `RM_DIST_STATS`, indexed by `RM_DIST_STAT_*`).  Exact integers: every run gives the same words.
+    /// `read_distance` copies the distance volume out.  Leaves the context's mesh, slices and labelling alone.
+    pub fn distance_solid(&self, origin: [f32; 3], step: [f32; 3], nx: u32, ny: u32, nz: u32, level: f32, out_counts: &mut [u64],
+                          out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(out_counts.len() >= RM_DIST_COUNTS as usize, "distance_solid: out_counts is shorter than RM_DIST_COUNTS entries");
+        assert!(out_stats.len() >= RM_DIST_STATS as usize, "distance_solid: out_stats is shorter than RM_DIST_STATS entries");
+        self.distance.set(None);  // a failed call may have released the previous volume
+        self.check(unsafe {
+            rm_distance_solid(self.ctx, origin.as_ptr(), step.as_ptr(), nx, ny, nz, level, out_counts.as_mut_ptr(), RM_DIST_COUNTS as u32,
+                              out_stats.as_mut_ptr(), RM_DIST_STATS as u32)
+        })?;
+        self.distance.set(Some((nx as u64 * ny as u64 * nz as u64, false)));
+        Ok(())
+    }
+
+    /// `distance_solid` of a caller's occupancy in host memory (`rm_distance_occupancy`): one byte per point, x fastest,
+    /// nonzero = inside.  The brick statistics are 0.
+    pub fn distance_occupancy(&self, nx: u32, ny: u32, nz: u32, occupancy: &[u8], out_counts: &mut [u64],
+                              out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(occupancy.len() as u64 >= nx as u64 * ny as u64 * nz as u64, "distance_occupancy: occupancy is shorter than nx * ny * nz bytes");
+        assert!(out_counts.len() >= RM_DIST_COUNTS as usize, "distance_occupancy: out_counts is shorter than RM_DIST_COUNTS entries");
+        assert!(out_stats.len() >= RM_DIST_STATS as usize, "distance_occupancy: out_stats is shorter than RM_DIST_STATS entries");
+        self.distance.set(None);  // a failed call may have released the previous volume
+        self.check(unsafe {
+            rm_distance_occupancy(self.ctx, nx, ny, nz, occupancy.as_ptr() as *const c_void, 0, std::ptr::null_mut(),
+                                  out_counts.as_mut_ptr(), RM_DIST_COUNTS as u32, out_stats.as_mut_ptr(), RM_DIST_STATS as u32)
+        })?;
+        self.distance.set(Some((nx as u64 * ny as u64 * nz as u64, false)));
+        Ok(())
+    }
+
+    /// Thin walls and narrow gaps of the last distance volume (`rm_distance_features`): the inside points that no ball of
+    /// squared radius `r2_wall` (index units) inside the solid covers, and the outside points that none of squared radius
+    /// `r2_gap` centred on an outside lattice point covers; `None` skips that half.  Fills `out_counts` (at least
+    /// `RM_DIST_FEATURE_COUNTS` entries, indexed by `RM_DIST_CORE`, `THIN`, `GAP_CORE`, `NARROW`); `read_distance` copies the
+    /// mask out.  `RM_ERR_ARG` before any distance call, `RM_ERR_RANGE` for a squared radius of 2^22 or more.
+    pub fn distance_features(&self, r2_wall: Option<u32>, r2_gap: Option<u32>, out_counts: &mut [u64]) -> Result<(), RmError> {
+        assert!(out_counts.len() >= RM_DIST_FEATURE_COUNTS as usize, "distance_features: out_counts is shorter than RM_DIST_FEATURE_COUNTS entries");
+        assert!(r2_wall != Some(RM_DIST_SKIP) && r2_gap != Some(RM_DIST_SKIP), "distance_features: None skips a half");
+        if let Some((n, _)) = self.distance.get() {
+            self.distance.set(Some((n, false)));  // a failed call may have released the previous mask
+        }
+        self.check(unsafe {
+            rm_distance_features(self.ctx, r2_wall.unwrap_or(RM_DIST_SKIP), r2_gap.unwrap_or(RM_DIST_SKIP), out_counts.as_mut_ptr(),
+                                 RM_DIST_FEATURE_COUNTS as u32)
+        })?;
+        if let Some((n, _)) = self.distance.get() {
+            self.distance.set(Some((n, true)));
+        }
+        Ok(())
+    }
+
+    /// The last distance volume (one word per lattice point: the squared distance, `RM_DIST_INSIDE_BIT` ORed in for an inside
+    /// point) and the last feature mask (one byte per point: 0 outside, 1 inside, 2 thin, 3 narrow).  `None` skips that output.
+    /// `RM_ERR_ARG` before any distance call, and for a mask before any features call on the last volume.
+    pub fn read_distance(&self, out_d2: Option<&mut [u32]>, out_mask: Option<&mut [u8]>) -> Result<(), RmError> {
+        let (n, has_mask) = match self.distance.get() {
+            Some((n, m)) => (n as usize, m),
+            None => return Err(RmError { status: RM_ERR_ARG, message: "read_distance: no distance volume has been computed".to_string() }),
+        };
+        if out_mask.is_some() && !has_mask {
+            return Err(RmError { status: RM_ERR_ARG, message: "read_distance: no features call has made a mask of this volume".to_string() });
+        }
+        assert!(out_d2.as_ref().map_or(true, |s| s.len() >= n), "read_distance: out_d2 is shorter than {} points", n);
+        assert!(out_mask.as_ref().map_or(true, |s| s.len() >= n), "read_distance: out_mask is shorter than {} points", n);
+        let pd = out_d2.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pm = out_mask.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr() as *mut c_void);
+        self.check(unsafe { rm_read_distance(self.ctx, pd, pm, 0, std::ptr::null_mut()) })
     }
 
     /// The mesh of the last successful `extract_mesh` (of the (vertices, triangles) it returned): positions (three per

@@ -522,6 +522,67 @@ int rm_label_occupancy(rm_ctx* ctx, uint32_t nx, uint32_t ny, uint32_t nz, const
 int rm_read_topology(rm_ctx* ctx, uint64_t* out_body_moments, uint64_t* out_cavity_moments, uint32_t* out_labels,
                      int is_device, void* stream);
 
+/* Distance transform (extension; DESIGN.md section 20 is the contract, to the last bit): how thick is the part, how wide are
+ * its gaps -- the exact squared Euclidean distance transform of the occupancy lattice, the largest inscribed ball, and the
+ * material (the clearance) that no ball of a given radius fits into.
+ * Lattice, values, "inside" and limits are rm_label_solid's: point (i, j, k) at o + (float)i * s per axis, inside iff
+ * rm_query_points' distance < level (NaN is outside; the empty program: max_dist), linear index i + nx * (j + ny * k), 2..1024
+ * points per axis and at most 2^28 in all (RM_ERR_RANGE otherwise), and the lattice counts as surrounded by ONE LAYER OF
+ * OUTSIDE POINTS: every point with a coordinate of -1, or of n on that axis.
+ * Distance is measured in index space, exactly.  For an inside point p, D2(p) is the minimum of |p - q|^2 over all outside
+ * points q, the surrounding layer included (so never more than min(i+1, nx-i, j+1, ny-j, k+1, nz-k)^2).  For an outside point
+ * p, D2(p) is the minimum of |p - q|^2 over all inside points q of the lattice; the layer plays no part, and when the solid is
+ * empty D2 = RM_DIST_NONE.  Every finite value is below 3 * 1023^2 < 2^22.  World distance is step * sqrt(D2) when the three
+ * steps are equal; this interface stays in index units.
+ * The distance volume: one u32 per point, x fastest -- D2, with RM_DIST_INSIDE_BIT ORed in for an inside point.
+ * out_counts[RM_DIST_*]:
+ *   POINTS                      the inside points (RM_TOPO_POINTS on the same lattice)
+ *   MAX_INSIDE, ARGMAX_INSIDE   the largest inside D2 and the smallest linear index that attains it: squared radius and centre
+ *                               of the largest inscribed ball.  An empty solid: 0 and 0xFFFFFFFF
+ *   MAX_OUTSIDE, ARGMAX_OUTSIDE the same over the outside points.  A full lattice: 0 and 0xFFFFFFFF; an empty solid:
+ *                               RM_DIST_NONE and 0
+ * out_stats[RM_DIST_STAT_*]: BRICKS, BRICKS_KEPT, BRICKS_INSIDE, EVALUATIONS as rm_mass_moments reports them for the same
+ * lattice and level (0 for rm_distance_occupancy); SCRATCH_BYTES, the device memory the call used besides the distance volume.
+ * rm_distance_occupancy transforms the caller's occupancy instead: one byte per point, x fastest, nonzero = inside; in host
+ * memory, or (is_device) in device memory, read after the work queued on `stream` (RM_STREAM_OWN: the context's).
+ * rm_distance_features works on the last distance volume, with squared radii in index units (RM_DIST_SKIP skips that half):
+ *   core   = { inside p : D2(p) > r2_wall }: the centres of closed balls of radius sqrt(r2_wall) that hold no outside point
+ *   opened = { p : some c in core has |p - c|^2 <= r2_wall }, a subset of the inside (the morphological opening)
+ *   THIN   = inside \ opened: the material that no ball of that radius fits into
+ *   NARROW   the same with the classes exchanged and r2_gap: the outside points that no ball of radius sqrt(r2_gap) centred on
+ *            an outside point of the lattice with D2 > r2_gap covers.  Centres lie on the lattice only: a solid nearer than
+ *            2 sqrt(r2_gap) to the lattice's border can report gap points against the border.
+ * The feature mask: one byte per point -- 0 outside and not narrow, 1 inside and not thin, 2 thin, 3 narrow; a skipped half
+ * leaves its class at 0 or 1.  out_counts[RM_DIST_CORE, THIN, GAP_CORE, NARROW]: the points of core, thin, the gap's core and
+ * narrow (0 for a skipped half).  (mask == 2) as bytes is an occupancy for rm_label_occupancy: the thin regions as bodies.
+ * rm_read_distance copies the last distance volume (out_d2, nx * ny * nz u32) and the last feature mask (out_mask, one byte per
+ * point) out; either may be NULL; is_device and stream as for rm_query_points (a device out_d2: 4-byte aligned); the next
+ * distance call waits for a device read that is still running.
+ * Every output is an integer defined by a minimum or a count: two runs, and any correct implementation, give identical words.
+ * The calls are synchronous on the context's own stream, ordered after its earlier work; they never touch the draw state, and
+ * the result lives in buffers of its own until the next distance call or rm_destroy: it replaces neither the context's mesh,
+ * its slices nor its labelling.  Errors (every check precedes the first launch, and a failed call leaves the outputs
+ * untouched): RM_ERR_NULL for a NULL output or occupancy; RM_ERR_ARG for n_counts < RM_DIST_COUNTS (features:
+ * RM_DIST_FEATURE_COUNTS), n_stats < RM_DIST_STATS, a level, origin or step that is not finite or a step <= 0, for
+ * rm_distance_features or rm_read_distance before any distance call, and for rm_read_distance asked for a mask that no
+ * features call has made of the last volume; RM_ERR_RANGE for the lattice, and for an r2 >= 2^22 that is not RM_DIST_SKIP;
+ * RM_ERR_DEVICE when device memory runs out (about 5 bytes per point, 4 more during the features); otherwise those of a query
+ * for the program and limits. */
+#define RM_DIST_INSIDE_BIT 0x80000000u /* distance volume: ORed into the D2 of an inside point */
+#define RM_DIST_NONE 0x7FFFFFFFu       /* distance volume: the D2 of an outside point when the solid is empty */
+#define RM_DIST_SKIP 0xFFFFFFFFu       /* rm_distance_features: leave this half out */
+enum rm_distcount { RM_DIST_POINTS = 0, RM_DIST_MAX_INSIDE = 1, RM_DIST_ARGMAX_INSIDE = 2, RM_DIST_MAX_OUTSIDE = 3,
+                    RM_DIST_ARGMAX_OUTSIDE = 4, RM_DIST_COUNTS = 5 };
+enum rm_distfeature { RM_DIST_CORE = 0, RM_DIST_THIN = 1, RM_DIST_GAP_CORE = 2, RM_DIST_NARROW = 3, RM_DIST_FEATURE_COUNTS = 4 };
+enum rm_diststat { RM_DIST_STAT_BRICKS = 0, RM_DIST_STAT_BRICKS_KEPT = 1, RM_DIST_STAT_BRICKS_INSIDE = 2,
+                   RM_DIST_STAT_EVALUATIONS = 3, RM_DIST_STAT_SCRATCH_BYTES = 4, RM_DIST_STATS = 5 };
+int rm_distance_solid(rm_ctx* ctx, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                      uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats);
+int rm_distance_occupancy(rm_ctx* ctx, uint32_t nx, uint32_t ny, uint32_t nz, const void* occupancy, int is_device, void* stream,
+                          uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats);
+int rm_distance_features(rm_ctx* ctx, uint32_t r2_wall, uint32_t r2_gap, uint64_t* out_counts, uint32_t n_counts);
+int rm_read_distance(rm_ctx* ctx, uint32_t* out_d2, void* out_mask, int is_device, void* stream);
+
 /* Slicing (extension; DESIGN.md section 16 is the contract, to the last bit): the closed outlines of the solid d < level in a
  * stack of planes, as ordered polylines -- what a slicer or a section drawing needs, evaluated directly on a 2-D lattice
  * per layer instead of through a triangle mesh.  From the program, limits and material table as they are at the call.

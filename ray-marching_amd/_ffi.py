@@ -69,6 +69,17 @@ TOPO_COUNT_NAMES = ("bodies", "cavities", "points", "edges", "faces", "cells", "
  RM_TOPO_STAT_SCRATCH_BYTES, RM_TOPO_STATS) = range(7)
 TOPO_STAT_NAMES = ("bricks", "bricks_kept", "bricks_inside", "evaluations", "merge_passes", "scratch_bytes")
 RM_TOPO_CAVITY_BIT, RM_TOPO_EXTERIOR = 0x80000000, 0xFFFFFFFF
+# distance transform (rm_distance_solid / rm_distance_occupancy / rm_distance_features / rm_read_distance): enum rm_distcount,
+# enum rm_distfeature, enum rm_diststat, the marks of the distance volume and the values of the feature mask
+RM_DIST_POINTS, RM_DIST_MAX_INSIDE, RM_DIST_ARGMAX_INSIDE, RM_DIST_MAX_OUTSIDE, RM_DIST_ARGMAX_OUTSIDE, RM_DIST_COUNTS = range(6)
+DIST_COUNT_NAMES = ("points", "max_inside", "argmax_inside", "max_outside", "argmax_outside")
+RM_DIST_CORE, RM_DIST_THIN, RM_DIST_GAP_CORE, RM_DIST_NARROW, RM_DIST_FEATURE_COUNTS = range(5)
+DIST_FEATURE_NAMES = ("core", "thin", "gap_core", "narrow")
+(RM_DIST_STAT_BRICKS, RM_DIST_STAT_BRICKS_KEPT, RM_DIST_STAT_BRICKS_INSIDE, RM_DIST_STAT_EVALUATIONS, RM_DIST_STAT_SCRATCH_BYTES,
+ RM_DIST_STATS) = range(6)
+DIST_STAT_NAMES = ("bricks", "bricks_kept", "bricks_inside", "evaluations", "scratch_bytes")
+RM_DIST_INSIDE_BIT, RM_DIST_NONE, RM_DIST_SKIP = 0x80000000, 0x7FFFFFFF, 0xFFFFFFFF
+DIST_MASK_OUTSIDE, DIST_MASK_INSIDE, DIST_MASK_THIN, DIST_MASK_NARROW = range(4)
 # slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table): enum rm_slicecount, the indices of out_counts
 RM_SLICE_POINTS, RM_SLICE_CONTOURS, RM_SLICE_COUNTS = 0, 1, 2
 # lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit): enum rm_light, the parameter names in index order
@@ -205,6 +216,14 @@ def hip_lib():
         L.rm_label_occupancy.restype = C.c_int
         L.rm_read_topology.argtypes = [vp, vp, vp, vp, C.c_int, vp]
         L.rm_read_topology.restype = C.c_int
+        L.rm_distance_solid.argtypes = [vp, f3, f3, u32, u32, u32, C.c_float, C.POINTER(u64), u32, C.POINTER(u64), u32]
+        L.rm_distance_solid.restype = C.c_int
+        L.rm_distance_occupancy.argtypes = [vp, u32, u32, u32, vp, C.c_int, vp, C.POINTER(u64), u32, C.POINTER(u64), u32]
+        L.rm_distance_occupancy.restype = C.c_int
+        L.rm_distance_features.argtypes = [vp, u32, u32, C.POINTER(u64), u32]
+        L.rm_distance_features.restype = C.c_int
+        L.rm_read_distance.argtypes = [vp, vp, vp, C.c_int, vp]
+        L.rm_read_distance.restype = C.c_int
         L.rm_slice_contours.argtypes = [vp, u32, f3, f3, u32, u32, f3, u32, C.c_float, u32, C.POINTER(u64), u32]
         L.rm_slice_contours.restype = C.c_int
         L.rm_read_slices.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]

@@ -31,6 +31,7 @@
 #include "rm_mesh_sparse.h"
 #include "rm_mass.h"
 #include "rm_topology.h"
+#include "rm_distance.h"
 #include "rm_slice.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
@@ -166,6 +167,11 @@ struct rm_ctx {
     DevBuf<char> d_tlabels, d_trows;
     bool topo_valid = false;
     uint64_t topo_n = 0, topo_b = 0, topo_c = 0;
+    // distance transform (rm_distance.h): the distance volume of the last distance call and the feature mask of the last features
+    // call on it, in buffers of their own (their scratch is d_mscratch)
+    DevBuf<char> d_dvol, d_dmask;
+    bool dist_valid = false, dist_mask_valid = false;
+    uint32_t dist_nx = 0, dist_ny = 0, dist_nz = 0;
     // scratch for host-destination draws and batch uniforms
     DevBuf<char> d_out;
     DevBuf<rm_uniforms> d_frames;
@@ -1606,6 +1612,9 @@ constexpr uint64_t kMaxTopoPoints = 1ull << 28;  // ... and every moment stays f
 constexpr uint32_t kMaxMergePasses = 8u;
 static_assert(rmk::kTopoFold == 256u, "TopoScratch folds the bricks' rows by the probe's blocks of 256");
 static_assert(rmk::kTopoExterior == RM_TOPO_EXTERIOR && rmk::kTopoCavityBit == RM_TOPO_CAVITY_BIT, "the label volume's marks");
+static_assert(rmk::kDistInside == RM_DIST_INSIDE_BIT && rmk::kDistNone == RM_DIST_NONE, "the distance volume's marks");
+static_assert(rml::kDistMaxAxis == kMaxTopoDim, "a column tile holds the longest axis");
+constexpr uint32_t kMaxDistR2 = 1u << 22;  // rm_distance_features: every finite D2 is below it
 // One workgroup of `kernel` per grid entry, with the query's LDS columns behind the kernel's own LDS.
 template <class K, class... Args>
 int sparse_launch(rm_ctx* c, K kernel, uint32_t blocks, size_t shmem, hipStream_t s, Args... args) {
@@ -1977,6 +1986,39 @@ bool topo_lattice_ok(uint32_t nx, uint32_t ny, uint32_t nz) {
            (uint64_t)nx * ny * nz <= kMaxTopoPoints;
 }
 
+// The occupancy {d < level} of a lattice, as rm_label_solid and rm_distance_solid fill it (rm_topology.h, probe and occupancy):
+// begin: the query's launch state and the program's bounds for points up to the lattice's largest coordinate (as the kernels
+// compute it), every check before the first launch; fill: probe, scan of the block sums (kept low, inside high -> ptot),
+// occupancy, the evaluations of the kept bricks' points in evals[0].
+struct SolidOccupancy {
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    RmProgramBound bound;
+};
+int solid_occupancy_begin(rm_ctx* c, const char* fn, hipStream_t s, const float* origin, const float* step, uint32_t nx, uint32_t ny,
+                          uint32_t nz, SolidOccupancy* O) {
+    int rc = query_begin(c, s, false, false, &O->Q, &O->loop, &O->shmem);
+    if (rc != RM_OK) return rc;
+    if (O->shmem + 4096u > std::max<size_t>(c->max_lds, 64u * 1024u))
+        return fail(c, RM_ERR_TOO_LARGE, "%s: the program needs %zu bytes of LDS per workgroup", fn, O->shmem + 4096u);
+    double P = 0.0;
+    const uint32_t dims[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; a++) {
+        const float last = origin[a] + (float)(dims[a] - 1u) * step[a];
+        P = std::fmax(P, std::fmax(std::fabs((double)origin[a]), std::fabs((double)last)));
+    }
+    return rm_program_bound(c->cmd[0], c->cmd.data() + 1, (uint32_t)c->cmd.size() - 1u, P, &O->bound);
+}
+int solid_occupancy_fill(rm_ctx* c, hipStream_t s, const SolidOccupancy& O, const TopoGrid& G, float level, uint8_t* cls,
+                         unsigned long long* psums, unsigned long long* ptot, uint8_t* occ, unsigned long long* evals) {
+    HIP_TRY(c, hipMemsetAsync(evals, 0, 8, s));
+    int rc = sparse_launch(c, topo_probe_kernel(O.loop), G.n_pblocks, O.shmem, s, O.Q, G.g, level, O.bound.L, 2.0 * O.bound.E, cls, psums);
+    if (rc != RM_OK) return rc;
+    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, psums, G.n_pblocks, ptot);
+    return sparse_launch(c, topo_occupancy_kernel(O.loop), G.g.nb, O.shmem, s, O.Q, G.g, level, static_cast<const uint8_t*>(cls), occ, evals);
+}
+
 // From the occupancy in T.occ on: local labelling; merge, flatten and verify until no pair of neighbours has two roots; the
 // exterior; the numbering; the rows, the counts and the label volume.  counts: RM_TOPO_COUNTS words.
 int label_lattice(rm_ctx* c, const char* fn, hipStream_t s, const TopoGrid& G, const rml::TopoScratch& T, uint64_t* counts,
@@ -2076,36 +2118,16 @@ RM_EXPORT int rm_label_solid(rm_ctx* c, const float* origin, const float* step, 
         return fail(c, RM_ERR_RANGE, "rm_label_solid: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", nx, ny, nz);
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = c->stream;
-    rmk::QueryLaunch Q;
-    int loop = 0;
-    size_t shmem = 0;
-    int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);  // after a device read of the previous labelling, too
+    SolidOccupancy O;
+    int rc = solid_occupancy_begin(c, "rm_label_solid", s, origin, step, nx, ny, nz, &O);  // after a device read of the previous labelling, too
     if (rc != RM_OK) return rc;
-    if (shmem + 4096u > std::max<size_t>(c->max_lds, 64u * 1024u))
-        return fail(c, RM_ERR_TOO_LARGE, "rm_label_solid: the program needs %zu bytes of LDS per workgroup", shmem + 4096u);
-    // the bounds of the program, for points up to the lattice's largest coordinate (as the kernels compute it)
-    double P = 0.0;
-    const uint32_t dims[3] = {nx, ny, nz};
-    for (int a = 0; a < 3; a++) {
-        const float last = origin[a] + (float)(dims[a] - 1u) * step[a];
-        P = std::fmax(P, std::fmax(std::fabs((double)origin[a]), std::fabs((double)last)));
-    }
-    RmProgramBound bound;
-    if ((rc = rm_program_bound(c->cmd[0], c->cmd.data() + 1, (uint32_t)c->cmd.size() - 1u, P, &bound)) != RM_OK) return rc;
     const TopoGrid G = topo_grid(origin, step, nx, ny, nz);
     const rml::TopoScratch T(G.n, G.g.nb, G.n_pblocks, G.n_rblocks);
     if ((rc = c->d_mscratch.reserve(c, T.bytes)) != RM_OK) return rc;
     c->topo_valid = false;  // its buffers change from here on
     char* sc = c->d_mscratch.p;
     unsigned long long* evals = T.evals.at(sc);
-    HIP_TRY(c, hipMemsetAsync(evals, 0, 8, s));
-    if ((rc = sparse_launch(c, topo_probe_kernel(loop), G.n_pblocks, shmem, s, Q, G.g, level, bound.L, 2.0 * bound.E, T.cls.at(sc),
-                            T.psums.at(sc))) != RM_OK)
-        return rc;
-    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, T.psums.at(sc), G.n_pblocks, T.ptot.at(sc));
-    if ((rc = sparse_launch(c, topo_occupancy_kernel(loop), G.g.nb, shmem, s, Q, G.g, level, static_cast<const uint8_t*>(T.cls.at(sc)),
-                            T.occ.at(sc), evals)) != RM_OK)
-        return rc;
+    if ((rc = solid_occupancy_fill(c, s, O, G, level, T.cls.at(sc), T.psums.at(sc), T.ptot.at(sc), T.occ.at(sc), evals)) != RM_OK) return rc;
     uint64_t counts[RM_TOPO_COUNTS], passes = 0;
     if ((rc = label_lattice(c, "rm_label_solid", s, G, T, counts, &passes)) != RM_OK) return rc;
     unsigned long long tot[2] = {0ull, 0ull}, ev = 0ull;
@@ -2170,6 +2192,215 @@ RM_EXPORT int rm_read_topology(rm_ctx* c, uint64_t* out_body_moments, uint64_t* 
     if (out_body_moments && R.bodies.bytes) HIP_TRY(c, hipMemcpyAsync(out_body_moments, R.bodies.at(rows), R.bodies.bytes, kind, s));
     if (out_cavity_moments && R.cavities.bytes) HIP_TRY(c, hipMemcpyAsync(out_cavity_moments, R.cavities.at(rows), R.cavities.bytes, kind, s));
     if (out_labels) HIP_TRY(c, hipMemcpyAsync(out_labels, c->d_tlabels.p, (size_t)c->topo_n * 4u, kind, s));
+    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+// ---- distance transform (rm_distance.h) ----
+namespace {
+
+struct DistBlocks {
+    uint32_t n_rblocks, n_fblocks;  // rows of 2048 points, folded rows of 256 rows
+    explicit DistBlocks(uint32_t n) : n_rblocks((n + rmk::kDistBlock - 1u) / rmk::kDistBlock), n_fblocks((n_rblocks + rmk::kTopoFold - 1u) / rmk::kTopoFold) {}
+};
+
+// The y and the z pass over `vol` (rm_dist_column_kernel): a launch each.
+template <bool SINGLE>
+int dist_columns(rm_ctx* c, hipStream_t s, const rmk::SparseGrid& g, uint32_t none, uint32_t* vol) {
+    const auto kernel = rmk::rm_dist_column_kernel<SINGLE>;
+    const uint32_t axes[2][3] = {{g.ny, g.nx, g.nx * g.ny}, {g.nz, g.nx * g.ny, g.nx}};  // points, stride, outer stride
+    const uint32_t slabs[2] = {g.nz, g.ny};
+    for (int a = 0; a < 2; a++) {
+        const uint32_t n = axes[a][0], xl = rml::dist_columns_log2(n), xt = 1u << xl;
+        const uint32_t shmem = rml::DistColumnLds(xt, n).bytes;
+        if (shmem + 1024u > rml::kLdsLaunchLimit)
+            HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+        hipLaunchKernelGGL(kernel, dim3((g.nx + xt - 1u) / xt, slabs[a]), dim3(256), shmem, s, g.nx, n, axes[a][1], axes[a][2], xl, none, vol);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return RM_OK;
+}
+
+// rows -> the reduced row of 16 words, on the host.
+int dist_reduce(rm_ctx* c, hipStream_t s, const DistBlocks& D, const unsigned long long* rows, unsigned long long* folded,
+                unsigned long long* result, unsigned long long* row) {
+    hipLaunchKernelGGL(rmk::rm_topo_fold_kernel, dim3(D.n_fblocks), dim3(256), 0, s, rows, D.n_rblocks, folded);
+    hipLaunchKernelGGL(rmk::rm_mass_reduce_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned long long*>(folded), D.n_fblocks,
+                       static_cast<const unsigned long long*>(nullptr), 0u, result);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(row, result, RM_MOMENTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+// From the occupancy in S.occ on: rows, columns, maxima.  counts: RM_DIST_COUNTS words.
+int distance_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rml::DistScratch& S, uint64_t* counts) {
+    const rmk::SparseGrid& g = G.g;
+    char* sc = c->d_mscratch.p;
+    uint32_t* vol = c->d_dvol.as<uint32_t>();
+    const DistBlocks D(G.n);
+    const uint32_t n_rows = g.ny * g.nz;
+    hipLaunchKernelGGL(rmk::rm_dist_row_kernel<rmk::DIST_FROM_OCCUPANCY>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, g.nx, n_rows,
+                       static_cast<const uint8_t*>(S.occ.at(sc)), static_cast<const uint32_t*>(nullptr), 0u, vol);
+    if (int rc = dist_columns<false>(c, s, g, rmk::kDistNone, vol)) return rc;
+    hipLaunchKernelGGL(rmk::rm_dist_max_kernel, dim3(D.n_rblocks), dim3(256), 0, s, G.n, static_cast<const uint32_t*>(vol), S.rows.at(sc));
+    unsigned long long row[RM_MOMENTS];
+    if (int rc = dist_reduce(c, s, D, S.rows.at(sc), S.folded.at(sc), S.result.at(sc), row)) return rc;
+    counts[RM_DIST_POINTS] = row[0];
+    counts[RM_DIST_MAX_INSIDE] = row[13] >> 32;
+    counts[RM_DIST_ARGMAX_INSIDE] = ~row[13] & 0xFFFFFFFFull;
+    counts[RM_DIST_MAX_OUTSIDE] = row[14] >> 32;
+    counts[RM_DIST_ARGMAX_OUTSIDE] = ~row[14] & 0xFFFFFFFFull;
+    c->dist_valid = true;
+    c->dist_nx = g.nx;
+    c->dist_ny = g.ny;
+    c->dist_nz = g.nz;
+    return RM_OK;
+}
+
+}  // namespace
+
+RM_EXPORT int rm_distance_solid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                                uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_counts || !out_stats) return fail(c, RM_ERR_NULL, "rm_distance_solid: out_counts or out_stats is NULL");
+    if (n_counts < (uint32_t)RM_DIST_COUNTS) return fail(c, RM_ERR_ARG, "rm_distance_solid: n_counts %u < RM_DIST_COUNTS", n_counts);
+    if (n_stats < (uint32_t)RM_DIST_STATS) return fail(c, RM_ERR_ARG, "rm_distance_solid: n_stats %u < RM_DIST_STATS", n_stats);
+    if (int rc = check_lattice(c, "rm_distance_solid", origin, step)) return rc;
+    if (int rc = check_iso(c, "rm_distance_solid", level, 0u)) return rc;
+    if (!topo_lattice_ok(nx, ny, nz))
+        return fail(c, RM_ERR_RANGE, "rm_distance_solid: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", nx, ny, nz);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    SolidOccupancy O;
+    int rc = solid_occupancy_begin(c, "rm_distance_solid", s, origin, step, nx, ny, nz, &O);  // after a device read of the last volume, too
+    if (rc != RM_OK) return rc;
+    const TopoGrid G = topo_grid(origin, step, nx, ny, nz);
+    const DistBlocks D(G.n);
+    const rml::DistScratch S(G.n, G.g.nb, G.n_pblocks, D.n_rblocks, D.n_fblocks);
+    if ((rc = c->d_mscratch.reserve(c, S.bytes)) != RM_OK) return rc;
+    c->dist_valid = c->dist_mask_valid = false;  // its buffers change from here on
+    if ((rc = c->d_dvol.reserve(c, (size_t)G.n * 4u, "distance volume")) != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    unsigned long long* evals = S.evals.at(sc);
+    if ((rc = solid_occupancy_fill(c, s, O, G, level, S.cls.at(sc), S.psums.at(sc), S.ptot.at(sc), S.occ.at(sc), evals)) != RM_OK) return rc;
+    uint64_t counts[RM_DIST_COUNTS];
+    if ((rc = distance_lattice(c, s, G, S, counts)) != RM_OK) return rc;
+    unsigned long long tot[2] = {0ull, 0ull}, ev = 0ull;
+    HIP_TRY(c, hipMemcpyAsync(tot, S.ptot.at(sc), sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (int k = 0; k < RM_DIST_COUNTS; k++) out_counts[k] = counts[k];
+    out_stats[RM_DIST_STAT_BRICKS] = G.g.nb;
+    out_stats[RM_DIST_STAT_BRICKS_KEPT] = tot[0];
+    out_stats[RM_DIST_STAT_BRICKS_INSIDE] = tot[1];
+    out_stats[RM_DIST_STAT_EVALUATIONS] = G.g.nb + ev;
+    out_stats[RM_DIST_STAT_SCRATCH_BYTES] = S.bytes;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_distance_occupancy(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz, const void* occupancy, int is_device, void* stream,
+                                    uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
+    if (!c) return RM_ERR_NULL;
+    if (!occupancy || !out_counts || !out_stats)
+        return fail(c, RM_ERR_NULL, "rm_distance_occupancy: occupancy, out_counts or out_stats is NULL");
+    if (n_counts < (uint32_t)RM_DIST_COUNTS) return fail(c, RM_ERR_ARG, "rm_distance_occupancy: n_counts %u < RM_DIST_COUNTS", n_counts);
+    if (n_stats < (uint32_t)RM_DIST_STATS) return fail(c, RM_ERR_ARG, "rm_distance_occupancy: n_stats %u < RM_DIST_STATS", n_stats);
+    if (!topo_lattice_ok(nx, ny, nz))
+        return fail(c, RM_ERR_RANGE, "rm_distance_occupancy: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", nx, ny, nz);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    order_with_previous(c, s);  // after a device read of the last volume, too
+    const float zero[3] = {0.0f, 0.0f, 0.0f}, one[3] = {1.0f, 1.0f, 1.0f};
+    const TopoGrid G = topo_grid(zero, one, nx, ny, nz);
+    const DistBlocks D(G.n);
+    const rml::DistScratch S(G.n, G.g.nb, G.n_pblocks, D.n_rblocks, D.n_fblocks);
+    int rc = c->d_mscratch.reserve(c, S.bytes);
+    if (rc != RM_OK) return rc;
+    c->dist_valid = c->dist_mask_valid = false;  // its buffers change from here on
+    if ((rc = c->d_dvol.reserve(c, (size_t)G.n * 4u, "distance volume")) != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    if (is_device) {
+        // the caller's array is ready when the work queued on its stream is done; the call is synchronous anyway
+        const hipStream_t su = user_stream(c, stream);
+        if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
+    }
+    HIP_TRY(c, hipMemcpyAsync(S.occ.at(sc), occupancy, G.n, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    uint64_t counts[RM_DIST_COUNTS];
+    if ((rc = distance_lattice(c, s, G, S, counts)) != RM_OK) return rc;
+    for (int k = 0; k < RM_DIST_COUNTS; k++) out_counts[k] = counts[k];
+    for (int k = 0; k < RM_DIST_STATS; k++) out_stats[k] = 0u;
+    out_stats[RM_DIST_STAT_SCRATCH_BYTES] = S.bytes;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_distance_features(rm_ctx* c, uint32_t r2_wall, uint32_t r2_gap, uint64_t* out_counts, uint32_t n_counts) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_counts) return fail(c, RM_ERR_NULL, "rm_distance_features: out_counts is NULL");
+    if (n_counts < (uint32_t)RM_DIST_FEATURE_COUNTS)
+        return fail(c, RM_ERR_ARG, "rm_distance_features: n_counts %u < RM_DIST_FEATURE_COUNTS", n_counts);
+    if (!c->dist_valid) return fail(c, RM_ERR_ARG, "rm_distance_features: no distance volume has been computed");
+    if ((r2_wall != RM_DIST_SKIP && r2_wall >= kMaxDistR2) || (r2_gap != RM_DIST_SKIP && r2_gap >= kMaxDistR2))
+        return fail(c, RM_ERR_RANGE, "rm_distance_features: r2_wall %u, r2_gap %u: below 2^22, or RM_DIST_SKIP", r2_wall, r2_gap);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    order_with_previous(c, s);  // after a device read of the last mask, too
+    const float zero[3] = {0.0f, 0.0f, 0.0f}, one[3] = {1.0f, 1.0f, 1.0f};
+    const TopoGrid G = topo_grid(zero, one, c->dist_nx, c->dist_ny, c->dist_nz);
+    const rmk::SparseGrid& g = G.g;
+    const DistBlocks D(G.n);
+    const rml::DistFeatureScratch S(G.n, D.n_rblocks, D.n_fblocks);
+    int rc = c->d_mscratch.reserve(c, S.bytes);
+    if (rc != RM_OK) return rc;
+    c->dist_mask_valid = false;  // the mask changes from here on
+    if ((rc = c->d_dmask.reserve(c, G.n, "feature mask")) != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    const uint32_t* vol = c->d_dvol.as<uint32_t>();
+    uint8_t* mask = reinterpret_cast<uint8_t*>(c->d_dmask.p);
+    uint32_t* feat = S.feat.at(sc);
+    const uint32_t n_rows = g.ny * g.nz;
+    hipLaunchKernelGGL(rmk::rm_dist_mask_init_kernel, dim3((G.n + 255u) / 256u), dim3(256), 0, s, G.n, vol, mask);
+    uint64_t counts[RM_DIST_FEATURE_COUNTS] = {0u, 0u, 0u, 0u};
+    unsigned long long row[RM_MOMENTS];
+    if (r2_wall != RM_DIST_SKIP) {
+        hipLaunchKernelGGL(rmk::rm_dist_row_kernel<rmk::DIST_FROM_WALL_CORE>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, g.nx, n_rows,
+                           static_cast<const uint8_t*>(nullptr), vol, r2_wall, feat);
+        if ((rc = dist_columns<true>(c, s, g, r2_wall + 1u, feat)) != RM_OK) return rc;
+        hipLaunchKernelGGL((rmk::rm_dist_compose_kernel<1u, 2u>), dim3(D.n_rblocks), dim3(256), 0, s, G.n, vol, static_cast<const uint32_t*>(feat),
+                           r2_wall, mask, S.rows.at(sc));
+        if ((rc = dist_reduce(c, s, D, S.rows.at(sc), S.folded.at(sc), S.result.at(sc), row)) != RM_OK) return rc;
+        counts[RM_DIST_CORE] = row[0];
+        counts[RM_DIST_THIN] = row[1];
+    }
+    if (r2_gap != RM_DIST_SKIP) {
+        hipLaunchKernelGGL(rmk::rm_dist_row_kernel<rmk::DIST_FROM_GAP_CORE>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, g.nx, n_rows,
+                           static_cast<const uint8_t*>(nullptr), vol, r2_gap, feat);
+        if ((rc = dist_columns<true>(c, s, g, r2_gap + 1u, feat)) != RM_OK) return rc;
+        hipLaunchKernelGGL((rmk::rm_dist_compose_kernel<0u, 3u>), dim3(D.n_rblocks), dim3(256), 0, s, G.n, vol, static_cast<const uint32_t*>(feat),
+                           r2_gap, mask, S.rows.at(sc));
+        if ((rc = dist_reduce(c, s, D, S.rows.at(sc), S.folded.at(sc), S.result.at(sc), row)) != RM_OK) return rc;
+        counts[RM_DIST_GAP_CORE] = row[0];
+        counts[RM_DIST_NARROW] = row[1];
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (int k = 0; k < RM_DIST_FEATURE_COUNTS; k++) out_counts[k] = counts[k];
+    c->dist_mask_valid = true;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_read_distance(rm_ctx* c, uint32_t* out_d2, void* out_mask, int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!c->dist_valid) return fail(c, RM_ERR_ARG, "rm_read_distance: no distance volume has been computed");
+    if (out_mask && !c->dist_mask_valid) return fail(c, RM_ERR_ARG, "rm_read_distance: rm_distance_features has made no mask of this volume");
+    if (is_device && misaligned(out_d2, 4)) return fail(c, RM_ERR_ARG, "rm_read_distance: a device out_d2 needs 4-byte alignment");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = dest_stream(c, is_device, stream);
+    order_with_previous(c, s);  // (the next distance call waits for this stream in turn)
+    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const size_t n = (size_t)c->dist_nx * c->dist_ny * c->dist_nz;
+    if (out_d2) HIP_TRY(c, hipMemcpyAsync(out_d2, c->d_dvol.p, n * 4u, kind, s));
+    if (out_mask) HIP_TRY(c, hipMemcpyAsync(out_mask, c->d_dmask.p, n, kind, s));
     if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
     return RM_OK;
 }

@@ -128,6 +128,33 @@ struct TopoRows {
     TopoRows(uint64_t B, uint64_t C) : bodies(a.take<unsigned long long>(B * 16u)), cavities(a.take<unsigned long long>(C * 16u)), bytes(a.total) {}
 };
 
+// rm_distance_solid / rm_distance_occupancy, for a lattice of n points in nb bricks: per point its occupancy (1 B); per brick its
+// class (1 B); per 256 bricks the probe's block sum; per 2048 points one row of 16 words (the maxima and the count), per 256 of
+// those rows one folded row; totals, the evaluation count and the reduced row.  The distance volume itself (4 B per point) and
+// the feature mask (1 B per point) are the result and lie in buffers of their own.
+struct DistScratch {
+    Carver a;
+    Region<uint8_t> occ, cls;
+    Region<unsigned long long> psums, rows, folded, ptot, evals, result;
+    size_t bytes;
+    DistScratch(uint32_t n, uint32_t nb, uint32_t n_pblocks, uint32_t n_rblocks, uint32_t n_fblocks)
+        : occ(a.take<uint8_t>(n)), cls(a.take<uint8_t>(nb)), psums(a.take<unsigned long long>(n_pblocks)),
+          rows(a.take<unsigned long long>((size_t)n_rblocks * 16u)), folded(a.take<unsigned long long>((size_t)n_fblocks * 16u)),
+          ptot(a.take<unsigned long long>(2)), evals(a.take<unsigned long long>(2)), result(a.take<unsigned long long>(16)), bytes(a.total) {}
+};
+
+// rm_distance_features: per point the transform towards the core (4 B: one half after the other); the rows, the folded rows and
+// the reduced row as above.
+struct DistFeatureScratch {
+    Carver a;
+    Region<uint32_t> feat;
+    Region<unsigned long long> rows, folded, result;
+    size_t bytes;
+    DistFeatureScratch(uint32_t n, uint32_t n_rblocks, uint32_t n_fblocks)
+        : feat(a.take<uint32_t>(n)), rows(a.take<unsigned long long>((size_t)n_rblocks * 16u)),
+          folded(a.take<unsigned long long>((size_t)n_fblocks * 16u)), result(a.take<unsigned long long>(16)), bytes(a.total) {}
+};
+
 // rm_slice_contours' per-layer tables: heights, layer_first, the first vertex of each layer of a batch of `per`, totals.
 // (heights and layer_first lie before anything `per` sizes: rm_read_slices finds layer_first without it.)
 struct SliceLayerTables {

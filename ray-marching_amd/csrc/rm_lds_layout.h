@@ -110,4 +110,20 @@ struct PixelLds {
     RM_LDS_FN PixelLds(uint32_t n_rec, uint32_t spill_depth) : prog(0u), spill(prog + n_rec * 32u), bytes(spill + spill_depth * 256u * 4u) {}
 };
 
+// ---- Distance transform, column passes (rm_distance.h rm_dist_column_kernel) ------------------------------------------------
+// A tile of `xt` adjacent columns of n points each, one word per point, point q of column lx at word q * xt + lx (the lanes of
+// a wave read and write consecutive words).  xt: the power of two that keeps the tile within 32 KB, but at least 16 columns
+// (64 contiguous bytes per row of the tile) and at most 64 (one row per wave): 64 KB, the launch limit, at the longest axis
+// of 1024 points.
+constexpr uint32_t kDistTileWords = 8192u, kDistMinColumns = 16u, kDistMaxColumns = 64u, kDistMaxAxis = 1024u;
+RM_LDS_FN uint32_t dist_columns_log2(uint32_t n) {
+    uint32_t l = 6u;  // kDistMaxColumns
+    while (l > 4u && (n << l) > kDistTileWords) l--;
+    return l;
+}
+struct DistColumnLds {
+    uint32_t col, bytes;
+    RM_LDS_FN DistColumnLds(uint32_t xt, uint32_t n) : col(0u), bytes(col + xt * n * 4u) {}
+};
+
 }  // namespace rml

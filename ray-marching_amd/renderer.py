@@ -560,6 +560,17 @@ class RayMarchingResources:
         """rm_label_occupancy: the topology of a caller's occupancy, indexed [k, j, i] (shape (nz, ny, nx); nonzero = inside): a
         numpy array of a one-byte type (bool, uint8, int8), or such a contiguous torch tensor on this context's GPU, read after
         the work queued on torch.cuda.current_stream().  The Topology's lattice is the unit lattice at the origin."""
+        nx, ny, nz, ptr, is_device, stream, keep = self._occupancy_arg(occupancy)
+        counts = (C.c_uint64 * _ffi.RM_TOPO_COUNTS)()
+        stats = (C.c_uint64 * _ffi.RM_TOPO_STATS)()
+        self._check(self._L.rm_label_occupancy(self._h, nx, ny, nz, ptr, is_device, stream, counts, _ffi.RM_TOPO_COUNTS, stats,
+                                               _ffi.RM_TOPO_STATS))
+        del keep
+        return self._read_topology(counts, stats, np.zeros(3, dtype=np.float32), np.ones(3, dtype=np.float32), (nx, ny, nz))
+
+    def _occupancy_arg(self, occupancy):
+        """A caller's occupancy as the library takes it: nx, ny, nz, its address, is_device, the stream, and the object to keep
+        alive during the call."""
         if type(occupancy).__module__.split(".")[0] == "torch":
             t = occupancy
             if t.device.type != "cuda" or t.device.index != self.device:
@@ -577,12 +588,7 @@ class RayMarchingResources:
             ptr, is_device, stream = C.c_void_p(keep.ctypes.data), 0, None
         if min(nx, ny, nz) < 2:
             raise ValueError("a lattice needs at least 2 points per axis, not %s" % ((nx, ny, nz),))
-        counts = (C.c_uint64 * _ffi.RM_TOPO_COUNTS)()
-        stats = (C.c_uint64 * _ffi.RM_TOPO_STATS)()
-        self._check(self._L.rm_label_occupancy(self._h, nx, ny, nz, ptr, is_device, stream, counts, _ffi.RM_TOPO_COUNTS, stats,
-                                               _ffi.RM_TOPO_STATS))
-        del keep
-        return self._read_topology(counts, stats, np.zeros(3, dtype=np.float32), np.ones(3, dtype=np.float32), (nx, ny, nz))
+        return nx, ny, nz, ptr, is_device, stream, keep
 
     def _read_topology(self, counts, stats, origin, step, shape):
         """The Topology of the labelling call that just returned: its counts and statistics, and both row tables read back."""
@@ -601,6 +607,44 @@ class RayMarchingResources:
         """rm_read_topology of the last labelling call into device memory (integer addresses; 0 = not wanted), asynchronous."""
         self._check(self._L.rm_read_topology(self._h, C.c_void_p(body_moments_ptr or None), C.c_void_p(cavity_moments_ptr or None),
                                              C.c_void_p(labels_ptr or None), 1, C.c_void_p(stream) if stream else None))
+
+    # -- distance transform (rm_distance_solid / rm_distance_occupancy / rm_distance_features / rm_read_distance) ----------------
+    def distance_solid(self, lo, hi, resolution, level=0.0):
+        """The exact squared distance transform of the solid map_scene < level inside the box [lo, hi], on the lattice
+        extract_mesh builds from (lo, hi, resolution) (2..1024 points per axis, at most 2^28 in all): a Distance."""
+        lo, step, n = self._box_lattice(lo, hi, resolution)
+        return self.distance_solid_grid(lo, step, n, level)
+
+    def distance_solid_grid(self, origin, step, shape, level=0.0):
+        """distance_solid on an exact lattice (origin, step, shape as sample_grid takes them)."""
+        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
+        counts = (C.c_uint64 * _ffi.RM_DIST_COUNTS)()
+        stats = (C.c_uint64 * _ffi.RM_DIST_STATS)()
+        self._check(self._L.rm_distance_solid(self._h, fp(o), fp(s), nx, ny, nz, float(level), counts, _ffi.RM_DIST_COUNTS, stats,
+                                              _ffi.RM_DIST_STATS))
+        return self._distance(counts, stats, o, s, (nx, ny, nz))
+
+    def distance_occupancy(self, occupancy):
+        """rm_distance_occupancy: the distance transform of a caller's occupancy, as label_occupancy takes it (indexed [k, j, i],
+        nonzero = inside; numpy, or a torch tensor on this context's GPU).  The Distance's lattice is the unit lattice at the
+        origin."""
+        nx, ny, nz, ptr, is_device, stream, keep = self._occupancy_arg(occupancy)
+        counts = (C.c_uint64 * _ffi.RM_DIST_COUNTS)()
+        stats = (C.c_uint64 * _ffi.RM_DIST_STATS)()
+        self._check(self._L.rm_distance_occupancy(self._h, nx, ny, nz, ptr, is_device, stream, counts, _ffi.RM_DIST_COUNTS, stats,
+                                                  _ffi.RM_DIST_STATS))
+        del keep
+        return self._distance(counts, stats, np.zeros(3, dtype=np.float32), np.ones(3, dtype=np.float32), (nx, ny, nz))
+
+    def _distance(self, counts, stats, origin, step, shape):
+        return Distance(self, {name: int(counts[k]) for k, name in enumerate(_ffi.DIST_COUNT_NAMES)},
+                        {name: int(stats[k]) for k, name in enumerate(_ffi.DIST_STAT_NAMES)}, origin, step, shape)
+
+    def read_distance_device(self, d2_ptr=0, mask_ptr=0, stream=None):
+        """rm_read_distance of the last distance volume and feature mask into device memory (integer addresses; 0 = not wanted),
+        asynchronous."""
+        self._check(self._L.rm_read_distance(self._h, C.c_void_p(d2_ptr or None), C.c_void_p(mask_ptr or None), 1,
+                                             C.c_void_p(stream) if stream else None))
 
     def _read_mesh(self, V, T, normals, ids, device):
         """rm_read_mesh of the extraction that just returned V vertices and T triangles, as a mesh.Mesh."""
@@ -816,6 +860,88 @@ class Topology:
         nx, ny, nz = self.shape
         out = np.empty((nz, ny, nx), dtype=np.uint32)
         self._res._check(self._res._L.rm_read_topology(self._res._h, None, None, out.ctypes.data, 0, None))
+        return out
+
+
+def squared_radius(width, step):
+    """The squared radius, in index units, of the ball that a wall (or gap) of `width` world units must hold: floor((width / 2 /
+    step)^2).  step: one number, or three equal ones; ValueError otherwise (index distance is world distance / step only then)."""
+    st = np.asarray(step, dtype=np.float64).reshape(-1)
+    if st.size not in (1, 3) or not np.all(st == st[0]) or not st[0] > 0:
+        raise ValueError("thickness in world units needs one step for all three axes, not %s" % (step,))
+    w = float(width)
+    if not w >= 0.0 or not np.isfinite(w):
+        raise ValueError("a width must be finite and >= 0, not %r" % (width,))
+    return int(np.floor((w / 2.0 / float(st[0])) ** 2))
+
+
+class Distance:
+    """The result of distance_solid / distance_occupancy.  counts and stats: dicts (_ffi.DIST_COUNT_NAMES, _ffi.DIST_STAT_NAMES);
+    origin, step (float32[3]) and shape of the lattice.  d2(), features() and mask() read the context's buffers: they hold while
+    this is the context's last distance call."""
+
+    def __init__(self, resources, counts, stats, origin, step, shape):
+        self._res = resources
+        self.counts, self.stats = counts, stats
+        self.origin, self.step, self.shape = origin, step, shape
+
+    def __repr__(self):
+        return "Distance(%d inside points, largest inside D2 %d, on %s)" % (self.counts["points"], self.counts["max_inside"],
+                                                                           "x".join(map(str, self.shape)))
+
+    def d2(self):
+        """The distance volume, uint32 (nz, ny, nx): D2 in index units, | _ffi.RM_DIST_INSIDE_BIT for an inside point."""
+        nx, ny, nz = self.shape
+        out = np.empty((nz, ny, nx), dtype=np.uint32)
+        self._res._check(self._res._L.rm_read_distance(self._res._h, out.ctypes.data, None, 0, None))
+        return out
+
+    def inscribed_radius(self, step=None):
+        """Radius (world units) and centre (i, j, k) of the largest inscribed ball: step * sqrt(max_inside) and the point of
+        argmax_inside; (0.0, None) for an empty solid.  step defaults to the lattice's; ValueError when its three differ."""
+        st = np.asarray(self.step if step is None else step, dtype=np.float64).reshape(-1)
+        if not np.all(st == st[0]):
+            raise ValueError("a radius in world units needs one step for all three axes, not %s" % (st,))
+        if self.counts["points"] == 0:
+            return 0.0, None
+        nx, ny, _ = self.shape
+        p = self.counts["argmax_inside"]
+        return float(st[0]) * float(np.sqrt(self.counts["max_inside"])), (p % nx, (p // nx) % ny, p // (nx * ny))
+
+    def features(self, r2_wall=None, r2_gap=None, wall=None, gap=None):
+        """rm_distance_features: thin walls and narrow gaps.  r2_wall, r2_gap: squared radii in index units; or wall, gap: widths in
+        world units (squared_radius with this lattice's step); None skips that half.  A DistanceFeatures."""
+        if wall is not None:
+            if r2_wall is not None:
+                raise ValueError("give r2_wall or wall, not both")
+            r2_wall = squared_radius(wall, self.step)
+        if gap is not None:
+            if r2_gap is not None:
+                raise ValueError("give r2_gap or gap, not both")
+            r2_gap = squared_radius(gap, self.step)
+        skip = _ffi.RM_DIST_SKIP
+        for r2 in (r2_wall, r2_gap):
+            if r2 is not None and not 0 <= int(r2) < skip:
+                raise ValueError("a squared radius must be >= 0, not %r" % (r2,))
+        counts = (C.c_uint64 * _ffi.RM_DIST_FEATURE_COUNTS)()
+        self._res._check(self._res._L.rm_distance_features(self._res._h, skip if r2_wall is None else int(r2_wall),
+                                                           skip if r2_gap is None else int(r2_gap), counts, _ffi.RM_DIST_FEATURE_COUNTS))
+        return DistanceFeatures(self._res, {name: int(counts[k]) for k, name in enumerate(_ffi.DIST_FEATURE_NAMES)}, r2_wall, r2_gap,
+                                self.shape)
+
+
+class DistanceFeatures:
+    """The result of Distance.features: counts (a dict: _ffi.DIST_FEATURE_NAMES), r2_wall and r2_gap as used (None: skipped)."""
+
+    def __init__(self, resources, counts, r2_wall, r2_gap, shape):
+        self._res = resources
+        self.counts, self.r2_wall, self.r2_gap, self.shape = counts, r2_wall, r2_gap, shape
+
+    def mask(self):
+        """The feature mask, uint8 (nz, ny, nx): 0 outside, 1 inside, 2 thin, 3 narrow (_ffi.DIST_MASK_*)."""
+        nx, ny, nz = self.shape
+        out = np.empty((nz, ny, nx), dtype=np.uint8)
+        self._res._check(self._res._L.rm_read_distance(self._res._h, None, out.ctypes.data, 0, None))
         return out
 
 

@@ -1,0 +1,121 @@
+"""Wall thickness and clearance from RayMarchingResources.distance_solid: the largest ball that fits into the part, the material
+that no ball of a given diameter fits into (thin walls), and the clearance that none fits into (narrow gaps) -- from the exact
+squared distance transform of the solid map_scene < level on a lattice.
+
+  python -m ray_marching_amd.thickness --scene g32 --lo -2.5 --hi 2.5 --res 256 --min-wall 0.1
+  python -m ray_marching_amd.thickness --program part.json --res 512 --min-wall 0.8 --min-gap 0.5 --regions --fail-on "thin>0,narrow>0"
+
+evaluates a named scene (csg.scene) or a program file (massprops.load_program) on the GPU and prints one JSON line: the inside
+points, the inscribed radius and its centre, and with --min-wall W / --min-gap G (world units; the box must give one step for all
+three axes) the points of walls thinner than W and of gaps narrower than G.  --d2 and --mask write the distance volume (uint32
+[k, j, i]: squared distance in lattice steps, | 0x80000000 inside) and the feature mask (uint8: 0 outside, 1 inside, 2 thin,
+3 narrow) as .npy files.  --regions labels the thin points (label_occupancy) and reports each region's volume and centre.
+--fail-on is a printability gate: a comma-separated list of `thin>N`, `narrow>N` (points) and `inscribed<R` (world units); the
+exit status is 2 when one holds.  Ball centres lie on the lattice only: a solid nearer than the gap width to the box's border can
+report narrow points against the border, and the report then carries a warning."""
+import argparse
+import json
+import re
+import sys
+
+from .massprops import load_program
+from .mesh import _three
+
+GATES = {"thin": ">", "narrow": ">", "inscribed": "<"}
+
+
+def parse_gates(text):
+    """"thin>0,inscribed<1.5" -> [("thin", ">", 0.0), ("inscribed", "<", 1.5)]."""
+    gates = []
+    for part in filter(None, (p.strip() for p in (text or "").split(","))):
+        m = re.fullmatch(r"(\w+)\s*([<>])\s*(-?\d+(?:\.\d*)?(?:[eE][-+]?\d+)?)", part)
+        if not m or GATES.get(m.group(1)) != m.group(2):
+            raise ValueError("--fail-on: %r is not one of thin>N, narrow>N, inscribed<R" % part)
+        gates.append((m.group(1), m.group(2), float(m.group(3))))
+    return gates
+
+
+def failed_gates(gates, values):
+    return ["%s = %g %s %g" % (name, values[name], op, limit) for name, op, limit in gates
+            if (values[name] > limit if op == ">" else values[name] < limit)]
+
+
+def border_warning(mask_inside_box, shape, r2_gap):
+    """A warning when the solid's index box (lo, hi per axis, or None for an empty solid) is nearer than 2 sqrt(r2_gap) to the
+    lattice's border: no ball centred on the lattice fits between the two, whatever lies beyond the box."""
+    if mask_inside_box is None or not r2_gap:
+        return None
+    reach = 2.0 * r2_gap ** 0.5
+    lo, hi = mask_inside_box
+    near = [ax for ax, (a, b, n) in zip("xyz", zip(lo, hi, shape)) if a < reach or (n - 1 - b) < reach]
+    if not near:
+        return None
+    return "the solid is nearer than the gap width to the box's border along %s: narrow points there are against the border" % ", ".join(near)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m ray_marching_amd.thickness", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--scene", default="g32", help="a csg.scene name (g1, g8, g32, g32_balanced, mat_mix, ...)")
+    ap.add_argument("--program", default=None, help='a program file instead of --scene: JSON {"cmd_count": n, "words": [...]}')
+    ap.add_argument("--lo", default="-2.5", help="lower box corner: one value for all axes, or x,y,z")
+    ap.add_argument("--hi", default="2.5", help="upper box corner: one value, or x,y,z")
+    ap.add_argument("--res", default="256", help="lattice points per axis (2..1024, at most 2^28 in all): n, or nx,ny,nz")
+    ap.add_argument("--level", type=float, default=0.0)
+    ap.add_argument("--min-wall", type=float, default=None, help="report the material that no ball of this diameter fits into")
+    ap.add_argument("--min-gap", type=float, default=None, help="report the clearance that no ball of this diameter fits into")
+    ap.add_argument("--d2", default=None, help="write the distance volume to this .npy file")
+    ap.add_argument("--mask", default=None, help="write the feature mask to this .npy file")
+    ap.add_argument("--regions", action="store_true", help="label the thin points and report every region")
+    ap.add_argument("--fail-on", default="", help='e.g. "thin>0,narrow>0,inscribed<0.4": exit status 2 when one of them holds')
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    gates = parse_gates(a.fail_on)
+    import numpy as np
+    from . import _ffi, csg, renderer
+    res = renderer.RayMarchingResources(a.device)
+    try:
+        if a.program is not None:
+            cc, words = load_program(a.program)
+            res.resize_command_buffer(max(1024, 4 * (len(words) + 1)))
+            res.set_program(cc, words)
+        else:
+            res.set_scene(csg.scene(a.scene))
+        dist = res.distance_solid(_three(a.lo, float, "--lo"), _three(a.hi, float, "--hi"), _three(a.res, int, "--res"), level=a.level)
+        radius, centre = dist.inscribed_radius()          # ValueError for unequal steps: thickness needs one step
+        report = {"shape": list(dist.shape), "step": float(dist.step[0]), "points": dist.counts["points"], "inscribed": radius,
+                  "inscribed_at": None if centre is None else [float(dist.origin[ax] + np.float32(centre[ax]) * dist.step[ax]) for ax in range(3)],
+                  "stats": dist.stats}
+        if a.d2:
+            np.save(a.d2, dist.d2())
+        values = {"inscribed": radius, "thin": 0, "narrow": 0}
+        if a.min_wall is not None or a.min_gap is not None or a.mask or a.regions:
+            feats = dist.features(wall=a.min_wall, gap=a.min_gap)
+            report.update(r2_wall=feats.r2_wall, r2_gap=feats.r2_gap, **feats.counts)
+            values.update(thin=feats.counts["thin"], narrow=feats.counts["narrow"])
+            mask = feats.mask() if (a.mask or a.regions or feats.r2_gap) else None
+            if a.mask:
+                np.save(a.mask, mask)
+            if feats.r2_gap and dist.counts["points"]:
+                k, j, i = np.nonzero((mask == _ffi.DIST_MASK_INSIDE) | (mask == _ffi.DIST_MASK_THIN))
+                warn = border_warning(((i.min(), j.min(), k.min()), (i.max(), j.max(), k.max())), dist.shape, feats.r2_gap)
+                if warn:
+                    report["warning"] = warn
+                    print("warning: " + warn, file=sys.stderr)
+            if a.regions:
+                regions = []
+                if feats.counts["thin"]:
+                    topo = res.label_occupancy((mask == _ffi.DIST_MASK_THIN).astype(np.uint8))
+                    for row in topo.body_moments:
+                        p = renderer.mass_from_moments(row, dist.origin, dist.step, 1.0)
+                        regions.append({"points": int(row[0]), "volume": p["volume"], "centre": [float(x) for x in p["centroid"]]})
+                report["regions"] = regions
+    finally:
+        res.close()
+    failed = failed_gates(gates, values)
+    report["failed"] = failed
+    print(json.dumps(report))
+    return 2 if failed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
