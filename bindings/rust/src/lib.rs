@@ -247,6 +247,34 @@ pub const RM_DIST_STAT_EVALUATIONS: c_int = 3;
 pub const RM_DIST_STAT_SCRATCH_BYTES: c_int = 4;
 pub const RM_DIST_STATS: c_int = 5;
 
+// Overhangs and supports (rm_support_solid / rm_support_occupancy / rm_read_support).
+/// `RM_SUPPORT_PLATE_AUTO`: as a plate, the lowest height that holds an inside point.
+pub const RM_SUPPORT_PLATE_AUTO: u32 = 0xFFFF_FFFF;
+// enum rm_up: the build directions
+pub const RM_UP_POS_X: c_int = 0;
+pub const RM_UP_NEG_X: c_int = 1;
+pub const RM_UP_POS_Y: c_int = 2;
+pub const RM_UP_NEG_Y: c_int = 3;
+pub const RM_UP_POS_Z: c_int = 4;
+pub const RM_UP_NEG_Z: c_int = 5;
+// enum rm_supcount: indices into the counts of a support call; RM_SUP_COUNTS is their number
+pub const RM_SUP_POINTS: c_int = 0;
+pub const RM_SUP_PLATE: c_int = 1;
+pub const RM_SUP_BASE: c_int = 2;
+pub const RM_SUP_OVERHANG: c_int = 3;
+pub const RM_SUP_SUPPORT_ON_PLATE: c_int = 4;
+pub const RM_SUP_SUPPORT_ON_PART: c_int = 5;
+pub const RM_SUP_RUNS: c_int = 6;
+pub const RM_SUP_LANDINGS: c_int = 7;
+pub const RM_SUP_COUNTS: c_int = 8;
+// enum rm_supstat: indices into the statistics of a support call; RM_SUP_STATS is their number
+pub const RM_SUP_STAT_BRICKS: c_int = 0;
+pub const RM_SUP_STAT_BRICKS_KEPT: c_int = 1;
+pub const RM_SUP_STAT_BRICKS_INSIDE: c_int = 2;
+pub const RM_SUP_STAT_EVALUATIONS: c_int = 3;
+pub const RM_SUP_STAT_SCRATCH_BYTES: c_int = 4;
+pub const RM_SUP_STATS: c_int = 5;
+
 // Slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table).
 // enum rm_slicecount: indices into the counts of rm_slice_contours; RM_SLICE_COUNTS is their number
 pub const RM_SLICE_POINTS: c_int = 0;
@@ -354,6 +382,12 @@ extern "C" {
                                  stream: *mut c_void, out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
     pub fn rm_distance_features(ctx: *mut rm_ctx, r2_wall: u32, r2_gap: u32, out_counts: *mut u64, n_counts: u32) -> c_int;
     pub fn rm_read_distance(ctx: *mut rm_ctx, out_d2: *mut u32, out_mask: *mut c_void, is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_support_solid(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, level: f32, up: u32,
+                            r2: u32, plate: u32, out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_support_occupancy(ctx: *mut rm_ctx, nx: u32, ny: u32, nz: u32, occupancy: *const c_void, is_device: c_int,
+                                stream: *mut c_void, up: u32, r2: u32, plate: u32, out_counts: *mut u64, n_counts: u32,
+                                out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_read_support(ctx: *mut rm_ctx, out_mask: *mut c_void, out_profile: *mut u32, is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_slice_contours(ctx: *mut rm_ctx, axis: u32, origin_uv: *const f32, step_uv: *const f32, nu: u32, nv: u32,
                              heights: *const f32, n_layers: u32, level: f32, flags: u32, out_counts: *mut u64,
                              n_counts: u32) -> c_int;
@@ -473,6 +507,8 @@ pub struct RayMarchingResources {
     topology: Cell<Option<(u64, u64, u64)>>,
     /// (lattice points, whether a features call has made a mask) of the last successful distance call: what `read_distance` writes
     distance: Cell<Option<(u64, bool)>>,
+    /// (lattice points, layers along the build direction) of the last successful support call: what `read_support` writes
+    support: Cell<Option<(u64, u32)>>,
 }
 
 unsafe impl Send for RayMarchingResources {} // a context may move between threads; it is not Sync
@@ -486,7 +522,8 @@ impl RayMarchingResources {
             let msg = unsafe { CStr::from_ptr(rm_last_error(std::ptr::null_mut())) };
             return Err(RmError { status: rc, message: msg.to_string_lossy().into_owned() });
         }
-        Ok(Self { ctx, mesh: Cell::new(None), slices: Cell::new(None), topology: Cell::new(None), distance: Cell::new(None) })
+        Ok(Self { ctx, mesh: Cell::new(None), slices: Cell::new(None), topology: Cell::new(None), distance: Cell::new(None),
+                  support: Cell::new(None) })
     }
 
     fn check(&self, rc: c_int) -> Result<(), RmError> {
@@ -830,6 +867,59 @@ impl RayMarchingResources {
         let pd = out_d2.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
         let pm = out_mask.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr() as *mut c_void);
         self.check(unsafe { rm_read_distance(self.ctx, pd, pm, 0, std::ptr::null_mut()) })
+    }
+
+    /// Overhangs and supports of the solid `map_scene < level` on the lattice (`rm_support_solid`; 2..1024 points per axis, at
+    /// most 2^28 in all) for the build direction `up` (`RM_UP_*`), the squared reach `r2` (index units, 0..255) and the plate's
+    /// height (`None`: the lowest layer that holds an inside point): fills `out_counts` (at least `RM_SUP_COUNTS` entries,
+    /// indexed by `RM_SUP_*`) and `out_stats` (at least `RM_SUP_STATS`, indexed by `RM_SUP_STAT_*`).  Exact integers: every run
+    /// gives the same words.  `read_support` copies mask and profile out.  Leaves the context's mesh, slices, labelling and
+    /// distance volume alone.
+    pub fn support_solid(&self, origin: [f32; 3], step: [f32; 3], nx: u32, ny: u32, nz: u32, level: f32, up: c_int, r2: u32,
+                         plate: Option<u32>, out_counts: &mut [u64], out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(out_counts.len() >= RM_SUP_COUNTS as usize, "support_solid: out_counts is shorter than RM_SUP_COUNTS entries");
+        assert!(out_stats.len() >= RM_SUP_STATS as usize, "support_solid: out_stats is shorter than RM_SUP_STATS entries");
+        assert!(plate != Some(RM_SUPPORT_PLATE_AUTO), "support_solid: None is the automatic plate");
+        self.support.set(None);  // a failed call may have released the previous result
+        self.check(unsafe {
+            rm_support_solid(self.ctx, origin.as_ptr(), step.as_ptr(), nx, ny, nz, level, up as u32, r2, plate.unwrap_or(RM_SUPPORT_PLATE_AUTO),
+                             out_counts.as_mut_ptr(), RM_SUP_COUNTS as u32, out_stats.as_mut_ptr(), RM_SUP_STATS as u32)
+        })?;
+        self.support.set(Some((nx as u64 * ny as u64 * nz as u64, [nx, ny, nz][(up >> 1) as usize])));
+        Ok(())
+    }
+
+    /// `support_solid` of a caller's occupancy in host memory (`rm_support_occupancy`): one byte per point, x fastest, nonzero =
+    /// inside.  The brick statistics are 0.
+    pub fn support_occupancy(&self, nx: u32, ny: u32, nz: u32, occupancy: &[u8], up: c_int, r2: u32, plate: Option<u32>,
+                             out_counts: &mut [u64], out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(occupancy.len() as u64 >= nx as u64 * ny as u64 * nz as u64, "support_occupancy: occupancy is shorter than nx * ny * nz bytes");
+        assert!(out_counts.len() >= RM_SUP_COUNTS as usize, "support_occupancy: out_counts is shorter than RM_SUP_COUNTS entries");
+        assert!(out_stats.len() >= RM_SUP_STATS as usize, "support_occupancy: out_stats is shorter than RM_SUP_STATS entries");
+        assert!(plate != Some(RM_SUPPORT_PLATE_AUTO), "support_occupancy: None is the automatic plate");
+        self.support.set(None);  // a failed call may have released the previous result
+        self.check(unsafe {
+            rm_support_occupancy(self.ctx, nx, ny, nz, occupancy.as_ptr() as *const c_void, 0, std::ptr::null_mut(), up as u32, r2,
+                                 plate.unwrap_or(RM_SUPPORT_PLATE_AUTO), out_counts.as_mut_ptr(), RM_SUP_COUNTS as u32,
+                                 out_stats.as_mut_ptr(), RM_SUP_STATS as u32)
+        })?;
+        self.support.set(Some((nx as u64 * ny as u64 * nz as u64, [nx, ny, nz][(up >> 1) as usize])));
+        Ok(())
+    }
+
+    /// The mask of the last support call (one byte per lattice point: 0 outside, 1 inside, 2 overhang, 3 support on the plate,
+    /// 4 support on the part) and its profile (four words per layer along the build direction, height 0 first: inside, overhang,
+    /// support on the plate, support on the part).  `None` skips that output.  `RM_ERR_ARG` before any support call.
+    pub fn read_support(&self, out_mask: Option<&mut [u8]>, out_profile: Option<&mut [u32]>) -> Result<(), RmError> {
+        let (n, layers) = match self.support.get() {
+            Some((n, l)) => (n as usize, l as usize),
+            None => return Err(RmError { status: RM_ERR_ARG, message: "read_support: no support call has been made".to_string() }),
+        };
+        assert!(out_mask.as_ref().map_or(true, |s| s.len() >= n), "read_support: out_mask is shorter than {} points", n);
+        assert!(out_profile.as_ref().map_or(true, |s| s.len() >= 4 * layers), "read_support: out_profile is shorter than {} words", 4 * layers);
+        let pm = out_mask.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr() as *mut c_void);
+        let pp = out_profile.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        self.check(unsafe { rm_read_support(self.ctx, pm, pp, 0, std::ptr::null_mut()) })
     }
 
     /// The mesh of the last successful `extract_mesh` (of the (vertices, triangles) it returned): positions (three per

@@ -583,6 +583,66 @@ int rm_distance_occupancy(rm_ctx* ctx, uint32_t nx, uint32_t ny, uint32_t nz, co
 int rm_distance_features(rm_ctx* ctx, uint32_t r2_wall, uint32_t r2_gap, uint64_t* out_counts, uint32_t n_counts);
 int rm_read_distance(rm_ctx* ctx, uint32_t* out_d2, void* out_mask, int is_device, void* stream);
 
+/* Overhangs and supports (extension; DESIGN.md section 21 is the contract, to the last bit): for one of the six axis directions
+ * as the build direction, which points of the solid overhang, which points of the clearance a support column would fill, and
+ * whether that column stands on the plate or on the part.
+ * Lattice, values, "inside" and limits are rm_label_solid's and rm_distance_solid's (2..1024 points per axis, at most 2^28 in
+ * all, RM_ERR_RANGE otherwise; linear index i + nx * (j + ny * k)); points beyond the lattice are outside.
+ * `up` is one of RM_UP_* (RM_ERR_ARG otherwise), a its axis and n_a that axis' points.  The HEIGHT of a point is h = p_a for a
+ * positive direction and n_a - 1 - p_a for a negative one; BELOW p is the point of height h - 1 with the same other two
+ * coordinates; a LAYER is all points of one height, a COLUMN all points that share the other two coordinates.
+ * `plate` is a height h0 in 0..n_a - 1 (RM_ERR_RANGE for more), or RM_SUPPORT_PLATE_AUTO: the lowest height that holds an
+ * inside point, 0 for an empty solid.  Layers below h0 are under the plate: their points keep class 0 or 1 in the mask, count
+ * in POINTS and in column 0 of the profile, and take part in nothing else.
+ * `r2` is a squared reach in index units, 0..255 (RM_ERR_RANGE otherwise).  An inside point p with h > h0 is an OVERHANG iff no
+ * inside point q of layer h - 1 has du^2 + dv^2 <= r2, du and dv the differences of p and q in the two in-layer coordinates
+ * (the digital disc).  Inside points of layer h0 rest on the plate and never overhang.  r2 = 0: only the point directly below
+ * supports; 1: 45 degrees at equal steps, with the four neighbours; 2: with eight.  The test is local, as in a slicer: material
+ * in the layer below counts as built.
+ * An outside point p with h >= h0 is a SUPPORT point iff the first inside point above it in its column exists and is an
+ * overhang.  Its RUN is the maximal stretch of support points of its column around it; the run ends ON THE PLATE if no inside
+ * point of the column has a height in [h0, h), ON THE PART otherwise.
+ * The mask: one byte per point, x fastest -- 0 outside, 1 inside, 2 overhang (inside), 3 support on the plate, 4 support on the
+ * part.  (mask == 2) or (mask >= 3) as bytes is an occupancy for rm_label_occupancy: overhang regions, support bodies.
+ * out_counts[RM_SUP_*]:
+ *   POINTS            the inside points (RM_TOPO_POINTS on the same lattice)
+ *   PLATE             the h0 used
+ *   BASE              the inside points of layer h0
+ *   OVERHANG          the overhang points
+ *   SUPPORT_ON_PLATE, SUPPORT_ON_PART   the support points whose run ends on the plate / on the part
+ *   RUNS              the support points directly below an overhang point
+ *   LANDINGS          the support points with h > h0 whose point below is inside
+ * The profile: n_a x 4 u32 in height order (height 0 first) -- per layer its inside points, overhang points, support points on
+ * the plate and support points on the part; the last three are 0 below h0.
+ * out_stats[RM_SUP_STAT_*]: BRICKS, BRICKS_KEPT, BRICKS_INSIDE, EVALUATIONS as rm_mass_moments reports them for the same lattice
+ * and level (0 for rm_support_occupancy); SCRATCH_BYTES, the device memory the call used besides mask and profile.
+ * rm_support_occupancy analyses the caller's occupancy instead: one byte per point, x fastest, nonzero = inside; in host memory,
+ * or (is_device) in device memory, read after the work queued on `stream` (RM_STREAM_OWN: the context's).
+ * rm_read_support copies the last mask (out_mask, one byte per point) and the last profile (out_profile, n_a * 4 u32) out; either
+ * may be NULL; is_device and stream as for rm_query_points (a device out_profile: 4-byte aligned); the next support call waits
+ * for a device read that is still running.
+ * Every output is a bit, a count or a minimum: two runs, and any correct implementation, give identical words.
+ * The calls are synchronous on the context's own stream, ordered after its earlier work; they never touch the draw state, and
+ * the result lives in buffers of its own until the next support call or rm_destroy: it replaces neither the context's mesh, its
+ * slices, its labelling nor its distance volume.  Errors (every check precedes the first launch, and a failed call leaves the
+ * outputs untouched): RM_ERR_NULL for a NULL output or occupancy; RM_ERR_ARG for n_counts < RM_SUP_COUNTS, n_stats <
+ * RM_SUP_STATS, an `up` above 5, a level, origin or step that is not finite or a step <= 0, and for rm_read_support before any
+ * support call; RM_ERR_RANGE for the lattice, r2 and plate; RM_ERR_DEVICE when device memory runs out (about 2.6 bytes per
+ * point); otherwise those of a query for the program and limits. */
+#define RM_SUPPORT_PLATE_AUTO 0xFFFFFFFFu /* plate: the lowest height that holds an inside point */
+enum rm_up { RM_UP_POS_X = 0, RM_UP_NEG_X = 1, RM_UP_POS_Y = 2, RM_UP_NEG_Y = 3, RM_UP_POS_Z = 4, RM_UP_NEG_Z = 5 };
+enum rm_supcount { RM_SUP_POINTS = 0, RM_SUP_PLATE = 1, RM_SUP_BASE = 2, RM_SUP_OVERHANG = 3, RM_SUP_SUPPORT_ON_PLATE = 4,
+                   RM_SUP_SUPPORT_ON_PART = 5, RM_SUP_RUNS = 6, RM_SUP_LANDINGS = 7, RM_SUP_COUNTS = 8 };
+enum rm_supstat { RM_SUP_STAT_BRICKS = 0, RM_SUP_STAT_BRICKS_KEPT = 1, RM_SUP_STAT_BRICKS_INSIDE = 2,
+                  RM_SUP_STAT_EVALUATIONS = 3, RM_SUP_STAT_SCRATCH_BYTES = 4, RM_SUP_STATS = 5 };
+int rm_support_solid(rm_ctx* ctx, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                     uint32_t up, uint32_t r2, uint32_t plate, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
+                     uint32_t n_stats);
+int rm_support_occupancy(rm_ctx* ctx, uint32_t nx, uint32_t ny, uint32_t nz, const void* occupancy, int is_device, void* stream,
+                         uint32_t up, uint32_t r2, uint32_t plate, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
+                         uint32_t n_stats);
+int rm_read_support(rm_ctx* ctx, void* out_mask, uint32_t* out_profile, int is_device, void* stream);
+
 /* Slicing (extension; DESIGN.md section 16 is the contract, to the last bit): the closed outlines of the solid d < level in a
  * stack of planes, as ordered polylines -- what a slicer or a section drawing needs, evaluated directly on a 2-D lattice
  * per layer instead of through a triangle mesh.  From the program, limits and material table as they are at the call.

@@ -80,6 +80,18 @@ DIST_FEATURE_NAMES = ("core", "thin", "gap_core", "narrow")
 DIST_STAT_NAMES = ("bricks", "bricks_kept", "bricks_inside", "evaluations", "scratch_bytes")
 RM_DIST_INSIDE_BIT, RM_DIST_NONE, RM_DIST_SKIP = 0x80000000, 0x7FFFFFFF, 0xFFFFFFFF
 DIST_MASK_OUTSIDE, DIST_MASK_INSIDE, DIST_MASK_THIN, DIST_MASK_NARROW = range(4)
+# overhangs and supports (rm_support_solid / rm_support_occupancy / rm_read_support): enum rm_up, enum rm_supcount, enum rm_supstat,
+# the automatic plate and the values of the mask
+RM_UP_POS_X, RM_UP_NEG_X, RM_UP_POS_Y, RM_UP_NEG_Y, RM_UP_POS_Z, RM_UP_NEG_Z = range(6)
+UP_NAMES = ("+x", "-x", "+y", "-y", "+z", "-z")
+(RM_SUP_POINTS, RM_SUP_PLATE, RM_SUP_BASE, RM_SUP_OVERHANG, RM_SUP_SUPPORT_ON_PLATE, RM_SUP_SUPPORT_ON_PART, RM_SUP_RUNS,
+ RM_SUP_LANDINGS, RM_SUP_COUNTS) = range(9)
+SUP_COUNT_NAMES = ("points", "plate", "base", "overhang", "support_on_plate", "support_on_part", "runs", "landings")
+(RM_SUP_STAT_BRICKS, RM_SUP_STAT_BRICKS_KEPT, RM_SUP_STAT_BRICKS_INSIDE, RM_SUP_STAT_EVALUATIONS, RM_SUP_STAT_SCRATCH_BYTES,
+ RM_SUP_STATS) = range(6)
+SUP_STAT_NAMES = ("bricks", "bricks_kept", "bricks_inside", "evaluations", "scratch_bytes")
+RM_SUPPORT_PLATE_AUTO = 0xFFFFFFFF
+SUP_MASK_OUTSIDE, SUP_MASK_INSIDE, SUP_MASK_OVERHANG, SUP_MASK_ON_PLATE, SUP_MASK_ON_PART = range(5)
 # slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table): enum rm_slicecount, the indices of out_counts
 RM_SLICE_POINTS, RM_SLICE_CONTOURS, RM_SLICE_COUNTS = 0, 1, 2
 # lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit): enum rm_light, the parameter names in index order
@@ -224,6 +236,12 @@ def hip_lib():
         L.rm_distance_features.restype = C.c_int
         L.rm_read_distance.argtypes = [vp, vp, vp, C.c_int, vp]
         L.rm_read_distance.restype = C.c_int
+        L.rm_support_solid.argtypes = [vp, f3, f3, u32, u32, u32, C.c_float, u32, u32, u32, C.POINTER(u64), u32, C.POINTER(u64), u32]
+        L.rm_support_solid.restype = C.c_int
+        L.rm_support_occupancy.argtypes = [vp, u32, u32, u32, vp, C.c_int, vp, u32, u32, u32, C.POINTER(u64), u32, C.POINTER(u64), u32]
+        L.rm_support_occupancy.restype = C.c_int
+        L.rm_read_support.argtypes = [vp, vp, vp, C.c_int, vp]
+        L.rm_read_support.restype = C.c_int
         L.rm_slice_contours.argtypes = [vp, u32, f3, f3, u32, u32, f3, u32, C.c_float, u32, C.POINTER(u64), u32]
         L.rm_slice_contours.restype = C.c_int
         L.rm_read_slices.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]

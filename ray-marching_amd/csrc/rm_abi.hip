@@ -32,6 +32,7 @@
 #include "rm_mass.h"
 #include "rm_topology.h"
 #include "rm_distance.h"
+#include "rm_support.h"
 #include "rm_slice.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
@@ -172,6 +173,11 @@ struct rm_ctx {
     DevBuf<char> d_dvol, d_dmask;
     bool dist_valid = false, dist_mask_valid = false;
     uint32_t dist_nx = 0, dist_ny = 0, dist_nz = 0;
+    // overhangs and supports (rm_support.h): the mask and the profile of the last support call, in buffers of their own (their
+    // scratch is d_mscratch)
+    DevBuf<char> d_smask, d_sprof;
+    bool sup_valid = false;
+    uint32_t sup_n = 0, sup_nh = 0;
     // scratch for host-destination draws and batch uniforms
     DevBuf<char> d_out;
     DevBuf<rm_uniforms> d_frames;
@@ -2401,6 +2407,202 @@ RM_EXPORT int rm_read_distance(rm_ctx* c, uint32_t* out_d2, void* out_mask, int 
     const size_t n = (size_t)c->dist_nx * c->dist_ny * c->dist_nz;
     if (out_d2) HIP_TRY(c, hipMemcpyAsync(out_d2, c->d_dvol.p, n * 4u, kind, s));
     if (out_mask) HIP_TRY(c, hipMemcpyAsync(out_mask, c->d_dmask.p, n, kind, s));
+    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+// ---- overhangs and supports (rm_support.h) ----
+namespace {
+
+static_assert(rmk::kSupPlateAuto == RM_SUPPORT_PLATE_AUTO, "the automatic plate");
+static_assert(rml::kSupMaxWords * 64u == kMaxTopoDim, "a bit row holds the longest axis");
+static_assert(rml::kSupMaxReach * rml::kSupMaxReach <= rml::kSupMaxR2 && (rml::kSupMaxReach + 1u) * (rml::kSupMaxReach + 1u) > rml::kSupMaxR2,
+              "the halo of the overhang tile is floor(sqrt(r2))");
+
+// The canonical frame (rm_support.h) of a lattice for a build direction.
+rmk::SupFrame sup_frame(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t up) {
+    rmk::SupFrame f;
+    switch (up >> 1) {
+    case 0: f = rmk::SupFrame{ny, nz, nx, 0u, nx, nx * ny, 1u, 0u}; break;   // x up: the bits run along y
+    case 1: f = rmk::SupFrame{nx, nz, ny, 0u, 1u, nx * ny, nx, 0u}; break;   // y up
+    default: f = rmk::SupFrame{nx, ny, nz, 0u, 1u, nx, nx * ny, 0u}; break;  // z up
+    }
+    f.nw = (f.nu + 63u) / 64u;
+    f.neg = up & 1u;
+    return f;
+}
+uint32_t sup_plane_words(const rmk::SupFrame& f) { return f.nh * f.nv * f.nw; }  // (<= 2^28 / 64 * 2: a 65th point costs a whole word)
+
+// The argument checks the two support calls share, after those of their outputs and their lattice's values.
+int check_support(rm_ctx* c, const char* fn, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t up, uint32_t r2, uint32_t plate) {
+    if (up > (uint32_t)RM_UP_NEG_Z) return fail(c, RM_ERR_ARG, "%s: up %u is not one of RM_UP_*", fn, up);
+    if (!topo_lattice_ok(nx, ny, nz))
+        return fail(c, RM_ERR_RANGE, "%s: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", fn, nx, ny, nz);
+    if (r2 > rml::kSupMaxR2) return fail(c, RM_ERR_RANGE, "%s: r2 %u: a squared reach is 0..255", fn, r2);
+    const uint32_t nh = sup_frame(nx, ny, nz, up).nh;
+    if (plate != RM_SUPPORT_PLATE_AUTO && plate >= nh)
+        return fail(c, RM_ERR_RANGE, "%s: plate %u: a height of 0..%u, or RM_SUPPORT_PLATE_AUTO", fn, plate, nh - 1u);
+    return RM_OK;
+}
+
+// From the occupancy in S.occ on: pack, overhang, columns, count, compose; the profile summed on the host (at most 1024 layers of
+// six words).  counts: RM_SUP_COUNTS words.
+int support_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupFrame& f, const rml::SupportScratch& S, uint32_t r2,
+                    uint32_t plate, uint64_t* counts) {
+    char* sc = c->d_mscratch.p;
+    const rml::SupportProfile R(f.nh);
+    char* pr = c->d_sprof.p;
+    uint8_t* mask = reinterpret_cast<uint8_t*>(c->d_smask.p);
+    unsigned long long *ins = S.ins.at(sc), *ov = S.ov.at(sc), *sup = S.sup.at(sc), *plt = S.plt.at(sc);
+    uint32_t* h0w = S.plate.at(sc);
+    const uint32_t n_words = sup_plane_words(f), ncw = f.nv * f.nw;
+    const bool xup = f.sh == 1u;
+    // a wave's tasks in pack and compose: four words each, or with x up one (row, word) and 64 layers
+    const uint32_t n_tasks = xup ? f.nv * f.nw * ((f.nh + 63u) / 64u) : n_words;
+    const uint32_t n_waves = xup ? n_tasks : (n_tasks + rmk::kSupWordsPerWave - 1u) / rmk::kSupWordsPerWave;
+    const dim3 task_grid((n_waves + 3u) / 4u);
+    HIP_TRY(c, hipMemsetAsync(h0w, 0xFF, 16, s));
+    HIP_TRY(c, hipMemsetAsync(pr, 0, R.bytes, s));
+    const uint8_t* occ = S.occ.at(sc);
+    if (xup)
+        hipLaunchKernelGGL(rmk::rm_sup_pack_kernel<true>, task_grid, dim3(256), 0, s, f, n_tasks, plate, occ, ins, h0w);
+    else
+        hipLaunchKernelGGL(rmk::rm_sup_pack_kernel<false>, task_grid, dim3(256), 0, s, f, n_tasks, plate, occ, ins, h0w);
+    uint32_t reach = 0u;
+    while ((reach + 1u) * (reach + 1u) <= r2) reach++;
+    const uint32_t tv = rml::sup_tile_rows(f.nw);
+    hipLaunchKernelGGL(rmk::rm_sup_overhang_kernel, dim3((f.nv + tv - 1u) / tv, f.nh), dim3(256), rml::SupCoverLds(tv, reach, f.nw).bytes, s, f.nv,
+                       f.nw, tv, r2, reach, plate, static_cast<const uint32_t*>(h0w), static_cast<const unsigned long long*>(ins), ov);
+    hipLaunchKernelGGL(rmk::rm_sup_columns_kernel, dim3((ncw + rmk::kSupColumnThreads - 1u) / rmk::kSupColumnThreads), dim3(rmk::kSupColumnThreads), 0, s, ncw, f.nh, plate, static_cast<const uint32_t*>(h0w),
+                       static_cast<const unsigned long long*>(ins), static_cast<const unsigned long long*>(ov), sup, plt);
+    hipLaunchKernelGGL(rmk::rm_sup_count_kernel, dim3((ncw + 255u) / 256u, f.nh), dim3(256), 0, s, ncw, f.nh, plate, static_cast<const uint32_t*>(h0w),
+                       static_cast<const unsigned long long*>(ins), static_cast<const unsigned long long*>(ov),
+                       static_cast<const unsigned long long*>(sup), static_cast<const unsigned long long*>(plt), R.profile.at(pr), R.extra.at(pr));
+    if (xup)
+        hipLaunchKernelGGL(rmk::rm_sup_compose_kernel<true>, task_grid, dim3(256), 0, s, f, n_tasks, static_cast<const unsigned long long*>(ins),
+                           static_cast<const unsigned long long*>(ov), static_cast<const unsigned long long*>(sup),
+                           static_cast<const unsigned long long*>(plt), mask);
+    else
+        hipLaunchKernelGGL(rmk::rm_sup_compose_kernel<false>, task_grid, dim3(256), 0, s, f, n_tasks, static_cast<const unsigned long long*>(ins),
+                           static_cast<const unsigned long long*>(ov), static_cast<const unsigned long long*>(sup),
+                           static_cast<const unsigned long long*>(plt), mask);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint32_t> rows((size_t)f.nh * 6u);
+    uint32_t h0 = 0u;
+    HIP_TRY(c, hipMemcpyAsync(rows.data(), R.profile.at(pr), (size_t)f.nh * 16u, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(rows.data() + (size_t)f.nh * 4u, R.extra.at(pr), (size_t)f.nh * 8u, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&h0, h0w, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    h0 = plate != RM_SUPPORT_PLATE_AUTO ? plate : h0 == RM_SUPPORT_PLATE_AUTO ? 0u : h0;
+    for (int k = 0; k < RM_SUP_COUNTS; k++) counts[k] = 0u;
+    for (uint32_t h = 0; h < f.nh; h++) {
+        counts[RM_SUP_POINTS] += rows[4u * h];
+        counts[RM_SUP_OVERHANG] += rows[4u * h + 1u];
+        counts[RM_SUP_SUPPORT_ON_PLATE] += rows[4u * h + 2u];
+        counts[RM_SUP_SUPPORT_ON_PART] += rows[4u * h + 3u];
+        counts[RM_SUP_RUNS] += rows[4u * f.nh + 2u * h];
+        counts[RM_SUP_LANDINGS] += rows[4u * f.nh + 2u * h + 1u];
+    }
+    counts[RM_SUP_PLATE] = h0;
+    counts[RM_SUP_BASE] = rows[4u * h0];
+    c->sup_valid = true;
+    c->sup_n = G.n;
+    c->sup_nh = f.nh;
+    return RM_OK;
+}
+
+// The buffers of a support call: scratch, mask and profile.  The last result is gone from here on.
+int support_reserve(rm_ctx* c, const TopoGrid& G, const rmk::SupFrame& f, const rml::SupportScratch& S) {
+    int rc = c->d_mscratch.reserve(c, S.bytes);
+    if (rc != RM_OK) return rc;
+    c->sup_valid = false;
+    if ((rc = c->d_smask.reserve(c, G.n, "support mask")) != RM_OK) return rc;
+    return c->d_sprof.reserve(c, rml::SupportProfile(f.nh).bytes, "support profile");
+}
+
+}  // namespace
+
+RM_EXPORT int rm_support_solid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                               uint32_t up, uint32_t r2, uint32_t plate, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
+                               uint32_t n_stats) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_counts || !out_stats) return fail(c, RM_ERR_NULL, "rm_support_solid: out_counts or out_stats is NULL");
+    if (n_counts < (uint32_t)RM_SUP_COUNTS) return fail(c, RM_ERR_ARG, "rm_support_solid: n_counts %u < RM_SUP_COUNTS", n_counts);
+    if (n_stats < (uint32_t)RM_SUP_STATS) return fail(c, RM_ERR_ARG, "rm_support_solid: n_stats %u < RM_SUP_STATS", n_stats);
+    if (int rc = check_lattice(c, "rm_support_solid", origin, step)) return rc;
+    if (int rc = check_iso(c, "rm_support_solid", level, 0u)) return rc;
+    if (int rc = check_support(c, "rm_support_solid", nx, ny, nz, up, r2, plate)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    SolidOccupancy O;
+    int rc = solid_occupancy_begin(c, "rm_support_solid", s, origin, step, nx, ny, nz, &O);  // after a device read of the last mask, too
+    if (rc != RM_OK) return rc;
+    const TopoGrid G = topo_grid(origin, step, nx, ny, nz);
+    const rmk::SupFrame f = sup_frame(nx, ny, nz, up);
+    const rml::SupportScratch S(G.n, G.g.nb, G.n_pblocks, sup_plane_words(f));
+    if ((rc = support_reserve(c, G, f, S)) != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    unsigned long long* evals = S.evals.at(sc);
+    if ((rc = solid_occupancy_fill(c, s, O, G, level, S.cls.at(sc), S.psums.at(sc), S.ptot.at(sc), S.occ.at(sc), evals)) != RM_OK) return rc;
+    uint64_t counts[RM_SUP_COUNTS];
+    if ((rc = support_lattice(c, s, G, f, S, r2, plate, counts)) != RM_OK) return rc;
+    unsigned long long tot[2] = {0ull, 0ull}, ev = 0ull;
+    HIP_TRY(c, hipMemcpyAsync(tot, S.ptot.at(sc), sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (int k = 0; k < RM_SUP_COUNTS; k++) out_counts[k] = counts[k];
+    out_stats[RM_SUP_STAT_BRICKS] = G.g.nb;
+    out_stats[RM_SUP_STAT_BRICKS_KEPT] = tot[0];
+    out_stats[RM_SUP_STAT_BRICKS_INSIDE] = tot[1];
+    out_stats[RM_SUP_STAT_EVALUATIONS] = G.g.nb + ev;
+    out_stats[RM_SUP_STAT_SCRATCH_BYTES] = S.bytes;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_support_occupancy(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz, const void* occupancy, int is_device, void* stream,
+                                   uint32_t up, uint32_t r2, uint32_t plate, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
+                                   uint32_t n_stats) {
+    if (!c) return RM_ERR_NULL;
+    if (!occupancy || !out_counts || !out_stats)
+        return fail(c, RM_ERR_NULL, "rm_support_occupancy: occupancy, out_counts or out_stats is NULL");
+    if (n_counts < (uint32_t)RM_SUP_COUNTS) return fail(c, RM_ERR_ARG, "rm_support_occupancy: n_counts %u < RM_SUP_COUNTS", n_counts);
+    if (n_stats < (uint32_t)RM_SUP_STATS) return fail(c, RM_ERR_ARG, "rm_support_occupancy: n_stats %u < RM_SUP_STATS", n_stats);
+    if (int rc = check_support(c, "rm_support_occupancy", nx, ny, nz, up, r2, plate)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    order_with_previous(c, s);  // after a device read of the last mask, too
+    const float zero[3] = {0.0f, 0.0f, 0.0f}, one[3] = {1.0f, 1.0f, 1.0f};
+    const TopoGrid G = topo_grid(zero, one, nx, ny, nz);
+    const rmk::SupFrame f = sup_frame(nx, ny, nz, up);
+    const rml::SupportScratch S(G.n, G.g.nb, G.n_pblocks, sup_plane_words(f));
+    int rc = support_reserve(c, G, f, S);
+    if (rc != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    if (is_device) {
+        // the caller's array is ready when the work queued on its stream is done; the call is synchronous anyway
+        const hipStream_t su = user_stream(c, stream);
+        if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
+    }
+    HIP_TRY(c, hipMemcpyAsync(S.occ.at(sc), occupancy, G.n, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    uint64_t counts[RM_SUP_COUNTS];
+    if ((rc = support_lattice(c, s, G, f, S, r2, plate, counts)) != RM_OK) return rc;
+    for (int k = 0; k < RM_SUP_COUNTS; k++) out_counts[k] = counts[k];
+    for (int k = 0; k < RM_SUP_STATS; k++) out_stats[k] = 0u;
+    out_stats[RM_SUP_STAT_SCRATCH_BYTES] = S.bytes;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_read_support(rm_ctx* c, void* out_mask, uint32_t* out_profile, int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!c->sup_valid) return fail(c, RM_ERR_ARG, "rm_read_support: no support call has been made");
+    if (is_device && misaligned(out_profile, 4)) return fail(c, RM_ERR_ARG, "rm_read_support: a device out_profile needs 4-byte alignment");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = dest_stream(c, is_device, stream);
+    order_with_previous(c, s);  // (the next support call waits for this stream in turn)
+    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (out_mask) HIP_TRY(c, hipMemcpyAsync(out_mask, c->d_smask.p, c->sup_n, kind, s));
+    if (out_profile)
+        HIP_TRY(c, hipMemcpyAsync(out_profile, rml::SupportProfile(c->sup_nh).profile.at(c->d_sprof.p), (size_t)c->sup_nh * 16u, kind, s));
     if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
     return RM_OK;
 }

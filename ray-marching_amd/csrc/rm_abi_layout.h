@@ -155,6 +155,33 @@ struct DistFeatureScratch {
           folded(a.take<unsigned long long>((size_t)n_fblocks * 16u)), result(a.take<unsigned long long>(16)), bytes(a.total) {}
 };
 
+// rm_support_solid / rm_support_occupancy, for a lattice of n points in nb bricks whose bit planes hold n_words u64 words each
+// (rm_support.h: layers x rows x ceil(bit-axis points / 64)): per point its occupancy (1 B); per brick its class (1 B); per 256
+// bricks the probe's block sum; totals and the evaluation count; the four planes (inside, overhang, support, support on the
+// plate: half a byte per point in all when the bit axis fills its words); the automatic plate's height.  The mask (1 B per
+// point) and the profile are the result and lie in buffers of their own.
+struct SupportScratch {
+    Carver a;
+    Region<uint8_t> occ, cls;
+    Region<unsigned long long> psums, ptot, evals, ins, ov, sup, plt;
+    Region<uint32_t> plate;
+    size_t bytes;
+    SupportScratch(uint32_t n, uint32_t nb, uint32_t n_pblocks, uint32_t n_words)
+        : occ(a.take<uint8_t>(n)), cls(a.take<uint8_t>(nb)), psums(a.take<unsigned long long>(n_pblocks)),
+          ptot(a.take<unsigned long long>(2)), evals(a.take<unsigned long long>(2)), ins(a.take<unsigned long long>(n_words)),
+          ov(a.take<unsigned long long>(n_words)), sup(a.take<unsigned long long>(n_words)), plt(a.take<unsigned long long>(n_words)),
+          plate(a.take<uint32_t>(4)), bytes(a.total) {}
+};
+
+// ... and its profile, for nh layers: 4 words per layer (what rm_read_support copies out), then 2 per layer for the runs and
+// the landings.
+struct SupportProfile {
+    Carver a;
+    Region<uint32_t> profile, extra;
+    size_t bytes;
+    explicit SupportProfile(uint32_t nh) : profile(a.take<uint32_t>((size_t)nh * 4u)), extra(a.take<uint32_t>((size_t)nh * 2u)), bytes(a.total) {}
+};
+
 // rm_slice_contours' per-layer tables: heights, layer_first, the first vertex of each layer of a batch of `per`, totals.
 // (heights and layer_first lie before anything `per` sizes: rm_read_slices finds layer_first without it.)
 struct SliceLayerTables {

@@ -126,4 +126,15 @@ struct DistColumnLds {
     RM_LDS_FN DistColumnLds(uint32_t xt, uint32_t n) : col(0u), bytes(col + xt * n * 4u) {}
 };
 
+// ---- Overhang test (rm_support.h rm_sup_overhang_kernel) --------------------------------------------------------------------
+// The bit rows of the layer below that a tile of `tv` rows of one layer can see: tv + 2 reach rows (reach = floor(sqrt(r2)) <= 15
+// rows of halo on either side) of nw u64 words each (nw = ceil(points along the bit axis / 64) <= 16), row r at word r * nw.
+// tv: as many rows as give every one of the workgroup's 256 threads at most one word, 64 at the most: 5888 bytes for the widest rows.
+constexpr uint32_t kSupMaxReach = 15u, kSupMaxRows = 64u, kSupMaxWords = 16u, kSupMaxR2 = 255u;
+RM_LDS_FN uint32_t sup_tile_rows(uint32_t nw) { return 256u / nw < kSupMaxRows ? 256u / nw : kSupMaxRows; }
+struct SupCoverLds {
+    uint32_t rows, bytes;
+    RM_LDS_FN SupCoverLds(uint32_t tv, uint32_t reach, uint32_t nw) : rows(0u), bytes(rows + (tv + 2u * reach) * nw * 8u) {}
+};
+
 }  // namespace rml

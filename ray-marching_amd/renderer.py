@@ -646,6 +646,47 @@ class RayMarchingResources:
         self._check(self._L.rm_read_distance(self._h, C.c_void_p(d2_ptr or None), C.c_void_p(mask_ptr or None), 1,
                                              C.c_void_p(stream) if stream else None))
 
+    # -- overhangs and supports (rm_support_solid / rm_support_occupancy / rm_read_support) ---------------------------------------
+    def support_solid(self, lo, hi, resolution, level=0.0, up="+z", r2=1, plate=None):
+        """Overhangs and supports of the solid map_scene < level inside the box [lo, hi], on the lattice extract_mesh builds from
+        (lo, hi, resolution) (2..1024 points per axis, at most 2^28 in all), for the build direction `up` ("+x" .. "-z", or
+        _ffi.RM_UP_*), the squared reach r2 (index units, 0..255; reach_r2 converts an angle) and the plate's height (None: the
+        lowest layer that holds an inside point): a Support."""
+        lo, step, n = self._box_lattice(lo, hi, resolution)
+        return self.support_solid_grid(lo, step, n, level, up, r2, plate)
+
+    def support_solid_grid(self, origin, step, shape, level=0.0, up="+z", r2=1, plate=None):
+        """support_solid on an exact lattice (origin, step, shape as sample_grid takes them)."""
+        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
+        up, r2, plate = _support_args(up, r2, plate)
+        counts = (C.c_uint64 * _ffi.RM_SUP_COUNTS)()
+        stats = (C.c_uint64 * _ffi.RM_SUP_STATS)()
+        self._check(self._L.rm_support_solid(self._h, fp(o), fp(s), nx, ny, nz, float(level), up, r2, plate, counts, _ffi.RM_SUP_COUNTS,
+                                             stats, _ffi.RM_SUP_STATS))
+        return self._support(counts, stats, o, s, (nx, ny, nz), up, r2)
+
+    def support_occupancy(self, occupancy, up="+z", r2=1, plate=None):
+        """rm_support_occupancy: overhangs and supports of a caller's occupancy, as label_occupancy takes it (indexed [k, j, i],
+        nonzero = inside; numpy, or a torch tensor on this context's GPU).  The Support's lattice is the unit lattice at the
+        origin."""
+        nx, ny, nz, ptr, is_device, stream, keep = self._occupancy_arg(occupancy)
+        up, r2, plate = _support_args(up, r2, plate)
+        counts = (C.c_uint64 * _ffi.RM_SUP_COUNTS)()
+        stats = (C.c_uint64 * _ffi.RM_SUP_STATS)()
+        self._check(self._L.rm_support_occupancy(self._h, nx, ny, nz, ptr, is_device, stream, up, r2, plate, counts, _ffi.RM_SUP_COUNTS,
+                                                 stats, _ffi.RM_SUP_STATS))
+        del keep
+        return self._support(counts, stats, np.zeros(3, dtype=np.float32), np.ones(3, dtype=np.float32), (nx, ny, nz), up, r2)
+
+    def _support(self, counts, stats, origin, step, shape, up, r2):
+        return Support(self, {name: int(counts[k]) for k, name in enumerate(_ffi.SUP_COUNT_NAMES)},
+                       {name: int(stats[k]) for k, name in enumerate(_ffi.SUP_STAT_NAMES)}, origin, step, shape, up, r2)
+
+    def read_support_device(self, mask_ptr=0, profile_ptr=0, stream=None):
+        """rm_read_support of the last mask and profile into device memory (integer addresses; 0 = not wanted), asynchronous."""
+        self._check(self._L.rm_read_support(self._h, C.c_void_p(mask_ptr or None), C.c_void_p(profile_ptr or None), 1,
+                                            C.c_void_p(stream) if stream else None))
+
     def _read_mesh(self, V, T, normals, ids, device):
         """rm_read_mesh of the extraction that just returned V vertices and T triangles, as a mesh.Mesh."""
         from . import mesh as _mesh
@@ -943,6 +984,89 @@ class DistanceFeatures:
         out = np.empty((nz, ny, nx), dtype=np.uint8)
         self._res._check(self._res._L.rm_read_distance(self._res._h, None, out.ctypes.data, 0, None))
         return out
+
+
+def reach_r2(angle_deg, step_up, step_in):
+    """The squared reach r2 (index units) of support_solid for a largest self-supporting overhang angle, measured from the build
+    direction: a layer may step out by t = tan(angle) * step_up / step_in points per layer, and r2 = floor(t^2 + 1e-9) (tan(45
+    degrees) is 0.9999999999999999 in binary64, and 45 degrees at equal steps must give 1).  step_in: the in-layer step, one
+    number or two equal ones.  ValueError for unequal in-layer steps, an angle outside [0, 90) and an r2 above 255."""
+    si = np.asarray(step_in, dtype=np.float64).reshape(-1)
+    if si.size not in (1, 2) or not np.all(si == si[0]) or not si[0] > 0 or not float(step_up) > 0:
+        raise ValueError("a reach needs one positive step for both in-layer axes and a positive step upwards, not %s and %s" % (step_in, step_up))
+    a = float(angle_deg)
+    if not 0.0 <= a < 90.0:
+        raise ValueError("an overhang angle lies in [0, 90) degrees, not %r" % (angle_deg,))
+    t = float(np.tan(np.radians(a))) * float(step_up) / float(si[0])
+    r2 = int(np.floor(t * t + 1e-9))
+    if r2 > 255:
+        raise ValueError("%g degrees at these steps reach %d squared points; the most is 255" % (a, r2))
+    return r2
+
+
+def _support_args(up, r2, plate):
+    """up, r2 and plate as the library takes them."""
+    if isinstance(up, str):
+        if up not in _ffi.UP_NAMES:
+            raise ValueError("up is one of %s, not %r" % (", ".join(_ffi.UP_NAMES), up))
+        up = _ffi.UP_NAMES.index(up)
+    if not 0 <= int(up) < 6:
+        raise ValueError("up is one of _ffi.RM_UP_* (0..5), not %r" % (up,))
+    if not 0 <= int(r2) < _ffi.RM_SUPPORT_PLATE_AUTO:
+        raise ValueError("a squared reach must be >= 0, not %r" % (r2,))
+    if plate is not None and not 0 <= int(plate) < _ffi.RM_SUPPORT_PLATE_AUTO:
+        raise ValueError("a plate is a height >= 0 or None, not %r" % (plate,))
+    return int(up), int(r2), _ffi.RM_SUPPORT_PLATE_AUTO if plate is None else int(plate)
+
+
+class Support:
+    """The result of support_solid / support_occupancy.  counts and stats: dicts (_ffi.SUP_COUNT_NAMES, _ffi.SUP_STAT_NAMES); up
+    (_ffi.RM_UP_*), r2, and origin, step (float32[3]) and shape of the lattice.  mask() and profile() read the context's buffers:
+    they hold while this is the context's last support call."""
+
+    def __init__(self, resources, counts, stats, origin, step, shape, up, r2):
+        self._res = resources
+        self.counts, self.stats = counts, stats
+        self.origin, self.step, self.shape = origin, step, shape
+        self.up, self.r2 = up, r2
+
+    def __repr__(self):
+        return "Support(up %s, %d overhang points, %d support points, on %s)" % (
+            _ffi.UP_NAMES[self.up], self.counts["overhang"], self.support_points, "x".join(map(str, self.shape)))
+
+    @property
+    def support_points(self):
+        return self.counts["support_on_plate"] + self.counts["support_on_part"]
+
+    @property
+    def layers(self):
+        """The points along the up axis."""
+        return self.shape[self.up >> 1]
+
+    def mask(self):
+        """The mask, uint8 (nz, ny, nx): 0 outside, 1 inside, 2 overhang, 3 support on the plate, 4 support on the part
+        (_ffi.SUP_MASK_*)."""
+        nx, ny, nz = self.shape
+        out = np.empty((nz, ny, nx), dtype=np.uint8)
+        self._res._check(self._res._L.rm_read_support(self._res._h, out.ctypes.data, None, 0, None))
+        return out
+
+    def profile(self):
+        """The profile, uint32 (layers, 4), height 0 first: per layer its inside points, overhang points, support points on the
+        plate and support points on the part."""
+        out = np.empty((self.layers, 4), dtype=np.uint32)
+        self._res._check(self._res._L.rm_read_support(self._res._h, None, out.ctypes.data, 0, None))
+        return out
+
+    def volume(self):
+        """The support material in world units: the support points times the volume of a cell."""
+        return self.support_points * float(np.prod(np.asarray(self.step, dtype=np.float64)))
+
+    def contact_area(self):
+        """The area (world units) over which supports touch the part: the runs (a support's top under an overhang point) and the
+        landings (its foot on the part), times the area of a cell of a layer."""
+        st = np.asarray(self.step, dtype=np.float64)
+        return (self.counts["runs"] + self.counts["landings"]) * float(np.prod(np.delete(st, self.up >> 1)))
 
 
 MASS_PROP_NAMES = ("volume", "mass", "cx", "cy", "cz", "ixx", "iyy", "izz", "ixy", "iyz", "ixz", "lo_x", "lo_y", "lo_z", "hi_x", "hi_y",
