@@ -26,6 +26,7 @@
 //              order); V, E, F, K and the exterior's points from the occupancy alone, one row per brick + the mass reducer.
 #pragma once
 #include "rm_mass.h"
+#include "rm_topo_union.h"
 
 namespace rmk {
 
@@ -173,61 +174,9 @@ __global__ __launch_bounds__(256) void rm_topo_local_kernel(SparseGrid g, const 
 }
 
 // ---- merge ------------------------------------------------------------------------------------------------------------------
-// parent[x] < x or parent[x] == x (a root), always: an index falls at every step, so `bound` (the number of lattice points) is
-// never reached.  Relaxed agent-scope loads: a plain load may be served by a stale line of another XCD's L2; a stale parent is an
-// older, still valid ancestor.
-// HALVE (the merge pass): every visited point is hung below its grandparent on the way -- by atomicMin, so a parent only ever falls
-// and stays a member of the component -- which keeps the chains of roots that unions across many bricks build short.
-template <bool HALVE>
-RM_DEV uint32_t topo_find(uint32_t* parent, uint32_t x, uint32_t bound) {
-    for (uint32_t n = 0; n < bound; n++) {
-        const uint32_t up = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (up == x) break;
-        if (HALVE) {
-            const uint32_t over = __hip_atomic_load(parent + up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (over == up) return up;
-            atomicMin(parent + x, over);
-            x = over;
-        } else {
-            x = up;
-        }
-    }
-    return x;
-}
-// Unites the components of a and b.  The larger root receives the smaller one by atomicMin.  When it was no root any more
-// (`old` != a), its parent is now min(old, b): the link that lost is made good by uniting `old` with b.  Each retry continues
-// with strictly smaller indices.
-RM_DEV void topo_unite(uint32_t* parent, uint32_t a, uint32_t b, uint32_t bound) {
-    for (uint32_t n = 0; n < bound; n++) {
-        a = topo_find<true>(parent, a, bound);
-        b = topo_find<true>(parent, b, bound);
-        if (a == b) return;
-        if (a < b) { const uint32_t s = a; a = b; b = s; }
-        const uint32_t old = atomicMin(parent + a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-// The neighbours (dx, dy, dz) that PRECEDE a point in linear order: 13 of the 26, 3 of the 6.  f(qi, qj, qk, faces) for those
-// inside the lattice.
-template <class F>
-RM_DEV void topo_for_preceding(const SparseGrid& g, uint32_t i, uint32_t j, uint32_t k, bool faces_only, F f) {
-#pragma unroll
-    for (int dz = -1; dz <= 0; dz++)
-#pragma unroll
-        for (int dy = -1; dy <= 1; dy++)
-#pragma unroll
-            for (int dx = -1; dx <= 1; dx++) {
-                if (!(dz < 0 || dy < 0 || (dy == 0 && dx < 0))) continue;
-                const int faces = (dx != 0) + (dy != 0) + (dz != 0);
-                if (faces_only && faces != 1) continue;
-                const uint32_t qi = i + (uint32_t)dx, qj = j + (uint32_t)dy, qk = k + (uint32_t)dz;  // (wraps past 0: >= n)
-                if (qi >= g.nx || qj >= g.ny || qk >= g.nz) continue;
-                f(qi, qj, qk);
-            }
-}
-
+// topo_find, topo_unite and topo_for_preceding live in rm_topo_union.h (included above), written in two memory primitives --
+// topo_load, a relaxed agent-scope load, and topo_fetch_min, atomicMin returning the old value -- so that the same three functions
+// also run on CPU threads in tests/cpp/topo_union_model.cpp.
 __global__ __launch_bounds__(256) void rm_topo_merge_kernel(SparseGrid g, const uint8_t* __restrict__ occ, uint32_t* parent) {
     const SparseBrick B = sparse_brick(g, blockIdx.x);
     const uint32_t bound = g.nx * g.ny * g.nz;
@@ -244,7 +193,7 @@ __global__ __launch_bounds__(256) void rm_topo_merge_kernel(SparseGrid g, const 
             if ((((qi ^ t.i) | (qj ^ t.j) | (qk ^ t.k)) >> 3) == 0u) return;  // the same brick: the local pass has united them
             const uint32_t q = topo_index(g, qi, qj, qk);
             if ((occ[q] != 0u) != c) return;
-            const uint32_t up = __hip_atomic_load(parent + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t up = topo_load(parent + q);
             if (up == last) return;
             last = up;
             mine = topo_find<true>(parent, mine, bound);  // (an ancestor of t.p: the walk continues where the last one ended)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import mass_ref as M
+import topology_cases as TC
 import topology_ref as TR
 
 F = np.float32
@@ -122,6 +123,63 @@ def test_full_and_empty():
     assert summary(t) == (1, 0, 1, 0) and t["counts"]["exterior_points"] == 0
     t = TR.topology(empty(2, 3, 4))
     assert summary(t) == (0, 0, 0, 0) and t["counts"]["exterior_points"] == 24 and np.all(t["labels"] == TR.EXTERIOR)
+
+
+# ---- the hand-built cases of the GPU tests (tests/topology_cases.py): their literals against the restatement ---------------------
+def test_border_case_generator_counts():
+    assert len(TC.OFFSETS) == 26 and len(TC.BORDER_CASES) == 124 == 6 * 2 + 12 * 4 + 8 * 8
+    assert len(set(TC.BORDER_CASES)) == 124
+    for d, s in TC.BORDER_CASES:
+        a, b = TC.pair(d, s)
+        assert tuple(y - x for x, y in zip(a, b)) == d
+        for x in range(3):
+            assert (a[x] // 8 != b[x] // 8) == (x in s)                         # a border exactly on the axes in s
+            assert x in s or d[x] == 0 or 1 <= min(a[x], b[x]) % 8 and max(a[x], b[x]) % 8 <= 6   # well inside one brick otherwise
+
+
+@pytest.mark.parametrize("inside", [True, False])
+@pytest.mark.parametrize("d", TC.OFFSETS)
+def test_border_pairs_literals_against_the_restatement(d, inside):
+    pairs = TC.packed_pairs(d)
+    assert len(pairs) == 2 ** TC.faces_of(d)
+    occ = TC.occupancy_of(pairs, TC.PACKED_SHAPE, inside)
+    t = TR.topology(occ)
+    TC.check_expected(t["counts"], t["cavity_rows"], TC.expected_of_pairs(d, pairs, TC.PACKED_SHAPE, inside))
+    if not inside:
+        assert t["counts"]["exterior_points"] == 0 and t["counts"]["cavities"] == len(pairs)
+    # thin last bricks: i = 16 is the lattice's border there
+    pairs = [TC.thin_pair(d)]
+    occ = TC.occupancy_of(pairs, TC.THIN_SHAPE, inside)
+    t = TR.topology(occ)
+    want = TC.expected_of_pairs(d, pairs, TC.THIN_SHAPE, inside)
+    TC.check_expected(t["counts"], t["cavity_rows"], want)
+    if not inside:
+        assert (want["cavities"], want["exterior_points"]) == ((0, 2) if d[0] != 0 else (1, 0))
+
+
+@pytest.mark.parametrize("way", sorted(TC.SNAKE_WAYS))
+def test_snake_literals_against_the_restatement(way):
+    for mirror in TC.ORIENTATIONS:
+        occ = TC.snake_case(way, mirror)
+        t = TR.topology(occ)
+        assert summary(t) == TC.SNAKE_WAYS[way], mirror
+        if way == "complement":
+            assert t["cavity_rows"][0][0] == TC.SNAKE_POINTS == 143
+        else:
+            assert t["counts"]["points"] == TC.SNAKE_POINTS and t["counts"]["edges"] == TC.SNAKE_POINTS - 1   # a path
+
+
+def test_checkerboard_frames_and_rods_literals_against_the_restatement():
+    t = TR.topology(TC.checkerboard(TC.SMALL))
+    assert summary(t) == (5610, 0, 5610, 0) and t["counts"]["exterior_points"] == 5610
+    t = TR.topology(TC.checkerboard(TC.SMALL, 1))
+    assert summary(t) == (5610, 0, 5610, 0) and t["counts"]["exterior_points"] == 5610
+    for axis, want in TC.FRAMED.items():
+        assert summary(TR.topology(TC.framed_planes(axis))) == want, axis
+    t = TR.topology(TC.rods())
+    assert summary(t) == (90, 0, 90, 0) and all(r[0] == 33 for r in t["body_rows"])
+    t = TR.topology(TC.buried_voids(8))                                       # the small sibling of the 64^3 case
+    assert summary(t)[:2] == (1, 27) and all(r[0] == 1 for r in t["cavity_rows"])
 
 
 # ---- random occupancies ---------------------------------------------------------------------------------------------------------
