@@ -275,6 +275,39 @@ pub const RM_SUP_STAT_EVALUATIONS: c_int = 3;
 pub const RM_SUP_STAT_SCRATCH_BYTES: c_int = 4;
 pub const RM_SUP_STATS: c_int = 5;
 
+// Layer regions and islands (rm_islands_solid / rm_islands_occupancy / rm_read_islands).
+// enum rm_islcount: indices into the counts of an islands call; RM_ISL_COUNTS is their number
+pub const RM_ISL_POINTS: c_int = 0;
+pub const RM_ISL_PLATE: c_int = 1;
+pub const RM_ISL_REGIONS: c_int = 2;
+pub const RM_ISL_BASE_REGIONS: c_int = 3;
+pub const RM_ISL_ISLANDS: c_int = 4;
+pub const RM_ISL_ISLAND_POINTS: c_int = 5;
+pub const RM_ISL_MERGES: c_int = 6;
+pub const RM_ISL_MAX_LAYER_REGIONS: c_int = 7;
+pub const RM_ISL_COUNTS: c_int = 8;
+// enum rm_islstat: indices into the statistics of an islands call; RM_ISL_STATS is their number
+pub const RM_ISL_STAT_BRICKS: c_int = 0;
+pub const RM_ISL_STAT_BRICKS_KEPT: c_int = 1;
+pub const RM_ISL_STAT_BRICKS_INSIDE: c_int = 2;
+pub const RM_ISL_STAT_EVALUATIONS: c_int = 3;
+pub const RM_ISL_STAT_SCRATCH_BYTES: c_int = 4;
+pub const RM_ISL_STATS: c_int = 5;
+// enum rm_islrow: the words of a row of the region table; RM_ISL_ROW_WORDS is their number
+pub const RM_ISL_ROW_LAYER: c_int = 0;
+pub const RM_ISL_ROW_FIRST: c_int = 1;
+pub const RM_ISL_ROW_POINTS: c_int = 2;
+pub const RM_ISL_ROW_SUPPORTED: c_int = 3;
+pub const RM_ISL_ROW_SUM_A: c_int = 4;
+pub const RM_ISL_ROW_SUM_B: c_int = 5;
+pub const RM_ISL_ROW_MIN_A: c_int = 6;
+pub const RM_ISL_ROW_MAX_A: c_int = 7;
+pub const RM_ISL_ROW_MIN_B: c_int = 8;
+pub const RM_ISL_ROW_MAX_B: c_int = 9;
+pub const RM_ISL_ROW_BELOW_MIN: c_int = 10;
+pub const RM_ISL_ROW_BELOW_MAX: c_int = 11;
+pub const RM_ISL_ROW_WORDS: c_int = 12;
+
 // Slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table).
 // enum rm_slicecount: indices into the counts of rm_slice_contours; RM_SLICE_COUNTS is their number
 pub const RM_SLICE_POINTS: c_int = 0;
@@ -388,6 +421,13 @@ extern "C" {
                                 stream: *mut c_void, up: u32, r2: u32, plate: u32, out_counts: *mut u64, n_counts: u32,
                                 out_stats: *mut u64, n_stats: u32) -> c_int;
     pub fn rm_read_support(ctx: *mut rm_ctx, out_mask: *mut c_void, out_profile: *mut u32, is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_islands_solid(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, level: f32, up: u32,
+                            r2: u32, plate: u32, out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_islands_occupancy(ctx: *mut rm_ctx, nx: u32, ny: u32, nz: u32, occupancy: *const c_void, is_device: c_int,
+                                stream: *mut c_void, up: u32, r2: u32, plate: u32, out_counts: *mut u64, n_counts: u32,
+                                out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_read_islands(ctx: *mut rm_ctx, out_rows: *mut u32, row_capacity: u64, out_labels: *mut u32, out_mask: *mut c_void,
+                           out_profile: *mut u32, is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_slice_contours(ctx: *mut rm_ctx, axis: u32, origin_uv: *const f32, step_uv: *const f32, nu: u32, nv: u32,
                              heights: *const f32, n_layers: u32, level: f32, flags: u32, out_counts: *mut u64,
                              n_counts: u32) -> c_int;
@@ -509,6 +549,8 @@ pub struct RayMarchingResources {
     distance: Cell<Option<(u64, bool)>>,
     /// (lattice points, layers along the build direction) of the last successful support call: what `read_support` writes
     support: Cell<Option<(u64, u32)>>,
+    /// (lattice points, layers along the build direction, regions) of the last successful islands call: what `read_islands` writes
+    islands: Cell<Option<(u64, u32, u64)>>,
 }
 
 unsafe impl Send for RayMarchingResources {} // a context may move between threads; it is not Sync
@@ -523,7 +565,7 @@ impl RayMarchingResources {
             return Err(RmError { status: rc, message: msg.to_string_lossy().into_owned() });
         }
         Ok(Self { ctx, mesh: Cell::new(None), slices: Cell::new(None), topology: Cell::new(None), distance: Cell::new(None),
-                  support: Cell::new(None) })
+                  support: Cell::new(None), islands: Cell::new(None) })
     }
 
     fn check(&self, rc: c_int) -> Result<(), RmError> {
@@ -920,6 +962,79 @@ impl RayMarchingResources {
         let pm = out_mask.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr() as *mut c_void);
         let pp = out_profile.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
         self.check(unsafe { rm_read_support(self.ctx, pm, pp, 0, std::ptr::null_mut()) })
+    }
+
+    /// Layer regions and islands of the solid `map_scene < level` on the lattice (`rm_islands_solid`; lattice, `up`, `r2` and
+    /// `plate` as `support_solid` takes them): fills `out_counts` (at least `RM_ISL_COUNTS` entries, indexed by `RM_ISL_*`) and
+    /// `out_stats` (at least `RM_ISL_STATS`, indexed by `RM_ISL_STAT_*`).  Exact integers: every run gives the same words.
+    /// `read_islands` copies the region table, the labels, the mask and the profile out.  Leaves the context's mesh, slices,
+    /// labelling, distance volume and support result alone.
+    pub fn islands_solid(&self, origin: [f32; 3], step: [f32; 3], nx: u32, ny: u32, nz: u32, level: f32, up: c_int, r2: u32,
+                         plate: Option<u32>, out_counts: &mut [u64], out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(out_counts.len() >= RM_ISL_COUNTS as usize, "islands_solid: out_counts is shorter than RM_ISL_COUNTS entries");
+        assert!(out_stats.len() >= RM_ISL_STATS as usize, "islands_solid: out_stats is shorter than RM_ISL_STATS entries");
+        assert!(plate != Some(RM_SUPPORT_PLATE_AUTO), "islands_solid: None is the automatic plate");
+        self.islands.set(None);  // a failed call may have released the previous result
+        self.check(unsafe {
+            rm_islands_solid(self.ctx, origin.as_ptr(), step.as_ptr(), nx, ny, nz, level, up as u32, r2, plate.unwrap_or(RM_SUPPORT_PLATE_AUTO),
+                             out_counts.as_mut_ptr(), RM_ISL_COUNTS as u32, out_stats.as_mut_ptr(), RM_ISL_STATS as u32)
+        })?;
+        self.islands.set(Some((nx as u64 * ny as u64 * nz as u64, [nx, ny, nz][(up >> 1) as usize], out_counts[RM_ISL_REGIONS as usize])));
+        Ok(())
+    }
+
+    /// `islands_solid` of a caller's occupancy in host memory (`rm_islands_occupancy`): one byte per point, x fastest, nonzero =
+    /// inside.
+    pub fn islands_occupancy(&self, nx: u32, ny: u32, nz: u32, occupancy: &[u8], up: c_int, r2: u32, plate: Option<u32>,
+                             out_counts: &mut [u64], out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(occupancy.len() as u64 >= nx as u64 * ny as u64 * nz as u64, "islands_occupancy: occupancy is shorter than nx * ny * nz bytes");
+        assert!(out_counts.len() >= RM_ISL_COUNTS as usize, "islands_occupancy: out_counts is shorter than RM_ISL_COUNTS entries");
+        assert!(out_stats.len() >= RM_ISL_STATS as usize, "islands_occupancy: out_stats is shorter than RM_ISL_STATS entries");
+        assert!(plate != Some(RM_SUPPORT_PLATE_AUTO), "islands_occupancy: None is the automatic plate");
+        self.islands.set(None);  // a failed call may have released the previous result
+        self.check(unsafe {
+            rm_islands_occupancy(self.ctx, nx, ny, nz, occupancy.as_ptr() as *const c_void, 0, std::ptr::null_mut(), up as u32, r2,
+                                 plate.unwrap_or(RM_SUPPORT_PLATE_AUTO), out_counts.as_mut_ptr(), RM_ISL_COUNTS as u32,
+                                 out_stats.as_mut_ptr(), RM_ISL_STATS as u32)
+        })?;
+        self.islands.set(Some((nx as u64 * ny as u64 * nz as u64, [nx, ny, nz][(up >> 1) as usize], out_counts[RM_ISL_REGIONS as usize])));
+        Ok(())
+    }
+
+    /// The result of the last islands call: the region table (`RM_ISL_ROW_WORDS` words per region, row r - 1 for region r), the
+    /// label volume (one word per lattice point), the mask (one byte per point: 0 outside, 1 inside, 2 inside and in an island)
+    /// and the profile (four words per layer along the build direction, height 0 first: inside points, regions, islands, island
+    /// points).  `None` skips that output.  `RM_ERR_ARG` before any islands call.
+    pub fn read_islands(&self, out_rows: Option<&mut [u32]>, out_labels: Option<&mut [u32]>, out_mask: Option<&mut [u8]>,
+                        out_profile: Option<&mut [u32]>) -> Result<(), RmError> {
+        let (n, layers, regions) = match self.islands.get() {
+            Some((n, l, r)) => (n as usize, l as usize, r as usize),
+            None => return Err(RmError { status: RM_ERR_ARG, message: "read_islands: no islands call has been made".to_string() }),
+        };
+        let words = RM_ISL_ROW_WORDS as usize;
+        assert!(out_rows.as_ref().map_or(true, |s| s.len() >= words * regions), "read_islands: out_rows is shorter than {} rows", regions);
+        assert!(out_labels.as_ref().map_or(true, |s| s.len() >= n), "read_islands: out_labels is shorter than {} points", n);
+        assert!(out_mask.as_ref().map_or(true, |s| s.len() >= n), "read_islands: out_mask is shorter than {} points", n);
+        assert!(out_profile.as_ref().map_or(true, |s| s.len() >= 4 * layers), "read_islands: out_profile is shorter than {} words", 4 * layers);
+        let capacity = out_rows.as_ref().map_or(0, |s| (s.len() / words) as u64);
+        let pr = out_rows.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pl = out_labels.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pm = out_mask.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr() as *mut c_void);
+        let pp = out_profile.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        self.check(unsafe { rm_read_islands(self.ctx, pr, capacity, pl, pm, pp, 0, std::ptr::null_mut()) })
+    }
+
+    /// For every region of a region table the number of the island or base region it grows from, following `BELOW_MIN`
+    /// downwards: one pass, because the rows are sorted by layer.
+    pub fn island_roots(rows: &[u32]) -> Vec<u32> {
+        let words = RM_ISL_ROW_WORDS as usize;
+        let mut root = vec![0u32; rows.len() / words + 1];
+        for r in 1..root.len() {
+            let below = rows[(r - 1) * words + RM_ISL_ROW_BELOW_MIN as usize] as usize;
+            root[r] = if below != 0 { root[below] } else { r as u32 };
+        }
+        root.remove(0);
+        root
     }
 
     /// The mesh of the last successful `extract_mesh` (of the (vertices, triangles) it returned): positions (three per

@@ -643,6 +643,52 @@ int rm_support_occupancy(rm_ctx* ctx, uint32_t nx, uint32_t ny, uint32_t nz, con
                          uint32_t n_stats);
 int rm_read_support(rm_ctx* ctx, void* out_mask, uint32_t* out_profile, int is_device, void* stream);
 
+/* Layer regions and islands (extension; DESIGN.md section 22 is the contract, to the last bit): for a build direction, the
+ * 4-connected REGIONS of the inside points of every layer at or above the plate, which regions of the layer below each one rests
+ * on, and which are ISLANDS -- regions that start printing in mid air.
+ * Lattice, "inside", `up`, height, layer, `plate` / RM_SUPPORT_PLATE_AUTO -> h0, `r2`, the digital disc, OVERHANG and the limits
+ * are rm_support_solid's.  Neighbours differ by one in exactly one in-layer coordinate; layers below h0 have no regions.  A point
+ * of a region is SUPPORTED iff h == h0 or it is no overhang.  A region R of layer h > h0 LINKS to Q of layer h - 1 iff some p in R
+ * and q in Q have du^2 + dv^2 <= r2.  R is an ISLAND iff h > h0 and it has no supported point (iff it links to nothing), a MERGE
+ * iff it links to at least two regions, a BASE region iff h == h0.  Regions are numbered 1..REGIONS by ascending (h, FIRST), FIRST
+ * the smallest linear index i + nx * (j + ny * k) among the region's points.
+ * out_counts[RM_ISL_*]: POINTS (all inside points, RM_SUP_POINTS), PLATE (the h0 used), REGIONS, BASE_REGIONS, ISLANDS,
+ * ISLAND_POINTS, MERGES, MAX_LAYER_REGIONS (the most regions in one layer).
+ * out_stats[RM_ISL_STAT_*]: as RM_SUP_STAT_* (the first four are 0 for rm_islands_occupancy).
+ * rm_read_islands copies the last result out; any output may be NULL; is_device and stream as for rm_read_support (device arrays
+ * of u32: 4-byte aligned):
+ *   out_rows     REGIONS rows of RM_ISL_ROW_WORDS u32, row r - 1 for region r (row_capacity: the rows out_rows holds;
+ *                RM_ERR_RANGE when it is below REGIONS).  A and B are the two in-layer axes in ascending axis order (up z: x, y).
+ *                LAYER, FIRST, POINTS, SUPPORTED, SUM_A, SUM_B (coordinate sums), MIN_A, MAX_A, MIN_B, MAX_B (bounding box),
+ *                BELOW_MIN, BELOW_MAX (the smallest and largest number of a linked region; 0, 0 without one).
+ *                Island: LAYER > PLATE && BELOW_MIN == 0.  Merge: BELOW_MIN != BELOW_MAX.
+ *   out_labels   one u32 per point, x fastest: the region's number for inside points with h >= h0, else 0
+ *   out_mask     one byte per point: 0 outside, 1 inside, 2 inside and in an island ((mask == 2) is an occupancy for
+ *                rm_label_occupancy)
+ *   out_profile  n_a x 4 u32, height 0 first: per layer its inside points, regions, islands, island points (the last three 0
+ *                below h0)
+ * Every word is a bit, a count, a sum of small integers, a minimum or a maximum: two runs, and any correct implementation, give
+ * identical words.  The calls are synchronous on the context's own stream; the result lives in buffers of its own until the next
+ * islands call or rm_destroy and replaces neither the draw state, the mesh, the slices, the labelling, the distance volume nor the
+ * support result.  Errors (every check precedes the first launch; a failed call leaves the outputs untouched): those of
+ * rm_support_solid / rm_support_occupancy, word for word; RM_ERR_ARG for rm_read_islands before any islands call; RM_ERR_DEVICE
+ * when device memory runs out (about 14.3 bytes per point, and 48 per region: a checkerboard has half its points as regions). */
+enum rm_islcount { RM_ISL_POINTS = 0, RM_ISL_PLATE = 1, RM_ISL_REGIONS = 2, RM_ISL_BASE_REGIONS = 3, RM_ISL_ISLANDS = 4,
+                   RM_ISL_ISLAND_POINTS = 5, RM_ISL_MERGES = 6, RM_ISL_MAX_LAYER_REGIONS = 7, RM_ISL_COUNTS = 8 };
+enum rm_islstat { RM_ISL_STAT_BRICKS = 0, RM_ISL_STAT_BRICKS_KEPT = 1, RM_ISL_STAT_BRICKS_INSIDE = 2,
+                  RM_ISL_STAT_EVALUATIONS = 3, RM_ISL_STAT_SCRATCH_BYTES = 4, RM_ISL_STATS = 5 };
+enum rm_islrow { RM_ISL_ROW_LAYER = 0, RM_ISL_ROW_FIRST = 1, RM_ISL_ROW_POINTS = 2, RM_ISL_ROW_SUPPORTED = 3, RM_ISL_ROW_SUM_A = 4,
+                 RM_ISL_ROW_SUM_B = 5, RM_ISL_ROW_MIN_A = 6, RM_ISL_ROW_MAX_A = 7, RM_ISL_ROW_MIN_B = 8, RM_ISL_ROW_MAX_B = 9,
+                 RM_ISL_ROW_BELOW_MIN = 10, RM_ISL_ROW_BELOW_MAX = 11, RM_ISL_ROW_WORDS = 12 };
+int rm_islands_solid(rm_ctx* ctx, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                     uint32_t up, uint32_t r2, uint32_t plate, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
+                     uint32_t n_stats);
+int rm_islands_occupancy(rm_ctx* ctx, uint32_t nx, uint32_t ny, uint32_t nz, const void* occupancy, int is_device, void* stream,
+                         uint32_t up, uint32_t r2, uint32_t plate, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
+                         uint32_t n_stats);
+int rm_read_islands(rm_ctx* ctx, uint32_t* out_rows, uint64_t row_capacity, uint32_t* out_labels, void* out_mask,
+                    uint32_t* out_profile, int is_device, void* stream);
+
 /* Slicing (extension; DESIGN.md section 16 is the contract, to the last bit): the closed outlines of the solid d < level in a
  * stack of planes, as ordered polylines -- what a slicer or a section drawing needs, evaluated directly on a 2-D lattice
  * per layer instead of through a triangle mesh.  From the program, limits and material table as they are at the call.

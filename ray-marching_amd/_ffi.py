@@ -92,6 +92,17 @@ SUP_COUNT_NAMES = ("points", "plate", "base", "overhang", "support_on_plate", "s
 SUP_STAT_NAMES = ("bricks", "bricks_kept", "bricks_inside", "evaluations", "scratch_bytes")
 RM_SUPPORT_PLATE_AUTO = 0xFFFFFFFF
 SUP_MASK_OUTSIDE, SUP_MASK_INSIDE, SUP_MASK_OVERHANG, SUP_MASK_ON_PLATE, SUP_MASK_ON_PART = range(5)
+# layer regions and islands (rm_islands_solid / rm_islands_occupancy / rm_read_islands): enum rm_islcount, enum rm_islstat, enum
+# rm_islrow; the region table as a structured array
+(RM_ISL_POINTS, RM_ISL_PLATE, RM_ISL_REGIONS, RM_ISL_BASE_REGIONS, RM_ISL_ISLANDS, RM_ISL_ISLAND_POINTS, RM_ISL_MERGES,
+ RM_ISL_MAX_LAYER_REGIONS, RM_ISL_COUNTS) = range(9)
+ISL_COUNT_NAMES = ("points", "plate", "regions", "base_regions", "islands", "island_points", "merges", "max_layer_regions")
+(RM_ISL_STAT_BRICKS, RM_ISL_STAT_BRICKS_KEPT, RM_ISL_STAT_BRICKS_INSIDE, RM_ISL_STAT_EVALUATIONS, RM_ISL_STAT_SCRATCH_BYTES,
+ RM_ISL_STATS) = range(6)
+ISL_STAT_NAMES = SUP_STAT_NAMES
+ISL_ROW_NAMES = ("layer", "first", "points", "supported", "sum_a", "sum_b", "min_a", "max_a", "min_b", "max_b", "below_min", "below_max")
+RM_ISL_ROW_WORDS = len(ISL_ROW_NAMES)
+ISL_MASK_OUTSIDE, ISL_MASK_INSIDE, ISL_MASK_ISLAND = range(3)
 # slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table): enum rm_slicecount, the indices of out_counts
 RM_SLICE_POINTS, RM_SLICE_CONTOURS, RM_SLICE_COUNTS = 0, 1, 2
 # lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit): enum rm_light, the parameter names in index order
@@ -242,6 +253,12 @@ def hip_lib():
         L.rm_support_occupancy.restype = C.c_int
         L.rm_read_support.argtypes = [vp, vp, vp, C.c_int, vp]
         L.rm_read_support.restype = C.c_int
+        L.rm_islands_solid.argtypes = L.rm_support_solid.argtypes
+        L.rm_islands_solid.restype = C.c_int
+        L.rm_islands_occupancy.argtypes = L.rm_support_occupancy.argtypes
+        L.rm_islands_occupancy.restype = C.c_int
+        L.rm_read_islands.argtypes = [vp, vp, u64, vp, vp, vp, C.c_int, vp]
+        L.rm_read_islands.restype = C.c_int
         L.rm_slice_contours.argtypes = [vp, u32, f3, f3, u32, u32, f3, u32, C.c_float, u32, C.POINTER(u64), u32]
         L.rm_slice_contours.restype = C.c_int
         L.rm_read_slices.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]

@@ -33,6 +33,7 @@
 #include "rm_topology.h"
 #include "rm_distance.h"
 #include "rm_support.h"
+#include "rm_islands.h"
 #include "rm_slice.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
@@ -178,6 +179,12 @@ struct rm_ctx {
     DevBuf<char> d_smask, d_sprof;
     bool sup_valid = false;
     uint32_t sup_n = 0, sup_nh = 0;
+    // layer regions and islands (rm_islands.h): the label volume, the mask, the profile and the region table of the last islands
+    // call, in buffers of their own (their scratch is d_mscratch)
+    DevBuf<char> d_ilabels, d_imask, d_iprof, d_irows;
+    bool isl_valid = false;
+    uint32_t isl_n = 0, isl_nh = 0;
+    uint64_t isl_regions = 0;
     // scratch for host-destination draws and batch uniforms
     DevBuf<char> d_out;
     DevBuf<rm_uniforms> d_frames;
@@ -2445,6 +2452,24 @@ int check_support(rm_ctx* c, const char* fn, uint32_t nx, uint32_t ny, uint32_t 
     return RM_OK;
 }
 
+// The planes `ins` and `ov` of an occupancy (rm_support.h pack and overhang); h0w: the automatic plate's word, 0xFF.. before.
+void support_planes(hipStream_t s, const rmk::SupFrame& f, uint32_t r2, uint32_t plate, const uint8_t* occ, unsigned long long* ins,
+                    unsigned long long* ov, uint32_t* h0w) {
+    const bool xup = f.sh == 1u;
+    const uint32_t n_tasks = xup ? f.nv * f.nw * ((f.nh + 63u) / 64u) : sup_plane_words(f);
+    const uint32_t n_waves = xup ? n_tasks : (n_tasks + rmk::kSupWordsPerWave - 1u) / rmk::kSupWordsPerWave;
+    const dim3 task_grid((n_waves + 3u) / 4u);
+    if (xup)
+        hipLaunchKernelGGL(rmk::rm_sup_pack_kernel<true>, task_grid, dim3(256), 0, s, f, n_tasks, plate, occ, ins, h0w);
+    else
+        hipLaunchKernelGGL(rmk::rm_sup_pack_kernel<false>, task_grid, dim3(256), 0, s, f, n_tasks, plate, occ, ins, h0w);
+    uint32_t reach = 0u;
+    while ((reach + 1u) * (reach + 1u) <= r2) reach++;
+    const uint32_t tv = rml::sup_tile_rows(f.nw);
+    hipLaunchKernelGGL(rmk::rm_sup_overhang_kernel, dim3((f.nv + tv - 1u) / tv, f.nh), dim3(256), rml::SupCoverLds(tv, reach, f.nw).bytes, s, f.nv,
+                       f.nw, tv, r2, reach, plate, static_cast<const uint32_t*>(h0w), static_cast<const unsigned long long*>(ins), ov);
+}
+
 // From the occupancy in S.occ on: pack, overhang, columns, count, compose; the profile summed on the host (at most 1024 layers of
 // six words).  counts: RM_SUP_COUNTS words.
 int support_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupFrame& f, const rml::SupportScratch& S, uint32_t r2,
@@ -2464,15 +2489,7 @@ int support_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
     HIP_TRY(c, hipMemsetAsync(h0w, 0xFF, 16, s));
     HIP_TRY(c, hipMemsetAsync(pr, 0, R.bytes, s));
     const uint8_t* occ = S.occ.at(sc);
-    if (xup)
-        hipLaunchKernelGGL(rmk::rm_sup_pack_kernel<true>, task_grid, dim3(256), 0, s, f, n_tasks, plate, occ, ins, h0w);
-    else
-        hipLaunchKernelGGL(rmk::rm_sup_pack_kernel<false>, task_grid, dim3(256), 0, s, f, n_tasks, plate, occ, ins, h0w);
-    uint32_t reach = 0u;
-    while ((reach + 1u) * (reach + 1u) <= r2) reach++;
-    const uint32_t tv = rml::sup_tile_rows(f.nw);
-    hipLaunchKernelGGL(rmk::rm_sup_overhang_kernel, dim3((f.nv + tv - 1u) / tv, f.nh), dim3(256), rml::SupCoverLds(tv, reach, f.nw).bytes, s, f.nv,
-                       f.nw, tv, r2, reach, plate, static_cast<const uint32_t*>(h0w), static_cast<const unsigned long long*>(ins), ov);
+    support_planes(s, f, r2, plate, occ, ins, ov, h0w);
     hipLaunchKernelGGL(rmk::rm_sup_columns_kernel, dim3((ncw + rmk::kSupColumnThreads - 1u) / rmk::kSupColumnThreads), dim3(rmk::kSupColumnThreads), 0, s, ncw, f.nh, plate, static_cast<const uint32_t*>(h0w),
                        static_cast<const unsigned long long*>(ins), static_cast<const unsigned long long*>(ov), sup, plt);
     hipLaunchKernelGGL(rmk::rm_sup_count_kernel, dim3((ncw + 255u) / 256u, f.nh), dim3(256), 0, s, ncw, f.nh, plate, static_cast<const uint32_t*>(h0w),
@@ -2603,6 +2620,206 @@ RM_EXPORT int rm_read_support(rm_ctx* c, void* out_mask, uint32_t* out_profile, 
     if (out_mask) HIP_TRY(c, hipMemcpyAsync(out_mask, c->d_smask.p, c->sup_n, kind, s));
     if (out_profile)
         HIP_TRY(c, hipMemcpyAsync(out_profile, rml::SupportProfile(c->sup_nh).profile.at(c->d_sprof.p), (size_t)c->sup_nh * 16u, kind, s));
+    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+// ---- layer regions and islands (rm_islands.h) ----
+namespace {
+
+static_assert(rmk::kIslRowWords == RM_ISL_ROW_WORDS && rml::kIslRowWords == RM_ISL_ROW_WORDS, "a row of the region table");
+static_assert(rmk::kIslLayer == RM_ISL_ROW_LAYER && rmk::kIslFirst == RM_ISL_ROW_FIRST && rmk::kIslPoints == RM_ISL_ROW_POINTS &&
+                  rmk::kIslSupported == RM_ISL_ROW_SUPPORTED && rmk::kIslSumA == RM_ISL_ROW_SUM_A && rmk::kIslSumB == RM_ISL_ROW_SUM_B &&
+                  rmk::kIslMinA == RM_ISL_ROW_MIN_A && rmk::kIslMaxA == RM_ISL_ROW_MAX_A && rmk::kIslMinB == RM_ISL_ROW_MIN_B &&
+                  rmk::kIslMaxB == RM_ISL_ROW_MAX_B && rmk::kIslBelowMin == RM_ISL_ROW_BELOW_MIN && rmk::kIslBelowMax == RM_ISL_ROW_BELOW_MAX,
+              "the words of a row");
+static_assert(rml::IslLinkLds(rml::kSupMaxReach).bytes + 256u <= rml::kLdsLaunchLimit, "the links tile fits a workgroup");
+
+struct IslandsPlan {
+    rmk::SupFrame f;
+    uint32_t n_words, n_rblocks;
+    IslandsPlan(const TopoGrid& G, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t up)
+        : f(sup_frame(nx, ny, nz, up)), n_words(sup_plane_words(f)), n_rblocks((G.n + 255u) / 256u) {}
+    rml::IslandsScratch scratch(const TopoGrid& G) const { return rml::IslandsScratch(G.n, G.g.nb, G.n_pblocks, n_words, n_rblocks, f.nh); }
+};
+
+// The buffers of an islands call: scratch, labels, mask and profile (the region table follows the count).  The last result is
+// gone from here on.
+int islands_reserve(rm_ctx* c, const TopoGrid& G, const rmk::SupFrame& f, const rml::IslandsScratch& S) {
+    int rc = c->d_mscratch.reserve(c, S.bytes);
+    if (rc != RM_OK) return rc;
+    c->isl_valid = false;
+    if ((rc = c->d_ilabels.reserve(c, (size_t)G.n * 4u, "region labels")) != RM_OK) return rc;
+    if ((rc = c->d_imask.reserve(c, G.n, "island mask")) != RM_OK) return rc;
+    return c->d_iprof.reserve(c, (size_t)f.nh * 16u, "region profile");
+}
+
+// From the occupancy in S.occ on (rm_islands.h): pack, overhang, local, border, roots, scan; the table; rank, spread, rows, links,
+// finish, compose; the profile summed on the host (at most 1024 layers of four words).  counts: RM_ISL_COUNTS words.
+int islands_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const IslandsPlan& P, const rml::IslandsScratch& S, uint32_t up, uint32_t r2,
+                    uint32_t plate, uint64_t* counts) {
+    const rmk::SupFrame& f = P.f;
+    char* sc = c->d_mscratch.p;
+    unsigned long long *ins = S.ins.at(sc), *ov = S.ov.at(sc), *rsums = S.rsums.at(sc), *rtot = S.rtot.at(sc);
+    uint32_t *h0w = S.plate.at(sc), *parent = S.parent.at(sc), *lab = S.lab.at(sc), *lbase = S.lbase.at(sc), *totals = S.totals.at(sc);
+    uint32_t* prof = c->d_iprof.as<uint32_t>();
+    const auto cins = static_cast<const unsigned long long*>(ins);
+    const auto cov = static_cast<const unsigned long long*>(ov);
+    const auto ch0 = static_cast<const uint32_t*>(h0w);
+    HIP_TRY(c, hipMemsetAsync(h0w, 0xFF, 16, s));
+    HIP_TRY(c, hipMemsetAsync(totals, 0, 16, s));
+    HIP_TRY(c, hipMemsetAsync(prof, 0, (size_t)f.nh * 16u, s));
+    support_planes(s, f, r2, plate, S.occ.at(sc), ins, ov, h0w);
+    uint32_t reach = 0u;
+    while ((reach + 1u) * (reach + 1u) <= r2) reach++;
+    const uint32_t ncw = f.nv * f.nw;
+    hipLaunchKernelGGL(rmk::rm_isl_local_kernel, dim3(f.nw, (f.nv + rml::kIslTile - 1u) / rml::kIslTile, f.nh), dim3(64), rml::IslTileLds().bytes, s,
+                       f, plate, ch0, cins, parent);
+    hipLaunchKernelGGL(rmk::rm_isl_border_kernel, dim3((P.n_words + 255u) / 256u), dim3(256), 0, s, f, P.n_words, G.n, plate, ch0, cins, parent);
+    hipLaunchKernelGGL(rmk::rm_isl_roots_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, G.n, plate, ch0, cins, parent, rsums);
+    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, rsums, P.n_rblocks, rtot);
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long tot[2] = {0ull, 0ull};
+    HIP_TRY(c, hipMemcpyAsync(tot, rtot, sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const uint64_t R = tot[0];  // (<= 2^27: no two neighbours are both roots)
+    const rml::IslandsRows T(R);
+    uint32_t* rows = nullptr;
+    if (R != 0u) {
+        if (int rc = c->d_irows.reserve(c, T.bytes, "region table")) return rc;
+        rows = T.rows.at(c->d_irows.p);
+        hipLaunchKernelGGL(rmk::rm_isl_rows_init_kernel, dim3((uint32_t)((R * rmk::kIslRowWords + 255u) / 256u)), dim3(256), 0, s,
+                           (uint32_t)(R * rmk::kIslRowWords), rows);
+    }
+    const auto cpar = static_cast<const uint32_t*>(parent);
+    const auto clab = static_cast<const uint32_t*>(lab);
+    hipLaunchKernelGGL(rmk::rm_isl_rank_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, G.n, plate, ch0, cins, cpar,
+                       static_cast<const unsigned long long*>(rsums), lab, rows, lbase);
+    hipLaunchKernelGGL(rmk::rm_isl_spread_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, G.n, plate, ch0, cins, cpar, lab);
+    hipLaunchKernelGGL(rmk::rm_isl_rows_kernel, dim3((ncw + 255u) / 256u, f.nh), dim3(256), 0, s, f, plate, ch0, cins, cov, clab, rows, prof);
+    if (R != 0u)
+        hipLaunchKernelGGL(rmk::rm_isl_links_kernel, dim3(f.nw, (f.nv + rml::kIslLinkRows - 1u) / rml::kIslLinkRows, f.nh), dim3(256),
+                           rml::IslLinkLds(reach).bytes, s, f, r2, reach, plate, ch0, cins, cov, clab, rows);
+    hipLaunchKernelGGL(rmk::rm_isl_finish_kernel, dim3((uint32_t)((std::max<uint64_t>(R, f.nh) + 255u) / 256u)), dim3(256), 0, s, (uint32_t)R, f.nh,
+                       plate, ch0, static_cast<const uint32_t*>(lbase), rows, prof, totals);
+    hipLaunchKernelGGL(rmk::rm_isl_compose_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, up >> 1, G.g.nx, G.g.ny, G.n, plate, ch0, cins, clab,
+                       static_cast<const uint32_t*>(rows), c->d_ilabels.as<uint32_t>(), reinterpret_cast<uint8_t*>(c->d_imask.p));
+    HIP_TRY(c, hipGetLastError());
+    std::vector<uint32_t> layers((size_t)f.nh * 4u);
+    uint32_t h0 = 0u, merges = 0u;
+    HIP_TRY(c, hipMemcpyAsync(layers.data(), prof, (size_t)f.nh * 16u, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&h0, h0w, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&merges, totals, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    h0 = plate != RM_SUPPORT_PLATE_AUTO ? plate : h0 == RM_SUPPORT_PLATE_AUTO ? 0u : h0;
+    for (int k = 0; k < RM_ISL_COUNTS; k++) counts[k] = 0u;
+    for (uint32_t h = 0; h < f.nh; h++) {
+        counts[RM_ISL_POINTS] += layers[4u * h];
+        counts[RM_ISL_ISLANDS] += layers[4u * h + 2u];
+        counts[RM_ISL_ISLAND_POINTS] += layers[4u * h + 3u];
+        counts[RM_ISL_MAX_LAYER_REGIONS] = std::max<uint64_t>(counts[RM_ISL_MAX_LAYER_REGIONS], layers[4u * h + 1u]);
+    }
+    counts[RM_ISL_PLATE] = h0;
+    counts[RM_ISL_REGIONS] = R;
+    counts[RM_ISL_BASE_REGIONS] = layers[4u * h0 + 1u];
+    counts[RM_ISL_MERGES] = merges;
+    c->isl_valid = true;
+    c->isl_n = G.n;
+    c->isl_nh = f.nh;
+    c->isl_regions = R;
+    return RM_OK;
+}
+
+}  // namespace
+
+RM_EXPORT int rm_islands_solid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                               uint32_t up, uint32_t r2, uint32_t plate, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
+                               uint32_t n_stats) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_counts || !out_stats) return fail(c, RM_ERR_NULL, "rm_islands_solid: out_counts or out_stats is NULL");
+    if (n_counts < (uint32_t)RM_ISL_COUNTS) return fail(c, RM_ERR_ARG, "rm_islands_solid: n_counts %u < RM_ISL_COUNTS", n_counts);
+    if (n_stats < (uint32_t)RM_ISL_STATS) return fail(c, RM_ERR_ARG, "rm_islands_solid: n_stats %u < RM_ISL_STATS", n_stats);
+    if (int rc = check_lattice(c, "rm_islands_solid", origin, step)) return rc;
+    if (int rc = check_iso(c, "rm_islands_solid", level, 0u)) return rc;
+    if (int rc = check_support(c, "rm_islands_solid", nx, ny, nz, up, r2, plate)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    SolidOccupancy O;
+    int rc = solid_occupancy_begin(c, "rm_islands_solid", s, origin, step, nx, ny, nz, &O);  // after a device read of the last result, too
+    if (rc != RM_OK) return rc;
+    const TopoGrid G = topo_grid(origin, step, nx, ny, nz);
+    const IslandsPlan P(G, nx, ny, nz, up);
+    const rml::IslandsScratch S = P.scratch(G);
+    if ((rc = islands_reserve(c, G, P.f, S)) != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    unsigned long long* evals = S.evals.at(sc);
+    if ((rc = solid_occupancy_fill(c, s, O, G, level, S.cls.at(sc), S.psums.at(sc), S.ptot.at(sc), S.occ.at(sc), evals)) != RM_OK) return rc;
+    uint64_t counts[RM_ISL_COUNTS];
+    if ((rc = islands_lattice(c, s, G, P, S, up, r2, plate, counts)) != RM_OK) return rc;
+    unsigned long long tot[2] = {0ull, 0ull}, ev = 0ull;
+    HIP_TRY(c, hipMemcpyAsync(tot, S.ptot.at(sc), sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    for (int k = 0; k < RM_ISL_COUNTS; k++) out_counts[k] = counts[k];
+    out_stats[RM_ISL_STAT_BRICKS] = G.g.nb;
+    out_stats[RM_ISL_STAT_BRICKS_KEPT] = tot[0];
+    out_stats[RM_ISL_STAT_BRICKS_INSIDE] = tot[1];
+    out_stats[RM_ISL_STAT_EVALUATIONS] = G.g.nb + ev;
+    out_stats[RM_ISL_STAT_SCRATCH_BYTES] = S.bytes;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_islands_occupancy(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz, const void* occupancy, int is_device, void* stream,
+                                   uint32_t up, uint32_t r2, uint32_t plate, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
+                                   uint32_t n_stats) {
+    if (!c) return RM_ERR_NULL;
+    if (!occupancy || !out_counts || !out_stats)
+        return fail(c, RM_ERR_NULL, "rm_islands_occupancy: occupancy, out_counts or out_stats is NULL");
+    if (n_counts < (uint32_t)RM_ISL_COUNTS) return fail(c, RM_ERR_ARG, "rm_islands_occupancy: n_counts %u < RM_ISL_COUNTS", n_counts);
+    if (n_stats < (uint32_t)RM_ISL_STATS) return fail(c, RM_ERR_ARG, "rm_islands_occupancy: n_stats %u < RM_ISL_STATS", n_stats);
+    if (int rc = check_support(c, "rm_islands_occupancy", nx, ny, nz, up, r2, plate)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    order_with_previous(c, s);  // after a device read of the last result, too
+    const float zero[3] = {0.0f, 0.0f, 0.0f}, one[3] = {1.0f, 1.0f, 1.0f};
+    const TopoGrid G = topo_grid(zero, one, nx, ny, nz);
+    const IslandsPlan P(G, nx, ny, nz, up);
+    const rml::IslandsScratch S = P.scratch(G);
+    int rc = islands_reserve(c, G, P.f, S);
+    if (rc != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    if (is_device) {
+        // the caller's array is ready when the work queued on its stream is done; the call is synchronous anyway
+        const hipStream_t su = user_stream(c, stream);
+        if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
+    }
+    HIP_TRY(c, hipMemcpyAsync(S.occ.at(sc), occupancy, G.n, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    uint64_t counts[RM_ISL_COUNTS];
+    if ((rc = islands_lattice(c, s, G, P, S, up, r2, plate, counts)) != RM_OK) return rc;
+    for (int k = 0; k < RM_ISL_COUNTS; k++) out_counts[k] = counts[k];
+    for (int k = 0; k < RM_ISL_STATS; k++) out_stats[k] = 0u;
+    out_stats[RM_ISL_STAT_SCRATCH_BYTES] = S.bytes;
+    return RM_OK;
+}
+
+RM_EXPORT int rm_read_islands(rm_ctx* c, uint32_t* out_rows, uint64_t row_capacity, uint32_t* out_labels, void* out_mask,
+                              uint32_t* out_profile, int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!c->isl_valid) return fail(c, RM_ERR_ARG, "rm_read_islands: no islands call has been made");
+    if (out_rows && row_capacity < c->isl_regions)
+        return fail(c, RM_ERR_RANGE, "rm_read_islands: row_capacity %llu < %llu regions", (unsigned long long)row_capacity,
+                    (unsigned long long)c->isl_regions);
+    if (is_device && (misaligned(out_rows, 4) || misaligned(out_labels, 4) || misaligned(out_profile, 4)))
+        return fail(c, RM_ERR_ARG, "rm_read_islands: device out_rows, out_labels and out_profile need 4-byte alignment");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = dest_stream(c, is_device, stream);
+    order_with_previous(c, s);  // (the next islands call waits for this stream in turn)
+    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const rml::IslandsRows T(c->isl_regions);
+    if (out_rows && T.rows.bytes) HIP_TRY(c, hipMemcpyAsync(out_rows, T.rows.at(c->d_irows.p), T.rows.bytes, kind, s));
+    if (out_labels) HIP_TRY(c, hipMemcpyAsync(out_labels, c->d_ilabels.p, (size_t)c->isl_n * 4u, kind, s));
+    if (out_mask) HIP_TRY(c, hipMemcpyAsync(out_mask, c->d_imask.p, c->isl_n, kind, s));
+    if (out_profile) HIP_TRY(c, hipMemcpyAsync(out_profile, c->d_iprof.p, (size_t)c->isl_nh * 16u, kind, s));
     if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
     return RM_OK;
 }

@@ -182,6 +182,36 @@ struct SupportProfile {
     explicit SupportProfile(uint32_t nh) : profile(a.take<uint32_t>((size_t)nh * 4u)), extra(a.take<uint32_t>((size_t)nh * 2u)), bytes(a.total) {}
 };
 
+// rm_islands_solid / rm_islands_occupancy, for a lattice of n points in nb bricks, nh layers, bit planes of n_words u64 words and
+// n_rblocks blocks of 256 points for the numbering: the occupancy, the brick classes, the probe's sums, totals and evaluation
+// count and the planes `ins` and `ov` as SupportScratch has them; per point its parent and its region number in the canonical
+// frame (4 B each); the numbering's block sums and total; per layer the regions before it (nh + 1 words); the automatic plate's
+// height and the merge count.  Labels, mask, profile and the region table are the result and lie in buffers of their own.
+struct IslandsScratch {
+    Carver a;
+    Region<uint8_t> occ, cls;
+    Region<unsigned long long> psums, ptot, evals, ins, ov;
+    Region<uint32_t> parent, lab;
+    Region<unsigned long long> rsums, rtot;
+    Region<uint32_t> lbase, plate, totals;
+    size_t bytes;
+    IslandsScratch(uint32_t n, uint32_t nb, uint32_t n_pblocks, uint32_t n_words, uint32_t n_rblocks, uint32_t nh)
+        : occ(a.take<uint8_t>(n)), cls(a.take<uint8_t>(nb)), psums(a.take<unsigned long long>(n_pblocks)),
+          ptot(a.take<unsigned long long>(2)), evals(a.take<unsigned long long>(2)), ins(a.take<unsigned long long>(n_words)),
+          ov(a.take<unsigned long long>(n_words)), parent(a.take<uint32_t>(n)), lab(a.take<uint32_t>(n)),
+          rsums(a.take<unsigned long long>(n_rblocks)), rtot(a.take<unsigned long long>(2)), lbase(a.take<uint32_t>((size_t)nh + 1u)),
+          plate(a.take<uint32_t>(4)), totals(a.take<uint32_t>(4)), bytes(a.total) {}
+};
+
+// ... and its region table: kIslRowWords u32 per region (RM_ISL_ROW_*), allocated once the regions are counted.
+constexpr uint32_t kIslRowWords = 12u;
+struct IslandsRows {
+    Carver a;
+    Region<uint32_t> rows;
+    size_t bytes;
+    explicit IslandsRows(uint64_t regions) : rows(a.take<uint32_t>(regions * kIslRowWords)), bytes(a.total) {}
+};
+
 // rm_slice_contours' per-layer tables: heights, layer_first, the first vertex of each layer of a batch of `per`, totals.
 // (heights and layer_first lie before anything `per` sizes: rm_read_slices finds layer_first without it.)
 struct SliceLayerTables {

@@ -137,4 +137,23 @@ struct SupCoverLds {
     RM_LDS_FN SupCoverLds(uint32_t tv, uint32_t reach, uint32_t nw) : rows(0u), bytes(rows + (tv + 2u * reach) * nw * 8u) {}
 };
 
+// ---- Layer regions, local labelling (rm_islands.h rm_isl_local_kernel) -------------------------------------------------------
+// One tile is kIslTile rows x 64 bits (one word column) of one layer: the rows' words (8 B each), then one parent per bit, the
+// bit b of row r at word r * 64 + b (only the entries of run starts are used).
+constexpr uint32_t kIslTile = 64u;
+struct IslTileLds {
+    uint32_t words, parent, bytes;
+    RM_LDS_FN IslTileLds() : words(0u), parent(words + kIslTile * 8u), bytes(parent + kIslTile * 64u * 4u) {}
+};
+
+// ---- Layer regions, links (rm_islands.h rm_isl_links_kernel) ------------------------------------------------------------------
+// The labels of the layer below that a tile of kIslLinkRows rows x 64 points can see: kIslLinkRows + 2 reach rows of 64 + 2 reach
+// u32 words, the point (v0 - reach + r, u0 - reach + c) at word r * pitch + c (reach = floor(sqrt(r2)) <= kSupMaxReach).
+constexpr uint32_t kIslLinkRows = 16u;
+struct IslLinkLds {
+    uint32_t labels, pitch, rows, bytes;
+    RM_LDS_FN explicit IslLinkLds(uint32_t reach)
+        : labels(0u), pitch(64u + 2u * reach), rows(kIslLinkRows + 2u * reach), bytes(labels + rows * pitch * 4u) {}
+};
+
 }  // namespace rml

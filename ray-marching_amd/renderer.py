@@ -687,6 +687,48 @@ class RayMarchingResources:
         self._check(self._L.rm_read_support(self._h, C.c_void_p(mask_ptr or None), C.c_void_p(profile_ptr or None), 1,
                                             C.c_void_p(stream) if stream else None))
 
+    # -- layer regions and islands (rm_islands_solid / rm_islands_occupancy / rm_read_islands) -----------------------------------
+    def islands_solid(self, lo, hi, resolution, level=0.0, up="+z", r2=1, plate=None):
+        """Layer regions and islands of the solid map_scene < level inside the box [lo, hi], on the lattice extract_mesh builds
+        from (lo, hi, resolution) (2..1024 points per axis, at most 2^28 in all), for the build direction `up`, the squared reach
+        r2 and the plate's height as support_solid takes them: an Islands."""
+        lo, step, n = self._box_lattice(lo, hi, resolution)
+        return self.islands_solid_grid(lo, step, n, level, up, r2, plate)
+
+    def islands_solid_grid(self, origin, step, shape, level=0.0, up="+z", r2=1, plate=None):
+        """islands_solid on an exact lattice (origin, step, shape as sample_grid takes them)."""
+        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
+        up, r2, plate = _support_args(up, r2, plate)
+        counts = (C.c_uint64 * _ffi.RM_ISL_COUNTS)()
+        stats = (C.c_uint64 * _ffi.RM_ISL_STATS)()
+        self._check(self._L.rm_islands_solid(self._h, fp(o), fp(s), nx, ny, nz, float(level), up, r2, plate, counts, _ffi.RM_ISL_COUNTS,
+                                             stats, _ffi.RM_ISL_STATS))
+        return self._islands(counts, stats, o, s, (nx, ny, nz), up, r2)
+
+    def islands_occupancy(self, occupancy, up="+z", r2=1, plate=None):
+        """rm_islands_occupancy: layer regions and islands of a caller's occupancy, as label_occupancy takes it (indexed [k, j, i],
+        nonzero = inside; numpy, or a torch tensor on this context's GPU).  The Islands' lattice is the unit lattice at the
+        origin."""
+        nx, ny, nz, ptr, is_device, stream, keep = self._occupancy_arg(occupancy)
+        up, r2, plate = _support_args(up, r2, plate)
+        counts = (C.c_uint64 * _ffi.RM_ISL_COUNTS)()
+        stats = (C.c_uint64 * _ffi.RM_ISL_STATS)()
+        self._check(self._L.rm_islands_occupancy(self._h, nx, ny, nz, ptr, is_device, stream, up, r2, plate, counts, _ffi.RM_ISL_COUNTS,
+                                                 stats, _ffi.RM_ISL_STATS))
+        del keep
+        return self._islands(counts, stats, np.zeros(3, dtype=np.float32), np.ones(3, dtype=np.float32), (nx, ny, nz), up, r2)
+
+    def _islands(self, counts, stats, origin, step, shape, up, r2):
+        return Islands(self, {name: int(counts[k]) for k, name in enumerate(_ffi.ISL_COUNT_NAMES)},
+                       {name: int(stats[k]) for k, name in enumerate(_ffi.ISL_STAT_NAMES)}, origin, step, shape, up, r2)
+
+    def read_islands_device(self, rows_ptr=0, row_capacity=0, labels_ptr=0, mask_ptr=0, profile_ptr=0, stream=None):
+        """rm_read_islands of the last region table (row_capacity rows of room), label volume, mask and profile into device memory
+        (integer addresses; 0 = not wanted), asynchronous."""
+        self._check(self._L.rm_read_islands(self._h, C.c_void_p(rows_ptr or None), int(row_capacity), C.c_void_p(labels_ptr or None),
+                                            C.c_void_p(mask_ptr or None), C.c_void_p(profile_ptr or None), 1,
+                                            C.c_void_p(stream) if stream else None))
+
     def _read_mesh(self, V, T, normals, ids, device):
         """rm_read_mesh of the extraction that just returned V vertices and T triangles, as a mesh.Mesh."""
         from . import mesh as _mesh
@@ -1067,6 +1109,96 @@ class Support:
         landings (its foot on the part), times the area of a cell of a layer."""
         st = np.asarray(self.step, dtype=np.float64)
         return (self.counts["runs"] + self.counts["landings"]) * float(np.prod(np.delete(st, self.up >> 1)))
+
+
+ISL_ROW_DTYPE = np.dtype([(name, np.uint32) for name in _ffi.ISL_ROW_NAMES])
+
+
+def island_roots(rows):
+    """For every region (row r - 1 for region r) the number of the island or base region it grows from, following BELOW_MIN
+    downwards: one pass, because the rows are sorted by layer.  int64 (REGIONS,)."""
+    below = np.asarray(rows["below_min"] if getattr(rows, "dtype", None) is not None and rows.dtype.names else
+                       np.asarray(rows)[:, _ffi.ISL_ROW_NAMES.index("below_min")], dtype=np.int64)
+    root = np.zeros(len(below) + 1, dtype=np.int64)
+    for r in range(1, len(below) + 1):
+        root[r] = root[below[r - 1]] if below[r - 1] else r
+    return root[1:]
+
+
+class Islands:
+    """The result of islands_solid / islands_occupancy.  counts and stats: dicts (_ffi.ISL_COUNT_NAMES, _ffi.ISL_STAT_NAMES); up
+    (_ffi.RM_UP_*), r2, and origin, step (float32[3]) and shape of the lattice.  rows(), labels(), mask() and profile() read the
+    context's buffers: they hold while this is the context's last islands call."""
+
+    def __init__(self, resources, counts, stats, origin, step, shape, up, r2):
+        self._res = resources
+        self.counts, self.stats = counts, stats
+        self.origin, self.step, self.shape = origin, step, shape
+        self.up, self.r2 = up, r2
+
+    def __repr__(self):
+        return "Islands(up %s, %d regions, %d islands of %d points, on %s)" % (
+            _ffi.UP_NAMES[self.up], self.counts["regions"], self.counts["islands"], self.counts["island_points"],
+            "x".join(map(str, self.shape)))
+
+    @property
+    def layers(self):
+        """The points along the up axis."""
+        return self.shape[self.up >> 1]
+
+    def _read(self, rows=None, labels=None, mask=None, profile=None):
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        self._res._check(self._res._L.rm_read_islands(self._res._h, ptr(rows), 0 if rows is None else len(rows), ptr(labels), ptr(mask),
+                                                      ptr(profile), 0, None))
+
+    def rows(self):
+        """The region table, a structured array (REGIONS,) of uint32 fields _ffi.ISL_ROW_NAMES; row r - 1 is region r.  a and b
+        are the two in-layer axes in ascending axis order (up z: x and y)."""
+        out = np.zeros(self.counts["regions"], dtype=ISL_ROW_DTYPE)
+        if out.size:
+            self._read(rows=out)
+        return out
+
+    def labels(self):
+        """The label volume, uint32 (nz, ny, nx): the region's number for inside points at or above the plate, 0 elsewhere."""
+        nx, ny, nz = self.shape
+        out = np.empty((nz, ny, nx), dtype=np.uint32)
+        self._read(labels=out)
+        return out
+
+    def mask(self):
+        """The mask, uint8 (nz, ny, nx): 0 outside, 1 inside, 2 inside and in an island (_ffi.ISL_MASK_*)."""
+        nx, ny, nz = self.shape
+        out = np.empty((nz, ny, nx), dtype=np.uint8)
+        self._read(mask=out)
+        return out
+
+    def profile(self):
+        """The profile, uint32 (layers, 4), height 0 first: per layer its inside points, regions, islands and island points."""
+        out = np.empty((self.layers, 4), dtype=np.uint32)
+        self._read(profile=out)
+        return out
+
+    def roots(self, rows=None):
+        """island_roots of the region table."""
+        return island_roots(self.rows() if rows is None else rows)
+
+    def islands(self, rows=None):
+        """Per island a dict: its region number, layer, points, centroid (world x, y, z) and area (world units: points times the
+        area of a cell of a layer)."""
+        rows = self.rows() if rows is None else rows
+        a = self.up >> 1
+        b, c = [ax for ax in range(3) if ax != a]
+        o, st = np.asarray(self.origin, dtype=np.float64), np.asarray(self.step, dtype=np.float64)
+        out = []
+        for r in np.flatnonzero((rows["layer"] > self.counts["plate"]) & (rows["below_min"] == 0)):
+            row = rows[r]
+            idx = np.zeros(3)
+            idx[a] = self.layers - 1 - int(row["layer"]) if self.up & 1 else int(row["layer"])
+            idx[b], idx[c] = row["sum_a"] / row["points"], row["sum_b"] / row["points"]
+            out.append({"region": int(r) + 1, "layer": int(row["layer"]), "points": int(row["points"]),
+                        "centroid": [float(x) for x in o + idx * st], "area": float(row["points"] * st[b] * st[c])})
+        return out
 
 
 MASS_PROP_NAMES = ("volume", "mass", "cx", "cy", "cz", "ixx", "iyy", "izz", "ixy", "iyz", "ixz", "lo_x", "lo_y", "lo_z", "hi_x", "hi_y",
