@@ -1638,6 +1638,43 @@ int sparse_launch(rm_ctx* c, K kernel, uint32_t blocks, size_t shmem, hipStream_
     return RM_OK;
 }
 
+// The lattice of a caller's occupancy: the unit lattice at the origin.
+constexpr float kUnitOrigin[3] = {0.0f, 0.0f, 0.0f}, kUnitStep[3] = {1.0f, 1.0f, 1.0f};
+
+// A lattice in bricks.  nb stays 0: how many bricks a call takes is its own check.
+rmk::SparseGrid sparse_grid(const float* o, const float* st, uint32_t nx, uint32_t ny, uint32_t nz) {
+    return rmk::SparseGrid{o[0], o[1], o[2], st[0], st[1], st[2], nx, ny, nz,
+                           (nx + rmk::kBrick - 1u) / rmk::kBrick, (ny + rmk::kBrick - 1u) / rmk::kBrick, (nz + rmk::kBrick - 1u) / rmk::kBrick, 0u};
+}
+
+// What a call over the bricks of a lattice does after query_begin (which gave shmem): the LDS check of its workgroups (the
+// query's columns behind 4 KiB of their own), the bounds of the program for points up to the lattice's largest coordinate (as
+// the kernels compute it), the lattice in bricks.  result_valid, if given, is cleared once the LDS check has passed: the mesh's
+// buffers change from there on.
+int brick_lattice(rm_ctx* c, const char* fn, size_t shmem, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
+                  bool* result_valid, RmProgramBound* bound, rmk::SparseGrid* g) {
+    if (shmem + 4096u > std::max<size_t>(c->max_lds, 64u * 1024u))
+        return fail(c, RM_ERR_TOO_LARGE, "%s: the program needs %zu bytes of LDS per workgroup", fn, shmem + 4096u);
+    if (result_valid) *result_valid = false;
+    double P = 0.0;
+    const uint32_t dims[3] = {nx, ny, nz};
+    for (int a = 0; a < 3; a++) {
+        const float last = origin[a] + (float)(dims[a] - 1u) * step[a];
+        P = std::fmax(P, std::fmax(std::fabs((double)origin[a]), std::fabs((double)last)));
+    }
+    *g = sparse_grid(origin, step, nx, ny, nz);
+    return rm_program_bound(c->cmd[0], c->cmd.data() + 1, (uint32_t)c->cmd.size() - 1u, P, bound);
+}
+
+// The bricks of rm_extract_mesh_sparse and rm_mass_moments, whose lattices can hold more than a brick table has entries.
+int count_bricks(rm_ctx* c, const char* fn, rmk::SparseGrid* g) {
+    const uint64_t nb64 = (uint64_t)g->bx * g->by * g->bz;
+    if (nb64 >= 0xFFFFFFFFull - 256u)
+        return fail(c, RM_ERR_DEVICE, "%s: %llu bricks: the brick table is limited to 2^32 entries", fn, (unsigned long long)nb64);
+    g->nb = (uint32_t)nb64;
+    return RM_OK;
+}
+
 }  // namespace
 
 RM_EXPORT int rm_sample_grid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
@@ -1747,24 +1784,10 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
     size_t shmem = 0;
     int rc = query_begin(c, s, (flags & RM_MESH_IDS) != 0, false, &Q, &loop, &shmem);  // after a device read of the previous mesh, too
     if (rc != RM_OK) return rc;
-    if (shmem + 4096u > std::max<size_t>(c->max_lds, 64u * 1024u))
-        return fail(c, RM_ERR_TOO_LARGE, "rm_extract_mesh_sparse: the program needs %zu bytes of LDS per workgroup", shmem + 4096u);
-    c->mesh_valid = false;  // its buffers change from here on
-    // the bounds of the program, for points up to the lattice's largest coordinate (as the kernels compute it)
-    double P = 0.0;
-    const uint32_t dims[3] = {nx, ny, nz};
-    for (int a = 0; a < 3; a++) {
-        const float last = origin[a] + (float)(dims[a] - 1u) * step[a];
-        P = std::fmax(P, std::fmax(std::fabs((double)origin[a]), std::fabs((double)last)));
-    }
     RmProgramBound bound;
-    if ((rc = rm_program_bound(c->cmd[0], c->cmd.data() + 1, (uint32_t)c->cmd.size() - 1u, P, &bound)) != RM_OK) return rc;
-    rmk::SparseGrid g{origin[0], origin[1], origin[2], step[0], step[1], step[2], nx, ny, nz,
-                      (nx + rmk::kBrick - 1u) / rmk::kBrick, (ny + rmk::kBrick - 1u) / rmk::kBrick, (nz + rmk::kBrick - 1u) / rmk::kBrick, 0u};
-    const uint64_t nb64 = (uint64_t)g.bx * g.by * g.bz;
-    if (nb64 >= 0xFFFFFFFFull - 256u)
-        return fail(c, RM_ERR_DEVICE, "rm_extract_mesh_sparse: %llu bricks: the brick table is limited to 2^32 entries", (unsigned long long)nb64);
-    g.nb = (uint32_t)nb64;
+    rmk::SparseGrid g;
+    if ((rc = brick_lattice(c, "rm_extract_mesh_sparse", shmem, origin, step, nx, ny, nz, &c->mesh_valid, &bound, &g)) != RM_OK) return rc;
+    if ((rc = count_bricks(c, "rm_extract_mesh_sparse", &g)) != RM_OK) return rc;
     // per brick: 4 B (keep flag, then the kept bricks before it); per 256 bricks a block sum; totals and the evaluation count
     const uint32_t n_entries = g.nb + 1u, n_pblocks = (n_entries + 255u) / 256u;
     const rml::SparseBrickTables B(n_entries, n_pblocks);
@@ -1865,23 +1888,10 @@ RM_EXPORT int rm_mass_moments(rm_ctx* c, const float* origin, const float* step,
     size_t shmem = 0;
     int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);
     if (rc != RM_OK) return rc;
-    if (shmem + 4096u > std::max<size_t>(c->max_lds, 64u * 1024u))
-        return fail(c, RM_ERR_TOO_LARGE, "rm_mass_moments: the program needs %zu bytes of LDS per workgroup", shmem + 4096u);
-    // the bounds of the program, for points up to the lattice's largest coordinate (as the kernels compute it)
-    double P = 0.0;
-    const uint32_t dims[3] = {nx, ny, nz};
-    for (int a = 0; a < 3; a++) {
-        const float last = origin[a] + (float)(dims[a] - 1u) * step[a];
-        P = std::fmax(P, std::fmax(std::fabs((double)origin[a]), std::fabs((double)last)));
-    }
     RmProgramBound bound;
-    if ((rc = rm_program_bound(c->cmd[0], c->cmd.data() + 1, (uint32_t)c->cmd.size() - 1u, P, &bound)) != RM_OK) return rc;
-    rmk::SparseGrid g{origin[0], origin[1], origin[2], step[0], step[1], step[2], nx, ny, nz,
-                      (nx + rmk::kBrick - 1u) / rmk::kBrick, (ny + rmk::kBrick - 1u) / rmk::kBrick, (nz + rmk::kBrick - 1u) / rmk::kBrick, 0u};
-    const uint64_t nb64 = (uint64_t)g.bx * g.by * g.bz;  // (<= 2^27 with 4096 points per axis)
-    if (nb64 >= 0xFFFFFFFFull - 256u)
-        return fail(c, RM_ERR_DEVICE, "rm_mass_moments: %llu bricks: the brick table is limited to 2^32 entries", (unsigned long long)nb64);
-    g.nb = (uint32_t)nb64;
+    rmk::SparseGrid g;
+    if ((rc = brick_lattice(c, "rm_mass_moments", shmem, origin, step, nx, ny, nz, nullptr, &bound, &g)) != RM_OK) return rc;
+    if ((rc = count_bricks(c, "rm_mass_moments", &g)) != RM_OK) return rc;  // (<= 2^27 with 4096 points per axis)
     // the mesh's scratch buffers (neither holds a result): the brick tables, then the kept bricks' rows
     const uint32_t n_entries = g.nb + 1u, n_pblocks = (n_entries + 255u) / 256u;
     const rml::MassBrickTables B(n_entries, n_pblocks);
@@ -1984,52 +1994,142 @@ struct TopoGrid {
     rmk::SparseGrid g;
     uint32_t n, n_pblocks, n_rblocks;
 };
-TopoGrid topo_grid(const float* o, const float* st, uint32_t nx, uint32_t ny, uint32_t nz) {
+TopoGrid topo_grid(const rmk::SparseGrid& g) {
     TopoGrid t;
-    t.g = rmk::SparseGrid{o[0], o[1], o[2], st[0], st[1], st[2], nx, ny, nz,
-                          (nx + rmk::kBrick - 1u) / rmk::kBrick, (ny + rmk::kBrick - 1u) / rmk::kBrick, (nz + rmk::kBrick - 1u) / rmk::kBrick, 0u};
-    t.g.nb = t.g.bx * t.g.by * t.g.bz;  // (<= 2^21 with 1024 points per axis)
-    t.n = nx * ny * nz;                 // (<= 2^28)
+    t.g = g;
+    t.g.nb = g.bx * g.by * g.bz;  // (<= 2^21 with 1024 points per axis)
+    t.n = g.nx * g.ny * g.nz;     // (<= 2^28)
     t.n_pblocks = (t.g.nb + 255u) / 256u;
     t.n_rblocks = (t.n + rmk::kTopoRankBlock - 1u) / rmk::kTopoRankBlock;
     return t;
 }
-bool topo_lattice_ok(uint32_t nx, uint32_t ny, uint32_t nz) {
-    return nx >= 2 && ny >= 2 && nz >= 2 && nx <= kMaxTopoDim && ny <= kMaxTopoDim && nz <= kMaxTopoDim &&
-           (uint64_t)nx * ny * nz <= kMaxTopoPoints;
+int check_topo_lattice(rm_ctx* c, const char* fn, uint32_t nx, uint32_t ny, uint32_t nz) {
+    if (nx >= 2 && ny >= 2 && nz >= 2 && nx <= kMaxTopoDim && ny <= kMaxTopoDim && nz <= kMaxTopoDim && (uint64_t)nx * ny * nz <= kMaxTopoPoints)
+        return RM_OK;
+    return fail(c, RM_ERR_RANGE, "%s: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", fn, nx, ny, nz);
 }
 
-// The occupancy {d < level} of a lattice, as rm_label_solid and rm_distance_solid fill it (rm_topology.h, probe and occupancy):
-// begin: the query's launch state and the program's bounds for points up to the lattice's largest coordinate (as the kernels
-// compute it), every check before the first launch; fill: probe, scan of the block sums (kept low, inside high -> ptot),
-// occupancy, the evaluations of the kept bricks' points in evals[0].
-struct SolidOccupancy {
-    rmk::QueryLaunch Q;
+// ---- the front end of the lattice analyses: labelling, distance, supports, islands, each of a solid and of an occupancy ----
+// The statistics every analysis reports first, and the size of its scratch last.
+enum { kStatBricks = 0, kStatBricksKept = 1, kStatBricksInside = 2, kStatEvaluations = 3 };
+#define RM_LATTICE_STATS_ASSERT(P)                                                                                             \
+    static_assert(P##_STAT_BRICKS == kStatBricks && P##_STAT_BRICKS_KEPT == kStatBricksKept &&                                 \
+                      P##_STAT_BRICKS_INSIDE == kStatBricksInside && P##_STAT_EVALUATIONS == kStatEvaluations &&               \
+                      P##_STAT_SCRATCH_BYTES == P##_STATS - 1,                                                                 \
+                  "lattice_call writes the brick statistics first and the scratch size last")
+RM_LATTICE_STATS_ASSERT(RM_TOPO);
+RM_LATTICE_STATS_ASSERT(RM_DIST);
+RM_LATTICE_STATS_ASSERT(RM_SUP);
+RM_LATTICE_STATS_ASSERT(RM_ISL);
+#undef RM_LATTICE_STATS_ASSERT
+
+// Where the occupancy of a call comes from: the solid {d < level} of the program on the lattice (origin, step), or the caller's
+// bytes on the unit lattice.  A scratch layout S of any analysis has the regions occ, cls, psums, ptot and evals.
+struct OccupancySource {
+    bool solid;
+    const float *origin, *step;
+    float level;
+    const void* bytes;
+    int is_device;
+    void* stream;
+    rmk::QueryLaunch Q;  // begin's, for fill (a solid)
     int loop = 0;
     size_t shmem = 0;
     RmProgramBound bound;
-};
-int solid_occupancy_begin(rm_ctx* c, const char* fn, hipStream_t s, const float* origin, const float* step, uint32_t nx, uint32_t ny,
-                          uint32_t nz, SolidOccupancy* O) {
-    int rc = query_begin(c, s, false, false, &O->Q, &O->loop, &O->shmem);
-    if (rc != RM_OK) return rc;
-    if (O->shmem + 4096u > std::max<size_t>(c->max_lds, 64u * 1024u))
-        return fail(c, RM_ERR_TOO_LARGE, "%s: the program needs %zu bytes of LDS per workgroup", fn, O->shmem + 4096u);
-    double P = 0.0;
-    const uint32_t dims[3] = {nx, ny, nz};
-    for (int a = 0; a < 3; a++) {
-        const float last = origin[a] + (float)(dims[a] - 1u) * step[a];
-        P = std::fmax(P, std::fmax(std::fabs((double)origin[a]), std::fabs((double)last)));
+
+    static OccupancySource of_solid(const float* origin, const float* step, float level) {
+        return OccupancySource{true, origin, step, level, nullptr, 0, nullptr};
     }
-    return rm_program_bound(c->cmd[0], c->cmd.data() + 1, (uint32_t)c->cmd.size() - 1u, P, &O->bound);
-}
-int solid_occupancy_fill(rm_ctx* c, hipStream_t s, const SolidOccupancy& O, const TopoGrid& G, float level, uint8_t* cls,
-                         unsigned long long* psums, unsigned long long* ptot, uint8_t* occ, unsigned long long* evals) {
-    HIP_TRY(c, hipMemsetAsync(evals, 0, 8, s));
-    int rc = sparse_launch(c, topo_probe_kernel(O.loop), G.n_pblocks, O.shmem, s, O.Q, G.g, level, O.bound.L, 2.0 * O.bound.E, cls, psums);
+    static OccupancySource of_bytes(const void* occupancy, int is_device, void* stream) {
+        return OccupancySource{false, kUnitOrigin, kUnitStep, 0.0f, occupancy, is_device, stream};
+    }
+
+    // Orders stream s after the context's earlier work -- a device read of the family's previous result, too -- and gives the
+    // lattice in bricks; a solid: the query's launch state and the program's bounds, every check before the first launch.
+    int begin(rm_ctx* c, const char* fn, hipStream_t s, uint32_t nx, uint32_t ny, uint32_t nz, rmk::SparseGrid* g) {
+        if (!solid) {
+            order_with_previous(c, s);
+            *g = sparse_grid(origin, step, nx, ny, nz);
+            return RM_OK;
+        }
+        int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);
+        if (rc != RM_OK) return rc;
+        return brick_lattice(c, fn, shmem, origin, step, nx, ny, nz, nullptr, &bound, g);
+    }
+
+    // The occupancy into S.occ.  A solid (rm_topology.h): probe, scan of the block sums (kept low, inside high -> ptot),
+    // occupancy, the evaluations of the kept bricks' points in evals[0].
+    template <class S>
+    int fill(rm_ctx* c, hipStream_t s, const TopoGrid& G, const S& L) const {
+        char* sc = c->d_mscratch.p;
+        if (!solid) {
+            if (is_device) {
+                // the caller's array is ready when the work queued on its stream is done; the call is synchronous anyway
+                const hipStream_t su = user_stream(c, stream);
+                if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
+            }
+            HIP_TRY(c, hipMemcpyAsync(L.occ.at(sc), bytes, G.n, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+            return RM_OK;
+        }
+        uint8_t* cls = L.cls.at(sc);
+        unsigned long long *psums = L.psums.at(sc), *evals = L.evals.at(sc);
+        HIP_TRY(c, hipMemsetAsync(evals, 0, 8, s));
+        int rc = sparse_launch(c, topo_probe_kernel(loop), G.n_pblocks, shmem, s, Q, G.g, level, bound.L, 2.0 * bound.E, cls, psums);
+        if (rc != RM_OK) return rc;
+        hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, psums, G.n_pblocks, L.ptot.at(sc));
+        return sparse_launch(c, topo_occupancy_kernel(loop), G.g.nb, shmem, s, Q, G.g, level, static_cast<const uint8_t*>(cls), L.occ.at(sc), evals);
+    }
+
+    // The brick statistics of the fill; those of a caller's occupancy stay 0.
+    template <class S>
+    int brick_stats(rm_ctx* c, hipStream_t s, const TopoGrid& G, const S& L, uint64_t* stats) const {
+        if (!solid) return RM_OK;
+        char* sc = c->d_mscratch.p;
+        unsigned long long tot[2] = {0ull, 0ull}, ev = 0ull;
+        HIP_TRY(c, hipMemcpyAsync(tot, L.ptot.at(sc), sizeof tot, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(&ev, L.evals.at(sc), sizeof ev, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        stats[kStatBricks] = G.g.nb;
+        stats[kStatBricksKept] = tot[0];
+        stats[kStatBricksInside] = tot[1];
+        stats[kStatEvaluations] = G.g.nb + ev;
+        return RM_OK;
+    }
+};
+
+// One call of an analysis A on the occupancy of `src`, on the context's own stream.  A names its outputs (kCounts, kStats and
+// what rm_abi.h calls them) and gives check() of its own arguments, layout() of its scratch, reserve() of its buffers -- which
+// drops the family's previous result once the scratch is reserved, not before -- and run() from the occupancy in the scratch's
+// occ on, which writes the counts and what statistics are the analysis' own.
+template <class A>
+int lattice_call(rm_ctx* c, const char* fn, OccupancySource src, uint32_t nx, uint32_t ny, uint32_t nz, A a, uint64_t* out_counts,
+                 uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
+    if (!c) return RM_ERR_NULL;
+    if ((!src.solid && !src.bytes) || !out_counts || !out_stats)
+        return fail(c, RM_ERR_NULL, "%s: %sout_counts or out_stats is NULL", fn, src.solid ? "" : "occupancy, ");
+    if (n_counts < A::kCounts) return fail(c, RM_ERR_ARG, "%s: n_counts %u < %s", fn, n_counts, A::kCountsName);
+    if (n_stats < A::kStats) return fail(c, RM_ERR_ARG, "%s: n_stats %u < %s", fn, n_stats, A::kStatsName);
+    if (src.solid) {
+        if (int rc = check_lattice(c, fn, src.origin, src.step)) return rc;
+        if (int rc = check_iso(c, fn, src.level, 0u)) return rc;
+    }
+    if (int rc = a.check(c, fn, nx, ny, nz)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    rmk::SparseGrid g;
+    int rc = src.begin(c, fn, s, nx, ny, nz, &g);
     if (rc != RM_OK) return rc;
-    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, psums, G.n_pblocks, ptot);
-    return sparse_launch(c, topo_occupancy_kernel(O.loop), G.g.nb, O.shmem, s, O.Q, G.g, level, static_cast<const uint8_t*>(cls), occ, evals);
+    const TopoGrid G = topo_grid(g);
+    const auto S = a.layout(G);
+    if ((rc = a.reserve(c, G, S)) != RM_OK) return rc;
+    if ((rc = src.fill(c, s, G, S)) != RM_OK) return rc;
+    uint64_t counts[A::kCounts], stats[A::kStats] = {};
+    if ((rc = a.run(c, fn, s, G, S, counts, stats)) != RM_OK) return rc;
+    if ((rc = src.brick_stats(c, s, G, S, stats)) != RM_OK) return rc;
+    stats[A::kStats - 1u] = S.bytes;
+    for (uint32_t k = 0; k < A::kCounts; k++) out_counts[k] = counts[k];
+    for (uint32_t k = 0; k < A::kStats; k++) out_stats[k] = stats[k];
+    return RM_OK;
 }
 
 // From the occupancy in T.occ on: local labelling; merge, flatten and verify until no pair of neighbours has two roots; the
@@ -2117,77 +2217,33 @@ int label_lattice(rm_ctx* c, const char* fn, hipStream_t s, const TopoGrid& G, c
     return RM_OK;
 }
 
+struct LabelAnalysis {
+    static constexpr uint32_t kCounts = RM_TOPO_COUNTS, kStats = RM_TOPO_STATS;
+    static constexpr const char *kCountsName = "RM_TOPO_COUNTS", *kStatsName = "RM_TOPO_STATS";
+    int check(rm_ctx* c, const char* fn, uint32_t nx, uint32_t ny, uint32_t nz) const { return check_topo_lattice(c, fn, nx, ny, nz); }
+    rml::TopoScratch layout(const TopoGrid& G) const { return rml::TopoScratch(G.n, G.g.nb, G.n_pblocks, G.n_rblocks); }
+    int reserve(rm_ctx* c, const TopoGrid&, const rml::TopoScratch& T) const {
+        const int rc = c->d_mscratch.reserve(c, T.bytes);
+        if (rc == RM_OK) c->topo_valid = false;  // its buffers change from here on
+        return rc;
+    }
+    int run(rm_ctx* c, const char* fn, hipStream_t s, const TopoGrid& G, const rml::TopoScratch& T, uint64_t* counts, uint64_t* stats) const {
+        return label_lattice(c, fn, s, G, T, counts, &stats[RM_TOPO_STAT_MERGE_PASSES]);
+    }
+};
+
 }  // namespace
 
 RM_EXPORT int rm_label_solid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
                              uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
-    if (!c) return RM_ERR_NULL;
-    if (!out_counts || !out_stats) return fail(c, RM_ERR_NULL, "rm_label_solid: out_counts or out_stats is NULL");
-    if (n_counts < (uint32_t)RM_TOPO_COUNTS) return fail(c, RM_ERR_ARG, "rm_label_solid: n_counts %u < RM_TOPO_COUNTS", n_counts);
-    if (n_stats < (uint32_t)RM_TOPO_STATS) return fail(c, RM_ERR_ARG, "rm_label_solid: n_stats %u < RM_TOPO_STATS", n_stats);
-    if (int rc = check_lattice(c, "rm_label_solid", origin, step)) return rc;
-    if (int rc = check_iso(c, "rm_label_solid", level, 0u)) return rc;
-    if (!topo_lattice_ok(nx, ny, nz))
-        return fail(c, RM_ERR_RANGE, "rm_label_solid: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", nx, ny, nz);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = c->stream;
-    SolidOccupancy O;
-    int rc = solid_occupancy_begin(c, "rm_label_solid", s, origin, step, nx, ny, nz, &O);  // after a device read of the previous labelling, too
-    if (rc != RM_OK) return rc;
-    const TopoGrid G = topo_grid(origin, step, nx, ny, nz);
-    const rml::TopoScratch T(G.n, G.g.nb, G.n_pblocks, G.n_rblocks);
-    if ((rc = c->d_mscratch.reserve(c, T.bytes)) != RM_OK) return rc;
-    c->topo_valid = false;  // its buffers change from here on
-    char* sc = c->d_mscratch.p;
-    unsigned long long* evals = T.evals.at(sc);
-    if ((rc = solid_occupancy_fill(c, s, O, G, level, T.cls.at(sc), T.psums.at(sc), T.ptot.at(sc), T.occ.at(sc), evals)) != RM_OK) return rc;
-    uint64_t counts[RM_TOPO_COUNTS], passes = 0;
-    if ((rc = label_lattice(c, "rm_label_solid", s, G, T, counts, &passes)) != RM_OK) return rc;
-    unsigned long long tot[2] = {0ull, 0ull}, ev = 0ull;
-    HIP_TRY(c, hipMemcpyAsync(tot, T.ptot.at(sc), sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    for (int k = 0; k < RM_TOPO_COUNTS; k++) out_counts[k] = counts[k];
-    out_stats[RM_TOPO_STAT_BRICKS] = G.g.nb;
-    out_stats[RM_TOPO_STAT_BRICKS_KEPT] = tot[0];
-    out_stats[RM_TOPO_STAT_BRICKS_INSIDE] = tot[1];
-    out_stats[RM_TOPO_STAT_EVALUATIONS] = G.g.nb + ev;
-    out_stats[RM_TOPO_STAT_MERGE_PASSES] = passes;
-    out_stats[RM_TOPO_STAT_SCRATCH_BYTES] = T.bytes;
-    return RM_OK;
+    return lattice_call(c, "rm_label_solid", OccupancySource::of_solid(origin, step, level), nx, ny, nz, LabelAnalysis(), out_counts, n_counts,
+                        out_stats, n_stats);
 }
 
 RM_EXPORT int rm_label_occupancy(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz, const void* occupancy, int is_device, void* stream,
                                  uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
-    if (!c) return RM_ERR_NULL;
-    if (!occupancy || !out_counts || !out_stats) return fail(c, RM_ERR_NULL, "rm_label_occupancy: occupancy, out_counts or out_stats is NULL");
-    if (n_counts < (uint32_t)RM_TOPO_COUNTS) return fail(c, RM_ERR_ARG, "rm_label_occupancy: n_counts %u < RM_TOPO_COUNTS", n_counts);
-    if (n_stats < (uint32_t)RM_TOPO_STATS) return fail(c, RM_ERR_ARG, "rm_label_occupancy: n_stats %u < RM_TOPO_STATS", n_stats);
-    if (!topo_lattice_ok(nx, ny, nz))
-        return fail(c, RM_ERR_RANGE, "rm_label_occupancy: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", nx, ny, nz);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = c->stream;
-    order_with_previous(c, s);  // after a device read of the previous labelling, too
-    const float zero[3] = {0.0f, 0.0f, 0.0f}, one[3] = {1.0f, 1.0f, 1.0f};
-    const TopoGrid G = topo_grid(zero, one, nx, ny, nz);
-    const rml::TopoScratch T(G.n, G.g.nb, G.n_pblocks, G.n_rblocks);
-    int rc = c->d_mscratch.reserve(c, T.bytes);
-    if (rc != RM_OK) return rc;
-    c->topo_valid = false;  // its buffers change from here on
-    char* sc = c->d_mscratch.p;
-    if (is_device) {
-        // the caller's array is ready when the work queued on its stream is done; the call is synchronous anyway
-        const hipStream_t su = user_stream(c, stream);
-        if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
-    }
-    HIP_TRY(c, hipMemcpyAsync(T.occ.at(sc), occupancy, G.n, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    uint64_t counts[RM_TOPO_COUNTS], passes = 0;
-    if ((rc = label_lattice(c, "rm_label_occupancy", s, G, T, counts, &passes)) != RM_OK) return rc;
-    for (int k = 0; k < RM_TOPO_COUNTS; k++) out_counts[k] = counts[k];
-    for (int k = 0; k < RM_TOPO_STATS; k++) out_stats[k] = 0u;
-    out_stats[RM_TOPO_STAT_MERGE_PASSES] = passes;
-    out_stats[RM_TOPO_STAT_SCRATCH_BYTES] = T.bytes;
-    return RM_OK;
+    return lattice_call(c, "rm_label_occupancy", OccupancySource::of_bytes(occupancy, is_device, stream), nx, ny, nz, LabelAnalysis(), out_counts,
+                        n_counts, out_stats, n_stats);
 }
 
 RM_EXPORT int rm_read_topology(rm_ctx* c, uint64_t* out_body_moments, uint64_t* out_cavity_moments, uint32_t* out_labels, int is_device,
@@ -2271,80 +2327,37 @@ int distance_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rml::Dis
     return RM_OK;
 }
 
+struct DistanceAnalysis {
+    static constexpr uint32_t kCounts = RM_DIST_COUNTS, kStats = RM_DIST_STATS;
+    static constexpr const char *kCountsName = "RM_DIST_COUNTS", *kStatsName = "RM_DIST_STATS";
+    int check(rm_ctx* c, const char* fn, uint32_t nx, uint32_t ny, uint32_t nz) const { return check_topo_lattice(c, fn, nx, ny, nz); }
+    rml::DistScratch layout(const TopoGrid& G) const {
+        const DistBlocks D(G.n);
+        return rml::DistScratch(G.n, G.g.nb, G.n_pblocks, D.n_rblocks, D.n_fblocks);
+    }
+    int reserve(rm_ctx* c, const TopoGrid& G, const rml::DistScratch& S) const {
+        const int rc = c->d_mscratch.reserve(c, S.bytes);
+        if (rc != RM_OK) return rc;
+        c->dist_valid = c->dist_mask_valid = false;  // its buffers change from here on
+        return c->d_dvol.reserve(c, (size_t)G.n * 4u, "distance volume");
+    }
+    int run(rm_ctx* c, const char*, hipStream_t s, const TopoGrid& G, const rml::DistScratch& S, uint64_t* counts, uint64_t*) const {
+        return distance_lattice(c, s, G, S, counts);
+    }
+};
+
 }  // namespace
 
 RM_EXPORT int rm_distance_solid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
                                 uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
-    if (!c) return RM_ERR_NULL;
-    if (!out_counts || !out_stats) return fail(c, RM_ERR_NULL, "rm_distance_solid: out_counts or out_stats is NULL");
-    if (n_counts < (uint32_t)RM_DIST_COUNTS) return fail(c, RM_ERR_ARG, "rm_distance_solid: n_counts %u < RM_DIST_COUNTS", n_counts);
-    if (n_stats < (uint32_t)RM_DIST_STATS) return fail(c, RM_ERR_ARG, "rm_distance_solid: n_stats %u < RM_DIST_STATS", n_stats);
-    if (int rc = check_lattice(c, "rm_distance_solid", origin, step)) return rc;
-    if (int rc = check_iso(c, "rm_distance_solid", level, 0u)) return rc;
-    if (!topo_lattice_ok(nx, ny, nz))
-        return fail(c, RM_ERR_RANGE, "rm_distance_solid: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", nx, ny, nz);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = c->stream;
-    SolidOccupancy O;
-    int rc = solid_occupancy_begin(c, "rm_distance_solid", s, origin, step, nx, ny, nz, &O);  // after a device read of the last volume, too
-    if (rc != RM_OK) return rc;
-    const TopoGrid G = topo_grid(origin, step, nx, ny, nz);
-    const DistBlocks D(G.n);
-    const rml::DistScratch S(G.n, G.g.nb, G.n_pblocks, D.n_rblocks, D.n_fblocks);
-    if ((rc = c->d_mscratch.reserve(c, S.bytes)) != RM_OK) return rc;
-    c->dist_valid = c->dist_mask_valid = false;  // its buffers change from here on
-    if ((rc = c->d_dvol.reserve(c, (size_t)G.n * 4u, "distance volume")) != RM_OK) return rc;
-    char* sc = c->d_mscratch.p;
-    unsigned long long* evals = S.evals.at(sc);
-    if ((rc = solid_occupancy_fill(c, s, O, G, level, S.cls.at(sc), S.psums.at(sc), S.ptot.at(sc), S.occ.at(sc), evals)) != RM_OK) return rc;
-    uint64_t counts[RM_DIST_COUNTS];
-    if ((rc = distance_lattice(c, s, G, S, counts)) != RM_OK) return rc;
-    unsigned long long tot[2] = {0ull, 0ull}, ev = 0ull;
-    HIP_TRY(c, hipMemcpyAsync(tot, S.ptot.at(sc), sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    for (int k = 0; k < RM_DIST_COUNTS; k++) out_counts[k] = counts[k];
-    out_stats[RM_DIST_STAT_BRICKS] = G.g.nb;
-    out_stats[RM_DIST_STAT_BRICKS_KEPT] = tot[0];
-    out_stats[RM_DIST_STAT_BRICKS_INSIDE] = tot[1];
-    out_stats[RM_DIST_STAT_EVALUATIONS] = G.g.nb + ev;
-    out_stats[RM_DIST_STAT_SCRATCH_BYTES] = S.bytes;
-    return RM_OK;
+    return lattice_call(c, "rm_distance_solid", OccupancySource::of_solid(origin, step, level), nx, ny, nz, DistanceAnalysis(), out_counts,
+                        n_counts, out_stats, n_stats);
 }
 
 RM_EXPORT int rm_distance_occupancy(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz, const void* occupancy, int is_device, void* stream,
                                     uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
-    if (!c) return RM_ERR_NULL;
-    if (!occupancy || !out_counts || !out_stats)
-        return fail(c, RM_ERR_NULL, "rm_distance_occupancy: occupancy, out_counts or out_stats is NULL");
-    if (n_counts < (uint32_t)RM_DIST_COUNTS) return fail(c, RM_ERR_ARG, "rm_distance_occupancy: n_counts %u < RM_DIST_COUNTS", n_counts);
-    if (n_stats < (uint32_t)RM_DIST_STATS) return fail(c, RM_ERR_ARG, "rm_distance_occupancy: n_stats %u < RM_DIST_STATS", n_stats);
-    if (!topo_lattice_ok(nx, ny, nz))
-        return fail(c, RM_ERR_RANGE, "rm_distance_occupancy: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", nx, ny, nz);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = c->stream;
-    order_with_previous(c, s);  // after a device read of the last volume, too
-    const float zero[3] = {0.0f, 0.0f, 0.0f}, one[3] = {1.0f, 1.0f, 1.0f};
-    const TopoGrid G = topo_grid(zero, one, nx, ny, nz);
-    const DistBlocks D(G.n);
-    const rml::DistScratch S(G.n, G.g.nb, G.n_pblocks, D.n_rblocks, D.n_fblocks);
-    int rc = c->d_mscratch.reserve(c, S.bytes);
-    if (rc != RM_OK) return rc;
-    c->dist_valid = c->dist_mask_valid = false;  // its buffers change from here on
-    if ((rc = c->d_dvol.reserve(c, (size_t)G.n * 4u, "distance volume")) != RM_OK) return rc;
-    char* sc = c->d_mscratch.p;
-    if (is_device) {
-        // the caller's array is ready when the work queued on its stream is done; the call is synchronous anyway
-        const hipStream_t su = user_stream(c, stream);
-        if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
-    }
-    HIP_TRY(c, hipMemcpyAsync(S.occ.at(sc), occupancy, G.n, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    uint64_t counts[RM_DIST_COUNTS];
-    if ((rc = distance_lattice(c, s, G, S, counts)) != RM_OK) return rc;
-    for (int k = 0; k < RM_DIST_COUNTS; k++) out_counts[k] = counts[k];
-    for (int k = 0; k < RM_DIST_STATS; k++) out_stats[k] = 0u;
-    out_stats[RM_DIST_STAT_SCRATCH_BYTES] = S.bytes;
-    return RM_OK;
+    return lattice_call(c, "rm_distance_occupancy", OccupancySource::of_bytes(occupancy, is_device, stream), nx, ny, nz, DistanceAnalysis(),
+                        out_counts, n_counts, out_stats, n_stats);
 }
 
 RM_EXPORT int rm_distance_features(rm_ctx* c, uint32_t r2_wall, uint32_t r2_gap, uint64_t* out_counts, uint32_t n_counts) {
@@ -2358,8 +2371,7 @@ RM_EXPORT int rm_distance_features(rm_ctx* c, uint32_t r2_wall, uint32_t r2_gap,
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = c->stream;
     order_with_previous(c, s);  // after a device read of the last mask, too
-    const float zero[3] = {0.0f, 0.0f, 0.0f}, one[3] = {1.0f, 1.0f, 1.0f};
-    const TopoGrid G = topo_grid(zero, one, c->dist_nx, c->dist_ny, c->dist_nz);
+    const TopoGrid G = topo_grid(sparse_grid(kUnitOrigin, kUnitStep, c->dist_nx, c->dist_ny, c->dist_nz));
     const rmk::SparseGrid& g = G.g;
     const DistBlocks D(G.n);
     const rml::DistFeatureScratch S(G.n, D.n_rblocks, D.n_fblocks);
@@ -2443,8 +2455,7 @@ uint32_t sup_plane_words(const rmk::SupFrame& f) { return f.nh * f.nv * f.nw; } 
 // The argument checks the two support calls share, after those of their outputs and their lattice's values.
 int check_support(rm_ctx* c, const char* fn, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t up, uint32_t r2, uint32_t plate) {
     if (up > (uint32_t)RM_UP_NEG_Z) return fail(c, RM_ERR_ARG, "%s: up %u is not one of RM_UP_*", fn, up);
-    if (!topo_lattice_ok(nx, ny, nz))
-        return fail(c, RM_ERR_RANGE, "%s: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", fn, nx, ny, nz);
+    if (int rc = check_topo_lattice(c, fn, nx, ny, nz)) return rc;
     if (r2 > rml::kSupMaxR2) return fail(c, RM_ERR_RANGE, "%s: r2 %u: a squared reach is 0..255", fn, r2);
     const uint32_t nh = sup_frame(nx, ny, nz, up).nh;
     if (plate != RM_SUPPORT_PLATE_AUTO && plate >= nh)
@@ -2452,20 +2463,34 @@ int check_support(rm_ctx* c, const char* fn, uint32_t nx, uint32_t ny, uint32_t 
     return RM_OK;
 }
 
+// A wave's tasks in pack and compose: four words each, or with x up (the kernels' template argument) one (row, word) and 64 layers.
+struct SupTasks {
+    bool xup;
+    uint32_t n;
+    dim3 grid;
+    explicit SupTasks(const rmk::SupFrame& f) : xup(f.sh == 1u), n(xup ? f.nv * f.nw * ((f.nh + 63u) / 64u) : sup_plane_words(f)) {
+        const uint32_t n_waves = xup ? n : (n + rmk::kSupWordsPerWave - 1u) / rmk::kSupWordsPerWave;
+        grid = dim3((n_waves + 3u) / 4u);
+    }
+};
+// floor(sqrt(r2)): the halo, in points, of a squared reach.
+uint32_t sup_reach(uint32_t r2) {
+    uint32_t reach = 0u;
+    while ((reach + 1u) * (reach + 1u) <= r2) reach++;
+    return reach;
+}
+// The plate's height: the caller's, or what the pack kernel found for RM_SUPPORT_PLATE_AUTO (h0: its word; no inside point: 0).
+uint32_t sup_plate_height(uint32_t plate, uint32_t h0) { return plate != RM_SUPPORT_PLATE_AUTO ? plate : h0 == RM_SUPPORT_PLATE_AUTO ? 0u : h0; }
+
 // The planes `ins` and `ov` of an occupancy (rm_support.h pack and overhang); h0w: the automatic plate's word, 0xFF.. before.
 void support_planes(hipStream_t s, const rmk::SupFrame& f, uint32_t r2, uint32_t plate, const uint8_t* occ, unsigned long long* ins,
                     unsigned long long* ov, uint32_t* h0w) {
-    const bool xup = f.sh == 1u;
-    const uint32_t n_tasks = xup ? f.nv * f.nw * ((f.nh + 63u) / 64u) : sup_plane_words(f);
-    const uint32_t n_waves = xup ? n_tasks : (n_tasks + rmk::kSupWordsPerWave - 1u) / rmk::kSupWordsPerWave;
-    const dim3 task_grid((n_waves + 3u) / 4u);
-    if (xup)
-        hipLaunchKernelGGL(rmk::rm_sup_pack_kernel<true>, task_grid, dim3(256), 0, s, f, n_tasks, plate, occ, ins, h0w);
+    const SupTasks tasks(f);
+    if (tasks.xup)
+        hipLaunchKernelGGL(rmk::rm_sup_pack_kernel<true>, tasks.grid, dim3(256), 0, s, f, tasks.n, plate, occ, ins, h0w);
     else
-        hipLaunchKernelGGL(rmk::rm_sup_pack_kernel<false>, task_grid, dim3(256), 0, s, f, n_tasks, plate, occ, ins, h0w);
-    uint32_t reach = 0u;
-    while ((reach + 1u) * (reach + 1u) <= r2) reach++;
-    const uint32_t tv = rml::sup_tile_rows(f.nw);
+        hipLaunchKernelGGL(rmk::rm_sup_pack_kernel<false>, tasks.grid, dim3(256), 0, s, f, tasks.n, plate, occ, ins, h0w);
+    const uint32_t reach = sup_reach(r2), tv = rml::sup_tile_rows(f.nw);
     hipLaunchKernelGGL(rmk::rm_sup_overhang_kernel, dim3((f.nv + tv - 1u) / tv, f.nh), dim3(256), rml::SupCoverLds(tv, reach, f.nw).bytes, s, f.nv,
                        f.nw, tv, r2, reach, plate, static_cast<const uint32_t*>(h0w), static_cast<const unsigned long long*>(ins), ov);
 }
@@ -2480,12 +2505,8 @@ int support_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
     uint8_t* mask = reinterpret_cast<uint8_t*>(c->d_smask.p);
     unsigned long long *ins = S.ins.at(sc), *ov = S.ov.at(sc), *sup = S.sup.at(sc), *plt = S.plt.at(sc);
     uint32_t* h0w = S.plate.at(sc);
-    const uint32_t n_words = sup_plane_words(f), ncw = f.nv * f.nw;
-    const bool xup = f.sh == 1u;
-    // a wave's tasks in pack and compose: four words each, or with x up one (row, word) and 64 layers
-    const uint32_t n_tasks = xup ? f.nv * f.nw * ((f.nh + 63u) / 64u) : n_words;
-    const uint32_t n_waves = xup ? n_tasks : (n_tasks + rmk::kSupWordsPerWave - 1u) / rmk::kSupWordsPerWave;
-    const dim3 task_grid((n_waves + 3u) / 4u);
+    const uint32_t ncw = f.nv * f.nw;
+    const SupTasks tasks(f);
     HIP_TRY(c, hipMemsetAsync(h0w, 0xFF, 16, s));
     HIP_TRY(c, hipMemsetAsync(pr, 0, R.bytes, s));
     const uint8_t* occ = S.occ.at(sc);
@@ -2495,12 +2516,12 @@ int support_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
     hipLaunchKernelGGL(rmk::rm_sup_count_kernel, dim3((ncw + 255u) / 256u, f.nh), dim3(256), 0, s, ncw, f.nh, plate, static_cast<const uint32_t*>(h0w),
                        static_cast<const unsigned long long*>(ins), static_cast<const unsigned long long*>(ov),
                        static_cast<const unsigned long long*>(sup), static_cast<const unsigned long long*>(plt), R.profile.at(pr), R.extra.at(pr));
-    if (xup)
-        hipLaunchKernelGGL(rmk::rm_sup_compose_kernel<true>, task_grid, dim3(256), 0, s, f, n_tasks, static_cast<const unsigned long long*>(ins),
+    if (tasks.xup)
+        hipLaunchKernelGGL(rmk::rm_sup_compose_kernel<true>, tasks.grid, dim3(256), 0, s, f, tasks.n, static_cast<const unsigned long long*>(ins),
                            static_cast<const unsigned long long*>(ov), static_cast<const unsigned long long*>(sup),
                            static_cast<const unsigned long long*>(plt), mask);
     else
-        hipLaunchKernelGGL(rmk::rm_sup_compose_kernel<false>, task_grid, dim3(256), 0, s, f, n_tasks, static_cast<const unsigned long long*>(ins),
+        hipLaunchKernelGGL(rmk::rm_sup_compose_kernel<false>, tasks.grid, dim3(256), 0, s, f, tasks.n, static_cast<const unsigned long long*>(ins),
                            static_cast<const unsigned long long*>(ov), static_cast<const unsigned long long*>(sup),
                            static_cast<const unsigned long long*>(plt), mask);
     HIP_TRY(c, hipGetLastError());
@@ -2510,7 +2531,7 @@ int support_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
     HIP_TRY(c, hipMemcpyAsync(rows.data() + (size_t)f.nh * 4u, R.extra.at(pr), (size_t)f.nh * 8u, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(&h0, h0w, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    h0 = plate != RM_SUPPORT_PLATE_AUTO ? plate : h0 == RM_SUPPORT_PLATE_AUTO ? 0u : h0;
+    h0 = sup_plate_height(plate, h0);
     for (int k = 0; k < RM_SUP_COUNTS; k++) counts[k] = 0u;
     for (uint32_t h = 0; h < f.nh; h++) {
         counts[RM_SUP_POINTS] += rows[4u * h];
@@ -2528,85 +2549,49 @@ int support_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
     return RM_OK;
 }
 
-// The buffers of a support call: scratch, mask and profile.  The last result is gone from here on.
-int support_reserve(rm_ctx* c, const TopoGrid& G, const rmk::SupFrame& f, const rml::SupportScratch& S) {
-    int rc = c->d_mscratch.reserve(c, S.bytes);
-    if (rc != RM_OK) return rc;
-    c->sup_valid = false;
-    if ((rc = c->d_smask.reserve(c, G.n, "support mask")) != RM_OK) return rc;
-    return c->d_sprof.reserve(c, rml::SupportProfile(f.nh).bytes, "support profile");
-}
+// The arguments of the analyses with a build direction, and their frame (layout() sets it).
+struct DirectedAnalysis {
+    uint32_t up, r2, plate;
+    rmk::SupFrame f;
+    DirectedAnalysis(uint32_t up_, uint32_t r2_, uint32_t plate_) : up(up_), r2(r2_), plate(plate_), f() {}
+    int check(rm_ctx* c, const char* fn, uint32_t nx, uint32_t ny, uint32_t nz) const { return check_support(c, fn, nx, ny, nz, up, r2, plate); }
+};
+
+struct SupportAnalysis : DirectedAnalysis {
+    using DirectedAnalysis::DirectedAnalysis;
+    static constexpr uint32_t kCounts = RM_SUP_COUNTS, kStats = RM_SUP_STATS;
+    static constexpr const char *kCountsName = "RM_SUP_COUNTS", *kStatsName = "RM_SUP_STATS";
+    rml::SupportScratch layout(const TopoGrid& G) {
+        f = sup_frame(G.g.nx, G.g.ny, G.g.nz, up);
+        return rml::SupportScratch(G.n, G.g.nb, G.n_pblocks, sup_plane_words(f));
+    }
+    // The buffers of a support call: scratch, mask and profile.  The last result is gone once the scratch is reserved.
+    int reserve(rm_ctx* c, const TopoGrid& G, const rml::SupportScratch& S) const {
+        int rc = c->d_mscratch.reserve(c, S.bytes);
+        if (rc != RM_OK) return rc;
+        c->sup_valid = false;
+        if ((rc = c->d_smask.reserve(c, G.n, "support mask")) != RM_OK) return rc;
+        return c->d_sprof.reserve(c, rml::SupportProfile(f.nh).bytes, "support profile");
+    }
+    int run(rm_ctx* c, const char*, hipStream_t s, const TopoGrid& G, const rml::SupportScratch& S, uint64_t* counts, uint64_t*) const {
+        return support_lattice(c, s, G, f, S, r2, plate, counts);
+    }
+};
 
 }  // namespace
 
 RM_EXPORT int rm_support_solid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
                                uint32_t up, uint32_t r2, uint32_t plate, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
                                uint32_t n_stats) {
-    if (!c) return RM_ERR_NULL;
-    if (!out_counts || !out_stats) return fail(c, RM_ERR_NULL, "rm_support_solid: out_counts or out_stats is NULL");
-    if (n_counts < (uint32_t)RM_SUP_COUNTS) return fail(c, RM_ERR_ARG, "rm_support_solid: n_counts %u < RM_SUP_COUNTS", n_counts);
-    if (n_stats < (uint32_t)RM_SUP_STATS) return fail(c, RM_ERR_ARG, "rm_support_solid: n_stats %u < RM_SUP_STATS", n_stats);
-    if (int rc = check_lattice(c, "rm_support_solid", origin, step)) return rc;
-    if (int rc = check_iso(c, "rm_support_solid", level, 0u)) return rc;
-    if (int rc = check_support(c, "rm_support_solid", nx, ny, nz, up, r2, plate)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = c->stream;
-    SolidOccupancy O;
-    int rc = solid_occupancy_begin(c, "rm_support_solid", s, origin, step, nx, ny, nz, &O);  // after a device read of the last mask, too
-    if (rc != RM_OK) return rc;
-    const TopoGrid G = topo_grid(origin, step, nx, ny, nz);
-    const rmk::SupFrame f = sup_frame(nx, ny, nz, up);
-    const rml::SupportScratch S(G.n, G.g.nb, G.n_pblocks, sup_plane_words(f));
-    if ((rc = support_reserve(c, G, f, S)) != RM_OK) return rc;
-    char* sc = c->d_mscratch.p;
-    unsigned long long* evals = S.evals.at(sc);
-    if ((rc = solid_occupancy_fill(c, s, O, G, level, S.cls.at(sc), S.psums.at(sc), S.ptot.at(sc), S.occ.at(sc), evals)) != RM_OK) return rc;
-    uint64_t counts[RM_SUP_COUNTS];
-    if ((rc = support_lattice(c, s, G, f, S, r2, plate, counts)) != RM_OK) return rc;
-    unsigned long long tot[2] = {0ull, 0ull}, ev = 0ull;
-    HIP_TRY(c, hipMemcpyAsync(tot, S.ptot.at(sc), sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    for (int k = 0; k < RM_SUP_COUNTS; k++) out_counts[k] = counts[k];
-    out_stats[RM_SUP_STAT_BRICKS] = G.g.nb;
-    out_stats[RM_SUP_STAT_BRICKS_KEPT] = tot[0];
-    out_stats[RM_SUP_STAT_BRICKS_INSIDE] = tot[1];
-    out_stats[RM_SUP_STAT_EVALUATIONS] = G.g.nb + ev;
-    out_stats[RM_SUP_STAT_SCRATCH_BYTES] = S.bytes;
-    return RM_OK;
+    return lattice_call(c, "rm_support_solid", OccupancySource::of_solid(origin, step, level), nx, ny, nz, SupportAnalysis(up, r2, plate),
+                        out_counts, n_counts, out_stats, n_stats);
 }
 
 RM_EXPORT int rm_support_occupancy(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz, const void* occupancy, int is_device, void* stream,
                                    uint32_t up, uint32_t r2, uint32_t plate, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
                                    uint32_t n_stats) {
-    if (!c) return RM_ERR_NULL;
-    if (!occupancy || !out_counts || !out_stats)
-        return fail(c, RM_ERR_NULL, "rm_support_occupancy: occupancy, out_counts or out_stats is NULL");
-    if (n_counts < (uint32_t)RM_SUP_COUNTS) return fail(c, RM_ERR_ARG, "rm_support_occupancy: n_counts %u < RM_SUP_COUNTS", n_counts);
-    if (n_stats < (uint32_t)RM_SUP_STATS) return fail(c, RM_ERR_ARG, "rm_support_occupancy: n_stats %u < RM_SUP_STATS", n_stats);
-    if (int rc = check_support(c, "rm_support_occupancy", nx, ny, nz, up, r2, plate)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = c->stream;
-    order_with_previous(c, s);  // after a device read of the last mask, too
-    const float zero[3] = {0.0f, 0.0f, 0.0f}, one[3] = {1.0f, 1.0f, 1.0f};
-    const TopoGrid G = topo_grid(zero, one, nx, ny, nz);
-    const rmk::SupFrame f = sup_frame(nx, ny, nz, up);
-    const rml::SupportScratch S(G.n, G.g.nb, G.n_pblocks, sup_plane_words(f));
-    int rc = support_reserve(c, G, f, S);
-    if (rc != RM_OK) return rc;
-    char* sc = c->d_mscratch.p;
-    if (is_device) {
-        // the caller's array is ready when the work queued on its stream is done; the call is synchronous anyway
-        const hipStream_t su = user_stream(c, stream);
-        if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
-    }
-    HIP_TRY(c, hipMemcpyAsync(S.occ.at(sc), occupancy, G.n, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    uint64_t counts[RM_SUP_COUNTS];
-    if ((rc = support_lattice(c, s, G, f, S, r2, plate, counts)) != RM_OK) return rc;
-    for (int k = 0; k < RM_SUP_COUNTS; k++) out_counts[k] = counts[k];
-    for (int k = 0; k < RM_SUP_STATS; k++) out_stats[k] = 0u;
-    out_stats[RM_SUP_STAT_SCRATCH_BYTES] = S.bytes;
-    return RM_OK;
+    return lattice_call(c, "rm_support_occupancy", OccupancySource::of_bytes(occupancy, is_device, stream), nx, ny, nz,
+                        SupportAnalysis(up, r2, plate), out_counts, n_counts, out_stats, n_stats);
 }
 
 RM_EXPORT int rm_read_support(rm_ctx* c, void* out_mask, uint32_t* out_profile, int is_device, void* stream) {
@@ -2635,30 +2620,17 @@ static_assert(rmk::kIslLayer == RM_ISL_ROW_LAYER && rmk::kIslFirst == RM_ISL_ROW
               "the words of a row");
 static_assert(rml::IslLinkLds(rml::kSupMaxReach).bytes + 256u <= rml::kLdsLaunchLimit, "the links tile fits a workgroup");
 
+// The plane words and the blocks of 256 points of an islands call.
 struct IslandsPlan {
-    rmk::SupFrame f;
     uint32_t n_words, n_rblocks;
-    IslandsPlan(const TopoGrid& G, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t up)
-        : f(sup_frame(nx, ny, nz, up)), n_words(sup_plane_words(f)), n_rblocks((G.n + 255u) / 256u) {}
-    rml::IslandsScratch scratch(const TopoGrid& G) const { return rml::IslandsScratch(G.n, G.g.nb, G.n_pblocks, n_words, n_rblocks, f.nh); }
+    IslandsPlan(const TopoGrid& G, const rmk::SupFrame& f) : n_words(sup_plane_words(f)), n_rblocks((G.n + 255u) / 256u) {}
 };
-
-// The buffers of an islands call: scratch, labels, mask and profile (the region table follows the count).  The last result is
-// gone from here on.
-int islands_reserve(rm_ctx* c, const TopoGrid& G, const rmk::SupFrame& f, const rml::IslandsScratch& S) {
-    int rc = c->d_mscratch.reserve(c, S.bytes);
-    if (rc != RM_OK) return rc;
-    c->isl_valid = false;
-    if ((rc = c->d_ilabels.reserve(c, (size_t)G.n * 4u, "region labels")) != RM_OK) return rc;
-    if ((rc = c->d_imask.reserve(c, G.n, "island mask")) != RM_OK) return rc;
-    return c->d_iprof.reserve(c, (size_t)f.nh * 16u, "region profile");
-}
 
 // From the occupancy in S.occ on (rm_islands.h): pack, overhang, local, border, roots, scan; the table; rank, spread, rows, links,
 // finish, compose; the profile summed on the host (at most 1024 layers of four words).  counts: RM_ISL_COUNTS words.
-int islands_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const IslandsPlan& P, const rml::IslandsScratch& S, uint32_t up, uint32_t r2,
+int islands_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupFrame& f, const rml::IslandsScratch& S, uint32_t up, uint32_t r2,
                     uint32_t plate, uint64_t* counts) {
-    const rmk::SupFrame& f = P.f;
+    const IslandsPlan P(G, f);
     char* sc = c->d_mscratch.p;
     unsigned long long *ins = S.ins.at(sc), *ov = S.ov.at(sc), *rsums = S.rsums.at(sc), *rtot = S.rtot.at(sc);
     uint32_t *h0w = S.plate.at(sc), *parent = S.parent.at(sc), *lab = S.lab.at(sc), *lbase = S.lbase.at(sc), *totals = S.totals.at(sc);
@@ -2670,9 +2642,7 @@ int islands_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const IslandsPl
     HIP_TRY(c, hipMemsetAsync(totals, 0, 16, s));
     HIP_TRY(c, hipMemsetAsync(prof, 0, (size_t)f.nh * 16u, s));
     support_planes(s, f, r2, plate, S.occ.at(sc), ins, ov, h0w);
-    uint32_t reach = 0u;
-    while ((reach + 1u) * (reach + 1u) <= r2) reach++;
-    const uint32_t ncw = f.nv * f.nw;
+    const uint32_t reach = sup_reach(r2), ncw = f.nv * f.nw;
     hipLaunchKernelGGL(rmk::rm_isl_local_kernel, dim3(f.nw, (f.nv + rml::kIslTile - 1u) / rml::kIslTile, f.nh), dim3(64), rml::IslTileLds().bytes, s,
                        f, plate, ch0, cins, parent);
     hipLaunchKernelGGL(rmk::rm_isl_border_kernel, dim3((P.n_words + 255u) / 256u), dim3(256), 0, s, f, P.n_words, G.n, plate, ch0, cins, parent);
@@ -2711,7 +2681,7 @@ int islands_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const IslandsPl
     HIP_TRY(c, hipMemcpyAsync(&h0, h0w, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(&merges, totals, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    h0 = plate != RM_SUPPORT_PLATE_AUTO ? plate : h0 == RM_SUPPORT_PLATE_AUTO ? 0u : h0;
+    h0 = sup_plate_height(plate, h0);
     for (int k = 0; k < RM_ISL_COUNTS; k++) counts[k] = 0u;
     for (uint32_t h = 0; h < f.nh; h++) {
         counts[RM_ISL_POINTS] += layers[4u * h];
@@ -2730,76 +2700,44 @@ int islands_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const IslandsPl
     return RM_OK;
 }
 
+struct IslandsAnalysis : DirectedAnalysis {
+    using DirectedAnalysis::DirectedAnalysis;
+    static constexpr uint32_t kCounts = RM_ISL_COUNTS, kStats = RM_ISL_STATS;
+    static constexpr const char *kCountsName = "RM_ISL_COUNTS", *kStatsName = "RM_ISL_STATS";
+    rml::IslandsScratch layout(const TopoGrid& G) {
+        f = sup_frame(G.g.nx, G.g.ny, G.g.nz, up);
+        const IslandsPlan P(G, f);
+        return rml::IslandsScratch(G.n, G.g.nb, G.n_pblocks, P.n_words, P.n_rblocks, f.nh);
+    }
+    // The buffers of an islands call: scratch, labels, mask and profile (the region table follows the count).  The last result is
+    // gone once the scratch is reserved.
+    int reserve(rm_ctx* c, const TopoGrid& G, const rml::IslandsScratch& S) const {
+        int rc = c->d_mscratch.reserve(c, S.bytes);
+        if (rc != RM_OK) return rc;
+        c->isl_valid = false;
+        if ((rc = c->d_ilabels.reserve(c, (size_t)G.n * 4u, "region labels")) != RM_OK) return rc;
+        if ((rc = c->d_imask.reserve(c, G.n, "island mask")) != RM_OK) return rc;
+        return c->d_iprof.reserve(c, (size_t)f.nh * 16u, "region profile");
+    }
+    int run(rm_ctx* c, const char*, hipStream_t s, const TopoGrid& G, const rml::IslandsScratch& S, uint64_t* counts, uint64_t*) const {
+        return islands_lattice(c, s, G, f, S, up, r2, plate, counts);
+    }
+};
+
 }  // namespace
 
 RM_EXPORT int rm_islands_solid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
                                uint32_t up, uint32_t r2, uint32_t plate, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
                                uint32_t n_stats) {
-    if (!c) return RM_ERR_NULL;
-    if (!out_counts || !out_stats) return fail(c, RM_ERR_NULL, "rm_islands_solid: out_counts or out_stats is NULL");
-    if (n_counts < (uint32_t)RM_ISL_COUNTS) return fail(c, RM_ERR_ARG, "rm_islands_solid: n_counts %u < RM_ISL_COUNTS", n_counts);
-    if (n_stats < (uint32_t)RM_ISL_STATS) return fail(c, RM_ERR_ARG, "rm_islands_solid: n_stats %u < RM_ISL_STATS", n_stats);
-    if (int rc = check_lattice(c, "rm_islands_solid", origin, step)) return rc;
-    if (int rc = check_iso(c, "rm_islands_solid", level, 0u)) return rc;
-    if (int rc = check_support(c, "rm_islands_solid", nx, ny, nz, up, r2, plate)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = c->stream;
-    SolidOccupancy O;
-    int rc = solid_occupancy_begin(c, "rm_islands_solid", s, origin, step, nx, ny, nz, &O);  // after a device read of the last result, too
-    if (rc != RM_OK) return rc;
-    const TopoGrid G = topo_grid(origin, step, nx, ny, nz);
-    const IslandsPlan P(G, nx, ny, nz, up);
-    const rml::IslandsScratch S = P.scratch(G);
-    if ((rc = islands_reserve(c, G, P.f, S)) != RM_OK) return rc;
-    char* sc = c->d_mscratch.p;
-    unsigned long long* evals = S.evals.at(sc);
-    if ((rc = solid_occupancy_fill(c, s, O, G, level, S.cls.at(sc), S.psums.at(sc), S.ptot.at(sc), S.occ.at(sc), evals)) != RM_OK) return rc;
-    uint64_t counts[RM_ISL_COUNTS];
-    if ((rc = islands_lattice(c, s, G, P, S, up, r2, plate, counts)) != RM_OK) return rc;
-    unsigned long long tot[2] = {0ull, 0ull}, ev = 0ull;
-    HIP_TRY(c, hipMemcpyAsync(tot, S.ptot.at(sc), sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    for (int k = 0; k < RM_ISL_COUNTS; k++) out_counts[k] = counts[k];
-    out_stats[RM_ISL_STAT_BRICKS] = G.g.nb;
-    out_stats[RM_ISL_STAT_BRICKS_KEPT] = tot[0];
-    out_stats[RM_ISL_STAT_BRICKS_INSIDE] = tot[1];
-    out_stats[RM_ISL_STAT_EVALUATIONS] = G.g.nb + ev;
-    out_stats[RM_ISL_STAT_SCRATCH_BYTES] = S.bytes;
-    return RM_OK;
+    return lattice_call(c, "rm_islands_solid", OccupancySource::of_solid(origin, step, level), nx, ny, nz, IslandsAnalysis(up, r2, plate),
+                        out_counts, n_counts, out_stats, n_stats);
 }
 
 RM_EXPORT int rm_islands_occupancy(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz, const void* occupancy, int is_device, void* stream,
                                    uint32_t up, uint32_t r2, uint32_t plate, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
                                    uint32_t n_stats) {
-    if (!c) return RM_ERR_NULL;
-    if (!occupancy || !out_counts || !out_stats)
-        return fail(c, RM_ERR_NULL, "rm_islands_occupancy: occupancy, out_counts or out_stats is NULL");
-    if (n_counts < (uint32_t)RM_ISL_COUNTS) return fail(c, RM_ERR_ARG, "rm_islands_occupancy: n_counts %u < RM_ISL_COUNTS", n_counts);
-    if (n_stats < (uint32_t)RM_ISL_STATS) return fail(c, RM_ERR_ARG, "rm_islands_occupancy: n_stats %u < RM_ISL_STATS", n_stats);
-    if (int rc = check_support(c, "rm_islands_occupancy", nx, ny, nz, up, r2, plate)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = c->stream;
-    order_with_previous(c, s);  // after a device read of the last result, too
-    const float zero[3] = {0.0f, 0.0f, 0.0f}, one[3] = {1.0f, 1.0f, 1.0f};
-    const TopoGrid G = topo_grid(zero, one, nx, ny, nz);
-    const IslandsPlan P(G, nx, ny, nz, up);
-    const rml::IslandsScratch S = P.scratch(G);
-    int rc = islands_reserve(c, G, P.f, S);
-    if (rc != RM_OK) return rc;
-    char* sc = c->d_mscratch.p;
-    if (is_device) {
-        // the caller's array is ready when the work queued on its stream is done; the call is synchronous anyway
-        const hipStream_t su = user_stream(c, stream);
-        if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
-    }
-    HIP_TRY(c, hipMemcpyAsync(S.occ.at(sc), occupancy, G.n, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    uint64_t counts[RM_ISL_COUNTS];
-    if ((rc = islands_lattice(c, s, G, P, S, up, r2, plate, counts)) != RM_OK) return rc;
-    for (int k = 0; k < RM_ISL_COUNTS; k++) out_counts[k] = counts[k];
-    for (int k = 0; k < RM_ISL_STATS; k++) out_stats[k] = 0u;
-    out_stats[RM_ISL_STAT_SCRATCH_BYTES] = S.bytes;
-    return RM_OK;
+    return lattice_call(c, "rm_islands_occupancy", OccupancySource::of_bytes(occupancy, is_device, stream), nx, ny, nz,
+                        IslandsAnalysis(up, r2, plate), out_counts, n_counts, out_stats, n_stats);
 }
 
 RM_EXPORT int rm_read_islands(rm_ctx* c, uint32_t* out_rows, uint64_t row_capacity, uint32_t* out_labels, void* out_mask,

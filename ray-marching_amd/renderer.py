@@ -549,24 +549,34 @@ class RayMarchingResources:
 
     def label_solid_grid(self, origin, step, shape, level=0.0):
         """label_solid on an exact lattice (origin, step, shape as sample_grid takes them)."""
-        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
-        counts = (C.c_uint64 * _ffi.RM_TOPO_COUNTS)()
-        stats = (C.c_uint64 * _ffi.RM_TOPO_STATS)()
-        self._check(self._L.rm_label_solid(self._h, fp(o), fp(s), nx, ny, nz, float(level), counts, _ffi.RM_TOPO_COUNTS, stats,
-                                           _ffi.RM_TOPO_STATS))
-        return self._read_topology(counts, stats, o, s, (nx, ny, nz))
+        return self._solid_grid_call(self._L.rm_label_solid, *_TOPO_OUTPUTS, origin, step, shape, level, None, self._read_topology)
 
     def label_occupancy(self, occupancy):
         """rm_label_occupancy: the topology of a caller's occupancy, indexed [k, j, i] (shape (nz, ny, nx); nonzero = inside): a
         numpy array of a one-byte type (bool, uint8, int8), or such a contiguous torch tensor on this context's GPU, read after
         the work queued on torch.cuda.current_stream().  The Topology's lattice is the unit lattice at the origin."""
+        return self._occupancy_call(self._L.rm_label_occupancy, *_TOPO_OUTPUTS, occupancy, None, self._read_topology)
+
+    # What the eight analyses of a lattice share (rm_label_*, rm_distance_*, rm_support_*, rm_islands_*): fn, the sizes and the names
+    # of its counts and statistics (a row of the _*_OUTPUTS below), `direction` -- None, or (up, r2, plate) as the caller gave
+    # them --, and result(counts, stats, origin, step, shape[, up, r2]), which takes both outputs as dicts.
+    def _solid_grid_call(self, fn, n_counts, n_stats, count_names, stat_names, origin, step, shape, level, direction, result):
+        """A *_solid_grid call: fn = rm_*_solid on an exact lattice."""
+        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
+        extra = _support_args(*direction) if direction else ()
+        counts, stats = (C.c_uint64 * n_counts)(), (C.c_uint64 * n_stats)()
+        self._check(fn(self._h, fp(o), fp(s), nx, ny, nz, float(level), *extra, counts, n_counts, stats, n_stats))
+        return result(_named(counts, count_names), _named(stats, stat_names), o, s, (nx, ny, nz), *extra[:2])
+
+    def _occupancy_call(self, fn, n_counts, n_stats, count_names, stat_names, occupancy, direction, result):
+        """A *_occupancy call: fn = rm_*_occupancy on a caller's occupancy; the result's lattice is the unit lattice."""
         nx, ny, nz, ptr, is_device, stream, keep = self._occupancy_arg(occupancy)
-        counts = (C.c_uint64 * _ffi.RM_TOPO_COUNTS)()
-        stats = (C.c_uint64 * _ffi.RM_TOPO_STATS)()
-        self._check(self._L.rm_label_occupancy(self._h, nx, ny, nz, ptr, is_device, stream, counts, _ffi.RM_TOPO_COUNTS, stats,
-                                               _ffi.RM_TOPO_STATS))
+        extra = _support_args(*direction) if direction else ()
+        counts, stats = (C.c_uint64 * n_counts)(), (C.c_uint64 * n_stats)()
+        self._check(fn(self._h, nx, ny, nz, ptr, is_device, stream, *extra, counts, n_counts, stats, n_stats))
         del keep
-        return self._read_topology(counts, stats, np.zeros(3, dtype=np.float32), np.ones(3, dtype=np.float32), (nx, ny, nz))
+        return result(_named(counts, count_names), _named(stats, stat_names), np.zeros(3, dtype=np.float32), np.ones(3, dtype=np.float32),
+                      (nx, ny, nz), *extra[:2])
 
     def _occupancy_arg(self, occupancy):
         """A caller's occupancy as the library takes it: nx, ny, nz, its address, is_device, the stream, and the object to keep
@@ -590,12 +600,10 @@ class RayMarchingResources:
             raise ValueError("a lattice needs at least 2 points per axis, not %s" % ((nx, ny, nz),))
         return nx, ny, nz, ptr, is_device, stream, keep
 
-    def _read_topology(self, counts, stats, origin, step, shape):
+    def _read_topology(self, cd, sd, origin, step, shape):
         """The Topology of the labelling call that just returned: its counts and statistics, and both row tables read back."""
-        cd = {name: int(counts[k]) for k, name in enumerate(_ffi.TOPO_COUNT_NAMES)}
         for name in ("euler", "tunnels"):                                    # two's-complement int64
             cd[name] -= (cd[name] >> 63) << 64
-        sd = {name: int(stats[k]) for k, name in enumerate(_ffi.TOPO_STAT_NAMES)}
         body = np.zeros((cd["bodies"], _ffi.RM_MOMENTS), dtype=np.uint64)
         cav = np.zeros((cd["cavities"], _ffi.RM_MOMENTS), dtype=np.uint64)
         ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
@@ -617,28 +625,14 @@ class RayMarchingResources:
 
     def distance_solid_grid(self, origin, step, shape, level=0.0):
         """distance_solid on an exact lattice (origin, step, shape as sample_grid takes them)."""
-        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
-        counts = (C.c_uint64 * _ffi.RM_DIST_COUNTS)()
-        stats = (C.c_uint64 * _ffi.RM_DIST_STATS)()
-        self._check(self._L.rm_distance_solid(self._h, fp(o), fp(s), nx, ny, nz, float(level), counts, _ffi.RM_DIST_COUNTS, stats,
-                                              _ffi.RM_DIST_STATS))
-        return self._distance(counts, stats, o, s, (nx, ny, nz))
+        return self._solid_grid_call(self._L.rm_distance_solid, *_DIST_OUTPUTS, origin, step, shape, level, None,
+                                     lambda *a: Distance(self, *a))
 
     def distance_occupancy(self, occupancy):
         """rm_distance_occupancy: the distance transform of a caller's occupancy, as label_occupancy takes it (indexed [k, j, i],
         nonzero = inside; numpy, or a torch tensor on this context's GPU).  The Distance's lattice is the unit lattice at the
         origin."""
-        nx, ny, nz, ptr, is_device, stream, keep = self._occupancy_arg(occupancy)
-        counts = (C.c_uint64 * _ffi.RM_DIST_COUNTS)()
-        stats = (C.c_uint64 * _ffi.RM_DIST_STATS)()
-        self._check(self._L.rm_distance_occupancy(self._h, nx, ny, nz, ptr, is_device, stream, counts, _ffi.RM_DIST_COUNTS, stats,
-                                                  _ffi.RM_DIST_STATS))
-        del keep
-        return self._distance(counts, stats, np.zeros(3, dtype=np.float32), np.ones(3, dtype=np.float32), (nx, ny, nz))
-
-    def _distance(self, counts, stats, origin, step, shape):
-        return Distance(self, {name: int(counts[k]) for k, name in enumerate(_ffi.DIST_COUNT_NAMES)},
-                        {name: int(stats[k]) for k, name in enumerate(_ffi.DIST_STAT_NAMES)}, origin, step, shape)
+        return self._occupancy_call(self._L.rm_distance_occupancy, *_DIST_OUTPUTS, occupancy, None, lambda *a: Distance(self, *a))
 
     def read_distance_device(self, d2_ptr=0, mask_ptr=0, stream=None):
         """rm_read_distance of the last distance volume and feature mask into device memory (integer addresses; 0 = not wanted),
@@ -657,30 +651,14 @@ class RayMarchingResources:
 
     def support_solid_grid(self, origin, step, shape, level=0.0, up="+z", r2=1, plate=None):
         """support_solid on an exact lattice (origin, step, shape as sample_grid takes them)."""
-        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
-        up, r2, plate = _support_args(up, r2, plate)
-        counts = (C.c_uint64 * _ffi.RM_SUP_COUNTS)()
-        stats = (C.c_uint64 * _ffi.RM_SUP_STATS)()
-        self._check(self._L.rm_support_solid(self._h, fp(o), fp(s), nx, ny, nz, float(level), up, r2, plate, counts, _ffi.RM_SUP_COUNTS,
-                                             stats, _ffi.RM_SUP_STATS))
-        return self._support(counts, stats, o, s, (nx, ny, nz), up, r2)
+        return self._solid_grid_call(self._L.rm_support_solid, *_SUP_OUTPUTS, origin, step, shape, level, (up, r2, plate),
+                                     lambda *a: Support(self, *a))
 
     def support_occupancy(self, occupancy, up="+z", r2=1, plate=None):
         """rm_support_occupancy: overhangs and supports of a caller's occupancy, as label_occupancy takes it (indexed [k, j, i],
         nonzero = inside; numpy, or a torch tensor on this context's GPU).  The Support's lattice is the unit lattice at the
         origin."""
-        nx, ny, nz, ptr, is_device, stream, keep = self._occupancy_arg(occupancy)
-        up, r2, plate = _support_args(up, r2, plate)
-        counts = (C.c_uint64 * _ffi.RM_SUP_COUNTS)()
-        stats = (C.c_uint64 * _ffi.RM_SUP_STATS)()
-        self._check(self._L.rm_support_occupancy(self._h, nx, ny, nz, ptr, is_device, stream, up, r2, plate, counts, _ffi.RM_SUP_COUNTS,
-                                                 stats, _ffi.RM_SUP_STATS))
-        del keep
-        return self._support(counts, stats, np.zeros(3, dtype=np.float32), np.ones(3, dtype=np.float32), (nx, ny, nz), up, r2)
-
-    def _support(self, counts, stats, origin, step, shape, up, r2):
-        return Support(self, {name: int(counts[k]) for k, name in enumerate(_ffi.SUP_COUNT_NAMES)},
-                       {name: int(stats[k]) for k, name in enumerate(_ffi.SUP_STAT_NAMES)}, origin, step, shape, up, r2)
+        return self._occupancy_call(self._L.rm_support_occupancy, *_SUP_OUTPUTS, occupancy, (up, r2, plate), lambda *a: Support(self, *a))
 
     def read_support_device(self, mask_ptr=0, profile_ptr=0, stream=None):
         """rm_read_support of the last mask and profile into device memory (integer addresses; 0 = not wanted), asynchronous."""
@@ -697,30 +675,14 @@ class RayMarchingResources:
 
     def islands_solid_grid(self, origin, step, shape, level=0.0, up="+z", r2=1, plate=None):
         """islands_solid on an exact lattice (origin, step, shape as sample_grid takes them)."""
-        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
-        up, r2, plate = _support_args(up, r2, plate)
-        counts = (C.c_uint64 * _ffi.RM_ISL_COUNTS)()
-        stats = (C.c_uint64 * _ffi.RM_ISL_STATS)()
-        self._check(self._L.rm_islands_solid(self._h, fp(o), fp(s), nx, ny, nz, float(level), up, r2, plate, counts, _ffi.RM_ISL_COUNTS,
-                                             stats, _ffi.RM_ISL_STATS))
-        return self._islands(counts, stats, o, s, (nx, ny, nz), up, r2)
+        return self._solid_grid_call(self._L.rm_islands_solid, *_ISL_OUTPUTS, origin, step, shape, level, (up, r2, plate),
+                                     lambda *a: Islands(self, *a))
 
     def islands_occupancy(self, occupancy, up="+z", r2=1, plate=None):
         """rm_islands_occupancy: layer regions and islands of a caller's occupancy, as label_occupancy takes it (indexed [k, j, i],
         nonzero = inside; numpy, or a torch tensor on this context's GPU).  The Islands' lattice is the unit lattice at the
         origin."""
-        nx, ny, nz, ptr, is_device, stream, keep = self._occupancy_arg(occupancy)
-        up, r2, plate = _support_args(up, r2, plate)
-        counts = (C.c_uint64 * _ffi.RM_ISL_COUNTS)()
-        stats = (C.c_uint64 * _ffi.RM_ISL_STATS)()
-        self._check(self._L.rm_islands_occupancy(self._h, nx, ny, nz, ptr, is_device, stream, up, r2, plate, counts, _ffi.RM_ISL_COUNTS,
-                                                 stats, _ffi.RM_ISL_STATS))
-        del keep
-        return self._islands(counts, stats, np.zeros(3, dtype=np.float32), np.ones(3, dtype=np.float32), (nx, ny, nz), up, r2)
-
-    def _islands(self, counts, stats, origin, step, shape, up, r2):
-        return Islands(self, {name: int(counts[k]) for k, name in enumerate(_ffi.ISL_COUNT_NAMES)},
-                       {name: int(stats[k]) for k, name in enumerate(_ffi.ISL_STAT_NAMES)}, origin, step, shape, up, r2)
+        return self._occupancy_call(self._L.rm_islands_occupancy, *_ISL_OUTPUTS, occupancy, (up, r2, plate), lambda *a: Islands(self, *a))
 
     def read_islands_device(self, rows_ptr=0, row_capacity=0, labels_ptr=0, mask_ptr=0, profile_ptr=0, stream=None):
         """rm_read_islands of the last region table (row_capacity rows of room), label volume, mask and profile into device memory
@@ -897,6 +859,17 @@ class RayMarchingCallback:
         W = int(self.viewport[0]) if width is None else width
         H = int(self.viewport[1]) if height is None else height
         return resources.draw(W, H)
+
+
+# The outputs of the lattice analyses (RayMarchingResources._solid_grid_call): how many counts and statistics, and their names.
+_TOPO_OUTPUTS = (_ffi.RM_TOPO_COUNTS, _ffi.RM_TOPO_STATS, _ffi.TOPO_COUNT_NAMES, _ffi.TOPO_STAT_NAMES)
+_DIST_OUTPUTS = (_ffi.RM_DIST_COUNTS, _ffi.RM_DIST_STATS, _ffi.DIST_COUNT_NAMES, _ffi.DIST_STAT_NAMES)
+_SUP_OUTPUTS = (_ffi.RM_SUP_COUNTS, _ffi.RM_SUP_STATS, _ffi.SUP_COUNT_NAMES, _ffi.SUP_STAT_NAMES)
+_ISL_OUTPUTS = (_ffi.RM_ISL_COUNTS, _ffi.RM_ISL_STATS, _ffi.ISL_COUNT_NAMES, _ffi.ISL_STAT_NAMES)
+
+
+def _named(words, names):
+    return {name: int(words[k]) for k, name in enumerate(names)}
 
 
 class MassMoments:
