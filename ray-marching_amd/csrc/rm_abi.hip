@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -151,40 +152,66 @@ struct rm_ctx {
     size_t max_lds = 0;  // LDS a workgroup may allocate on this device
     // lit rendering (rm_light.h): enum rm_light, validated by rm_set_lighting; travels with each lit draw as kernel arguments
     float light[RM_LIGHT_PARAMS] = RM_LIGHT_DEFAULTS;
-    // mesh export (rm_mesh.h): the extraction's scratch (distances, vertex bases, flags, block sums) and the last mesh
-    DevBuf<char> d_mscratch;
-    DevBuf<char> d_mbricks;  // sparse extraction (rm_mesh_sparse.h): the per-brick tables; d_mscratch holds the kept bricks' data
-    DevBuf<char> d_mesh;
-    bool mesh_valid = false;
-    uint64_t mesh_v = 0, mesh_t = 0;
-    uint32_t mesh_flags = 0;
-    // slicing (rm_slice.h): the per-vertex scratch of a batch of layers (its per-point scratch is d_mscratch), the small
-    // per-layer tables (heights, layer_first, the layers' first vertices, totals) and the last result, in buffers of its own
-    DevBuf<char> d_swork, d_slayers, d_spoints, d_scontours, d_sattr;
-    bool slice_valid = false;
-    uint64_t slice_p = 0, slice_c = 0;
-    uint32_t slice_layers = 0, slice_flags = 0;
-    // solid topology (rm_topology.h): the label volume and the components' rows of the last labelling, in buffers of their own
-    // (its scratch is d_mscratch)
-    DevBuf<char> d_tlabels, d_trows;
-    bool topo_valid = false;
-    uint64_t topo_n = 0, topo_b = 0, topo_c = 0;
-    // distance transform (rm_distance.h): the distance volume of the last distance call and the feature mask of the last features
-    // call on it, in buffers of their own (their scratch is d_mscratch)
-    DevBuf<char> d_dvol, d_dmask;
-    bool dist_valid = false, dist_mask_valid = false;
-    uint32_t dist_nx = 0, dist_ny = 0, dist_nz = 0;
-    // overhangs and supports (rm_support.h): the mask and the profile of the last support call, in buffers of their own (their
-    // scratch is d_mscratch)
-    DevBuf<char> d_smask, d_sprof;
-    bool sup_valid = false;
-    uint32_t sup_n = 0, sup_nh = 0;
-    // layer regions and islands (rm_islands.h): the label volume, the mask, the profile and the region table of the last islands
-    // call, in buffers of their own (their scratch is d_mscratch)
-    DevBuf<char> d_ilabels, d_imask, d_iprof, d_irows;
-    bool isl_valid = false;
-    uint32_t isl_n = 0, isl_nh = 0;
-    uint64_t isl_regions = 0;
+    // the scratch of the lattice calls (mesh, slices, mass and the analyses; none of it holds a result), and that of the sparse
+    // extraction's and the mass moments' per-brick tables (rm_mesh_sparse.h; d_mscratch then holds the kept bricks' data)
+    DevBuf<char> d_mscratch, d_mbricks;
+    // Retained results (DESIGN.md "Retained results"): what a call leaves behind for rm_read_*, one slot per family -- its own
+    // buffers, the dimensions a read needs, and `valid`, which only the slot's two operations write.  drop(): the previous result
+    // is gone; a call says so after its last check that can refuse, when its scratch is reserved and the slot's buffers start to
+    // change, not before.  commit(dims): the last statement of a successful call.
+    struct Mesh {  // rm_extract_mesh, rm_extract_mesh_sparse: the arrays of mesh_layout(v, t, flags) in buf
+        DevBuf<char> buf;
+        bool valid = false;
+        uint64_t v = 0, t = 0;
+        uint32_t flags = 0;
+        void drop() { valid = false; }
+        void commit(uint64_t v_, uint64_t t_, uint32_t flags_) { v = v_, t = t_, flags = flags_, valid = true; }
+    } mesh;
+    struct Slices {  // rm_slice_contours: points, contours, attributes (rml::SliceAttributes) and layer_first in the per-layer tables
+        DevBuf<char> points, contours, attr, layers;  // layers (rml::SliceLayerTables) also holds the call's small scratch
+        bool valid = false;
+        uint64_t p = 0, c = 0;
+        uint32_t n_layers = 0, flags = 0;
+        void drop() { valid = false; }
+        void commit(uint64_t p_, uint64_t c_, uint32_t n_layers_, uint32_t flags_) { p = p_, c = c_, n_layers = n_layers_, flags = flags_, valid = true; }
+    } slices;
+    DevBuf<char> d_swork;  // slicing (rm_slice.h): the per-vertex scratch of a batch of layers
+    struct Labels {  // rm_label_*: the label volume of n points and the rows (rml::TopoRows) of b bodies and c cavities
+        DevBuf<char> labels, rows;
+        bool valid = false;
+        uint64_t n = 0, b = 0, c = 0;
+        void drop() { valid = false; }
+        void commit(uint64_t n_, uint64_t b_, uint64_t c_) { n = n_, b = b_, c = c_, valid = true; }
+    } topo;
+    struct Distance {  // rm_distance_*: the distance volume, and nested the feature mask rm_distance_features made of it
+        DevBuf<char> vol;
+        bool valid = false;
+        uint32_t nx = 0, ny = 0, nz = 0;
+        struct Mask {
+            DevBuf<char> buf;
+            bool valid = false;
+            void drop() { valid = false; }
+            void commit() { valid = true; }
+        } mask;
+        size_t points() const { return (size_t)nx * ny * nz; }
+        void drop() { valid = false, mask.drop(); }
+        void commit(uint32_t nx_, uint32_t ny_, uint32_t nz_) { nx = nx_, ny = ny_, nz = nz_, valid = true; }
+    } dist;
+    struct Support {  // rm_support_*: the mask of n points and the profile (rml::SupportProfile) of nh layers
+        DevBuf<char> mask, profile;
+        bool valid = false;
+        uint32_t n = 0, nh = 0;
+        void drop() { valid = false; }
+        void commit(uint32_t n_, uint32_t nh_) { n = n_, nh = nh_, valid = true; }
+    } sup;
+    struct Islands {  // rm_islands_*: labels and mask of n points, the profile of nh layers, the table (rml::IslandsRows) of `regions`
+        DevBuf<char> labels, mask, profile, rows;
+        bool valid = false;
+        uint32_t n = 0, nh = 0;
+        uint64_t regions = 0;
+        void drop() { valid = false; }
+        void commit(uint32_t n_, uint32_t nh_, uint64_t regions_) { n = n_, nh = nh_, regions = regions_, valid = true; }
+    } isl;
     // scratch for host-destination draws and batch uniforms
     DevBuf<char> d_out;
     DevBuf<rm_uniforms> d_frames;
@@ -1062,6 +1089,32 @@ auto with_loop(int loop, F&& f) {
 // pairs of rm_query_points 8 B, the hit records and id quadruples of rm_cast_rays 16 B.  A pointer off that alignment is refused.
 bool misaligned(const void* p, uintptr_t align) { return p != nullptr && (reinterpret_cast<uintptr_t>(p) & (align - 1u)) != 0u; }
 
+// The one read path of the retained results: what every rm_read_* ends in once its own refusals are past.  A device
+// destination off an item's alignment is refused with the family's message; then the copies go out on the destination's
+// stream, ordered after the context's earlier work (the family's next producing call waits for this stream in turn) -- one per
+// item the caller wants (out) that holds anything (bytes) --, and a host destination waits for them.
+struct ReadItem {
+    void* out;
+    const void* src;
+    size_t bytes;
+    uintptr_t align;
+    ReadItem(void* out_, const void* src_, size_t bytes_, uintptr_t align_) : out(out_), src(src_), bytes(bytes_), align(align_) {}
+    template <class T>  // a region of the buffer at `base`
+    ReadItem(void* out_, const rml::Region<T>& r, const void* base, uintptr_t align_) : ReadItem(out_, r.at(base), r.bytes, align_) {}
+};
+int read_back(rm_ctx* c, int is_device, void* stream, const char* misaligned_message, std::initializer_list<ReadItem> items) {
+    for (const ReadItem& it : items)
+        if (is_device && misaligned(it.out, it.align)) return fail(c, RM_ERR_ARG, "%s", misaligned_message);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = dest_stream(c, is_device, stream);
+    order_with_previous(c, s);
+    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    for (const ReadItem& it : items)
+        if (it.out && it.bytes) HIP_TRY(c, hipMemcpyAsync(it.out, it.src, it.bytes, kind, s));
+    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
 // LDS dwords per lane of a wave's column: what the distance loop needs (value stack, then 3 floats per transform level) and,
 // with the leaf walk, the larger of that and the walk's ([depth] distances, [depth] pairs, 3 floats per transform level).
 uint32_t query_slots(const RmDecoded& d, int loop, bool walk) {
@@ -1575,7 +1628,7 @@ int check_iso(rm_ctx* c, const char* fn, float level, uint32_t flags) {
     return RM_OK;
 }
 
-// Where the arrays of a mesh of v vertices and t triangles lie in rm_ctx::d_mesh.
+// Where the arrays of a mesh of v vertices and t triangles lie in rm_ctx::mesh.buf.
 rml::MeshLayout mesh_layout(uint64_t v, uint64_t t, uint32_t flags) {
     return rml::MeshLayout(v, t, (flags & RM_MESH_NORMALS) != 0, (flags & RM_MESH_IDS) != 0);
 }
@@ -1649,13 +1702,11 @@ rmk::SparseGrid sparse_grid(const float* o, const float* st, uint32_t nx, uint32
 
 // What a call over the bricks of a lattice does after query_begin (which gave shmem): the LDS check of its workgroups (the
 // query's columns behind 4 KiB of their own), the bounds of the program for points up to the lattice's largest coordinate (as
-// the kernels compute it), the lattice in bricks.  result_valid, if given, is cleared once the LDS check has passed: the mesh's
-// buffers change from there on.
+// the kernels compute it), the lattice in bricks.
 int brick_lattice(rm_ctx* c, const char* fn, size_t shmem, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
-                  bool* result_valid, RmProgramBound* bound, rmk::SparseGrid* g) {
+                  RmProgramBound* bound, rmk::SparseGrid* g) {
     if (shmem + 4096u > std::max<size_t>(c->max_lds, 64u * 1024u))
         return fail(c, RM_ERR_TOO_LARGE, "%s: the program needs %zu bytes of LDS per workgroup", fn, shmem + 4096u);
-    if (result_valid) *result_valid = false;
     double P = 0.0;
     const uint32_t dims[3] = {nx, ny, nz};
     for (int a = 0; a < 3; a++) {
@@ -1716,7 +1767,7 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
     size_t shmem = 0;
     int rc = query_begin(c, s, (flags & RM_MESH_IDS) != 0, false, &Q, &loop, &shmem);  // after a device read of the previous mesh, too
     if (rc != RM_OK) return rc;
-    c->mesh_valid = false;  // its buffers change from here on
+    c->mesh.drop();
     const uint32_t n = (uint32_t)n64, nb = (n + rmk::kMeshBlock - 1u) / rmk::kMeshBlock;
     const rml::DenseMeshScratch S(n, nb);
     if ((rc = c->d_mscratch.reserve(c, S.bytes)) != RM_OK) return rc;
@@ -1736,8 +1787,8 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
     HIP_TRY(c, hipStreamSynchronize(s));
     const uint64_t V = tot[0], T = tot[1];
     const rml::MeshLayout L = mesh_layout(V, T, flags);
-    if ((rc = c->d_mesh.reserve(c, L.bytes)) != RM_OK) return rc;
-    char* m = c->d_mesh.p;
+    if ((rc = c->mesh.buf.reserve(c, L.bytes)) != RM_OK) return rc;
+    char* m = c->mesh.buf.p;
     float* verts = L.vertices.at(m);
     if (V > 0u) {
         const unsigned long long* offs = sums;
@@ -1750,12 +1801,9 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
         if ((rc = point_attributes(c, Q, loop, shmem, s, flags, V, verts, m, L.normals, L.ids)) != RM_OK) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
-    c->mesh_valid = true;
-    c->mesh_v = V;
-    c->mesh_t = T;
-    c->mesh_flags = flags;
     out_counts[0] = V;
     out_counts[1] = T;
+    c->mesh.commit(V, T, flags);
     return RM_OK;
 }
 
@@ -1786,7 +1834,8 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
     if (rc != RM_OK) return rc;
     RmProgramBound bound;
     rmk::SparseGrid g;
-    if ((rc = brick_lattice(c, "rm_extract_mesh_sparse", shmem, origin, step, nx, ny, nz, &c->mesh_valid, &bound, &g)) != RM_OK) return rc;
+    if ((rc = brick_lattice(c, "rm_extract_mesh_sparse", shmem, origin, step, nx, ny, nz, &bound, &g)) != RM_OK) return rc;
+    c->mesh.drop();  // (brick_lattice refuses at its LDS check only: the program's bound decodes what query_begin has decoded)
     if ((rc = count_bricks(c, "rm_extract_mesh_sparse", &g)) != RM_OK) return rc;
     // per brick: 4 B (keep flag, then the kept bricks before it); per 256 bricks a block sum; totals and the evaluation count
     const uint32_t n_entries = g.nb + 1u, n_pblocks = (n_entries + 255u) / 256u;
@@ -1843,8 +1892,8 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
             return fail(c, RM_ERR_RANGE, "rm_extract_mesh_sparse: %llu vertices and %llu triangles do not fit 32-bit indices",
                         (unsigned long long)V, (unsigned long long)T);
         L = mesh_layout(V, T, flags);
-        if ((rc = c->d_mesh.reserve(c, L.bytes)) != RM_OK) return rc;
-        char* m = c->d_mesh.p;
+        if ((rc = c->mesh.buf.reserve(c, L.bytes)) != RM_OK) return rc;
+        char* m = c->mesh.buf.p;
         if (V > 0u) {
             hipLaunchKernelGGL(rmk::rm_sparse_seg_scan_kernel, dim3(n_sblocks), dim3(256), 0, s, n_segs, static_cast<const uint32_t*>(words),
                                static_cast<const unsigned long long*>(ssums), first);
@@ -1857,16 +1906,13 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
         }
         HIP_TRY(c, hipStreamSynchronize(s));
     }
-    c->mesh_valid = true;
-    c->mesh_v = V;
-    c->mesh_t = T;
-    c->mesh_flags = flags;
     out_stats[RM_MESH_STAT_VERTICES] = V;
     out_stats[RM_MESH_STAT_TRIANGLES] = T;
     out_stats[RM_MESH_STAT_BRICKS] = g.nb;
     out_stats[RM_MESH_STAT_BRICKS_KEPT] = K;
     out_stats[RM_MESH_STAT_EVALUATIONS] = n_evals;
     out_stats[RM_MESH_STAT_SCRATCH_BYTES] = B.bytes + kept_bytes;
+    c->mesh.commit(V, T, flags);
     return RM_OK;
 }
 
@@ -1890,7 +1936,7 @@ RM_EXPORT int rm_mass_moments(rm_ctx* c, const float* origin, const float* step,
     if (rc != RM_OK) return rc;
     RmProgramBound bound;
     rmk::SparseGrid g;
-    if ((rc = brick_lattice(c, "rm_mass_moments", shmem, origin, step, nx, ny, nz, nullptr, &bound, &g)) != RM_OK) return rc;
+    if ((rc = brick_lattice(c, "rm_mass_moments", shmem, origin, step, nx, ny, nz, &bound, &g)) != RM_OK) return rc;
     if ((rc = count_bricks(c, "rm_mass_moments", &g)) != RM_OK) return rc;  // (<= 2^27 with 4096 points per axis)
     // the mesh's scratch buffers (neither holds a result): the brick tables, then the kept bricks' rows
     const uint32_t n_entries = g.nb + 1u, n_pblocks = (n_entries + 255u) / 256u;
@@ -2054,7 +2100,7 @@ struct OccupancySource {
         }
         int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);
         if (rc != RM_OK) return rc;
-        return brick_lattice(c, fn, shmem, origin, step, nx, ny, nz, nullptr, &bound, g);
+        return brick_lattice(c, fn, shmem, origin, step, nx, ny, nz, &bound, g);
     }
 
     // The occupancy into S.occ.  A solid (rm_topology.h): probe, scan of the block sums (kept low, inside high -> ptot),
@@ -2145,9 +2191,8 @@ int label_lattice(rm_ctx* c, const char* fn, hipStream_t s, const TopoGrid& G, c
     unsigned long long* rsums = T.rsums.at(sc);
     unsigned long long* rtot = T.rtot.at(sc);
     unsigned long long* result = T.result.at(sc);
-    int rc = c->d_tlabels.reserve(c, (size_t)G.n * 4u, "label volume");
-    if (rc != RM_OK) return rc;
-    uint32_t* labels = c->d_tlabels.as<uint32_t>();
+    int rc = RM_OK;
+    uint32_t* labels = c->topo.labels.as<uint32_t>();
     const uint32_t point_blocks = (G.n + 255u) / 256u;
     unsigned long long row[RM_MOMENTS];
     // the bricks' rows -> result: 256 rows to a workgroup, then the mass reducer over the folded ones
@@ -2186,14 +2231,14 @@ int label_lattice(rm_ctx* c, const char* fn, hipStream_t s, const TopoGrid& G, c
     const uint64_t B = tot[0], C = tot[1];
     const rml::TopoRows R(B, C);
     if (R.bytes > 0u) {
-        if ((rc = c->d_trows.reserve(c, R.bytes, "component rows")) != RM_OK) return rc;
+        if ((rc = c->topo.rows.reserve(c, R.bytes, "component rows")) != RM_OK) return rc;
         hipLaunchKernelGGL(rmk::rm_topo_rows_init_kernel, dim3((uint32_t)(((B + C) * rmk::kMoments + 255u) / 256u)), dim3(256), 0, s,
-                           (uint32_t)(B + C), R.bodies.at(c->d_trows.p));
+                           (uint32_t)(B + C), R.bodies.at(c->topo.rows.p));
     }
     hipLaunchKernelGGL(rmk::rm_topo_rank_kernel, dim3(G.n_rblocks), dim3(256), 0, s, G.n, occ, static_cast<const uint32_t*>(parent),
                        static_cast<const uint8_t*>(ext), static_cast<const unsigned long long*>(rsums), labels);
     hipLaunchKernelGGL(rmk::rm_topo_rows_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, static_cast<const uint32_t*>(parent), labels, (uint32_t)B,
-                       R.bodies.at(c->d_trows.p), rows);
+                       R.bodies.at(c->topo.rows.p), rows);
     reduce_rows();
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(row, result, sizeof row, hipMemcpyDeviceToHost, s));
@@ -2210,10 +2255,7 @@ int label_lattice(rm_ctx* c, const char* fn, hipStream_t s, const TopoGrid& G, c
     counts[RM_TOPO_TUNNELS] = (uint64_t)((int64_t)B + (int64_t)C - euler);
     counts[RM_TOPO_EXTERIOR_POINTS] = row[4];
     *merge_passes = passes;
-    c->topo_valid = true;
-    c->topo_n = G.n;
-    c->topo_b = B;
-    c->topo_c = C;
+    c->topo.commit(G.n, B, C);
     return RM_OK;
 }
 
@@ -2222,10 +2264,10 @@ struct LabelAnalysis {
     static constexpr const char *kCountsName = "RM_TOPO_COUNTS", *kStatsName = "RM_TOPO_STATS";
     int check(rm_ctx* c, const char* fn, uint32_t nx, uint32_t ny, uint32_t nz) const { return check_topo_lattice(c, fn, nx, ny, nz); }
     rml::TopoScratch layout(const TopoGrid& G) const { return rml::TopoScratch(G.n, G.g.nb, G.n_pblocks, G.n_rblocks); }
-    int reserve(rm_ctx* c, const TopoGrid&, const rml::TopoScratch& T) const {
-        const int rc = c->d_mscratch.reserve(c, T.bytes);
-        if (rc == RM_OK) c->topo_valid = false;  // its buffers change from here on
-        return rc;
+    int reserve(rm_ctx* c, const TopoGrid& G, const rml::TopoScratch& T) const {
+        if (int rc = c->d_mscratch.reserve(c, T.bytes)) return rc;
+        c->topo.drop();
+        return c->topo.labels.reserve(c, (size_t)G.n * 4u, "label volume");
     }
     int run(rm_ctx* c, const char* fn, hipStream_t s, const TopoGrid& G, const rml::TopoScratch& T, uint64_t* counts, uint64_t* stats) const {
         return label_lattice(c, fn, s, G, T, counts, &stats[RM_TOPO_STAT_MERGE_PASSES]);
@@ -2249,20 +2291,12 @@ RM_EXPORT int rm_label_occupancy(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t n
 RM_EXPORT int rm_read_topology(rm_ctx* c, uint64_t* out_body_moments, uint64_t* out_cavity_moments, uint32_t* out_labels, int is_device,
                                void* stream) {
     if (!c) return RM_ERR_NULL;
-    if (!c->topo_valid) return fail(c, RM_ERR_ARG, "rm_read_topology: nothing has been labelled");
-    if (is_device && (misaligned(out_body_moments, 8) || misaligned(out_cavity_moments, 8) || misaligned(out_labels, 4)))
-        return fail(c, RM_ERR_ARG, "rm_read_topology: device arrays need 8-byte alignment (out_labels: 4-byte)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = dest_stream(c, is_device, stream);
-    order_with_previous(c, s);  // (the next labelling call waits for this stream in turn)
-    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const rml::TopoRows R(c->topo_b, c->topo_c);
-    const char* rows = c->d_trows.p;
-    if (out_body_moments && R.bodies.bytes) HIP_TRY(c, hipMemcpyAsync(out_body_moments, R.bodies.at(rows), R.bodies.bytes, kind, s));
-    if (out_cavity_moments && R.cavities.bytes) HIP_TRY(c, hipMemcpyAsync(out_cavity_moments, R.cavities.at(rows), R.cavities.bytes, kind, s));
-    if (out_labels) HIP_TRY(c, hipMemcpyAsync(out_labels, c->d_tlabels.p, (size_t)c->topo_n * 4u, kind, s));
-    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+    const rm_ctx::Labels& r = c->topo;
+    if (!r.valid) return fail(c, RM_ERR_ARG, "rm_read_topology: nothing has been labelled");
+    const rml::TopoRows R(r.b, r.c);
+    return read_back(c, is_device, stream, "rm_read_topology: device arrays need 8-byte alignment (out_labels: 4-byte)",
+                     {{out_body_moments, R.bodies, r.rows.p, 8}, {out_cavity_moments, R.cavities, r.rows.p, 8},
+                      {out_labels, r.labels.p, (size_t)r.n * 4u, 4}});
 }
 
 // ---- distance transform (rm_distance.h) ----
@@ -2306,7 +2340,7 @@ int dist_reduce(rm_ctx* c, hipStream_t s, const DistBlocks& D, const unsigned lo
 int distance_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rml::DistScratch& S, uint64_t* counts) {
     const rmk::SparseGrid& g = G.g;
     char* sc = c->d_mscratch.p;
-    uint32_t* vol = c->d_dvol.as<uint32_t>();
+    uint32_t* vol = c->dist.vol.as<uint32_t>();
     const DistBlocks D(G.n);
     const uint32_t n_rows = g.ny * g.nz;
     hipLaunchKernelGGL(rmk::rm_dist_row_kernel<rmk::DIST_FROM_OCCUPANCY>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, g.nx, n_rows,
@@ -2320,10 +2354,7 @@ int distance_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rml::Dis
     counts[RM_DIST_ARGMAX_INSIDE] = ~row[13] & 0xFFFFFFFFull;
     counts[RM_DIST_MAX_OUTSIDE] = row[14] >> 32;
     counts[RM_DIST_ARGMAX_OUTSIDE] = ~row[14] & 0xFFFFFFFFull;
-    c->dist_valid = true;
-    c->dist_nx = g.nx;
-    c->dist_ny = g.ny;
-    c->dist_nz = g.nz;
+    c->dist.commit(g.nx, g.ny, g.nz);
     return RM_OK;
 }
 
@@ -2336,10 +2367,9 @@ struct DistanceAnalysis {
         return rml::DistScratch(G.n, G.g.nb, G.n_pblocks, D.n_rblocks, D.n_fblocks);
     }
     int reserve(rm_ctx* c, const TopoGrid& G, const rml::DistScratch& S) const {
-        const int rc = c->d_mscratch.reserve(c, S.bytes);
-        if (rc != RM_OK) return rc;
-        c->dist_valid = c->dist_mask_valid = false;  // its buffers change from here on
-        return c->d_dvol.reserve(c, (size_t)G.n * 4u, "distance volume");
+        if (int rc = c->d_mscratch.reserve(c, S.bytes)) return rc;
+        c->dist.drop();  // (the mask of the previous volume with it)
+        return c->dist.vol.reserve(c, (size_t)G.n * 4u, "distance volume");
     }
     int run(rm_ctx* c, const char*, hipStream_t s, const TopoGrid& G, const rml::DistScratch& S, uint64_t* counts, uint64_t*) const {
         return distance_lattice(c, s, G, S, counts);
@@ -2365,23 +2395,23 @@ RM_EXPORT int rm_distance_features(rm_ctx* c, uint32_t r2_wall, uint32_t r2_gap,
     if (!out_counts) return fail(c, RM_ERR_NULL, "rm_distance_features: out_counts is NULL");
     if (n_counts < (uint32_t)RM_DIST_FEATURE_COUNTS)
         return fail(c, RM_ERR_ARG, "rm_distance_features: n_counts %u < RM_DIST_FEATURE_COUNTS", n_counts);
-    if (!c->dist_valid) return fail(c, RM_ERR_ARG, "rm_distance_features: no distance volume has been computed");
+    if (!c->dist.valid) return fail(c, RM_ERR_ARG, "rm_distance_features: no distance volume has been computed");
     if ((r2_wall != RM_DIST_SKIP && r2_wall >= kMaxDistR2) || (r2_gap != RM_DIST_SKIP && r2_gap >= kMaxDistR2))
         return fail(c, RM_ERR_RANGE, "rm_distance_features: r2_wall %u, r2_gap %u: below 2^22, or RM_DIST_SKIP", r2_wall, r2_gap);
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = c->stream;
     order_with_previous(c, s);  // after a device read of the last mask, too
-    const TopoGrid G = topo_grid(sparse_grid(kUnitOrigin, kUnitStep, c->dist_nx, c->dist_ny, c->dist_nz));
+    const TopoGrid G = topo_grid(sparse_grid(kUnitOrigin, kUnitStep, c->dist.nx, c->dist.ny, c->dist.nz));
     const rmk::SparseGrid& g = G.g;
     const DistBlocks D(G.n);
     const rml::DistFeatureScratch S(G.n, D.n_rblocks, D.n_fblocks);
     int rc = c->d_mscratch.reserve(c, S.bytes);
     if (rc != RM_OK) return rc;
-    c->dist_mask_valid = false;  // the mask changes from here on
-    if ((rc = c->d_dmask.reserve(c, G.n, "feature mask")) != RM_OK) return rc;
+    c->dist.mask.drop();
+    if ((rc = c->dist.mask.buf.reserve(c, G.n, "feature mask")) != RM_OK) return rc;
     char* sc = c->d_mscratch.p;
-    const uint32_t* vol = c->d_dvol.as<uint32_t>();
-    uint8_t* mask = reinterpret_cast<uint8_t*>(c->d_dmask.p);
+    const uint32_t* vol = c->dist.vol.as<uint32_t>();
+    uint8_t* mask = c->dist.mask.buf.as<uint8_t>();
     uint32_t* feat = S.feat.at(sc);
     const uint32_t n_rows = g.ny * g.nz;
     hipLaunchKernelGGL(rmk::rm_dist_mask_init_kernel, dim3((G.n + 255u) / 256u), dim3(256), 0, s, G.n, vol, mask);
@@ -2410,24 +2440,17 @@ RM_EXPORT int rm_distance_features(rm_ctx* c, uint32_t r2_wall, uint32_t r2_gap,
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(s));
     for (int k = 0; k < RM_DIST_FEATURE_COUNTS; k++) out_counts[k] = counts[k];
-    c->dist_mask_valid = true;
+    c->dist.mask.commit();
     return RM_OK;
 }
 
 RM_EXPORT int rm_read_distance(rm_ctx* c, uint32_t* out_d2, void* out_mask, int is_device, void* stream) {
     if (!c) return RM_ERR_NULL;
-    if (!c->dist_valid) return fail(c, RM_ERR_ARG, "rm_read_distance: no distance volume has been computed");
-    if (out_mask && !c->dist_mask_valid) return fail(c, RM_ERR_ARG, "rm_read_distance: rm_distance_features has made no mask of this volume");
-    if (is_device && misaligned(out_d2, 4)) return fail(c, RM_ERR_ARG, "rm_read_distance: a device out_d2 needs 4-byte alignment");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = dest_stream(c, is_device, stream);
-    order_with_previous(c, s);  // (the next distance call waits for this stream in turn)
-    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const size_t n = (size_t)c->dist_nx * c->dist_ny * c->dist_nz;
-    if (out_d2) HIP_TRY(c, hipMemcpyAsync(out_d2, c->d_dvol.p, n * 4u, kind, s));
-    if (out_mask) HIP_TRY(c, hipMemcpyAsync(out_mask, c->d_dmask.p, n, kind, s));
-    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+    const rm_ctx::Distance& r = c->dist;
+    if (!r.valid) return fail(c, RM_ERR_ARG, "rm_read_distance: no distance volume has been computed");
+    if (out_mask && !r.mask.valid) return fail(c, RM_ERR_ARG, "rm_read_distance: rm_distance_features has made no mask of this volume");
+    return read_back(c, is_device, stream, "rm_read_distance: a device out_d2 needs 4-byte alignment",
+                     {{out_d2, r.vol.p, r.points() * 4u, 4}, {out_mask, r.mask.buf.p, r.points(), 1}});
 }
 
 // ---- overhangs and supports (rm_support.h) ----
@@ -2501,8 +2524,8 @@ int support_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
                     uint32_t plate, uint64_t* counts) {
     char* sc = c->d_mscratch.p;
     const rml::SupportProfile R(f.nh);
-    char* pr = c->d_sprof.p;
-    uint8_t* mask = reinterpret_cast<uint8_t*>(c->d_smask.p);
+    char* pr = c->sup.profile.p;
+    uint8_t* mask = c->sup.mask.as<uint8_t>();
     unsigned long long *ins = S.ins.at(sc), *ov = S.ov.at(sc), *sup = S.sup.at(sc), *plt = S.plt.at(sc);
     uint32_t* h0w = S.plate.at(sc);
     const uint32_t ncw = f.nv * f.nw;
@@ -2543,9 +2566,7 @@ int support_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
     }
     counts[RM_SUP_PLATE] = h0;
     counts[RM_SUP_BASE] = rows[4u * h0];
-    c->sup_valid = true;
-    c->sup_n = G.n;
-    c->sup_nh = f.nh;
+    c->sup.commit(G.n, f.nh);
     return RM_OK;
 }
 
@@ -2565,13 +2586,11 @@ struct SupportAnalysis : DirectedAnalysis {
         f = sup_frame(G.g.nx, G.g.ny, G.g.nz, up);
         return rml::SupportScratch(G.n, G.g.nb, G.n_pblocks, sup_plane_words(f));
     }
-    // The buffers of a support call: scratch, mask and profile.  The last result is gone once the scratch is reserved.
     int reserve(rm_ctx* c, const TopoGrid& G, const rml::SupportScratch& S) const {
-        int rc = c->d_mscratch.reserve(c, S.bytes);
-        if (rc != RM_OK) return rc;
-        c->sup_valid = false;
-        if ((rc = c->d_smask.reserve(c, G.n, "support mask")) != RM_OK) return rc;
-        return c->d_sprof.reserve(c, rml::SupportProfile(f.nh).bytes, "support profile");
+        if (int rc = c->d_mscratch.reserve(c, S.bytes)) return rc;
+        c->sup.drop();
+        if (int rc = c->sup.mask.reserve(c, G.n, "support mask")) return rc;
+        return c->sup.profile.reserve(c, rml::SupportProfile(f.nh).bytes, "support profile");
     }
     int run(rm_ctx* c, const char*, hipStream_t s, const TopoGrid& G, const rml::SupportScratch& S, uint64_t* counts, uint64_t*) const {
         return support_lattice(c, s, G, f, S, r2, plate, counts);
@@ -2596,17 +2615,10 @@ RM_EXPORT int rm_support_occupancy(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t
 
 RM_EXPORT int rm_read_support(rm_ctx* c, void* out_mask, uint32_t* out_profile, int is_device, void* stream) {
     if (!c) return RM_ERR_NULL;
-    if (!c->sup_valid) return fail(c, RM_ERR_ARG, "rm_read_support: no support call has been made");
-    if (is_device && misaligned(out_profile, 4)) return fail(c, RM_ERR_ARG, "rm_read_support: a device out_profile needs 4-byte alignment");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = dest_stream(c, is_device, stream);
-    order_with_previous(c, s);  // (the next support call waits for this stream in turn)
-    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (out_mask) HIP_TRY(c, hipMemcpyAsync(out_mask, c->d_smask.p, c->sup_n, kind, s));
-    if (out_profile)
-        HIP_TRY(c, hipMemcpyAsync(out_profile, rml::SupportProfile(c->sup_nh).profile.at(c->d_sprof.p), (size_t)c->sup_nh * 16u, kind, s));
-    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+    const rm_ctx::Support& r = c->sup;
+    if (!r.valid) return fail(c, RM_ERR_ARG, "rm_read_support: no support call has been made");
+    return read_back(c, is_device, stream, "rm_read_support: a device out_profile needs 4-byte alignment",
+                     {{out_mask, r.mask.p, r.n, 1}, {out_profile, rml::SupportProfile(r.nh).profile.at(r.profile.p), (size_t)r.nh * 16u, 4}});
 }
 
 // ---- layer regions and islands (rm_islands.h) ----
@@ -2634,7 +2646,7 @@ int islands_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
     char* sc = c->d_mscratch.p;
     unsigned long long *ins = S.ins.at(sc), *ov = S.ov.at(sc), *rsums = S.rsums.at(sc), *rtot = S.rtot.at(sc);
     uint32_t *h0w = S.plate.at(sc), *parent = S.parent.at(sc), *lab = S.lab.at(sc), *lbase = S.lbase.at(sc), *totals = S.totals.at(sc);
-    uint32_t* prof = c->d_iprof.as<uint32_t>();
+    uint32_t* prof = c->isl.profile.as<uint32_t>();
     const auto cins = static_cast<const unsigned long long*>(ins);
     const auto cov = static_cast<const unsigned long long*>(ov);
     const auto ch0 = static_cast<const uint32_t*>(h0w);
@@ -2656,8 +2668,8 @@ int islands_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
     const rml::IslandsRows T(R);
     uint32_t* rows = nullptr;
     if (R != 0u) {
-        if (int rc = c->d_irows.reserve(c, T.bytes, "region table")) return rc;
-        rows = T.rows.at(c->d_irows.p);
+        if (int rc = c->isl.rows.reserve(c, T.bytes, "region table")) return rc;
+        rows = T.rows.at(c->isl.rows.p);
         hipLaunchKernelGGL(rmk::rm_isl_rows_init_kernel, dim3((uint32_t)((R * rmk::kIslRowWords + 255u) / 256u)), dim3(256), 0, s,
                            (uint32_t)(R * rmk::kIslRowWords), rows);
     }
@@ -2673,7 +2685,7 @@ int islands_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
     hipLaunchKernelGGL(rmk::rm_isl_finish_kernel, dim3((uint32_t)((std::max<uint64_t>(R, f.nh) + 255u) / 256u)), dim3(256), 0, s, (uint32_t)R, f.nh,
                        plate, ch0, static_cast<const uint32_t*>(lbase), rows, prof, totals);
     hipLaunchKernelGGL(rmk::rm_isl_compose_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, up >> 1, G.g.nx, G.g.ny, G.n, plate, ch0, cins, clab,
-                       static_cast<const uint32_t*>(rows), c->d_ilabels.as<uint32_t>(), reinterpret_cast<uint8_t*>(c->d_imask.p));
+                       static_cast<const uint32_t*>(rows), c->isl.labels.as<uint32_t>(), c->isl.mask.as<uint8_t>());
     HIP_TRY(c, hipGetLastError());
     std::vector<uint32_t> layers((size_t)f.nh * 4u);
     uint32_t h0 = 0u, merges = 0u;
@@ -2693,10 +2705,7 @@ int islands_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
     counts[RM_ISL_REGIONS] = R;
     counts[RM_ISL_BASE_REGIONS] = layers[4u * h0 + 1u];
     counts[RM_ISL_MERGES] = merges;
-    c->isl_valid = true;
-    c->isl_n = G.n;
-    c->isl_nh = f.nh;
-    c->isl_regions = R;
+    c->isl.commit(G.n, f.nh, R);
     return RM_OK;
 }
 
@@ -2709,15 +2718,12 @@ struct IslandsAnalysis : DirectedAnalysis {
         const IslandsPlan P(G, f);
         return rml::IslandsScratch(G.n, G.g.nb, G.n_pblocks, P.n_words, P.n_rblocks, f.nh);
     }
-    // The buffers of an islands call: scratch, labels, mask and profile (the region table follows the count).  The last result is
-    // gone once the scratch is reserved.
-    int reserve(rm_ctx* c, const TopoGrid& G, const rml::IslandsScratch& S) const {
-        int rc = c->d_mscratch.reserve(c, S.bytes);
-        if (rc != RM_OK) return rc;
-        c->isl_valid = false;
-        if ((rc = c->d_ilabels.reserve(c, (size_t)G.n * 4u, "region labels")) != RM_OK) return rc;
-        if ((rc = c->d_imask.reserve(c, G.n, "island mask")) != RM_OK) return rc;
-        return c->d_iprof.reserve(c, (size_t)f.nh * 16u, "region profile");
+    int reserve(rm_ctx* c, const TopoGrid& G, const rml::IslandsScratch& S) const {  // (the region table follows the count)
+        if (int rc = c->d_mscratch.reserve(c, S.bytes)) return rc;
+        c->isl.drop();
+        if (int rc = c->isl.labels.reserve(c, (size_t)G.n * 4u, "region labels")) return rc;
+        if (int rc = c->isl.mask.reserve(c, G.n, "island mask")) return rc;
+        return c->isl.profile.reserve(c, (size_t)f.nh * 16u, "region profile");
     }
     int run(rm_ctx* c, const char*, hipStream_t s, const TopoGrid& G, const rml::IslandsScratch& S, uint64_t* counts, uint64_t*) const {
         return islands_lattice(c, s, G, f, S, up, r2, plate, counts);
@@ -2743,46 +2749,27 @@ RM_EXPORT int rm_islands_occupancy(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t
 RM_EXPORT int rm_read_islands(rm_ctx* c, uint32_t* out_rows, uint64_t row_capacity, uint32_t* out_labels, void* out_mask,
                               uint32_t* out_profile, int is_device, void* stream) {
     if (!c) return RM_ERR_NULL;
-    if (!c->isl_valid) return fail(c, RM_ERR_ARG, "rm_read_islands: no islands call has been made");
-    if (out_rows && row_capacity < c->isl_regions)
+    const rm_ctx::Islands& r = c->isl;
+    if (!r.valid) return fail(c, RM_ERR_ARG, "rm_read_islands: no islands call has been made");
+    if (out_rows && row_capacity < r.regions)
         return fail(c, RM_ERR_RANGE, "rm_read_islands: row_capacity %llu < %llu regions", (unsigned long long)row_capacity,
-                    (unsigned long long)c->isl_regions);
-    if (is_device && (misaligned(out_rows, 4) || misaligned(out_labels, 4) || misaligned(out_profile, 4)))
-        return fail(c, RM_ERR_ARG, "rm_read_islands: device out_rows, out_labels and out_profile need 4-byte alignment");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = dest_stream(c, is_device, stream);
-    order_with_previous(c, s);  // (the next islands call waits for this stream in turn)
-    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const rml::IslandsRows T(c->isl_regions);
-    if (out_rows && T.rows.bytes) HIP_TRY(c, hipMemcpyAsync(out_rows, T.rows.at(c->d_irows.p), T.rows.bytes, kind, s));
-    if (out_labels) HIP_TRY(c, hipMemcpyAsync(out_labels, c->d_ilabels.p, (size_t)c->isl_n * 4u, kind, s));
-    if (out_mask) HIP_TRY(c, hipMemcpyAsync(out_mask, c->d_imask.p, c->isl_n, kind, s));
-    if (out_profile) HIP_TRY(c, hipMemcpyAsync(out_profile, c->d_iprof.p, (size_t)c->isl_nh * 16u, kind, s));
-    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+                    (unsigned long long)r.regions);
+    return read_back(c, is_device, stream, "rm_read_islands: device out_rows, out_labels and out_profile need 4-byte alignment",
+                     {{out_rows, rml::IslandsRows(r.regions).rows, r.rows.p, 4}, {out_labels, r.labels.p, (size_t)r.n * 4u, 4},
+                      {out_mask, r.mask.p, r.n, 1}, {out_profile, r.profile.p, (size_t)r.nh * 16u, 4}});
 }
 
 RM_EXPORT int rm_read_mesh(rm_ctx* c, float* out_vertices, uint32_t* out_triangles, float* out_normals, uint32_t* out_ids,
                            int is_device, void* stream) {
     if (!c) return RM_ERR_NULL;
-    if (!c->mesh_valid) return fail(c, RM_ERR_ARG, "rm_read_mesh: no mesh has been extracted");
-    if (out_normals && !(c->mesh_flags & RM_MESH_NORMALS))
-        return fail(c, RM_ERR_ARG, "rm_read_mesh: the mesh was extracted without RM_MESH_NORMALS");
-    if (out_ids && !(c->mesh_flags & RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_read_mesh: the mesh was extracted without RM_MESH_IDS");
-    if (is_device && (misaligned(out_vertices, 4) || misaligned(out_triangles, 4) || misaligned(out_normals, 4) || misaligned(out_ids, 8)))
-        return fail(c, RM_ERR_ARG, "rm_read_mesh: device arrays need 4-byte alignment (out_ids: 8-byte)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = dest_stream(c, is_device, stream);
-    order_with_previous(c, s);  // (the next extraction waits for this stream in turn)
-    const rml::MeshLayout L = mesh_layout(c->mesh_v, c->mesh_t, c->mesh_flags);
-    const char* m = c->d_mesh.p;
-    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (out_vertices && L.vertices.bytes) HIP_TRY(c, hipMemcpyAsync(out_vertices, L.vertices.at(m), L.vertices.bytes, kind, s));
-    if (out_triangles && L.triangles.bytes) HIP_TRY(c, hipMemcpyAsync(out_triangles, L.triangles.at(m), L.triangles.bytes, kind, s));
-    if (out_normals && L.normals.bytes) HIP_TRY(c, hipMemcpyAsync(out_normals, L.normals.at(m), L.normals.bytes, kind, s));
-    if (out_ids && L.ids.bytes) HIP_TRY(c, hipMemcpyAsync(out_ids, L.ids.at(m), L.ids.bytes, kind, s));
-    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+    const rm_ctx::Mesh& r = c->mesh;
+    if (!r.valid) return fail(c, RM_ERR_ARG, "rm_read_mesh: no mesh has been extracted");
+    if (out_normals && !(r.flags & RM_MESH_NORMALS)) return fail(c, RM_ERR_ARG, "rm_read_mesh: the mesh was extracted without RM_MESH_NORMALS");
+    if (out_ids && !(r.flags & RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_read_mesh: the mesh was extracted without RM_MESH_IDS");
+    const rml::MeshLayout L = mesh_layout(r.v, r.t, r.flags);
+    const char* m = r.buf.p;
+    return read_back(c, is_device, stream, "rm_read_mesh: device arrays need 4-byte alignment (out_ids: 8-byte)",
+                     {{out_vertices, L.vertices, m, 4}, {out_triangles, L.triangles, m, 4}, {out_normals, L.normals, m, 4}, {out_ids, L.ids, m, 8}});
 }
 
 RM_EXPORT int rm_mesh_case_table(uint32_t* out, uint32_t n_out) {
@@ -2833,12 +2820,12 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
     size_t shmem = 0;
     int rc = query_begin(c, s, (flags & RM_MESH_IDS) != 0, false, &Q, &loop, &shmem);  // after a device read of the previous slices, too
     if (rc != RM_OK) return rc;
-    c->slice_valid = false;  // its buffers change from here on
+    c->slices.drop();
     const uint32_t n2 = (uint32_t)n2_64, per = std::min(n_layers, std::max(1u, rmk::kSliceBatchPoints / n2));
     const uint32_t n_max = per * n2, nb_max = blocks_of(n_max, rmk::kSliceBlock);
     const rml::SliceLayerTables T(n_layers, per);
-    if ((rc = c->d_slayers.reserve(c, T.bytes)) != RM_OK) return rc;
-    char* lt = c->d_slayers.p;
+    if ((rc = c->slices.layers.reserve(c, T.bytes)) != RM_OK) return rc;
+    char* lt = c->slices.layers.p;
     float* d_heights = T.heights.at(lt);
     uint32_t* d_lf = T.layer_first.at(lt);
     uint32_t* d_base = T.base.at(lt);
@@ -2890,7 +2877,7 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
         uint32_t* vsums = Wk.vsums.at(wk);
         uint32_t* length = Wk.length.at(wk);
         uint32_t* first_point = Wk.first_point.at(wk);
-        if ((rc = c->d_spoints.grow_keep(c, (size_t)(P + V) * 12u, (size_t)P * 12u, s)) != RM_OK) return rc;
+        if ((rc = c->slices.points.grow_keep(c, (size_t)(P + V) * 12u, (size_t)P * 12u, s)) != RM_OK) return rc;
         HIP_TRY(c, hipMemsetAsync(wk, 0xFF, Wk.state0.offset, s));  // next and prev: kSliceNil
         hipLaunchKernelGGL(rmk::rm_slice_link_kernel, dim3(pb), dim3(256), 0, s, g, static_cast<const uint32_t*>(packed), next, prev);
         hipLaunchKernelGGL(rmk::rm_slice_low_init_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint32_t*>(next), V, st_a);
@@ -2914,7 +2901,7 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
         HIP_TRY(c, hipStreamSynchronize(s));
         if (Cb > c_max) return fail(c, RM_ERR_DEVICE, "rm_slice_contours: %u contours from %u vertices", Cb, V);
         if (Cn + Cb > 0xFFFFFFFFull) return fail(c, RM_ERR_RANGE, "rm_slice_contours: more than 2^32 - 1 contours");
-        if ((rc = c->d_scontours.grow_keep(c, (size_t)(Cn + Cb) * 16u, (size_t)Cn * 16u, s)) != RM_OK) return rc;
+        if ((rc = c->slices.contours.grow_keep(c, (size_t)(Cn + Cb) * 16u, (size_t)Cn * 16u, s)) != RM_OK) return rc;
         const uint32_t cb = blocks_of(Cb, rmk::kSliceBlock);
         hipLaunchKernelGGL(rmk::rm_slice_length_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint2*>(st_a),
                            static_cast<const uint32_t*>(next), static_cast<const uint32_t*>(start), V, length);
@@ -2927,8 +2914,8 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
         hipLaunchKernelGGL(rmk::rm_slice_emit_kernel, dim3(pb), dim3(256), 0, s, g, level, static_cast<const float*>(dist),
                            static_cast<const float*>(d_heights), static_cast<const uint32_t*>(packed), static_cast<const uint2*>(st_a),
                            static_cast<const uint32_t*>(start), static_cast<const uint32_t*>(length),
-                           static_cast<const uint32_t*>(first_point), (uint32_t)P, (uint32_t)Cn, c->d_spoints.as<float>(),
-                           c->d_scontours.as<uint4>());
+                           static_cast<const uint32_t*>(first_point), (uint32_t)P, (uint32_t)Cn, c->slices.points.as<float>(),
+                           c->slices.contours.as<uint4>());
         HIP_TRY(c, hipGetLastError());
         P += V;
         Cn += Cb;
@@ -2936,45 +2923,28 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
     // the attributes of the points: rm_query_points at their positions, device to device
     const rml::SliceAttributes A(P, (flags & RM_MESH_NORMALS) != 0, (flags & RM_MESH_IDS) != 0);
     if (P > 0u) {
-        if ((rc = c->d_sattr.reserve(c, A.bytes)) != RM_OK) return rc;
-        if ((rc = point_attributes(c, Q, loop, shmem, s, flags, P, c->d_spoints.as<const float>(), c->d_sattr.p, A.normals, A.ids)) != RM_OK) return rc;
+        if ((rc = c->slices.attr.reserve(c, A.bytes)) != RM_OK) return rc;
+        if ((rc = point_attributes(c, Q, loop, shmem, s, flags, P, c->slices.points.as<const float>(), c->slices.attr.p, A.normals, A.ids)) != RM_OK) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
-    c->slice_valid = true;
-    c->slice_p = P;
-    c->slice_c = Cn;
-    c->slice_layers = n_layers;
-    c->slice_flags = flags;
     out_counts[RM_SLICE_POINTS] = P;
     out_counts[RM_SLICE_CONTOURS] = Cn;
+    c->slices.commit(P, Cn, n_layers, flags);
     return RM_OK;
 }
 
 RM_EXPORT int rm_read_slices(rm_ctx* c, float* out_points, uint32_t* out_contours, uint32_t* out_layer_first, float* out_normals,
                              uint32_t* out_ids, int is_device, void* stream) {
     if (!c) return RM_ERR_NULL;
-    if (!c->slice_valid) return fail(c, RM_ERR_ARG, "rm_read_slices: nothing has been sliced");
-    if (out_normals && !(c->slice_flags & RM_MESH_NORMALS))
-        return fail(c, RM_ERR_ARG, "rm_read_slices: the slices were computed without RM_MESH_NORMALS");
-    if (out_ids && !(c->slice_flags & RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_read_slices: the slices were computed without RM_MESH_IDS");
-    if (is_device && (misaligned(out_points, 4) || misaligned(out_contours, 16) || misaligned(out_layer_first, 4) ||
-                      misaligned(out_normals, 4) || misaligned(out_ids, 8)))
-        return fail(c, RM_ERR_ARG, "rm_read_slices: device arrays need 4-byte alignment (out_contours: 16-byte, out_ids: 8-byte)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const hipStream_t s = dest_stream(c, is_device, stream);
-    order_with_previous(c, s);  // (the next slice call waits for this stream in turn)
-    const hipMemcpyKind kind = is_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    const size_t pb = (size_t)c->slice_p * 12u, cb = (size_t)c->slice_c * 16u;
-    const rml::SliceLayerTables T(c->slice_layers);
-    const rml::SliceAttributes A(c->slice_p, (c->slice_flags & RM_MESH_NORMALS) != 0, (c->slice_flags & RM_MESH_IDS) != 0);
-    const char* at = c->d_sattr.p;
-    if (out_points && pb) HIP_TRY(c, hipMemcpyAsync(out_points, c->d_spoints.p, pb, kind, s));
-    if (out_contours && cb) HIP_TRY(c, hipMemcpyAsync(out_contours, c->d_scontours.p, cb, kind, s));
-    if (out_layer_first) HIP_TRY(c, hipMemcpyAsync(out_layer_first, T.layer_first.at(c->d_slayers.p), T.layer_first.bytes, kind, s));
-    if (out_normals && A.normals.bytes) HIP_TRY(c, hipMemcpyAsync(out_normals, A.normals.at(at), A.normals.bytes, kind, s));
-    if (out_ids && A.ids.bytes) HIP_TRY(c, hipMemcpyAsync(out_ids, A.ids.at(at), A.ids.bytes, kind, s));
-    if (!is_device) HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
+    const rm_ctx::Slices& r = c->slices;
+    if (!r.valid) return fail(c, RM_ERR_ARG, "rm_read_slices: nothing has been sliced");
+    if (out_normals && !(r.flags & RM_MESH_NORMALS)) return fail(c, RM_ERR_ARG, "rm_read_slices: the slices were computed without RM_MESH_NORMALS");
+    if (out_ids && !(r.flags & RM_MESH_IDS)) return fail(c, RM_ERR_ARG, "rm_read_slices: the slices were computed without RM_MESH_IDS");
+    const rml::SliceLayerTables T(r.n_layers);
+    const rml::SliceAttributes A(r.p, (r.flags & RM_MESH_NORMALS) != 0, (r.flags & RM_MESH_IDS) != 0);
+    return read_back(c, is_device, stream, "rm_read_slices: device arrays need 4-byte alignment (out_contours: 16-byte, out_ids: 8-byte)",
+                     {{out_points, r.points.p, (size_t)r.p * 12u, 4}, {out_contours, r.contours.p, (size_t)r.c * 16u, 16},
+                      {out_layer_first, T.layer_first, r.layers.p, 4}, {out_normals, A.normals, r.attr.p, 4}, {out_ids, A.ids, r.attr.p, 8}});
 }
 
 RM_EXPORT int rm_slice_case_table(uint32_t* out, uint32_t n_out) {

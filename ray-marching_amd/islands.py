@@ -95,7 +95,7 @@ def main(argv=None):
         run = lambda up: direction_report(res, lo, hi, shape, a.level, up, a.max_overhang, a.plate)   # noqa: E731
         if a.up == "best":
             every = {up: run(up)[0] for up in BEST_ORDER}
-            report, isl = run(best_direction(every))                # again: the buffers hold the last call's result
+            report, isl = run(best_direction(every))                # again: only the context's last Islands reads
             report["directions"] = every
         else:
             report, isl = run(a.up)

@@ -38,6 +38,7 @@ class RayMarchingResources:
         self._h = h
         self.device = int(device)
         self._dtype = np.float32
+        self._serials = {family: [0, None] for family in _FAMILIES}    # see _advance
 
     def close(self):
         if getattr(self, "_h", None):
@@ -557,23 +558,25 @@ class RayMarchingResources:
         the work queued on torch.cuda.current_stream().  The Topology's lattice is the unit lattice at the origin."""
         return self._occupancy_call(self._L.rm_label_occupancy, *_TOPO_OUTPUTS, occupancy, None, self._read_topology)
 
-    # What the eight analyses of a lattice share (rm_label_*, rm_distance_*, rm_support_*, rm_islands_*): fn, the sizes and the names
-    # of its counts and statistics (a row of the _*_OUTPUTS below), `direction` -- None, or (up, r2, plate) as the caller gave
-    # them --, and result(counts, stats, origin, step, shape[, up, r2]), which takes both outputs as dicts.
-    def _solid_grid_call(self, fn, n_counts, n_stats, count_names, stat_names, origin, step, shape, level, direction, result):
+    # What the eight analyses of a lattice share (rm_label_*, rm_distance_*, rm_support_*, rm_islands_*): fn, the families of retained
+    # results it replaces, the sizes and the names of its counts and statistics (a row of the _*_OUTPUTS below), `direction` -- None,
+    # or (up, r2, plate) as the caller gave them --, and result(counts, stats, origin, step, shape[, up, r2]): both outputs as dicts.
+    def _solid_grid_call(self, fn, families, n_counts, n_stats, count_names, stat_names, origin, step, shape, level, direction, result):
         """A *_solid_grid call: fn = rm_*_solid on an exact lattice."""
         o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
         extra = _support_args(*direction) if direction else ()
         counts, stats = (C.c_uint64 * n_counts)(), (C.c_uint64 * n_stats)()
         self._check(fn(self._h, fp(o), fp(s), nx, ny, nz, float(level), *extra, counts, n_counts, stats, n_stats))
+        self._advance(fn, *families)
         return result(_named(counts, count_names), _named(stats, stat_names), o, s, (nx, ny, nz), *extra[:2])
 
-    def _occupancy_call(self, fn, n_counts, n_stats, count_names, stat_names, occupancy, direction, result):
+    def _occupancy_call(self, fn, families, n_counts, n_stats, count_names, stat_names, occupancy, direction, result):
         """A *_occupancy call: fn = rm_*_occupancy on a caller's occupancy; the result's lattice is the unit lattice."""
         nx, ny, nz, ptr, is_device, stream, keep = self._occupancy_arg(occupancy)
         extra = _support_args(*direction) if direction else ()
         counts, stats = (C.c_uint64 * n_counts)(), (C.c_uint64 * n_stats)()
         self._check(fn(self._h, nx, ny, nz, ptr, is_device, stream, *extra, counts, n_counts, stats, n_stats))
+        self._advance(fn, *families)
         del keep
         return result(_named(counts, count_names), _named(stats, stat_names), np.zeros(3, dtype=np.float32), np.ones(3, dtype=np.float32),
                       (nx, ny, nz), *extra[:2])
@@ -604,17 +607,13 @@ class RayMarchingResources:
         """The Topology of the labelling call that just returned: its counts and statistics, and both row tables read back."""
         for name in ("euler", "tunnels"):                                    # two's-complement int64
             cd[name] -= (cd[name] >> 63) << 64
-        body = np.zeros((cd["bodies"], _ffi.RM_MOMENTS), dtype=np.uint64)
-        cav = np.zeros((cd["cavities"], _ffi.RM_MOMENTS), dtype=np.uint64)
-        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
-        if body.size or cav.size:
-            self._check(self._L.rm_read_topology(self._h, ptr(body), ptr(cav), None, 0, None))
+        body, cav, _ = self._read_new(self._L.rm_read_topology, [((cd["bodies"], _ffi.RM_MOMENTS), *_U64, True),
+                                                                 ((cd["cavities"], _ffi.RM_MOMENTS), *_U64, True), _SKIP])
         return Topology(self, cd, sd, body, cav, origin, step, shape)
 
     def read_topology_device(self, body_moments_ptr=0, cavity_moments_ptr=0, labels_ptr=0, stream=None):
         """rm_read_topology of the last labelling call into device memory (integer addresses; 0 = not wanted), asynchronous."""
-        self._check(self._L.rm_read_topology(self._h, C.c_void_p(body_moments_ptr or None), C.c_void_p(cavity_moments_ptr or None),
-                                             C.c_void_p(labels_ptr or None), 1, C.c_void_p(stream) if stream else None))
+        self._read_into(self._L.rm_read_topology, (body_moments_ptr, cavity_moments_ptr, labels_ptr), True, stream)
 
     # -- distance transform (rm_distance_solid / rm_distance_occupancy / rm_distance_features / rm_read_distance) ----------------
     def distance_solid(self, lo, hi, resolution, level=0.0):
@@ -637,8 +636,7 @@ class RayMarchingResources:
     def read_distance_device(self, d2_ptr=0, mask_ptr=0, stream=None):
         """rm_read_distance of the last distance volume and feature mask into device memory (integer addresses; 0 = not wanted),
         asynchronous."""
-        self._check(self._L.rm_read_distance(self._h, C.c_void_p(d2_ptr or None), C.c_void_p(mask_ptr or None), 1,
-                                             C.c_void_p(stream) if stream else None))
+        self._read_into(self._L.rm_read_distance, (d2_ptr, mask_ptr), True, stream)
 
     # -- overhangs and supports (rm_support_solid / rm_support_occupancy / rm_read_support) ---------------------------------------
     def support_solid(self, lo, hi, resolution, level=0.0, up="+z", r2=1, plate=None):
@@ -662,8 +660,7 @@ class RayMarchingResources:
 
     def read_support_device(self, mask_ptr=0, profile_ptr=0, stream=None):
         """rm_read_support of the last mask and profile into device memory (integer addresses; 0 = not wanted), asynchronous."""
-        self._check(self._L.rm_read_support(self._h, C.c_void_p(mask_ptr or None), C.c_void_p(profile_ptr or None), 1,
-                                            C.c_void_p(stream) if stream else None))
+        self._read_into(self._L.rm_read_support, (mask_ptr, profile_ptr), True, stream)
 
     # -- layer regions and islands (rm_islands_solid / rm_islands_occupancy / rm_read_islands) -----------------------------------
     def islands_solid(self, lo, hi, resolution, level=0.0, up="+z", r2=1, plate=None):
@@ -687,37 +684,50 @@ class RayMarchingResources:
     def read_islands_device(self, rows_ptr=0, row_capacity=0, labels_ptr=0, mask_ptr=0, profile_ptr=0, stream=None):
         """rm_read_islands of the last region table (row_capacity rows of room), label volume, mask and profile into device memory
         (integer addresses; 0 = not wanted), asynchronous."""
-        self._check(self._L.rm_read_islands(self._h, C.c_void_p(rows_ptr or None), int(row_capacity), C.c_void_p(labels_ptr or None),
-                                            C.c_void_p(mask_ptr or None), C.c_void_p(profile_ptr or None), 1,
-                                            C.c_void_p(stream) if stream else None))
+        self._read_into(self._islands_reader(row_capacity), (rows_ptr, labels_ptr, mask_ptr, profile_ptr), True, stream)
+
+    # -- retained results (rm_read_*) ------------------------------------------------------------------------------------------
+    # rm_read_* copies the size of the CONTEXT's last result, whatever the caller allocated.  So every read goes through _read_into,
+    # and the result objects that read on demand (_Retained) are held to a serial per family: _advance moves it on when a producing
+    # call has returned RM_OK (after a call that failed late the library itself refuses reads), and an object made under an earlier
+    # serial refuses to read.  Mesh and slices are read inside their calls and need no serial.
+    def _advance(self, fn, *families):
+        for family in families:
+            self._serials[family] = [self._serials[family][0] + 1, fn.__name__]
+
+    def _islands_reader(self, row_capacity):
+        return lambda h, rows, *rest: self._L.rm_read_islands(h, rows, int(row_capacity), *rest)    # (as _read_into calls a reader)
+
+    def _read_into(self, fn, addresses, device=False, stream=None):
+        """The one read path: fn(handle, a pointer per address, is_device, stream), status checked.  An output that is not wanted,
+        or is empty, has the address 0 or None and goes as NULL."""
+        self._check(fn(self._h, *[C.c_void_p(int(a) if a else None) for a in addresses], 1 if device else 0,
+                       C.c_void_p(stream) if stream else None))
+
+    def _read_new(self, fn, specs, device=False):
+        """_read_into new arrays: per output (shape, numpy dtype, name of the torch dtype, wanted) of specs a numpy array, or with
+        device=True a torch tensor on this context's GPU, filled on torch.cuda.current_stream(); None where not wanted."""
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            outs = [torch.empty(shape, dtype=getattr(torch, tdt), device=dev) if want else None for shape, _, tdt, want in specs]
+            addresses, stream = [t.data_ptr() if t is not None and t.numel() else 0 for t in outs], torch.cuda.current_stream(dev).cuda_stream
+        else:
+            outs = [np.empty(shape, dtype=ndt) if want else None for shape, ndt, _, want in specs]
+            addresses, stream = [a.ctypes.data if a is not None and a.size else 0 for a in outs], None
+        self._read_into(fn, addresses, device, stream)
+        return outs
 
     def _read_mesh(self, V, T, normals, ids, device):
         """rm_read_mesh of the extraction that just returned V vertices and T triangles, as a mesh.Mesh."""
         from . import mesh as _mesh
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
-            tris = torch.empty((T, 3), dtype=torch.int32, device=dev)       # int32 views of the u32 indices
-            nrm = torch.empty((V, 3), dtype=torch.float32, device=dev) if normals else None
-            idv = torch.empty((V, 2), dtype=torch.int32, device=dev) if ids else None
-            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
-            self._check(self._L.rm_read_mesh(self._h, ptr(verts), ptr(tris), ptr(nrm), ptr(idv), 1,
-                                             C.c_void_p(self._torch_stream(verts))))
-        else:
-            verts = np.empty((V, 3), dtype=np.float32)
-            tris = np.empty((T, 3), dtype=np.uint32)
-            nrm = np.empty((V, 3), dtype=np.float32) if normals else None
-            idv = np.empty((V, 2), dtype=np.uint32) if ids else None
-            ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-            self._check(self._L.rm_read_mesh(self._h, ptr(verts), ptr(tris), ptr(nrm), ptr(idv), 0, None))
+        verts, tris, nrm, idv = self._read_new(self._L.rm_read_mesh, [((V, 3), *_F32, True), ((T, 3), *_U32, True),
+                                                                      ((V, 3), *_F32, normals), ((V, 2), *_U32, ids)], device)
         return _mesh.Mesh(verts, tris, nrm, idv[:, 0] if ids else None, idv[:, 1] if ids else None)
 
     def read_mesh_device(self, vertices_ptr=0, triangles_ptr=0, normals_ptr=0, ids_ptr=0, stream=None):
         """rm_read_mesh of the last extraction into device memory (integer addresses; 0 = not wanted), asynchronous."""
-        self._check(self._L.rm_read_mesh(self._h, C.c_void_p(vertices_ptr or None), C.c_void_p(triangles_ptr or None),
-                                         C.c_void_p(normals_ptr or None), C.c_void_p(ids_ptr or None), 1,
-                                         C.c_void_p(stream) if stream else None))
+        self._read_into(self._L.rm_read_mesh, (vertices_ptr, triangles_ptr, normals_ptr, ids_ptr), True, stream)
 
     # -- slicing (rm_slice_contours / rm_read_slices) ------------------------------------------------------------------------
     # The slicing axis w is 0, 1 or 2 (x, y, z); the in-plane axes are u = (w + 1) % 3 and v = (w + 2) % 3.
@@ -804,33 +814,14 @@ class RayMarchingResources:
     def _read_slices(self, P, Cn, axis, heights, lattice, normals, ids, device):
         """rm_read_slices of the call that just returned P points and Cn contours, as a slicer.Slices."""
         from . import slicer as _slicer
-        nl = len(heights)
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            pts = torch.empty((P, 3), dtype=torch.float32, device=dev)
-            con = torch.empty((Cn, 4), dtype=torch.int32, device=dev)       # int32 views of the u32 records
-            lf = torch.empty(nl + 1, dtype=torch.int32, device=dev)
-            nrm = torch.empty((P, 3), dtype=torch.float32, device=dev) if normals else None
-            idv = torch.empty((P, 2), dtype=torch.int32, device=dev) if ids else None
-            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
-            self._check(self._L.rm_read_slices(self._h, ptr(pts), ptr(con), ptr(lf), ptr(nrm), ptr(idv), 1,
-                                               C.c_void_p(self._torch_stream(pts))))
-        else:
-            pts = np.empty((P, 3), dtype=np.float32)
-            con = np.empty((Cn, 4), dtype=np.uint32)
-            lf = np.empty(nl + 1, dtype=np.uint32)
-            nrm = np.empty((P, 3), dtype=np.float32) if normals else None
-            idv = np.empty((P, 2), dtype=np.uint32) if ids else None
-            ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-            self._check(self._L.rm_read_slices(self._h, ptr(pts), ptr(con), ptr(lf), ptr(nrm), ptr(idv), 0, None))
+        pts, con, lf, nrm, idv = self._read_new(self._L.rm_read_slices, [((P, 3), *_F32, True), ((Cn, 4), *_U32, True),
+                                                                         ((len(heights) + 1,), *_U32, True), ((P, 3), *_F32, normals),
+                                                                         ((P, 2), *_U32, ids)], device)
         return _slicer.Slices(pts, con, lf, heights, axis, nrm, idv[:, 0] if ids else None, idv[:, 1] if ids else None, lattice)
 
     def read_slices_device(self, points_ptr=0, contours_ptr=0, layer_first_ptr=0, normals_ptr=0, ids_ptr=0, stream=None):
         """rm_read_slices of the last slice call into device memory (integer addresses; 0 = not wanted), asynchronous."""
-        self._check(self._L.rm_read_slices(self._h, C.c_void_p(points_ptr or None), C.c_void_p(contours_ptr or None),
-                                           C.c_void_p(layer_first_ptr or None), C.c_void_p(normals_ptr or None),
-                                           C.c_void_p(ids_ptr or None), 1, C.c_void_p(stream) if stream else None))
+        self._read_into(self._L.rm_read_slices, (points_ptr, contours_ptr, layer_first_ptr, normals_ptr, ids_ptr), True, stream)
 
 
 class RayMarchingCallback:
@@ -861,15 +852,43 @@ class RayMarchingCallback:
         return resources.draw(W, H)
 
 
-# The outputs of the lattice analyses (RayMarchingResources._solid_grid_call): how many counts and statistics, and their names.
-_TOPO_OUTPUTS = (_ffi.RM_TOPO_COUNTS, _ffi.RM_TOPO_STATS, _ffi.TOPO_COUNT_NAMES, _ffi.TOPO_STAT_NAMES)
-_DIST_OUTPUTS = (_ffi.RM_DIST_COUNTS, _ffi.RM_DIST_STATS, _ffi.DIST_COUNT_NAMES, _ffi.DIST_STAT_NAMES)
-_SUP_OUTPUTS = (_ffi.RM_SUP_COUNTS, _ffi.RM_SUP_STATS, _ffi.SUP_COUNT_NAMES, _ffi.SUP_STAT_NAMES)
-_ISL_OUTPUTS = (_ffi.RM_ISL_COUNTS, _ffi.RM_ISL_STATS, _ffi.ISL_COUNT_NAMES, _ffi.ISL_STAT_NAMES)
+# The outputs of the lattice analyses (RayMarchingResources._solid_grid_call): the families of retained results a call replaces
+# (a new distance volume has no mask), how many counts and statistics, and their names.
+_FAMILIES = ("topology", "distance", "distance_mask", "support", "islands")
+_TOPO_OUTPUTS = (("topology",), _ffi.RM_TOPO_COUNTS, _ffi.RM_TOPO_STATS, _ffi.TOPO_COUNT_NAMES, _ffi.TOPO_STAT_NAMES)
+_DIST_OUTPUTS = (("distance", "distance_mask"), _ffi.RM_DIST_COUNTS, _ffi.RM_DIST_STATS, _ffi.DIST_COUNT_NAMES, _ffi.DIST_STAT_NAMES)
+_SUP_OUTPUTS = (("support",), _ffi.RM_SUP_COUNTS, _ffi.RM_SUP_STATS, _ffi.SUP_COUNT_NAMES, _ffi.SUP_STAT_NAMES)
+_ISL_OUTPUTS = (("islands",), _ffi.RM_ISL_COUNTS, _ffi.RM_ISL_STATS, _ffi.ISL_COUNT_NAMES, _ffi.ISL_STAT_NAMES)
+
+# RayMarchingResources._read_new's specs: (numpy dtype, name of the torch dtype: u32 and u64 words as int32 and int64 views); _SKIP.
+_F32, _U32, _U64, _U8 = (np.float32, "float32"), (np.uint32, "int32"), (np.uint64, "int64"), (np.uint8, "uint8")
+_SKIP = ((0,), *_U8, False)
 
 
 def _named(words, names):
     return {name: int(words[k]) for k, name in enumerate(names)}
+
+
+class _Retained:
+    """What the result objects that read on demand share.  They stand for the retained result of their family in their context and
+    record the family's serial they were made under (RayMarchingResources._advance).  Once a newer call has replaced that result, a
+    read would copy the newer one's size into arrays of this one's shape: _check_current raises ValueError before that."""
+
+    def _retain(self, resources, family):
+        self._res, self._family, self._serial = resources, family, resources._serials[family][0]
+
+    def _check_current(self):
+        serial, call = self._res._serials[self._family]
+        if serial != self._serial:
+            raise ValueError("%r is stale: %s has replaced the %s result of its context (now number %d, this was number %d)"
+                             % (self, call, self._family.replace("_", " "), serial, self._serial))
+
+    def _read(self, fn, position, n_outputs, dtype, shape=None):
+        """Output `position` of fn's n_outputs as a new host array of `shape`; None: a volume (nz, ny, nx) of the lattice."""
+        self._check_current()
+        specs = [_SKIP] * n_outputs
+        specs[position] = (shape or tuple(self.shape)[::-1], *dtype, True)
+        return self._res._read_new(fn, specs)[position]
 
 
 class MassMoments:
@@ -886,13 +905,14 @@ class MassMoments:
         return mass_from_moments(self.moments, self.origin, self.step, density)
 
 
-class Topology:
+class Topology(_Retained):
     """The result of label_solid / label_occupancy.  bodies, cavities, euler, tunnels: ints; counts and stats: dicts
     (_ffi.TOPO_COUNT_NAMES, _ffi.TOPO_STAT_NAMES); body_moments (B, 16) and cavity_moments (C, 16): uint64 rows of the
-    _ffi.RM_MOMENT_* words, in body and cavity order; origin, step (float32[3]) and shape of the lattice."""
+    _ffi.RM_MOMENT_* words, in body and cavity order; origin, step (float32[3]) and shape of the lattice.  labels() reads the
+    context's buffers: after a later labelling call of the context it raises ValueError."""
 
     def __init__(self, resources, counts, stats, body_moments, cavity_moments, origin, step, shape):
-        self._res = resources
+        self._retain(resources, "topology")
         self.counts, self.stats = counts, stats
         self.bodies, self.cavities, self.euler, self.tunnels = counts["bodies"], counts["cavities"], counts["euler"], counts["tunnels"]
         self.body_moments, self.cavity_moments = body_moments, cavity_moments
@@ -912,11 +932,8 @@ class Topology:
 
     def labels(self):
         """The label volume, uint32 (nz, ny, nx): a body's number, _ffi.RM_TOPO_CAVITY_BIT | a cavity's number, or
-        _ffi.RM_TOPO_EXTERIOR.  Read on demand, and only while this is the context's last labelling."""
-        nx, ny, nz = self.shape
-        out = np.empty((nz, ny, nx), dtype=np.uint32)
-        self._res._check(self._res._L.rm_read_topology(self._res._h, None, None, out.ctypes.data, 0, None))
-        return out
+        _ffi.RM_TOPO_EXTERIOR.  Read on demand."""
+        return self._read(self._res._L.rm_read_topology, 2, 3, _U32)
 
 
 def squared_radius(width, step):
@@ -931,13 +948,13 @@ def squared_radius(width, step):
     return int(np.floor((w / 2.0 / float(st[0])) ** 2))
 
 
-class Distance:
+class Distance(_Retained):
     """The result of distance_solid / distance_occupancy.  counts and stats: dicts (_ffi.DIST_COUNT_NAMES, _ffi.DIST_STAT_NAMES);
-    origin, step (float32[3]) and shape of the lattice.  d2(), features() and mask() read the context's buffers: they hold while
-    this is the context's last distance call."""
+    origin, step (float32[3]) and shape of the lattice.  d2() and features() work on the context's buffers: after a later distance
+    call of the context they raise ValueError."""
 
     def __init__(self, resources, counts, stats, origin, step, shape):
-        self._res = resources
+        self._retain(resources, "distance")
         self.counts, self.stats = counts, stats
         self.origin, self.step, self.shape = origin, step, shape
 
@@ -947,10 +964,7 @@ class Distance:
 
     def d2(self):
         """The distance volume, uint32 (nz, ny, nx): D2 in index units, | _ffi.RM_DIST_INSIDE_BIT for an inside point."""
-        nx, ny, nz = self.shape
-        out = np.empty((nz, ny, nx), dtype=np.uint32)
-        self._res._check(self._res._L.rm_read_distance(self._res._h, out.ctypes.data, None, 0, None))
-        return out
+        return self._read(self._res._L.rm_read_distance, 0, 2, _U32)
 
     def inscribed_radius(self, step=None):
         """Radius (world units) and centre (i, j, k) of the largest inscribed ball: step * sqrt(max_inside) and the point of
@@ -979,26 +993,26 @@ class Distance:
         for r2 in (r2_wall, r2_gap):
             if r2 is not None and not 0 <= int(r2) < skip:
                 raise ValueError("a squared radius must be >= 0, not %r" % (r2,))
+        self._check_current()
         counts = (C.c_uint64 * _ffi.RM_DIST_FEATURE_COUNTS)()
-        self._res._check(self._res._L.rm_distance_features(self._res._h, skip if r2_wall is None else int(r2_wall),
-                                                           skip if r2_gap is None else int(r2_gap), counts, _ffi.RM_DIST_FEATURE_COUNTS))
+        fn = self._res._L.rm_distance_features
+        self._res._check(fn(self._res._h, *(skip if r2 is None else int(r2) for r2 in (r2_wall, r2_gap)), counts, _ffi.RM_DIST_FEATURE_COUNTS))
+        self._res._advance(fn, "distance_mask")
         return DistanceFeatures(self._res, {name: int(counts[k]) for k, name in enumerate(_ffi.DIST_FEATURE_NAMES)}, r2_wall, r2_gap,
                                 self.shape)
 
 
-class DistanceFeatures:
-    """The result of Distance.features: counts (a dict: _ffi.DIST_FEATURE_NAMES), r2_wall and r2_gap as used (None: skipped)."""
+class DistanceFeatures(_Retained):
+    """The result of Distance.features: counts (a dict: _ffi.DIST_FEATURE_NAMES), r2_wall and r2_gap as used (None: skipped).
+    mask() reads the context's buffer: after a later features or distance call of the context it raises ValueError."""
 
     def __init__(self, resources, counts, r2_wall, r2_gap, shape):
-        self._res = resources
+        self._retain(resources, "distance_mask")
         self.counts, self.r2_wall, self.r2_gap, self.shape = counts, r2_wall, r2_gap, shape
 
     def mask(self):
         """The feature mask, uint8 (nz, ny, nx): 0 outside, 1 inside, 2 thin, 3 narrow (_ffi.DIST_MASK_*)."""
-        nx, ny, nz = self.shape
-        out = np.empty((nz, ny, nx), dtype=np.uint8)
-        self._res._check(self._res._L.rm_read_distance(self._res._h, None, out.ctypes.data, 0, None))
-        return out
+        return self._read(self._res._L.rm_read_distance, 1, 2, _U8)
 
 
 def reach_r2(angle_deg, step_up, step_in):
@@ -1034,13 +1048,13 @@ def _support_args(up, r2, plate):
     return int(up), int(r2), _ffi.RM_SUPPORT_PLATE_AUTO if plate is None else int(plate)
 
 
-class Support:
+class Support(_Retained):
     """The result of support_solid / support_occupancy.  counts and stats: dicts (_ffi.SUP_COUNT_NAMES, _ffi.SUP_STAT_NAMES); up
     (_ffi.RM_UP_*), r2, and origin, step (float32[3]) and shape of the lattice.  mask() and profile() read the context's buffers:
-    they hold while this is the context's last support call."""
+    after a later support call of the context they raise ValueError."""
 
     def __init__(self, resources, counts, stats, origin, step, shape, up, r2):
-        self._res = resources
+        self._retain(resources, "support")
         self.counts, self.stats = counts, stats
         self.origin, self.step, self.shape = origin, step, shape
         self.up, self.r2 = up, r2
@@ -1061,17 +1075,12 @@ class Support:
     def mask(self):
         """The mask, uint8 (nz, ny, nx): 0 outside, 1 inside, 2 overhang, 3 support on the plate, 4 support on the part
         (_ffi.SUP_MASK_*)."""
-        nx, ny, nz = self.shape
-        out = np.empty((nz, ny, nx), dtype=np.uint8)
-        self._res._check(self._res._L.rm_read_support(self._res._h, out.ctypes.data, None, 0, None))
-        return out
+        return self._read(self._res._L.rm_read_support, 0, 2, _U8)
 
     def profile(self):
         """The profile, uint32 (layers, 4), height 0 first: per layer its inside points, overhang points, support points on the
         plate and support points on the part."""
-        out = np.empty((self.layers, 4), dtype=np.uint32)
-        self._res._check(self._res._L.rm_read_support(self._res._h, None, out.ctypes.data, 0, None))
-        return out
+        return self._read(self._res._L.rm_read_support, 1, 2, _U32, (self.layers, 4))
 
     def volume(self):
         """The support material in world units: the support points times the volume of a cell."""
@@ -1098,13 +1107,13 @@ def island_roots(rows):
     return root[1:]
 
 
-class Islands:
+class Islands(_Retained):
     """The result of islands_solid / islands_occupancy.  counts and stats: dicts (_ffi.ISL_COUNT_NAMES, _ffi.ISL_STAT_NAMES); up
     (_ffi.RM_UP_*), r2, and origin, step (float32[3]) and shape of the lattice.  rows(), labels(), mask() and profile() read the
-    context's buffers: they hold while this is the context's last islands call."""
+    context's buffers: after a later islands call of the context they raise ValueError."""
 
     def __init__(self, resources, counts, stats, origin, step, shape, up, r2):
-        self._res = resources
+        self._retain(resources, "islands")
         self.counts, self.stats = counts, stats
         self.origin, self.step, self.shape = origin, step, shape
         self.up, self.r2 = up, r2
@@ -1119,38 +1128,25 @@ class Islands:
         """The points along the up axis."""
         return self.shape[self.up >> 1]
 
-    def _read(self, rows=None, labels=None, mask=None, profile=None):
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        self._res._check(self._res._L.rm_read_islands(self._res._h, ptr(rows), 0 if rows is None else len(rows), ptr(labels), ptr(mask),
-                                                      ptr(profile), 0, None))
+    def _read_islands(self, position, dtype, shape=None):
+        return self._read(self._res._islands_reader(self.counts["regions"]), position, 4, dtype, shape)
 
     def rows(self):
         """The region table, a structured array (REGIONS,) of uint32 fields _ffi.ISL_ROW_NAMES; row r - 1 is region r.  a and b
         are the two in-layer axes in ascending axis order (up z: x and y)."""
-        out = np.zeros(self.counts["regions"], dtype=ISL_ROW_DTYPE)
-        if out.size:
-            self._read(rows=out)
-        return out
+        return self._read_islands(0, (ISL_ROW_DTYPE, None), (self.counts["regions"],))
 
     def labels(self):
         """The label volume, uint32 (nz, ny, nx): the region's number for inside points at or above the plate, 0 elsewhere."""
-        nx, ny, nz = self.shape
-        out = np.empty((nz, ny, nx), dtype=np.uint32)
-        self._read(labels=out)
-        return out
+        return self._read_islands(1, _U32)
 
     def mask(self):
         """The mask, uint8 (nz, ny, nx): 0 outside, 1 inside, 2 inside and in an island (_ffi.ISL_MASK_*)."""
-        nx, ny, nz = self.shape
-        out = np.empty((nz, ny, nx), dtype=np.uint8)
-        self._read(mask=out)
-        return out
+        return self._read_islands(2, _U8)
 
     def profile(self):
         """The profile, uint32 (layers, 4), height 0 first: per layer its inside points, regions, islands and island points."""
-        out = np.empty((self.layers, 4), dtype=np.uint32)
-        self._read(profile=out)
-        return out
+        return self._read_islands(3, _U32, (self.layers, 4))
 
     def roots(self, rows=None):
         """island_roots of the region table."""

@@ -94,7 +94,7 @@ def main(argv=None):
         if a.up == "best":
             every = {up: run(up)[0] for up in BEST_ORDER}
             up = best_direction(every)
-            report, sup = run(up)                                   # again: mask and profile are the last call's
+            report, sup = run(up)                                   # again: only the context's last Support reads
             report["directions"] = every
         else:
             report, sup = run(a.up)
