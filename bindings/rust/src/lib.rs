@@ -459,6 +459,7 @@ extern "C" {
     pub fn rm_selftest_cull_tiles(ctx: *mut rm_ctx, w: u32, h: u32, xy: *const u32, n: u32, out: *mut f32) -> c_int;
     pub fn rm_selftest_cull_waves(ctx: *mut rm_ctx, origin: *const f32, pos: *const f32, thr: *const f32, live: *const u64, n_waves: u32,
                                   extra_margin: f32, out_masks: *mut u64) -> c_int;
+    pub fn rm_selftest_anchor(ctx: *mut rm_ctx, origin: *const f32, pairs: *const f32, n: u32, out: *mut f32) -> c_int;
     pub fn rm_read_wave_stats(ctx: *mut rm_ctx, dst: *mut c_void, cap_bytes: u64, out_bytes: *mut u64) -> c_int;
     pub fn rm_jit_source(cmd_count: u32, words: *const u32, n_words: u32, waves_per_tile: c_int, buf: *mut c_char,
                          cap: usize, needed: *mut usize) -> c_int;

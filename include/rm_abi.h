@@ -871,6 +871,14 @@ int rm_selftest_cull_pixels(rm_ctx* ctx, uint32_t W, uint32_t H, const uint32_t*
 int rm_selftest_cull_tiles(rm_ctx* ctx, uint32_t W, uint32_t H, const uint32_t* xy, uint32_t n, float* out);
 int rm_selftest_cull_waves(rm_ctx* ctx, const float* origin, const float* pos, const float* thr, const uint64_t* live, uint32_t n_waves,
                            float extra_margin, uint64_t* out_masks);
+/* rm_selftest_anchor: the anchored pruning threshold of a ray's first own step (rm_kernel_v5.h "Pruning"; the device functions
+ * the march calls, anchor_reach and anchor_thr_base) on n <= 2^20 pairs of points the caller chooses, pairs[6 i + 0..2] the
+ * anchor a and 3..5 the evaluation point q; camera position origin[3] (the |ro|_1 of the margins).  The context's program is
+ * evaluated at both points by the interpreter loop a query of it runs.  out[4 i + ..]: 0 the anchor's reach aT, 1 the
+ * threshold the step would hand to the culling at q when the camera's own bound is +inf -- anchor_thr_base(+inf, q, a, aT)
+ * plus the step's position term --, 2 the value computed at a, 3 the value computed at q.  (Additive: RM_ABI_VERSION stays 2.)
+ * tests/test_gpu_anchor.py holds 1 against |3| and against binary64 geometry. */
+int rm_selftest_anchor(rm_ctx* ctx, const float* origin, const float* pairs, uint32_t n, float* out);
 
 /* Diagnostics: per-wave records of the last draw made with RM_OPT_WAVE_STATS = 1, four u64 per
  * wave in dispatch order (frame, workgroup, wave of the workgroup): [0] start, [1] end (100 MHz s_memrealtime ticks),

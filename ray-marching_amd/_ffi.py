@@ -206,6 +206,8 @@ def hip_lib():
         L.rm_selftest_cull_tiles.restype = C.c_int
         L.rm_selftest_cull_waves.argtypes = [vp, vp, vp, vp, vp, u32, C.c_float, vp]
         L.rm_selftest_cull_waves.restype = C.c_int
+        L.rm_selftest_anchor.argtypes = [vp, vp, vp, u32, vp]
+        L.rm_selftest_anchor.restype = C.c_int
         L.rm_read_wave_stats.argtypes = [vp, vp, u64, C.POINTER(u64)]
         L.rm_read_wave_stats.restype = C.c_int
         L.rm_query_points.argtypes = [vp, u32, vp, vp, vp, vp, C.c_int, vp]

@@ -3283,6 +3283,28 @@ RM_EXPORT int rm_selftest_cull_waves(rm_ctx* c, const float* origin, const float
     return RM_OK;
 }
 
+RM_EXPORT int rm_selftest_anchor(rm_ctx* c, const float* origin, const float* pairs, uint32_t n, float* out) {
+    if (!c) return RM_ERR_NULL;
+    if (!origin || !pairs || !out) return fail(c, RM_ERR_NULL, "rm_selftest_anchor: NULL argument");
+    if (n == 0u || n > (1u << 20)) return fail(c, RM_ERR_ARG, "rm_selftest_anchor: n = %u, must be 1 .. 2^20", n);
+    RmLaunch L;
+    if (int rc = cull_probe_begin(c, "rm_selftest_anchor", 8u, 8u, &L)) return rc;  // the march's scene_scale
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    size_t shmem = 0;
+    if (int rc = query_begin(c, c->stream, false, false, &Q, &loop, &shmem)) return rc;
+    DevBuf<float> d_pairs, d_out;
+    if (int rc = probe_put(c, d_pairs, pairs, (size_t)n * 6u)) return rc;
+    if (int rc = d_out.reserve(c, (size_t)n * 4u)) return rc;
+    const float prune_scale = L.scene_scale + ((std::fabs(origin[0]) + std::fabs(origin[1])) + std::fabs(origin[2]));  // prune_scale_v5
+    using AnchorFn = void (*)(rmk::QueryLaunch, float, uint32_t, const float*, float*);
+    const AnchorFn kernel = with_loop(loop, [](auto tag) -> AnchorFn { return rmk::rm_selftest_anchor_kernel<decltype(tag)::value>; });
+    if (int rc = query_launch(c, kernel, n, shmem, c->stream, Q, prune_scale, n, (const float*)d_pairs.p, d_out.p)) return rc;
+    if (int rc = probe_finish(c, "rm_selftest_anchor")) return rc;
+    HIP_TRY(c, hipMemcpy(out, d_out.p, (size_t)n * 16u, hipMemcpyDeviceToHost));
+    return RM_OK;
+}
+
 RM_EXPORT int rm_measure_write_bandwidth(rm_ctx* c, uint64_t bytes, int iters, double* out_gbps) {
     if (!c) return RM_ERR_NULL;
     if (!out_gbps) return fail(c, RM_ERR_NULL, "rm_measure_write_bandwidth: out is NULL");

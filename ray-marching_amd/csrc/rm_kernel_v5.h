@@ -87,6 +87,39 @@ RM_DEV void map_scene_taps(LdsF lp, float cx, float cy, float cz, unsigned long 
 // Programs with a Plane (|n| arbitrary) or a SmoothUnion (not a lattice operator) are not pruned this way; programs that
 // blend have rules of their own (below).
 constexpr float kPruneAbs = 4.0e-6f;
+// Anchored first step.  The inequality above never asks that q and q' lie on one ray: ANY pair (p_a, F_a = the value this launch
+// computed at p_a) bounds the value at q' by |F_a| + |q' - p_a| + 2E.  The first own step of a ray that took the frame's shared
+// step is anchored at the camera (F(ro) = f0, |q' - ro| <= |f0|): thr = 2 |f0|, larger than the scene for a camera that stands
+// back from it -- nothing is skipped there.  But the wave has just evaluated the scene a few pixels away on the same start
+// sphere: it keeps one such pair (ax, ay, az, aT), wave-uniform, taken from its first live lane at the first evaluation after
+// it handed out rays, and a ray that takes the shared step afterwards gets
+//     aT       = |F_a| (1 + 1e-5) + 4e-6 (scene_scale + |ro|_1 + |p_a|_1)                      (anchor_reach)
+//     thr_base = min(2 |f0| (1 + 1e-5), fl(fl(l1) (1 + 1e-5) + aT)),   l1 = |q' - p_a|_1      (anchor_thr_base)
+// to which the step adds its own position term m(q') as for every threshold.  Why that bounds |F'_computed|:
+//   - p_a and q' are the binary32 points the evaluations ran AT (q' by the step's own expression, which with contraction off
+//     gives the same bits here; were it an ulp off, m(q') covers the rounding of q' as it always did), so the real distance
+//     between them is what counts, and |q' - p_a|_2 <= |q' - p_a|_1: the triangle inequality holds a fortiori with the L1 norm
+//     (the choice of wave_cull_lattice: no square root);
+//   - fl(l1): each of the three differences, and each of the two sums, is one rounding -- relative error 2^-24, none where it
+//     underflows (sums and differences of binary32 numbers are exact there) --, so fl(l1) >= l1 (1 - 2^-24)^3 > l1 (1 - 1.8e-7);
+//     the multiply-add rounds once more, fl(t) >= t (1 - 2^-24).  The factor 1.00001f (>= 1 + 9.9e-6 as a binary32 number) on
+//     both l1 and |F_a| leaves 9.6e-6 (l1 + |F_a|) after these losses; the term aT adds beyond |F_a| loses 6e-8 of itself to
+//     the last rounding, which its threefold reserve (next line) does not notice;
+//   - the evaluation error at BOTH points: E(p_a) <= 4e-7 (scene_scale + |ro|_1 + |p_a|_1) sits in aT with its factor 4e-6,
+//     E(q') in m(q') -- each term has one E to cover where the march step's single m covers three;
+//   - non-finite inputs: a NaN F_a or a non-finite p_a makes aT NaN or +inf; a non-finite q' or an overflow makes l1, and so
+//     t, +inf or NaN (inf - inf); `t < thr_base` is false for all of them and the camera's threshold stays.  A NaN thr_base
+//     (f0 NaN) stays NaN.  No anchor yet: aT = +inf.
+// The anchor is never reset between tiles (a far anchor loses the min: it can only fail to help) and lives in four scalar
+// registers.  tools/sim/wave_cull_sim.py --anchor: leaves evaluated at the first own step of a batch 16.0 -> 2.7 of 16.
+RM_DEV float anchor_reach(float px, float py, float pz, float sd, float prune_scale) {
+    return __builtin_fabsf(sd) * 1.00001f + kPruneAbs * (prune_scale + ((__builtin_fabsf(px) + __builtin_fabsf(py)) + __builtin_fabsf(pz)));
+}
+RM_DEV float anchor_thr_base(float thr_base, float qx, float qy, float qz, float ax, float ay, float az, float aT) {
+    const float l1 = (__builtin_fabsf(qx - ax) + __builtin_fabsf(qy - ay)) + __builtin_fabsf(qz - az);
+    const float t = __builtin_fmaf(l1, 1.00001f, aT);
+    return t < thr_base ? t : thr_base;  // NaN t: the old value stays
+}
 // The thresholds are kept (a register per ray, |sd| of a hit in its hit-buffer entry) by the generated kernels compiled
 // with pruning and by the library's interpreter kernels
 #if defined(RM_JIT_PRUNE_ON) || !defined(RM_JIT_TU)
@@ -968,6 +1001,17 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
     if (L.max_iter != 0u)
         start = f0 < L.min_dist ? START_HIT : (f0 > L.max_dist || L.max_iter <= 1u) ? START_DONE : START_MARCH;
     const float inf_f = __uint_as_float(0x7F800000u);
+    // The wave's anchor ("Pruning", anchored first step): a point of this launch and the reach of the value computed there; kept
+    // by the kernels whose wave-level culling reads the threshold -- the generated lattice kernels, the interpreter's masked loops
+#if defined(RM_JIT_PRUNE_ON)
+    constexpr bool ANCHOR = SPEC;
+#elif defined(RM_PRUNE_PLUMBING)
+    constexpr bool ANCHOR = !SPEC && (LOOP == 2 || LOOP == 4);
+#else
+    constexpr bool ANCHOR = false;
+#endif
+    float anc_x = 0.0f, anc_y = 0.0f, anc_z = 0.0f, anc_t = inf_f;  // wave-uniform; never reset between tiles
+    unsigned long long anc_due = 0ull;  // wave-uniform, all ones: rays were handed out, the next march evaluation is captured
 
     const unsigned long long t_start = L.stats ? __builtin_amdgcn_s_memrealtime() : 0ull;
     // (diagnostics, RM_OPT_WAVE_STATS; a generated kernel keeps them only when it was compiled for that: RM_NO_WAVE_STATS, rm_jit.h)
@@ -1092,9 +1136,13 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
                             sc = shared ? 0.0f + f0 : 0.0f;  // dist (wgsl:88), dist += scene_dist (wgsl:114)
                             itr = rid | (shared ? 1024u : 0u);
                             thr_base = shared ? __builtin_fabsf(f0) * 2.00002f : inf_f;
+                            if constexpr (ANCHOR) {  // the step's own expression for its first point: the same bits
+                                if (shared) thr_base = anchor_thr_base(thr_base, ro.x + dx * sc, ro.y + dy * sc, ro.z + dz * sc, anc_x, anc_y, anc_z, anc_t);
+                            }
                         }
                     }
                     rq_pos += n_want < avail ? n_want : avail;
+                    if constexpr (ANCHOR) anc_due = ~0ull;
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                     want = __ballot(lane_empty());
                 }
@@ -1247,6 +1295,19 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
 #endif
             const unsigned long long miss_mask = esc_m | (go_m & __ballot(itr >= iter_limit));             // loop bound, wgsl:90
             const unsigned long long done_m = hit_mask | miss_mask;
+            if constexpr (ANCHOR) {
+                if ((done_m | anc_due) == 0ull) continue;  // (as below; one scalar OR is all a step pays for the capture)
+                if (anc_due != 0ull) {  // first evaluation after rays were handed out: the first live lane's point and value
+                    const int al = (int)__builtin_ctzll(live_m);  // (section A leaves a marching lane: live_m != 0)
+                    const float at = anchor_reach(ex, ey, ez, sd, prune_scale);
+                    anc_x = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(ex), al));
+                    anc_y = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(ey), al));
+                    anc_z = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(ez), al));
+                    anc_t = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(at), al));
+                    anc_due = 0ull;
+                    if (done_m == 0ull) continue;
+                }
+            }
             if (done_m == 0ull) continue;  // every live ray goes on: nothing section A asks about has changed
             const bool hit = is_live && sd < L.min_dist, miss = lane_of(miss_mask, lane);
             if (hit_mask != 0ull) {  // -> hit buffer (capacity 128: a tap phase takes 64 as soon as 64 are waiting)

@@ -13,6 +13,7 @@
 // stacks live in per-wave LDS columns [slot][lane], sized by the host from the program's actual depths.
 #pragma once
 #include "rm_interp.h"
+#include "rm_kernel_v5.h"  // anchor_reach, anchor_thr_base for rm_selftest_anchor_kernel
 
 namespace rmk {
 
@@ -257,6 +258,25 @@ __global__ __launch_bounds__(256) void rm_camera_rays_kernel(rm_uniforms u, uint
     gen_ray_at(u.inv_proj, u.inv_view, ro, screen_x(px, W), screen_y(py, H), ox, oy, dx, dy, dz);
     out[6u * i] = ro.x; out[6u * i + 1u] = ro.y; out[6u * i + 2u] = ro.z;
     out[6u * i + 3u] = dx; out[6u * i + 4u] = dy; out[6u * i + 5u] = dz;
+}
+
+// ---- rm_selftest_anchor: the anchored threshold of a first own step (rm_kernel_v5.h "Pruning") on pairs (a, q) ----------------
+// The march's own two functions around two evaluations of the program: out[4 i + ..] = aT, anchor_thr_base(+inf, ...) plus the
+// step's position term, F(a), F(q).  prune_scale: the march kernel's (scene_scale + |ro|_1).
+template <int LOOP>
+__global__ __launch_bounds__(256) void rm_selftest_anchor_kernel(QueryLaunch Q, float prune_scale, uint32_t n, const float* __restrict__ pairs,
+                                                                 float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    float* spill = query_spill(Q.slots);
+    const float ax = pairs[6u * i], ay = pairs[6u * i + 1u], az = pairs[6u * i + 2u];
+    const float qx = pairs[6u * i + 3u], qy = pairs[6u * i + 4u], qz = pairs[6u * i + 5u];
+    const float fa = query_distance<LOOP>(Q, spill, ax, ay, az);
+    const float fq = query_distance<LOOP>(Q, spill, qx, qy, qz);
+    const float aT = anchor_reach(ax, ay, az, fa, prune_scale);
+    const float thr_base = anchor_thr_base(__uint_as_float(0x7F800000u), qx, qy, qz, ax, ay, az, aT);
+    const float thr = thr_base + kPruneAbs * (prune_scale + ((__builtin_fabsf(qx) + __builtin_fabsf(qy)) + __builtin_fabsf(qz)));
+    out[4u * i] = aT; out[4u * i + 1u] = thr; out[4u * i + 2u] = fa; out[4u * i + 3u] = fq;
 }
 
 }  // namespace rmk

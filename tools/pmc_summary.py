@@ -22,6 +22,8 @@ def main():
             for r in csv.DictReader(open(f)):
                 k = short(r["Kernel_Name"])
                 agg[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
+                if r.get("Start_Timestamp") and r.get("End_Timestamp"):   # the dispatch's duration in this counter pass, once per row
+                    agg[k]["kernel_duration_us"].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
                 meta[k] = (r.get("VGPR_Count"), r.get("SGPR_Count"), r.get("LDS_Block_Size"), r.get("Scratch_Size"),
                            r.get("Grid_Size"), r.get("Workgroup_Size"))
             for k in agg:

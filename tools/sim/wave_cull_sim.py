@@ -12,7 +12,14 @@ starts at dist = f0 with threshold 2 |f0| and that evaluation is not counted.  T
     L2       Euclidean norm (shipped until round 14: three multiply-adds and a square root per lane)
     L1       sum of the magnitudes (shipped: two additions)
     Linf     sqrt(3) times the largest magnitude
-usage: wave_cull_sim.py [scene] [W H] [n_batches]"""
+With --anchor (lattice programs) two more tables follow, for the anchored first step (rm_kernel_v5.h "Pruning"):
+  per step index   leaves evaluated per wave-iteration under the shipped L1 rule and under the ideal -- the exact rule with the
+                   threshold |F| at the point itself --, by the index of the march step (2 = a batch's first own step)
+  anchor policies  a wave marches four batches of a tile in turn (batches w, w + 4, w + 8, w + 12 of the tile's claim order, w random;
+                   n_batches / 2 tiles); the anchor is the first live lane's position and value at the first evaluation of the wave's
+                   previous batch, thr = min(2 |f0|, |F_a| + |q - p_a|_1) at the first own step: none (shipped), taken inside the tile
+                   (the wave's first batch of each tile as shipped), and carried over from the previously drawn tile (a random one)
+usage: wave_cull_sim.py [scene] [W H] [n_batches] [--anchor]"""
 import os
 import sys
 
@@ -24,6 +31,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import scenes  # noqa: E402
 from oracle import cbind  # noqa: E402
 
+ANCHOR = "--anchor" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--anchor"]
 scene = sys.argv[1] if len(sys.argv) > 1 else "g32"
 W, H = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (1920, 1080)
 NT = int(sys.argv[4]) if len(sys.argv) > 4 else 300
@@ -175,6 +184,82 @@ print("leaves of %d evaluated per wave-iteration: per-lane average %.2f" % (N, s
 for rule, label in (("exact", "exact per-lane union (ideal)"), ("pairs", "pair + box tests per lane (rounds 1, 2)"), ("rho+T", "rho + T, two reductions"),
                     ("L2", "L2 reach, one reduction"), ("L1", "L1 reach, one reduction (shipped)"), ("Linf", "sqrt(3) Linf reach, one reduction")):
     print("  %-42s %.2f" % (label, stat[rule] / it))
+
+# ---- the anchored first step: leaves per step index, and what an anchor from the wave's previous batch saves ---------------
+if ANCHOR and MIN_D <= F0 <= MAX_D and not any(isinstance(c[2], tuple) for c in chain):
+    CLAIM = [(0xEDB87421A965FC30 >> (4 * k)) & 15 for k in range(16)]   # k-th batch of a tile's pool -> its 2x2 block (rm_kernel_v5.h)
+
+    def march_batch(tx, ty, blk):
+        """the own steps of one batch, [(live, p, v, F, thr)], or None when fewer than 8 of its rays hit (as above)"""
+        px = (tx * 8 + 2 * (blk & 3) + (lane & 1)).astype(float)
+        py = (ty * 8 + 2 * (blk >> 2) + ((lane >> 1) & 1)).astype(float)
+        d = np.concatenate([rays(px[4 * s:4 * s + 4], py[4 * s:4 * s + 4], s) for s in range(16)])
+        sc, live, hit, thr, steps = np.full(64, F0), np.ones(64, bool), np.zeros(64, bool), np.full(64, 2 * abs(F0)), []
+        for it in range(1, MAX_ITER):
+            if not live.any():
+                break
+            p = ro[None] + d * sc[:, None]
+            v = leaf_values(p)
+            F = fold(v)
+            steps.append((live.copy(), p, v, F, thr.copy()))
+            h = live & (F < MIN_D)
+            hit |= h
+            go = live & ~h & ~(F > MAX_D)
+            sc = np.where(go, sc + F, sc)
+            thr = np.where(go, 2 * np.abs(F), thr)
+            live = go
+        return steps if hit.sum() >= 8 else None
+
+    def l1_count(live, p, thr):
+        pl, tl = p[live], thr[live]
+        gap = np.linalg.norm(C - pl[0][None], axis=1) - RB
+        return int((gap <= (np.abs(pl - pl[0][None]).sum(axis=1) + tl).max()).sum())
+
+    def anchored(thr, p, anchor):
+        return thr if anchor is None else np.minimum(thr, abs(anchor[1]) + np.abs(p - anchor[0][None]).sum(axis=1))
+
+    rng = np.random.default_rng(2)
+    by_step = {}                                     # step index -> [shipped L1, ideal, wave-iterations]
+    POLICIES = ("shipped", "inside the tile", "carried over")
+    first = dict.fromkeys(POLICIES, 0)
+    total = dict.fromkeys(POLICIES, 0)
+    n_first, tiles, attempts, carried = 0, 0, 0, None
+    while tiles < max(NT // 2, 1) and attempts < 40 * NT:
+        attempts += 1
+        tx, ty, w0 = int(rng.integers(tiles_x)), int(rng.integers(tiles_y)), int(rng.integers(4))
+        inside, marched = None, False
+        for k in range(w0, 16, 4):
+            steps = march_batch(tx, ty, CLAIM[k])
+            if steps is None:
+                continue
+            marched = True
+            for idx, (live, p, v, F, thr) in enumerate(steps):
+                n = l1_count(live, p, thr)
+                row = by_step.setdefault(idx + 2, [0, 0, 0])
+                row[0] += n
+                row[1] += int((v[live] <= np.abs(F[live])[:, None]).any(axis=0).sum())
+                row[2] += 1
+                for pol, anchor in zip(POLICIES, (None, inside, carried)):
+                    m = n if idx > 0 or anchor is None else l1_count(live, p, anchored(thr, p, anchor))
+                    total[pol] += m
+                    if idx == 0:
+                        first[pol] += m
+            n_first += 1
+            live, p, v, F, thr = steps[0]
+            k0 = int(np.argmax(live))
+            inside = carried = (p[k0].copy(), float(F[k0]))
+        tiles += int(marched)
+    print("anchored first step: %d tiles, %d marched batches, one wave of four batches per tile" % (tiles, n_first))
+    print("  step   wave-iterations   shipped L1   ideal (thr = |F| at the point)")
+    for idx in sorted(by_step)[:14]:
+        a, b, n = by_step[idx]
+        print("  %4d   %15d   %10.2f   %5.2f" % (idx, n, a / n, b / n))
+    n_all = sum(r[2] for r in by_step.values())
+    print("   all   %15d   %10.2f   %5.2f" % (n_all, sum(r[0] for r in by_step.values()) / n_all, sum(r[1] for r in by_step.values()) / n_all))
+    print("  share of the first own step in the shipped rule's leaf evaluations: %.1f %%" % (100.0 * first["shipped"] / total["shipped"]))
+    print("  anchor policy      first own step, leaves of %d   all march-step leaf evaluations" % N)
+    for pol in POLICIES:
+        print("  %-16s   %28.2f   %8d (%+.1f %%)" % (pol, first[pol] / max(n_first, 1), total[pol], 100.0 * (total[pol] / total["shipped"] - 1.0)))
 
 # ---- programs that blend: the local rule, per lane and through the wave's ball -----------------------------------------
 if any(isinstance(c[2], tuple) for c in chain):

@@ -25,6 +25,8 @@ for line in summary.splitlines():
         counters.setdefault(kernel, {})[m.group(1)] = float(m.group(2))
         if m.group(1) == "GRBM_GUI_ACTIVE":
             grbm.setdefault(kernel, {})[run] = float(m.group(2))
+        if m.group(1) == "kernel_duration_us":   # (a counter pass without a kernel trace of its own: the durations of its dispatches)
+            durations.setdefault((run, kernel), float(m.group(2)))
 detail = {}
 total = 0.0
 for k in ("rm_tile_pre_v5", "rm_tile_sort_v5", "rm_render_v5_spec"):
@@ -38,6 +40,7 @@ c = counters["rm_render_v5_spec"]
 for key in ("SQ_INSTS_VALU", "SQ_INSTS_VALU_ADD_F32", "SQ_INSTS_VALU_MUL_F32", "SQ_INSTS_VALU_FMA_F32", "SQ_INSTS_VALU_TRANS_F32",
             "SQ_INSTS_VALU_INT32", "SQ_INSTS_SALU", "SQ_INSTS_BRANCH", "SQ_INSTS_LDS", "SQ_ACTIVE_INST_LDS", "GRBM_GUI_ACTIVE"):
     v[key] = c[key]
+v["source"] = sys.argv[1]
 # the clock of the pass that counted GRBM_GUI_ACTIVE (8 XCDs), over that pass's own kernel duration (PMC passes serialise the
 # kernels: their durations are a few % above the plain trace's)
 run = sorted(grbm["rm_render_v5_spec"])[0]
