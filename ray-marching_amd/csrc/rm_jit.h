@@ -19,6 +19,7 @@
 // cached per (structure, waves per tile).  Everything falls back to the interpreter kernel:
 // hipRTC missing, a compile error, an empty or very long program.
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -152,8 +153,11 @@ enum : int { KERNEL_WITH_STATS = 0x100, PRUNE_KIND_MASK = 0xFF };
 //                      SmoothUnion / Subtraction / Intersection (skipped: the accumulator stays), an opaque stretch of records
 // Returns false if the records do not form a valid program (cannot happen for the output of rm_decode_program) or the
 // program has no units of the kind asked for.
-inline bool generate_scene_code(const std::vector<RmRecord>& rec, int prune, int T, std::string* out) {
-    const int count_mode = (prune && T == 1) ? jit_knob("RM_JIT_PRUNE_STATS", 0) : 0;  // 1: leaves evaluated (tools/wave_stats.py)
+// walk_out (nullable, T = 1): map_scene_walk<FAST>, the single-unit path in front of map_scene_spec ("Single-unit steps" below); left
+// empty when the program gets none.
+inline bool generate_scene_code(const std::vector<RmRecord>& rec, int prune, int T, std::string* out, std::string* walk_out = nullptr) {
+    // 1: leaves evaluated, 5: evaluations that took the single-unit path (tools/wave_stats.py)
+    const int count_mode = (prune && T == 1) ? jit_knob("RM_JIT_PRUNE_STATS", 0) : 0;
     const char* counted = count_mode == 1 ? " n_eval += 1u;" : "";
     // A scheduling barrier after every few leaves: left alone the compiler hoists the parameter loads of the whole
     // program to the top of the straight-line code (88 VGPRs for 16 leaves, 120-139 for 32: 3 waves per SIMD);
@@ -166,6 +170,48 @@ inline bool generate_scene_code(const std::vector<RmRecord>& rec, int prune, int
     if (prune == PRUNE_BLEND && !rm_blend_units(rec, &units)) return false;
     std::vector<int> unit_at(rec.size(), -1);
     for (size_t u = 0; u < units.size(); u++) unit_at[(size_t)units[u].first] = (int)u;
+
+    // Single-unit steps (RM_JIT_UNIT_WALK).  More than half of the march steps of a lattice scene need ONE unit (the rays of a wave
+    // are near one primitive), and the straight-line code below still pays every group test and the bit tests of the group it
+    // enters to find it.  For programs whose unit u is record u and whose mask is one word -- chains of at most 32 leaves, trees
+    // that push their leaves before they combine them -- and unless RM_JIT_UNIT_WALK is 0 (the default is 1), map_scene_walk
+    // finds the unit with a find-first-set on the mask and returns what the straight-line code returns with every other unit
+    // skipped.  That value is worked out HERE, by the walk that emits the straight-line code: next to every value it names, the
+    // walk keeps what the value is when all units are skipped (`cst`: +inf or -inf) and, for every unit u it has met, what it is
+    // when u alone is evaluated (`one[u]`): a constant -- nothing is evaluated then --, or an expression in the leaf's value "@"
+    // that applies the operators the value still meets, with the constants in the other operand, in program order ("vmin(inf, @)":
+    // a NaN leaf comes out as +inf, as it does below).  Operators with two constant operands fold by min / max of infinities.
+    struct One { int state; float c; std::string expr; };  // state: 0 constant c, 1 expression, 2 not worked out (the step takes the code below)
+    struct Sym { float cst; std::map<int, One> one; };
+    const float kInf = INFINITY;
+    const int walk_knob = jit_knob("RM_JIT_UNIT_WALK", 1);
+    bool walk_ok = walk_out != nullptr && T == 1 && prune == PRUNE_LATTICE && walk_knob != 0 && units.size() >= 2 && units.size() <= 32;
+    for (size_t u = 0; walk_ok && u < units.size(); u++) walk_ok = units[u].first == (int)u && units[u].last == (int)u;
+    std::map<int, Sym> sym;  // by value number
+    auto cname = [&](float c) { return std::string(c > 0.0f ? "inf" : "-inf"); };
+    // op(l, r), at most one of them an expression
+    auto fold = [&](uint32_t mode, const One& l, const One& r) -> One {
+        if (l.state == 2 || r.state == 2 || (l.state == 1 && r.state == 1)) return One{2, 0.0f, ""};
+        const char* fn = mode == RM_MODE_UNION ? "vmin" : mode == RM_MODE_SUB ? "vmax_negb" : "fmax_";
+        if (l.state == 0 && r.state == 0)
+            return One{0, mode == RM_MODE_UNION ? std::fmin(l.c, r.c) : mode == RM_MODE_SUB ? std::fmax(l.c, -r.c) : std::fmax(l.c, r.c), ""};
+        // a constant that decides the result whatever the other operand is (a NaN loses in v_min_f32 / v_max_f32)
+        if (l.state == 0) {
+            if (mode == RM_MODE_UNION ? l.c < 0.0f : l.c > 0.0f) return One{0, l.c, ""};
+            return One{1, 0.0f, std::string(fn) + "(" + cname(l.c) + ", " + r.expr + ")"};
+        }
+        if (mode == RM_MODE_UNION ? r.c < 0.0f : mode == RM_MODE_SUB ? r.c < 0.0f : r.c > 0.0f) return One{0, mode == RM_MODE_UNION ? r.c : kInf, ""};
+        return One{1, 0.0f, std::string(fn) + "(" + l.expr + ", " + cname(r.c) + ")"};
+    };
+    auto sym_pop = [&](uint32_t mode, int a, int b, int w) {  // w = op(a, b) on two named values
+        if (!walk_ok) return;
+        const Sym &A = sym[a], &B = sym[b];
+        Sym W;
+        W.cst = fold(mode, One{0, A.cst, ""}, One{0, B.cst, ""}).c;
+        for (const auto& kv : A.one) W.one[kv.first] = fold(mode, kv.second, One{0, B.cst, ""});
+        for (const auto& kv : B.one) W.one[kv.first] = fold(mode, One{0, A.cst, ""}, kv.second);
+        sym[w] = std::move(W);
+    };
 
     std::string s;
     char line[1024];
@@ -237,6 +283,7 @@ inline bool generate_scene_code(const std::vector<RmRecord>& rec, int prune, int
             const unsigned off = (unsigned)i * 8u;
             if (kind == RM_KIND_MATERIAL) return false;  // (`rec` never holds tags)
             if (kind == RM_KIND_XFORM) {  // space transformation: a new position value (push) or back to the enclosing one (pop)
+                walk_ok = false;  // (not in a lattice program)
                 const int c = pos.back();
                 if ((mode & 1u) == 0u) {
                     const int n = ++np;
@@ -276,9 +323,11 @@ inline bool generate_scene_code(const std::vector<RmRecord>& rec, int prune, int
                 const int a = stack.back(); stack.pop_back();
                 const int w = nv++;
                 if (mode == RM_MODE_SMOOTH) {
+                    walk_ok = false;
                     emit_smooth("const float ", w, off, names(a), names(b), ind);
                 } else {
                     if (!op) return false;
+                    sym_pop(mode, a, b, w);
                     for (int t = 0; t < T; t++) {
                         std::snprintf(line, sizeof line, "%sconst float %s = %s(%s, %s);\n", ind, V(w, t).c_str(), op, V(a, t).c_str(), V(b, t).c_str());
                         s += line;
@@ -288,6 +337,7 @@ inline bool generate_scene_code(const std::vector<RmRecord>& rec, int prune, int
                 continue;
             }
             if (!leaf_fn(kind) || mode == RM_MODE_SMOOTH || (mode != RM_MODE_PUSH && !op)) return false;  // the decoder never fuses an operator with a parameter
+            walk_ok = false;  // a leaf that is no unit (not in a lattice program)
             int a = -1;
             if (mode != RM_MODE_PUSH) {
                 if (stack.empty()) return false;
@@ -374,11 +424,13 @@ inline bool generate_scene_code(const std::vector<RmRecord>& rec, int prune, int
             if (group_left == 0 || --group_left != 0) return;
             for (int t = 0; t < T; t++) { std::snprintf(line, sizeof line, "        %s = %s;\n", V(group_value, t).c_str(), V(stack.back(), t).c_str()); s += line; }
             s += "    } }\n";
+            if (walk_ok) sym[group_value] = sym[stack.back()];  // (skipped whole, the group's value is what its units leave when each is skipped)
             stack.back() = group_value;
         };
         if (u.kind == RM_UNIT_OPAQUE) {
             // an opaque stretch of the chain: from the accumulator to its next value; evaluated unless it is dead
             if (stack.empty()) return false;
+            walk_ok = false;
             const int a = stack.back();
             const int w = nv++;
             for (int t = 0; t < T; t++) { std::snprintf(line, sizeof line, "    float %s = %s;\n", V(w, t).c_str(), V(a, t).c_str()); s += line; }
@@ -403,6 +455,18 @@ inline bool generate_scene_code(const std::vector<RmRecord>& rec, int prune, int
         }
         const int w = nv++;
         const bool to_inf = eff_mode == RM_MODE_PUSH || (eff_mode == RM_MODE_INTER && u.kind == RM_UNIT_LEAF);
+        if (with_smooth) walk_ok = false;
+        if (walk_ok) {  // skipped, the unit leaves +inf or the accumulator; evaluated alone, its operator meets the accumulator's constant
+            Sym W;
+            W.cst = to_inf ? kInf : sym[a].cst;
+            if (!to_inf) W.one = sym[a].one;
+            if (eff_mode == RM_MODE_PUSH) W.one[ui] = One{1, 0.0f, "@"};
+            else W.one[ui] = fold(eff_mode, One{0, sym[a].cst, ""}, One{1, 0.0f, "@"});
+            // (a subtracted leaf behind its local test returns the accumulator or max(acc, -v): with acc = +inf both are +inf -- the
+            // constant fold found; any other accumulator goes through the code below)
+            if (eff_mode == RM_MODE_SUB && W.one[ui].state != 0) W.one[ui] = One{2, 0.0f, ""};
+            sym[w] = std::move(W);
+        }
         for (int t = 0; t < T; t++) {
             if (to_inf) std::snprintf(line, sizeof line, "    float %s = inf;\n", V(w, t).c_str());
             else std::snprintf(line, sizeof line, "    float %s = %s;\n", V(w, t).c_str(), V(a, t).c_str());
@@ -445,6 +509,63 @@ inline bool generate_scene_code(const std::vector<RmRecord>& rec, int prune, int
     if (T == 1) {
         std::snprintf(line, sizeof line, "    return %s;\n}\n}  // namespace rmk\n", V(stack.back(), 0).c_str());
         s += line;
+        if (walk_out) walk_out->clear();
+        if (walk_ok) {
+            // The units by what a step that needs only them returns: one class per constant, per (leaf kind, expression), and a last
+            // one for the units whose step takes the straight-line code.  Every class is ONE test of the mask word -- one bit -- against
+            // the constant set of its units (s_and_b32, s_cmp, branch), the classes with the most units first; the last class needs none.
+            struct Class { std::string key, action; uint32_t mask; bool open; };
+            std::vector<Class> classes;
+            const Sym& R = sym[stack.back()];
+            const char* count = count_mode == 1 || count_mode == 5 ? " n_eval += 1u;" : "";
+            for (size_t u = 0; u < units.size(); u++) {
+                const auto it = R.one.find((int)u);
+                const One o = it == R.one.end() ? One{0, R.cst, ""} : it->second;
+                Class c;
+                c.mask = 1u << u;
+                c.open = o.state == 2;
+                if (o.state == 0) {
+                    c.key = "c" + cname(o.c);
+                    c.action = std::string(count) + " return " + cname(o.c) + ";";
+                } else if (o.state == 1) {
+                    const uint32_t kind = RM_OP_KIND(rec[(size_t)units[u].first].op);
+                    std::string call = std::string(leaf_fn(kind)) + "(r, qx, qy, qz, tiny)", e = o.expr;
+                    e.replace(e.find('@'), 1, call);
+                    if (o.expr == "vmin(inf, @)") e = "vmin_pinf(" + call + ")";  // (the constant as a literal of the instruction, not a register)
+                    c.key = std::to_string(kind) + "|" + o.expr;
+                    c.action = std::string(count) + " return " + e + ";";
+                } else {
+                    c.key = "open";
+                }
+                size_t k = 0;
+                while (k < classes.size() && classes[k].key != c.key) k++;
+                if (k == classes.size()) classes.push_back(c);
+                else classes[k].mask |= c.mask;
+            }
+            std::stable_sort(classes.begin(), classes.end(), [](const Class& a, const Class& b) {
+                if (a.open != b.open) return b.open;
+                return __builtin_popcount(a.mask) > __builtin_popcount(b.mask);
+            });
+            std::string w;
+            w += "namespace rmk {\ntemplate <bool FAST>\n";
+            w += "RM_DEV float map_scene_walk(LdsF lp, float qx, float qy, float qz, unsigned long long need, unsigned long long live, SqrtGuard& tiny, uint32_t& n_eval) {\n";
+            w += "    const uint32_t m = (uint32_t)need;\n";
+            // (the count as an instruction of its own: the test stays a scalar compare and a branch where it stands; __builtin_popcount
+            // the compiler shares with the second evaluation behind the sqrt guard, as a 64-bit boolean -- s_cselect_b64, s_and_b64 vcc,
+            // s_cbranch_vccz -- or as a register it copies first)
+            w += "    uint32_t n_units;\n    asm volatile(\"s_bcnt1_i32_b32 %0, %1\" : \"=s\"(n_units) : \"s\"(m) : \"scc\");\n";
+            w += "    if (n_units == 1u) {  // exactly one unit: s_bcnt1_i32_b32, s_cmp_lg_u32, branch\n";
+            w += "        const float inf = __uint_as_float(0x7F800000u);\n";
+            w += "        const LdsF r = lp + 8u * (uint32_t)__builtin_ctz(m);\n";
+            for (size_t k = 0; k < classes.size(); k++) {
+                if (classes[k].open) break;  // (sorted last)
+                if (k + 1 < classes.size()) std::snprintf(line, sizeof line, "        if ((m & 0x%xu) != 0u) {%s }\n", classes[k].mask, classes[k].action.c_str());
+                else std::snprintf(line, sizeof line, "       %s\n", classes[k].action.c_str());
+                w += line;
+            }
+            w += "    }\n    return map_scene_spec<FAST>(lp, qx, qy, qz, need, live, tiny, n_eval);\n}\n}  // namespace rmk\n";
+            *walk_out = std::move(w);
+        }
     } else {
         for (int t = 0; t < 4; t++) {
             std::snprintf(line, sizeof line, "    f[%d] = %s;\n", t, V(stack.back(), t).c_str());
@@ -601,8 +722,8 @@ inline bool generate_source(const std::vector<RmRecord>& rec, const std::vector<
     const bool materials = !mrec.empty();
     const bool with_stats = (prune_kind & KERNEL_WITH_STATS) != 0;
     prune_kind &= PRUNE_KIND_MASK;
-    std::string body, taps, walk;
-    if (!generate_scene_code(rec, prune_kind, 1, &body)) return false;
+    std::string body, taps, walk, unit_walk;
+    if (!generate_scene_code(rec, prune_kind, 1, &body, &unit_walk)) return false;
     const bool walk_spec = materials && mrec.size() <= kMaxRecords && generate_material_walk(mrec, &walk);
     if (walk_generated) *walk_generated = walk_spec;
     const bool taps4 = generate_scene_code(rec, prune_kind, 4, &taps);
@@ -620,8 +741,11 @@ inline bool generate_source(const std::vector<RmRecord>& rec, const std::vector<
     if (walk_spec) s += "#define RM_JIT_MATERIAL_WALK 1\n";
     if (structure_allows_bound_walk(rec)) s += "#define RM_JIT_BOUND_WALK 1\n";
     if (!with_stats) s += "#define RM_NO_WAVE_STATS 1\n";
+    if (!unit_walk.empty()) s += "#define RM_JIT_UNIT_WALK 1\n";
+    if (prune_kind && jit_knob("RM_JIT_PRUNE_STATS", 0) == 5) s += "#define RM_JIT_WALK_COUNTER 1\n";
     s += "#include \"rm_kernel_v5.h\"\n";
     s += body;
+    s += unit_walk;
     if (taps4) s += taps;
     if (walk_spec) s += walk;
     char line[512];
@@ -898,7 +1022,7 @@ public:
     std::shared_ptr<Entry> request(const std::vector<RmRecord>& rec, const std::vector<RmRecord>& mrec, int wpt, int prune) {
         // a tagged program's kernel also depends on where its tags sit (the material walk is generated from mrec), and on the
         // knobs of the generator as the environment holds them now (so that a process may compare two settings)
-        static const char* const knobs[] = {"RM_JIT_PRUNE_STATS", "RM_JIT_SUB_TESTS", "RM_JIT_UNIT_GROUPS", "RM_JIT_PROBE_CAP"};
+        static const char* const knobs[] = {"RM_JIT_PRUNE_STATS", "RM_JIT_SUB_TESTS", "RM_JIT_UNIT_GROUPS", "RM_JIT_UNIT_WALK", "RM_JIT_PROBE_CAP"};
         std::string knob_key;
         for (const char* name : knobs)
             if (const char* v = std::getenv(name)) knob_key += std::string("|") + name + "=" + v;

@@ -53,6 +53,16 @@ RM_DEV LdsF lds_vector_base(const void* generic_lds_ptr) {
 // when the kernel does not cull); `live`: wave mask of the lanes whose value will be used
 template <bool FAST>
 RM_DEV float map_scene_spec(LdsF lp, float qx, float qy, float qz, unsigned long long need, unsigned long long live, SqrtGuard& tiny, uint32_t& n_eval);
+#ifdef RM_JIT_UNIT_WALK
+// map_scene_spec behind the single-unit path (rm_jit.h "Single-unit steps"): a step whose mask holds one unit evaluates that leaf
+// at an LDS address computed from the bit's position instead of walking the tests of the straight-line code; the same value, bit
+// for bit.  The march steps call this one.
+template <bool FAST>
+RM_DEV float map_scene_walk(LdsF lp, float qx, float qy, float qz, unsigned long long need, unsigned long long live, SqrtGuard& tiny, uint32_t& n_eval);
+#define RM_MAP_SCENE_STEP map_scene_walk
+#else
+#define RM_MAP_SCENE_STEP map_scene_spec
+#endif
 #ifdef RM_JIT_MATERIAL_WALK
 // The material walk of a tagged program as straight-line code (rm_jit.h generate_material_walk): which material does the
 // surface at (x, y, z) carry.  mp: the tagged records in device memory (uniform addresses: scalar loads).
@@ -395,6 +405,14 @@ RM_DEV uint32_t unit_word(unsigned long long need, uint32_t u) {
     return w;
 }
 RM_DEV bool unit_in_word(uint32_t w, uint32_t u) { return ((w >> (u & 31u)) & 1u) != 0u; }
+// vmin(+inf, b) of the single-unit path (rm_jit.h "Single-unit steps"): the v_min_f32 a Union applies to a skipped (+inf) accumulator
+// and the one leaf of the step, with +inf as a literal of the instruction -- as a register it is one more value live across the march
+// loop of a kernel that sits at its register limit.  b for every number, +inf for a NaN.
+RM_DEV float vmin_pinf(float b) {
+    float r;
+    asm("v_min_f32 %0, 0x7f800000, %1" : "=v"(r) : "v"(b));
+    return r;
+}
 
 typedef float lds_f4 __attribute__((ext_vector_type(4)));
 typedef float lds_f2 __attribute__((ext_vector_type(2)));
@@ -945,13 +963,13 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
         SqrtGuard tiny;
         if constexpr (SPEC) {  // straight-line code compiled for this program's structure (rm_jit.h)
             const unsigned long long need = units_needed(x, y, z, thr, 0.0f, is_live, live_mask);
-            v[0] = map_scene_spec<true>(lprog_v, x, y, z, need, live_mask, tiny, n_eval);
+            v[0] = RM_MAP_SCENE_STEP<true>(lprog_v, x, y, z, need, live_mask, tiny, n_eval);
             if (tiny.any_bad()) {
                 // (an empty volatile asm keeps this a branch: for a program of one or two leaves the compiler otherwise
                 // evaluates both forms at every step and selects -- a second square root and 16 more vector instructions)
                 asm volatile("");
                 uint32_t again = 0u;
-                v[0] = map_scene_spec<false>(lprog_v, x, y, z, need, live_mask, tiny, again);
+                v[0] = RM_MAP_SCENE_STEP<false>(lprog_v, x, y, z, need, live_mask, tiny, again);
             }
         } else if (LOOP == 1 || LOOP == 2 || (LOOP == 0 && (L.flags & 4u))) {  // chain program (wave-uniform): the stack-free record loop
             const unsigned long long need = units_needed(x, y, z, thr, 0.0f, is_live, live_mask);
@@ -1396,7 +1414,11 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
         st[0] = t_start;
         st[1] = __builtin_amdgcn_s_memrealtime();
         st[2] = ((unsigned long long)n_tiles_done << 32) | n_iter;
+#ifdef RM_JIT_WALK_COUNTER  // RM_JIT_PRUNE_STATS=5: evaluations that took the single-unit path -- a count that may well be zero
+        st[3] = ((unsigned long long)n_eval << 32) | n_live;
+#else
         st[3] = ((unsigned long long)(n_eval != 0u ? n_eval : n_prod) << 32) | n_live;
+#endif
     }
 }
 

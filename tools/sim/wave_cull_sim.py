@@ -12,13 +12,15 @@ starts at dist = f0 with threshold 2 |f0| and that evaluation is not counted.  T
     L2       Euclidean norm (shipped until round 14: three multiply-adds and a square root per lane)
     L1       sum of the magnitudes (shipped: two additions)
     Linf     sqrt(3) times the largest magnitude
-With --anchor (lattice programs) two more tables follow, for the anchored first step (rm_kernel_v5.h "Pruning"):
+With --anchor (lattice programs) three more tables follow, for the anchored first step (rm_kernel_v5.h "Pruning"):
   per step index   leaves evaluated per wave-iteration under the shipped L1 rule and under the ideal -- the exact rule with the
                    threshold |F| at the point itself --, by the index of the march step (2 = a batch's first own step)
   anchor policies  a wave marches four batches of a tile in turn (batches w, w + 4, w + 8, w + 12 of the tile's claim order, w random;
                    n_batches / 2 tiles); the anchor is the first live lane's position and value at the first evaluation of the wave's
                    previous batch, thr = min(2 |f0|, |F_a| + |q - p_a|_1) at the first own step: none (shipped), taken inside the tile
                    (the wave's first batch of each tile as shipped), and carried over from the previously drawn tile (a random one)
+  units per step   under "carried over", which the device matches: how many units a wave-step needs (the share of steps with 1, 2, ...)
+                   and how many groups of four units are not empty -- what the single-unit path of rm_jit.h is sized by
 usage: wave_cull_sim.py [scene] [W H] [n_batches] [--anchor]"""
 import os
 import sys
@@ -210,10 +212,13 @@ if ANCHOR and MIN_D <= F0 <= MAX_D and not any(isinstance(c[2], tuple) for c in 
             live = go
         return steps if hit.sum() >= 8 else None
 
-    def l1_count(live, p, thr):
+    def l1_mask(live, p, thr):
         pl, tl = p[live], thr[live]
         gap = np.linalg.norm(C - pl[0][None], axis=1) - RB
-        return int((gap <= (np.abs(pl - pl[0][None]).sum(axis=1) + tl).max()).sum())
+        return gap <= (np.abs(pl - pl[0][None]).sum(axis=1) + tl).max()
+
+    def l1_count(live, p, thr):
+        return int(l1_mask(live, p, thr).sum())
 
     def anchored(thr, p, anchor):
         return thr if anchor is None else np.minimum(thr, abs(anchor[1]) + np.abs(p - anchor[0][None]).sum(axis=1))
@@ -224,6 +229,7 @@ if ANCHOR and MIN_D <= F0 <= MAX_D and not any(isinstance(c[2], tuple) for c in 
     first = dict.fromkeys(POLICIES, 0)
     total = dict.fromkeys(POLICIES, 0)
     n_first, tiles, attempts, carried = 0, 0, 0, None
+    units_hist, groups_hist = {}, {}                 # "carried over" (the device's policy): units a wave-step needs, non-empty groups of four
     while tiles < max(NT // 2, 1) and attempts < 40 * NT:
         attempts += 1
         tx, ty, w0 = int(rng.integers(tiles_x)), int(rng.integers(tiles_y)), int(rng.integers(4))
@@ -244,6 +250,10 @@ if ANCHOR and MIN_D <= F0 <= MAX_D and not any(isinstance(c[2], tuple) for c in 
                     total[pol] += m
                     if idx == 0:
                         first[pol] += m
+                need = l1_mask(live, p, thr if idx > 0 or carried is None else anchored(thr, p, carried))
+                units_hist[int(need.sum())] = units_hist.get(int(need.sum()), 0) + 1
+                g = int(sum(need[k4:k4 + 4].any() for k4 in range(0, N, 4)))
+                groups_hist[g] = groups_hist.get(g, 0) + 1
             n_first += 1
             live, p, v, F, thr = steps[0]
             k0 = int(np.argmax(live))
@@ -260,6 +270,13 @@ if ANCHOR and MIN_D <= F0 <= MAX_D and not any(isinstance(c[2], tuple) for c in 
     print("  anchor policy      first own step, leaves of %d   all march-step leaf evaluations" % N)
     for pol in POLICIES:
         print("  %-16s   %28.2f   %8d (%+.1f %%)" % (pol, first[pol] / max(n_first, 1), total[pol], 100.0 * (total[pol] / total["shipped"] - 1.0)))
+    # what a march step pays to find its units (rm_jit.h "Single-unit steps"): how many it needs, in how many groups of four
+    n_steps = sum(units_hist.values())
+    print("  units needed per wave-step (carried over), %d wave-steps:" % n_steps)
+    print("    units   share of steps")
+    for k in sorted(units_hist)[:8]:
+        print("    %5d   %5.1f %%" % (k, 100.0 * units_hist[k] / n_steps))
+    print("    non-empty groups of four:  " + "  ".join("%d: %.0f %%" % (k, 100.0 * groups_hist[k] / n_steps) for k in sorted(groups_hist)))
 
 # ---- programs that blend: the local rule, per lane and through the wave's ball -----------------------------------------
 if any(isinstance(c[2], tuple) for c in chain):

@@ -21,7 +21,8 @@ p.add_argument("--wpt", type=int, default=4)
 p.add_argument("--no-cull", action="store_true")
 p.add_argument("--specialize", type=int, default=2)
 p.add_argument("--prune", action="store_true", help="pruned specialised kernel; with RM_JIT_PRUNE_STATS=1 in the environment the "
-               "'refills' field becomes the number of leaves evaluated")
+               "'refills' field becomes the number of leaves evaluated, with RM_JIT_PRUNE_STATS=5 the number of evaluations "
+               "that took the single-unit path (RM_JIT_UNIT_WALK)")
 p.add_argument("--refill-min", type=int, default=0)
 p.add_argument("--interp-stats", action="store_true", help="a library built with -DRM_INTERP_STATS (tools/ab_build.sh): the 'refills' field is the "
                "number of records the interpreter's masked loops executed")
@@ -66,8 +67,12 @@ if a.prune and os.environ.get("RM_JIT_PRUNE_STATS"):
     per = a.leaves if mode in ("1", "2") else a.leaves // 2
     if mode == "4":
         refills = refills / 64.0
-    print("%s: %.2f per iteration = %.3f of %d (iterations include tap phases, which are not counted)" % (
-        what, refills.sum() / max(1.0, float(iters.sum())), refills.sum() / max(1.0, float(iters.sum()) * per), per))
+    if mode == "5":   # RM_JIT_UNIT_WALK: the evaluations whose mask held exactly one unit (rm_jit.h "Single-unit steps")
+        print("evaluations through the single-unit path: %d of %d iterations = %.3f (iterations include tap phases, which do not take it)" % (
+            refills.sum(), iters.sum(), refills.sum() / max(1.0, float(iters.sum()))))
+    else:
+        print("%s: %.2f per iteration = %.3f of %d (iterations include tap phases, which are not counted)" % (
+            what, refills.sum() / max(1.0, float(iters.sum())), refills.sum() / max(1.0, float(iters.sum()) * per), per))
 if a.interp_stats:
     print("records executed: %.2f per iteration (iterations include tap phases: one evaluation each)" % (refills.sum() / max(1.0, float(iters.sum()))))
 k = np.argsort(-end)[:8]
