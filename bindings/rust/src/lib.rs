@@ -308,6 +308,36 @@ pub const RM_ISL_ROW_BELOW_MIN: c_int = 10;
 pub const RM_ISL_ROW_BELOW_MAX: c_int = 11;
 pub const RM_ISL_ROW_WORDS: c_int = 12;
 
+// Surface measures (rm_surface_solid / rm_surface_classes / rm_surface_directions / rm_surface_measures).
+// enum rm_surfcount: classes, directions, where POINTS and PAIR start in the counts of a surface call; RM_SURF_COUNTS is their number
+pub const RM_SURF_CLASSES: c_int = 8;
+pub const RM_SURF_DIRS: c_int = 13;
+pub const RM_SURF_POINTS: c_int = 0;
+pub const RM_SURF_PAIRS: c_int = 8;
+pub const RM_SURF_COUNTS: c_int = 840;
+// enum rm_surfstat: indices into the statistics of a surface call; RM_SURF_STATS is their number
+pub const RM_SURF_STAT_BRICKS: c_int = 0;
+pub const RM_SURF_STAT_BRICKS_KEPT: c_int = 1;
+pub const RM_SURF_STAT_BRICKS_INSIDE: c_int = 2;
+pub const RM_SURF_STAT_EVALUATIONS: c_int = 3;
+pub const RM_SURF_STAT_SCRATCH_BYTES: c_int = 4;
+pub const RM_SURF_STATS: c_int = 5;
+// enum rm_surfmeasure: indices into the output of rm_surface_measures; RM_SURF_MEASURES is their number
+pub const RM_SURF_AREA: c_int = 0;
+pub const RM_SURF_FACET_AREA: c_int = 1;
+pub const RM_SURF_FACET_POS_X: c_int = 2;
+pub const RM_SURF_FACET_NEG_X: c_int = 3;
+pub const RM_SURF_FACET_POS_Y: c_int = 4;
+pub const RM_SURF_FACET_NEG_Y: c_int = 5;
+pub const RM_SURF_FACET_POS_Z: c_int = 6;
+pub const RM_SURF_FACET_NEG_Z: c_int = 7;
+pub const RM_SURF_MEASURES: c_int = 8;
+
+/// The index of `PAIR[a][b][nu]` in the counts of a surface call (the header's `RM_SURF_PAIR`).
+pub const fn surf_pair(a: usize, b: usize, nu: usize) -> usize {
+    8 + (8 * a + b) * 13 + nu
+}
+
 // Slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table).
 // enum rm_slicecount: indices into the counts of rm_slice_contours; RM_SLICE_COUNTS is their number
 pub const RM_SLICE_POINTS: c_int = 0;
@@ -428,6 +458,13 @@ extern "C" {
                                 out_stats: *mut u64, n_stats: u32) -> c_int;
     pub fn rm_read_islands(ctx: *mut rm_ctx, out_rows: *mut u32, row_capacity: u64, out_labels: *mut u32, out_mask: *mut c_void,
                            out_profile: *mut u32, is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_surface_solid(ctx: *mut rm_ctx, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32, level: f32,
+                            out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_surface_classes(ctx: *mut rm_ctx, nx: u32, ny: u32, nz: u32, classes: *const c_void, is_device: c_int,
+                              stream: *mut c_void, out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_surface_directions(out: *mut c_int, n_out: u32) -> c_int;
+    pub fn rm_surface_measures(counts: *const u64, n_counts: u32, step: *const f32, mask_a: u32, mask_b: u32, out: *mut f64,
+                               n_out: u32) -> c_int;
     pub fn rm_slice_contours(ctx: *mut rm_ctx, axis: u32, origin_uv: *const f32, step_uv: *const f32, nu: u32, nv: u32,
                              heights: *const f32, n_layers: u32, level: f32, flags: u32, out_counts: *mut u64,
                              n_counts: u32) -> c_int;
@@ -515,6 +552,27 @@ pub fn mass_from_moments(moments: &[u64], origin: [f32; 3], step: [f32; 3], dens
     let rc = unsafe {
         rm_mass_from_moments(moments.as_ptr(), RM_MOMENTS as u32, origin.as_ptr(), step.as_ptr(), density, out.as_mut_ptr(),
                              RM_MASS_PROPS as u32)
+    };
+    if rc == RM_OK { Ok(()) } else { Err(rc) }
+}
+
+/// The 13 directions of the pair counts of a surface call, (x, y, z) each (`rm_surface_directions`; host code, no GPU needed).
+pub fn surface_directions() -> [[c_int; 3]; RM_SURF_DIRS as usize] {
+    let mut out = [[0 as c_int; 3]; RM_SURF_DIRS as usize];
+    let rc = unsafe { rm_surface_directions(out.as_mut_ptr() as *mut c_int, 3 * RM_SURF_DIRS as u32) };
+    assert_eq!(rc, RM_OK);
+    out
+}
+
+/// The interface between the class sets `mask_a` and `mask_b` (bit a = class a; disjoint, not empty) from the counts of
+/// `surface_solid` / `surface_classes` and the lattice's `step`: fills `out` (at least `RM_SURF_MEASURES` entries indexed by
+/// `RM_SURF_AREA`, `RM_SURF_FACET_*`; AREA is NaN unless the three steps are equal) (`rm_surface_measures`; host code, no GPU
+/// needed).  `Err(status)` for masks that are empty, overlap or name a ninth class, and a step that is not finite or <= 0.
+pub fn surface_measures(counts: &[u64], step: [f32; 3], mask_a: u32, mask_b: u32, out: &mut [f64]) -> Result<(), c_int> {
+    assert!(counts.len() >= RM_SURF_COUNTS as usize, "surface_measures: counts is shorter than RM_SURF_COUNTS entries");
+    assert!(out.len() >= RM_SURF_MEASURES as usize, "surface_measures: out is shorter than RM_SURF_MEASURES entries");
+    let rc = unsafe {
+        rm_surface_measures(counts.as_ptr(), RM_SURF_COUNTS as u32, step.as_ptr(), mask_a, mask_b, out.as_mut_ptr(), RM_SURF_MEASURES as u32)
     };
     if rc == RM_OK { Ok(()) } else { Err(rc) }
 }
@@ -818,6 +876,35 @@ impl RayMarchingResources {
         self.topology.set(Some((out_counts[RM_TOPO_BODIES as usize], out_counts[RM_TOPO_CAVITIES as usize],
                                 nx as u64 * ny as u64 * nz as u64)));
         Ok(())
+    }
+
+    /// The pair counts of the solid `map_scene < level` (class 1 inside, 0 outside) on the lattice (`rm_surface_solid`; 2..1024
+    /// points per axis, at most 2^28 in all): fills `out_counts` (at least `RM_SURF_COUNTS` entries: the points per class at
+    /// `RM_SURF_POINTS`, `PAIR[a][b][nu]` at `surf_pair(a, b, nu)`) and `out_stats` (at least `RM_SURF_STATS`, indexed by
+    /// `RM_SURF_STAT_*`).  Exact integers: every run gives the same words.  `surface_measures` turns them into areas.  Nothing
+    /// is retained, and no retained result of the context is touched.
+    pub fn surface_solid(&self, origin: [f32; 3], step: [f32; 3], nx: u32, ny: u32, nz: u32, level: f32, out_counts: &mut [u64],
+                         out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(out_counts.len() >= RM_SURF_COUNTS as usize, "surface_solid: out_counts is shorter than RM_SURF_COUNTS entries");
+        assert!(out_stats.len() >= RM_SURF_STATS as usize, "surface_solid: out_stats is shorter than RM_SURF_STATS entries");
+        self.check(unsafe {
+            rm_surface_solid(self.ctx, origin.as_ptr(), step.as_ptr(), nx, ny, nz, level, out_counts.as_mut_ptr(), RM_SURF_COUNTS as u32,
+                             out_stats.as_mut_ptr(), RM_SURF_STATS as u32)
+        })
+    }
+
+    /// `surface_solid` of a caller's classes in host memory (`rm_surface_classes`): one byte per point, x fastest, the class
+    /// min(byte, 7) -- an occupancy, or the mask of `read_support`, `read_distance` or `read_islands` as it is.  The brick
+    /// statistics are 0.
+    pub fn surface_classes(&self, nx: u32, ny: u32, nz: u32, classes: &[u8], out_counts: &mut [u64],
+                           out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(classes.len() as u64 >= nx as u64 * ny as u64 * nz as u64, "surface_classes: classes is shorter than nx * ny * nz bytes");
+        assert!(out_counts.len() >= RM_SURF_COUNTS as usize, "surface_classes: out_counts is shorter than RM_SURF_COUNTS entries");
+        assert!(out_stats.len() >= RM_SURF_STATS as usize, "surface_classes: out_stats is shorter than RM_SURF_STATS entries");
+        self.check(unsafe {
+            rm_surface_classes(self.ctx, nx, ny, nz, classes.as_ptr() as *const c_void, 0, std::ptr::null_mut(),
+                               out_counts.as_mut_ptr(), RM_SURF_COUNTS as u32, out_stats.as_mut_ptr(), RM_SURF_STATS as u32)
+        })
     }
 
     /// The result of the last successful labelling call: the bodies' rows and the cavities' rows (`RM_MOMENTS` words each, in

@@ -689,6 +689,61 @@ int rm_islands_occupancy(rm_ctx* ctx, uint32_t nx, uint32_t ny, uint32_t nz, con
 int rm_read_islands(rm_ctx* ctx, uint32_t* out_rows, uint64_t row_capacity, uint32_t* out_labels, void* out_mask,
                     uint32_t* out_profile, int is_device, void* stream);
 
+/* Surface measures (extension; DESIGN.md section 25 is the contract, to the last bit): what is the surface area, how large is
+ * the interface between two materials, how much area do the supports touch the part with -- from the counts of the pairs of
+ * neighbouring lattice points by the classes of their two ends.
+ * Lattice, "inside", limits and linear index are rm_label_solid's (2..1024 points per axis, at most 2^28 in all, RM_ERR_RANGE
+ * otherwise; i + nx * (j + ny * k)).  Every point has a CLASS 0..7 (RM_SURF_CLASSES).  rm_surface_solid: 1 inside, 0 outside.
+ * rm_surface_classes: min(byte, 7) of the caller's bytes (one per point, x fastest; host memory, or (is_device) device memory
+ * read after the work queued on `stream`) -- a total function, so no call fails after a launch for its input; the 0/1
+ * occupancies and the masks of rm_read_support (0..4), rm_read_distance (0..3) and rm_read_islands (0..2) are valid as they are.
+ * The lattice counts as surrounded by ONE LAYER OF CLASS-0 POINTS (every point with a coordinate of -1, or of n on that axis):
+ * the PADDED lattice; a solid that touches the border still has a closed surface.
+ * Thirteen DIRECTIONS nu, in this order (RM_SURF_DIRS; rm_surface_directions writes the 39 words): the axes (1,0,0) (0,1,0)
+ * (0,0,1); the face diagonals (1,1,0) (1,-1,0) (1,0,1) (1,0,-1) (0,1,1) (0,1,-1); the space diagonals (1,1,1) (1,1,-1) (1,-1,1)
+ * (1,-1,-1).
+ * out_counts, RM_SURF_COUNTS = 840 words:
+ *   POINTS[a]        at RM_SURF_POINTS + a: the lattice points of class a (padding is not counted)
+ *   PAIR[a][b][nu]   at RM_SURF_PAIR(a, b, nu) = 8 + (8 a + b) * 13 + nu: the pairs (p, p + nu), both in the padded lattice, with
+ *                    class(p) = a and class(p + nu) = b.  PAIR[0][0][.] is written as 0 (it would only count padding).  The
+ *                    ordered pair carries the orientation: PAIR[1][0][z] are up-facing faces, PAIR[0][1][z] down-facing ones.
+ * out_stats[RM_SURF_STAT_*]: BRICKS, BRICKS_KEPT, BRICKS_INSIDE, EVALUATIONS as rm_mass_moments reports them for the same lattice
+ * and level (0 for rm_surface_classes); SCRATCH_BYTES, the device memory the call used.
+ * Every word is a count: two runs, and any correct implementation, give identical words.  The calls are synchronous on the
+ * context's own stream, ordered after its earlier work; nothing is retained (there is no rm_read_*), and no earlier retained
+ * result -- mesh, slices, labelling, distance volume, support or islands result -- is dropped or replaced.  Errors (every check
+ * precedes the first launch, and a failed call leaves the outputs untouched) are those of rm_label_solid / rm_label_occupancy,
+ * word for word, with RM_SURF_COUNTS and RM_SURF_STATS; RM_ERR_DEVICE when device memory runs out (about 1 byte per point).
+ * rm_surface_measures (host code, binary64, no context) measures the interface between the class sets A and B, bit masks over
+ * the classes (bit a = class a), from the counts and the lattice's step.  out[RM_SURF_*], RM_SURF_MEASURES doubles:
+ *   FACET_POS_X .. FACET_NEG_Z   the exact staircase areas by orientation from A into B: POS_X = s_y s_z * sum over a in A, b in B
+ *                                of PAIR[a][b][x], NEG_X the same of PAIR[b][a][x]; for any steps
+ *   FACET_AREA                   the sum of the six
+ *   AREA                         the Cauchy-Crofton estimate 2 dV sum over nu of w_nu N_nu / r_nu: N_nu = sum over a in A, b in B
+ *                                of PAIR[a][b][nu] + PAIR[b][a][nu] (the crossings), dV = s_x s_y s_z, r_nu = |nu o step|, w_nu the
+ *                                fraction of the sphere nearer to +-nu than to any other of the 26 directions (0.0915557824...,
+ *                                0.0739612557..., 0.0703912795... for an axis, a face and a space diagonal).  Defined for three
+ *                                equal steps only: NaN otherwise.  Balls converge (over six centres within 3.5 % of 4 pi R^2
+ *                                at a radius of 6 points, 1.1 % at 10.3, 0.65 % at 14.7, 0.11 % at 20.2); an axis-aligned box
+ *                                is the worst case (-12.6 % for a 10-point cube), for which FACET_AREA is exact.
+ * RM_ERR_NULL for a NULL array; RM_ERR_ARG for n_counts < RM_SURF_COUNTS, n_out < RM_SURF_MEASURES, a mask that is empty or has
+ * a bit above class 7, masks that overlap, and a step that is not finite or <= 0.  rm_surface_directions: RM_ERR_NULL,
+ * RM_ERR_ARG for n_out < 3 * RM_SURF_DIRS. */
+#define RM_SURF_PAIR(a, b, nu) (8 + (8 * (int)(a) + (int)(b)) * 13 + (int)(nu)) /* the index of PAIR[a][b][nu] in out_counts */
+enum rm_surfcount { RM_SURF_CLASSES = 8, RM_SURF_DIRS = 13, RM_SURF_POINTS = 0, RM_SURF_PAIRS = 8, RM_SURF_COUNTS = 840 };
+enum rm_surfstat { RM_SURF_STAT_BRICKS = 0, RM_SURF_STAT_BRICKS_KEPT = 1, RM_SURF_STAT_BRICKS_INSIDE = 2,
+                   RM_SURF_STAT_EVALUATIONS = 3, RM_SURF_STAT_SCRATCH_BYTES = 4, RM_SURF_STATS = 5 };
+enum rm_surfmeasure { RM_SURF_AREA = 0, RM_SURF_FACET_AREA = 1, RM_SURF_FACET_POS_X = 2, RM_SURF_FACET_NEG_X = 3,
+                      RM_SURF_FACET_POS_Y = 4, RM_SURF_FACET_NEG_Y = 5, RM_SURF_FACET_POS_Z = 6, RM_SURF_FACET_NEG_Z = 7,
+                      RM_SURF_MEASURES = 8 };
+int rm_surface_solid(rm_ctx* ctx, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                     uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats);
+int rm_surface_classes(rm_ctx* ctx, uint32_t nx, uint32_t ny, uint32_t nz, const void* classes, int is_device, void* stream,
+                       uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats);
+int rm_surface_directions(int* out, uint32_t n_out);
+int rm_surface_measures(const uint64_t* counts, uint32_t n_counts, const float* step, uint32_t mask_a, uint32_t mask_b,
+                        double* out, uint32_t n_out);
+
 /* Slicing (extension; DESIGN.md section 16 is the contract, to the last bit): the closed outlines of the solid d < level in a
  * stack of planes, as ordered polylines -- what a slicer or a section drawing needs, evaluated directly on a 2-D lattice
  * per layer instead of through a triangle mesh.  From the program, limits and material table as they are at the call.

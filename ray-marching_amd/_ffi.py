@@ -103,6 +103,22 @@ ISL_STAT_NAMES = SUP_STAT_NAMES
 ISL_ROW_NAMES = ("layer", "first", "points", "supported", "sum_a", "sum_b", "min_a", "max_a", "min_b", "max_b", "below_min", "below_max")
 RM_ISL_ROW_WORDS = len(ISL_ROW_NAMES)
 ISL_MASK_OUTSIDE, ISL_MASK_INSIDE, ISL_MASK_ISLAND = range(3)
+# surface measures (rm_surface_solid / rm_surface_classes / rm_surface_directions / rm_surface_measures): enum rm_surfcount, enum
+# rm_surfstat, enum rm_surfmeasure
+RM_SURF_CLASSES, RM_SURF_DIRS, RM_SURF_POINTS, RM_SURF_PAIRS, RM_SURF_COUNTS = 8, 13, 0, 8, 840
+(RM_SURF_STAT_BRICKS, RM_SURF_STAT_BRICKS_KEPT, RM_SURF_STAT_BRICKS_INSIDE, RM_SURF_STAT_EVALUATIONS, RM_SURF_STAT_SCRATCH_BYTES,
+ RM_SURF_STATS) = range(6)
+SURF_STAT_NAMES = SUP_STAT_NAMES
+(RM_SURF_AREA, RM_SURF_FACET_AREA, RM_SURF_FACET_POS_X, RM_SURF_FACET_NEG_X, RM_SURF_FACET_POS_Y, RM_SURF_FACET_NEG_Y,
+ RM_SURF_FACET_POS_Z, RM_SURF_FACET_NEG_Z, RM_SURF_MEASURES) = range(9)
+SURF_MEASURE_NAMES = ("area", "facet_area", "facet_pos_x", "facet_neg_x", "facet_pos_y", "facet_neg_y", "facet_pos_z", "facet_neg_z")
+
+
+def RM_SURF_PAIR(a, b, nu):
+    """The index of PAIR[a][b][nu] in the counts of a surface call."""
+    return 8 + (8 * a + b) * 13 + nu
+
+
 # slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table): enum rm_slicecount, the indices of out_counts
 RM_SLICE_POINTS, RM_SLICE_CONTOURS, RM_SLICE_COUNTS = 0, 1, 2
 # lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit): enum rm_light, the parameter names in index order
@@ -261,6 +277,14 @@ def hip_lib():
         L.rm_islands_occupancy.restype = C.c_int
         L.rm_read_islands.argtypes = [vp, vp, u64, vp, vp, vp, C.c_int, vp]
         L.rm_read_islands.restype = C.c_int
+        L.rm_surface_solid.argtypes = L.rm_label_solid.argtypes
+        L.rm_surface_solid.restype = C.c_int
+        L.rm_surface_classes.argtypes = L.rm_label_occupancy.argtypes
+        L.rm_surface_classes.restype = C.c_int
+        L.rm_surface_directions.argtypes = [C.POINTER(C.c_int), u32]
+        L.rm_surface_directions.restype = C.c_int
+        L.rm_surface_measures.argtypes = [C.POINTER(u64), u32, f3, u32, u32, C.POINTER(C.c_double), u32]
+        L.rm_surface_measures.restype = C.c_int
         L.rm_slice_contours.argtypes = [vp, u32, f3, f3, u32, u32, f3, u32, C.c_float, u32, C.POINTER(u64), u32]
         L.rm_slice_contours.restype = C.c_int
         L.rm_read_slices.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]

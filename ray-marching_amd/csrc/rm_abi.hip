@@ -35,6 +35,7 @@
 #include "rm_distance.h"
 #include "rm_support.h"
 #include "rm_islands.h"
+#include "rm_surface.h"
 #include "rm_slice.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
@@ -2055,7 +2056,7 @@ int check_topo_lattice(rm_ctx* c, const char* fn, uint32_t nx, uint32_t ny, uint
     return fail(c, RM_ERR_RANGE, "%s: lattice %ux%ux%u: 2..1024 points per axis, at most 2^28 in all", fn, nx, ny, nz);
 }
 
-// ---- the front end of the lattice analyses: labelling, distance, supports, islands, each of a solid and of an occupancy ----
+// ---- the front end of the lattice analyses: labelling, distance, supports, islands, surface measures, each of a solid and of an occupancy ----
 // The statistics every analysis reports first, and the size of its scratch last.
 enum { kStatBricks = 0, kStatBricksKept = 1, kStatBricksInside = 2, kStatEvaluations = 3 };
 #define RM_LATTICE_STATS_ASSERT(P)                                                                                             \
@@ -2067,6 +2068,7 @@ RM_LATTICE_STATS_ASSERT(RM_TOPO);
 RM_LATTICE_STATS_ASSERT(RM_DIST);
 RM_LATTICE_STATS_ASSERT(RM_SUP);
 RM_LATTICE_STATS_ASSERT(RM_ISL);
+RM_LATTICE_STATS_ASSERT(RM_SURF);
 #undef RM_LATTICE_STATS_ASSERT
 
 // Where the occupancy of a call comes from: the solid {d < level} of the program on the lattice (origin, step), or the caller's
@@ -2757,6 +2759,121 @@ RM_EXPORT int rm_read_islands(rm_ctx* c, uint32_t* out_rows, uint64_t row_capaci
     return read_back(c, is_device, stream, "rm_read_islands: device out_rows, out_labels and out_profile need 4-byte alignment",
                      {{out_rows, rml::IslandsRows(r.regions).rows, r.rows.p, 4}, {out_labels, r.labels.p, (size_t)r.n * 4u, 4},
                       {out_mask, r.mask.p, r.n, 1}, {out_profile, r.profile.p, (size_t)r.nh * 16u, 4}});
+}
+
+// ---- surface measures (rm_surface.h) ----
+namespace {
+
+static_assert(RM_SURF_COUNTS == (int)rml::kSurfCounts && RM_SURF_COUNTS == (int)rml::kSurfRowWords && RM_SURF_CLASSES == (int)rmk::kSurfClasses &&
+                  RM_SURF_DIRS == (int)rmk::kSurfDirs && RM_SURF_PAIR(0, 0, 0) == (int)rmk::kSurfPairs && RM_SURF_PAIR(7, 7, 12) == RM_SURF_COUNTS - 1,
+              "rm_abi.h's layout of out_counts is the kernel's table");
+
+// The tiles of the padded lattice and the workgroups that walk them.
+struct SurfTiles {
+    uint32_t tx, ty, tz, n_tiles, groups;
+    explicit SurfTiles(const rmk::SparseGrid& g)
+        : tx(rml::surf_tiles(g.nx, rml::kSurfTileX)), ty(rml::surf_tiles(g.ny, rml::kSurfTileY)), tz(rml::surf_tiles(g.nz, rml::kSurfTileZ)),
+          n_tiles(tx * ty * tz), groups(std::min(n_tiles, rml::kSurfMaxGroups)) {}  // (<= 17 * 65 * 129 tiles)
+};
+
+struct SurfaceAnalysis {
+    static constexpr uint32_t kCounts = RM_SURF_COUNTS, kStats = RM_SURF_STATS;
+    static constexpr const char *kCountsName = "RM_SURF_COUNTS", *kStatsName = "RM_SURF_STATS";
+    int check(rm_ctx* c, const char* fn, uint32_t nx, uint32_t ny, uint32_t nz) const { return check_topo_lattice(c, fn, nx, ny, nz); }
+    rml::SurfScratch layout(const TopoGrid& G) const { return rml::SurfScratch(G.n, G.g.nb, G.n_pblocks, SurfTiles(G.g).groups); }
+    int reserve(rm_ctx* c, const TopoGrid&, const rml::SurfScratch& S) const { return c->d_mscratch.reserve(c, S.bytes); }  // (nothing retained)
+    // From the classes in S.occ on: one row per workgroup, the rows' sums.  A workgroup counts at most its tiles' owners per bin:
+    // ceil(n_tiles / groups) * 8192 < 2^32.
+    int run(rm_ctx* c, const char*, hipStream_t s, const TopoGrid& G, const rml::SurfScratch& S, uint64_t* counts, uint64_t*) const {
+        const rmk::SparseGrid& g = G.g;
+        char* sc = c->d_mscratch.p;
+        const SurfTiles T(g);
+        constexpr rml::SurfTileLds L;
+        static_assert(L.bytes + 1024u <= rml::kLdsLaunchLimit, "a tile and its table fit a workgroup's LDS");
+        hipLaunchKernelGGL(rmk::rm_surf_count_kernel, dim3(T.groups), dim3(256), L.bytes, s, g.nx, g.ny, g.nz, T.tx, T.ty, T.n_tiles,
+                           static_cast<const uint8_t*>(S.occ.at(sc)), S.rows.at(sc));
+        hipLaunchKernelGGL(rmk::rm_surf_reduce_kernel, dim3(rml::kSurfCounts / 8u), dim3(256), 0, s, static_cast<const uint32_t*>(S.rows.at(sc)),
+                           T.groups, S.result.at(sc));
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(counts, S.result.at(sc), sizeof(uint64_t) * RM_SURF_COUNTS, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        uint64_t others = 0u;
+        for (int a = 1; a < RM_SURF_CLASSES; a++) others += counts[RM_SURF_POINTS + a];
+        counts[RM_SURF_POINTS] = (uint64_t)G.n - others;
+        return RM_OK;
+    }
+};
+
+// The direction weights of AREA: the fraction of the sphere nearer to +-nu than to any other of the 26 directions, for an axis, a
+// face diagonal and a space diagonal (tools/surface_weights.py derives them in closed form; 3 w1 + 6 w2 + 4 w3 = 1).
+constexpr double kSurfWeight[3] = {0.091555782409523431, 0.073961255752150262, 0.070391279564633452};
+
+}  // namespace
+
+RM_EXPORT int rm_surface_solid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, float level,
+                               uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
+    return lattice_call(c, "rm_surface_solid", OccupancySource::of_solid(origin, step, level), nx, ny, nz, SurfaceAnalysis(), out_counts,
+                        n_counts, out_stats, n_stats);
+}
+
+RM_EXPORT int rm_surface_classes(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz, const void* classes, int is_device, void* stream,
+                                 uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
+    return lattice_call(c, "rm_surface_classes", OccupancySource::of_bytes(classes, is_device, stream), nx, ny, nz, SurfaceAnalysis(), out_counts,
+                        n_counts, out_stats, n_stats);
+}
+
+RM_EXPORT int rm_surface_directions(int* out, uint32_t n_out) {
+    if (!out) return RM_ERR_NULL;
+    if (n_out < 3u * (uint32_t)RM_SURF_DIRS) return RM_ERR_ARG;
+    for (uint32_t d = 0; d < (uint32_t)RM_SURF_DIRS; d++) {
+        const rmk::SurfDir nu = rmk::surf_dir(d);
+        out[3u * d] = nu.x;
+        out[3u * d + 1u] = nu.y;
+        out[3u * d + 2u] = nu.z;
+    }
+    return RM_OK;
+}
+
+RM_EXPORT int rm_surface_measures(const uint64_t* counts, uint32_t n_counts, const float* step, uint32_t mask_a, uint32_t mask_b, double* out,
+                                  uint32_t n_out) {
+    if (!counts || !step || !out) return RM_ERR_NULL;
+    if (n_counts < (uint32_t)RM_SURF_COUNTS || n_out < (uint32_t)RM_SURF_MEASURES) return RM_ERR_ARG;
+    const uint32_t all = (1u << RM_SURF_CLASSES) - 1u;
+    if (mask_a == 0u || mask_b == 0u || (mask_a & mask_b) != 0u || ((mask_a | mask_b) & ~all) != 0u) return RM_ERR_ARG;
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(step[a]) || !(step[a] > 0.0f)) return RM_ERR_ARG;
+    const double st[3] = {step[0], step[1], step[2]};
+    // from[nu]: the pairs that lead from A into B along +nu; back[nu]: from B into A
+    uint64_t from[RM_SURF_DIRS] = {}, back[RM_SURF_DIRS] = {};
+    for (uint32_t a = 0; a < (uint32_t)RM_SURF_CLASSES; a++)
+        for (uint32_t b = 0; b < (uint32_t)RM_SURF_CLASSES; b++)
+            if (((mask_a >> a) & 1u) != 0u && ((mask_b >> b) & 1u) != 0u)
+                for (uint32_t d = 0; d < (uint32_t)RM_SURF_DIRS; d++) {
+                    from[d] += counts[RM_SURF_PAIR(a, b, d)];
+                    back[d] += counts[RM_SURF_PAIR(b, a, d)];
+                }
+    double facets = 0.0;
+    for (int a = 0; a < 3; a++) {
+        const double cell = st[(a + 1) % 3] * st[(a + 2) % 3];
+        out[RM_SURF_FACET_POS_X + 2 * a] = cell * (double)from[a];
+        out[RM_SURF_FACET_NEG_X + 2 * a] = cell * (double)back[a];
+        facets += out[RM_SURF_FACET_POS_X + 2 * a] + out[RM_SURF_FACET_NEG_X + 2 * a];
+    }
+    out[RM_SURF_FACET_AREA] = facets;
+    if (step[0] != step[1] || step[1] != step[2]) {
+        out[RM_SURF_AREA] = std::nan("");
+        return RM_OK;
+    }
+    const double dV = st[0] * st[1] * st[2];
+    double sum = 0.0;
+    for (uint32_t d = 0; d < (uint32_t)RM_SURF_DIRS; d++) {
+        const rmk::SurfDir nu = rmk::surf_dir(d);
+        const double vx = nu.x * st[0], vy = nu.y * st[1], vz = nu.z * st[2];
+        const int kind = nu.x * nu.x + nu.y * nu.y + nu.z * nu.z;  // 1, 2, 3
+        sum += kSurfWeight[kind - 1] * (double)(from[d] + back[d]) / std::sqrt(vx * vx + vy * vy + vz * vz);
+    }
+    out[RM_SURF_AREA] = 2.0 * dV * sum;
+    return RM_OK;
 }
 
 RM_EXPORT int rm_read_mesh(rm_ctx* c, float* out_vertices, uint32_t* out_triangles, float* out_normals, uint32_t* out_ids,

@@ -212,6 +212,25 @@ struct IslandsRows {
     explicit IslandsRows(uint64_t regions) : rows(a.take<uint32_t>(regions * kIslRowWords)), bytes(a.total) {}
 };
 
+// rm_surface_solid / rm_surface_classes, for a lattice of n points in nb bricks counted by n_groups workgroups: per point its
+// class (1 B; `occ`, as the front end names the region it fills); per brick its class, per 256 bricks the probe's block sum,
+// totals and the evaluation count as above; per workgroup one row of kSurfRowWords u32 counts; the reduced row (u64).  Nothing
+// is retained.
+constexpr uint32_t kSurfRowWords = 840u;  // RM_SURF_COUNTS (rm_lds_layout.h kSurfCounts)
+struct SurfScratch {
+    Carver a;
+    Region<uint8_t> occ, cls;
+    Region<unsigned long long> psums, ptot, evals;
+    Region<uint32_t> rows;
+    Region<unsigned long long> result;
+    uint32_t n_groups;
+    size_t bytes;
+    SurfScratch(uint32_t n, uint32_t nb, uint32_t n_pblocks, uint32_t groups)
+        : occ(a.take<uint8_t>(n)), cls(a.take<uint8_t>(nb)), psums(a.take<unsigned long long>(n_pblocks)),
+          ptot(a.take<unsigned long long>(2)), evals(a.take<unsigned long long>(2)), rows(a.take<uint32_t>((size_t)groups * kSurfRowWords)),
+          result(a.take<unsigned long long>(kSurfRowWords)), n_groups(groups), bytes(a.total) {}
+};
+
 // rm_slice_contours' per-layer tables: heights, layer_first, the first vertex of each layer of a batch of `per`, totals.
 // (heights and layer_first lie before anything `per` sizes: rm_read_slices finds layer_first without it.)
 struct SliceLayerTables {

@@ -156,4 +156,19 @@ struct IslLinkLds {
         : labels(0u), pitch(64u + 2u * reach), rows(kIslLinkRows + 2u * reach), bytes(labels + rows * pitch * 4u) {}
 };
 
+// ---- Surface measures, pair counts (rm_surface.h rm_surf_count_kernel) --------------------------------------------------------
+// One tile is kSurfTileX x kSurfTileY x kSurfTileZ points of the PADDED lattice (coordinates -1 .. n per axis), one class byte per
+// point, with the halo its 13 forward pairs reach: one point more on +x, one on either side of y and of z.  The point
+// (x0 + cx, y0 - 1 + cy, z0 - 1 + cz) of the tile at (x0, y0, z0) lies at byte (cz * rows_y + cy) * pitch + cx.  Then the
+// workgroup's table of counts: kSurfCounts u32 words (8 point bins, 8 x 8 x 13 pair bins).
+constexpr uint32_t kSurfTileX = 64u, kSurfTileY = 16u, kSurfTileZ = 8u, kSurfCounts = 8u + 8u * 8u * 13u;
+constexpr uint32_t kSurfMaxGroups = 1024u;  // workgroups of a launch: each walks the tiles g, g + groups, ... and writes one row
+RM_LDS_FN uint32_t surf_tiles(uint32_t n, uint32_t extent) { return (n + 2u + extent - 1u) / extent; }
+struct SurfTileLds {
+    uint32_t pitch, rows_y, rows_z, cls, counts, bytes;
+    RM_LDS_FN SurfTileLds()
+        : pitch(kSurfTileX + 1u), rows_y(kSurfTileY + 2u), rows_z(kSurfTileZ + 2u), cls(0u),
+          counts((cls + pitch * rows_y * rows_z + 15u) & ~15u), bytes(counts + kSurfCounts * 4u) {}
+};
+
 }  // namespace rml

@@ -686,6 +686,25 @@ class RayMarchingResources:
         (integer addresses; 0 = not wanted), asynchronous."""
         self._read_into(self._islands_reader(row_capacity), (rows_ptr, labels_ptr, mask_ptr, profile_ptr), True, stream)
 
+    # -- surface measures (rm_surface_solid / rm_surface_classes / rm_surface_measures) -----------------------------------------------
+    def surface_solid(self, lo, hi, resolution, level=0.0):
+        """The pair counts of the solid map_scene < level (class 1 inside, 0 outside) inside the box [lo, hi], on the lattice
+        extract_mesh builds from (lo, hi, resolution) (2..1024 points per axis, at most 2^28 in all): a Surface, whose
+        measures(1, 0) are the solid's surface area."""
+        lo, step, n = self._box_lattice(lo, hi, resolution)
+        return self.surface_solid_grid(lo, step, n, level)
+
+    def surface_solid_grid(self, origin, step, shape, level=0.0):
+        """surface_solid on an exact lattice (origin, step, shape as sample_grid takes them)."""
+        return self._solid_grid_call(self._L.rm_surface_solid, *_SURF_OUTPUTS, origin, step, shape, level, None, Surface)
+
+    def surface_classes(self, classes):
+        """rm_surface_classes: the pair counts of a caller's classes, as label_occupancy takes an occupancy (indexed [k, j, i];
+        numpy, or a torch tensor on this context's GPU): one byte per point, the class min(byte, 7) -- an occupancy, or the mask
+        of a Support, a DistanceFeatures or an Islands as it is.  The Surface's lattice is the unit lattice at the origin; give
+        measures() the step of the lattice the classes came from."""
+        return self._occupancy_call(self._L.rm_surface_classes, *_SURF_OUTPUTS, classes, None, Surface)
+
     # -- retained results (rm_read_*) ------------------------------------------------------------------------------------------
     # rm_read_* copies the size of the CONTEXT's last result, whatever the caller allocated.  So every read goes through _read_into,
     # and the result objects that read on demand (_Retained) are held to a serial per family: _advance moves it on when a producing
@@ -859,6 +878,8 @@ _TOPO_OUTPUTS = (("topology",), _ffi.RM_TOPO_COUNTS, _ffi.RM_TOPO_STATS, _ffi.TO
 _DIST_OUTPUTS = (("distance", "distance_mask"), _ffi.RM_DIST_COUNTS, _ffi.RM_DIST_STATS, _ffi.DIST_COUNT_NAMES, _ffi.DIST_STAT_NAMES)
 _SUP_OUTPUTS = (("support",), _ffi.RM_SUP_COUNTS, _ffi.RM_SUP_STATS, _ffi.SUP_COUNT_NAMES, _ffi.SUP_STAT_NAMES)
 _ISL_OUTPUTS = (("islands",), _ffi.RM_ISL_COUNTS, _ffi.RM_ISL_STATS, _ffi.ISL_COUNT_NAMES, _ffi.ISL_STAT_NAMES)
+# (no family: a surface call retains nothing; its 840 counts are named by their index)
+_SURF_OUTPUTS = ((), _ffi.RM_SURF_COUNTS, _ffi.RM_SURF_STATS, tuple(range(_ffi.RM_SURF_COUNTS)), _ffi.SURF_STAT_NAMES)
 
 # RayMarchingResources._read_new's specs: (numpy dtype, name of the torch dtype: u32 and u64 words as int32 and int64 views); _SKIP.
 _F32, _U32, _U64, _U8 = (np.float32, "float32"), (np.uint32, "int32"), (np.uint64, "int64"), (np.uint8, "uint8")
@@ -1168,6 +1189,64 @@ class Islands(_Retained):
             out.append({"region": int(r) + 1, "layer": int(row["layer"]), "points": int(row["points"]),
                         "centroid": [float(x) for x in o + idx * st], "area": float(row["points"] * st[b] * st[c])})
         return out
+
+
+def surface_directions():
+    """rm_surface_directions: the 13 directions of the pair counts, int32 (13, 3) of (x, y, z) (host code, no GPU)."""
+    out = np.zeros((_ffi.RM_SURF_DIRS, 3), dtype=np.int32)
+    rc = _ffi.hip_lib().rm_surface_directions(out.ctypes.data_as(C.POINTER(C.c_int)), out.size)
+    if rc != _ffi.RM_OK:
+        raise _ffi.RmError(rc, "rm_surface_directions: " + _ffi.hip_lib().rm_status_string(rc).decode())
+    return out
+
+
+def _class_mask(classes):
+    """A set of classes as rm_surface_measures takes it: one class, or an iterable of classes -> the bit mask."""
+    members = [classes] if isinstance(classes, (int, np.integer)) else list(classes)
+    if any(not 0 <= int(a) < _ffi.RM_SURF_CLASSES for a in members):
+        raise ValueError("a class is 0..%d, not %r" % (_ffi.RM_SURF_CLASSES - 1, classes))
+    mask = 0
+    for a in members:
+        mask |= 1 << int(a)
+    return mask
+
+
+def surface_measures(counts, step, a, b, raw=False):
+    """rm_surface_measures (host code, no GPU): the interface between the class sets a and b (a class, or an iterable of
+    classes; disjoint, not empty) from the 840 counts of a surface call and the lattice's step -> a dict
+    (_ffi.SURF_MEASURE_NAMES): area (the Cauchy-Crofton estimate; NaN unless the three steps are equal), facet_area and the six
+    facet areas by orientation from a into b (exact staircase areas).  raw=True: the float64[8] array in _ffi.RM_SURF_* order."""
+    c = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    s = np.array(step, dtype=np.float32, copy=True).reshape(-1)
+    if s.shape != (3,):
+        raise ValueError("step must have 3 entries (x, y, z)")
+    out = np.zeros(_ffi.RM_SURF_MEASURES, dtype=np.float64)
+    rc = _ffi.hip_lib().rm_surface_measures(c.ctypes.data_as(C.POINTER(C.c_uint64)), len(c), s.ctypes.data_as(C.POINTER(C.c_float)),
+                                            _class_mask(a), _class_mask(b), out.ctypes.data_as(C.POINTER(C.c_double)), len(out))
+    if rc != _ffi.RM_OK:
+        raise _ffi.RmError(rc, "rm_surface_measures: " + _ffi.hip_lib().rm_status_string(rc).decode())
+    return out if raw else {name: float(out[k]) for k, name in enumerate(_ffi.SURF_MEASURE_NAMES)}
+
+
+class Surface:
+    """The result of surface_solid / surface_classes.  points: uint64[8], the lattice points per class; pairs: uint64 (8, 8, 13),
+    pairs[a, b, nu] the pairs (p, p + nu) with class(p) = a and class(p + nu) = b (surface_directions() gives nu); counts: the
+    840 words as the library wrote them; stats: a dict (_ffi.SURF_STAT_NAMES); origin, step (float32[3]) and shape of the
+    lattice.  Nothing of it lives in the context."""
+
+    def __init__(self, counts, stats, origin, step, shape):
+        self.counts = np.array([counts[k] for k in range(_ffi.RM_SURF_COUNTS)], dtype=np.uint64)
+        self.points = self.counts[_ffi.RM_SURF_POINTS:_ffi.RM_SURF_POINTS + _ffi.RM_SURF_CLASSES]
+        self.pairs = self.counts[_ffi.RM_SURF_PAIRS:].reshape(_ffi.RM_SURF_CLASSES, _ffi.RM_SURF_CLASSES, _ffi.RM_SURF_DIRS)
+        self.stats, self.origin, self.step, self.shape = stats, origin, step, shape
+
+    def __repr__(self):
+        return "Surface(%s points per class on %s)" % (" ".join(str(int(x)) for x in self.points), "x".join(map(str, self.shape)))
+
+    def measures(self, a, b, step=None):
+        """surface_measures of the interface between the class sets a and b, on this lattice's step (or `step`: that of the
+        lattice a caller's classes came from)."""
+        return surface_measures(self.counts, self.step if step is None else step, a, b)
 
 
 MASS_PROP_NAMES = ("volume", "mass", "cx", "cy", "cz", "ixx", "iyy", "izz", "ixy", "iyz", "ixz", "lo_x", "lo_y", "lo_z", "hi_x", "hi_y",
