@@ -96,6 +96,16 @@ RM_HD bool rm_tree_keeps(unsigned long long L, unsigned long long R, uint32_t in
 // ... and does a fused leaf push its value because there is nothing to combine it with
 RM_HD bool rm_tree_pushes(unsigned long long L, uint32_t info, unsigned long long need) { return (info & 3u) == 1u && (L & need) == 0ull; }
 
+// The unit table a workgroup stages in LDS (rm_kernel_v5.h stage_units), 8 n_units dwords: which dword of the unit records
+// (RmDecoded::units, 8 dwords each: the first word, then p[0 .. 6]) does dword k of the table hold?  Fields 0 .. 3 -- centre
+// and outer radius -- stand together, one float4 per unit in dwords [0, 4 n_units); fields 4, 5, 6 and the record's first
+// word are rows 4 .. 7 of n_units dwords each.  Shared with the CPU check of the arrangement (tests/cpp/unit_table_probe.cpp).
+RM_HD uint32_t rm_unit_table_source(uint32_t k, uint32_t n_units) {
+    const uint32_t row = k / n_units;
+    const uint32_t f = row < 4u ? (k & 3u) : row, u = row < 4u ? (k >> 2) : k - row * n_units;
+    return 8u * u + ((f + 1u) & 7u);
+}
+
 struct RmLaunch {
     const RmRecord* prog;      // decoded program, device memory
     uint32_t n_rec;            // == cmd_count of the reference program

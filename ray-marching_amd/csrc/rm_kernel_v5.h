@@ -105,7 +105,7 @@ constexpr float kPruneAbs = 4.0e-6f;
 // it handed out rays, and a ray that takes the shared step afterwards gets
 //     aT       = |F_a| (1 + 1e-5) + 4e-6 (scene_scale + |ro|_1 + |p_a|_1)                      (anchor_reach)
 //     thr_base = min(2 |f0| (1 + 1e-5), fl(fl(l1) (1 + 1e-5) + aT)),   l1 = |q' - p_a|_1      (anchor_thr_base)
-// to which the step adds its own position term m(q') as for every threshold.  Why that bounds |F'_computed|:
+// to which the step adds its own position term m(q') -- or a bound of it, below -- as for every threshold.  Why that bounds |F'_computed|:
 //   - p_a and q' are the binary32 points the evaluations ran AT (q' by the step's own expression, which with contraction off
 //     gives the same bits here; were it an ulp off, m(q') covers the rounding of q' as it always did), so the real distance
 //     between them is what counts, and |q' - p_a|_2 <= |q' - p_a|_1: the triangle inequality holds a fortiori with the L1 norm
@@ -130,6 +130,59 @@ RM_DEV float anchor_thr_base(float thr_base, float qx, float qy, float qz, float
     const float t = __builtin_fmaf(l1, 1.00001f, aT);
     return t < thr_base ? t : thr_base;  // NaN t: the old value stays
 }
+// The position term along a ray.  m(q') = 4e-6 (prune_scale + |q'|_1), prune_scale = scene_scale + |ro|_1, is there to cover
+// evaluation error "with 3x to spare": any upper bound of it serves, and a march step has a cheap one.  Its point is
+// q' = ro + d sc with |d|_2 <= 1 + 1e-5 (a normalised ray; the "|rd| <= 1" of the rule above), so
+//     |q'|_1 <= |ro|_1 + |d|_1 |sc| <= |ro|_1 + sqrt(3) (1 + 1e-5) |sc|
+// and the step's threshold is ONE multiply-add, thr = fma(|sc|, kPruneRay, thr_base), where it was five instructions (two sums
+// of magnitudes, + prune_scale, * 4e-6, + thr_base), with the wave-uniform rest c0 >= 4e-6 (prune_scale + |ro|_1) carried
+// inside thr_base: added where the bookkeeping forms it (a multiply-add in place of the multiply), and where a ray is handed out.
+//     c0       = fl(fl(kPruneAbsUp * fl(prune_scale + fl(|ro|_1))) + 1e-30)                    (step_thr_c0, once per wave)
+//                (a product and a sum, two roundings: both builds compile with -ffp-contract=off, build.py HIP_FLAGS and rm_jit.h
+//                compile_options, and tests/step_thr_ref.py restates it so; contracted to one multiply-add it would lose one rounding
+//                less, and every bound below holds for that form too)
+//     thr_base = fma(|sd|, kStepReach, c0)                                                      (step_thr_base, every step)
+//     thr_base = fma(min(2 |f0| (1 + 1e-5), the anchored bound), 1 + 2^-22, c0)                 (handout_thr_base, per ray)
+//     thr      = fma(|sc|, kPruneRay, thr_base)                                                 (step_thr, every step)
+// new >= old for every finite input, old = fl(T + M) with T = fl(|sd| 2.00002f) (or the hand-out's minimum, the same number on
+// both sides) and M = fl(4e-6f fl(prune_scale + fl(|q'|_1))).  With u = 2^-24, every rounding to nearest and monotone, and an
+// absolute error of at most 2^-150 where a PRODUCT lands among the denormals (sums are exact there):
+//   - M: each coordinate fl(ro + fl(d sc)) is at most (|ro| + |d| |sc| (1 + u)) (1 + u), the two sums of |q'|_1, the sum with
+//     prune_scale and the product add (1 + u) each: M <= 4e-6f (prune_scale + |ro|_1 + |d|_1 |sc|) (1 + u)^6 + 2^-150, and
+//     (1 + u)^6 < 1 + 3.6e-7;
+//   - c0: the two sums of |ro|_1, the sum with prune_scale and the product lose (1 - u) each, the last sum is monotone:
+//     c0 >= kPruneAbsUp (prune_scale + |ro|_1) (1 - 2.4e-7) - 2^-150 and c0 >= 1e-30 (1 - u).  kPruneAbsUp >= 4e-6f (1 + 2.5e-5) as
+//     binary32 numbers: a hundred times what the two lines lose together;
+//   - kPruneRay = 6.9285e-6f >= 4e-6f sqrt(3) (1 + 4.2e-5): |d|_1 <= sqrt(3) |d|_2, the 1e-5 of |d|_2, the 3.6e-7 of M, 3e-5 left over;
+//   - thr_base, step: fma(|sd|, kStepReach, c0) >= (|sd| kStepReach + c0) (1 - u) - 2^-150 with kStepReach = 2.0000205f =
+//     2.00002f (1 + 4 u): (1 + 4 u) (1 - u) > 1 + u, so it is at least |sd| 2.00002f (1 + u) + c0 (1 - u) - 2^-150
+//     >= T + c0 (1 - u) - 2^-149.  (Two units in the last place on the factor: 2.4e-7 of the threshold.  Without them the
+//     rounding of the LARGE term could eat the small one: u T against c0.)  Hand-out: the same with the factor 1 + 2^-22
+//     = 1 + 4 u on the minimum, T itself: >= T + c0 (1 - u) - 2^-150; +inf stays +inf;
+//   - together, in real numbers, |sc| kPruneRay + thr_base >= T + M: the reserves above against the losses, the 1e-30 in c0
+//     against the 2^-150s; the last multiply-add and the old last sum each round once, monotonically: thr >= old.
+// Hence every bound proven for the old threshold holds for this one, the anchored form included (its minimum is taken first,
+// on the same numbers as before: anchor_reach and anchor_thr_base are untouched and c0 is added to the result).  It is larger
+// by at most 4e-6 (|ro|_1 + |d|_1 |sc| - |q'|_1) + 3e-5 m + 2.4e-7 T: 1e-5 .. 1e-4 for the metric camera against thresholds
+// of 1e-2 .. 1 -- the leaves evaluated do not move (profiles/r25_step_front_end_ab.txt).
+// Non-finite inputs: a non-finite sc makes |sc| kPruneRay +inf or NaN, and thr with it (thr_base is never -inf).  A non-finite
+// d with a finite sc leaves thr finite where the old form, which read q', did not -- but thr is only ever read by the
+// wave-level masks, at the same q': a non-finite coordinate of a live lane gives sl = +inf or NaN there (wave_cull_lattice,
+// "Slack") and no comparison holds.  A NaN sd, or a NaN or infinite f0, goes through both multiply-adds as NaN or +inf; a
+// ray that does not take the shared step starts from +inf.
+// The taps keep the old term: their point is not on a ray, and they run once per hit.  So does the general interpreter loop,
+// which reads the threshold without keeping an anchor: the form above is compiled in where ANCHOR is (rm_render_v5_body).
+// tests/step_thr_ref.py restates the four functions in binary32; tests/test_step_thr_cpu.py holds new >= old, the bound on the
+// value and the non-finite cases.
+constexpr float kPruneAbsUp = 4.0001e-6f;
+constexpr float kPruneRay = 6.9285e-6f;
+constexpr float kStepReach = 2.0000205f;
+RM_DEV float step_thr_c0(float prune_scale, float rox, float roy, float roz) {
+    return kPruneAbsUp * (prune_scale + ((__builtin_fabsf(rox) + __builtin_fabsf(roy)) + __builtin_fabsf(roz))) + 1.0e-30f;
+}
+RM_DEV float step_thr_base(float sd, float c0) { return __builtin_fmaf(__builtin_fabsf(sd), kStepReach, c0); }
+RM_DEV float handout_thr_base(float thr_base, float c0) { return __builtin_fmaf(thr_base, 1.00000024f, c0); }
+RM_DEV float step_thr(float thr_base, float sc) { return __builtin_fmaf(__builtin_fabsf(sc), kPruneRay, thr_base); }
 // The thresholds are kept (a register per ray, |sd| of a hit in its hit-buffer entry) by the generated kernels compiled
 // with pruning and by the library's interpreter kernels
 #if defined(RM_JIT_PRUNE_ON) || !defined(RM_JIT_TU)
@@ -216,26 +269,35 @@ RM_DEV WaveBall wave_ball(float x, float y, float z, bool is_live, unsigned long
     b.rho = __builtin_amdgcn_sqrtf(r2) * 1.00001f + 1.0e-30f;
     return b;
 }
-// The unit table in LDS, one ROW per field so that lane u's reads do not collide with its neighbours' (unit records are 32
-// bytes apart in device memory; a workgroup transposes them when it stages the program): row f of n_units floats holds
-// RmDecoded::units[u].p[f] -- 0..2 centre, 3 outer radius, 4 inner radius, 5 blend radius, 6 kind; row 7 the record's first word (the
-// records the unit stands for, first | last << 16).
+// The unit table in LDS (unit records are 32 bytes apart in device memory; a workgroup rearranges them when it stages the
+// program), 8 n_units dwords in two parts:
+//   dwords [0, 4 n_units)   one float4 per unit, RmDecoded::units[u].p[0..3]: centre and outer radius -- all a lattice mask asks
+//                           of unit `lane`, so it is ONE 16-byte read per step (ds_read_b128 at lunits + 4 lane; a stride of 16
+//                           bytes between lanes is what a 128-bit read serves without a conflict) where a row per field was four
+//                           reads, four waits and four address registers live through the march loop;
+//   rows 4 .. 7             one ROW of n_units dwords per field, at lunits + f n_units as before, so that lane u's reads do not
+//                           collide with its neighbours': 4 inner radius, 5 blend radius, 6 kind; row 7 the record's first word
+//                           (the records the unit stands for, first | last << 16).
+// The table starts on a 16-byte boundary: behind the records (32 bytes each) behind the float4 cull tables; dynamic LDS itself.
 constexpr uint32_t kUnitRows = 8u;
 RM_DEV void stage_units(uint32_t* lunits, const RmRecord* __restrict__ units, uint32_t n_units, uint32_t tid, uint32_t n_threads) {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(units);
-    for (uint32_t k = tid; k < kUnitRows * n_units; k += n_threads) {
-        const uint32_t f = k / n_units, u = k - f * n_units;
-        lunits[k] = src[8u * u + ((f + 1u) & 7u)];
-    }
+    for (uint32_t k = tid; k < kUnitRows * n_units; k += n_threads) lunits[k] = src[rm_unit_table_source(k, n_units)];
+}
+// centre and outer radius of unit `lane` (unit 0 for the lanes at or above n_units)
+RM_DEV float4 unit_sphere(const uint32_t* lunits, uint32_t n_units) {
+    const uint32_t lane = threadIdx.x & 63u;
+    return reinterpret_cast<const float4*>(lunits)[lane < n_units ? lane : 0u];
 }
 struct UnitBounds { float L, H, k; uint32_t kind; };
 RM_DEV UnitBounds unit_bounds(const uint32_t* lunits, uint32_t n_units, const WaveBall& b) {
     const uint32_t lane = threadIdx.x & 63u;
+    const float4 c = unit_sphere(lunits, n_units);
     const float* u = reinterpret_cast<const float*>(lunits) + (lane < n_units ? lane : 0u);
-    const float dx = u[0] - b.px, dy = u[n_units] - b.py, dz = u[2u * n_units] - b.pz;
+    const float dx = c.x - b.px, dy = c.y - b.py, dz = c.z - b.pz;
     const float d = __builtin_amdgcn_sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)));
     UnitBounds r;
-    r.L = (d * 0.999998f - u[3u * n_units]) - b.rho;  // v_sqrt_f32 is within an ulp, the fused sum of squares within 3e-7
+    r.L = (d * 0.999998f - c.w) - b.rho;  // v_sqrt_f32 is within an ulp, the fused sum of squares within 3e-7
     r.H = (d * 1.000002f + b.rho) - u[4u * n_units];
     r.k = u[5u * n_units];
     r.kind = __float_as_uint(u[6u * n_units]);
@@ -251,6 +313,10 @@ RM_DEV unsigned long long wave_cull_lattice(const uint32_t* lunits, uint32_t n_u
     // ONE reduction: unit u is far for lane l when value_u(p_l) >= |p* - c| - R - |p_l - p*| > thr_l, i.e. for every live lane when
     // |p* - c| - R > S = max over live lanes (|p_l - p*| + thr_l) -- sharper than rho + T (a maximum of sums, not a sum of maxima)
     // and a wave reduction less.  thr >= 0 or NaN; a NaN's bit pattern is above +inf's and wins the maximum: nothing is far then.
+    // (asked for first, and kept first: left to itself the scheduler issues the 128-bit read right in front of its use, behind the
+    // reduction, and the step waits out the LDS latency the reduction would have covered)
+    const float4 c = unit_sphere(lunits, n_units);
+    __builtin_amdgcn_sched_barrier(0);
     const int first = __builtin_ctzll(live_m);  // (the caller has a live lane)
     const float px = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(x), first));
     const float py = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(y), first));
@@ -279,11 +345,9 @@ RM_DEV unsigned long long wave_cull_lattice(const uint32_t* lunits, uint32_t n_u
     const float sl = __builtin_fmaf(l1, 1.00001f, thr);
     const float S = __uint_as_float(wave_max_u32(is_live ? __float_as_uint(sl) : 0u)) * 1.000005f;
     // far: |p* - c| - R > S, decided on the squares (every term is >= 0; a NaN or an infinity makes it false)
-    const uint32_t lane = threadIdx.x & 63u;
-    const float* u = reinterpret_cast<const float*>(lunits) + (lane < n_units ? lane : 0u);
-    const float dx = u[0] - px, dy = u[n_units] - py, dz = u[2u * n_units] - pz;
+    const float dx = c.x - px, dy = c.y - py, dz = c.z - pz;
     const float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-    const float s = S + u[3u * n_units];
+    const float s = S + c.w;
     return ~__builtin_amdgcn_ballot_w64(d2 > (s * s) * 1.000004f) & valid;
 }
 // margin_scale: scene_scale + |ro|_1 (the `prune_scale` of the kernels)
@@ -317,7 +381,7 @@ RM_DEV unsigned long long wave_cull_blend(const uint32_t* lunits, uint32_t n_uni
     return valid & from_r & (~skip_m | behind_poison | (1ull << r));
 }
 // Tree programs under the interpreter (rm_interp.h map_scene_tree_masked): from the wave's unit mask to the RECORDS the wave has
-// to execute.  Lane r looks at records r and r + 64 (RmDecoded::tree, staged like the unit table: one row per field), L and R
+// to execute.  Lane r looks at records r and r + 64 (RmDecoded::tree, staged like rows 4 .. 7 of the unit table: one row per field), L and R
 // being the units of the record's operands:
 //   a leaf is kept iff its unit is needed; an operator record iff both operands hold a needed leaf -- with one of them all +inf a
 //   Union or the right side of a Subtraction is the identity on the other: dropped, with the operand's records;
@@ -899,6 +963,7 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
     // (prune_scale_v5 and bound_scale_march_v5, written out: called here, even with their operands by value, they moved the
     // scalar spill counts of these kernels, some up)
     const float prune_scale = L.scene_scale + ((__builtin_fabsf(ro.x) + __builtin_fabsf(ro.y)) + __builtin_fabsf(ro.z));  // "Pruning"
+    const float thr_c0 = step_thr_c0(prune_scale, ro.x, ro.y, ro.z);  // the wave-uniform part of a march step's threshold
     const float eps = 0.0001f;                                    // wgsl:136
     if (PROG_IN_LDS) {
         const uint32_t* src = reinterpret_cast<const uint32_t*>(L.prog);
@@ -1156,6 +1221,7 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
                             thr_base = shared ? __builtin_fabsf(f0) * 2.00002f : inf_f;
                             if constexpr (ANCHOR) {  // the step's own expression for its first point: the same bits
                                 if (shared) thr_base = anchor_thr_base(thr_base, ro.x + dx * sc, ro.y + dy * sc, ro.z + dz * sc, anc_x, anc_y, anc_z, anc_t);
+                                thr_base = handout_thr_base(thr_base, thr_c0);  // (after the minimum: both of its sides carry c0)
                             }
                         }
                     }
@@ -1272,7 +1338,8 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
             } else {
                 ex = ro.x + dx * sc; ey = ro.y + dy * sc; ez = ro.z + dz * sc;  // wgsl:91
                 is_live = lane_marching();
-                thr = thr_base + kPruneAbs * (prune_scale + ((__builtin_fabsf(ex) + __builtin_fabsf(ey)) + __builtin_fabsf(ez)));
+                if constexpr (ANCHOR) thr = step_thr(thr_base, sc);  // ("Pruning", the position term along a ray)
+                else thr = thr_base + kPruneAbs * (prune_scale + ((__builtin_fabsf(ex) + __builtin_fabsf(ey)) + __builtin_fabsf(ez)));
             }
             const unsigned long long live_m = __builtin_amdgcn_ballot_w64(is_live);
 #ifndef RM_NO_WAVE_STATS
@@ -1309,7 +1376,7 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
             sc = select_by_mask(sc, sc + sd, go_m);                                                       // wgsl:114
             itr = select_by_mask(itr, itr + 1024u, go_m);
 #ifdef RM_PRUNE_PLUMBING  // only pruning kernels read it
-            thr_base = select_by_mask(thr_base, __builtin_fabsf(sd) * 2.00002f, go_m);  // the next point is |sd| |rd| away
+            thr_base = select_by_mask(thr_base, ANCHOR ? step_thr_base(sd, thr_c0) : __builtin_fabsf(sd) * 2.00002f, go_m);  // the next point is |sd| |rd| away
 #endif
             const unsigned long long miss_mask = esc_m | (go_m & __ballot(itr >= iter_limit));             // loop bound, wgsl:90
             const unsigned long long done_m = hit_mask | miss_mask;
