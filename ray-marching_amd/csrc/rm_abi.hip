@@ -1124,65 +1124,96 @@ uint32_t query_slots(const RmDecoded& d, int loop, bool walk) {
     return slots;
 }
 
-// What every query of the program does first, on stream `s`, exactly as a draw would: ordering with the context's earlier
-// work, the program (decoded, validated and uploaded by ensure_program), the limits and -- for colours of a tagged program --
-// the material table.  Fills the launch and the dynamic LDS of one 256-thread workgroup: four wave columns of `slots` dwords
-// per lane, the larger of what the distance loop (value stack, then 3 floats per transform level) and the leaf walk
-// ([depth] distances, [depth] (leaf, material) pairs, 3 floats per transform level) need for THIS program.
-int query_begin(rm_ctx* c, hipStream_t s, bool walk, bool rgb, rmk::QueryLaunch* Q, int* loop, size_t* shmem) {
-    order_with_previous(c, s);
-    int rc = ensure_program(c, s);
-    if (rc == RM_OK && rgb) rc = ensure_materials(c, s);
-    if (rc == RM_OK) rc = check_limits(c);
-    if (rc != RM_OK) return rc;
-    const RmDecoded& d = c->decoded;
-    // the query program of this decoding, stream-ordered like the draws' images (a query still queued on an earlier stream
-    // keeps the previous one: order_with_previous above made this stream wait for it)
-    if (c->qprog_gen != c->prog_gen) {
-        if (d.qrec.size() > c->d_qprog.cap)
-            if ((rc = c->d_qprog.reserve(c, std::max<size_t>(64, d.qrec.size() * 2), "query program")) != RM_OK) return rc;
-        if (!d.qrec.empty())
-            if (int urc = upload(c, c->d_qprog.p, d.qrec.data(), d.qrec.size() * sizeof(RmRecord), s)) return urc;
-        c->qprog_gen = c->prog_gen;
+// A kernel template over the record loop alone, as QueryCall::launch chooses it.
+#define RM_BY_LOOP(kernel) [](auto tag) { return rmk::kernel<decltype(tag)::value>; }
+
+// As many 256-thread workgroups as give `items` one lane each.
+uint32_t query_blocks(uint64_t items) { return (uint32_t)((items + 255u) / 256u); }
+
+// The launch state of a call that runs query kernels of the program on one stream: what the kernels take (Q), the record loop
+// they are instantiated for and their LDS columns (rml::QueryLds: four wave columns of Q.slots dwords per lane).
+struct QueryCall {
+    rm_ctx* c = nullptr;
+    hipStream_t s = nullptr;
+    rmk::QueryLaunch Q;
+    int loop = 0;
+    rml::QueryLds lds{0u, 0u};
+
+    // What every query does first, on stream `s`, exactly as a draw would: ordering with the context's earlier work and the
+    // program (decoded, validated and uploaded by ensure_program).  A call that has to see the program before it knows
+    // whether the leaf walk runs takes this step by itself and begin_columns after it.
+    int begin_program(rm_ctx* ctx, hipStream_t stream) {
+        c = ctx;
+        s = stream;
+        order_with_previous(c, s);
+        return ensure_program(c, s);
     }
-    *loop = query_loop(d);
-    const uint32_t slots = query_slots(d, *loop, walk);
-    *shmem = (size_t)slots * 64u * 4u * 4u;
-    const size_t cap = std::max<size_t>(c->max_lds, 64u * 1024u);
-    if (*shmem > cap) return fail(c, RM_ERR_TOO_LARGE, "the query needs %zu bytes of LDS per workgroup", *shmem);
-    Q->prog = c->d_prog.p;
-    Q->qprog = c->d_qprog.p;
-    Q->n_rec = (uint32_t)d.rec.size();
-    Q->n_qrec = (uint32_t)d.qrec.size();
-    Q->value_spill_depth = d.spill_depth;
-    Q->q_value_depth = d.q_spill_depth;
-    Q->slots = slots;
-    Q->tagged = d.has_materials ? 1u : 0u;
-    Q->min_dist = c->limits.min_dist;
-    Q->max_dist = c->limits.max_dist;
-    Q->max_iter = c->limits.max_iter;
-    Q->materials = rgb && d.has_materials ? c->d_materials.p : nullptr;
-    return RM_OK;
-}
+    // Then the limits and -- for colours of a tagged program -- the material table, the query program, the launch and the
+    // columns of one workgroup: the larger of what the distance loop and, with `walk`, the leaf walk need for THIS program
+    // (query_slots).
+    int begin_columns(bool walk, bool rgb) {
+        int rc = rgb ? ensure_materials(c, s) : RM_OK;
+        if (rc == RM_OK) rc = check_limits(c);
+        if (rc != RM_OK) return rc;
+        const RmDecoded& d = c->decoded;
+        // the query program of this decoding, stream-ordered like the draws' images (a query still queued on an earlier stream
+        // keeps the previous one: order_with_previous made this stream wait for it)
+        if (c->qprog_gen != c->prog_gen) {
+            if (d.qrec.size() > c->d_qprog.cap)
+                if ((rc = c->d_qprog.reserve(c, std::max<size_t>(64, d.qrec.size() * 2), "query program")) != RM_OK) return rc;
+            if (!d.qrec.empty())
+                if (int urc = upload(c, c->d_qprog.p, d.qrec.data(), d.qrec.size() * sizeof(RmRecord), s)) return urc;
+            c->qprog_gen = c->prog_gen;
+        }
+        loop = query_loop(d);
+        lds = rml::QueryLds(query_slots(d, loop, walk), 0u);
+        if (!fits(0u)) return fail(c, RM_ERR_TOO_LARGE, "the query needs %zu bytes of LDS per workgroup", (size_t)lds.bytes);
+        Q.prog = c->d_prog.p;
+        Q.qprog = c->d_qprog.p;
+        Q.n_rec = (uint32_t)d.rec.size();
+        Q.n_qrec = (uint32_t)d.qrec.size();
+        Q.value_spill_depth = d.spill_depth;
+        Q.q_value_depth = d.q_spill_depth;
+        Q.slots = lds.slots;
+        Q.tagged = d.has_materials ? 1u : 0u;
+        Q.min_dist = c->limits.min_dist;
+        Q.max_dist = c->limits.max_dist;
+        Q.max_iter = c->limits.max_iter;
+        Q.materials = rgb && d.has_materials ? c->d_materials.p : nullptr;
+        return RM_OK;
+    }
+    int begin(rm_ctx* ctx, hipStream_t stream, bool walk, bool rgb) {
+        const int rc = begin_program(ctx, stream);
+        return rc == RM_OK ? begin_columns(walk, rgb) : rc;
+    }
 
-// `blocks` 256-thread workgroups of a query kernel ...
-template <class K, class... Args>
-int query_launch_blocks(rm_ctx* c, K kernel, uint32_t blocks, size_t shmem, hipStream_t s, Args... args) {
-    if (shmem > 64u * 1024u)  // (deep programs: gfx950 gives a workgroup up to 160 KB)
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), shmem, s, args...);
-    HIP_TRY(c, hipGetLastError());
-    return RM_OK;
-}
-// ... and as many as give `count` items one lane each.
-template <class K, class... Args>
-int query_launch(rm_ctx* c, K kernel, size_t count, size_t shmem, hipStream_t s, Args... args) {
-    return query_launch_blocks(c, kernel, (uint32_t)((count + 255u) / 256u), shmem, s, args...);
-}
+    // Whether a workgroup of a kernel with `own` bytes of static LDS fits what the device gives one (gfx950: up to 160 KB).
+    bool fits(uint32_t own) const { return lds.behind(own).fits(std::max<size_t>(c->max_lds, rml::kLdsLaunchLimit)); }
+    // The same call with columns of other `slots` (a second pass over the program with or without the leaf walk).
+    QueryCall with_slots(uint32_t slots) const {
+        QueryCall q = *this;
+        q.lds = rml::QueryLds(slots, lds.own);
+        q.Q.slots = slots;
+        return q;
+    }
 
-using PointsFn = void (*)(rmk::QueryLaunch, uint32_t, const float*, float*, float*, uint32_t*);
-PointsFn points_kernel(int loop, bool dist, bool normal, bool ids) {
-    return with_loop(loop, [&](auto tag) -> PointsFn {
+    // `blocks` 256-thread workgroups of the kernel that choose(std::integral_constant<int, LOOP>) gives for this call's loop,
+    // on (Q, args...), with the columns behind the kernel's `own` bytes of static LDS.
+    template <class F, class... Args>
+    int launch(F&& choose, uint32_t blocks, uint32_t own, Args... args) const {
+        const auto kernel = with_loop(loop, choose);
+        const rml::QueryLds L = lds.behind(own);
+        if (L.needs_opt_in())  // (deep programs)
+            HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.dynamic));
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), L.dynamic, s, Q, args...);
+        HIP_TRY(c, hipGetLastError());
+        return RM_OK;
+    }
+};
+
+// The kernels that are chosen by more than the loop: each gives QueryCall::launch its chooser.
+auto points_kernel(bool dist, bool normal, bool ids) {
+    return [=](auto tag) {
         constexpr int LOOP = decltype(tag)::value;
         switch ((dist ? 1 : 0) | (normal ? 2 : 0) | (ids ? 4 : 0)) {
         case 1: return rmk::rm_query_points_kernel<LOOP, true, false, false>;
@@ -1193,15 +1224,14 @@ PointsFn points_kernel(int loop, bool dist, bool normal, bool ids) {
         case 6: return rmk::rm_query_points_kernel<LOOP, false, true, true>;
         default: return rmk::rm_query_points_kernel<LOOP, true, true, true>;
         }
-    });
+    };
 }
-using RaysFn = void (*)(rmk::QueryLaunch, uint32_t, const float*, float*, uint32_t*, float*);
-RaysFn rays_kernel(int loop, bool taps, bool walk) {
-    return with_loop(loop, [&](auto tag) -> RaysFn {
+auto rays_kernel(bool taps, bool walk) {
+    return [=](auto tag) {
         constexpr int LOOP = decltype(tag)::value;
         if (!walk) return rmk::rm_cast_rays_kernel<LOOP, true, false>;
         return taps ? rmk::rm_cast_rays_kernel<LOOP, true, true> : rmk::rm_cast_rays_kernel<LOOP, false, true>;
-    });
+    };
 }
 
 // The input array of a query with outputs `o`: the caller's device array, or -- host memory: staged through the context's query
@@ -1228,10 +1258,8 @@ RM_EXPORT int rm_query_points(rm_ctx* c, uint32_t n, const float* xyz, float* ou
         return fail(c, RM_ERR_ARG, "rm_query_points: device arrays need 4-byte alignment (out_ids: 8-byte)");
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = dest_stream(c, is_device, stream);
-    rmk::QueryLaunch Q;
-    int loop = 0;
-    size_t shmem = 0;
-    int rc = query_begin(c, s, out_ids != nullptr, false, &Q, &loop, &shmem);
+    QueryCall q;
+    int rc = q.begin(c, s, out_ids != nullptr, false);
     if (rc != RM_OK) return rc;
     Outputs o(c, is_device, c->d_qout);
     o.add(out_dist, (size_t)n * 4u);
@@ -1239,8 +1267,7 @@ RM_EXPORT int rm_query_points(rm_ctx* c, uint32_t n, const float* xyz, float* ou
     o.add(out_ids, (size_t)n * 8u);
     const float* d_xyz = nullptr;
     if ((rc = query_input(c, o, xyz, (size_t)n * 12u, s, &d_xyz)) != RM_OK) return rc;
-    rc = query_launch(c, points_kernel(loop, out_dist, out_normal, out_ids), n, shmem, s, Q, n, d_xyz, o.dev<float>(0), o.dev<float>(1),
-                      o.dev<uint32_t>(2));
+    rc = q.launch(points_kernel(out_dist, out_normal, out_ids), query_blocks(n), 0u, n, d_xyz, o.dev<float>(0), o.dev<float>(1), o.dev<uint32_t>(2));
     return rc == RM_OK ? o.finish(s) : rc;
 }
 
@@ -1254,27 +1281,20 @@ RM_EXPORT int rm_cast_rays(rm_ctx* c, uint32_t n, const float* rays, float* out_
         return fail(c, RM_ERR_ARG, "rm_cast_rays: device arrays need 4-byte alignment (out_hit, out_ids: 16-byte)");
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = dest_stream(c, is_device, stream);
-    rmk::QueryLaunch Q;
-    int loop = 0;
-    size_t shmem = 0;
+    QueryCall q;
+    int rc = q.begin_program(c, s);
+    if (rc != RM_OK) return rc;
     // the leaf walk runs for the ids, and for the colour of a tagged program (its albedo)
     const bool taps = out_hit || out_rgb;
-    bool walk = out_ids != nullptr;
-    if (out_rgb && !walk) {
-        order_with_previous(c, s);
-        int rc = ensure_program(c, s);  // (query_begin repeats both at no cost)
-        if (rc != RM_OK) return rc;
-        walk = c->decoded.has_materials;
-    }
-    int rc = query_begin(c, s, walk, out_rgb != nullptr, &Q, &loop, &shmem);
-    if (rc != RM_OK) return rc;
+    const bool walk = out_ids != nullptr || (out_rgb != nullptr && c->decoded.has_materials);
+    if ((rc = q.begin_columns(walk, out_rgb != nullptr)) != RM_OK) return rc;
     Outputs o(c, is_device, c->d_qout);
     o.add(out_hit, (size_t)n * 32u);
     o.add(out_ids, (size_t)n * 16u);
     o.add(out_rgb, (size_t)n * 12u);
     const float* d_rays = nullptr;
     if ((rc = query_input(c, o, rays, (size_t)n * 24u, s, &d_rays)) != RM_OK) return rc;
-    rc = query_launch(c, rays_kernel(loop, taps, walk), n, shmem, s, Q, n, d_rays, o.dev<float>(0), o.dev<uint32_t>(1), o.dev<float>(2));
+    rc = q.launch(rays_kernel(taps, walk), query_blocks(n), 0u, n, d_rays, o.dev<float>(0), o.dev<uint32_t>(1), o.dev<float>(2));
     return rc == RM_OK ? o.finish(s) : rc;
 }
 
@@ -1295,8 +1315,10 @@ RM_EXPORT int rm_camera_rays(rm_ctx* c, uint32_t W, uint32_t H, uint32_t x0, uin
     Outputs o(c, is_device, c->d_qout);
     o.add(out_rays, (size_t)count * 24u);
     int rc = o.reserve();
-    if (rc == RM_OK) rc = query_launch(c, rmk::rm_camera_rays_kernel, count, 0u, s, c->uniforms, W, H, x0, y0, w, count, sample, o.dev<float>(0));
-    return rc == RM_OK ? o.finish(s) : rc;
+    if (rc != RM_OK) return rc;
+    hipLaunchKernelGGL(rmk::rm_camera_rays_kernel, dim3(query_blocks(count)), dim3(256), 0, s, c->uniforms, W, H, x0, y0, w, count, sample, o.dev<float>(0));
+    HIP_TRY(c, hipGetLastError());
+    return o.finish(s);
 }
 
 // ---- ray traversal (rm_trace.h) ------------------------------------------------------------------------------------------
@@ -1317,18 +1339,12 @@ int bad_trace_param(const float* p) {
     return -1;
 }
 
-using TraceMarchFn = void (*)(rmk::QueryLaunch, rmk::TraceLaunch, uint32_t, const float*, float*, uint32_t*, uint32_t*, float*,
-                              uint32_t*, unsigned long long*);
-TraceMarchFn trace_march_kernel(int loop) {
-    return with_loop(loop, [&](auto tag) -> TraceMarchFn { return rmk::rm_trace_march_kernel<decltype(tag)::value>; });
-}
-using TraceAttrFn = void (*)(rmk::QueryLaunch, uint32_t, const uint32_t*, const uint2*, const float*, float*, uint32_t*);
-TraceAttrFn trace_attr_kernel(int loop, bool normals, bool ids) {
-    return with_loop(loop, [&](auto tag) -> TraceAttrFn {
+auto trace_attr_kernel(bool normals, bool ids) {
+    return [=](auto tag) {
         constexpr int LOOP = decltype(tag)::value;
         if (normals) return ids ? rmk::rm_trace_attr_kernel<LOOP, true, true> : rmk::rm_trace_attr_kernel<LOOP, true, false>;
         return rmk::rm_trace_attr_kernel<LOOP, false, true>;
-    });
+    };
 }
 
 }  // namespace
@@ -1362,19 +1378,15 @@ RM_EXPORT int rm_trace_rays(rm_ctx* c, uint32_t n, const float* rays, const floa
         return fail(c, RM_ERR_ARG, "rm_trace_rays: device arrays need 16-byte alignment (rays: 4-byte)");
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = dest_stream(c, is_device, stream);
-    rmk::QueryLaunch Q;
-    int loop = 0;
-    size_t shmem = 0;
-    int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);  // the march: the distance loop's columns
+    QueryCall q;
+    int rc = q.begin(c, s, false, false);  // the march: the distance loop's columns
     if (rc != RM_OK) return rc;
-    const size_t cap = std::max<size_t>(c->max_lds, 64u * 1024u);
-    if (shmem + 64u > cap) return fail(c, RM_ERR_TOO_LARGE, "the query needs %zu bytes of LDS per workgroup", shmem + 64u);
+    if (!q.fits(rml::kQueryOwnTrace))
+        return fail(c, RM_ERR_TOO_LARGE, "the query needs %zu bytes of LDS per workgroup", (size_t)q.lds.behind(rml::kQueryOwnTrace).bytes);
     // the attribute pass runs for what the caller both asked for and takes; with the ids its columns hold the walk's layout
     const bool normals = (flags & RM_MESH_NORMALS) && out_events, ids = (flags & RM_MESH_IDS) && out_event_ids, attr = normals || ids;
-    rmk::QueryLaunch QA = Q;
-    QA.slots = query_slots(c->decoded, loop, ids);
-    const size_t shmem_attr = (size_t)QA.slots * 64u * 4u * 4u;
-    if (attr && shmem_attr > cap) return fail(c, RM_ERR_TOO_LARGE, "the query needs %zu bytes of LDS per workgroup", shmem_attr);
+    const QueryCall qa = q.with_slots(query_slots(c->decoded, q.loop, ids));
+    if (attr && !qa.fits(0u)) return fail(c, RM_ERR_TOO_LARGE, "the query needs %zu bytes of LDS per workgroup", (size_t)qa.lds.bytes);
     const uint32_t K = max_events, nb = (uint32_t)(((uint64_t)n + 255u) / 256u);
     const rmk::TraceLaunch T{params[RM_TRACE_T_MIN], params[RM_TRACE_T_MAX], params[RM_TRACE_MIN_STEP], params[RM_TRACE_STEP_SCALE],
                              params[RM_TRACE_LEVEL], (uint32_t)params[RM_TRACE_MAX_STEPS], K};
@@ -1391,21 +1403,20 @@ RM_EXPORT int rm_trace_rays(rm_ctx* c, uint32_t n, const float* rays, const floa
     void* base = c->d_tscratch.p;
     // the event records the march writes and the attribute pass reads the positions from: the caller's, else the scratch copy
     float* d_events = out_events ? o.dev<float>(0) : attr ? L.events.at(base) : nullptr;
-    rc = query_launch(c, trace_march_kernel(loop), n, shmem, s, Q, T, n, d_rays, d_events, o.dev<uint32_t>(1), o.dev<uint32_t>(2),
-                      o.dev<float>(3), attr ? L.stored.at(base) : nullptr, attr ? L.sums.at(base) : nullptr);
+    rc = q.launch(RM_BY_LOOP(rm_trace_march_kernel), nb, rml::kQueryOwnTrace, T, n, d_rays, d_events, o.dev<uint32_t>(1), o.dev<uint32_t>(2),
+                  o.dev<float>(3), attr ? L.stored.at(base) : nullptr, attr ? L.sums.at(base) : nullptr);
     if (rc == RM_OK && attr) {
         hipLaunchKernelGGL(rmk::rm_mesh_scan_kernel, dim3(1), dim3(1024), 0, s, L.sums.at(base), nb, L.totals.at(base));
         HIP_TRY(c, hipGetLastError());
-        rc = query_launch(c, rmk::rm_trace_list_kernel, n, 0u, s, n, static_cast<const uint32_t*>(L.stored.at(base)),
-                          static_cast<const unsigned long long*>(L.sums.at(base)), L.list.at(base));
+        hipLaunchKernelGGL(rmk::rm_trace_list_kernel, dim3(nb), dim3(256), 0, s, n, static_cast<const uint32_t*>(L.stored.at(base)),
+                           static_cast<const unsigned long long*>(L.sums.at(base)), L.list.at(base));
+        HIP_TRY(c, hipGetLastError());
         // one lane per stored event; how many there are only the device knows, so a fixed number of workgroups strides over them
         const uint64_t most = ((uint64_t)n * K + 255u) / 256u;
         const uint32_t blocks = (uint32_t)std::min<uint64_t>(most, (uint64_t)std::max(c->cu_count, 1) * 8u);
-        if (rc == RM_OK)
-            rc = query_launch_blocks(c, trace_attr_kernel(loop, normals, ids), blocks, shmem_attr, s, QA, K,
-                                     static_cast<const uint32_t*>(L.totals.at(base)), static_cast<const uint2*>(L.list.at(base)),
-                                     static_cast<const float*>(d_events), normals ? o.dev<float>(0) : nullptr,
-                                     ids ? o.dev<uint32_t>(1) : nullptr);
+        rc = qa.launch(trace_attr_kernel(normals, ids), blocks, 0u, K, static_cast<const uint32_t*>(L.totals.at(base)),
+                       static_cast<const uint2*>(L.list.at(base)), static_cast<const float*>(d_events), normals ? o.dev<float>(0) : nullptr,
+                       ids ? o.dev<uint32_t>(1) : nullptr);
     }
     return rc == RM_OK ? o.finish(s) : rc;
 }
@@ -1431,13 +1442,12 @@ int bad_light_param(const float* p) {
     return -1;
 }
 
-using LitFn = void (*)(rmk::QueryLaunch, rmk::LightLaunch, rmk::LitFrame);
-LitFn lit_kernel(int loop, bool shadow, bool ao) {
-    return with_loop(loop, [&](auto tag) -> LitFn {
+auto lit_kernel(bool shadow, bool ao) {
+    return [=](auto tag) {
         constexpr int LOOP = decltype(tag)::value;
         if (shadow) return ao ? rmk::rm_draw_lit_kernel<LOOP, true, true> : rmk::rm_draw_lit_kernel<LOOP, true, false>;
         return ao ? rmk::rm_draw_lit_kernel<LOOP, false, true> : rmk::rm_draw_lit_kernel<LOOP, false, false>;
-    });
+    };
 }
 
 }  // namespace
@@ -1467,15 +1477,10 @@ RM_EXPORT int rm_draw_lit(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, uint
     if (rc != RM_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = dest_stream(c, out_is_device, stream);
-    order_with_previous(c, s);
-    rc = ensure_program(c, s);  // (query_begin repeats both at no cost)
-    if (rc != RM_OK) return rc;
-    rmk::QueryLaunch Q;
-    int loop = 0;
-    size_t shmem = 0;
+    QueryCall q;
+    if ((rc = q.begin_program(c, s)) != RM_OK) return rc;
     // the leaf walk runs for the albedo of a tagged program
-    rc = query_begin(c, s, c->decoded.has_materials, true, &Q, &loop, &shmem);
-    if (rc != RM_OK) return rc;
+    if ((rc = q.begin_columns(c->decoded.has_materials, true)) != RM_OK) return rc;
     const float* p = c->light;
     rmk::LightLaunch P{p[RM_LIGHT_POS_X], p[RM_LIGHT_POS_Y], p[RM_LIGHT_POS_Z], p[RM_LIGHT_SHADOW], p[RM_LIGHT_SHADOW_SOFTNESS],
                        p[RM_LIGHT_BIAS], p[RM_LIGHT_SHADOW_MAX_T], (uint32_t)p[RM_LIGHT_SHADOW_STEPS], p[RM_LIGHT_AO],
@@ -1491,7 +1496,7 @@ RM_EXPORT int rm_draw_lit(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, uint
     o.add(out_rgba, (size_t)rows * W * pixel_bytes(c));
     if ((rc = o.reserve()) != RM_OK) return rc;
     F.out = o.dev<void>(0);
-    rc = query_launch(c, lit_kernel(loop, shadow, ao), lanes, shmem, s, Q, P, F);
+    rc = q.launch(lit_kernel(shadow, ao), query_blocks(lanes), 0u, P, F);
     return rc == RM_OK ? o.finish(s) : rc;
 }
 
@@ -1539,12 +1544,11 @@ RM_EXPORT int rm_program_subtree(uint32_t cmd_count, const uint32_t* words, uint
 }
 
 namespace {
-using GBufferFn = void (*)(rmk::QueryLaunch, rmk::GBufferFrame);
-GBufferFn gbuffer_kernel(int loop, bool all) {
-    return with_loop(loop, [&](auto tag) -> GBufferFn {
+auto gbuffer_kernel(bool all) {
+    return [=](auto tag) {
         constexpr int LOOP = decltype(tag)::value;
         return all ? rmk::rm_draw_gbuffer_kernel<LOOP, true> : rmk::rm_draw_gbuffer_kernel<LOOP, false>;
-    });
+    };
 }
 }  // namespace
 
@@ -1562,18 +1566,13 @@ RM_EXPORT int rm_draw_gbuffer(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, 
         return fail(c, RM_ERR_ARG, "rm_draw_gbuffer: device arrays need 16-byte alignment");
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = dest_stream(c, is_device, stream);
-    order_with_previous(c, s);
-    rc = ensure_program(c, s);  // (query_begin repeats both at no cost)
-    if (rc != RM_OK) return rc;
+    QueryCall q;
+    if ((rc = q.begin_program(c, s)) != RM_OK) return rc;
     if ((uint64_t)sel_first + sel_count > c->cmd[0])
         return fail(c, RM_ERR_ARG, "rm_draw_gbuffer: selection [%u,+%u) reaches past the program's %u commands", sel_first, sel_count, c->cmd[0]);
     // the leaf walk runs for the ids, and for the selected mask of a selection that is not empty
     const bool walk = out_ids != nullptr || (out_masks != nullptr && sel_count != 0u);
-    rmk::QueryLaunch Q;
-    int loop = 0;
-    size_t shmem = 0;
-    rc = query_begin(c, s, walk, false, &Q, &loop, &shmem);
-    if (rc != RM_OK) return rc;
+    if ((rc = q.begin_columns(walk, false)) != RM_OK) return rc;
     const bool all = sample == (uint32_t)RM_SAMPLE_ALL;
     rmk::GBufferFrame F;
     F.u = c->uniforms;
@@ -1592,7 +1591,7 @@ RM_EXPORT int rm_draw_gbuffer(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, 
     o.add(out_masks, n * 16u);
     if ((rc = o.reserve()) != RM_OK) return rc;
     F.geom = o.dev<float>(0); F.ids = o.dev<uint32_t>(1); F.masks = o.dev<uint32_t>(2);
-    rc = query_launch(c, gbuffer_kernel(loop, all), lanes, shmem, s, Q, F);
+    rc = q.launch(gbuffer_kernel(all), query_blocks(lanes), 0u, F);
     return rc == RM_OK ? o.finish(s) : rc;
 }
 
@@ -1613,13 +1612,8 @@ int check_lattice(rm_ctx* c, const char* fn, const float* origin, const float* s
     return RM_OK;
 }
 
-using GridFn = void (*)(rmk::QueryLaunch, float, float, float, float, float, float, uint32_t, uint32_t, uint64_t, float*);
-GridFn grid_kernel(int loop) {
-    return with_loop(loop, [](auto tag) -> GridFn { return rmk::rm_grid_dist_kernel<decltype(tag)::value>; });
-}
-int launch_grid(rm_ctx* c, const rmk::QueryLaunch& Q, int loop, size_t shmem, hipStream_t s, const float* o, const float* st,
-                uint32_t nx, uint32_t ny, uint64_t n, float* out) {
-    return query_launch(c, grid_kernel(loop), n, shmem, s, Q, o[0], o[1], o[2], st[0], st[1], st[2], nx, ny, n, out);
+int launch_grid(const QueryCall& q, const float* o, const float* st, uint32_t nx, uint32_t ny, uint64_t n, float* out) {
+    return q.launch(RM_BY_LOOP(rm_grid_dist_kernel), query_blocks(n), 0u, o[0], o[1], o[2], st[0], st[1], st[2], nx, ny, n, out);
 }
 
 // level and flags of the iso-surface entry points (rm_extract_mesh, rm_extract_mesh_sparse, rm_slice_contours)
@@ -1635,45 +1629,20 @@ rml::MeshLayout mesh_layout(uint64_t v, uint64_t t, uint32_t flags) {
 }
 
 // The attributes (regions of the buffer at `base`) of n points: rm_query_points at their positions, device to device.
-int point_attributes(rm_ctx* c, const rmk::QueryLaunch& Q, int loop, size_t shmem, hipStream_t s, uint32_t flags, uint64_t n,
-                     const float* points, char* base, const rml::Region<float>& nrm, const rml::Region<uint32_t>& idp) {
+int point_attributes(const QueryCall& q, uint32_t flags, uint64_t n, const float* points, char* base, const rml::Region<float>& nrm,
+                     const rml::Region<uint32_t>& idp) {
     const bool normals = (flags & RM_MESH_NORMALS) != 0, ids = (flags & RM_MESH_IDS) != 0;
     if (!(normals || ids) || n == 0u) return RM_OK;
-    return query_launch(c, points_kernel(loop, false, normals, ids), n, shmem, s, Q, (uint32_t)n, points, static_cast<float*>(nullptr),
-                        normals ? nrm.at(base) : nullptr, ids ? idp.at(base) : nullptr);
+    return q.launch(points_kernel(false, normals, ids), query_blocks(n), 0u, (uint32_t)n, points, static_cast<float*>(nullptr),
+                    normals ? nrm.at(base) : nullptr, ids ? idp.at(base) : nullptr);
 }
 
 // ---- sparse extraction (rm_mesh_sparse.h) ----
-using ProbeFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, double, double, uint32_t*, unsigned long long*);
-ProbeFn sparse_probe_kernel(int loop) {
-    return with_loop(loop, [](auto tag) -> ProbeFn { return rmk::rm_sparse_probe_kernel<decltype(tag)::value>; });
-}
-using SparseCountFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, const uint32_t*, const uint32_t*, float*, rmk::SparseSegMap*,
-                               uint32_t*, unsigned long long*);
-SparseCountFn sparse_count_kernel(int loop) {
-    return with_loop(loop, [](auto tag) -> SparseCountFn { return rmk::rm_sparse_count_kernel<decltype(tag)::value>; });
-}
 // The regions of the kept bricks' scratch round up to 16 bytes like all others; the segment maps and the segments' first
 // (vertex, triangle) pairs always were whole multiples of 16, so RM_MESH_STAT_SCRATCH_BYTES is what it was.
 static_assert(sizeof(rmk::SparseSegMap) % 16u == 0u && (rmk::kBrickSegs * sizeof(uint2)) % 16u == 0u, "sparse scratch layout");
-using MassProbeFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, double, double, uint32_t*, unsigned long long*, unsigned long long*);
-MassProbeFn mass_probe_kernel(int loop) {
-    return with_loop(loop, [](auto tag) -> MassProbeFn { return rmk::rm_mass_probe_kernel<decltype(tag)::value>; });
-}
-using MassCountFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, const uint32_t*, unsigned long long*, unsigned long long*);
-MassCountFn mass_count_kernel(int loop) {
-    return with_loop(loop, [](auto tag) -> MassCountFn { return rmk::rm_mass_count_kernel<decltype(tag)::value>; });
-}
 static_assert(rmk::kMoments == (uint32_t)RM_MOMENTS, "a row holds the moments of enum rm_moment");
 constexpr uint32_t kMaxMassDim = 4096u;  // rm_mass_moments: every sum below 2^60 (rm_abi.h)
-using TopoProbeFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, double, double, uint8_t*, unsigned long long*);
-TopoProbeFn topo_probe_kernel(int loop) {
-    return with_loop(loop, [](auto tag) -> TopoProbeFn { return rmk::rm_topo_probe_kernel<decltype(tag)::value>; });
-}
-using TopoOccupancyFn = void (*)(rmk::QueryLaunch, rmk::SparseGrid, float, const uint8_t*, uint8_t*, unsigned long long*);
-TopoOccupancyFn topo_occupancy_kernel(int loop) {
-    return with_loop(loop, [](auto tag) -> TopoOccupancyFn { return rmk::rm_topo_occupancy_kernel<decltype(tag)::value>; });
-}
 constexpr uint32_t kMaxTopoDim = 1024u;        // rm_label_solid: labels are linear indices with the two top bits free ...
 constexpr uint64_t kMaxTopoPoints = 1ull << 28;  // ... and every moment stays far below 2^60
 constexpr uint32_t kMaxMergePasses = 8u;
@@ -1682,15 +1651,6 @@ static_assert(rmk::kTopoExterior == RM_TOPO_EXTERIOR && rmk::kTopoCavityBit == R
 static_assert(rmk::kDistInside == RM_DIST_INSIDE_BIT && rmk::kDistNone == RM_DIST_NONE, "the distance volume's marks");
 static_assert(rml::kDistMaxAxis == kMaxTopoDim, "a column tile holds the longest axis");
 constexpr uint32_t kMaxDistR2 = 1u << 22;  // rm_distance_features: every finite D2 is below it
-// One workgroup of `kernel` per grid entry, with the query's LDS columns behind the kernel's own LDS.
-template <class K, class... Args>
-int sparse_launch(rm_ctx* c, K kernel, uint32_t blocks, size_t shmem, hipStream_t s, Args... args) {
-    if (shmem + 4096u > 64u * 1024u)
-        HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), shmem, s, args...);
-    HIP_TRY(c, hipGetLastError());
-    return RM_OK;
-}
 
 // The lattice of a caller's occupancy: the unit lattice at the origin.
 constexpr float kUnitOrigin[3] = {0.0f, 0.0f, 0.0f}, kUnitStep[3] = {1.0f, 1.0f, 1.0f};
@@ -1701,13 +1661,14 @@ rmk::SparseGrid sparse_grid(const float* o, const float* st, uint32_t nx, uint32
                            (nx + rmk::kBrick - 1u) / rmk::kBrick, (ny + rmk::kBrick - 1u) / rmk::kBrick, (nz + rmk::kBrick - 1u) / rmk::kBrick, 0u};
 }
 
-// What a call over the bricks of a lattice does after query_begin (which gave shmem): the LDS check of its workgroups (the
-// query's columns behind 4 KiB of their own), the bounds of the program for points up to the lattice's largest coordinate (as
-// the kernels compute it), the lattice in bricks.
-int brick_lattice(rm_ctx* c, const char* fn, size_t shmem, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
+// What a call over the bricks of a lattice does after QueryCall::begin: the LDS check of its workgroups (the query's columns
+// behind the brick kernels' own LDS), the bounds of the program for points up to the lattice's largest coordinate (as the
+// kernels compute it), the lattice in bricks.
+int brick_lattice(const QueryCall& q, const char* fn, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
                   RmProgramBound* bound, rmk::SparseGrid* g) {
-    if (shmem + 4096u > std::max<size_t>(c->max_lds, 64u * 1024u))
-        return fail(c, RM_ERR_TOO_LARGE, "%s: the program needs %zu bytes of LDS per workgroup", fn, shmem + 4096u);
+    rm_ctx* c = q.c;
+    if (!q.fits(rml::kQueryOwnBrick))
+        return fail(c, RM_ERR_TOO_LARGE, "%s: the program needs %zu bytes of LDS per workgroup", fn, (size_t)q.lds.behind(rml::kQueryOwnBrick).bytes);
     double P = 0.0;
     const uint32_t dims[3] = {nx, ny, nz};
     for (int a = 0; a < 3; a++) {
@@ -1727,6 +1688,42 @@ int count_bricks(rm_ctx* c, const char* fn, rmk::SparseGrid* g) {
     return RM_OK;
 }
 
+// The front of a pass over the bricks, in the tables B of the buffer at `base` (regions psums, ptot, evals): the evaluation
+// counter zeroed, the probe `probe` of n_pblocks blocks of 256 bricks on (g, level, the program's bounds, its table, psums,
+// extra...), the scan of its block sums (kept in the low half, inside in the high half -> ptot).
+template <class F, class Tables, class T, class... Extra>
+int brick_probe(const QueryCall& q, F&& probe, const rmk::SparseGrid& g, float level, const RmProgramBound& bound, uint32_t n_pblocks,
+                const Tables& B, char* base, T* table, Extra... extra) {
+    unsigned long long* psums = B.psums.at(base);
+    HIP_TRY(q.c, hipMemsetAsync(B.evals.at(base), 0, 8, q.s));
+    if (int rc = q.launch(probe, n_pblocks, rml::kQueryOwnBrick, g, level, bound.L, 2.0 * bound.E, table, psums, extra...)) return rc;
+    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, q.s, psums, n_pblocks, B.ptot.at(base));
+    HIP_TRY(q.c, hipGetLastError());
+    return RM_OK;
+}
+
+// The whole pass of a call that goes on with the kept bricks alone: the front above with the keep flags in B.boff, its two
+// totals read into tot (kept, inside), and -- any kept -- their indices compacted into the list that reserve_kept(kept, &klist)
+// makes room for.
+template <class F, class Tables, class R, class... Extra>
+int brick_pass(const QueryCall& q, F&& probe, const rmk::SparseGrid& g, float level, const RmProgramBound& bound, uint32_t n_entries,
+               uint32_t n_pblocks, const Tables& B, char* base, uint64_t tot[2], R&& reserve_kept, Extra... extra) {
+    rm_ctx* c = q.c;
+    uint32_t* boff = B.boff.at(base);
+    if (int rc = brick_probe(q, probe, g, level, bound, n_pblocks, B, base, boff, extra...)) return rc;
+    unsigned long long t[2] = {0ull, 0ull};
+    HIP_TRY(c, hipMemcpyAsync(t, B.ptot.at(base), sizeof t, hipMemcpyDeviceToHost, q.s));
+    HIP_TRY(c, hipStreamSynchronize(q.s));
+    tot[0] = t[0];
+    tot[1] = t[1];
+    if (t[0] == 0u) return RM_OK;
+    uint32_t* klist = nullptr;
+    if (int rc = reserve_kept(tot[0], &klist)) return rc;
+    hipLaunchKernelGGL(rmk::rm_sparse_compact_kernel, dim3(n_pblocks), dim3(256), 0, q.s, n_entries,
+                       static_cast<const unsigned long long*>(B.psums.at(base)), boff, klist);
+    return RM_OK;
+}
+
 }  // namespace
 
 RM_EXPORT int rm_sample_grid(rm_ctx* c, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
@@ -1740,15 +1737,13 @@ RM_EXPORT int rm_sample_grid(rm_ctx* c, const float* origin, const float* step, 
     if (is_device && misaligned(out_dist, 4)) return fail(c, RM_ERR_ARG, "rm_sample_grid: out_dist needs 4-byte alignment");
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = dest_stream(c, is_device, stream);
-    rmk::QueryLaunch Q;
-    int loop = 0;
-    size_t shmem = 0;
-    int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);
+    QueryCall q;
+    int rc = q.begin(c, s, false, false);
     if (rc != RM_OK) return rc;
     Outputs o(c, is_device, c->d_qout);
     o.add(out_dist, n * 4u);
     if ((rc = o.reserve()) != RM_OK) return rc;
-    rc = launch_grid(c, Q, loop, shmem, s, origin, step, nx, ny, n, o.dev<float>(0));
+    rc = launch_grid(q, origin, step, nx, ny, n, o.dev<float>(0));
     return rc == RM_OK ? o.finish(s) : rc;
 }
 
@@ -1763,10 +1758,8 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
         return fail(c, RM_ERR_RANGE, "rm_extract_mesh: lattice %ux%ux%u: 2..65536 points per axis, at most 2^28 in all", nx, ny, nz);
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = c->stream;
-    rmk::QueryLaunch Q;
-    int loop = 0;
-    size_t shmem = 0;
-    int rc = query_begin(c, s, (flags & RM_MESH_IDS) != 0, false, &Q, &loop, &shmem);  // after a device read of the previous mesh, too
+    QueryCall q;
+    int rc = q.begin(c, s, (flags & RM_MESH_IDS) != 0, false);  // after a device read of the previous mesh, too
     if (rc != RM_OK) return rc;
     c->mesh.drop();
     const uint32_t n = (uint32_t)n64, nb = (n + rmk::kMeshBlock - 1u) / rmk::kMeshBlock;
@@ -1779,7 +1772,7 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
     unsigned long long* sums = S.sums.at(sc);
     uint32_t* totals = S.totals.at(sc);
     const rmk::MeshGrid g{origin[0], origin[1], origin[2], step[0], step[1], step[2], nx, ny, nz, n};
-    if ((rc = launch_grid(c, Q, loop, shmem, s, origin, step, nx, ny, n, dist)) != RM_OK) return rc;
+    if ((rc = launch_grid(q, origin, step, nx, ny, n, dist)) != RM_OK) return rc;
     hipLaunchKernelGGL(rmk::rm_mesh_count_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist), sums);
     hipLaunchKernelGGL(rmk::rm_mesh_scan_kernel, dim3(1), dim3(1024), 0, s, sums, nb, totals);
     HIP_TRY(c, hipGetLastError());
@@ -1799,7 +1792,7 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
             hipLaunchKernelGGL(rmk::rm_mesh_triangle_kernel, dim3(nb), dim3(256), 0, s, g, offs, static_cast<const uint32_t*>(vbase),
                                static_cast<const uint8_t*>(fl), L.triangles.at(m));
         HIP_TRY(c, hipGetLastError());
-        if ((rc = point_attributes(c, Q, loop, shmem, s, flags, V, verts, m, L.normals, L.ids)) != RM_OK) return rc;
+        if ((rc = point_attributes(q, flags, V, verts, m, L.normals, L.ids)) != RM_OK) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     out_counts[0] = V;
@@ -1828,15 +1821,13 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
         return fail(c, RM_ERR_RANGE, "rm_extract_mesh_sparse: lattice %ux%ux%u: 2..65536 points per axis", nx, ny, nz);
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = c->stream;
-    rmk::QueryLaunch Q;
-    int loop = 0;
-    size_t shmem = 0;
-    int rc = query_begin(c, s, (flags & RM_MESH_IDS) != 0, false, &Q, &loop, &shmem);  // after a device read of the previous mesh, too
+    QueryCall q;
+    int rc = q.begin(c, s, (flags & RM_MESH_IDS) != 0, false);  // after a device read of the previous mesh, too
     if (rc != RM_OK) return rc;
     RmProgramBound bound;
     rmk::SparseGrid g;
-    if ((rc = brick_lattice(c, "rm_extract_mesh_sparse", shmem, origin, step, nx, ny, nz, &bound, &g)) != RM_OK) return rc;
-    c->mesh.drop();  // (brick_lattice refuses at its LDS check only: the program's bound decodes what query_begin has decoded)
+    if ((rc = brick_lattice(q, "rm_extract_mesh_sparse", origin, step, nx, ny, nz, &bound, &g)) != RM_OK) return rc;
+    c->mesh.drop();  // (brick_lattice refuses at its LDS check only: the program's bound decodes what QueryCall::begin has decoded)
     if ((rc = count_bricks(c, "rm_extract_mesh_sparse", &g)) != RM_OK) return rc;
     // per brick: 4 B (keep flag, then the kept bricks before it); per 256 bricks a block sum; totals and the evaluation count
     const uint32_t n_entries = g.nb + 1u, n_pblocks = (n_entries + 255u) / 256u;
@@ -1844,28 +1835,29 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
     if ((rc = c->d_mbricks.reserve(c, B.bytes)) != RM_OK) return rc;
     char* bs = c->d_mbricks.p;
     uint32_t* boff = B.boff.at(bs);
-    unsigned long long* psums = B.psums.at(bs);
-    unsigned long long* ptot = B.ptot.at(bs);
     unsigned long long* evals = B.evals.at(bs);
-    HIP_TRY(c, hipMemsetAsync(evals, 0, 8, s));
-    if ((rc = sparse_launch(c, sparse_probe_kernel(loop), n_pblocks, shmem, s, Q, g, level, bound.L, 2.0 * bound.E, boff, psums)) != RM_OK) return rc;
-    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, psums, n_pblocks, ptot);
-    HIP_TRY(c, hipGetLastError());
-    unsigned long long tot[2] = {0ull, 0ull};
-    HIP_TRY(c, hipMemcpyAsync(tot, ptot, sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    // per kept brick: its index, its segment map, its tile of distances, 64 segment words and their first (vertex, triangle)
+    using Kept = rml::SparseKeptScratch<rmk::SparseSegMap, uint2>;
+    Kept S(0u, rmk::kTilePoints, 0u, 0u);
+    uint32_t n_segs = 0u, n_sblocks = 0u;
+    uint64_t tot[2] = {0u, 0u};
+    rc = brick_pass(q, RM_BY_LOOP(rm_sparse_probe_kernel), g, level, bound, n_entries, n_pblocks, B, bs, tot, [&](uint64_t kept, uint32_t** klist) {
+        if (kept * rmk::kBrickSegs >= 0xFFFFFFFFull)
+            return fail(c, RM_ERR_DEVICE, "rm_extract_mesh_sparse: %llu bricks to evaluate: more than the segment index holds", (unsigned long long)kept);
+        n_segs = (uint32_t)(kept * rmk::kBrickSegs);
+        n_sblocks = (n_segs + rmk::kSegBlock - 1u) / rmk::kSegBlock;
+        S = Kept(kept, rmk::kTilePoints, n_segs, n_sblocks);
+        if (int rrc = c->d_mscratch.reserve(c, S.bytes)) return rrc;
+        *klist = S.klist.at(c->d_mscratch.p);
+        return (int)RM_OK;
+    });
+    if (rc != RM_OK) return rc;
     const uint64_t K = tot[0];
     uint64_t V = 0, T = 0, n_evals = g.nb;
     size_t kept_bytes = 0;
     rml::MeshLayout L = mesh_layout(0, 0, flags);
     if (K > 0u) {
-        if (K * rmk::kBrickSegs >= 0xFFFFFFFFull)
-            return fail(c, RM_ERR_DEVICE, "rm_extract_mesh_sparse: %llu bricks to evaluate: more than the segment index holds", (unsigned long long)K);
-        // per kept brick: its index, its segment map, its tile of distances, 64 segment words and their first (vertex, triangle)
-        const uint32_t n_segs = (uint32_t)(K * rmk::kBrickSegs), n_sblocks = (n_segs + rmk::kSegBlock - 1u) / rmk::kSegBlock;
-        const rml::SparseKeptScratch<rmk::SparseSegMap, uint2> S(K, rmk::kTilePoints, n_segs, n_sblocks);
         kept_bytes = S.bytes;
-        if ((rc = c->d_mscratch.reserve(c, kept_bytes)) != RM_OK) return rc;
         char* sc = c->d_mscratch.p;
         uint32_t* klist = S.klist.at(sc);
         rmk::SparseSegMap* maps = S.maps.at(sc);
@@ -1874,10 +1866,8 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
         uint2* first = S.first.at(sc);
         unsigned long long* ssums = S.ssums.at(sc);
         unsigned long long* stot = S.stot.at(sc);
-        hipLaunchKernelGGL(rmk::rm_sparse_compact_kernel, dim3(n_pblocks), dim3(256), 0, s, n_entries,
-                           static_cast<const unsigned long long*>(psums), boff, klist);
-        if ((rc = sparse_launch(c, sparse_count_kernel(loop), (uint32_t)K, shmem, s, Q, g, level, static_cast<const uint32_t*>(boff),
-                                static_cast<const uint32_t*>(klist), tiles, maps, words, evals)) != RM_OK)
+        if ((rc = q.launch(RM_BY_LOOP(rm_sparse_count_kernel), (uint32_t)K, rml::kQueryOwnBrick, g, level, static_cast<const uint32_t*>(boff),
+                           static_cast<const uint32_t*>(klist), tiles, maps, words, evals)) != RM_OK)
             return rc;
         hipLaunchKernelGGL(rmk::rm_sparse_seg_sum_kernel, dim3(n_sblocks), dim3(256), 0, s, n_segs, static_cast<const uint32_t*>(words), ssums);
         hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, ssums, n_sblocks, stot);
@@ -1903,7 +1893,7 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
                                static_cast<const rmk::SparseSegMap*>(maps), static_cast<const uint32_t*>(words), static_cast<const uint2*>(first),
                                L.vertices.at(m), L.triangles.at(m));
             HIP_TRY(c, hipGetLastError());
-            if ((rc = point_attributes(c, Q, loop, shmem, s, flags, V, L.vertices.at(m), m, L.normals, L.ids)) != RM_OK) return rc;
+            if ((rc = point_attributes(q, flags, V, L.vertices.at(m), m, L.normals, L.ids)) != RM_OK) return rc;
         }
         HIP_TRY(c, hipStreamSynchronize(s));
     }
@@ -1930,47 +1920,38 @@ RM_EXPORT int rm_mass_moments(rm_ctx* c, const float* origin, const float* step,
         return fail(c, RM_ERR_RANGE, "rm_mass_moments: lattice %ux%ux%u: 2..4096 points per axis", nx, ny, nz);
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = c->stream;
-    rmk::QueryLaunch Q;
-    int loop = 0;
-    size_t shmem = 0;
-    int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);
+    QueryCall q;
+    int rc = q.begin(c, s, false, false);
     if (rc != RM_OK) return rc;
     RmProgramBound bound;
     rmk::SparseGrid g;
-    if ((rc = brick_lattice(c, "rm_mass_moments", shmem, origin, step, nx, ny, nz, &bound, &g)) != RM_OK) return rc;
+    if ((rc = brick_lattice(q, "rm_mass_moments", origin, step, nx, ny, nz, &bound, &g)) != RM_OK) return rc;
     if ((rc = count_bricks(c, "rm_mass_moments", &g)) != RM_OK) return rc;  // (<= 2^27 with 4096 points per axis)
     // the mesh's scratch buffers (neither holds a result): the brick tables, then the kept bricks' rows
     const uint32_t n_entries = g.nb + 1u, n_pblocks = (n_entries + 255u) / 256u;
     const rml::MassBrickTables B(n_entries, n_pblocks);
     if ((rc = c->d_mbricks.reserve(c, B.bytes)) != RM_OK) return rc;
     char* bs = c->d_mbricks.p;
-    uint32_t* boff = B.boff.at(bs);
-    unsigned long long* psums = B.psums.at(bs);
-    unsigned long long* ptot = B.ptot.at(bs);
     unsigned long long* evals = B.evals.at(bs);
     unsigned long long* prows = B.prows.at(bs);
     unsigned long long* result = B.result.at(bs);
-    HIP_TRY(c, hipMemsetAsync(evals, 0, 8, s));
-    if ((rc = sparse_launch(c, mass_probe_kernel(loop), n_pblocks, shmem, s, Q, g, level, bound.L, 2.0 * bound.E, boff, psums, prows)) != RM_OK)
-        return rc;
-    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, psums, n_pblocks, ptot);
-    HIP_TRY(c, hipGetLastError());
-    unsigned long long tot[2] = {0ull, 0ull};
-    HIP_TRY(c, hipMemcpyAsync(tot, ptot, sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    rml::MassKeptScratch S(0u);
+    uint64_t tot[2] = {0u, 0u};
+    rc = brick_pass(q, RM_BY_LOOP(rm_mass_probe_kernel), g, level, bound, n_entries, n_pblocks, B, bs, tot, [&](uint64_t kept, uint32_t** klist) {
+        S = rml::MassKeptScratch(kept);
+        if (int rrc = c->d_mscratch.reserve(c, S.bytes)) return rrc;
+        *klist = S.klist.at(c->d_mscratch.p);
+        return (int)RM_OK;
+    }, prows);
+    if (rc != RM_OK) return rc;
     const uint64_t K = tot[0], n_inside = tot[1];
     size_t kept_bytes = 0;
     const unsigned long long* krows = nullptr;
     if (K > 0u) {
-        const rml::MassKeptScratch S(K);
         kept_bytes = S.bytes;
-        if ((rc = c->d_mscratch.reserve(c, kept_bytes)) != RM_OK) return rc;
         char* sc = c->d_mscratch.p;
-        uint32_t* klist = S.klist.at(sc);
-        hipLaunchKernelGGL(rmk::rm_sparse_compact_kernel, dim3(n_pblocks), dim3(256), 0, s, n_entries,
-                           static_cast<const unsigned long long*>(psums), boff, klist);
-        if ((rc = sparse_launch(c, mass_count_kernel(loop), (uint32_t)K, shmem, s, Q, g, level, static_cast<const uint32_t*>(klist),
-                                S.krows.at(sc), evals)) != RM_OK)
+        if ((rc = q.launch(RM_BY_LOOP(rm_mass_count_kernel), (uint32_t)K, rml::kQueryOwnBrick, g, level, static_cast<const uint32_t*>(S.klist.at(sc)),
+                           S.krows.at(sc), evals)) != RM_OK)
             return rc;
         krows = S.krows.at(sc);
     }
@@ -2080,9 +2061,7 @@ struct OccupancySource {
     const void* bytes;
     int is_device;
     void* stream;
-    rmk::QueryLaunch Q;  // begin's, for fill (a solid)
-    int loop = 0;
-    size_t shmem = 0;
+    QueryCall q;  // begin's, for fill (a solid)
     RmProgramBound bound;
 
     static OccupancySource of_solid(const float* origin, const float* step, float level) {
@@ -2100,9 +2079,9 @@ struct OccupancySource {
             *g = sparse_grid(origin, step, nx, ny, nz);
             return RM_OK;
         }
-        int rc = query_begin(c, s, false, false, &Q, &loop, &shmem);
+        int rc = q.begin(c, s, false, false);
         if (rc != RM_OK) return rc;
-        return brick_lattice(c, fn, shmem, origin, step, nx, ny, nz, &bound, g);
+        return brick_lattice(q, fn, origin, step, nx, ny, nz, &bound, g);
     }
 
     // The occupancy into S.occ.  A solid (rm_topology.h): probe, scan of the block sums (kept low, inside high -> ptot),
@@ -2120,12 +2099,10 @@ struct OccupancySource {
             return RM_OK;
         }
         uint8_t* cls = L.cls.at(sc);
-        unsigned long long *psums = L.psums.at(sc), *evals = L.evals.at(sc);
-        HIP_TRY(c, hipMemsetAsync(evals, 0, 8, s));
-        int rc = sparse_launch(c, topo_probe_kernel(loop), G.n_pblocks, shmem, s, Q, G.g, level, bound.L, 2.0 * bound.E, cls, psums);
+        int rc = brick_probe(q, RM_BY_LOOP(rm_topo_probe_kernel), G.g, level, bound, G.n_pblocks, L, sc, cls);
         if (rc != RM_OK) return rc;
-        hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, psums, G.n_pblocks, L.ptot.at(sc));
-        return sparse_launch(c, topo_occupancy_kernel(loop), G.g.nb, shmem, s, Q, G.g, level, static_cast<const uint8_t*>(cls), L.occ.at(sc), evals);
+        return q.launch(RM_BY_LOOP(rm_topo_occupancy_kernel), G.g.nb, rml::kQueryOwnBrick, G.g, level, static_cast<const uint8_t*>(cls), L.occ.at(sc),
+                        L.evals.at(sc));
     }
 
     // The brick statistics of the fill; those of a caller's occupancy stay 0.
@@ -2901,11 +2878,6 @@ namespace {
 
 constexpr uint64_t kMaxSlicePoints = 1ull << 26;  // lattice points of one layer
 
-using SliceDistFn = void (*)(rmk::QueryLaunch, rmk::SliceGrid, const float*, float*);
-SliceDistFn slice_dist_kernel(int loop) {
-    return with_loop(loop, [](auto tag) -> SliceDistFn { return rmk::rm_slice_dist_kernel<decltype(tag)::value>; });
-}
-
 uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1u) / per); }
 
 }  // namespace
@@ -2932,10 +2904,8 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
         if (!std::isfinite(heights[k])) return fail(c, RM_ERR_ARG, "rm_slice_contours: heights[%u] = %g is not finite", k, (double)heights[k]);
     HIP_TRY(c, hipSetDevice(c->device));
     const hipStream_t s = c->stream;
-    rmk::QueryLaunch Q;
-    int loop = 0;
-    size_t shmem = 0;
-    int rc = query_begin(c, s, (flags & RM_MESH_IDS) != 0, false, &Q, &loop, &shmem);  // after a device read of the previous slices, too
+    QueryCall q;
+    int rc = q.begin(c, s, (flags & RM_MESH_IDS) != 0, false);  // after a device read of the previous slices, too
     if (rc != RM_OK) return rc;
     c->slices.drop();
     const uint32_t n2 = (uint32_t)n2_64, per = std::min(n_layers, std::max(1u, rmk::kSliceBatchPoints / n2));
@@ -2959,7 +2929,7 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
     for (uint32_t k0 = 0; k0 < n_layers; k0 += per) {
         const uint32_t nl = std::min(per, n_layers - k0), n = nl * n2, nb = blocks_of(n, rmk::kSliceBlock), pb = blocks_of(n, 256u);
         const rmk::SliceGrid g{origin_uv[0], origin_uv[1], step_uv[0], step_uv[1], nu, nv, n2, axis, k0, n};
-        if ((rc = query_launch(c, slice_dist_kernel(loop), n, shmem, s, Q, g, static_cast<const float*>(d_heights), dist)) != RM_OK) return rc;
+        if ((rc = q.launch(RM_BY_LOOP(rm_slice_dist_kernel), query_blocks(n), 0u, g, static_cast<const float*>(d_heights), dist)) != RM_OK) return rc;
         hipLaunchKernelGGL(rmk::rm_slice_count_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist), sums);
         hipLaunchKernelGGL(rmk::rm_slice_scan_kernel, dim3(1), dim3(1024), 0, s, sums, nb, d_totals);
         hipLaunchKernelGGL(rmk::rm_slice_pack_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist),
@@ -3041,7 +3011,7 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
     const rml::SliceAttributes A(P, (flags & RM_MESH_NORMALS) != 0, (flags & RM_MESH_IDS) != 0);
     if (P > 0u) {
         if ((rc = c->slices.attr.reserve(c, A.bytes)) != RM_OK) return rc;
-        if ((rc = point_attributes(c, Q, loop, shmem, s, flags, P, c->slices.points.as<const float>(), c->slices.attr.p, A.normals, A.ids)) != RM_OK) return rc;
+        if ((rc = point_attributes(q, flags, P, c->slices.points.as<const float>(), c->slices.attr.p, A.normals, A.ids)) != RM_OK) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(s));
     out_counts[RM_SLICE_POINTS] = P;
@@ -3406,17 +3376,13 @@ RM_EXPORT int rm_selftest_anchor(rm_ctx* c, const float* origin, const float* pa
     if (n == 0u || n > (1u << 20)) return fail(c, RM_ERR_ARG, "rm_selftest_anchor: n = %u, must be 1 .. 2^20", n);
     RmLaunch L;
     if (int rc = cull_probe_begin(c, "rm_selftest_anchor", 8u, 8u, &L)) return rc;  // the march's scene_scale
-    rmk::QueryLaunch Q;
-    int loop = 0;
-    size_t shmem = 0;
-    if (int rc = query_begin(c, c->stream, false, false, &Q, &loop, &shmem)) return rc;
+    QueryCall q;
+    if (int rc = q.begin(c, c->stream, false, false)) return rc;
     DevBuf<float> d_pairs, d_out;
     if (int rc = probe_put(c, d_pairs, pairs, (size_t)n * 6u)) return rc;
     if (int rc = d_out.reserve(c, (size_t)n * 4u)) return rc;
     const float prune_scale = L.scene_scale + ((std::fabs(origin[0]) + std::fabs(origin[1])) + std::fabs(origin[2]));  // prune_scale_v5
-    using AnchorFn = void (*)(rmk::QueryLaunch, float, uint32_t, const float*, float*);
-    const AnchorFn kernel = with_loop(loop, [](auto tag) -> AnchorFn { return rmk::rm_selftest_anchor_kernel<decltype(tag)::value>; });
-    if (int rc = query_launch(c, kernel, n, shmem, c->stream, Q, prune_scale, n, (const float*)d_pairs.p, d_out.p)) return rc;
+    if (int rc = q.launch(RM_BY_LOOP(rm_selftest_anchor_kernel), query_blocks(n), 0u, prune_scale, n, (const float*)d_pairs.p, d_out.p)) return rc;
     if (int rc = probe_finish(c, "rm_selftest_anchor")) return rc;
     HIP_TRY(c, hipMemcpy(out, d_out.p, (size_t)n * 16u, hipMemcpyDeviceToHost));
     return RM_OK;

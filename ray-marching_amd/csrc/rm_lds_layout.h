@@ -110,6 +110,23 @@ struct PixelLds {
     RM_LDS_FN PixelLds(uint32_t n_rec, uint32_t spill_depth) : prog(0u), spill(prog + n_rec * 32u), bytes(spill + spill_depth * 256u * 4u) {}
 };
 
+// ---- Query kernels (rm_query.h query_spill and every kernel that calls it) ---------------------------------------------------
+// The whole dynamic LDS of a 256-thread workgroup: one column per wave of `slots` dwords per lane, slot k of lane l of wave w
+// at dword (w * slots + k) * kQueryLanes + l.  It lies behind `own` bytes of the kernel's static __shared__ arrays, which count
+// against what a workgroup may take: nothing for the point, ray and lattice kernels, kQueryOwnTrace for the traversal march,
+// kQueryOwnBrick for the kernels that work a brick per workgroup -- each of those holds a static_assert next to its arrays.
+constexpr uint32_t kQueryWaves = 4u, kQueryLanes = 64u;
+constexpr uint32_t kQueryOwnTrace = 64u, kQueryOwnBrick = 4096u;
+struct QueryLds {
+    uint32_t slots, own, stride, dynamic, bytes;  // stride: bytes of one wave's column; dynamic: what the launch asks for
+    RM_LDS_FN QueryLds(uint32_t slots_, uint32_t own_)
+        : slots(slots_), own(own_), stride(slots_ * kQueryLanes * 4u), dynamic(kQueryWaves * stride), bytes(own + dynamic) {}
+    RM_LDS_FN QueryLds behind(uint32_t other_own) const { return QueryLds(slots, other_own); }
+    // `cap`: what the device gives one workgroup; a kernel has to ask for more than kLdsLaunchLimit before its launch
+    RM_LDS_FN bool fits(uint64_t cap) const { return bytes <= cap; }
+    RM_LDS_FN bool needs_opt_in() const { return bytes > kLdsLaunchLimit; }
+};
+
 // ---- Distance transform, column passes (rm_distance.h rm_dist_column_kernel) ------------------------------------------------
 // A tile of `xt` adjacent columns of n points each, one word per point, point q of column lx at word q * xt + lx (the lanes of
 // a wave read and write consecutive words).  xt: the power of two that keeps the tile within 32 KB, but at least 16 columns

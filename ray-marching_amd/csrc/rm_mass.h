@@ -44,6 +44,7 @@ __global__ __launch_bounds__(256) void rm_mass_probe_kernel(QueryLaunch Q, Spars
                                                             unsigned long long* __restrict__ rows) {
     __shared__ unsigned long long wsum[4];
     __shared__ unsigned long long wrow[4][kMoments];
+    static_assert(sizeof wsum + sizeof wrow <= rml::kQueryOwnBrick, "the static LDS the host counts in front of the query columns");
     const uint32_t b = blockIdx.x * 256u + threadIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     uint32_t k = 0u, in = 0u;
     unsigned long long m[kMoments];
@@ -98,6 +99,7 @@ __global__ __launch_bounds__(256) void rm_mass_count_kernel(QueryLaunch Q, Spars
                                                             unsigned long long* __restrict__ rows,
                                                             unsigned long long* __restrict__ evaluations) {
     __shared__ uint32_t wred[4][8];
+    static_assert(sizeof wred <= rml::kQueryOwnBrick, "the static LDS the host counts in front of the query columns");
     const uint32_t c = blockIdx.x, b = klist[c], wave = threadIdx.x >> 6;
     const SparseBrick B = sparse_brick(g, b);
     const uint32_t ex = min(kBrick, g.nx - B.i0), ey = min(kBrick, g.ny - B.j0), ez = min(kBrick, g.nz - B.k0);  // its own points

@@ -83,6 +83,7 @@ template <int LOOP>
 __global__ __launch_bounds__(256) void rm_sparse_probe_kernel(QueryLaunch Q, SparseGrid g, float level, double L, double err2,
                                                               uint32_t* __restrict__ keep, unsigned long long* __restrict__ block_sums) {
     __shared__ unsigned long long wsum[4];
+    static_assert(sizeof wsum <= rml::kQueryOwnBrick, "the static LDS the host counts in front of the query columns");
     const uint32_t b = blockIdx.x * 256u + threadIdx.x;
     uint32_t k = 0u;
     if (b < g.nb) {
@@ -181,6 +182,7 @@ __global__ __launch_bounds__(256) void rm_sparse_count_kernel(QueryLaunch Q, Spa
                                                               SparseSegMap* __restrict__ maps, uint32_t* __restrict__ seg_words,
                                                               unsigned long long* __restrict__ evaluations) {
     __shared__ float tile[kTilePoints];
+    static_assert(sizeof tile <= rml::kQueryOwnBrick, "the static LDS the host counts in front of the query columns");
     const uint32_t c = blockIdx.x, b = klist[c];
     const SparseBrick B = sparse_brick(g, b);
     float* spill = query_spill(Q.slots);

@@ -145,10 +145,10 @@ RM_DEV void query_normalize(float& nx, float& ny, float& nz) {
     nx = nx / nl; ny = ny / nl; nz = nz / nl;
 }
 
-// This lane's column of the wave's LDS stack area.
+// This lane's column of the wave's LDS stack area (rml::QueryLds, from which the host sizes the launch).
 RM_DEV float* query_spill(uint32_t slots) {
     extern __shared__ __attribute__((aligned(16))) float qsmem[];
-    return qsmem + (size_t)(threadIdx.x >> 6) * slots * 64u + (threadIdx.x & 63u);
+    return qsmem + (size_t)(threadIdx.x / rml::kQueryLanes) * slots * rml::kQueryLanes + (threadIdx.x % rml::kQueryLanes);
 }
 
 // ---- points: distance, normal, (leaf, material) -----------------------------------------------------------------------

@@ -59,6 +59,7 @@ template <int LOOP>
 __global__ __launch_bounds__(256) void rm_topo_probe_kernel(QueryLaunch Q, SparseGrid g, float level, double L, double err2,
                                                             uint8_t* __restrict__ cls, unsigned long long* __restrict__ block_sums) {
     __shared__ unsigned long long wsum[4];
+    static_assert(sizeof wsum <= rml::kQueryOwnBrick, "the static LDS the host counts in front of the query columns");
     const uint32_t b = blockIdx.x * 256u + threadIdx.x;
     uint32_t k = 0u, in = 0u;
     if (b < g.nb) {

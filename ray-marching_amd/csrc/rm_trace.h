@@ -29,6 +29,7 @@ __global__ __launch_bounds__(256) void rm_trace_march_kernel(QueryLaunch Q, Trac
                                                              uint32_t* __restrict__ counts, float* __restrict__ spans,
                                                              uint32_t* __restrict__ stored, unsigned long long* __restrict__ sums) {
     __shared__ unsigned long long wsum[4];
+    static_assert(sizeof wsum <= rml::kQueryOwnTrace, "the static LDS the host counts in front of the query columns");
     const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
     uint32_t kept = 0;
     if (i < n) {  // (the barrier below needs every lane of the workgroup; the record loops only the lanes that march)

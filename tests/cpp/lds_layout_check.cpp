@@ -1,7 +1,7 @@
 // lds_layout_check.cpp -- the dynamic-LDS layouts of the kernels (ray-marching_amd/csrc/rm_lds_layout.h) on the CPU, under
-// ASan + UBSan (tests/test_decoder_fuzz_cpu.py).  Every region offset and total of rml::CullLds, rml::MarchLds and
-// rml::PixelLds equals the expression the host and the kernels used before the layouts existed -- and the march kernel
-// still writes out for the offsets that depend on the launch --, written out here by hand; regions lie in declaration
+// ASan + UBSan (tests/test_decoder_fuzz_cpu.py).  Every region offset and total of rml::CullLds, rml::MarchLds,
+// rml::PixelLds and rml::QueryLds equals the expression the host and the kernels used before the layouts existed -- and
+// the march kernel still writes out for the offsets that depend on the launch --, written out here by hand; regions lie in declaration
 // order, do not overlap, start on 16-byte boundaries and end at `bytes`; rml::choose_march returns what launch_v5's
 // formulas returned, and never sizes a workgroup below what the launch that follows takes.
 //   lds_layout_check                 the sweeps
@@ -181,6 +181,41 @@ void pixel_kernel() {
         }
 }
 
+// The query kernels' columns: what query_begin, rm_trace_rays and brick_lattice wrote out before the layout existed -- `slots * 64
+// * 4 * 4` bytes, refused when that (+ 64 for the traversal march, + 4096 for a brick kernel) exceeds the device's LDS per
+// workgroup, opted in above 64 KiB -- and query_spill's stride of slots * 64 floats per wave.  slots: everything a program of
+// the largest command buffer (16384 words) can decode to, 2 * spill depth + 3 floats per transform level of the walk at the most.
+void query_columns() {
+    const uint32_t max_slots = 2u * 16384u + 3u * RM_MAX_XFORM_DEPTH;
+    const size_t caps[] = {64u * 1024u, 160u * 1024u};
+    CHECK(rml::kQueryOwnTrace == 64u && rml::kQueryOwnBrick == 4096u && rml::kQueryWaves == 4u && rml::kQueryLanes == 64u);
+    for (uint32_t own : {0u, rml::kQueryOwnTrace, rml::kQueryOwnBrick})
+        for (uint32_t slots = 0; slots <= max_slots; slots++) {
+            const rml::QueryLds L(slots, own);
+            const size_t shmem = (size_t)slots * 64u * 4u * 4u;
+            CHECK(L.slots == slots && L.own == own && L.dynamic == shmem && L.bytes == shmem + own);
+            CHECK(L.stride == (size_t)slots * 64u * sizeof(float) && 4u * (size_t)L.stride == L.dynamic);  // wave w at qsmem + w * slots * 64
+            check_regions({{0u, L.stride}, {L.stride, L.stride}, {2u * (size_t)L.stride, L.stride}, {3u * (size_t)L.stride, L.stride}}, L.dynamic);
+            CHECK(L.needs_opt_in() == (shmem + own > 64u * 1024u));
+            for (size_t cap : caps) CHECK(L.fits(cap) == !(shmem + own > cap));
+            const rml::QueryLds B = L.behind(rml::kQueryOwnBrick);
+            CHECK(B.slots == slots && B.dynamic == L.dynamic && B.bytes == shmem + 4096u);
+        }
+    // the boundary: workgroups of cap - 1 and of cap bytes fit, one of cap + 1 does not (columns are whole KiB: `own` gives the rest)
+    for (size_t cap : caps)
+        for (uint32_t own : {0u, rml::kQueryOwnTrace, rml::kQueryOwnBrick}) {
+            const uint32_t slots = (uint32_t)((cap - own) / 1024u);  // the most that fit behind `own`
+            CHECK(rml::QueryLds(slots, own).fits(cap) == true && rml::QueryLds(slots + 1u, own).fits(cap) == false);
+            for (int delta = -1; delta <= 1; delta++) {
+                const rml::QueryLds L(slots - 1u, (uint32_t)(cap + delta - (size_t)(slots - 1u) * 1024u));
+                CHECK(L.bytes == cap + delta && L.fits(cap) == (delta <= 0));
+                CHECK(L.fits(cap - 1u) == (delta < 0) && L.fits(cap + 1u) == true);
+            }
+        }
+    CHECK(rml::QueryLds(64u, 0u).needs_opt_in() == false && rml::QueryLds(64u, 1u).needs_opt_in() == true);
+    CHECK(rml::QueryLds(63u, rml::kQueryOwnBrick).needs_opt_in() == true && rml::QueryLds(60u, rml::kQueryOwnBrick).needs_opt_in() == false);
+}
+
 // The programs of the GPU test "frames at the layout's decision boundaries": what launch_v5 decides for each, from the decoder's
 // own numbers as fill_launch reads them, for a launch of few enough tiles to start from eight waves per tile.
 int boundary_programs(const char* path) {
@@ -215,6 +250,7 @@ int main(int argc, char** argv) {
     wave_buffers();
     march_and_chooser();
     pixel_kernel();
+    query_columns();
     const int n_prog = argc > 1 ? boundary_programs(argv[1]) : 0;
     std::printf("lds layout ok (%lld checks, %d programs)\n", g_checks, n_prog);
     return 0;
