@@ -333,6 +333,24 @@ pub const RM_SURF_FACET_POS_Z: c_int = 6;
 pub const RM_SURF_FACET_NEG_Z: c_int = 7;
 pub const RM_SURF_MEASURES: c_int = 8;
 
+// Mesh voxelisation (rm_voxelize_mesh / rm_read_voxels).
+// enum rm_voxcount: indices into the counts of a voxelisation; RM_VOX_COUNTS is their number
+pub const RM_VOX_TRIANGLES: c_int = 0;
+pub const RM_VOX_REJECTED: c_int = 1;
+pub const RM_VOX_EDGE_ON: c_int = 2;
+pub const RM_VOX_CROSSINGS: c_int = 3;
+pub const RM_VOX_INSIDE: c_int = 4;
+pub const RM_VOX_OPEN_ROWS: c_int = 5;
+pub const RM_VOX_COUNTS: c_int = 6;
+// enum rm_voxstat: indices into the statistics of a voxelisation; RM_VOX_STATS is their number
+pub const RM_VOX_STAT_BRICKS: c_int = 0;
+pub const RM_VOX_STAT_BRICKS_KEPT: c_int = 1;
+pub const RM_VOX_STAT_BRICKS_INSIDE: c_int = 2;
+pub const RM_VOX_STAT_EVALUATIONS: c_int = 3;
+pub const RM_VOX_STAT_ITEMS: c_int = 4;
+pub const RM_VOX_STAT_SCRATCH_BYTES: c_int = 5;
+pub const RM_VOX_STATS: c_int = 6;
+
 /// The index of `PAIR[a][b][nu]` in the counts of a surface call (the header's `RM_SURF_PAIR`).
 pub const fn surf_pair(a: usize, b: usize, nu: usize) -> usize {
     8 + (8 * a + b) * 13 + nu
@@ -465,6 +483,10 @@ extern "C" {
     pub fn rm_surface_directions(out: *mut c_int, n_out: u32) -> c_int;
     pub fn rm_surface_measures(counts: *const u64, n_counts: u32, step: *const f32, mask_a: u32, mask_b: u32, out: *mut f64,
                                n_out: u32) -> c_int;
+    pub fn rm_voxelize_mesh(ctx: *mut rm_ctx, n_vertices: u32, xyz: *const f32, n_triangles: u32, indices: *const u32,
+                            is_device: c_int, stream: *mut c_void, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32,
+                            out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_read_voxels(ctx: *mut rm_ctx, out_occupancy: *mut c_void, is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_slice_contours(ctx: *mut rm_ctx, axis: u32, origin_uv: *const f32, step_uv: *const f32, nu: u32, nv: u32,
                              heights: *const f32, n_layers: u32, level: f32, flags: u32, out_counts: *mut u64,
                              n_counts: u32) -> c_int;
@@ -610,6 +632,8 @@ pub struct RayMarchingResources {
     support: Cell<Option<(u64, u32)>>,
     /// (lattice points, layers along the build direction, regions) of the last successful islands call: what `read_islands` writes
     islands: Cell<Option<(u64, u32, u64)>>,
+    /// lattice points of the last successful `voxelize_mesh`: what `read_voxels` writes
+    voxels: Cell<Option<u64>>,
 }
 
 unsafe impl Send for RayMarchingResources {} // a context may move between threads; it is not Sync
@@ -624,7 +648,7 @@ impl RayMarchingResources {
             return Err(RmError { status: rc, message: msg.to_string_lossy().into_owned() });
         }
         Ok(Self { ctx, mesh: Cell::new(None), slices: Cell::new(None), topology: Cell::new(None), distance: Cell::new(None),
-                  support: Cell::new(None), islands: Cell::new(None) })
+                  support: Cell::new(None), islands: Cell::new(None), voxels: Cell::new(None) })
     }
 
     fn check(&self, rc: c_int) -> Result<(), RmError> {
@@ -905,6 +929,50 @@ impl RayMarchingResources {
             rm_surface_classes(self.ctx, nx, ny, nz, classes.as_ptr() as *const c_void, 0, std::ptr::null_mut(),
                                out_counts.as_mut_ptr(), RM_SURF_COUNTS as u32, out_stats.as_mut_ptr(), RM_SURF_STATS as u32)
         })
+    }
+
+    /// The occupancy of a triangle mesh in host memory on the lattice (`rm_voxelize_mesh`; 2..1024 points per axis, at most 2^28
+    /// in all), by the even-odd rule along +x: `xyz` holds three floats per vertex, `indices` three vertex indices per triangle,
+    /// or `None` for a soup (every three vertices a triangle).  Fills `out_counts` (at least `RM_VOX_COUNTS` entries indexed by
+    /// `RM_VOX_*`: triangles, rejected, edge-on, crossings, inside points, open rows) and `out_stats` (at least `RM_VOX_STATS`,
+    /// indexed by `RM_VOX_STAT_*`).  Exact integers: every run and every order of the triangles gives the same words.  The
+    /// occupancy stays in the context for `read_voxels`; no other retained result is touched.  Needs no program.
+    pub fn voxelize_mesh(&self, xyz: &[f32], indices: Option<&[u32]>, origin: [f32; 3], step: [f32; 3], nx: u32, ny: u32, nz: u32,
+                         out_counts: &mut [u64], out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(xyz.len() % 3 == 0 && xyz.len() / 3 <= u32::MAX as usize, "voxelize_mesh: xyz holds three floats per vertex");
+        let n_vertices = (xyz.len() / 3) as u32;
+        let n_triangles = match indices {
+            Some(t) => {
+                assert!(t.len() % 3 == 0 && t.len() / 3 <= u32::MAX as usize, "voxelize_mesh: indices holds three words per triangle");
+                (t.len() / 3) as u32
+            }
+            None => {
+                assert!(n_vertices % 3 == 0, "voxelize_mesh: a soup holds three vertices per triangle");
+                n_vertices / 3
+            }
+        };
+        assert!(out_counts.len() >= RM_VOX_COUNTS as usize, "voxelize_mesh: out_counts is shorter than RM_VOX_COUNTS entries");
+        assert!(out_stats.len() >= RM_VOX_STATS as usize, "voxelize_mesh: out_stats is shorter than RM_VOX_STATS entries");
+        self.voxels.set(None);  // a call that failed late may have released the previous occupancy
+        self.check(unsafe {
+            rm_voxelize_mesh(self.ctx, n_vertices, xyz.as_ptr(), n_triangles, indices.map_or(std::ptr::null(), |t| t.as_ptr()), 0,
+                             std::ptr::null_mut(), origin.as_ptr(), step.as_ptr(), nx, ny, nz, out_counts.as_mut_ptr(),
+                             RM_VOX_COUNTS as u32, out_stats.as_mut_ptr(), RM_VOX_STATS as u32)
+        })?;
+        self.voxels.set(Some(nx as u64 * ny as u64 * nz as u64));
+        Ok(())
+    }
+
+    /// The occupancy of the last successful `voxelize_mesh`: one byte per lattice point, 0 or 1, x fastest -- what
+    /// `label_occupancy`, `distance_occupancy`, `support_occupancy`, `islands_occupancy` and `surface_classes` take.
+    /// `RM_ERR_ARG` before any voxelisation.
+    pub fn read_voxels(&self, out_occupancy: &mut [u8]) -> Result<(), RmError> {
+        let n = match self.voxels.get() {
+            Some(n) => n as usize,
+            None => return Err(RmError { status: RM_ERR_ARG, message: "read_voxels: no mesh has been voxelised".to_string() }),
+        };
+        assert!(out_occupancy.len() >= n, "read_voxels: out_occupancy is shorter than {} points", n);
+        self.check(unsafe { rm_read_voxels(self.ctx, out_occupancy.as_mut_ptr() as *mut c_void, 0, std::ptr::null_mut()) })
     }
 
     /// The result of the last successful labelling call: the bodies' rows and the cavities' rows (`RM_MOMENTS` words each, in

@@ -744,6 +744,49 @@ int rm_surface_directions(int* out, uint32_t n_out);
 int rm_surface_measures(const uint64_t* counts, uint32_t n_counts, const float* step, uint32_t mask_a, uint32_t mask_b,
                         double* out, uint32_t n_out);
 
+/* Mesh voxelisation (extension; DESIGN.md section 27 is the contract, to the last bit): a triangle mesh into the occupancy of a
+ * lattice -- the source of the rm_*_occupancy calls and of rm_surface_classes for parts that arrive as STL, OBJ or PLY files.
+ * Needs no program: a context with an empty or invalid command buffer voxelises.
+ * Mesh: xyz holds n_vertices x 3 floats, indices n_triangles x 3 vertex indices, or NULL for a SOUP (triangle t has the vertices
+ * 3 t, 3 t + 1, 3 t + 2; n_vertices == 3 n_triangles).  Both in host memory, or (is_device) both in device memory, 4-byte aligned,
+ * read after the work queued on `stream`.  No host pass looks at the data: device inputs are judged on the device.
+ * Lattice: rm_label_solid's (2..1024 points per axis, at most 2^28 in all, RM_ERR_RANGE otherwise; linear index
+ * i + nx * (j + ny * k)); origin and step as rm_sample_grid takes them, but the snapping below is an exact affine map in binary64,
+ * not the o + (float)i * s of the lattice calls.
+ * A coordinate v on axis a becomes q = rint(((double)v - (double)o_a) / (double)s_a * 64): index space with 6 fractional bits,
+ * every operation rounded once, half to even; lattice point i sits at 64 i.  A triangle is REJECTED (counted, contributes
+ * nothing) when an index is >= n_vertices, a coordinate is not finite, or some |q| > 2^17.  An accepted triangle whose projection
+ * onto y-z has no area is EDGE_ON (counted, skipped).  Any other crosses the row (j, k) -- the ray along +x through (64 j, 64 k) --
+ * iff its three edge functions admit the row: E > 0, or E == 0 and (dy > 0 or (dy == 0 and dz > 0)) for the directed edge (dy, dz)
+ * of the triangle oriented counter-clockwise in y-z, so that a row through a shared edge or vertex counts as a generic row would.
+ * The crossing at x (exact, a quotient of int64) toggles bit t = ceil(x / 64), clamped to [0, nx], of the row's nx + 1 bits;
+ * occupancy(i, j, k) is the XOR of the bits 0..i: the even-odd rule, a point exactly on the surface inside where the row enters.
+ * A row whose bit nx has an odd prefix -- an odd number of crossings in all -- is an OPEN ROW: the mesh is not closed along it.
+ * out_counts[RM_VOX_*]: TRIANGLES (n_triangles), REJECTED, EDGE_ON, CROSSINGS (every admitted pair of a row and a triangle, the
+ * clamped ones included), INSIDE (points of occupancy 1), OPEN_ROWS.  out_stats[RM_VOX_STAT_*]: BRICKS, BRICKS_KEPT,
+ * BRICKS_INSIDE, EVALUATIONS are 0, as for a caller's occupancy; ITEMS, the work items of 64 rows the raster launch took;
+ * SCRATCH_BYTES, the device memory the call used beside the occupancy.
+ * Every word is an integer that no order of execution changes: two runs, any order of the triangles, any rotation or reversal
+ * of a triangle's vertices, and any correct implementation give identical words.
+ * The call is synchronous on the context's own stream, ordered after its earlier work.  The occupancy (one byte per point, 0 or
+ * 1, x fastest -- what rm_label_occupancy, rm_distance_occupancy, rm_support_occupancy, rm_islands_occupancy and
+ * rm_surface_classes take) stays in the context until the next rm_voxelize_mesh; rm_read_voxels copies it out (is_device and
+ * stream as for rm_read_distance).  No other retained result is dropped or replaced, and no other call replaces this one.
+ * Errors, every check before the first launch, outputs untouched and the previous voxel result still readable: RM_ERR_NULL for
+ * a NULL ctx, xyz, out_counts or out_stats (and origin or step); RM_ERR_ARG for n_counts < RM_VOX_COUNTS, then n_stats <
+ * RM_VOX_STATS, then an origin or a step that is not finite or a step <= 0; RM_ERR_RANGE for the lattice; RM_ERR_ARG for
+ * n_triangles == 0, n_vertices == 0, a soup with n_vertices != 3 n_triangles and device arrays off 4-byte alignment.  After the
+ * first launches: RM_ERR_TOO_LARGE for 2^31 work items or more (the previous result is still readable); RM_ERR_DEVICE when
+ * device memory runs out.  rm_read_voxels: RM_ERR_ARG before any voxelisation. */
+enum rm_voxcount { RM_VOX_TRIANGLES = 0, RM_VOX_REJECTED = 1, RM_VOX_EDGE_ON = 2, RM_VOX_CROSSINGS = 3, RM_VOX_INSIDE = 4,
+                   RM_VOX_OPEN_ROWS = 5, RM_VOX_COUNTS = 6 };
+enum rm_voxstat { RM_VOX_STAT_BRICKS = 0, RM_VOX_STAT_BRICKS_KEPT = 1, RM_VOX_STAT_BRICKS_INSIDE = 2,
+                  RM_VOX_STAT_EVALUATIONS = 3, RM_VOX_STAT_ITEMS = 4, RM_VOX_STAT_SCRATCH_BYTES = 5, RM_VOX_STATS = 6 };
+int rm_voxelize_mesh(rm_ctx* ctx, uint32_t n_vertices, const float* xyz, uint32_t n_triangles, const uint32_t* indices,
+                     int is_device, void* stream, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz,
+                     uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats);
+int rm_read_voxels(rm_ctx* ctx, void* out_occupancy, int is_device, void* stream);
+
 /* Slicing (extension; DESIGN.md section 16 is the contract, to the last bit): the closed outlines of the solid d < level in a
  * stack of planes, as ordered polylines -- what a slicer or a section drawing needs, evaluated directly on a 2-D lattice
  * per layer instead of through a triangle mesh.  From the program, limits and material table as they are at the call.

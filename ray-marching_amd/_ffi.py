@@ -112,6 +112,12 @@ SURF_STAT_NAMES = SUP_STAT_NAMES
 (RM_SURF_AREA, RM_SURF_FACET_AREA, RM_SURF_FACET_POS_X, RM_SURF_FACET_NEG_X, RM_SURF_FACET_POS_Y, RM_SURF_FACET_NEG_Y,
  RM_SURF_FACET_POS_Z, RM_SURF_FACET_NEG_Z, RM_SURF_MEASURES) = range(9)
 SURF_MEASURE_NAMES = ("area", "facet_area", "facet_pos_x", "facet_neg_x", "facet_pos_y", "facet_neg_y", "facet_pos_z", "facet_neg_z")
+# mesh voxelisation (rm_voxelize_mesh / rm_read_voxels): enum rm_voxcount, enum rm_voxstat
+(RM_VOX_TRIANGLES, RM_VOX_REJECTED, RM_VOX_EDGE_ON, RM_VOX_CROSSINGS, RM_VOX_INSIDE, RM_VOX_OPEN_ROWS, RM_VOX_COUNTS) = range(7)
+VOX_COUNT_NAMES = ("triangles", "rejected", "edge_on", "crossings", "inside", "open_rows")
+(RM_VOX_STAT_BRICKS, RM_VOX_STAT_BRICKS_KEPT, RM_VOX_STAT_BRICKS_INSIDE, RM_VOX_STAT_EVALUATIONS, RM_VOX_STAT_ITEMS,
+ RM_VOX_STAT_SCRATCH_BYTES, RM_VOX_STATS) = range(7)
+VOX_STAT_NAMES = ("bricks", "bricks_kept", "bricks_inside", "evaluations", "items", "scratch_bytes")
 
 
 def RM_SURF_PAIR(a, b, nu):
@@ -285,6 +291,10 @@ def hip_lib():
         L.rm_surface_directions.restype = C.c_int
         L.rm_surface_measures.argtypes = [C.POINTER(u64), u32, f3, u32, u32, C.POINTER(C.c_double), u32]
         L.rm_surface_measures.restype = C.c_int
+        L.rm_voxelize_mesh.argtypes = [vp, u32, vp, u32, vp, C.c_int, vp, f3, f3, u32, u32, u32, C.POINTER(u64), u32, C.POINTER(u64), u32]
+        L.rm_voxelize_mesh.restype = C.c_int
+        L.rm_read_voxels.argtypes = [vp, vp, C.c_int, vp]
+        L.rm_read_voxels.restype = C.c_int
         L.rm_slice_contours.argtypes = [vp, u32, f3, f3, u32, u32, f3, u32, C.c_float, u32, C.POINTER(u64), u32]
         L.rm_slice_contours.restype = C.c_int
         L.rm_read_slices.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]

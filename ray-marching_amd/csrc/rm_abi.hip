@@ -36,6 +36,7 @@
 #include "rm_support.h"
 #include "rm_islands.h"
 #include "rm_surface.h"
+#include "rm_voxel.h"
 #include "rm_slice.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
@@ -213,6 +214,14 @@ struct rm_ctx {
         void drop() { valid = false; }
         void commit(uint32_t n_, uint32_t nh_, uint64_t regions_) { n = n_, nh = nh_, regions = regions_, valid = true; }
     } isl;
+    struct Voxels {  // rm_voxelize_mesh: the occupancy of nx x ny x nz points, one byte each
+        DevBuf<char> buf;
+        bool valid = false;
+        uint32_t nx = 0, ny = 0, nz = 0;
+        size_t points() const { return (size_t)nx * ny * nz; }
+        void drop() { valid = false; }
+        void commit(uint32_t nx_, uint32_t ny_, uint32_t nz_) { nx = nx_, ny = ny_, nz = nz_, valid = true; }
+    } vox;
     // scratch for host-destination draws and batch uniforms
     DevBuf<char> d_out;
     DevBuf<rm_uniforms> d_frames;
@@ -2851,6 +2860,116 @@ RM_EXPORT int rm_surface_measures(const uint64_t* counts, uint32_t n_counts, con
     }
     out[RM_SURF_AREA] = 2.0 * dV * sum;
     return RM_OK;
+}
+
+// ---- mesh voxelisation (rm_voxel.h) ----
+namespace {
+
+static_assert(rmk::kVoxTriWords == rml::kVoxTriWords && (uint32_t)rmk::VOX_N_COUNTERS == rml::kVoxCounters, "VoxScratch holds the kernels' records");
+static_assert(RM_VOX_STAT_BRICKS == kStatBricks && RM_VOX_STAT_BRICKS_KEPT == kStatBricksKept && RM_VOX_STAT_BRICKS_INSIDE == kStatBricksInside &&
+                  RM_VOX_STAT_EVALUATIONS == kStatEvaluations && RM_VOX_STAT_SCRATCH_BYTES == RM_VOX_STATS - 1,
+              "the brick statistics first (zeros, as for a caller's occupancy) and the scratch size last");
+constexpr uint64_t kMaxVoxItems = 1ull << 31;
+
+// The launches of a voxelisation: how many blocks of triangles, words of the bit volume, fill workgroups and folded rows.
+struct VoxPlan {
+    uint32_t n, n_blocks, row_words, n_words, n_groups, n_fblocks;
+    VoxPlan(uint32_t n_triangles, uint32_t nx, uint32_t ny, uint32_t nz)
+        : n(nx * ny * nz), n_blocks((uint32_t)(((uint64_t)n_triangles + rmk::kVoxBlock - 1u) / rmk::kVoxBlock)), row_words(rml::vox_row_words(nx)),
+          n_words(ny * nz * row_words), n_groups((n + rml::kVoxFillCells - 1u) / rml::kVoxFillCells),
+          n_fblocks((n_groups + rmk::kTopoFold - 1u) / rmk::kTopoFold) {}  // (rows <= 2^20, 33 words each at most)
+};
+
+}  // namespace
+
+RM_EXPORT int rm_voxelize_mesh(rm_ctx* c, uint32_t n_vertices, const float* xyz, uint32_t n_triangles, const uint32_t* indices, int is_device,
+                               void* stream, const float* origin, const float* step, uint32_t nx, uint32_t ny, uint32_t nz, uint64_t* out_counts,
+                               uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
+    const char* fn = "rm_voxelize_mesh";
+    if (!c) return RM_ERR_NULL;
+    if (!xyz || !out_counts || !out_stats) return fail(c, RM_ERR_NULL, "%s: xyz, out_counts or out_stats is NULL", fn);
+    if (n_counts < (uint32_t)RM_VOX_COUNTS) return fail(c, RM_ERR_ARG, "%s: n_counts %u < RM_VOX_COUNTS", fn, n_counts);
+    if (n_stats < (uint32_t)RM_VOX_STATS) return fail(c, RM_ERR_ARG, "%s: n_stats %u < RM_VOX_STATS", fn, n_stats);
+    if (int rc = check_lattice(c, fn, origin, step)) return rc;
+    if (int rc = check_topo_lattice(c, fn, nx, ny, nz)) return rc;
+    if (n_triangles == 0u || n_vertices == 0u) return fail(c, RM_ERR_ARG, "%s: %u vertices, %u triangles: at least one of each", fn, n_vertices, n_triangles);
+    if (!indices && (uint64_t)n_vertices != 3ull * n_triangles)
+        return fail(c, RM_ERR_ARG, "%s: a soup (indices NULL) of %u triangles has %llu vertices, not %u", fn, n_triangles, 3ull * n_triangles, n_vertices);
+    if (is_device && (misaligned(xyz, 4) || misaligned(indices, 4))) return fail(c, RM_ERR_ARG, "%s: device xyz and indices need 4-byte alignment", fn);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    order_with_previous(c, s);  // after a device read of the last occupancy, too
+    const VoxPlan P(n_triangles, nx, ny, nz);
+    const rml::VoxScratch S(n_triangles, P.n_blocks, P.n_words, P.n_groups, P.n_fblocks, is_device ? 0u : n_vertices,
+                            is_device || !indices ? 0u : n_triangles);
+    int rc = c->d_mscratch.reserve(c, S.bytes);
+    if (rc != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    const float* d_xyz = xyz;
+    const uint32_t* d_idx = indices;
+    if (is_device) {
+        // the caller's arrays are ready when the work queued on its stream is done; the call is synchronous anyway
+        const hipStream_t su = user_stream(c, stream);
+        if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
+    } else {
+        HIP_TRY(c, hipMemcpyAsync(S.xyz.at(sc), xyz, S.xyz.bytes, hipMemcpyHostToDevice, s));
+        d_xyz = S.xyz.at(sc);
+        if (indices) {
+            HIP_TRY(c, hipMemcpyAsync(S.idx.at(sc), indices, S.idx.bytes, hipMemcpyHostToDevice, s));
+            d_idx = S.idx.at(sc);
+        }
+    }
+    const rmk::VoxLattice g{origin[0], origin[1], origin[2], step[0], step[1], step[2], nx, ny, nz, P.row_words};
+    uint32_t* bits = S.bits.at(sc);
+    unsigned long long* counters = S.counters.at(sc);
+    HIP_TRY(c, hipMemsetAsync(sc + S.clear_offset(), 0, S.clear_bytes(), s));
+    hipLaunchKernelGGL(rmk::rm_vox_setup_kernel, dim3(P.n_blocks), dim3(256), 0, s, g, n_vertices, d_xyz, n_triangles, d_idx, S.tris.at(sc),
+                       S.starts.at(sc), S.bsums.at(sc), bits, counters);
+    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, S.bsums.at(sc), P.n_blocks, S.btot.at(sc));
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long tot[2] = {0ull, 0ull};
+    HIP_TRY(c, hipMemcpyAsync(tot, S.btot.at(sc), sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (tot[0] >= kMaxVoxItems) return fail(c, RM_ERR_TOO_LARGE, "%s: %llu work items of 64 rows: fewer than 2^31", fn, tot[0]);
+    // the last check that can refuse is past: the previous occupancy goes
+    c->vox.drop();
+    if ((rc = c->vox.buf.reserve(c, P.n, "occupancy")) != RM_OK) return rc;
+    const uint32_t n_items = (uint32_t)tot[0];
+    if (n_items)
+        hipLaunchKernelGGL(rmk::rm_vox_raster_kernel, dim3((n_items + 3u) / 4u), dim3(256), 0, s, g, n_triangles, n_items,
+                           static_cast<const uint32_t*>(S.tris.at(sc)), static_cast<const uint32_t*>(S.starts.at(sc)),
+                           static_cast<const unsigned long long*>(S.bsums.at(sc)), bits, counters);
+    constexpr rml::VoxFillLds L;
+    static_assert(L.bytes + 1024u <= rml::kLdsLaunchLimit, "the staged words fit a workgroup's LDS");
+    hipLaunchKernelGGL(rmk::rm_vox_fill_kernel, dim3(P.n_groups), dim3(256), L.bytes, s, nx, P.n, static_cast<const uint32_t*>(bits),
+                       c->vox.buf.as<uint8_t>(), S.rows.at(sc));
+    hipLaunchKernelGGL(rmk::rm_topo_fold_kernel, dim3(P.n_fblocks), dim3(256), 0, s, static_cast<const unsigned long long*>(S.rows.at(sc)), P.n_groups,
+                       S.folded.at(sc));
+    hipLaunchKernelGGL(rmk::rm_mass_reduce_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned long long*>(S.folded.at(sc)), P.n_fblocks,
+                       static_cast<const unsigned long long*>(nullptr), 0u, S.result.at(sc));
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long row[RM_MOMENTS], cnt[rmk::VOX_N_COUNTERS];
+    HIP_TRY(c, hipMemcpyAsync(row, S.result.at(sc), sizeof row, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(cnt, counters, sizeof cnt, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    out_counts[RM_VOX_TRIANGLES] = cnt[rmk::VOX_N_TRIANGLES];
+    out_counts[RM_VOX_REJECTED] = cnt[rmk::VOX_N_REJECTED];
+    out_counts[RM_VOX_EDGE_ON] = cnt[rmk::VOX_N_EDGE_ON];
+    out_counts[RM_VOX_CROSSINGS] = cnt[rmk::VOX_N_CROSSINGS];
+    out_counts[RM_VOX_INSIDE] = row[0];
+    out_counts[RM_VOX_OPEN_ROWS] = row[1];
+    for (uint32_t k = 0; k < (uint32_t)RM_VOX_STATS; k++) out_stats[k] = 0u;
+    out_stats[RM_VOX_STAT_ITEMS] = n_items;
+    out_stats[RM_VOX_STAT_SCRATCH_BYTES] = S.bytes;
+    c->vox.commit(nx, ny, nz);
+    return RM_OK;
+}
+
+RM_EXPORT int rm_read_voxels(rm_ctx* c, void* out_occupancy, int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    const rm_ctx::Voxels& r = c->vox;
+    if (!r.valid) return fail(c, RM_ERR_ARG, "rm_read_voxels: no mesh has been voxelised");
+    return read_back(c, is_device, stream, "rm_read_voxels: out_occupancy needs no alignment", {{out_occupancy, r.buf.p, r.points(), 1}});
 }
 
 RM_EXPORT int rm_read_mesh(rm_ctx* c, float* out_vertices, uint32_t* out_triangles, float* out_normals, uint32_t* out_ids,

@@ -128,6 +128,36 @@ struct TopoRows {
     TopoRows(uint64_t B, uint64_t C) : bodies(a.take<unsigned long long>(B * 16u)), cavities(a.take<unsigned long long>(C * 16u)), bytes(a.total) {}
 };
 
+// rm_voxelize_mesh, for n_triangles triangles in n_blocks blocks of 256, a bit volume of n_words u32 words (rows x words of a row
+// of nx + 1 bits) filled by n_groups workgroups: per triangle its record (kVoxTriWords u32: the snapped vertices and its box of
+// rows) and the work items before it in its block; per block the items' sum (scanned in place) and the total; the counters
+// (TRIANGLES, REJECTED, EDGE_ON, CROSSINGS) directly before the bit volume, so that one memset clears both; per fill workgroup one
+// row of 16 words (INSIDE, OPEN_ROWS), per 256 of them one folded row, the reduced row; and the copies of a caller's host arrays
+// (xyz: 3 floats per vertex, idx: 3 indices per triangle; empty for device inputs and for a soup).  The occupancy itself (1 B per
+// point) is the result and lies in a buffer of its own.
+constexpr uint32_t kVoxTriWords = 12u, kVoxCounters = 8u;
+struct VoxScratch {
+    Carver a;
+    Region<uint32_t> tris, starts;
+    Region<unsigned long long> bsums, btot, counters;
+    Region<uint32_t> bits;
+    Region<unsigned long long> rows, folded, result;
+    Region<float> xyz;
+    Region<uint32_t> idx;
+    size_t bytes;
+    VoxScratch(uint32_t n_triangles, uint32_t n_blocks, uint32_t n_words, uint32_t n_groups, uint32_t n_fblocks, uint64_t host_vertices,
+               uint64_t host_triangles)
+        : tris(a.take<uint32_t>((size_t)n_triangles * kVoxTriWords)), starts(a.take<uint32_t>(n_triangles)),
+          bsums(a.take<unsigned long long>(n_blocks)), btot(a.take<unsigned long long>(2)),
+          counters(a.take<unsigned long long>(kVoxCounters)), bits(a.take<uint32_t>(n_words)),
+          rows(a.take<unsigned long long>((size_t)n_groups * 16u)), folded(a.take<unsigned long long>((size_t)n_fblocks * 16u)),
+          result(a.take<unsigned long long>(16)), xyz(a.take<float>(host_vertices * 3u)), idx(a.take<uint32_t>(host_triangles * 3u)),
+          bytes(a.total) {}
+    // counters and bits as one span
+    size_t clear_offset() const { return counters.offset; }
+    size_t clear_bytes() const { return bits.offset + bits.bytes - counters.offset; }
+};
+
 // rm_distance_solid / rm_distance_occupancy, for a lattice of n points in nb bricks: per point its occupancy (1 B); per brick its
 // class (1 B); per 256 bricks the probe's block sum; per 2048 points one row of 16 words (the maxima and the count), per 256 of
 // those rows one folded row; totals, the evaluation count and the reduced row.  The distance volume itself (4 B per point) and

@@ -188,4 +188,16 @@ struct SurfTileLds {
           counts((cls + pitch * rows_y * rows_z + 15u) & ~15u), bytes(counts + kSurfCounts * 4u) {}
 };
 
+// ---- Mesh voxelisation, fill (rm_voxel.h rm_vox_fill_kernel) ------------------------------------------------------------------
+// A workgroup makes kVoxFillCells consecutive bytes of the occupancy.  A row of nx points has nx + 1 bits in vox_row_words(nx) u32
+// words; the cells lie in at most vox_fill_rows(nx) rows (a partial one at either end), whose words are staged as they are
+// (`raw`) and with their prefix parities (`prefix`): kVoxFillMaxWords words each, the most any nx of 2..1024 needs (nx = 2).
+constexpr uint32_t kVoxFillCells = 4096u, kVoxFillMaxWords = 2049u;
+RM_LDS_FN uint32_t vox_row_words(uint32_t nx) { return (nx >> 5) + 1u; }
+RM_LDS_FN uint32_t vox_fill_rows(uint32_t nx) { return (kVoxFillCells - 1u) / nx + 2u; }
+struct VoxFillLds {
+    uint32_t raw, prefix, bytes;
+    RM_LDS_FN VoxFillLds() : raw(0u), prefix((raw + kVoxFillMaxWords * 4u + 15u) & ~15u), bytes(prefix + kVoxFillMaxWords * 4u) {}
+};
+
 }  // namespace rml

@@ -5,7 +5,8 @@ normals, and vertex colours from a material table) and binary STL.
   python -m ray_marching_amd.mesh --scene g32 --lo -2.5 --hi 2.5 --res 1024 --sparse out.ply
 
 extracts the surface of a named scene (csg.scene) on the GPU and writes it; the format follows the file's extension.
-Triangles are wound counter-clockwise seen from outside.  The mesh is open where the surface leaves the box [lo, hi]."""
+Triangles are wound counter-clockwise seen from outside.  The mesh is open where the surface leaves the box [lo, hi].
+read() reads the three formats back (and ASCII STL and ASCII PLY): the source of RayMarchingResources.voxelize_mesh."""
 import argparse
 import struct
 import sys
@@ -132,6 +133,142 @@ def write(mesh, path, materials=None):
         write_stl(mesh, path)
     else:
         raise ValueError("unknown mesh format .%s (obj, ply or stl)" % ext)
+
+
+def read_obj(path):
+    """Wavefront OBJ: the v and f lines; a polygon is fanned from its first corner, a corner's index is what stands before its
+    first slash, 1-based or negative (counted back from the vertices read so far)."""
+    verts, tris = [], []
+    with open(path) as f:
+        for line in f:
+            p = line.split()
+            if not p:
+                continue
+            if p[0] == "v":
+                verts.append((float(p[1]), float(p[2]), float(p[3])))
+            elif p[0] == "f":
+                idx = []
+                for corner in p[1:]:
+                    k = int(corner.split("/")[0])
+                    k = k - 1 if k > 0 else len(verts) + k
+                    if k < 0 or k >= len(verts):
+                        raise ValueError("%s: face corner %r names no vertex read so far" % (path, corner))
+                    idx.append(k)
+                if len(idx) < 3:
+                    raise ValueError("%s: a face of %d corners" % (path, len(idx)))
+                tris += [(idx[0], idx[m], idx[m + 1]) for m in range(1, len(idx) - 1)]
+    return Mesh(np.array(verts, dtype=np.float32).reshape(-1, 3), np.array(tris, dtype=np.uint32).reshape(-1, 3))
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply(path):
+    """PLY, ASCII or binary little-endian: the vertex element's x, y, z (and nx, ny, nz when all three are there) and the face
+    element's index list, polygons fanned; other properties and elements are skipped."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError("%s is not a PLY file" % path)
+    body = data.index(b"\n", end) + 1
+    fmt, elements = None, []                                     # elements: [name, count, [(kind, name, type[, count type])]]
+    for line in data[:end].decode("ascii").splitlines():
+        p = line.split()
+        if not p:
+            continue
+        if p[0] == "format":
+            fmt = p[1]
+        elif p[0] == "element":
+            elements.append([p[1], int(p[2]), []])
+        elif p[0] == "property":
+            if p[1] == "list":
+                elements[-1][2].append(("list", p[4], _PLY_TYPES[p[3]], _PLY_TYPES[p[2]]))
+            else:
+                elements[-1][2].append(("scalar", p[2], _PLY_TYPES[p[1]]))
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError("%s: PLY format %r (ascii or binary_little_endian)" % (path, fmt))
+    verts = normals = None
+    tris = []
+    tokens = iter(data[body:].split()) if fmt == "ascii" else None
+    pos = body
+    for name, count, props in elements:
+        scalar_only = all(p[0] == "scalar" for p in props)
+        if scalar_only:
+            dt = np.dtype([(p[1], "<" + p[2]) for p in props])
+            if fmt == "ascii":
+                rows = np.array([tuple(float(next(tokens)) for _ in props) for _ in range(count)], dtype=np.float64).reshape(count, len(props))
+                table = {p[1]: rows[:, k] for k, p in enumerate(props)}
+            else:
+                rec = np.frombuffer(data, dtype=dt, count=count, offset=pos)
+                pos += dt.itemsize * count
+                table = {p[1]: rec[p[1]] for p in props}
+            if name == "vertex":
+                verts = np.stack([table["x"], table["y"], table["z"]], axis=1).astype(np.float32)
+                if all(k in table for k in ("nx", "ny", "nz")):
+                    normals = np.stack([table["nx"], table["ny"], table["nz"]], axis=1).astype(np.float32)
+            continue
+        if fmt != "ascii" and len(props) == 1 and name == "face" and count:     # all triangles (what write_ply writes): at once
+            dt = np.dtype([("n", "<" + props[0][3]), ("v", "<" + props[0][2], (3,))])
+            if pos + dt.itemsize * count <= len(data):
+                rec = np.frombuffer(data, dtype=dt, count=count, offset=pos)
+                if np.all(rec["n"] == 3):
+                    tris += rec["v"].tolist()
+                    pos += dt.itemsize * count
+                    continue
+        for _ in range(count):                                   # an element with lists: row by row
+            for p in props:
+                if p[0] == "scalar":
+                    if fmt == "ascii":
+                        next(tokens)
+                    else:
+                        pos += np.dtype(p[2]).itemsize
+                    continue
+                if fmt == "ascii":
+                    n = int(next(tokens))
+                    idx = [int(next(tokens)) for _ in range(n)]
+                else:
+                    n = int(np.frombuffer(data, dtype="<" + p[3], count=1, offset=pos)[0])
+                    pos += np.dtype(p[3]).itemsize
+                    idx = np.frombuffer(data, dtype="<" + p[2], count=n, offset=pos).tolist()
+                    pos += np.dtype(p[2]).itemsize * n
+                if name == "face" and p[1] in ("vertex_indices", "vertex_index"):
+                    tris += [(idx[0], idx[m], idx[m + 1]) for m in range(1, n - 1)]
+    if verts is None:
+        raise ValueError("%s has no vertex element" % path)
+    return Mesh(verts, np.array(tris, dtype=np.uint32).reshape(-1, 3), normals)
+
+
+def read_stl(path):
+    """STL, binary or ASCII: a soup -- three vertices per triangle in file order, not welded; triangles (T, 3) = 0 .. 3 T - 1."""
+    with open(path, "rb") as f:
+        data = f.read()
+    n = struct.unpack_from("<I", data, 80)[0] if len(data) >= 84 else None
+    if n is not None and len(data) == 84 + 50 * n:               # (a binary file may begin with "solid", too: the size decides)
+        rec = np.frombuffer(data, dtype=[("n", "<f4", (3,)), ("v", "<f4", (3, 3)), ("attr", "<u2")], count=n, offset=84)
+        verts = np.ascontiguousarray(rec["v"].reshape(-1, 3))
+    else:
+        text = data.decode("ascii", errors="replace").split()
+        if not text or text[0] != "solid":
+            raise ValueError("%s is neither a binary nor an ASCII STL file" % path)
+        coords = [float(text[k + 1 + m]) for k, w in enumerate(text) if w == "vertex" for m in range(3)]
+        verts = np.array(coords, dtype=np.float32).reshape(-1, 3)
+        if len(verts) % 3:
+            raise ValueError("%s: %d vertices are not whole triangles" % (path, len(verts)))
+    return Mesh(verts, np.arange(len(verts), dtype=np.uint32).reshape(-1, 3))
+
+
+def read(path):
+    """read_obj / read_ply / read_stl by the extension of `path`: what write() writes, and the ASCII forms of PLY and STL."""
+    ext = path.lower().rsplit(".", 1)[-1]
+    if ext == "obj":
+        return read_obj(path)
+    if ext == "ply":
+        return read_ply(path)
+    if ext == "stl":
+        return read_stl(path)
+    raise ValueError("unknown mesh format .%s (obj, ply or stl)" % ext)
 
 
 # The albedo table the CLI uploads to its context before extracting, so a PLY's colours are those the context's draws show.

@@ -705,6 +705,90 @@ class RayMarchingResources:
         measures() the step of the lattice the classes came from."""
         return self._occupancy_call(self._L.rm_surface_classes, *_SURF_OUTPUTS, classes, None, Surface)
 
+    # -- mesh voxelisation (rm_voxelize_mesh / rm_read_voxels) ------------------------------------------------------------------------
+    def _mesh_arg(self, vertices, triangles):
+        """A mesh as the library takes it: n_vertices, the address of xyz, n_triangles, the address of the indices (None: a soup),
+        is_device, the stream, and the objects to keep alive during the call."""
+        if hasattr(vertices, "vertices") and hasattr(vertices, "triangles"):      # a mesh.Mesh
+            if triangles is not None:
+                raise ValueError("a Mesh brings its own triangles")
+            vertices, triangles = vertices.vertices, vertices.triangles
+        if type(vertices).__module__.split(".")[0] == "torch":
+            import torch
+            v = vertices
+            if v.device.type != "cuda" or v.device.index != self.device:
+                raise ValueError("vertices are on %s; this context is on cuda:%d" % (v.device, self.device))
+            if v.dtype != torch.float32 or v.dim() != 2 or v.shape[1] != 3 or not v.is_contiguous():
+                raise ValueError("vertices must be a contiguous float32 tensor of shape (n, 3)")
+            t = triangles
+            if t is not None:
+                if type(t).__module__.split(".")[0] != "torch" or t.device != v.device:
+                    raise ValueError("triangles must be a tensor on the vertices' device")
+                if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+                    raise ValueError("triangles must be a contiguous int32 tensor of shape (n, 3) (the u32 indices' words)")
+            nv, nt = int(v.shape[0]), int(t.shape[0]) if t is not None else int(v.shape[0]) // 3
+            return (nv, C.c_void_p(v.data_ptr() if nv else None), nt, C.c_void_p(t.data_ptr()) if t is not None and nt else None, 1,
+                    C.c_void_p(self._torch_stream(v)), (v, t))
+        v = np.ascontiguousarray(np.asarray(vertices, dtype=np.float32))
+        if v.ndim != 2 or v.shape[1] != 3:
+            raise ValueError("vertices must be an array of shape (n, 3), not %s" % (v.shape,))
+        t = None
+        if triangles is not None:
+            t = np.asarray(triangles)
+            if t.dtype.kind not in "iu" or t.ndim != 2 or t.shape[1] != 3:
+                raise ValueError("triangles must be an integer array of shape (n, 3)")
+            if t.size and (int(t.min()) < 0 or int(t.max()) > 0xFFFFFFFF):
+                raise ValueError("a vertex index must fit 32 unsigned bits")
+            t = np.ascontiguousarray(t.astype(np.uint32))
+        nv, nt = len(v), len(t) if t is not None else len(v) // 3
+        return (nv, C.c_void_p(v.ctypes.data if nv else None), nt, C.c_void_p(t.ctypes.data) if t is not None and nt else None, 0, None,
+                (v, t))
+
+    def voxelize_mesh(self, vertices, triangles=None, origin=(0.0, 0.0, 0.0), step=(1.0, 1.0, 1.0), shape=(64, 64, 64)):
+        """rm_voxelize_mesh: the occupancy of a triangle mesh on an exact lattice (origin, step, shape as sample_grid takes them;
+        2..1024 points per axis, at most 2^28 in all), by the even-odd rule along +x: a Voxels.  vertices (n, 3) float32 and
+        triangles (m, 3) vertex indices -- None: a soup, every three vertices a triangle -- as numpy arrays, or as contiguous torch
+        tensors on this context's GPU (indices int32, as extract_mesh(device=True) gives them), read after the work queued on
+        torch.cuda.current_stream(); or a mesh.Mesh of either kind in place of both.  Needs no scene."""
+        nv, xyz, nt, idx, is_device, stream, keep = self._mesh_arg(vertices, triangles)
+        o, s, (nx, ny, nz), fp = self._lattice(origin, step, shape, 2)
+        counts, stats = (C.c_uint64 * _ffi.RM_VOX_COUNTS)(), (C.c_uint64 * _ffi.RM_VOX_STATS)()
+        fn = self._L.rm_voxelize_mesh
+        self._check(fn(self._h, nv, xyz, nt, idx, is_device, stream, fp(o), fp(s), nx, ny, nz, counts, _ffi.RM_VOX_COUNTS, stats,
+                       _ffi.RM_VOX_STATS))
+        self._advance(fn, "voxels")
+        del keep
+        return Voxels(self, _named(counts, _ffi.VOX_COUNT_NAMES), _named(stats, _ffi.VOX_STAT_NAMES), o, s, (nx, ny, nz))
+
+    def voxelize_mesh_box(self, vertices, triangles=None, resolution=128, margin=2):
+        """voxelize_mesh on a lattice chosen from the mesh's bounding box (over its finite coordinates): one step for all three
+        axes, `resolution` points along the longest one, on the others as many as the box needs, with `margin` empty points all
+        round -- the analyses treat what lies beyond the lattice as outside, and the distance transform measures to the border
+        only where there is one."""
+        resolution, margin = int(resolution), int(margin)
+        if margin < 0 or resolution - 2 * margin < 2:
+            raise ValueError("resolution %d leaves no two points between margins of %d" % (resolution, margin))
+        v = vertices.vertices if hasattr(vertices, "vertices") else vertices
+        if type(v).__module__.split(".")[0] == "torch":
+            import torch
+            finite = torch.where(torch.isfinite(v), v, torch.full_like(v, float("nan")))
+            lo = torch.nan_to_num(finite, nan=float("inf")).amin(dim=0).cpu().numpy().astype(np.float64)
+            hi = torch.nan_to_num(finite, nan=float("-inf")).amax(dim=0).cpu().numpy().astype(np.float64)
+        else:
+            a = np.asarray(v, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+            a = np.where(np.isfinite(a), a, np.nan)
+            with np.errstate(all="ignore"):
+                lo, hi = np.nanmin(a, axis=0), np.nanmax(a, axis=0)
+        if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.max(hi - lo) > 0):
+            raise ValueError("the mesh has no finite extent")
+        step = float(np.max(hi - lo)) / (resolution - 1 - 2 * margin)
+        shape = [min(resolution, max(2, int(np.ceil((hi[a] - lo[a]) / step)) + 1 + 2 * margin)) for a in range(3)]
+        return self.voxelize_mesh(vertices, triangles, lo - margin * step, (step, step, step), shape)
+
+    def read_voxels_device(self, occupancy_ptr, stream=None):
+        """rm_read_voxels of the last voxelisation into device memory (an integer address), asynchronous."""
+        self._read_into(self._L.rm_read_voxels, (occupancy_ptr,), True, stream)
+
     # -- retained results (rm_read_*) ------------------------------------------------------------------------------------------
     # rm_read_* copies the size of the CONTEXT's last result, whatever the caller allocated.  So every read goes through _read_into,
     # and the result objects that read on demand (_Retained) are held to a serial per family: _advance moves it on when a producing
@@ -873,7 +957,7 @@ class RayMarchingCallback:
 
 # The outputs of the lattice analyses (RayMarchingResources._solid_grid_call): the families of retained results a call replaces
 # (a new distance volume has no mask), how many counts and statistics, and their names.
-_FAMILIES = ("topology", "distance", "distance_mask", "support", "islands")
+_FAMILIES = ("topology", "distance", "distance_mask", "support", "islands", "voxels")
 _TOPO_OUTPUTS = (("topology",), _ffi.RM_TOPO_COUNTS, _ffi.RM_TOPO_STATS, _ffi.TOPO_COUNT_NAMES, _ffi.TOPO_STAT_NAMES)
 _DIST_OUTPUTS = (("distance", "distance_mask"), _ffi.RM_DIST_COUNTS, _ffi.RM_DIST_STATS, _ffi.DIST_COUNT_NAMES, _ffi.DIST_STAT_NAMES)
 _SUP_OUTPUTS = (("support",), _ffi.RM_SUP_COUNTS, _ffi.RM_SUP_STATS, _ffi.SUP_COUNT_NAMES, _ffi.SUP_STAT_NAMES)
@@ -1189,6 +1273,31 @@ class Islands(_Retained):
             out.append({"region": int(r) + 1, "layer": int(row["layer"]), "points": int(row["points"]),
                         "centroid": [float(x) for x in o + idx * st], "area": float(row["points"] * st[b] * st[c])})
         return out
+
+
+class Voxels(_Retained):
+    """The result of voxelize_mesh / voxelize_mesh_box.  counts and stats: dicts (_ffi.VOX_COUNT_NAMES: triangles, rejected,
+    edge_on, crossings, inside, open_rows; _ffi.VOX_STAT_NAMES); origin, step (float32[3]) and shape of the lattice.  open_rows > 0:
+    the mesh is not closed along that many rows.  occupancy() and occupancy_device() read the context's buffer: after a later
+    voxelisation of the context they raise ValueError."""
+
+    def __init__(self, resources, counts, stats, origin, step, shape):
+        self._retain(resources, "voxels")
+        self.counts, self.stats = counts, stats
+        self.origin, self.step, self.shape = origin, step, shape
+
+    def __repr__(self):
+        return "Voxels(%d inside points, %d open rows, on %s)" % (self.counts["inside"], self.counts["open_rows"],
+                                                                  "x".join(map(str, self.shape)))
+
+    def occupancy(self):
+        """The occupancy, uint8 (nz, ny, nx) of 0 and 1: what the *_occupancy calls and surface_classes take."""
+        return self._read(self._res._L.rm_read_voxels, 0, 1, _U8)
+
+    def occupancy_device(self):
+        """occupancy() as a torch tensor on the context's GPU, filled on torch.cuda.current_stream() without a host round trip."""
+        self._check_current()
+        return self._res._read_new(self._res._L.rm_read_voxels, [(tuple(self.shape)[::-1], *_U8, True)], device=True)[0]
 
 
 def surface_directions():
