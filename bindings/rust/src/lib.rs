@@ -351,6 +351,22 @@ pub const RM_VOX_STAT_ITEMS: c_int = 4;
 pub const RM_VOX_STAT_SCRATCH_BYTES: c_int = 5;
 pub const RM_VOX_STATS: c_int = 6;
 
+// Lattice draw (rm_set_lattice / rm_draw_lattice / rm_cast_lattice).
+// enum rm_latcount: indices into the counts of a lattice; RM_LAT_COUNTS is their number
+pub const RM_LAT_POINTS: c_int = 0;
+pub const RM_LAT_BRICKS: c_int = 1;
+pub const RM_LAT_COUNTS: c_int = 2;
+// enum rm_latstat: indices into the statistics of a lattice; RM_LAT_STATS is their number
+pub const RM_LAT_STAT_BRICKS: c_int = 0;
+pub const RM_LAT_STAT_BRICKS_KEPT: c_int = 1;
+pub const RM_LAT_STAT_BRICKS_INSIDE: c_int = 2;
+pub const RM_LAT_STAT_EVALUATIONS: c_int = 3;
+pub const RM_LAT_STAT_RETAINED_BYTES: c_int = 4;
+pub const RM_LAT_STAT_SCRATCH_BYTES: c_int = 5;
+pub const RM_LAT_STATS: c_int = 6;
+/// The face word of a cast whose origin lies inside a full cube.
+pub const RM_LAT_FACE_NONE: u32 = 6;
+
 /// The index of `PAIR[a][b][nu]` in the counts of a surface call (the header's `RM_SURF_PAIR`).
 pub const fn surf_pair(a: usize, b: usize, nu: usize) -> usize {
     8 + (8 * a + b) * 13 + nu
@@ -487,6 +503,13 @@ extern "C" {
                             is_device: c_int, stream: *mut c_void, origin: *const f32, step: *const f32, nx: u32, ny: u32, nz: u32,
                             out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
     pub fn rm_read_voxels(ctx: *mut rm_ctx, out_occupancy: *mut c_void, is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_set_lattice(ctx: *mut rm_ctx, nx: u32, ny: u32, nz: u32, classes: *const c_void, is_device: c_int, stream: *mut c_void,
+                          origin: *const f32, step: *const f32, out_counts: *mut u64, n_counts: u32, out_stats: *mut u64,
+                          n_stats: u32) -> c_int;
+    pub fn rm_draw_lattice(ctx: *mut rm_ctx, w: u32, h: u32, row0: u32, rows: u32, window: *const u32, out_rgba: *mut c_void,
+                           out_is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_cast_lattice(ctx: *mut rm_ctx, n: u32, rays: *const f32, window: *const u32, out_hit: *mut f32, out_ids: *mut u32,
+                           out_rgb: *mut f32, is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_slice_contours(ctx: *mut rm_ctx, axis: u32, origin_uv: *const f32, step_uv: *const f32, nu: u32, nv: u32,
                              heights: *const f32, n_layers: u32, level: f32, flags: u32, out_counts: *mut u64,
                              n_counts: u32) -> c_int;
@@ -961,6 +984,52 @@ impl RayMarchingResources {
         })?;
         self.voxels.set(Some(nx as u64 * ny as u64 * nz as u64));
         Ok(())
+    }
+
+    /// The lattice of class bytes that `draw_lattice` and `cast_lattice` show (`rm_set_lattice`): `classes`
+    /// holds nx x ny x nz bytes in host memory, x fastest; 2..1024 points per axis, at most 2^28 in all.  Byte 0 is empty, a byte
+    /// c > 0 the cube of its point with the albedo min(c, count - 1) of the material table as it stands at the draw.  Fills
+    /// `out_counts` (at least `RM_LAT_COUNTS` entries indexed by `RM_LAT_*`: points, bricks) and `out_stats` (at least
+    /// `RM_LAT_STATS`, indexed by `RM_LAT_STAT_*`).  The lattice stays in the context until the next `set_lattice`; no other
+    /// retained result is touched.  Needs no program.
+    pub fn set_lattice(&self, classes: &[u8], origin: [f32; 3], step: [f32; 3], nx: u32, ny: u32, nz: u32, out_counts: &mut [u64],
+                       out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(classes.len() as u64 >= nx as u64 * ny as u64 * nz as u64, "set_lattice: classes is shorter than the lattice");
+        assert!(out_counts.len() >= RM_LAT_COUNTS as usize, "set_lattice: out_counts is shorter than RM_LAT_COUNTS entries");
+        assert!(out_stats.len() >= RM_LAT_STATS as usize, "set_lattice: out_stats is shorter than RM_LAT_STATS entries");
+        self.check(unsafe {
+            rm_set_lattice(self.ctx, nx, ny, nz, classes.as_ptr() as *const c_void, 0, std::ptr::null_mut(), origin.as_ptr(),
+                           step.as_ptr(), out_counts.as_mut_ptr(), RM_LAT_COUNTS as u32, out_stats.as_mut_ptr(), RM_LAT_STATS as u32)
+        })
+    }
+
+    /// The image of the retained lattice through the uniforms' camera into a host RGBA32F image (top row first; with
+    /// `RM_OPT_OUTPUT_FORMAT` at its default).  `window`: (lo_x, lo_y, lo_z, hi_x, hi_y, hi_z), the points lo <= i < hi are shown;
+    /// `None`: the whole lattice.  `RM_ERR_ARG` before any `set_lattice` and for a bad window.
+    pub fn draw_lattice(&self, width: u32, height: u32, window: Option<&[u32; 6]>, out_rgba: &mut [f32]) -> Result<(), RmError> {
+        assert!(out_rgba.len() >= (width as usize) * (height as usize) * 4);
+        let w = window.map_or(std::ptr::null(), |w| w.as_ptr());
+        self.check(unsafe {
+            rm_draw_lattice(self.ctx, width, height, 0, height, w, out_rgba.as_mut_ptr() as *mut c_void, 0, std::ptr::null_mut())
+        })
+    }
+
+    /// Casts `rays.len() / 6` rays (host memory) through the retained lattice: hit records (`out_hit`, eight per ray, as
+    /// `cast_rays`), (kind, linear point index, class byte, face) (`out_ids`, four per ray; `RM_NO_ID` unless a surface; face
+    /// `RM_LAT_FACE_NONE` for an origin inside a cube) and the colour (`out_rgb`, three per ray).  `None` skips that output.
+    pub fn cast_lattice(&self, rays: &[f32], window: Option<&[u32; 6]>, out_hit: Option<&mut [f32]>, out_ids: Option<&mut [u32]>,
+                        out_rgb: Option<&mut [f32]>) -> Result<(), RmError> {
+        assert!(rays.len() % 6 == 0, "cast_lattice: rays holds {} floats, not a multiple of 6", rays.len());
+        let n = rays.len() / 6;
+        assert!(n <= u32::MAX as usize);
+        assert!(out_hit.as_ref().map_or(true, |s| s.len() >= 8 * n), "cast_lattice: out_hit is shorter than {} rays", n);
+        assert!(out_ids.as_ref().map_or(true, |s| s.len() >= 4 * n), "cast_lattice: out_ids is shorter than {} rays", n);
+        assert!(out_rgb.as_ref().map_or(true, |s| s.len() >= 3 * n), "cast_lattice: out_rgb is shorter than {} rays", n);
+        let w = window.map_or(std::ptr::null(), |w| w.as_ptr());
+        let hit = out_hit.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let ids = out_ids.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let rgb = out_rgb.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        self.check(unsafe { rm_cast_lattice(self.ctx, n as u32, rays.as_ptr(), w, hit, ids, rgb, 0, std::ptr::null_mut()) })
     }
 
     /// The occupancy of the last successful `voxelize_mesh`: one byte per lattice point, 0 or 1, x fastest -- what

@@ -787,6 +787,47 @@ int rm_voxelize_mesh(rm_ctx* ctx, uint32_t n_vertices, const float* xyz, uint32_
                      uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats);
 int rm_read_voxels(rm_ctx* ctx, void* out_occupancy, int is_device, void* stream);
 
+/* Lattice draw (extension; DESIGN.md section 28 is the contract, to the last bit): a lattice of class bytes -- an occupancy, a
+ * mask, their sum -- as an image through the draws' camera, or along a caller's rays.  Needs no program.
+ * rm_set_lattice copies the bytes (nx x ny x nz, x fastest, one byte per point; host memory, or (is_device) device memory read
+ * after the work queued on `stream`) into a retained slot of the context and builds the traversal's bit words there.  Lattice:
+ * rm_label_solid's (2..1024 points per axis, at most 2^28 in all, RM_ERR_RANGE otherwise); origin and step as rm_sample_grid
+ * takes them.  Byte 0 is empty; a byte c > 0 is the cube [i - 1/2, i + 1/2]^3 of its point in index space, of albedo
+ * table[min(c, count - 1)] of the material table (rm_set_materials) as it stands at the draw or cast.
+ * out_counts[RM_LAT_*]: POINTS (bytes != 0), BRICKS (the bricks of 8 x 8 x 8 points that hold one).  out_stats[RM_LAT_STAT_*]:
+ * the four brick statistics are 0, as for a caller's occupancy; RETAINED_BYTES, the device memory the slot keeps; SCRATCH_BYTES,
+ * the scratch memory the call used (0: the bytes are copied into the slot).  The call is synchronous on the context's own
+ * stream, ordered after its earlier work.  The lattice stays until the next rm_set_lattice; no other retained result is dropped
+ * or replaced, and no other call replaces this one.
+ * Errors, every check before the first launch, outputs untouched and the previous lattice still drawable: RM_ERR_NULL for a NULL
+ * ctx, classes, out_counts or out_stats (and origin or step); RM_ERR_ARG for n_counts < RM_LAT_COUNTS, then n_stats <
+ * RM_LAT_STATS, then an origin or a step that is not finite or a step <= 0; RM_ERR_RANGE for the lattice.  RM_ERR_DEVICE when
+ * device memory runs out (no lattice is retained then).
+ *
+ * rm_cast_lattice: n rays (n x 6 floats: origin, direction, used as given) through the retained lattice.  window: six u32
+ * (lo_x, lo_y, lo_z, hi_x, hi_y, hi_z), host memory, lo_a < hi_a <= n_a, points outside it are empty and the ray is clipped to
+ * its box; NULL: the whole lattice.  out_hit (n x 8 floats: t, position, normal, diffuse) and out_rgb (n x 3) as rm_cast_rays
+ * gives them -- a miss is exactly rm_cast_rays' miss: the floor, or nothing --; out_ids (n x 4 u32): kind (RM_HIT_*), linear
+ * point index i + nx (j + ny k), class byte, face (2 axis + (normal positive ? 1 : 0), or RM_LAT_FACE_NONE for an origin inside a
+ * cube), RM_NO_ID unless a surface was hit.  There is no step limit and the march limits are not used: a ray takes at most
+ * nx + ny + nz events.  NULL outputs, alignment, n == 0, is_device and stream as for rm_cast_rays.
+ * rm_draw_lattice: the image of the retained lattice through the uniforms' camera -- per pixel the sixteen AA sample rays
+ * of rm_draw, each cast as above, resolved as rm_draw resolves them, written in RM_OPT_OUTPUT_FORMAT.  Rows, destination,
+ * stream (RM_STREAM_OWN included) and ordering as for rm_draw; like a query it leaves the draw state alone.
+ * Errors of both: RM_ERR_NULL for NULL outputs; RM_ERR_ARG before any rm_set_lattice, for a bad window and for device arrays off
+ * their alignment; rm_draw_lattice: RM_ERR_RANGE for an image or a row band outside rm_draw's ranges. */
+enum rm_latcount { RM_LAT_POINTS = 0, RM_LAT_BRICKS = 1, RM_LAT_COUNTS = 2 };
+enum rm_latstat { RM_LAT_STAT_BRICKS = 0, RM_LAT_STAT_BRICKS_KEPT = 1, RM_LAT_STAT_BRICKS_INSIDE = 2, RM_LAT_STAT_EVALUATIONS = 3,
+                  RM_LAT_STAT_RETAINED_BYTES = 4, RM_LAT_STAT_SCRATCH_BYTES = 5, RM_LAT_STATS = 6 };
+#define RM_LAT_FACE_NONE 6u
+int rm_set_lattice(rm_ctx* ctx, uint32_t nx, uint32_t ny, uint32_t nz, const void* classes, int is_device, void* stream,
+                   const float* origin, const float* step, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
+                   uint32_t n_stats);
+int rm_draw_lattice(rm_ctx* ctx, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const uint32_t* window, void* out_rgba,
+                    int out_is_device, void* stream);
+int rm_cast_lattice(rm_ctx* ctx, uint32_t n, const float* rays, const uint32_t* window, float* out_hit, uint32_t* out_ids,
+                    float* out_rgb, int is_device, void* stream);
+
 /* Slicing (extension; DESIGN.md section 16 is the contract, to the last bit): the closed outlines of the solid d < level in a
  * stack of planes, as ordered polylines -- what a slicer or a section drawing needs, evaluated directly on a 2-D lattice
  * per layer instead of through a triangle mesh.  From the program, limits and material table as they are at the call.

@@ -118,6 +118,13 @@ VOX_COUNT_NAMES = ("triangles", "rejected", "edge_on", "crossings", "inside", "o
 (RM_VOX_STAT_BRICKS, RM_VOX_STAT_BRICKS_KEPT, RM_VOX_STAT_BRICKS_INSIDE, RM_VOX_STAT_EVALUATIONS, RM_VOX_STAT_ITEMS,
  RM_VOX_STAT_SCRATCH_BYTES, RM_VOX_STATS) = range(7)
 VOX_STAT_NAMES = ("bricks", "bricks_kept", "bricks_inside", "evaluations", "items", "scratch_bytes")
+# lattice draw (rm_set_lattice / rm_draw_lattice / rm_cast_lattice): enum rm_latcount, enum rm_latstat, RM_LAT_FACE_NONE
+(RM_LAT_POINTS, RM_LAT_BRICKS, RM_LAT_COUNTS) = range(3)
+LAT_COUNT_NAMES = ("points", "bricks")
+(RM_LAT_STAT_BRICKS, RM_LAT_STAT_BRICKS_KEPT, RM_LAT_STAT_BRICKS_INSIDE, RM_LAT_STAT_EVALUATIONS, RM_LAT_STAT_RETAINED_BYTES,
+ RM_LAT_STAT_SCRATCH_BYTES, RM_LAT_STATS) = range(7)
+LAT_STAT_NAMES = ("bricks", "bricks_kept", "bricks_inside", "evaluations", "retained_bytes", "scratch_bytes")
+RM_LAT_FACE_NONE = 6
 
 
 def RM_SURF_PAIR(a, b, nu):
@@ -295,6 +302,12 @@ def hip_lib():
         L.rm_voxelize_mesh.restype = C.c_int
         L.rm_read_voxels.argtypes = [vp, vp, C.c_int, vp]
         L.rm_read_voxels.restype = C.c_int
+        L.rm_set_lattice.argtypes = [vp, u32, u32, u32, vp, C.c_int, vp, f3, f3, C.POINTER(u64), u32, C.POINTER(u64), u32]
+        L.rm_set_lattice.restype = C.c_int
+        L.rm_draw_lattice.argtypes = [vp, u32, u32, u32, u32, vp, vp, C.c_int, vp]
+        L.rm_draw_lattice.restype = C.c_int
+        L.rm_cast_lattice.argtypes = [vp, u32, vp, vp, vp, vp, vp, C.c_int, vp]
+        L.rm_cast_lattice.restype = C.c_int
         L.rm_slice_contours.argtypes = [vp, u32, f3, f3, u32, u32, f3, u32, C.c_float, u32, C.POINTER(u64), u32]
         L.rm_slice_contours.restype = C.c_int
         L.rm_read_slices.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]

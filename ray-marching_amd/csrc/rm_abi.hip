@@ -37,6 +37,7 @@
 #include "rm_islands.h"
 #include "rm_surface.h"
 #include "rm_voxel.h"
+#include "rm_lattice.h"
 #include "rm_slice.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
@@ -222,6 +223,17 @@ struct rm_ctx {
         void drop() { valid = false; }
         void commit(uint32_t nx_, uint32_t ny_, uint32_t nz_) { nx = nx_, ny = ny_, nz = nz_, valid = true; }
     } vox;
+    struct Lattice {  // rm_set_lattice: the classes of nx x ny x nz points and the traversal's bit words (rml::LatticeSlot)
+        DevBuf<char> buf;
+        bool valid = false;
+        uint32_t nx = 0, ny = 0, nz = 0;
+        float origin[3] = {0.0f, 0.0f, 0.0f}, step[3] = {1.0f, 1.0f, 1.0f};
+        void drop() { valid = false; }
+        void commit(uint32_t nx_, uint32_t ny_, uint32_t nz_, const float* o, const float* st) {
+            nx = nx_, ny = ny_, nz = nz_, valid = true;
+            for (int a = 0; a < 3; a++) origin[a] = o[a], step[a] = st[a];
+        }
+    } lat;
     // scratch for host-destination draws and batch uniforms
     DevBuf<char> d_out;
     DevBuf<rm_uniforms> d_frames;
@@ -340,11 +352,16 @@ int ensure_program(rm_ctx* c, hipStream_t s) {
 }
 
 // The material table of a tagged program, on the stream of the draw that needs it.
+int upload_materials(rm_ctx* c, hipStream_t s);
 int ensure_materials(rm_ctx* c, hipStream_t s) {
     if (!c->decoded.has_materials) return RM_OK;
     if (c->decoded.max_material >= c->materials.size())
         return fail(c, RM_ERR_MATERIAL, "the program tags a surface with material %u, the material table has %zu entries "
                     "(rm_set_materials)", c->decoded.max_material, c->materials.size());
+    return upload_materials(c, s);
+}
+// The device copy of the material table as it stands (the lattice draw reads it whatever the program tags).
+int upload_materials(rm_ctx* c, hipStream_t s) {
     if (int rc = c->d_materials.reserve(c, RM_MAX_MATERIALS, "materials")) return rc;
     if (c->materials_dirty) {
         if (int rc = upload(c, c->d_materials.p, c->materials.data(), c->materials.size() * sizeof(float4), s)) return rc;
@@ -2970,6 +2987,135 @@ RM_EXPORT int rm_read_voxels(rm_ctx* c, void* out_occupancy, int is_device, void
     const rm_ctx::Voxels& r = c->vox;
     if (!r.valid) return fail(c, RM_ERR_ARG, "rm_read_voxels: no mesh has been voxelised");
     return read_back(c, is_device, stream, "rm_read_voxels: out_occupancy needs no alignment", {{out_occupancy, r.buf.p, r.points(), 1}});
+}
+
+// ---- lattice draw (rm_lattice.h) ----
+namespace {
+
+static_assert((uint32_t)rmk::LAT_N_COUNTERS == 2u && RM_LAT_FACE_NONE == rmk::kLatFaceNone, "LatticeSlot holds the kernel's two counters");
+static_assert(RM_LAT_STAT_BRICKS == kStatBricks && RM_LAT_STAT_BRICKS_KEPT == kStatBricksKept && RM_LAT_STAT_BRICKS_INSIDE == kStatBricksInside &&
+                  RM_LAT_STAT_EVALUATIONS == kStatEvaluations && RM_LAT_STAT_SCRATCH_BYTES == RM_LAT_STATS - 1,
+              "the brick statistics first (zeros, as for a caller's occupancy) and the scratch size last");
+
+// The retained lattice and a call's window (six u32 in host memory, or NULL: the whole lattice) as the kernels take them, with
+// the material table uploaded on stream s.  RM_ERR_ARG before any rm_set_lattice and for a bad window.
+int lattice_grid(rm_ctx* c, const char* fn, const uint32_t* window, hipStream_t s, rmk::LatGrid* G) {
+    const rm_ctx::Lattice& r = c->lat;
+    if (!r.valid) return fail(c, RM_ERR_ARG, "%s: no lattice has been set (rm_set_lattice)", fn);
+    const uint32_t n[3] = {r.nx, r.ny, r.nz};
+    uint32_t lo[3] = {0u, 0u, 0u}, hi[3] = {r.nx, r.ny, r.nz};
+    for (int a = 0; window && a < 3; a++) {
+        lo[a] = window[a], hi[a] = window[3 + a];
+        if (!(lo[a] < hi[a] && hi[a] <= n[a]))
+            return fail(c, RM_ERR_ARG, "%s: window [%u, %u) on axis %d of %u points: lo < hi <= n", fn, lo[a], hi[a], a, n[a]);
+    }
+    if (int rc = upload_materials(c, s)) return rc;
+    const rml::LatticeSlot S(r.nx, r.ny, r.nz);
+    const char* base = r.buf.p;
+    *G = rmk::LatGrid{r.origin[0], r.origin[1], r.origin[2], r.step[0], r.step[1], r.step[2], r.nx, r.ny, r.nz, rml::lat_row_words(r.nx),
+                      rml::lat_bricks(r.nx), rml::lat_bricks(r.ny), lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], S.classes.at(base), S.bits.at(base),
+                      S.bricks.at(base), reinterpret_cast<const float*>(c->d_materials.p), (uint32_t)c->materials.size()};
+    return RM_OK;
+}
+
+}  // namespace
+
+RM_EXPORT int rm_set_lattice(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz, const void* classes, int is_device, void* stream,
+                             const float* origin, const float* step, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats,
+                             uint32_t n_stats) {
+    const char* fn = "rm_set_lattice";
+    if (!c) return RM_ERR_NULL;
+    if (!classes || !out_counts || !out_stats) return fail(c, RM_ERR_NULL, "%s: classes, out_counts or out_stats is NULL", fn);
+    if (n_counts < (uint32_t)RM_LAT_COUNTS) return fail(c, RM_ERR_ARG, "%s: n_counts %u < RM_LAT_COUNTS", fn, n_counts);
+    if (n_stats < (uint32_t)RM_LAT_STATS) return fail(c, RM_ERR_ARG, "%s: n_stats %u < RM_LAT_STATS", fn, n_stats);
+    if (int rc = check_lattice(c, fn, origin, step)) return rc;
+    if (int rc = check_topo_lattice(c, fn, nx, ny, nz)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    order_with_previous(c, s);  // after a draw or a cast of the last lattice on another stream, too
+    const rml::LatticeSlot S(nx, ny, nz);
+    // the last check that can refuse is past: the previous lattice goes
+    c->lat.drop();
+    if (int rc = c->lat.buf.reserve(c, S.bytes, "lattice")) return rc;
+    char* base = c->lat.buf.p;
+    if (is_device) {
+        // the caller's array is ready when the work queued on its stream is done; the call is synchronous anyway
+        const hipStream_t su = user_stream(c, stream);
+        if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
+    }
+    HIP_TRY(c, hipMemcpyAsync(S.classes.at(base), classes, S.classes.bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(base + S.clear_offset(), 0, S.clear_bytes(), s));
+    const uint32_t row_words = rml::lat_row_words(nx), n_words = ny * nz * row_words;  // (<= 2^27: rows of two points)
+    hipLaunchKernelGGL(rmk::rm_lat_pack_kernel, dim3((n_words + 255u) / 256u), dim3(256), 0, s, nx, ny, row_words, n_words, rml::lat_bricks(nx),
+                       rml::lat_bricks(ny), static_cast<const uint8_t*>(S.classes.at(base)), S.bits.at(base), S.bricks.at(base), S.counters.at(base));
+#if !RM_LAT_SKIP
+    HIP_TRY(c, hipMemsetAsync(S.bricks.at(base), 0xFF, S.bricks.bytes, s));  // the probe's A/B library: no brick is ever jumped
+#endif
+    HIP_TRY(c, hipGetLastError());
+    unsigned long long cnt[rmk::LAT_N_COUNTERS];
+    HIP_TRY(c, hipMemcpyAsync(cnt, S.counters.at(base), sizeof cnt, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    out_counts[RM_LAT_POINTS] = cnt[rmk::LAT_N_POINTS];
+    out_counts[RM_LAT_BRICKS] = cnt[rmk::LAT_N_BRICKS];
+    for (uint32_t k = 0; k < (uint32_t)RM_LAT_STATS; k++) out_stats[k] = 0u;
+    out_stats[RM_LAT_STAT_RETAINED_BYTES] = S.bytes;
+    c->lat.commit(nx, ny, nz, origin, step);
+    return RM_OK;
+}
+
+RM_EXPORT int rm_draw_lattice(rm_ctx* c, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const uint32_t* window, void* out_rgba,
+                              int out_is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_rgba) return fail(c, RM_ERR_NULL, "rm_draw_lattice: out_rgba is NULL");
+    int rc = check_dims(c, W, H, row0, rows);
+    if (rc != RM_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = dest_stream(c, out_is_device, stream);
+    rmk::LatGrid G;
+    if (!c->lat.valid) return lattice_grid(c, "rm_draw_lattice", window, s, &G);  // (refused before the stream is touched)
+    order_with_previous(c, s);
+    if ((rc = lattice_grid(c, "rm_draw_lattice", window, s, &G)) != RM_OK) return rc;
+    // host memory: staged through the context's query buffer (never the draws' scratch), synchronously on its own stream
+    Outputs o(c, out_is_device, c->d_qout);
+    o.add(out_rgba, (size_t)rows * W * pixel_bytes(c));
+    if ((rc = o.reserve()) != RM_OK) return rc;
+    rmk::LatFrame F;
+    F.u = c->uniforms;
+    F.W = W; F.H = H; F.row0 = row0; F.rows = rows;
+    F.format = c->out_format;
+    F.out = o.dev<char>(0);
+    // one wave per 2 x 2 block of pixels
+    const size_t lanes = (size_t)((W + 1u) / 2u) * ((rows + 1u) / 2u) * 64u;
+    hipLaunchKernelGGL(rmk::rm_draw_lattice_kernel, dim3(query_blocks(lanes)), dim3(256), 0, s, G, F);
+    HIP_TRY(c, hipGetLastError());
+    return o.finish(s);
+}
+
+RM_EXPORT int rm_cast_lattice(rm_ctx* c, uint32_t n, const float* rays, const uint32_t* window, float* out_hit, uint32_t* out_ids,
+                              float* out_rgb, int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    if (!out_hit && !out_ids && !out_rgb) return fail(c, RM_ERR_NULL, "rm_cast_lattice: every output is NULL");
+    if (n == 0u) return RM_OK;
+    if (!rays) return fail(c, RM_ERR_NULL, "rm_cast_lattice: rays is NULL");
+    if (is_device && (misaligned(rays, 4) || misaligned(out_hit, 16) || misaligned(out_ids, 16) || misaligned(out_rgb, 4)))
+        return fail(c, RM_ERR_ARG, "rm_cast_lattice: device arrays need 4-byte alignment (out_hit, out_ids: 16-byte)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = dest_stream(c, is_device, stream);
+    rmk::LatGrid G;
+    if (!c->lat.valid) return lattice_grid(c, "rm_cast_lattice", window, s, &G);
+    order_with_previous(c, s);
+    int rc = lattice_grid(c, "rm_cast_lattice", window, s, &G);
+    if (rc != RM_OK) return rc;
+    Outputs o(c, is_device, c->d_qout);
+    o.add(out_hit, (size_t)n * 32u);
+    o.add(out_ids, (size_t)n * 16u);
+    o.add(out_rgb, (size_t)n * 12u);
+    const float* d_rays = nullptr;
+    if ((rc = query_input(c, o, rays, (size_t)n * 24u, s, &d_rays)) != RM_OK) return rc;
+    hipLaunchKernelGGL(rmk::rm_cast_lattice_kernel, dim3(query_blocks(n)), dim3(256), 0, s, G, n, d_rays, o.dev<float>(0), o.dev<uint32_t>(1),
+                       o.dev<float>(2));
+    HIP_TRY(c, hipGetLastError());
+    return o.finish(s);
 }
 
 RM_EXPORT int rm_read_mesh(rm_ctx* c, float* out_vertices, uint32_t* out_triangles, float* out_normals, uint32_t* out_ids,

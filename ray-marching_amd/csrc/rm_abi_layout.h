@@ -158,6 +158,28 @@ struct VoxScratch {
     size_t clear_bytes() const { return bits.offset + bits.bytes - counters.offset; }
 };
 
+// rm_set_lattice, the retained slot of a lattice of nx x ny x nz points: per point its class (1 B); per row (j, k) the bits
+// `byte != 0` of its points in lat_row_words(nx) u32 words, point i in bit i & 31 of word i >> 5; per brick of 8 x 8 x 8 points
+// (lat_bricks(n) along an axis, x fastest) one bit, brick b in bit b & 31 of word b >> 5; the two counters (POINTS, BRICKS)
+// directly behind the brick words, so that one memset clears both.  The call has no scratch: a caller's bytes are copied into
+// `classes` directly.
+constexpr uint32_t lat_row_words(uint32_t nx) { return (nx + 31u) >> 5; }
+constexpr uint32_t lat_bricks(uint32_t n) { return (n + 7u) >> 3; }
+struct LatticeSlot {
+    Carver a;
+    Region<uint8_t> classes;
+    Region<uint32_t> bits, bricks;
+    Region<unsigned long long> counters;
+    size_t bytes;
+    LatticeSlot(uint32_t nx, uint32_t ny, uint32_t nz)
+        : classes(a.take<uint8_t>((size_t)nx * ny * nz)), bits(a.take<uint32_t>((size_t)ny * nz * lat_row_words(nx))),
+          bricks(a.take<uint32_t>(((size_t)lat_bricks(nx) * lat_bricks(ny) * lat_bricks(nz) + 31u) >> 5)),
+          counters(a.take<unsigned long long>(2)), bytes(a.total) {}
+    // bricks and counters as one span
+    size_t clear_offset() const { return bricks.offset; }
+    size_t clear_bytes() const { return counters.offset + counters.bytes - bricks.offset; }
+};
+
 // rm_distance_solid / rm_distance_occupancy, for a lattice of n points in nb bricks: per point its occupancy (1 B); per brick its
 // class (1 B); per 256 bricks the probe's block sum; per 2048 points one row of 16 words (the maxima and the count), per 256 of
 // those rows one folded row; totals, the evaluation count and the reduced row.  The distance volume itself (4 B per point) and

@@ -20,6 +20,8 @@ import json
 import re
 import sys
 
+from . import lattice_image
+
 from .massprops import load_program
 from .mesh import _three
 
@@ -78,6 +80,7 @@ def main(argv=None):
     ap.add_argument("--rows", action="store_true", help="put the region table and every region's root into the report")
     ap.add_argument("--profile", action="store_true", help="put the per-layer table into the report")
     ap.add_argument("--fail-on", default="", help='e.g. "islands>0,island_points>0,layer_regions>40": exit status 2 when one of them holds')
+    lattice_image.add_options(ap)
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     gates = parse_gates(a.fail_on)
@@ -110,6 +113,9 @@ def main(argv=None):
             np.save(a.mask, isl.mask())
         if a.labels:
             np.save(a.labels, isl.labels())
+        if a.image:
+            cls = lattice_image.device_bytes(res, isl.shape, lambda p, st: res.read_islands_device(mask_ptr=p, stream=st))
+            report["image"] = lattice_image.write(res, cls, isl.origin, isl.step, a.image, a.size, a.cut)
     finally:
         res.close()
     failed = failed_gates(gates, gate_values(report))

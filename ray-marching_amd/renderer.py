@@ -789,6 +789,81 @@ class RayMarchingResources:
         """rm_read_voxels of the last voxelisation into device memory (an integer address), asynchronous."""
         self._read_into(self._L.rm_read_voxels, (occupancy_ptr,), True, stream)
 
+    # -- lattice draw (rm_set_lattice / rm_draw_lattice / rm_cast_lattice) -------------------------------------------------------------
+    def set_lattice(self, classes, origin=(0.0, 0.0, 0.0), step=(1.0, 1.0, 1.0)):
+        """rm_set_lattice: the lattice of class bytes that draw_lattice and cast_lattice show -- an occupancy, a mask, their sum --
+        as a 3-D array of a one-byte type indexed [k, j, i], or a contiguous torch tensor on this context's GPU (read after the
+        work queued on torch.cuda.current_stream(), copied without a host round trip).  Point (i, j, k) is the cube of one step
+        around origin + (i, j, k) * step; byte 0 is empty, a byte c > 0 takes the albedo min(c, count - 1) of the material table
+        (set_materials) as it stands when it is drawn.  Needs no scene.  Returns a Lattice (counts, stats)."""
+        nx, ny, nz, ptr, is_device, stream, keep = self._occupancy_arg(classes)
+        o, s, _, fp = self._lattice(origin, step, (nx, ny, nz), 2)
+        counts, stats = (C.c_uint64 * _ffi.RM_LAT_COUNTS)(), (C.c_uint64 * _ffi.RM_LAT_STATS)()
+        fn = self._L.rm_set_lattice
+        self._check(fn(self._h, nx, ny, nz, ptr, is_device, stream, fp(o), fp(s), counts, _ffi.RM_LAT_COUNTS, stats, _ffi.RM_LAT_STATS))
+        self._advance(fn, "lattice")
+        del keep
+        return Lattice(self, _named(counts, _ffi.LAT_COUNT_NAMES), _named(stats, _ffi.LAT_STAT_NAMES), o, s, (nx, ny, nz))
+
+    @staticmethod
+    def _window(window):
+        """A cut-away window (lo_x, lo_y, lo_z, hi_x, hi_y, hi_z) -- points lo <= i < hi are shown -- as the library takes it; None:
+        the whole lattice."""
+        if window is None:
+            return None, None
+        w = np.array(window, dtype=np.int64).reshape(-1)
+        if w.shape != (6,) or w.min() < 0 or w.max() > 0xFFFFFFFF:
+            raise ValueError("a window is (lo_x, lo_y, lo_z, hi_x, hi_y, hi_z), six unsigned integers")
+        w = w.astype(np.uint32)
+        return w.ctypes.data_as(C.c_void_p), w
+
+    def draw_lattice(self, W, H, row0=0, rows=None, window=None):
+        """rm_draw_lattice: rows [row0, row0 + rows) of the image of the retained lattice (set_lattice) through the uniforms'
+        camera, a new host array (rows, W, 4): float32, or uint8 for the 8-bit formats.  window: see _window."""
+        rows = H - row0 if rows is None else rows
+        out = np.empty((max(rows, 0), W, 4), dtype=self._dtype)
+        wp, keep = self._window(window)
+        self._check(self._L.rm_draw_lattice(self._h, W, H, row0, rows, wp, out.ctypes.data_as(C.c_void_p), 0, None))
+        del keep
+        return out
+
+    def draw_lattice_device(self, W, H, out_ptr, row0=0, rows=None, window=None, stream=None):
+        """rm_draw_lattice into device memory (out_ptr: integer device address), asynchronous on `stream`."""
+        rows = H - row0 if rows is None else rows
+        wp, keep = self._window(window)
+        self._check(self._L.rm_draw_lattice(self._h, W, H, row0, rows, wp, C.c_void_p(out_ptr), 1, C.c_void_p(stream) if stream else None))
+        del keep
+
+    def cast_lattice(self, origins, directions=None, window=None):
+        """rm_cast_lattice: rays (as cast_rays takes them) through the retained lattice.  Returns a dict: kind (RM_HIT_*), index
+        (the linear point index i + nx (j + ny k)), cls (the class byte), face (2 axis + (normal positive), RM_LAT_FACE_NONE for
+        an origin inside a cube) -- RM_NO_ID unless a surface --, t, position (n, 3), normal (n, 3), diffuse, rgb (n, 3)."""
+        kind, r, n = self._rays_input(origins, directions)
+        if kind == "torch":
+            import torch
+            hit = torch.empty((n, 8), dtype=torch.float32, device=r.device)
+            ids = torch.empty((n, 4), dtype=torch.int32, device=r.device)
+            rgb = torch.empty((n, 3), dtype=torch.float32, device=r.device)
+            self.cast_lattice_device(n, r.data_ptr(), hit.data_ptr(), ids.data_ptr(), rgb.data_ptr(), window=window,
+                                     stream=self._torch_stream(r))
+        else:
+            hit = np.empty((n, 8), dtype=np.float32)
+            ids = np.empty((n, 4), dtype=np.uint32)
+            rgb = np.empty((n, 3), dtype=np.float32)
+            wp, keep = self._window(window)
+            self._check(self._L.rm_cast_lattice(self._h, n, r.ctypes.data, wp, hit.ctypes.data, ids.ctypes.data, rgb.ctypes.data, 0, None))
+            del keep
+        return {"kind": ids[:, 0], "index": ids[:, 1], "cls": ids[:, 2], "face": ids[:, 3], "t": hit[:, 0],
+                "position": hit[:, 1:4], "normal": hit[:, 4:7], "diffuse": hit[:, 7], "rgb": rgb}
+
+    def cast_lattice_device(self, n, rays_ptr, hit_ptr=0, ids_ptr=0, rgb_ptr=0, window=None, stream=None):
+        """rm_cast_lattice on device memory (integer addresses; 0 = not wanted), asynchronous on `stream`."""
+        wp, keep = self._window(window)
+        self._check(self._L.rm_cast_lattice(self._h, int(n), C.c_void_p(rays_ptr), wp, C.c_void_p(hit_ptr or None),
+                                            C.c_void_p(ids_ptr or None), C.c_void_p(rgb_ptr or None), 1,
+                                            C.c_void_p(stream) if stream else None))
+        del keep
+
     # -- retained results (rm_read_*) ------------------------------------------------------------------------------------------
     # rm_read_* copies the size of the CONTEXT's last result, whatever the caller allocated.  So every read goes through _read_into,
     # and the result objects that read on demand (_Retained) are held to a serial per family: _advance moves it on when a producing
@@ -957,7 +1032,7 @@ class RayMarchingCallback:
 
 # The outputs of the lattice analyses (RayMarchingResources._solid_grid_call): the families of retained results a call replaces
 # (a new distance volume has no mask), how many counts and statistics, and their names.
-_FAMILIES = ("topology", "distance", "distance_mask", "support", "islands", "voxels")
+_FAMILIES = ("topology", "distance", "distance_mask", "support", "islands", "voxels", "lattice")
 _TOPO_OUTPUTS = (("topology",), _ffi.RM_TOPO_COUNTS, _ffi.RM_TOPO_STATS, _ffi.TOPO_COUNT_NAMES, _ffi.TOPO_STAT_NAMES)
 _DIST_OUTPUTS = (("distance", "distance_mask"), _ffi.RM_DIST_COUNTS, _ffi.RM_DIST_STATS, _ffi.DIST_COUNT_NAMES, _ffi.DIST_STAT_NAMES)
 _SUP_OUTPUTS = (("support",), _ffi.RM_SUP_COUNTS, _ffi.RM_SUP_STATS, _ffi.SUP_COUNT_NAMES, _ffi.SUP_STAT_NAMES)
@@ -1298,6 +1373,32 @@ class Voxels(_Retained):
         """occupancy() as a torch tensor on the context's GPU, filled on torch.cuda.current_stream() without a host round trip."""
         self._check_current()
         return self._res._read_new(self._res._L.rm_read_voxels, [(tuple(self.shape)[::-1], *_U8, True)], device=True)[0]
+
+
+class Lattice(_Retained):
+    """The result of set_lattice: the lattice draw_lattice and cast_lattice of its context show until the next set_lattice.
+    counts and stats: dicts (_ffi.LAT_COUNT_NAMES: points, bricks; _ffi.LAT_STAT_NAMES); origin, step (float32[3]) and shape."""
+
+    def __init__(self, resources, counts, stats, origin, step, shape):
+        self._retain(resources, "lattice")
+        self.counts, self.stats = counts, stats
+        self.origin, self.step, self.shape = origin, step, shape
+
+    def __repr__(self):
+        return "Lattice(%d points in %d bricks, on %s)" % (self.counts["points"], self.counts["bricks"], "x".join(map(str, self.shape)))
+
+    def current(self):
+        """Whether this is still the lattice its context draws."""
+        try:
+            self._check_current()
+        except ValueError:
+            return False
+        return True
+
+    def box(self):
+        """The lattice's box in world space, (lo, hi) float64[3]: the cubes' outer faces."""
+        o, s = self.origin.astype(np.float64), self.step.astype(np.float64)
+        return o - 0.5 * s, o + (np.asarray(self.shape, dtype=np.float64) - 0.5) * s
 
 
 def surface_directions():

@@ -20,6 +20,8 @@ import json
 import re
 import sys
 
+from . import lattice_image
+
 from .massprops import load_program
 from .mesh import _three
 
@@ -76,6 +78,7 @@ def main(argv=None):
     ap.add_argument("--profile", action="store_true", help="put the per-layer table into the report")
     ap.add_argument("--regions", action="store_true", help="label the overhang and the support points and report every region")
     ap.add_argument("--fail-on", default="", help='e.g. "overhang>0,support>2.5,landings>0": exit status 2 when one of them holds')
+    lattice_image.add_options(ap)
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     gates = parse_gates(a.fail_on)
@@ -110,6 +113,9 @@ def main(argv=None):
                         p = renderer.mass_from_moments(row, sup.origin, sup.step, 1.0)
                         regions.append({"points": int(row[0]), "volume": p["volume"], "centre": [float(x) for x in p["centroid"]]})
                 report[key] = regions
+        if a.image:
+            cls = lattice_image.device_bytes(res, sup.shape, lambda p, st: res.read_support_device(mask_ptr=p, stream=st))
+            report["image"] = lattice_image.write(res, cls, sup.origin, sup.step, a.image, a.size, a.cut)
     finally:
         res.close()
     failed = failed_gates(gates, {"overhang": report["overhang"], "support": report["support"], "landings": report["landings"]})

@@ -18,6 +18,8 @@ import json
 import re
 import sys
 
+from . import lattice_image
+
 from .massprops import load_program
 from .mesh import _three
 
@@ -67,6 +69,7 @@ def main(argv=None):
     ap.add_argument("--mask", default=None, help="write the feature mask to this .npy file")
     ap.add_argument("--regions", action="store_true", help="label the thin points and report every region")
     ap.add_argument("--fail-on", default="", help='e.g. "thin>0,narrow>0,inscribed<0.4": exit status 2 when one of them holds')
+    lattice_image.add_options(ap)
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     gates = parse_gates(a.fail_on)
@@ -88,7 +91,7 @@ def main(argv=None):
         if a.d2:
             np.save(a.d2, dist.d2())
         values = {"inscribed": radius, "thin": 0, "narrow": 0}
-        if a.min_wall is not None or a.min_gap is not None or a.mask or a.regions:
+        if a.min_wall is not None or a.min_gap is not None or a.mask or a.regions or a.image:
             feats = dist.features(wall=a.min_wall, gap=a.min_gap)
             report.update(r2_wall=feats.r2_wall, r2_gap=feats.r2_gap, **feats.counts)
             values.update(thin=feats.counts["thin"], narrow=feats.counts["narrow"])
@@ -109,6 +112,9 @@ def main(argv=None):
                         p = renderer.mass_from_moments(row, dist.origin, dist.step, 1.0)
                         regions.append({"points": int(row[0]), "volume": p["volume"], "centre": [float(x) for x in p["centroid"]]})
                 report["regions"] = regions
+        if a.image:
+            cls = lattice_image.device_bytes(res, dist.shape, lambda p, st: res.read_distance_device(mask_ptr=p, stream=st))
+            report["image"] = lattice_image.write(res, cls, dist.origin, dist.step, a.image, a.size, a.cut)
     finally:
         res.close()
     failed = failed_gates(gates, values)

@@ -11,7 +11,8 @@ that analysis of the occupancy: topology (label_occupancy), thickness (distance_
 units), supports and islands (support_occupancy, islands_occupancy for --up and --r2), surface (surface_classes: the area of the
 voxel solid).  --out writes the occupancy as a .npy file, uint8 indexed [k, j, i].  --fail-on is a gate: a comma-separated list
 of `name>N` or `name<N` over the voxel counts and the counts of the requested reports (`report.name` where two reports share a
-name); the exit status is 2 when one holds."""
+name); the exit status is 2 when one holds.  --image writes a picture of the voxel solid (a PNG of --size,
+through an orbit camera aimed at the lattice's box; --cut axis:lo:hi shows only that slab of lattice points: DESIGN.md section 28)."""
 import argparse
 import json
 import re
@@ -19,7 +20,7 @@ import sys
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, lattice_image
 
 REPORTS = {"topology": _ffi.TOPO_COUNT_NAMES, "thickness": _ffi.DIST_COUNT_NAMES + ("inscribed_radius",),
            "supports": _ffi.SUP_COUNT_NAMES, "islands": _ffi.ISL_COUNT_NAMES, "surface": _ffi.SURF_MEASURE_NAMES}
@@ -99,6 +100,7 @@ def main(argv=None):
     ap.add_argument("--up", default="+z", choices=UPS, help="the build direction of supports and islands")
     ap.add_argument("--r2", type=int, default=1, help="the squared reach of supports and islands (index units, 0..255)")
     ap.add_argument("--fail-on", default="", help='e.g. "open_rows>0,rejected>0,bodies>1": exit status 2 when one of them holds')
+    lattice_image.add_options(ap)
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     try:
@@ -116,6 +118,8 @@ def main(argv=None):
         report.update(analyse(res, vox, reports, a.up, a.r2))
         if a.out:
             np.save(a.out, vox.occupancy())
+        if a.image:                                              # the occupancy never leaves the device
+            report["image"] = lattice_image.write(res, vox.occupancy_device(), vox.origin, vox.step, a.image, a.size, a.cut)
     finally:
         res.close()
     report["failed"] = failed_gates(gates, gate_values(report, reports))
