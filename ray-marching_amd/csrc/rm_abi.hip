@@ -26,6 +26,7 @@
 #include "rm_interp.h"
 #include "rm_kernel_v5.h"
 #include "rm_query.h"
+#include "rm_reduce.h"
 #include "rm_trace.h"
 #include "rm_mesh.h"
 #include "rm_mesh_bound.h"
@@ -1434,15 +1435,13 @@ RM_EXPORT int rm_trace_rays(rm_ctx* c, uint32_t n, const float* rays, const floa
     if (rc == RM_OK && attr) {
         hipLaunchKernelGGL(rmk::rm_mesh_scan_kernel, dim3(1), dim3(1024), 0, s, L.sums.at(base), nb, L.totals.at(base));
         HIP_TRY(c, hipGetLastError());
-        hipLaunchKernelGGL(rmk::rm_trace_list_kernel, dim3(nb), dim3(256), 0, s, n, static_cast<const uint32_t*>(L.stored.at(base)),
-                           static_cast<const unsigned long long*>(L.sums.at(base)), L.list.at(base));
+        hipLaunchKernelGGL(rmk::rm_trace_list_kernel, dim3(nb), dim3(256), 0, s, n, L.stored.at(base), L.sums.at(base), L.list.at(base));
         HIP_TRY(c, hipGetLastError());
         // one lane per stored event; how many there are only the device knows, so a fixed number of workgroups strides over them
         const uint64_t most = ((uint64_t)n * K + 255u) / 256u;
         const uint32_t blocks = (uint32_t)std::min<uint64_t>(most, (uint64_t)std::max(c->cu_count, 1) * 8u);
-        rc = qa.launch(trace_attr_kernel(normals, ids), blocks, 0u, K, static_cast<const uint32_t*>(L.totals.at(base)),
-                       static_cast<const uint2*>(L.list.at(base)), static_cast<const float*>(d_events), normals ? o.dev<float>(0) : nullptr,
-                       ids ? o.dev<uint32_t>(1) : nullptr);
+        rc = qa.launch(trace_attr_kernel(normals, ids), blocks, 0u, K, L.totals.at(base), L.list.at(base), d_events,
+                       normals ? o.dev<float>(0) : nullptr, ids ? o.dev<uint32_t>(1) : nullptr);
     }
     return rc == RM_OK ? o.finish(s) : rc;
 }
@@ -1667,12 +1666,12 @@ int point_attributes(const QueryCall& q, uint32_t flags, uint64_t n, const float
 // The regions of the kept bricks' scratch round up to 16 bytes like all others; the segment maps and the segments' first
 // (vertex, triangle) pairs always were whole multiples of 16, so RM_MESH_STAT_SCRATCH_BYTES is what it was.
 static_assert(sizeof(rmk::SparseSegMap) % 16u == 0u && (rmk::kBrickSegs * sizeof(uint2)) % 16u == 0u, "sparse scratch layout");
-static_assert(rmk::kMoments == (uint32_t)RM_MOMENTS, "a row holds the moments of enum rm_moment");
+static_assert(rmk::kRowWords == (uint32_t)RM_MOMENTS, "a row holds the moments of enum rm_moment");
 constexpr uint32_t kMaxMassDim = 4096u;  // rm_mass_moments: every sum below 2^60 (rm_abi.h)
 constexpr uint32_t kMaxTopoDim = 1024u;        // rm_label_solid: labels are linear indices with the two top bits free ...
 constexpr uint64_t kMaxTopoPoints = 1ull << 28;  // ... and every moment stays far below 2^60
 constexpr uint32_t kMaxMergePasses = 8u;
-static_assert(rmk::kTopoFold == 256u, "TopoScratch folds the bricks' rows by the probe's blocks of 256");
+static_assert(rmk::kRowsFold == 256u, "TopoScratch folds the bricks' rows by the probe's blocks of 256");
 static_assert(rmk::kTopoExterior == RM_TOPO_EXTERIOR && rmk::kTopoCavityBit == RM_TOPO_CAVITY_BIT, "the label volume's marks");
 static_assert(rmk::kDistInside == RM_DIST_INSIDE_BIT && rmk::kDistNone == RM_DIST_NONE, "the distance volume's marks");
 static_assert(rml::kDistMaxAxis == kMaxTopoDim, "a column tile holds the longest axis");
@@ -1714,6 +1713,57 @@ int count_bricks(rm_ctx* c, const char* fn, rmk::SparseGrid* g) {
     return RM_OK;
 }
 
+// ---- the reductions' host side (rm_reduce.h) ----
+// One more copy from device to host that rides on the single synchronise of the helpers below.
+struct AlsoRead {
+    void* host = nullptr;
+    const void* dev = nullptr;
+    size_t bytes = 0;
+};
+
+// The two totals rm_block_scan_kernel left in totals_dev -> out, with `also` beside them; synchronises.
+int read_totals(rm_ctx* c, hipStream_t s, const unsigned long long* totals_dev, uint64_t out[2], AlsoRead also = AlsoRead()) {
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the totals are copied as they lie");
+    HIP_TRY(c, hipMemcpyAsync(out, totals_dev, 2u * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (also.bytes) HIP_TRY(c, hipMemcpyAsync(also.host, also.dev, also.bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+// The n_blocks block sums (lo | hi << 32) -> exclusive offsets in place, the two totals into totals_dev; queued, not read.
+int scan_launch(rm_ctx* c, hipStream_t s, unsigned long long* sums, uint32_t n_blocks, unsigned long long* totals_dev) {
+    hipLaunchKernelGGL(rmk::rm_block_scan_kernel, dim3(1), dim3(1024), 0, s, sums, n_blocks, totals_dev);
+    HIP_TRY(c, hipGetLastError());
+    return RM_OK;
+}
+
+// Both: the scan, and its totals on the host.
+int scan_totals(rm_ctx* c, hipStream_t s, unsigned long long* sums, uint32_t n_blocks, unsigned long long* totals_dev, uint64_t out[2],
+                AlsoRead also = AlsoRead()) {
+    if (int rc = scan_launch(c, s, sums, n_blocks, totals_dev)) return rc;
+    return read_totals(c, s, totals_dev, out, also);
+}
+
+// The rows a[0, na) and b[0, nb) -> result (rm_rows_reduce_kernel, one workgroup) -> row on the host, with `also` beside it;
+// synchronises.
+int reduce_to_row(rm_ctx* c, hipStream_t s, const unsigned long long* a, uint32_t na, const unsigned long long* b, uint32_t nb,
+                  unsigned long long* result, unsigned long long row[RM_MOMENTS], AlsoRead also = AlsoRead()) {
+    hipLaunchKernelGGL(rmk::rm_rows_reduce_kernel, dim3(1), dim3(256), 0, s, a, na, b, nb, result);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(row, result, RM_MOMENTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (also.bytes) HIP_TRY(c, hipMemcpyAsync(also.host, also.dev, also.bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return RM_OK;
+}
+
+// A launch's n_rows rows -> folded (rm_rows_fold_kernel, kRowsFold rows to a workgroup) -> result -> row, as above.
+int reduce_rows(rm_ctx* c, hipStream_t s, const unsigned long long* rows, uint32_t n_rows, unsigned long long* folded,
+                unsigned long long* result, unsigned long long row[RM_MOMENTS], AlsoRead also = AlsoRead()) {
+    const uint32_t n_folded = rmk::rows_folded(n_rows);
+    hipLaunchKernelGGL(rmk::rm_rows_fold_kernel, dim3(n_folded), dim3(256), 0, s, rows, n_rows, folded);
+    return reduce_to_row(c, s, folded, n_folded, nullptr, 0u, result, row, also);
+}
+
 // The front of a pass over the bricks, in the tables B of the buffer at `base` (regions psums, ptot, evals): the evaluation
 // counter zeroed, the probe `probe` of n_pblocks blocks of 256 bricks on (g, level, the program's bounds, its table, psums,
 // extra...), the scan of its block sums (kept in the low half, inside in the high half -> ptot).
@@ -1723,9 +1773,7 @@ int brick_probe(const QueryCall& q, F&& probe, const rmk::SparseGrid& g, float l
     unsigned long long* psums = B.psums.at(base);
     HIP_TRY(q.c, hipMemsetAsync(B.evals.at(base), 0, 8, q.s));
     if (int rc = q.launch(probe, n_pblocks, rml::kQueryOwnBrick, g, level, bound.L, 2.0 * bound.E, table, psums, extra...)) return rc;
-    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, q.s, psums, n_pblocks, B.ptot.at(base));
-    HIP_TRY(q.c, hipGetLastError());
-    return RM_OK;
+    return scan_launch(q.c, q.s, psums, n_pblocks, B.ptot.at(base));
 }
 
 // The whole pass of a call that goes on with the kept bricks alone: the front above with the keep flags in B.boff, its two
@@ -1734,19 +1782,13 @@ int brick_probe(const QueryCall& q, F&& probe, const rmk::SparseGrid& g, float l
 template <class F, class Tables, class R, class... Extra>
 int brick_pass(const QueryCall& q, F&& probe, const rmk::SparseGrid& g, float level, const RmProgramBound& bound, uint32_t n_entries,
                uint32_t n_pblocks, const Tables& B, char* base, uint64_t tot[2], R&& reserve_kept, Extra... extra) {
-    rm_ctx* c = q.c;
     uint32_t* boff = B.boff.at(base);
     if (int rc = brick_probe(q, probe, g, level, bound, n_pblocks, B, base, boff, extra...)) return rc;
-    unsigned long long t[2] = {0ull, 0ull};
-    HIP_TRY(c, hipMemcpyAsync(t, B.ptot.at(base), sizeof t, hipMemcpyDeviceToHost, q.s));
-    HIP_TRY(c, hipStreamSynchronize(q.s));
-    tot[0] = t[0];
-    tot[1] = t[1];
-    if (t[0] == 0u) return RM_OK;
+    if (int rc = read_totals(q.c, q.s, B.ptot.at(base), tot)) return rc;
+    if (tot[0] == 0u) return RM_OK;
     uint32_t* klist = nullptr;
     if (int rc = reserve_kept(tot[0], &klist)) return rc;
-    hipLaunchKernelGGL(rmk::rm_sparse_compact_kernel, dim3(n_pblocks), dim3(256), 0, q.s, n_entries,
-                       static_cast<const unsigned long long*>(B.psums.at(base)), boff, klist);
+    hipLaunchKernelGGL(rmk::rm_sparse_compact_kernel, dim3(n_pblocks), dim3(256), 0, q.s, n_entries, B.psums.at(base), boff, klist);
     return RM_OK;
 }
 
@@ -1799,7 +1841,7 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
     uint32_t* totals = S.totals.at(sc);
     const rmk::MeshGrid g{origin[0], origin[1], origin[2], step[0], step[1], step[2], nx, ny, nz, n};
     if ((rc = launch_grid(q, origin, step, nx, ny, n, dist)) != RM_OK) return rc;
-    hipLaunchKernelGGL(rmk::rm_mesh_count_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist), sums);
+    hipLaunchKernelGGL(rmk::rm_mesh_count_kernel, dim3(nb), dim3(256), 0, s, g, level, dist, sums);
     hipLaunchKernelGGL(rmk::rm_mesh_scan_kernel, dim3(1), dim3(1024), 0, s, sums, nb, totals);
     HIP_TRY(c, hipGetLastError());
     uint32_t tot[2] = {0u, 0u};
@@ -1812,11 +1854,9 @@ RM_EXPORT int rm_extract_mesh(rm_ctx* c, const float* origin, const float* step,
     float* verts = L.vertices.at(m);
     if (V > 0u) {
         const unsigned long long* offs = sums;
-        hipLaunchKernelGGL(rmk::rm_mesh_vertex_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist), offs,
-                           vbase, fl, verts);
+        hipLaunchKernelGGL(rmk::rm_mesh_vertex_kernel, dim3(nb), dim3(256), 0, s, g, level, dist, offs, vbase, fl, verts);
         if (T > 0u)
-            hipLaunchKernelGGL(rmk::rm_mesh_triangle_kernel, dim3(nb), dim3(256), 0, s, g, offs, static_cast<const uint32_t*>(vbase),
-                               static_cast<const uint8_t*>(fl), L.triangles.at(m));
+            hipLaunchKernelGGL(rmk::rm_mesh_triangle_kernel, dim3(nb), dim3(256), 0, s, g, offs, vbase, fl, L.triangles.at(m));
         HIP_TRY(c, hipGetLastError());
         if ((rc = point_attributes(q, flags, V, verts, m, L.normals, L.ids)) != RM_OK) return rc;
     }
@@ -1892,16 +1932,12 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
         uint2* first = S.first.at(sc);
         unsigned long long* ssums = S.ssums.at(sc);
         unsigned long long* stot = S.stot.at(sc);
-        if ((rc = q.launch(RM_BY_LOOP(rm_sparse_count_kernel), (uint32_t)K, rml::kQueryOwnBrick, g, level, static_cast<const uint32_t*>(boff),
-                           static_cast<const uint32_t*>(klist), tiles, maps, words, evals)) != RM_OK)
+        if ((rc = q.launch(RM_BY_LOOP(rm_sparse_count_kernel), (uint32_t)K, rml::kQueryOwnBrick, g, level, boff, klist, tiles, maps, words,
+                           evals)) != RM_OK)
             return rc;
-        hipLaunchKernelGGL(rmk::rm_sparse_seg_sum_kernel, dim3(n_sblocks), dim3(256), 0, s, n_segs, static_cast<const uint32_t*>(words), ssums);
-        hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, ssums, n_sblocks, stot);
-        HIP_TRY(c, hipGetLastError());
+        hipLaunchKernelGGL(rmk::rm_sparse_seg_sum_kernel, dim3(n_sblocks), dim3(256), 0, s, n_segs, words, ssums);
         unsigned long long ev = 0ull;
-        HIP_TRY(c, hipMemcpyAsync(tot, stot, sizeof tot, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
+        if ((rc = scan_totals(c, s, ssums, n_sblocks, stot, tot, {&ev, evals, sizeof ev})) != RM_OK) return rc;
         V = tot[0];
         T = tot[1];
         n_evals += ev;
@@ -1912,12 +1948,9 @@ RM_EXPORT int rm_extract_mesh_sparse(rm_ctx* c, const float* origin, const float
         if ((rc = c->mesh.buf.reserve(c, L.bytes)) != RM_OK) return rc;
         char* m = c->mesh.buf.p;
         if (V > 0u) {
-            hipLaunchKernelGGL(rmk::rm_sparse_seg_scan_kernel, dim3(n_sblocks), dim3(256), 0, s, n_segs, static_cast<const uint32_t*>(words),
-                               static_cast<const unsigned long long*>(ssums), first);
-            hipLaunchKernelGGL(rmk::rm_sparse_emit_kernel, dim3((uint32_t)K), dim3(256), 0, s, g, level, (uint32_t)K,
-                               static_cast<const uint32_t*>(boff), static_cast<const uint32_t*>(klist), static_cast<const float*>(tiles),
-                               static_cast<const rmk::SparseSegMap*>(maps), static_cast<const uint32_t*>(words), static_cast<const uint2*>(first),
-                               L.vertices.at(m), L.triangles.at(m));
+            hipLaunchKernelGGL(rmk::rm_sparse_seg_scan_kernel, dim3(n_sblocks), dim3(256), 0, s, n_segs, words, ssums, first);
+            hipLaunchKernelGGL(rmk::rm_sparse_emit_kernel, dim3((uint32_t)K), dim3(256), 0, s, g, level, (uint32_t)K, boff, klist, tiles, maps, words,
+                               first, L.vertices.at(m), L.triangles.at(m));
             HIP_TRY(c, hipGetLastError());
             if ((rc = point_attributes(q, flags, V, L.vertices.at(m), m, L.normals, L.ids)) != RM_OK) return rc;
         }
@@ -1976,18 +2009,13 @@ RM_EXPORT int rm_mass_moments(rm_ctx* c, const float* origin, const float* step,
     if (K > 0u) {
         kept_bytes = S.bytes;
         char* sc = c->d_mscratch.p;
-        if ((rc = q.launch(RM_BY_LOOP(rm_mass_count_kernel), (uint32_t)K, rml::kQueryOwnBrick, g, level, static_cast<const uint32_t*>(S.klist.at(sc)),
-                           S.krows.at(sc), evals)) != RM_OK)
+        if ((rc = q.launch(RM_BY_LOOP(rm_mass_count_kernel), (uint32_t)K, rml::kQueryOwnBrick, g, level, S.klist.at(sc), S.krows.at(sc),
+                           evals)) != RM_OK)
             return rc;
         krows = S.krows.at(sc);
     }
-    hipLaunchKernelGGL(rmk::rm_mass_reduce_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned long long*>(prows), n_pblocks, krows,
-                       (uint32_t)K, result);
-    HIP_TRY(c, hipGetLastError());
     unsigned long long mom[RM_MOMENTS], ev = 0ull;
-    HIP_TRY(c, hipMemcpyAsync(mom, result, sizeof mom, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(&ev, evals, sizeof ev, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    if ((rc = reduce_to_row(c, s, prows, n_pblocks, krows, (uint32_t)K, result, mom, {&ev, evals, sizeof ev})) != RM_OK) return rc;
     for (int m = 0; m < RM_MOMENTS; m++) out_moments[m] = mom[m];
     out_stats[RM_MASS_STAT_BRICKS] = g.nb;
     out_stats[RM_MASS_STAT_BRICKS_KEPT] = K;
@@ -2127,8 +2155,7 @@ struct OccupancySource {
         uint8_t* cls = L.cls.at(sc);
         int rc = brick_probe(q, RM_BY_LOOP(rm_topo_probe_kernel), G.g, level, bound, G.n_pblocks, L, sc, cls);
         if (rc != RM_OK) return rc;
-        return q.launch(RM_BY_LOOP(rm_topo_occupancy_kernel), G.g.nb, rml::kQueryOwnBrick, G.g, level, static_cast<const uint8_t*>(cls), L.occ.at(sc),
-                        L.evals.at(sc));
+        return q.launch(RM_BY_LOOP(rm_topo_occupancy_kernel), G.g.nb, rml::kQueryOwnBrick, G.g, level, cls, L.occ.at(sc), L.evals.at(sc));
     }
 
     // The brick statistics of the fill; those of a caller's occupancy stay 0.
@@ -2136,10 +2163,9 @@ struct OccupancySource {
     int brick_stats(rm_ctx* c, hipStream_t s, const TopoGrid& G, const S& L, uint64_t* stats) const {
         if (!solid) return RM_OK;
         char* sc = c->d_mscratch.p;
-        unsigned long long tot[2] = {0ull, 0ull}, ev = 0ull;
-        HIP_TRY(c, hipMemcpyAsync(tot, L.ptot.at(sc), sizeof tot, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(&ev, L.evals.at(sc), sizeof ev, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
+        uint64_t tot[2];
+        unsigned long long ev = 0ull;
+        if (int rc = read_totals(c, s, L.ptot.at(sc), tot, {&ev, L.evals.at(sc), sizeof ev})) return rc;
         stats[kStatBricks] = G.g.nb;
         stats[kStatBricksKept] = tot[0];
         stats[kStatBricksInside] = tot[1];
@@ -2200,13 +2226,7 @@ int label_lattice(rm_ctx* c, const char* fn, hipStream_t s, const TopoGrid& G, c
     uint32_t* labels = c->topo.labels.as<uint32_t>();
     const uint32_t point_blocks = (G.n + 255u) / 256u;
     unsigned long long row[RM_MOMENTS];
-    // the bricks' rows -> result: 256 rows to a workgroup, then the mass reducer over the folded ones
     unsigned long long* folded = T.folded.at(sc);
-    const auto reduce_rows = [&] {
-        hipLaunchKernelGGL(rmk::rm_topo_fold_kernel, dim3(G.n_pblocks), dim3(256), 0, s, static_cast<const unsigned long long*>(rows), g.nb, folded);
-        hipLaunchKernelGGL(rmk::rm_mass_reduce_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned long long*>(folded), G.n_pblocks,
-                           static_cast<const unsigned long long*>(nullptr), 0u, result);
-    };
     hipLaunchKernelGGL(rmk::rm_topo_local_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, parent);
     // A bounded host loop over a convergent process: one pass unites everything unless a union was lost, which the verification
     // after the kernel boundary (every write visible) would find.
@@ -2215,39 +2235,27 @@ int label_lattice(rm_ctx* c, const char* fn, hipStream_t s, const TopoGrid& G, c
         passes++;
         hipLaunchKernelGGL(rmk::rm_topo_merge_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, parent);
         hipLaunchKernelGGL(rmk::rm_topo_flatten_kernel, dim3(point_blocks), dim3(256), 0, s, G.n, parent);
-        hipLaunchKernelGGL(rmk::rm_topo_verify_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, static_cast<const uint32_t*>(parent), rows);
-        reduce_rows();
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(row, result, sizeof row, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
+        hipLaunchKernelGGL(rmk::rm_topo_verify_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, parent, rows);
+        if ((rc = reduce_rows(c, s, rows, g.nb, folded, result, row)) != RM_OK) return rc;
         if (row[4] == 0ull) break;
         if (passes == kMaxMergePasses)
             return fail(c, RM_ERR_DEVICE, "%s: %llu pairs of neighbours still have different roots after %u merge passes", fn, row[4], passes);
     }
     HIP_TRY(c, hipMemsetAsync(ext, 0, G.n, s));
-    hipLaunchKernelGGL(rmk::rm_topo_exterior_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, static_cast<const uint32_t*>(parent), ext);
-    hipLaunchKernelGGL(rmk::rm_topo_root_sum_kernel, dim3(G.n_rblocks), dim3(256), 0, s, G.n, occ, static_cast<const uint32_t*>(parent),
-                       static_cast<const uint8_t*>(ext), rsums);
-    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, rsums, G.n_rblocks, rtot);
-    HIP_TRY(c, hipGetLastError());
-    unsigned long long tot[2] = {0ull, 0ull};
-    HIP_TRY(c, hipMemcpyAsync(tot, rtot, sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    hipLaunchKernelGGL(rmk::rm_topo_exterior_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, parent, ext);
+    hipLaunchKernelGGL(rmk::rm_topo_root_sum_kernel, dim3(G.n_rblocks), dim3(256), 0, s, G.n, occ, parent, ext, rsums);
+    uint64_t tot[2];
+    if ((rc = scan_totals(c, s, rsums, G.n_rblocks, rtot, tot)) != RM_OK) return rc;
     const uint64_t B = tot[0], C = tot[1];
     const rml::TopoRows R(B, C);
     if (R.bytes > 0u) {
         if ((rc = c->topo.rows.reserve(c, R.bytes, "component rows")) != RM_OK) return rc;
-        hipLaunchKernelGGL(rmk::rm_topo_rows_init_kernel, dim3((uint32_t)(((B + C) * rmk::kMoments + 255u) / 256u)), dim3(256), 0, s,
+        hipLaunchKernelGGL(rmk::rm_topo_rows_init_kernel, dim3((uint32_t)(((B + C) * rmk::kRowWords + 255u) / 256u)), dim3(256), 0, s,
                            (uint32_t)(B + C), R.bodies.at(c->topo.rows.p));
     }
-    hipLaunchKernelGGL(rmk::rm_topo_rank_kernel, dim3(G.n_rblocks), dim3(256), 0, s, G.n, occ, static_cast<const uint32_t*>(parent),
-                       static_cast<const uint8_t*>(ext), static_cast<const unsigned long long*>(rsums), labels);
-    hipLaunchKernelGGL(rmk::rm_topo_rows_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, static_cast<const uint32_t*>(parent), labels, (uint32_t)B,
-                       R.bodies.at(c->topo.rows.p), rows);
-    reduce_rows();
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(row, result, sizeof row, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    hipLaunchKernelGGL(rmk::rm_topo_rank_kernel, dim3(G.n_rblocks), dim3(256), 0, s, G.n, occ, parent, ext, rsums, labels);
+    hipLaunchKernelGGL(rmk::rm_topo_rows_kernel, dim3(g.nb), dim3(256), 0, s, g, occ, parent, labels, (uint32_t)B, R.bodies.at(c->topo.rows.p), rows);
+    if ((rc = reduce_rows(c, s, rows, g.nb, folded, result, row)) != RM_OK) return rc;
     const uint64_t V = row[0], E = row[1], F = row[2], K = row[3];
     const int64_t euler = (int64_t)V - (int64_t)E + (int64_t)F - (int64_t)K;
     counts[RM_TOPO_BODIES] = B;
@@ -2309,7 +2317,7 @@ namespace {
 
 struct DistBlocks {
     uint32_t n_rblocks, n_fblocks;  // rows of 2048 points, folded rows of 256 rows
-    explicit DistBlocks(uint32_t n) : n_rblocks((n + rmk::kDistBlock - 1u) / rmk::kDistBlock), n_fblocks((n_rblocks + rmk::kTopoFold - 1u) / rmk::kTopoFold) {}
+    explicit DistBlocks(uint32_t n) : n_rblocks((n + rmk::kDistBlock - 1u) / rmk::kDistBlock), n_fblocks(rmk::rows_folded(n_rblocks)) {}
 };
 
 // The y and the z pass over `vol` (rm_dist_column_kernel): a launch each.
@@ -2329,18 +2337,6 @@ int dist_columns(rm_ctx* c, hipStream_t s, const rmk::SparseGrid& g, uint32_t no
     return RM_OK;
 }
 
-// rows -> the reduced row of 16 words, on the host.
-int dist_reduce(rm_ctx* c, hipStream_t s, const DistBlocks& D, const unsigned long long* rows, unsigned long long* folded,
-                unsigned long long* result, unsigned long long* row) {
-    hipLaunchKernelGGL(rmk::rm_topo_fold_kernel, dim3(D.n_fblocks), dim3(256), 0, s, rows, D.n_rblocks, folded);
-    hipLaunchKernelGGL(rmk::rm_mass_reduce_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned long long*>(folded), D.n_fblocks,
-                       static_cast<const unsigned long long*>(nullptr), 0u, result);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(row, result, RM_MOMENTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    return RM_OK;
-}
-
 // From the occupancy in S.occ on: rows, columns, maxima.  counts: RM_DIST_COUNTS words.
 int distance_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rml::DistScratch& S, uint64_t* counts) {
     const rmk::SparseGrid& g = G.g;
@@ -2348,12 +2344,12 @@ int distance_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rml::Dis
     uint32_t* vol = c->dist.vol.as<uint32_t>();
     const DistBlocks D(G.n);
     const uint32_t n_rows = g.ny * g.nz;
-    hipLaunchKernelGGL(rmk::rm_dist_row_kernel<rmk::DIST_FROM_OCCUPANCY>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, g.nx, n_rows,
-                       static_cast<const uint8_t*>(S.occ.at(sc)), static_cast<const uint32_t*>(nullptr), 0u, vol);
+    hipLaunchKernelGGL(rmk::rm_dist_row_kernel<rmk::DIST_FROM_OCCUPANCY>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, g.nx, n_rows, S.occ.at(sc),
+                       nullptr, 0u, vol);
     if (int rc = dist_columns<false>(c, s, g, rmk::kDistNone, vol)) return rc;
-    hipLaunchKernelGGL(rmk::rm_dist_max_kernel, dim3(D.n_rblocks), dim3(256), 0, s, G.n, static_cast<const uint32_t*>(vol), S.rows.at(sc));
+    hipLaunchKernelGGL(rmk::rm_dist_max_kernel, dim3(D.n_rblocks), dim3(256), 0, s, G.n, vol, S.rows.at(sc));
     unsigned long long row[RM_MOMENTS];
-    if (int rc = dist_reduce(c, s, D, S.rows.at(sc), S.folded.at(sc), S.result.at(sc), row)) return rc;
+    if (int rc = reduce_rows(c, s, S.rows.at(sc), D.n_rblocks, S.folded.at(sc), S.result.at(sc), row)) return rc;
     counts[RM_DIST_POINTS] = row[0];
     counts[RM_DIST_MAX_INSIDE] = row[13] >> 32;
     counts[RM_DIST_ARGMAX_INSIDE] = ~row[13] & 0xFFFFFFFFull;
@@ -2423,22 +2419,20 @@ RM_EXPORT int rm_distance_features(rm_ctx* c, uint32_t r2_wall, uint32_t r2_gap,
     uint64_t counts[RM_DIST_FEATURE_COUNTS] = {0u, 0u, 0u, 0u};
     unsigned long long row[RM_MOMENTS];
     if (r2_wall != RM_DIST_SKIP) {
-        hipLaunchKernelGGL(rmk::rm_dist_row_kernel<rmk::DIST_FROM_WALL_CORE>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, g.nx, n_rows,
-                           static_cast<const uint8_t*>(nullptr), vol, r2_wall, feat);
+        hipLaunchKernelGGL(rmk::rm_dist_row_kernel<rmk::DIST_FROM_WALL_CORE>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, g.nx, n_rows, nullptr, vol,
+                           r2_wall, feat);
         if ((rc = dist_columns<true>(c, s, g, r2_wall + 1u, feat)) != RM_OK) return rc;
-        hipLaunchKernelGGL((rmk::rm_dist_compose_kernel<1u, 2u>), dim3(D.n_rblocks), dim3(256), 0, s, G.n, vol, static_cast<const uint32_t*>(feat),
-                           r2_wall, mask, S.rows.at(sc));
-        if ((rc = dist_reduce(c, s, D, S.rows.at(sc), S.folded.at(sc), S.result.at(sc), row)) != RM_OK) return rc;
+        hipLaunchKernelGGL((rmk::rm_dist_compose_kernel<1u, 2u>), dim3(D.n_rblocks), dim3(256), 0, s, G.n, vol, feat, r2_wall, mask, S.rows.at(sc));
+        if ((rc = reduce_rows(c, s, S.rows.at(sc), D.n_rblocks, S.folded.at(sc), S.result.at(sc), row)) != RM_OK) return rc;
         counts[RM_DIST_CORE] = row[0];
         counts[RM_DIST_THIN] = row[1];
     }
     if (r2_gap != RM_DIST_SKIP) {
-        hipLaunchKernelGGL(rmk::rm_dist_row_kernel<rmk::DIST_FROM_GAP_CORE>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, g.nx, n_rows,
-                           static_cast<const uint8_t*>(nullptr), vol, r2_gap, feat);
+        hipLaunchKernelGGL(rmk::rm_dist_row_kernel<rmk::DIST_FROM_GAP_CORE>, dim3((n_rows + 3u) / 4u), dim3(256), 0, s, g.nx, n_rows, nullptr, vol,
+                           r2_gap, feat);
         if ((rc = dist_columns<true>(c, s, g, r2_gap + 1u, feat)) != RM_OK) return rc;
-        hipLaunchKernelGGL((rmk::rm_dist_compose_kernel<0u, 3u>), dim3(D.n_rblocks), dim3(256), 0, s, G.n, vol, static_cast<const uint32_t*>(feat),
-                           r2_gap, mask, S.rows.at(sc));
-        if ((rc = dist_reduce(c, s, D, S.rows.at(sc), S.folded.at(sc), S.result.at(sc), row)) != RM_OK) return rc;
+        hipLaunchKernelGGL((rmk::rm_dist_compose_kernel<0u, 3u>), dim3(D.n_rblocks), dim3(256), 0, s, G.n, vol, feat, r2_gap, mask, S.rows.at(sc));
+        if ((rc = reduce_rows(c, s, S.rows.at(sc), D.n_rblocks, S.folded.at(sc), S.result.at(sc), row)) != RM_OK) return rc;
         counts[RM_DIST_GAP_CORE] = row[0];
         counts[RM_DIST_NARROW] = row[1];
     }
@@ -2520,7 +2514,7 @@ void support_planes(hipStream_t s, const rmk::SupFrame& f, uint32_t r2, uint32_t
         hipLaunchKernelGGL(rmk::rm_sup_pack_kernel<false>, tasks.grid, dim3(256), 0, s, f, tasks.n, plate, occ, ins, h0w);
     const uint32_t reach = sup_reach(r2), tv = rml::sup_tile_rows(f.nw);
     hipLaunchKernelGGL(rmk::rm_sup_overhang_kernel, dim3((f.nv + tv - 1u) / tv, f.nh), dim3(256), rml::SupCoverLds(tv, reach, f.nw).bytes, s, f.nv,
-                       f.nw, tv, r2, reach, plate, static_cast<const uint32_t*>(h0w), static_cast<const unsigned long long*>(ins), ov);
+                       f.nw, tv, r2, reach, plate, h0w, ins, ov);
 }
 
 // From the occupancy in S.occ on: pack, overhang, columns, count, compose; the profile summed on the host (at most 1024 layers of
@@ -2539,19 +2533,14 @@ int support_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
     HIP_TRY(c, hipMemsetAsync(pr, 0, R.bytes, s));
     const uint8_t* occ = S.occ.at(sc);
     support_planes(s, f, r2, plate, occ, ins, ov, h0w);
-    hipLaunchKernelGGL(rmk::rm_sup_columns_kernel, dim3((ncw + rmk::kSupColumnThreads - 1u) / rmk::kSupColumnThreads), dim3(rmk::kSupColumnThreads), 0, s, ncw, f.nh, plate, static_cast<const uint32_t*>(h0w),
-                       static_cast<const unsigned long long*>(ins), static_cast<const unsigned long long*>(ov), sup, plt);
-    hipLaunchKernelGGL(rmk::rm_sup_count_kernel, dim3((ncw + 255u) / 256u, f.nh), dim3(256), 0, s, ncw, f.nh, plate, static_cast<const uint32_t*>(h0w),
-                       static_cast<const unsigned long long*>(ins), static_cast<const unsigned long long*>(ov),
-                       static_cast<const unsigned long long*>(sup), static_cast<const unsigned long long*>(plt), R.profile.at(pr), R.extra.at(pr));
+    hipLaunchKernelGGL(rmk::rm_sup_columns_kernel, dim3((ncw + rmk::kSupColumnThreads - 1u) / rmk::kSupColumnThreads), dim3(rmk::kSupColumnThreads),
+                       0, s, ncw, f.nh, plate, h0w, ins, ov, sup, plt);
+    hipLaunchKernelGGL(rmk::rm_sup_count_kernel, dim3((ncw + 255u) / 256u, f.nh), dim3(256), 0, s, ncw, f.nh, plate, h0w, ins, ov, sup, plt,
+                       R.profile.at(pr), R.extra.at(pr));
     if (tasks.xup)
-        hipLaunchKernelGGL(rmk::rm_sup_compose_kernel<true>, tasks.grid, dim3(256), 0, s, f, tasks.n, static_cast<const unsigned long long*>(ins),
-                           static_cast<const unsigned long long*>(ov), static_cast<const unsigned long long*>(sup),
-                           static_cast<const unsigned long long*>(plt), mask);
+        hipLaunchKernelGGL(rmk::rm_sup_compose_kernel<true>, tasks.grid, dim3(256), 0, s, f, tasks.n, ins, ov, sup, plt, mask);
     else
-        hipLaunchKernelGGL(rmk::rm_sup_compose_kernel<false>, tasks.grid, dim3(256), 0, s, f, tasks.n, static_cast<const unsigned long long*>(ins),
-                           static_cast<const unsigned long long*>(ov), static_cast<const unsigned long long*>(sup),
-                           static_cast<const unsigned long long*>(plt), mask);
+        hipLaunchKernelGGL(rmk::rm_sup_compose_kernel<false>, tasks.grid, dim3(256), 0, s, f, tasks.n, ins, ov, sup, plt, mask);
     HIP_TRY(c, hipGetLastError());
     std::vector<uint32_t> rows((size_t)f.nh * 6u);
     uint32_t h0 = 0u;
@@ -2652,23 +2641,17 @@ int islands_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
     unsigned long long *ins = S.ins.at(sc), *ov = S.ov.at(sc), *rsums = S.rsums.at(sc), *rtot = S.rtot.at(sc);
     uint32_t *h0w = S.plate.at(sc), *parent = S.parent.at(sc), *lab = S.lab.at(sc), *lbase = S.lbase.at(sc), *totals = S.totals.at(sc);
     uint32_t* prof = c->isl.profile.as<uint32_t>();
-    const auto cins = static_cast<const unsigned long long*>(ins);
-    const auto cov = static_cast<const unsigned long long*>(ov);
-    const auto ch0 = static_cast<const uint32_t*>(h0w);
     HIP_TRY(c, hipMemsetAsync(h0w, 0xFF, 16, s));
     HIP_TRY(c, hipMemsetAsync(totals, 0, 16, s));
     HIP_TRY(c, hipMemsetAsync(prof, 0, (size_t)f.nh * 16u, s));
     support_planes(s, f, r2, plate, S.occ.at(sc), ins, ov, h0w);
     const uint32_t reach = sup_reach(r2), ncw = f.nv * f.nw;
     hipLaunchKernelGGL(rmk::rm_isl_local_kernel, dim3(f.nw, (f.nv + rml::kIslTile - 1u) / rml::kIslTile, f.nh), dim3(64), rml::IslTileLds().bytes, s,
-                       f, plate, ch0, cins, parent);
-    hipLaunchKernelGGL(rmk::rm_isl_border_kernel, dim3((P.n_words + 255u) / 256u), dim3(256), 0, s, f, P.n_words, G.n, plate, ch0, cins, parent);
-    hipLaunchKernelGGL(rmk::rm_isl_roots_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, G.n, plate, ch0, cins, parent, rsums);
-    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, rsums, P.n_rblocks, rtot);
-    HIP_TRY(c, hipGetLastError());
-    unsigned long long tot[2] = {0ull, 0ull};
-    HIP_TRY(c, hipMemcpyAsync(tot, rtot, sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+                       f, plate, h0w, ins, parent);
+    hipLaunchKernelGGL(rmk::rm_isl_border_kernel, dim3((P.n_words + 255u) / 256u), dim3(256), 0, s, f, P.n_words, G.n, plate, h0w, ins, parent);
+    hipLaunchKernelGGL(rmk::rm_isl_roots_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, G.n, plate, h0w, ins, parent, rsums);
+    uint64_t tot[2];
+    if (int rc = scan_totals(c, s, rsums, P.n_rblocks, rtot, tot)) return rc;
     const uint64_t R = tot[0];  // (<= 2^27: no two neighbours are both roots)
     const rml::IslandsRows T(R);
     uint32_t* rows = nullptr;
@@ -2678,19 +2661,16 @@ int islands_lattice(rm_ctx* c, hipStream_t s, const TopoGrid& G, const rmk::SupF
         hipLaunchKernelGGL(rmk::rm_isl_rows_init_kernel, dim3((uint32_t)((R * rmk::kIslRowWords + 255u) / 256u)), dim3(256), 0, s,
                            (uint32_t)(R * rmk::kIslRowWords), rows);
     }
-    const auto cpar = static_cast<const uint32_t*>(parent);
-    const auto clab = static_cast<const uint32_t*>(lab);
-    hipLaunchKernelGGL(rmk::rm_isl_rank_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, G.n, plate, ch0, cins, cpar,
-                       static_cast<const unsigned long long*>(rsums), lab, rows, lbase);
-    hipLaunchKernelGGL(rmk::rm_isl_spread_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, G.n, plate, ch0, cins, cpar, lab);
-    hipLaunchKernelGGL(rmk::rm_isl_rows_kernel, dim3((ncw + 255u) / 256u, f.nh), dim3(256), 0, s, f, plate, ch0, cins, cov, clab, rows, prof);
+    hipLaunchKernelGGL(rmk::rm_isl_rank_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, G.n, plate, h0w, ins, parent, rsums, lab, rows, lbase);
+    hipLaunchKernelGGL(rmk::rm_isl_spread_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, G.n, plate, h0w, ins, parent, lab);
+    hipLaunchKernelGGL(rmk::rm_isl_rows_kernel, dim3((ncw + 255u) / 256u, f.nh), dim3(256), 0, s, f, plate, h0w, ins, ov, lab, rows, prof);
     if (R != 0u)
         hipLaunchKernelGGL(rmk::rm_isl_links_kernel, dim3(f.nw, (f.nv + rml::kIslLinkRows - 1u) / rml::kIslLinkRows, f.nh), dim3(256),
-                           rml::IslLinkLds(reach).bytes, s, f, r2, reach, plate, ch0, cins, cov, clab, rows);
+                           rml::IslLinkLds(reach).bytes, s, f, r2, reach, plate, h0w, ins, ov, lab, rows);
     hipLaunchKernelGGL(rmk::rm_isl_finish_kernel, dim3((uint32_t)((std::max<uint64_t>(R, f.nh) + 255u) / 256u)), dim3(256), 0, s, (uint32_t)R, f.nh,
-                       plate, ch0, static_cast<const uint32_t*>(lbase), rows, prof, totals);
-    hipLaunchKernelGGL(rmk::rm_isl_compose_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, up >> 1, G.g.nx, G.g.ny, G.n, plate, ch0, cins, clab,
-                       static_cast<const uint32_t*>(rows), c->isl.labels.as<uint32_t>(), c->isl.mask.as<uint8_t>());
+                       plate, h0w, lbase, rows, prof, totals);
+    hipLaunchKernelGGL(rmk::rm_isl_compose_kernel, dim3(P.n_rblocks), dim3(256), 0, s, f, up >> 1, G.g.nx, G.g.ny, G.n, plate, h0w, ins, lab, rows,
+                       c->isl.labels.as<uint32_t>(), c->isl.mask.as<uint8_t>());
     HIP_TRY(c, hipGetLastError());
     std::vector<uint32_t> layers((size_t)f.nh * 4u);
     uint32_t h0 = 0u, merges = 0u;
@@ -2793,10 +2773,9 @@ struct SurfaceAnalysis {
         const SurfTiles T(g);
         constexpr rml::SurfTileLds L;
         static_assert(L.bytes + 1024u <= rml::kLdsLaunchLimit, "a tile and its table fit a workgroup's LDS");
-        hipLaunchKernelGGL(rmk::rm_surf_count_kernel, dim3(T.groups), dim3(256), L.bytes, s, g.nx, g.ny, g.nz, T.tx, T.ty, T.n_tiles,
-                           static_cast<const uint8_t*>(S.occ.at(sc)), S.rows.at(sc));
-        hipLaunchKernelGGL(rmk::rm_surf_reduce_kernel, dim3(rml::kSurfCounts / 8u), dim3(256), 0, s, static_cast<const uint32_t*>(S.rows.at(sc)),
-                           T.groups, S.result.at(sc));
+        hipLaunchKernelGGL(rmk::rm_surf_count_kernel, dim3(T.groups), dim3(256), L.bytes, s, g.nx, g.ny, g.nz, T.tx, T.ty, T.n_tiles, S.occ.at(sc),
+                           S.rows.at(sc));
+        hipLaunchKernelGGL(rmk::rm_surf_reduce_kernel, dim3(rml::kSurfCounts / 8u), dim3(256), 0, s, S.rows.at(sc), T.groups, S.result.at(sc));
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(counts, S.result.at(sc), sizeof(uint64_t) * RM_SURF_COUNTS, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
@@ -2894,7 +2873,7 @@ struct VoxPlan {
     VoxPlan(uint32_t n_triangles, uint32_t nx, uint32_t ny, uint32_t nz)
         : n(nx * ny * nz), n_blocks((uint32_t)(((uint64_t)n_triangles + rmk::kVoxBlock - 1u) / rmk::kVoxBlock)), row_words(rml::vox_row_words(nx)),
           n_words(ny * nz * row_words), n_groups((n + rml::kVoxFillCells - 1u) / rml::kVoxFillCells),
-          n_fblocks((n_groups + rmk::kTopoFold - 1u) / rmk::kTopoFold) {}  // (rows <= 2^20, 33 words each at most)
+          n_fblocks(rmk::rows_folded(n_groups)) {}  // (rows <= 2^20, 33 words each at most)
 };
 
 }  // namespace
@@ -2942,33 +2921,22 @@ RM_EXPORT int rm_voxelize_mesh(rm_ctx* c, uint32_t n_vertices, const float* xyz,
     HIP_TRY(c, hipMemsetAsync(sc + S.clear_offset(), 0, S.clear_bytes(), s));
     hipLaunchKernelGGL(rmk::rm_vox_setup_kernel, dim3(P.n_blocks), dim3(256), 0, s, g, n_vertices, d_xyz, n_triangles, d_idx, S.tris.at(sc),
                        S.starts.at(sc), S.bsums.at(sc), bits, counters);
-    hipLaunchKernelGGL(rmk::rm_sparse_scan_kernel, dim3(1), dim3(1024), 0, s, S.bsums.at(sc), P.n_blocks, S.btot.at(sc));
-    HIP_TRY(c, hipGetLastError());
-    unsigned long long tot[2] = {0ull, 0ull};
-    HIP_TRY(c, hipMemcpyAsync(tot, S.btot.at(sc), sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (tot[0] >= kMaxVoxItems) return fail(c, RM_ERR_TOO_LARGE, "%s: %llu work items of 64 rows: fewer than 2^31", fn, tot[0]);
+    uint64_t tot[2];
+    if ((rc = scan_totals(c, s, S.bsums.at(sc), P.n_blocks, S.btot.at(sc), tot)) != RM_OK) return rc;
+    if (tot[0] >= kMaxVoxItems)
+        return fail(c, RM_ERR_TOO_LARGE, "%s: %llu work items of 64 rows: fewer than 2^31", fn, (unsigned long long)tot[0]);
     // the last check that can refuse is past: the previous occupancy goes
     c->vox.drop();
     if ((rc = c->vox.buf.reserve(c, P.n, "occupancy")) != RM_OK) return rc;
     const uint32_t n_items = (uint32_t)tot[0];
     if (n_items)
-        hipLaunchKernelGGL(rmk::rm_vox_raster_kernel, dim3((n_items + 3u) / 4u), dim3(256), 0, s, g, n_triangles, n_items,
-                           static_cast<const uint32_t*>(S.tris.at(sc)), static_cast<const uint32_t*>(S.starts.at(sc)),
-                           static_cast<const unsigned long long*>(S.bsums.at(sc)), bits, counters);
+        hipLaunchKernelGGL(rmk::rm_vox_raster_kernel, dim3((n_items + 3u) / 4u), dim3(256), 0, s, g, n_triangles, n_items, S.tris.at(sc),
+                           S.starts.at(sc), S.bsums.at(sc), bits, counters);
     constexpr rml::VoxFillLds L;
     static_assert(L.bytes + 1024u <= rml::kLdsLaunchLimit, "the staged words fit a workgroup's LDS");
-    hipLaunchKernelGGL(rmk::rm_vox_fill_kernel, dim3(P.n_groups), dim3(256), L.bytes, s, nx, P.n, static_cast<const uint32_t*>(bits),
-                       c->vox.buf.as<uint8_t>(), S.rows.at(sc));
-    hipLaunchKernelGGL(rmk::rm_topo_fold_kernel, dim3(P.n_fblocks), dim3(256), 0, s, static_cast<const unsigned long long*>(S.rows.at(sc)), P.n_groups,
-                       S.folded.at(sc));
-    hipLaunchKernelGGL(rmk::rm_mass_reduce_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned long long*>(S.folded.at(sc)), P.n_fblocks,
-                       static_cast<const unsigned long long*>(nullptr), 0u, S.result.at(sc));
-    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(rmk::rm_vox_fill_kernel, dim3(P.n_groups), dim3(256), L.bytes, s, nx, P.n, bits, c->vox.buf.as<uint8_t>(), S.rows.at(sc));
     unsigned long long row[RM_MOMENTS], cnt[rmk::VOX_N_COUNTERS];
-    HIP_TRY(c, hipMemcpyAsync(row, S.result.at(sc), sizeof row, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(cnt, counters, sizeof cnt, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    if ((rc = reduce_rows(c, s, S.rows.at(sc), P.n_groups, S.folded.at(sc), S.result.at(sc), row, {cnt, counters, sizeof cnt})) != RM_OK) return rc;
     out_counts[RM_VOX_TRIANGLES] = cnt[rmk::VOX_N_TRIANGLES];
     out_counts[RM_VOX_REJECTED] = cnt[rmk::VOX_N_REJECTED];
     out_counts[RM_VOX_EDGE_ON] = cnt[rmk::VOX_N_EDGE_ON];
@@ -3047,7 +3015,7 @@ RM_EXPORT int rm_set_lattice(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz, c
     HIP_TRY(c, hipMemsetAsync(base + S.clear_offset(), 0, S.clear_bytes(), s));
     const uint32_t row_words = rml::lat_row_words(nx), n_words = ny * nz * row_words;  // (<= 2^27: rows of two points)
     hipLaunchKernelGGL(rmk::rm_lat_pack_kernel, dim3((n_words + 255u) / 256u), dim3(256), 0, s, nx, ny, row_words, n_words, rml::lat_bricks(nx),
-                       rml::lat_bricks(ny), static_cast<const uint8_t*>(S.classes.at(base)), S.bits.at(base), S.bricks.at(base), S.counters.at(base));
+                       rml::lat_bricks(ny), S.classes.at(base), S.bits.at(base), S.bricks.at(base), S.counters.at(base));
 #if !RM_LAT_SKIP
     HIP_TRY(c, hipMemsetAsync(S.bricks.at(base), 0xFF, S.bricks.bytes, s));  // the probe's A/B library: no brick is ever jumped
 #endif
@@ -3194,21 +3162,19 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
     for (uint32_t k0 = 0; k0 < n_layers; k0 += per) {
         const uint32_t nl = std::min(per, n_layers - k0), n = nl * n2, nb = blocks_of(n, rmk::kSliceBlock), pb = blocks_of(n, 256u);
         const rmk::SliceGrid g{origin_uv[0], origin_uv[1], step_uv[0], step_uv[1], nu, nv, n2, axis, k0, n};
-        if ((rc = q.launch(RM_BY_LOOP(rm_slice_dist_kernel), query_blocks(n), 0u, g, static_cast<const float*>(d_heights), dist)) != RM_OK) return rc;
-        hipLaunchKernelGGL(rmk::rm_slice_count_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist), sums);
+        if ((rc = q.launch(RM_BY_LOOP(rm_slice_dist_kernel), query_blocks(n), 0u, g, d_heights, dist)) != RM_OK) return rc;
+        hipLaunchKernelGGL(rmk::rm_slice_count_kernel, dim3(nb), dim3(256), 0, s, g, level, dist, sums);
         hipLaunchKernelGGL(rmk::rm_slice_scan_kernel, dim3(1), dim3(1024), 0, s, sums, nb, d_totals);
-        hipLaunchKernelGGL(rmk::rm_slice_pack_kernel, dim3(nb), dim3(256), 0, s, g, level, static_cast<const float*>(dist),
-                           static_cast<const uint32_t*>(sums), packed);
-        hipLaunchKernelGGL(rmk::rm_slice_layer_base_kernel, dim3(blocks_of(nl + 1u, 256u)), dim3(256), 0, s,
-                           static_cast<const uint32_t*>(packed), n2, nl, static_cast<const uint32_t*>(d_totals), d_base);
+        hipLaunchKernelGGL(rmk::rm_slice_pack_kernel, dim3(nb), dim3(256), 0, s, g, level, dist, sums, packed);
+        hipLaunchKernelGGL(rmk::rm_slice_layer_base_kernel, dim3(blocks_of(nl + 1u, 256u)), dim3(256), 0, s, packed, n2, nl, d_totals, d_base);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(base.data(), d_base, ((size_t)nl + 1u) * 4u, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
         const uint32_t V = base[nl];
         if (P + V > 0xFFFFFFFFull) return fail(c, RM_ERR_RANGE, "rm_slice_contours: more than 2^32 - 1 points");
         if (V == 0u) {
-            hipLaunchKernelGGL(rmk::rm_slice_layer_first_kernel, dim3(blocks_of(nl + 1u, 256u)), dim3(256), 0, s,
-                               static_cast<const uint32_t*>(d_base), nl, 0u, static_cast<const uint32_t*>(nullptr), 0u, (uint32_t)Cn, d_lf + k0);
+            hipLaunchKernelGGL(rmk::rm_slice_layer_first_kernel, dim3(blocks_of(nl + 1u, 256u)), dim3(256), 0, s, d_base, nl, 0u, nullptr, 0u,
+                               (uint32_t)Cn, d_lf + k0);
             HIP_TRY(c, hipGetLastError());
             continue;
         }
@@ -3231,22 +3197,21 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
         uint32_t* first_point = Wk.first_point.at(wk);
         if ((rc = c->slices.points.grow_keep(c, (size_t)(P + V) * 12u, (size_t)P * 12u, s)) != RM_OK) return rc;
         HIP_TRY(c, hipMemsetAsync(wk, 0xFF, Wk.state0.offset, s));  // next and prev: kSliceNil
-        hipLaunchKernelGGL(rmk::rm_slice_link_kernel, dim3(pb), dim3(256), 0, s, g, static_cast<const uint32_t*>(packed), next, prev);
-        hipLaunchKernelGGL(rmk::rm_slice_low_init_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint32_t*>(next), V, st_a);
+        hipLaunchKernelGGL(rmk::rm_slice_link_kernel, dim3(pb), dim3(256), 0, s, g, packed, next, prev);
+        hipLaunchKernelGGL(rmk::rm_slice_low_init_kernel, dim3(vb), dim3(256), 0, s, next, V, st_a);
         for (uint32_t r = 0; r < rounds; r++) {
-            hipLaunchKernelGGL(rmk::rm_slice_low_round_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint2*>(st_a), V, st_b);
+            hipLaunchKernelGGL(rmk::rm_slice_low_round_kernel, dim3(vb), dim3(256), 0, s, st_a, V, st_b);
             std::swap(st_a, st_b);
         }
-        hipLaunchKernelGGL(rmk::rm_slice_cut_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint2*>(st_a),
-                           static_cast<const uint32_t*>(prev), V, start, st_b);
+        hipLaunchKernelGGL(rmk::rm_slice_cut_kernel, dim3(vb), dim3(256), 0, s, st_a, prev, V, start, st_b);
         std::swap(st_a, st_b);
         for (uint32_t r = 0; r < rounds; r++) {
-            hipLaunchKernelGGL(rmk::rm_slice_rank_round_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint2*>(st_a), V, st_b);
+            hipLaunchKernelGGL(rmk::rm_slice_rank_round_kernel, dim3(vb), dim3(256), 0, s, st_a, V, st_b);
             std::swap(st_a, st_b);
         }
-        hipLaunchKernelGGL(rmk::rm_slice_start_count_kernel, dim3(vsb), dim3(256), 0, s, static_cast<const uint32_t*>(start), V, vsums);
+        hipLaunchKernelGGL(rmk::rm_slice_start_count_kernel, dim3(vsb), dim3(256), 0, s, start, V, vsums);
         hipLaunchKernelGGL(rmk::rm_slice_scan_kernel, dim3(1), dim3(1024), 0, s, vsums, vsb, d_totals + 1);
-        hipLaunchKernelGGL(rmk::rm_slice_start_scan_kernel, dim3(vsb), dim3(256), 0, s, start, V, static_cast<const uint32_t*>(vsums));
+        hipLaunchKernelGGL(rmk::rm_slice_start_scan_kernel, dim3(vsb), dim3(256), 0, s, start, V, vsums);
         HIP_TRY(c, hipGetLastError());
         uint32_t Cb = 0;
         HIP_TRY(c, hipMemcpyAsync(&Cb, d_totals + 1, 4u, hipMemcpyDeviceToHost, s));
@@ -3255,19 +3220,14 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
         if (Cn + Cb > 0xFFFFFFFFull) return fail(c, RM_ERR_RANGE, "rm_slice_contours: more than 2^32 - 1 contours");
         if ((rc = c->slices.contours.grow_keep(c, (size_t)(Cn + Cb) * 16u, (size_t)Cn * 16u, s)) != RM_OK) return rc;
         const uint32_t cb = blocks_of(Cb, rmk::kSliceBlock);
-        hipLaunchKernelGGL(rmk::rm_slice_length_kernel, dim3(vb), dim3(256), 0, s, static_cast<const uint2*>(st_a),
-                           static_cast<const uint32_t*>(next), static_cast<const uint32_t*>(start), V, length);
-        hipLaunchKernelGGL(rmk::rm_slice_length_count_kernel, dim3(cb), dim3(256), 0, s, static_cast<const uint32_t*>(length), Cb, vsums);
+        hipLaunchKernelGGL(rmk::rm_slice_length_kernel, dim3(vb), dim3(256), 0, s, st_a, next, start, V, length);
+        hipLaunchKernelGGL(rmk::rm_slice_length_count_kernel, dim3(cb), dim3(256), 0, s, length, Cb, vsums);
         hipLaunchKernelGGL(rmk::rm_slice_scan_kernel, dim3(1), dim3(1024), 0, s, vsums, cb, d_totals + 2);
-        hipLaunchKernelGGL(rmk::rm_slice_length_scan_kernel, dim3(cb), dim3(256), 0, s, static_cast<const uint32_t*>(length), Cb,
-                           static_cast<const uint32_t*>(vsums), first_point);
-        hipLaunchKernelGGL(rmk::rm_slice_layer_first_kernel, dim3(blocks_of(nl + 1u, 256u)), dim3(256), 0, s,
-                           static_cast<const uint32_t*>(d_base), nl, V, static_cast<const uint32_t*>(start), Cb, (uint32_t)Cn, d_lf + k0);
-        hipLaunchKernelGGL(rmk::rm_slice_emit_kernel, dim3(pb), dim3(256), 0, s, g, level, static_cast<const float*>(dist),
-                           static_cast<const float*>(d_heights), static_cast<const uint32_t*>(packed), static_cast<const uint2*>(st_a),
-                           static_cast<const uint32_t*>(start), static_cast<const uint32_t*>(length),
-                           static_cast<const uint32_t*>(first_point), (uint32_t)P, (uint32_t)Cn, c->slices.points.as<float>(),
-                           c->slices.contours.as<uint4>());
+        hipLaunchKernelGGL(rmk::rm_slice_length_scan_kernel, dim3(cb), dim3(256), 0, s, length, Cb, vsums, first_point);
+        hipLaunchKernelGGL(rmk::rm_slice_layer_first_kernel, dim3(blocks_of(nl + 1u, 256u)), dim3(256), 0, s, d_base, nl, V, start, Cb, (uint32_t)Cn,
+                           d_lf + k0);
+        hipLaunchKernelGGL(rmk::rm_slice_emit_kernel, dim3(pb), dim3(256), 0, s, g, level, dist, d_heights, packed, st_a, start, length, first_point,
+                           (uint32_t)P, (uint32_t)Cn, c->slices.points.as<float>(), c->slices.contours.as<uint4>());
         HIP_TRY(c, hipGetLastError());
         P += V;
         Cn += Cb;

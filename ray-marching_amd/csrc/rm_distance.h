@@ -16,14 +16,14 @@
 //            gmin + d^2 >= the best so far; an outside point starts at the first row that holds a value at all.  Exact for
 //            every input; the cost per point is about the distance it finds, in points (section 20 has the worst case).  In
 //            place: a workgroup reads and writes its own columns only, and reads them all before it writes.
-//   maxima   per 2048 points one row of 16 words for the mass reducer: the inside points, and max of (D2 << 32 | ~index) per
+//   maxima   per 2048 points one row of 16 words (rm_reduce.h): the inside points, and max of (D2 << 32 | ~index) per
 //            class -- the largest D2 and the smallest index that attains it, whatever the order.
 // The features run the same row and column kernels from a core mask {class c, D2 > r2}: one class, no layer, values capped at
 // r2 + 1 (a window never reaches past sqrt(r2)); a compose kernel marks the points of class c farther than r2 from every core
 // point and counts.
 #pragma once
 #include "rm_lds_layout.h"
-#include "rm_topology.h"
+#include "rm_reduce.h"
 
 namespace rmk {
 
@@ -178,41 +178,6 @@ __global__ __launch_bounds__(256) void rm_dist_column_kernel(uint32_t nx, uint32
 }
 
 // ---- maxima and counts ------------------------------------------------------------------------------------------------------
-// One row of 16 words per workgroup for rm_topo_fold_kernel and rm_mass_reduce_kernel (entries 0-9 are summed, 13-15 maximised):
-// entries 0, 1 from the packed counts `sums` (two fields of 32 bits; a workgroup counts at most 2048), 13 and 14 from the keys.
-// wred: 12 words of LDS.
-RM_DEV void dist_block_row(unsigned long long sums, unsigned long long key_a, unsigned long long key_b, unsigned long long* wred,
-                           unsigned long long* __restrict__ rows) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        sums += __shfl_xor(sums, o, 64);
-        const unsigned long long a = __shfl_xor(key_a, o, 64), b = __shfl_xor(key_b, o, 64);
-        key_a = a > key_a ? a : key_a;
-        key_b = b > key_b ? b : key_b;
-    }
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 0u) {
-        wred[wave] = sums;
-        wred[4u + wave] = key_a;
-        wred[8u + wave] = key_b;
-    }
-    __syncthreads();
-    if (threadIdx.x < kMoments) {
-        const uint32_t e = threadIdx.x;
-        unsigned long long v = mass_identity(e);
-        if (e < 2u) {
-            const unsigned long long all = wred[0] + wred[1] + wred[2] + wred[3];
-            v = e == 0u ? all & 0xFFFFFFFFull : all >> 32;
-        } else if (e == 13u || e == 14u) {
-            const unsigned long long* k = wred + (e == 13u ? 4u : 8u);
-            v = k[0];
-#pragma unroll
-            for (uint32_t q = 1; q < 4u; q++) v = k[q] > v ? k[q] : v;
-        }
-        rows[(size_t)blockIdx.x * kMoments + e] = v;
-    }
-}
-
 // rows[16 b]: entry 0 the inside points among the points [2048 b, 2048 (b + 1)), entry 13 the largest (D2 << 32 | ~index) over
 // them, entry 14 the same over the outside points (0: no such point; D2 >= 1 otherwise).
 __global__ __launch_bounds__(256) void rm_dist_max_kernel(uint32_t n, const uint32_t* __restrict__ vol, unsigned long long* __restrict__ rows) {
@@ -231,7 +196,7 @@ __global__ __launch_bounds__(256) void rm_dist_max_kernel(uint32_t n, const uint
             kout = key > kout ? key : kout;
         }
     }
-    dist_block_row(cnt, kin, kout, wred, rows);
+    block_row<32, 32>(cnt, kin, kout, wred, rows);  // (a workgroup counts at most 2048)
 }
 
 // ---- features ---------------------------------------------------------------------------------------------------------------
@@ -245,7 +210,7 @@ __global__ __launch_bounds__(256) void rm_dist_mask_init_kernel(uint32_t n, cons
 template <uint32_t CLS, uint32_t MARK>
 __global__ __launch_bounds__(256) void rm_dist_compose_kernel(uint32_t n, const uint32_t* __restrict__ vol, const uint32_t* __restrict__ feat,
                                                               uint32_t r2, uint8_t* __restrict__ mask, unsigned long long* __restrict__ rows) {
-    __shared__ unsigned long long wred[12];
+    __shared__ unsigned long long wred[4];
     unsigned long long sums = 0ull;
 #pragma unroll
     for (uint32_t m = 0; m < kDistBlock / 256u; m++) {
@@ -260,7 +225,7 @@ __global__ __launch_bounds__(256) void rm_dist_compose_kernel(uint32_t n, const 
             sums += 1ull << 32;
         }
     }
-    dist_block_row(sums, 0ull, 0ull, wred, rows);
+    block_row<32, 32>(sums, wred, rows);  // (two counts of at most 2048)
 }
 
 }  // namespace rmk

@@ -14,7 +14,7 @@
 //   border    one lane per word: bit 63 with bit 0 of the next word, and the first row of a tile with the row before it, one
 //             union per common run, by topo_unite (rm_topo_union.h) in device memory.  Never across layers
 //   roots     every inside point at or above the plate is hung below its root; block sums of the root flags
-//   scan      rm_sparse_scan_kernel; the host reads REGIONS and allocates the table
+//   scan      rm_block_scan_kernel; the host reads REGIONS and allocates the table
 //   rank      the roots' numbers into `lab`, LAYER and FIRST into their rows, and per layer the regions before it
 //   spread    lab[p] = lab[root of p], 0 for every other point
 //   rows      one lane per word, a step per run: POINTS, SUPPORTED, the sums and the box by 32-bit integer atomics; per layer
@@ -25,6 +25,7 @@
 //   compose   labels and mask in the caller's frame (with pack, the only pass that knows it)
 #pragma once
 #include "rm_lds_layout.h"
+#include "rm_reduce.h"
 #include "rm_support.h"
 
 namespace rmk {
@@ -183,8 +184,7 @@ __global__ __launch_bounds__(256) void rm_isl_rows_kernel(SupFrame f, uint32_t p
         over = ov[h * ncw + cw];
     }
     uint32_t inside = (uint32_t)__popcll(word);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) inside += (uint32_t)__shfl_xor((int)inside, o, 64);
+    inside = wave_sum(inside);
     if ((threadIdx.x & 63u) == 0u && inside != 0u) atomicAdd(profile + 4u * h, inside);
     if (h < h0) return;
     const uint32_t v = cw / f.nw, w = cw - v * f.nw;

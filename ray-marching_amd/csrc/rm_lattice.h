@@ -10,6 +10,7 @@
 // of its planes inside the brick whose (t, axis) lies before E, a count that a binary search over at most 7 planes finds.
 #pragma once
 #include "rm_query.h"
+#include "rm_reduce.h"
 #include "rm_lattice_walk.h"
 
 #ifndef RM_LAT_SKIP
@@ -48,11 +49,8 @@ __global__ __launch_bounds__(256) void rm_lat_pack_kernel(uint32_t nx, uint32_t 
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        points += __shfl_xor(points, o);
-        fresh += __shfl_xor(fresh, o);
-    }
+    points = wave_sum(points);
+    fresh = wave_sum(fresh);
     if ((threadIdx.x & 63u) == 0u) {
         if (points) atomicAdd(&counters[LAT_N_POINTS], (unsigned long long)points);
         if (fresh) atomicAdd(&counters[LAT_N_BRICKS], (unsigned long long)fresh);

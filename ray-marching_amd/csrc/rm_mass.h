@@ -7,26 +7,17 @@
 // moments of its index box, otherwise nothing.  The passes:
 //   probe    one lane per brick: the decision of sparse_probe_brick (the mesh's, expression for expression); the keep flag for
 //            rm_sparse_compact_kernel; block sums with the kept bricks in the low half and the inside bricks in the high half
-//            (rm_sparse_scan_kernel scans both); the inside bricks' moments, reduced to ONE row of 16 u64 per workgroup.
+//            (rm_block_scan_kernel scans both); the inside bricks' moments, reduced to ONE row of 16 u64 per workgroup.
 //   count    one workgroup per kept brick, two own points per thread: query_distance, moments in brick-local coordinates 0..7
 //            (every local sum is below 2^15: two to a 32-bit word), reduced by shuffles and across the waves through LDS,
 //            shifted to lattice coordinates once in u64; one row per kept brick.  No tile, no distance goes to memory.
-//   reduce   one workgroup: the rows of both -> 16 u64 (sums for entries 0-9, minima for 10-12, maxima for 13-15).
-// Rows plus a reducer instead of 64-bit atomics: nothing to zero, no contention, and no atomic decides a result.  The one
-// atomic adds up a statistic (evaluations), as in section 15.
+//   reduce   rm_rows_reduce_kernel (rm_reduce.h, whose row protocol this is), one workgroup: the rows of both -> 16 u64.
+// The one atomic adds up a statistic (evaluations), as in section 15.
 #pragma once
 #include "rm_mesh_sparse.h"
+#include "rm_reduce.h"
 
 namespace rmk {
-
-constexpr uint32_t kMoments = 16u;  // RM_MOMENTS: one row
-constexpr unsigned long long kMassNoMin = 0xFFFFFFFFull;  // the minimum of an empty set (the maximum is 0)
-
-// An entry of a row: 0-9 sums, 10-12 minima, 13-15 maxima.
-RM_DEV unsigned long long mass_combine(uint32_t e, unsigned long long a, unsigned long long b) {
-    return e < 10u ? a + b : e < 13u ? (a < b ? a : b) : (a > b ? a : b);
-}
-RM_DEV unsigned long long mass_identity(uint32_t e) { return e >= 10u && e < 13u ? kMassNoMin : 0ull; }
 
 // sum of i and of i^2 over [i0, i0 + n), n in 1..8, i0 < 4096: below 2^27
 RM_DEV void mass_axis_sums(uint32_t i0, uint32_t n, unsigned long long& s1, unsigned long long& s2) {
@@ -43,13 +34,13 @@ __global__ __launch_bounds__(256) void rm_mass_probe_kernel(QueryLaunch Q, Spars
                                                             uint32_t* __restrict__ keep, unsigned long long* __restrict__ block_sums,
                                                             unsigned long long* __restrict__ rows) {
     __shared__ unsigned long long wsum[4];
-    __shared__ unsigned long long wrow[4][kMoments];
+    __shared__ unsigned long long wrow[4][kRowWords];
     static_assert(sizeof wsum + sizeof wrow <= rml::kQueryOwnBrick, "the static LDS the host counts in front of the query columns");
     const uint32_t b = blockIdx.x * 256u + threadIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     uint32_t k = 0u, in = 0u;
-    unsigned long long m[kMoments];
+    unsigned long long m[kRowWords];
 #pragma unroll
-    for (uint32_t e = 0; e < kMoments; e++) m[e] = mass_identity(e);
+    for (uint32_t e = 0; e < kRowWords; e++) m[e] = row_identity(e);
     if (b < g.nb) {
         const SparseBrick B = sparse_brick(g, b);
         float v;
@@ -73,23 +64,22 @@ __global__ __launch_bounds__(256) void rm_mass_probe_kernel(QueryLaunch Q, Spars
     if (b <= g.nb) keep[b] = k;
     if (__ballot(in) != 0ull) {  // wave-uniform: most waves hold no inside brick
 #pragma unroll
-        for (uint32_t e = 0; e < kMoments; e++)
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) m[e] = mass_combine(e, m[e], __shfl_xor(m[e], o, 64));
+        for (uint32_t e = 0; e < kRowWords; e++)
+            m[e] = wave_reduce<64>(m[e], [e](unsigned long long a, unsigned long long b) { return row_combine(e, a, b); });
     }
     if (lane == 0u) {
 #pragma unroll
-        for (uint32_t e = 0; e < kMoments; e++) wrow[wave][e] = m[e];
+        for (uint32_t e = 0; e < kRowWords; e++) wrow[wave][e] = m[e];
     }
     unsigned long long total;
     (void)block_exclusive_sum<4>((unsigned long long)k | (unsigned long long)in << 32, wsum, total);  // (its barriers order wrow)
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-    if (threadIdx.x < kMoments) {
+    if (threadIdx.x < kRowWords) {
         const uint32_t e = threadIdx.x;
         unsigned long long r = wrow[0][e];
 #pragma unroll
-        for (uint32_t w = 1; w < 4u; w++) r = mass_combine(e, r, wrow[w][e]);
-        rows[(size_t)blockIdx.x * kMoments + e] = r;
+        for (uint32_t w = 1; w < 4u; w++) r = row_combine(e, r, wrow[w][e]);
+        rows[(size_t)blockIdx.x * kRowWords + e] = r;
     }
 }
 
@@ -129,15 +119,8 @@ __global__ __launch_bounds__(256) void rm_mass_count_kernel(QueryLaunch Q, Spars
     uint32_t w3 = snn | (il * jl * cnt) << 16;          // sum n^2, sum l m
     uint32_t w4 = (jl * sn) | (il * sn) << 16;          // sum m n, sum l n
     uint32_t w5 = kbits | (cnt ? (1u << il) | (1u << (8u + jl)) : 0u);  // which l, m, n occur: bits 0-7, 8-15, 16-23
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        w0 += __shfl_xor(w0, o, 64);
-        w1 += __shfl_xor(w1, o, 64);
-        w2 += __shfl_xor(w2, o, 64);
-        w3 += __shfl_xor(w3, o, 64);
-        w4 += __shfl_xor(w4, o, 64);
-        w5 |= __shfl_xor(w5, o, 64);
-    }
+    w0 = wave_sum(w0); w1 = wave_sum(w1); w2 = wave_sum(w2); w3 = wave_sum(w3); w4 = wave_sum(w4);
+    w5 = wave_or(w5);
     if ((threadIdx.x & 63u) == 0u) {
         wred[wave][0] = w0; wred[wave][1] = w1; wred[wave][2] = w2; wred[wave][3] = w3; wred[wave][4] = w4; wred[wave][5] = w5;
     }
@@ -154,7 +137,7 @@ __global__ __launch_bounds__(256) void rm_mass_count_kernel(QueryLaunch Q, Spars
         const unsigned long long n = w0 & 0xFFFFu, sl = w0 >> 16, sm = w1 & 0xFFFFu, sN = w1 >> 16, sll = w2 & 0xFFFFu, smm = w2 >> 16,
                                  sNN = w3 & 0xFFFFu, slm = w3 >> 16, smn = w4 & 0xFFFFu, sln = w4 >> 16;
         const unsigned long long i0 = B.i0, j0 = B.j0, k0 = B.k0;
-        unsigned long long* row = rows + (size_t)c * kMoments;
+        unsigned long long* row = rows + (size_t)c * kRowWords;
         row[0] = n;
         row[1] = i0 * n + sl;
         row[2] = j0 * n + sm;
@@ -174,37 +157,6 @@ __global__ __launch_bounds__(256) void rm_mass_count_kernel(QueryLaunch Q, Spars
         row[14] = any ? j0 + (31u - (uint32_t)__builtin_clz(bm | 1u)) : 0ull;
         row[15] = any ? k0 + (31u - (uint32_t)__builtin_clz(bn | 1u)) : 0ull;
         atomicAdd(evaluations, (unsigned long long)(ex * ey * ez));  // a statistic: nothing depends on it
-    }
-}
-
-// ---- reduce -----------------------------------------------------------------------------------------------------------------
-// out[16] = the rows a[0, na) and b[0, nb) combined entry by entry.  Thread t takes entry t & 15 of the rows t >> 4, + 16, ...
-// (16 threads read one row: 128 contiguous bytes).
-__global__ __launch_bounds__(256) void rm_mass_reduce_kernel(const unsigned long long* __restrict__ a, uint32_t na,
-                                                             const unsigned long long* __restrict__ b, uint32_t nb,
-                                                             unsigned long long* __restrict__ out) {
-    __shared__ unsigned long long part[16][kMoments];
-    const uint32_t e = threadIdx.x & 15u, grp = threadIdx.x >> 4;
-    unsigned long long sum = 0ull, lo = kMassNoMin, hi = 0ull;
-    for (uint32_t r = grp; r < na; r += 16u) {
-        const unsigned long long v = a[(size_t)r * kMoments + e];
-        sum += v;
-        lo = v < lo ? v : lo;
-        hi = v > hi ? v : hi;
-    }
-    for (uint32_t r = grp; r < nb; r += 16u) {
-        const unsigned long long v = b[(size_t)r * kMoments + e];
-        sum += v;
-        lo = v < lo ? v : lo;
-        hi = v > hi ? v : hi;
-    }
-    part[grp][e] = e < 10u ? sum : e < 13u ? lo : hi;
-    __syncthreads();
-    if (threadIdx.x < kMoments) {
-        unsigned long long r = part[0][e];
-#pragma unroll
-        for (uint32_t q = 1; q < 16u; q++) r = mass_combine(e, r, part[q][e]);
-        out[e] = r;
     }
 }
 

@@ -12,6 +12,7 @@
 // redo their block's local scan on top of that offset.  Every order is fixed by the lattice: no atomics, identical runs.
 #pragma once
 #include "rm_query.h"
+#include "rm_reduce.h"
 
 namespace rmk {
 
@@ -156,40 +157,8 @@ __global__ __launch_bounds__(256) void rm_grid_dist_kernel(QueryLaunch Q, float 
     out[p] = query_distance<LOOP>(Q, spill, grid_coord(ox, i, sx), grid_coord(oy, j, sy), grid_coord(oz, k, sz));
 }
 
-// ---- scans ---------------------------------------------------------------------------------------------------------------
-// Inclusive scan across the 64 lanes of a wave (__shfl_up: the compiler places the cross-lane moves and their waits).
-template <class T>
-RM_DEV T wave_inclusive_sum(T x) {
-    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-#pragma unroll
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-        const T y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    return x;
-}
-
-// Exclusive scan across a workgroup of WAVES waves; `total` gets the sum of all.  wsum: WAVES words of LDS.  Ends with a
-// barrier, so wsum may be reused by the next call.
-template <int WAVES, class T>
-RM_DEV T block_exclusive_sum(T v, T* wsum, T& total) {
-    const T inc = wave_inclusive_sum(v);
-    const uint32_t w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 63u) wsum[w] = inc;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < WAVES; q++) {
-        const T s = wsum[q];
-        before += (uint32_t)q < w ? s : (T)0;
-        all += s;
-    }
-    total = all;
-    __syncthreads();
-    return before + inc - v;
-}
-
 // ---- extraction: count, scan, emit ---------------------------------------------------------------------------------------
+// (wave_inclusive_sum and block_exclusive_sum: rm_reduce.h)
 // Each 256-thread workgroup owns kMeshBlock consecutive lattice points, each thread kMeshPer of them in a row.
 constexpr uint32_t kMeshPer = 8, kMeshBlock = 256u * kMeshPer;
 constexpr uint8_t kMeshInside = 8u;  // flags byte: bits 0-2 the crossing edges along x, y, z from this point; bit 3 inside

@@ -7,7 +7,7 @@
 //   probe    one lane per brick: map_scene at the tile's centre; the brick is kept unless |v - level| exceeds
 //            L * radius + 2 E (L: the program's Lipschitz bound, E: the bound on the binary32 evaluation's error), in
 //            which case every point of the tile is on the same side of `level`.  Block sums of the keep flags.
-//   scan     rm_sparse_scan_kernel, one workgroup: block sums -> offsets, the totals as 64-bit numbers.
+//   scan     rm_block_scan_kernel (rm_reduce.h), one workgroup: block sums -> offsets, the totals as 64-bit numbers.
 //   compact  the kept bricks in linear order (klist), and for every brick the number of kept bricks before it (boff).
 //   count    one workgroup per kept brick: the tile's distances (query_distance, the bit patterns the dense path computes)
 //            into LDS and into the brick's tile in device memory; per row segment (the 8 points of the brick that share
@@ -19,6 +19,7 @@
 // Every order is fixed by the lattice.  The one atomic adds up a statistic (evaluations) and decides nothing.
 #pragma once
 #include "rm_mesh.h"
+#include "rm_reduce.h"
 
 namespace rmk {
 
@@ -94,33 +95,6 @@ __global__ __launch_bounds__(256) void rm_sparse_probe_kernel(QueryLaunch Q, Spa
     unsigned long long total;
     (void)block_exclusive_sum<4>((unsigned long long)k, wsum, total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-
-// Block sums packed lo | hi << 32 -> exclusive offsets in place (each half modulo 2^32), by one 1024-thread workgroup; the
-// two totals as 64-bit numbers, so that a sum that does not fit 32 bits is seen.
-__global__ __launch_bounds__(1024) void rm_sparse_scan_kernel(unsigned long long* __restrict__ block_sums, uint32_t n_blocks,
-                                                              unsigned long long* __restrict__ totals) {
-    __shared__ unsigned long long wsum[16];
-    const uint32_t per = (n_blocks + 1023u) / 1024u, b0 = min(threadIdx.x * per, n_blocks), b1 = min(b0 + per, n_blocks);
-    unsigned long long lo = 0, hi = 0;
-    for (uint32_t b = b0; b < b1; b++) {
-        const unsigned long long v = block_sums[b];
-        lo += v & 0xFFFFFFFFull;
-        hi += v >> 32;
-    }
-    unsigned long long tlo, thi;
-    unsigned long long olo = block_exclusive_sum<16>(lo, wsum, tlo);
-    unsigned long long ohi = block_exclusive_sum<16>(hi, wsum, thi);
-    for (uint32_t b = b0; b < b1; b++) {
-        const unsigned long long v = block_sums[b];
-        block_sums[b] = (olo & 0xFFFFFFFFull) | (ohi << 32);
-        olo += v & 0xFFFFFFFFull;
-        ohi += v >> 32;
-    }
-    if (threadIdx.x == 0) {
-        totals[0] = tlo;
-        totals[1] = thi;
-    }
 }
 
 // keep[] -> boff[] in place (kept bricks before b; entry nb: all of them) and the list of the kept bricks.
@@ -207,9 +181,7 @@ __global__ __launch_bounds__(256) void rm_sparse_count_kernel(QueryLaunch Q, Spa
         unsigned long long entry;
         const uint32_t f = sparse_point(g, B, tile, level, il, jl, kl, entry);
         uint32_t w = (f & 7u) << (3u * il) | (uint32_t)(entry & 15ull) << 24;  // disjoint fields: the sum is the union
-        w += __shfl_xor(w, 1, 64);
-        w += __shfl_xor(w, 2, 64);
-        w += __shfl_xor(w, 4, 64);
+        w = wave_sum<8>(w);
         if (il == 0u) seg_words[m.base + kl * m.stride_k + jl * m.stride_j] = w;
     }
 }

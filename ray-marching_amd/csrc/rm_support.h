@@ -26,6 +26,7 @@
 //   compose   the four planes -> the mask's bytes
 #pragma once
 #include "rm_lds_layout.h"
+#include "rm_reduce.h"
 #include "rm_topology.h"
 
 namespace rmk {
@@ -100,8 +101,7 @@ __global__ __launch_bounds__(256) void rm_sup_pack_kernel(SupFrame f, uint32_t n
         }
         if (plate == kSupPlateAuto) {
             uint32_t hm = live && word != 0ull ? h : kSupPlateAuto;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) hm = min(hm, (uint32_t)__shfl_xor((int)hm, o, 64));
+            hm = wave_min(hm);
             if (lane == 0u && hm != kSupPlateAuto) sup_note_height(h0w, hm);
         }
     }
@@ -199,8 +199,7 @@ __global__ __launch_bounds__(256) void rm_sup_count_kernel(uint32_t ncw, uint32_
     }
 #pragma unroll
     for (int k = 0; k < 6; k++) {
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) c[k] += (uint32_t)__shfl_xor((int)c[k], o, 64);
+        c[k] = wave_sum(c[k]);
         if ((threadIdx.x & 63u) == 0u) s_red[threadIdx.x >> 6][k] = c[k];
     }
     __syncthreads();

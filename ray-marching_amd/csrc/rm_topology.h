@@ -1,6 +1,6 @@
 // rm_topology.h -- solid topology (rm_label_solid, rm_label_occupancy): the connected components of the occupancy lattice
 // {d < level} -- bodies under 6-adjacency, voids under 26-adjacency, cavities the voids that do not reach the border --, their
-// canonical numbers, sixteen moments per component and the Euler characteristic.  Included by rm_abi.hip alone, after rm_mass.h.
+// canonical numbers, sixteen moments per component and the Euler characteristic.  Included by rm_abi.hip alone.
 // DESIGN.md section 19 is the contract; every output is an integer that no order of execution changes.
 //
 // The lattice is cut into the bricks of rm_mesh_sparse.h.  The passes:
@@ -17,15 +17,16 @@
 //              other access a relaxed agent-scope atomic load.  No workgroup waits for another; a stale parent is still a smaller
 //              member of the same component.
 //   flatten    parent[p] = its root.   verify: per brick the adjacent same-class pairs whose roots differ (a row per brick, folded
-//              256 to a workgroup, then the mass reducer); the host repeats merge and flatten while that count is not zero
+//              and reduced as rm_reduce.h has it); the host repeats merge and flatten while that count is not zero
 //              (expected: never).
 //   exterior   every outside point on the lattice's border marks its root's byte (plain stores of the same value).
-//   number     roots in linear order: block sums, rm_sparse_scan_kernel, ranks -> the label of each root in the label volume.
+//   number     roots in linear order: block sums, rm_block_scan_kernel, ranks -> the label of each root in the label volume.
 //   rows       per point its root's label into the label volume; the moments reduced over the lanes of a wave that share a root,
 //              then one 64-bit integer atomic per entry per root per wave (integer and commutative: no word depends on arrival
-//              order); V, E, F, K and the exterior's points from the occupancy alone, one row per brick + the mass reducer.
+//              order); V, E, F, K and the exterior's points from the occupancy alone, one row per brick + the row reducer.
 #pragma once
-#include "rm_mass.h"
+#include "rm_mesh_sparse.h"
+#include "rm_reduce.h"
 #include "rm_topo_union.h"
 
 namespace rmk {
@@ -211,39 +212,6 @@ __global__ __launch_bounds__(256) void rm_topo_flatten_kernel(uint32_t n, uint32
     __hip_atomic_store(parent + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (others walk through p meanwhile)
 }
 
-// One row of 16 words per brick for rm_mass_reduce_kernel: entries 0..4 from `v` (fields of 12 bits, the last of 16), the rest
-// the identities.  wred: 4 words of LDS.
-RM_DEV void topo_brick_row(unsigned long long v, unsigned long long* wred, unsigned long long* __restrict__ rows) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63u) == 0u) wred[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x < kMoments) {
-        const uint32_t e = threadIdx.x;
-        const unsigned long long all = wred[0] + wred[1] + wred[2] + wred[3];
-        rows[(size_t)blockIdx.x * kMoments + e] = e < 5u ? (all >> (12u * e)) & (e == 4u ? 0xFFFFull : 0xFFFull) : mass_identity(e);
-    }
-}
-
-// The bricks' rows, 256 to a workgroup, combined entry by entry into folded[16 block]: rm_mass_reduce_kernel (one workgroup) then
-// reads one row per 256 bricks.  Thread t takes entry t & 15 of the rows t >> 4, + 16, ... as there.
-constexpr uint32_t kTopoFold = 256u;
-__global__ __launch_bounds__(256) void rm_topo_fold_kernel(const unsigned long long* __restrict__ rows, uint32_t n_rows,
-                                                           unsigned long long* __restrict__ folded) {
-    __shared__ unsigned long long part[16][kMoments];
-    const uint32_t e = threadIdx.x & 15u, grp = threadIdx.x >> 4, r0 = blockIdx.x * kTopoFold, r1 = min(r0 + kTopoFold, n_rows);
-    unsigned long long acc = mass_identity(e);
-    for (uint32_t r = r0 + grp; r < r1; r += 16u) acc = mass_combine(e, acc, rows[(size_t)r * kMoments + e]);
-    part[grp][e] = acc;
-    __syncthreads();
-    if (threadIdx.x < kMoments) {
-        unsigned long long r = part[0][e];
-#pragma unroll
-        for (uint32_t q = 1; q < 16u; q++) r = mass_combine(e, r, part[q][e]);
-        folded[(size_t)blockIdx.x * kMoments + e] = r;
-    }
-}
-
 // rows[16 b + 4]: the pairs (p, preceding same-class neighbour) of brick b's points whose roots differ, after flatten.
 __global__ __launch_bounds__(256) void rm_topo_verify_kernel(SparseGrid g, const uint8_t* __restrict__ occ, const uint32_t* __restrict__ parent,
                                                              unsigned long long* __restrict__ rows) {
@@ -261,7 +229,7 @@ __global__ __launch_bounds__(256) void rm_topo_verify_kernel(SparseGrid g, const
             if ((occ[q] != 0u) == c && parent[q] != r) bad++;
         });
     }
-    topo_brick_row((unsigned long long)bad << 48, wred, rows);  // entry 4, the 16-bit field: at most 13 x 512 per brick
+    block_row<12, 12, 12, 12, 16>((unsigned long long)bad << 48, wred, rows);  // entry 4, the 16-bit field: at most 13 x 512 per brick
 }
 
 // ---- exterior ---------------------------------------------------------------------------------------------------------------
@@ -315,7 +283,7 @@ __global__ __launch_bounds__(256) void rm_topo_rank_kernel(uint32_t n, const uin
 // ---- rows and counts --------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rm_topo_rows_init_kernel(uint32_t n_rows, unsigned long long* __restrict__ rows) {
     const uint32_t w = blockIdx.x * 256u + threadIdx.x;
-    if (w < n_rows * kMoments) rows[w] = mass_identity(w & 15u);
+    if (w < n_rows * kRowWords) rows[w] = row_identity(w & 15u);
 }
 
 // comp_rows: the bodies' rows, then the cavities' (n_bodies rows before them).  count_rows[16 b]: V, E, F, K and the exterior's
@@ -361,14 +329,9 @@ __global__ __launch_bounds__(256) void rm_topo_rows_kernel(SparseGrid g, const u
             uint32_t w1 = (t.jl * cnt) | (t.il * t.il * cnt) << 16;        // sum m, sum l^2
             uint32_t w2 = (t.jl * t.jl * cnt) | (t.il * t.jl * cnt) << 16;  // sum m^2, sum l m
             uint32_t w3 = mine ? (1u << t.il) | (1u << (8u + t.jl)) : 0u;   // which l, m occur
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                w0 += __shfl_xor(w0, o, 64);
-                w1 += __shfl_xor(w1, o, 64);
-                w2 += __shfl_xor(w2, o, 64);
-                w3 |= __shfl_xor(w3, o, 64);
-            }
-            if (lane < kMoments) {  // lane e: entry e of the row
+            w0 = wave_sum(w0); w1 = wave_sum(w1); w2 = wave_sum(w2);
+            w3 = wave_or(w3);
+            if (lane < kRowWords) {  // lane e: entry e of the row
                 const unsigned long long n = w0 & 0xFFFFu, sl = w0 >> 16, sm = w1 & 0xFFFFu, sll = w1 >> 16, smm = w2 & 0xFFFFu, slm = w2 >> 16;
                 const unsigned long long i0 = B.i0, j0 = B.j0, k = t.k;
                 const unsigned long long sx = i0 * n + sl, sy = j0 * n + sm;
@@ -392,7 +355,7 @@ __global__ __launch_bounds__(256) void rm_topo_rows_kernel(SparseGrid g, const u
                     default: v = k; break;  // 12, 15
                 }
                 const size_t row = (key & kTopoCavityBit) ? (size_t)n_bodies + (key & ~kTopoCavityBit) : (size_t)key;
-                unsigned long long* dst = comp_rows + row * kMoments + lane;
+                unsigned long long* dst = comp_rows + row * kRowWords + lane;
                 if (lane < 10u) atomicAdd(dst, v);
                 else if (lane < 13u) atomicMin(dst, v);
                 else atomicMax(dst, v);
@@ -401,7 +364,8 @@ __global__ __launch_bounds__(256) void rm_topo_rows_kernel(SparseGrid g, const u
             pending = __ballot(active);
         }
     }
-    topo_brick_row(counts, wred, count_rows);
+    // a brick has 512 points, each counted at most 1, 3, 3 and 1 time in the fields of 12 bits and once in the last, of 16
+    block_row<12, 12, 12, 12, 16>(counts, wred, count_rows);
 }
 
 }  // namespace rmk

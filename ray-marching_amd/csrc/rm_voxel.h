@@ -9,19 +9,17 @@
 //   setup   one lane per triangle: gather, snap, reject, orient, the box of lattice rows its projection can reach and the number
 //           of work items of 64 rows in it; a box of at most kVoxSmallRows rows is finished by the lane itself (no items).  The
 //           record (12 words) and the items before the triangle in its block of 256; the block's sum for the scan
-//           (rm_sparse_scan_kernel); TRIANGLES, REJECTED, EDGE_ON and the lanes' crossings by one atomic add per wave.
+//           (rm_block_scan_kernel); TRIANGLES, REJECTED, EDGE_ON and the lanes' crossings by one atomic add per wave.
 //   raster  one wave per work item, found by binary search over the blocks' offsets and then the block's 256 entries; one lane
 //           per row of the box.  The 64-bit divide runs in admitted lanes only.
 //   fill    a workgroup makes kVoxFillCells consecutive bytes of the occupancy: the bit words of the rows they lie in staged
 //           in LDS (rml::VoxFillLds), each word's inclusive prefix XOR and the parity of the row's words before it, then 16
-//           bytes per lane.  INSIDE and OPEN_ROWS into one row of 16 words per workgroup (rm_topo_fold_kernel,
-//           rm_mass_reduce_kernel).
+//           bytes per lane.  INSIDE and OPEN_ROWS into one row of 16 words per workgroup (rm_reduce.h).
 // No kernel reads what another workgroup of its launch wrote; the atomics only accumulate and are read by the next launch.
 #pragma once
 #include "rm_device.h"
 #include "rm_lds_layout.h"
-#include "rm_mesh.h"
-#include "rm_mass.h"
+#include "rm_reduce.h"
 
 namespace rmk {
 
@@ -69,12 +67,6 @@ RM_DEV bool vox_cross_row(const int (&q)[9], long long A2, uint32_t j, uint32_t 
     if (num > 0) t = num > den * (long long)(g.nx - 1u) ? g.nx : (uint32_t)(((unsigned long long)num + (unsigned long long)den - 1ull) / (unsigned long long)den);
     atomicXor(bits + (size_t)(j + g.ny * k) * g.row_words + (t >> 5), 1u << (t & 31u));
     return true;
-}
-
-RM_DEV uint32_t vox_wave_sum(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
 }
 
 // ---- setup ----------------------------------------------------------------------------------------------------------------
@@ -147,7 +139,7 @@ __global__ __launch_bounds__(256) void rm_vox_setup_kernel(VoxLattice g, uint32_
     if (threadIdx.x == 0u) block_sums[blockIdx.x] = total;
     // the counts: one add per wave and count
     const uint32_t n_live = (uint32_t)__popcll(__ballot(live)), n_rej = (uint32_t)__popcll(__ballot(live && !ok)),
-                   n_edge = (uint32_t)__popcll(__ballot(edge_on)), n_cross = vox_wave_sum(crossings);
+                   n_edge = (uint32_t)__popcll(__ballot(edge_on)), n_cross = wave_sum(crossings);
     if ((threadIdx.x & 63u) == 0u) {
         if (n_live) atomicAdd(counters + VOX_N_TRIANGLES, (unsigned long long)n_live);
         if (n_rej) atomicAdd(counters + VOX_N_REJECTED, (unsigned long long)n_rej);
@@ -203,7 +195,7 @@ __global__ __launch_bounds__(256) void rm_vox_raster_kernel(VoxLattice g, uint32
 __global__ __launch_bounds__(256) void rm_vox_fill_kernel(uint32_t nx, uint32_t n, const uint32_t* __restrict__ bits, uint8_t* __restrict__ occ,
                                                           unsigned long long* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) unsigned char vox_smem[];
-    __shared__ uint32_t wred[4][2];
+    __shared__ unsigned long long wred[4];
     constexpr rml::VoxFillLds L;
     uint32_t* s_raw = reinterpret_cast<uint32_t*>(vox_smem + L.raw);
     uint32_t* s_pre = reinterpret_cast<uint32_t*>(vox_smem + L.prefix);
@@ -249,15 +241,7 @@ __global__ __launch_bounds__(256) void rm_vox_fill_kernel(uint32_t nx, uint32_t 
             for (uint32_t e = 0; p + e < p1; e++) occ[p + e] = (uint8_t)(out[e >> 2] >> (8u * (e & 3u)));
         }
     }
-    inside = vox_wave_sum(inside);
-    open = vox_wave_sum(open);
-    if ((t & 63u) == 0u) wred[t >> 6][0] = inside, wred[t >> 6][1] = open;
-    __syncthreads();
-    if (t < kMoments) {
-        unsigned long long v = 0ull;
-        if (t < 2u) v = (unsigned long long)wred[0][t] + wred[1][t] + wred[2][t] + wred[3][t];
-        rows[(size_t)blockIdx.x * kMoments + t] = v;
-    }
+    block_row<32, 32>((unsigned long long)inside | (unsigned long long)open << 32, wred, rows);  // (4096 cells: far below 2^32 each)
 }
 
 }  // namespace rmk
