@@ -367,6 +367,30 @@ pub const RM_LAT_STATS: c_int = 6;
 /// The face word of a cast whose origin lies inside a full cube.
 pub const RM_LAT_FACE_NONE: u32 = 6;
 
+// Lattice meshing (rm_mesh_classes / rm_read_class_mesh).
+// enum rm_cmeshcount: indices into the counts of a class mesh; RM_CMESH_COUNTS is their number
+pub const RM_CMESH_VERTICES: c_int = 0;
+pub const RM_CMESH_TRIANGLES: c_int = 1;
+pub const RM_CMESH_FACES: c_int = 2;
+pub const RM_CMESH_FACES_POS_X: c_int = 3;
+pub const RM_CMESH_FACES_NEG_X: c_int = 4;
+pub const RM_CMESH_FACES_POS_Y: c_int = 5;
+pub const RM_CMESH_FACES_NEG_Y: c_int = 6;
+pub const RM_CMESH_FACES_POS_Z: c_int = 7;
+pub const RM_CMESH_FACES_NEG_Z: c_int = 8;
+pub const RM_CMESH_EDGES: c_int = 9;
+pub const RM_CMESH_OPEN_EDGES: c_int = 10;
+pub const RM_CMESH_BRANCH_EDGES: c_int = 11;
+pub const RM_CMESH_COUNTS: c_int = 12;
+// enum rm_cmeshstat: indices into the statistics of a class mesh; RM_CMESH_STATS is their number
+pub const RM_CMESH_STAT_BRICKS: c_int = 0;
+pub const RM_CMESH_STAT_BRICKS_KEPT: c_int = 1;
+pub const RM_CMESH_STAT_BRICKS_INSIDE: c_int = 2;
+pub const RM_CMESH_STAT_EVALUATIONS: c_int = 3;
+pub const RM_CMESH_STAT_RETAINED_BYTES: c_int = 4;
+pub const RM_CMESH_STAT_SCRATCH_BYTES: c_int = 5;
+pub const RM_CMESH_STATS: c_int = 6;
+
 /// The index of `PAIR[a][b][nu]` in the counts of a surface call (the header's `RM_SURF_PAIR`).
 pub const fn surf_pair(a: usize, b: usize, nu: usize) -> usize {
     8 + (8 * a + b) * 13 + nu
@@ -510,6 +534,11 @@ extern "C" {
                            out_is_device: c_int, stream: *mut c_void) -> c_int;
     pub fn rm_cast_lattice(ctx: *mut rm_ctx, n: u32, rays: *const f32, window: *const u32, out_hit: *mut f32, out_ids: *mut u32,
                            out_rgb: *mut f32, is_device: c_int, stream: *mut c_void) -> c_int;
+    pub fn rm_mesh_classes(ctx: *mut rm_ctx, nx: u32, ny: u32, nz: u32, classes: *const c_void, is_device: c_int, stream: *mut c_void,
+                           origin: *const f32, step: *const f32, mask_a: u32, mask_b: u32, out_counts: *mut u64, n_counts: u32,
+                           out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_read_class_mesh(ctx: *mut rm_ctx, out_vertices: *mut f32, out_triangles: *mut u32, out_ids: *mut u32, is_device: c_int,
+                              stream: *mut c_void) -> c_int;
     pub fn rm_slice_contours(ctx: *mut rm_ctx, axis: u32, origin_uv: *const f32, step_uv: *const f32, nu: u32, nv: u32,
                              heights: *const f32, n_layers: u32, level: f32, flags: u32, out_counts: *mut u64,
                              n_counts: u32) -> c_int;
@@ -657,6 +686,8 @@ pub struct RayMarchingResources {
     islands: Cell<Option<(u64, u32, u64)>>,
     /// lattice points of the last successful `voxelize_mesh`: what `read_voxels` writes
     voxels: Cell<Option<u64>>,
+    /// (vertices, triangles) of the last successful `mesh_classes`: what `read_class_mesh` writes
+    class_mesh: Cell<Option<(u64, u64)>>,
 }
 
 unsafe impl Send for RayMarchingResources {} // a context may move between threads; it is not Sync
@@ -671,7 +702,8 @@ impl RayMarchingResources {
             return Err(RmError { status: rc, message: msg.to_string_lossy().into_owned() });
         }
         Ok(Self { ctx, mesh: Cell::new(None), slices: Cell::new(None), topology: Cell::new(None), distance: Cell::new(None),
-                  support: Cell::new(None), islands: Cell::new(None), voxels: Cell::new(None) })
+                  support: Cell::new(None), islands: Cell::new(None), voxels: Cell::new(None),
+                  class_mesh: Cell::new(None) })
     }
 
     fn check(&self, rc: c_int) -> Result<(), RmError> {
@@ -1032,6 +1064,44 @@ impl RayMarchingResources {
         self.check(unsafe { rm_cast_lattice(self.ctx, n as u32, rays.as_ptr(), w, hit, ids, rgb, 0, std::ptr::null_mut()) })
     }
 
+    /// The interface between two class sets of a lattice of class bytes as a welded, indexed triangle mesh (`rm_mesh_classes`;
+    /// DESIGN.md section 29): `classes` holds nx x ny x nz bytes in host memory, x fastest, class = min(byte, 7); `mask_a` and
+    /// `mask_b` are bit masks over the classes (non-empty, disjoint, no bit above 7).  The faces are the unit faces between a point
+    /// of A and a 6-neighbour of B on the lattice padded with one layer of class 0, wound counter-clockwise seen from the B side.
+    /// Fills `out_counts` (at least `RM_CMESH_COUNTS` entries indexed by `RM_CMESH_*`) and `out_stats` (at least `RM_CMESH_STATS`,
+    /// indexed by `RM_CMESH_STAT_*`).  The mesh stays in the context for `read_class_mesh`; no other retained result is touched.
+    /// Needs no program.
+    pub fn mesh_classes(&self, classes: &[u8], origin: [f32; 3], step: [f32; 3], nx: u32, ny: u32, nz: u32, mask_a: u32, mask_b: u32,
+                        out_counts: &mut [u64], out_stats: &mut [u64]) -> Result<(), RmError> {
+        assert!(classes.len() as u64 >= nx as u64 * ny as u64 * nz as u64, "mesh_classes: classes is shorter than the lattice");
+        assert!(out_counts.len() >= RM_CMESH_COUNTS as usize, "mesh_classes: out_counts is shorter than RM_CMESH_COUNTS entries");
+        assert!(out_stats.len() >= RM_CMESH_STATS as usize, "mesh_classes: out_stats is shorter than RM_CMESH_STATS entries");
+        let rc = unsafe {
+            rm_mesh_classes(self.ctx, nx, ny, nz, classes.as_ptr() as *const c_void, 0, std::ptr::null_mut(), origin.as_ptr(),
+                            step.as_ptr(), mask_a, mask_b, out_counts.as_mut_ptr(), RM_CMESH_COUNTS as u32, out_stats.as_mut_ptr(),
+                            RM_CMESH_STATS as u32)
+        };
+        if rc == RM_ERR_DEVICE {
+            self.class_mesh.set(None);  // a call that failed late has released the previous mesh
+        }
+        self.check(rc)?;
+        self.class_mesh.set(Some((out_counts[RM_CMESH_VERTICES as usize], out_counts[RM_CMESH_TRIANGLES as usize])));
+        Ok(())
+    }
+
+    /// The mesh of the last successful `mesh_classes`, as a `ClassMesh`.  `RM_ERR_ARG` before any.
+    pub fn read_class_mesh(&self) -> Result<ClassMesh, RmError> {
+        let (v, t) = match self.class_mesh.get() {
+            Some(vt) => (vt.0 as usize, vt.1 as usize),
+            None => return Err(RmError { status: RM_ERR_ARG, message: "read_class_mesh: no lattice has been meshed".to_string() }),
+        };
+        let mut m = ClassMesh { vertices: vec![0.0; 3 * v], triangles: vec![0; 3 * t], ids: vec![0; 2 * t] };
+        self.check(unsafe {
+            rm_read_class_mesh(self.ctx, m.vertices.as_mut_ptr(), m.triangles.as_mut_ptr(), m.ids.as_mut_ptr(), 0, std::ptr::null_mut())
+        })?;
+        Ok(m)
+    }
+
     /// The occupancy of the last successful `voxelize_mesh`: one byte per lattice point, 0 or 1, x fastest -- what
     /// `label_occupancy`, `distance_occupancy`, `support_occupancy`, `islands_occupancy` and `surface_classes` take.
     /// `RM_ERR_ARG` before any voxelisation.
@@ -1338,6 +1408,16 @@ pub struct Hit {
     pub normal: [f32; 3],
     pub diffuse: f32,
     pub rgb: [f32; 3],
+}
+
+/// A class mesh (`RayMarchingResources::read_class_mesh`): `vertices` three floats per vertex, `triangles` three vertex indices
+/// per triangle, `ids` two words per triangle -- class_A | class_B << 8 | face << 16 (face = 2 axis + (normal positive)), and
+/// the linear index of the face's A-side point (`RM_NO_ID` for padding).
+#[derive(Debug, Clone, PartialEq)]
+pub struct ClassMesh {
+    pub vertices: Vec<f32>,
+    pub triangles: Vec<u32>,
+    pub ids: Vec<u32>,
 }
 
 /// Output rows of strips `first`, `first + stride`, ... (`strip_rows` rows each; the frame's last strip may be ragged) of an

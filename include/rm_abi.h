@@ -828,6 +828,43 @@ int rm_draw_lattice(rm_ctx* ctx, uint32_t W, uint32_t H, uint32_t row0, uint32_t
 int rm_cast_lattice(rm_ctx* ctx, uint32_t n, const float* rays, const uint32_t* window, float* out_hit, uint32_t* out_ids,
                     float* out_rgb, int is_device, void* stream);
 
+/* Lattice meshing (extension; DESIGN.md section 29 is the contract, to the last bit): the interface between two class sets of a
+ * lattice of class bytes as a welded, indexed, consistently wound triangle mesh -- the unit faces that rm_surface_classes counts
+ * as PAIR[a][b][x|y|z] and rm_surface_measures measures as FACET_AREA, in a fixed order.  Needs no program.
+ * Lattice, bytes, is_device and stream as rm_surface_classes takes them (class = min(byte, 7), one layer of class-0 points
+ * around the lattice); origin and step as rm_set_lattice takes them; mask_a and mask_b as rm_surface_measures takes them
+ * (non-empty, disjoint, no bit above 7).
+ * Faces: a pair (p, p + e_a) of points of the padded lattice, a = x, y, z, is a face with normal +a when class(p) is in A and
+ * class(p + e_a) in B, with normal -a when the other way round.  Corners: (nx + 1)(ny + 1)(nz + 1), corner (ci, cj, ck) at index
+ * position (ci - 1/2, cj - 1/2, ck - 1/2), L = ci + (nx + 1)(cj + (ny + 1) ck); the face's lowest corner is p + e_a, its key
+ * 3 L + a.  Faces are ordered by key; vertices are the corners that a face touches, each once, ordered by L, at
+ * o + ((float)c - 0.5f) * s per axis (product and sum rounded once each, no fma).  Face f gives the triangles 2 f and 2 f + 1:
+ * with (u, v) the other two axes in cyclic order and q00, q10, q11, q01 the corners by their offsets in (u, v), (q00, q10, q11)
+ * and (q00, q11, q01) for a normal +a, (q00, q11, q10) and (q00, q01, q11) for -a: counter-clockwise seen from the B side.
+ * rm_read_class_mesh: out_vertices V x 3 floats, out_triangles T x 3 u32, out_ids T x 2 u32 -- word 0 is class_A | class_B << 8 |
+ * face << 16 (face = 2 axis + (normal positive ? 1 : 0), as rm_cast_lattice numbers faces), word 1 the linear index
+ * i + nx (j + ny k) of the face's A-side point, RM_NO_ID when that point is padding (only when class 0 is in A).  Any output may
+ * be NULL; device arrays need 4-byte alignment; an empty mesh is valid; the next producing call waits for a device read that is
+ * still running.
+ * out_counts[RM_CMESH_*]: VERTICES, TRIANGLES, FACES; FACES_POS_X .. FACES_NEG_Z; EDGES (corner-lattice edges with at least one
+ * face), OPEN_EDGES (with 1 or 3 faces: 0 whenever A and B together hold every class present), BRANCH_EDGES (with 3 or 4 faces:
+ * two voxels meet diagonally; the mesh is closed there but not 2-manifold).  V, T < 2^32: the lattice has at most 4.5 x 2^28
+ * faces.  out_stats[RM_CMESH_STAT_*]: the four brick statistics are 0, as for a caller's occupancy; RETAINED_BYTES, the device
+ * memory the mesh takes; SCRATCH_BYTES.  The call is synchronous on the context's own stream.  The mesh stays until the next
+ * rm_mesh_classes; no other retained result is dropped or replaced, and no other call replaces this one.
+ * Errors, every check before the first launch, outputs untouched and the previous class mesh still readable: rm_set_lattice's,
+ * in its order, with RM_CMESH_COUNTS and RM_CMESH_STATS; then RM_ERR_ARG for a bad mask.  RM_ERR_DEVICE when device memory runs
+ * out (no mesh is retained then).  rm_read_class_mesh: RM_ERR_ARG before any rm_mesh_classes. */
+enum rm_cmeshcount { RM_CMESH_VERTICES = 0, RM_CMESH_TRIANGLES = 1, RM_CMESH_FACES = 2, RM_CMESH_FACES_POS_X = 3, RM_CMESH_FACES_NEG_X = 4,
+                     RM_CMESH_FACES_POS_Y = 5, RM_CMESH_FACES_NEG_Y = 6, RM_CMESH_FACES_POS_Z = 7, RM_CMESH_FACES_NEG_Z = 8,
+                     RM_CMESH_EDGES = 9, RM_CMESH_OPEN_EDGES = 10, RM_CMESH_BRANCH_EDGES = 11, RM_CMESH_COUNTS = 12 };
+enum rm_cmeshstat { RM_CMESH_STAT_BRICKS = 0, RM_CMESH_STAT_BRICKS_KEPT = 1, RM_CMESH_STAT_BRICKS_INSIDE = 2, RM_CMESH_STAT_EVALUATIONS = 3,
+                    RM_CMESH_STAT_RETAINED_BYTES = 4, RM_CMESH_STAT_SCRATCH_BYTES = 5, RM_CMESH_STATS = 6 };
+int rm_mesh_classes(rm_ctx* ctx, uint32_t nx, uint32_t ny, uint32_t nz, const void* classes, int is_device, void* stream,
+                    const float* origin, const float* step, uint32_t mask_a, uint32_t mask_b, uint64_t* out_counts, uint32_t n_counts,
+                    uint64_t* out_stats, uint32_t n_stats);
+int rm_read_class_mesh(rm_ctx* ctx, float* out_vertices, uint32_t* out_triangles, uint32_t* out_ids, int is_device, void* stream);
+
 /* Slicing (extension; DESIGN.md section 16 is the contract, to the last bit): the closed outlines of the solid d < level in a
  * stack of planes, as ordered polylines -- what a slicer or a section drawing needs, evaluated directly on a 2-D lattice
  * per layer instead of through a triangle mesh.  From the program, limits and material table as they are at the call.

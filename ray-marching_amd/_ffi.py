@@ -125,6 +125,15 @@ LAT_COUNT_NAMES = ("points", "bricks")
  RM_LAT_STAT_SCRATCH_BYTES, RM_LAT_STATS) = range(7)
 LAT_STAT_NAMES = ("bricks", "bricks_kept", "bricks_inside", "evaluations", "retained_bytes", "scratch_bytes")
 RM_LAT_FACE_NONE = 6
+# lattice meshing (rm_mesh_classes / rm_read_class_mesh): enum rm_cmeshcount, enum rm_cmeshstat
+(RM_CMESH_VERTICES, RM_CMESH_TRIANGLES, RM_CMESH_FACES, RM_CMESH_FACES_POS_X, RM_CMESH_FACES_NEG_X, RM_CMESH_FACES_POS_Y,
+ RM_CMESH_FACES_NEG_Y, RM_CMESH_FACES_POS_Z, RM_CMESH_FACES_NEG_Z, RM_CMESH_EDGES, RM_CMESH_OPEN_EDGES, RM_CMESH_BRANCH_EDGES,
+ RM_CMESH_COUNTS) = range(13)
+CMESH_COUNT_NAMES = ("vertices", "triangles", "faces", "faces_pos_x", "faces_neg_x", "faces_pos_y", "faces_neg_y", "faces_pos_z",
+                     "faces_neg_z", "edges", "open_edges", "branch_edges")
+(RM_CMESH_STAT_BRICKS, RM_CMESH_STAT_BRICKS_KEPT, RM_CMESH_STAT_BRICKS_INSIDE, RM_CMESH_STAT_EVALUATIONS, RM_CMESH_STAT_RETAINED_BYTES,
+ RM_CMESH_STAT_SCRATCH_BYTES, RM_CMESH_STATS) = range(7)
+CMESH_STAT_NAMES = LAT_STAT_NAMES
 
 
 def RM_SURF_PAIR(a, b, nu):
@@ -308,6 +317,10 @@ def hip_lib():
         L.rm_draw_lattice.restype = C.c_int
         L.rm_cast_lattice.argtypes = [vp, u32, vp, vp, vp, vp, vp, C.c_int, vp]
         L.rm_cast_lattice.restype = C.c_int
+        L.rm_mesh_classes.argtypes = [vp, u32, u32, u32, vp, C.c_int, vp, f3, f3, u32, u32, C.POINTER(u64), u32, C.POINTER(u64), u32]
+        L.rm_mesh_classes.restype = C.c_int
+        L.rm_read_class_mesh.argtypes = [vp, vp, vp, vp, C.c_int, vp]
+        L.rm_read_class_mesh.restype = C.c_int
         L.rm_slice_contours.argtypes = [vp, u32, f3, f3, u32, u32, f3, u32, C.c_float, u32, C.POINTER(u64), u32]
         L.rm_slice_contours.restype = C.c_int
         L.rm_read_slices.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]

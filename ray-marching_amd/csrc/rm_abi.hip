@@ -39,6 +39,7 @@
 #include "rm_surface.h"
 #include "rm_voxel.h"
 #include "rm_lattice.h"
+#include "rm_class_mesh.h"
 #include "rm_slice.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
@@ -235,6 +236,13 @@ struct rm_ctx {
             for (int a = 0; a < 3; a++) origin[a] = o[a], step[a] = st[a];
         }
     } lat;
+    struct ClassMesh {  // rm_mesh_classes: the arrays of rml::ClassMeshSlot(v, t) in buf
+        DevBuf<char> buf;
+        bool valid = false;
+        uint64_t v = 0, t = 0;
+        void drop() { valid = false; }
+        void commit(uint64_t v_, uint64_t t_) { v = v_, t = t_, valid = true; }
+    } cmesh;
     // scratch for host-destination draws and batch uniforms
     DevBuf<char> d_out;
     DevBuf<rm_uniforms> d_frames;
@@ -2955,6 +2963,88 @@ RM_EXPORT int rm_read_voxels(rm_ctx* c, void* out_occupancy, int is_device, void
     const rm_ctx::Voxels& r = c->vox;
     if (!r.valid) return fail(c, RM_ERR_ARG, "rm_read_voxels: no mesh has been voxelised");
     return read_back(c, is_device, stream, "rm_read_voxels: out_occupancy needs no alignment", {{out_occupancy, r.buf.p, r.points(), 1}});
+}
+
+// ---- lattice meshing (rm_class_mesh.h) ----
+namespace {
+
+static_assert(rmk::kCmeshGroupWords == rml::kCmeshGroupWords && rmk::kCmeshNoId == RM_NO_ID, "ClassMeshScratch sizes the mark kernel's arrays");
+static_assert(RM_CMESH_STAT_BRICKS == kStatBricks && RM_CMESH_STAT_BRICKS_KEPT == kStatBricksKept && RM_CMESH_STAT_BRICKS_INSIDE == kStatBricksInside &&
+                  RM_CMESH_STAT_EVALUATIONS == kStatEvaluations && RM_CMESH_STAT_SCRATCH_BYTES == RM_CMESH_STATS - 1,
+              "the brick statistics first (zeros, as for a caller's occupancy) and the scratch size last");
+static_assert(RM_CMESH_FACES_POS_X == 3 && RM_CMESH_BRANCH_EDGES == RM_CMESH_FACES_POS_X + 8 && RM_CMESH_COUNTS == 12,
+              "the mark kernel's rows hold VERTICES in entry 0 and FACES_POS_X .. BRANCH_EDGES in the entries 1 .. 9");
+
+}  // namespace
+
+RM_EXPORT int rm_mesh_classes(rm_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz, const void* classes, int is_device, void* stream,
+                              const float* origin, const float* step, uint32_t mask_a, uint32_t mask_b, uint64_t* out_counts,
+                              uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
+    const char* fn = "rm_mesh_classes";
+    if (!c) return RM_ERR_NULL;
+    if (!classes || !out_counts || !out_stats) return fail(c, RM_ERR_NULL, "%s: classes, out_counts or out_stats is NULL", fn);
+    if (n_counts < (uint32_t)RM_CMESH_COUNTS) return fail(c, RM_ERR_ARG, "%s: n_counts %u < RM_CMESH_COUNTS", fn, n_counts);
+    if (n_stats < (uint32_t)RM_CMESH_STATS) return fail(c, RM_ERR_ARG, "%s: n_stats %u < RM_CMESH_STATS", fn, n_stats);
+    if (int rc = check_lattice(c, fn, origin, step)) return rc;
+    if (int rc = check_topo_lattice(c, fn, nx, ny, nz)) return rc;
+    const uint32_t all = (1u << RM_SURF_CLASSES) - 1u;
+    if (mask_a == 0u || mask_b == 0u || (mask_a & mask_b) != 0u || ((mask_a | mask_b) & ~all) != 0u)
+        return fail(c, RM_ERR_ARG, "%s: masks 0x%x, 0x%x: non-empty, disjoint, no bit above 7", fn, mask_a, mask_b);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    order_with_previous(c, s);  // after a device read of the last class mesh, too
+    const rml::ClassMeshScratch S(nx, ny, nz);
+    int rc = c->d_mscratch.reserve(c, S.bytes);
+    if (rc != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    if (is_device) {
+        // the caller's array is ready when the work queued on its stream is done; the call is synchronous anyway
+        const hipStream_t su = user_stream(c, stream);
+        if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
+    }
+    HIP_TRY(c, hipMemcpyAsync(S.cls.at(sc), classes, S.cls.bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    const rmk::CmeshGrid G{nx, ny, nz, nx + 1u, ny + 1u, rml::cmesh_row_words(nx), S.n_words, origin[0], origin[1], origin[2],
+                           step[0], step[1], step[2], mask_a, mask_b};
+    hipLaunchKernelGGL(rmk::rm_cmesh_mark_kernel, dim3(S.n_groups), dim3(256), 0, s, G, S.cls.at(sc), S.bits.at(sc), S.before.at(sc), S.bsums.at(sc),
+                       S.rows.at(sc));
+    if ((rc = scan_launch(c, s, S.bsums.at(sc), S.n_groups, S.btot.at(sc))) != RM_OK) return rc;
+    unsigned long long row[RM_MOMENTS];
+    uint64_t tot[2];
+    if ((rc = reduce_rows(c, s, S.rows.at(sc), 2u * S.n_groups, S.folded.at(sc), S.result.at(sc), row, {tot, S.btot.at(sc), sizeof tot})) != RM_OK)
+        return rc;
+    // V < 2^32 and T < 2^32: a lattice of n <= 2^28 points with at least 2 along every axis has 3 n + ny nz + nx nz + nx ny <= 4.5 n
+    // pairs with a point inside it, and four corners to a face
+    const uint64_t V = tot[0], F = tot[1], T = 2u * F;
+    const rml::ClassMeshSlot M(V, T);
+    // the last check that can refuse is past: the previous mesh goes
+    c->cmesh.drop();
+    if ((rc = c->cmesh.buf.reserve(c, M.bytes, "class mesh")) != RM_OK) return rc;
+    if (F) {
+        char* base = c->cmesh.buf.p;
+        hipLaunchKernelGGL(rmk::rm_cmesh_emit_kernel, dim3((S.n_words + 3u) / 4u), dim3(256), 0, s, G, S.cls.at(sc), S.bits.at(sc), S.before.at(sc),
+                           S.bsums.at(sc), M.vertices.at(base), M.triangles.at(base), M.ids.at(base));
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    out_counts[RM_CMESH_VERTICES] = V;
+    out_counts[RM_CMESH_TRIANGLES] = T;
+    out_counts[RM_CMESH_FACES] = F;
+    for (uint32_t k = 0; k < 9u; k++) out_counts[RM_CMESH_FACES_POS_X + k] = row[1u + k];
+    for (uint32_t k = 0; k < (uint32_t)RM_CMESH_STATS; k++) out_stats[k] = 0u;
+    out_stats[RM_CMESH_STAT_RETAINED_BYTES] = M.bytes;
+    out_stats[RM_CMESH_STAT_SCRATCH_BYTES] = S.bytes;
+    c->cmesh.commit(V, T);
+    return RM_OK;
+}
+
+RM_EXPORT int rm_read_class_mesh(rm_ctx* c, float* out_vertices, uint32_t* out_triangles, uint32_t* out_ids, int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    const rm_ctx::ClassMesh& r = c->cmesh;
+    if (!r.valid) return fail(c, RM_ERR_ARG, "rm_read_class_mesh: no lattice has been meshed");
+    const rml::ClassMeshSlot M(r.v, r.t);
+    const char* base = r.buf.p;
+    return read_back(c, is_device, stream, "rm_read_class_mesh: device arrays need 4-byte alignment",
+                     {{out_vertices, M.vertices, base, 4}, {out_triangles, M.triangles, base, 4}, {out_ids, M.ids, base, 4}});
 }
 
 // ---- lattice draw (rm_lattice.h) ----

@@ -283,6 +283,42 @@ struct SurfScratch {
           result(a.take<unsigned long long>(kSurfRowWords)), n_groups(groups), bytes(a.total) {}
 };
 
+// rm_mesh_classes, for a lattice of nx x ny x nz points: its corner lattice has (nx + 1)(ny + 1)(nz + 1) corners in WORDS of 64
+// consecutive corners of an x row (cmesh_row_words(nx) to a row, the last one partly beyond it), kCmeshGroupWords words to a
+// workgroup of the mark kernel.  Per point its class (1 B, the caller's bytes); per word the ballot of its used corners (8 B)
+// and the vertices and faces before it in its workgroup (4 B: v | f << 16); per workgroup its (vertices | faces << 32), scanned
+// in place, and the two totals; per workgroup two rows of 16 words, per 256 rows one folded row, the reduced row.
+constexpr uint32_t kCmeshGroupWords = 16u;
+constexpr uint32_t cmesh_row_words(uint32_t nx) { return (nx + 1u + 63u) >> 6; }
+constexpr uint32_t cmesh_words(uint32_t nx, uint32_t ny, uint32_t nz) { return cmesh_row_words(nx) * (ny + 1u) * (nz + 1u); }  // (< 2^24)
+constexpr uint32_t cmesh_groups(uint32_t n_words) { return (n_words + kCmeshGroupWords - 1u) / kCmeshGroupWords; }
+struct ClassMeshScratch {
+    Carver a;
+    Region<uint8_t> cls;
+    Region<unsigned long long> bits;
+    Region<uint32_t> before;
+    Region<unsigned long long> bsums, btot, rows, folded, result;
+    uint32_t n_words, n_groups;
+    size_t bytes;
+    ClassMeshScratch(uint32_t nx, uint32_t ny, uint32_t nz)
+        : cls(a.take<uint8_t>((size_t)nx * ny * nz)), bits(a.take<unsigned long long>(cmesh_words(nx, ny, nz))),
+          before(a.take<uint32_t>(cmesh_words(nx, ny, nz))), bsums(a.take<unsigned long long>(cmesh_groups(cmesh_words(nx, ny, nz)))),
+          btot(a.take<unsigned long long>(2)), rows(a.take<unsigned long long>((size_t)cmesh_groups(cmesh_words(nx, ny, nz)) * 2u * 16u)),
+          folded(a.take<unsigned long long>((size_t)((cmesh_groups(cmesh_words(nx, ny, nz)) * 2u + 255u) / 256u) * 16u)),
+          result(a.take<unsigned long long>(16)), n_words(cmesh_words(nx, ny, nz)), n_groups(cmesh_groups(cmesh_words(nx, ny, nz))),
+          bytes(a.total) {}
+};
+
+// ... and the retained slot of a class mesh of V vertices and T triangles: positions (3 floats), indices (3 u32 per triangle), ids
+// (2 u32 per triangle).
+struct ClassMeshSlot {
+    Carver a;
+    Region<float> vertices;
+    Region<uint32_t> triangles, ids;
+    size_t bytes;
+    ClassMeshSlot(uint64_t V, uint64_t T) : vertices(a.take<float>(V * 3u)), triangles(a.take<uint32_t>(T * 3u)), ids(a.take<uint32_t>(T * 2u)), bytes(a.total) {}
+};
+
 // rm_slice_contours' per-layer tables: heights, layer_first, the first vertex of each layer of a batch of `per`, totals.
 // (heights and layer_first lie before anything `per` sizes: rm_read_slices finds layer_first without it.)
 struct SliceLayerTables {

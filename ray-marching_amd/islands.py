@@ -14,13 +14,14 @@ region table (one list of twelve numbers per region, _ffi.ISL_ROW_NAMES) and for
 from; --profile the per-layer table (inside points, regions, islands, island points).  --mask writes the mask (uint8 [k, j, i]: 0
 outside, 1 inside, 2 inside and in an island) and --labels the label volume (uint32 [k, j, i]) as .npy files.  --fail-on is a
 printability gate: a comma-separated list of `islands>N`, `island_points>N` and `layer_regions>N` (the most regions in one layer);
-the exit status is 2 when one holds."""
+the exit status is 2 when one holds.  --mesh-out writes the island points (class 2 of the mask) as a closed
+triangle mesh of unit faces (.stl, .obj or .ply; mesh_classes: DESIGN.md section 29); the report carries its counts under "mesh"."""
 import argparse
 import json
 import re
 import sys
 
-from . import lattice_image
+from . import lattice_image, lattice_mesh
 
 from .massprops import load_program
 from .mesh import _three
@@ -81,9 +82,11 @@ def main(argv=None):
     ap.add_argument("--profile", action="store_true", help="put the per-layer table into the report")
     ap.add_argument("--fail-on", default="", help='e.g. "islands>0,island_points>0,layer_regions>40": exit status 2 when one of them holds')
     lattice_image.add_options(ap)
+    lattice_mesh.add_options(ap, "islands")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     gates = parse_gates(a.fail_on)
+    lattice_mesh.check_path(a.mesh_out)
     import numpy as np
     from . import csg, renderer
     res = renderer.RayMarchingResources(a.device)
@@ -116,6 +119,9 @@ def main(argv=None):
         if a.image:
             cls = lattice_image.device_bytes(res, isl.shape, lambda p, st: res.read_islands_device(mask_ptr=p, stream=st))
             report["image"] = lattice_image.write(res, cls, isl.origin, isl.step, a.image, a.size, a.cut)
+        if a.mesh_out:                                              # the island points (class 2) against everything else
+            cls = lattice_image.device_bytes(res, isl.shape, lambda p, st: res.read_islands_device(mask_ptr=p, stream=st))
+            report["mesh"] = lattice_mesh.write(res, "islands", cls, isl.origin, isl.step, a.mesh_out)
     finally:
         res.close()
     failed = failed_gates(gates, gate_values(report))

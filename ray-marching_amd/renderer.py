@@ -7,6 +7,7 @@ import numpy as np
 
 from . import _ffi
 from . import csg as _csg
+from . import mesh as _mesh
 from ._ffi import Limits, Uniforms
 
 
@@ -864,6 +865,33 @@ class RayMarchingResources:
                                             C.c_void_p(stream) if stream else None))
         del keep
 
+    # -- lattice meshing (rm_mesh_classes / rm_read_class_mesh) ----------------------------------------------------------------------
+    def mesh_classes(self, classes, a, b=None, origin=(0.0, 0.0, 0.0), step=(1.0, 1.0, 1.0), device=False):
+        """rm_mesh_classes: the interface between the class sets a and b (a class, or an iterable of classes; b=None: every class
+        not in a) of a lattice of class bytes, as set_lattice and surface_classes take one (indexed [k, j, i]; numpy, or a
+        contiguous torch tensor on this context's GPU, taken without a host copy), as a welded, indexed triangle mesh: the unit
+        faces between a point of a and a 6-neighbour of b, wound counter-clockwise seen from the b side.  Point (i, j, k) lies at
+        origin + (i, j, k) * step, the faces half a step from it.  Returns a ClassMesh -- a mesh.Mesh without normals, with counts,
+        stats and the per-triangle face_classes, face and face_point -- as numpy arrays, or (device=True) torch tensors on the
+        context's GPU.  Needs no scene."""
+        mask_a = _class_mask(a)
+        mask_b = ((1 << _ffi.RM_SURF_CLASSES) - 1) & ~mask_a if b is None else _class_mask(b)
+        if mask_a == 0 or mask_b == 0 or mask_a & mask_b:
+            raise ValueError("the class sets %r and %r must be disjoint and not empty" % (a, b))
+        nx, ny, nz, ptr, is_device, stream, keep = self._occupancy_arg(classes)
+        o, s, _, fp = self._lattice(origin, step, (nx, ny, nz), 2)
+        counts, stats = (C.c_uint64 * _ffi.RM_CMESH_COUNTS)(), (C.c_uint64 * _ffi.RM_CMESH_STATS)()
+        fn = self._L.rm_mesh_classes
+        self._check(fn(self._h, nx, ny, nz, ptr, is_device, stream, fp(o), fp(s), mask_a, mask_b, counts, _ffi.RM_CMESH_COUNTS, stats,
+                       _ffi.RM_CMESH_STATS))
+        self._advance(fn, "class_mesh")
+        del keep
+        return ClassMesh(self, _named(counts, _ffi.CMESH_COUNT_NAMES), _named(stats, _ffi.CMESH_STAT_NAMES), o, s, (nx, ny, nz), device)
+
+    def read_class_mesh_device(self, vertices_ptr=0, triangles_ptr=0, ids_ptr=0, stream=None):
+        """rm_read_class_mesh of the last mesh_classes into device memory (integer addresses; 0 = not wanted), asynchronous."""
+        self._read_into(self._L.rm_read_class_mesh, (vertices_ptr, triangles_ptr, ids_ptr), True, stream)
+
     # -- retained results (rm_read_*) ------------------------------------------------------------------------------------------
     # rm_read_* copies the size of the CONTEXT's last result, whatever the caller allocated.  So every read goes through _read_into,
     # and the result objects that read on demand (_Retained) are held to a serial per family: _advance moves it on when a producing
@@ -1032,7 +1060,7 @@ class RayMarchingCallback:
 
 # The outputs of the lattice analyses (RayMarchingResources._solid_grid_call): the families of retained results a call replaces
 # (a new distance volume has no mask), how many counts and statistics, and their names.
-_FAMILIES = ("topology", "distance", "distance_mask", "support", "islands", "voxels", "lattice")
+_FAMILIES = ("topology", "distance", "distance_mask", "support", "islands", "voxels", "lattice", "class_mesh")
 _TOPO_OUTPUTS = (("topology",), _ffi.RM_TOPO_COUNTS, _ffi.RM_TOPO_STATS, _ffi.TOPO_COUNT_NAMES, _ffi.TOPO_STAT_NAMES)
 _DIST_OUTPUTS = (("distance", "distance_mask"), _ffi.RM_DIST_COUNTS, _ffi.RM_DIST_STATS, _ffi.DIST_COUNT_NAMES, _ffi.DIST_STAT_NAMES)
 _SUP_OUTPUTS = (("support",), _ffi.RM_SUP_COUNTS, _ffi.RM_SUP_STATS, _ffi.SUP_COUNT_NAMES, _ffi.SUP_STAT_NAMES)
@@ -1436,6 +1464,37 @@ def surface_measures(counts, step, a, b, raw=False):
     if rc != _ffi.RM_OK:
         raise _ffi.RmError(rc, "rm_surface_measures: " + _ffi.hip_lib().rm_status_string(rc).decode())
     return out if raw else {name: float(out[k]) for k, name in enumerate(_ffi.SURF_MEASURE_NAMES)}
+
+
+class ClassMesh(_mesh.Mesh, _Retained):
+    """The result of mesh_classes: a mesh.Mesh (vertices (V, 3) float32, triangles (T, 3), normals None) with counts and stats
+    (dicts: _ffi.CMESH_COUNT_NAMES, _ffi.CMESH_STAT_NAMES), origin, step (float32[3]) and shape of the lattice, and per triangle
+    face_classes (T, 2: the class on the a side and on the b side), face (2 axis + (normal positive)) and face_point (the linear
+    index i + nx (j + ny k) of the a-side point, _ffi.RM_NO_ID for padding).  read() reads the context's buffers again: after a
+    later mesh_classes of the context it raises ValueError."""
+
+    def __init__(self, resources, counts, stats, origin, step, shape, device=False):
+        self._retain(resources, "class_mesh")
+        self.counts, self.stats = counts, stats
+        self.origin, self.step, self.shape = origin, step, shape
+        _mesh.Mesh.__init__(self, None, None)
+        self.read(device)
+
+    def __repr__(self):
+        return "ClassMesh(%d vertices, %d triangles, on %s)" % (self.counts["vertices"], self.counts["triangles"],
+                                                                "x".join(map(str, self.shape)))
+
+    def read(self, device=False):
+        """rm_read_class_mesh into new arrays of this mesh (numpy, or torch tensors on the context's GPU); returns self."""
+        self._check_current()
+        V, T = self.counts["vertices"], self.counts["triangles"]
+        self.vertices, self.triangles, ids = self._res._read_new(self._res._L.rm_read_class_mesh,
+                                                                 [((V, 3), *_F32, True), ((T, 3), *_U32, True), ((T, 2), *_U32, True)], device)
+        word = ids[:, 0]
+        self.face_classes = ids.new_empty((T, 2)) if device else np.empty((T, 2), dtype=np.uint32)
+        self.face_classes[:, 0], self.face_classes[:, 1] = word & 0xFF, (word >> 8) & 0xFF
+        self.face, self.face_point, self.ids = word >> 16, ids[:, 1], ids
+        return self
 
 
 class Surface:

@@ -14,13 +14,14 @@ all six.  --plate H puts the plate at height H (a layer index along the build di
 [k, j, i]: 0 outside, 1 inside, 2 overhang, 3 support on the plate, 4 support on the part) as a .npy file.  --regions labels the
 overhang points and the support points (label_occupancy) and reports each region's points, volume and centre.  --fail-on is a
 printability gate: a comma-separated list of `overhang>N`, `landings>N` (points) and `support>V` (world volume); the exit status
-is 2 when one holds."""
+is 2 when one holds.  --mesh-out writes the support points (classes 3 and 4 of the mask) as a closed
+triangle mesh of unit faces (.stl, .obj or .ply; mesh_classes: DESIGN.md section 29); the report carries its counts under "mesh"."""
 import argparse
 import json
 import re
 import sys
 
-from . import lattice_image
+from . import lattice_image, lattice_mesh
 
 from .massprops import load_program
 from .mesh import _three
@@ -79,9 +80,11 @@ def main(argv=None):
     ap.add_argument("--regions", action="store_true", help="label the overhang and the support points and report every region")
     ap.add_argument("--fail-on", default="", help='e.g. "overhang>0,support>2.5,landings>0": exit status 2 when one of them holds')
     lattice_image.add_options(ap)
+    lattice_mesh.add_options(ap, "supports")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     gates = parse_gates(a.fail_on)
+    lattice_mesh.check_path(a.mesh_out)
     import numpy as np
     from . import _ffi, csg, renderer
     res = renderer.RayMarchingResources(a.device)
@@ -116,6 +119,9 @@ def main(argv=None):
         if a.image:
             cls = lattice_image.device_bytes(res, sup.shape, lambda p, st: res.read_support_device(mask_ptr=p, stream=st))
             report["image"] = lattice_image.write(res, cls, sup.origin, sup.step, a.image, a.size, a.cut)
+        if a.mesh_out:                                              # the supports (classes 3 and 4) against everything else
+            cls = lattice_image.device_bytes(res, sup.shape, lambda p, st: res.read_support_device(mask_ptr=p, stream=st))
+            report["mesh"] = lattice_mesh.write(res, "supports", cls, sup.origin, sup.step, a.mesh_out)
     finally:
         res.close()
     failed = failed_gates(gates, {"overhang": report["overhang"], "support": report["support"], "landings": report["landings"]})

@@ -12,13 +12,15 @@ three axes) the points of walls thinner than W and of gaps narrower than G.  --d
 3 narrow) as .npy files.  --regions labels the thin points (label_occupancy) and reports each region's volume and centre.
 --fail-on is a printability gate: a comma-separated list of `thin>N`, `narrow>N` (points) and `inscribed<R` (world units); the
 exit status is 2 when one holds.  Ball centres lie on the lattice only: a solid nearer than the gap width to the box's border can
-report narrow points against the border, and the report then carries a warning."""
+report narrow points against the border, and the report then carries a warning.  --mesh-out writes the thin
+and the narrow points (classes 2 and 3 of the mask) as a closed triangle mesh of unit faces (.stl, .obj or .ply; mesh_classes:
+DESIGN.md section 29); the report carries its counts under "mesh"."""
 import argparse
 import json
 import re
 import sys
 
-from . import lattice_image
+from . import lattice_image, lattice_mesh
 
 from .massprops import load_program
 from .mesh import _three
@@ -70,9 +72,11 @@ def main(argv=None):
     ap.add_argument("--regions", action="store_true", help="label the thin points and report every region")
     ap.add_argument("--fail-on", default="", help='e.g. "thin>0,narrow>0,inscribed<0.4": exit status 2 when one of them holds')
     lattice_image.add_options(ap)
+    lattice_mesh.add_options(ap, "thickness")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     gates = parse_gates(a.fail_on)
+    lattice_mesh.check_path(a.mesh_out)
     import numpy as np
     from . import _ffi, csg, renderer
     res = renderer.RayMarchingResources(a.device)
@@ -91,7 +95,7 @@ def main(argv=None):
         if a.d2:
             np.save(a.d2, dist.d2())
         values = {"inscribed": radius, "thin": 0, "narrow": 0}
-        if a.min_wall is not None or a.min_gap is not None or a.mask or a.regions or a.image:
+        if a.min_wall is not None or a.min_gap is not None or a.mask or a.regions or a.image or a.mesh_out:
             feats = dist.features(wall=a.min_wall, gap=a.min_gap)
             report.update(r2_wall=feats.r2_wall, r2_gap=feats.r2_gap, **feats.counts)
             values.update(thin=feats.counts["thin"], narrow=feats.counts["narrow"])
@@ -115,6 +119,9 @@ def main(argv=None):
         if a.image:
             cls = lattice_image.device_bytes(res, dist.shape, lambda p, st: res.read_distance_device(mask_ptr=p, stream=st))
             report["image"] = lattice_image.write(res, cls, dist.origin, dist.step, a.image, a.size, a.cut)
+        if a.mesh_out:                                              # the thin and the narrow points (classes 2 and 3) against everything else
+            cls = lattice_image.device_bytes(res, dist.shape, lambda p, st: res.read_distance_device(mask_ptr=p, stream=st))
+            report["mesh"] = lattice_mesh.write(res, "thickness", cls, dist.origin, dist.step, a.mesh_out)
     finally:
         res.close()
     failed = failed_gates(gates, values)

@@ -12,7 +12,9 @@ units), supports and islands (support_occupancy, islands_occupancy for --up and 
 voxel solid).  --out writes the occupancy as a .npy file, uint8 indexed [k, j, i].  --fail-on is a gate: a comma-separated list
 of `name>N` or `name<N` over the voxel counts and the counts of the requested reports (`report.name` where two reports share a
 name); the exit status is 2 when one holds.  --image writes a picture of the voxel solid (a PNG of --size,
-through an orbit camera aimed at the lattice's box; --cut axis:lo:hi shows only that slab of lattice points: DESIGN.md section 28)."""
+through an orbit camera aimed at the lattice's box; --cut axis:lo:hi shows only that slab of lattice points: DESIGN.md section 28).
+--mesh-out writes the voxel solid as a closed triangle mesh of unit faces (.stl, .obj or .ply; mesh_classes: DESIGN.md section 29);
+the report carries its counts under "mesh"."""
 import argparse
 import json
 import re
@@ -20,7 +22,7 @@ import sys
 
 import numpy as np
 
-from . import _ffi, lattice_image
+from . import _ffi, lattice_image, lattice_mesh
 
 REPORTS = {"topology": _ffi.TOPO_COUNT_NAMES, "thickness": _ffi.DIST_COUNT_NAMES + ("inscribed_radius",),
            "supports": _ffi.SUP_COUNT_NAMES, "islands": _ffi.ISL_COUNT_NAMES, "surface": _ffi.SURF_MEASURE_NAMES}
@@ -101,8 +103,10 @@ def main(argv=None):
     ap.add_argument("--r2", type=int, default=1, help="the squared reach of supports and islands (index units, 0..255)")
     ap.add_argument("--fail-on", default="", help='e.g. "open_rows>0,rejected>0,bodies>1": exit status 2 when one of them holds')
     lattice_image.add_options(ap)
+    lattice_mesh.add_options(ap, "voxelize")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    lattice_mesh.check_path(a.mesh_out)
     try:
         reports = parse_reports(a.report)
         gates = parse_gates(a.fail_on, reports)
@@ -120,6 +124,8 @@ def main(argv=None):
             np.save(a.out, vox.occupancy())
         if a.image:                                              # the occupancy never leaves the device
             report["image"] = lattice_image.write(res, vox.occupancy_device(), vox.origin, vox.step, a.image, a.size, a.cut)
+        if a.mesh_out:
+            report["mesh"] = lattice_mesh.write(res, "voxelize", vox.occupancy_device(), vox.origin, vox.step, a.mesh_out)
     finally:
         res.close()
     report["failed"] = failed_gates(gates, gate_values(report, reports))
