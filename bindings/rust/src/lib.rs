@@ -102,6 +102,8 @@ pub const RM_INFO_JIT_COMPILE_MS: c_int = 8;
 pub const RM_INFO_PRUNED: c_int = 9;
 pub const RM_INFO_INTERPRETER_LOOP: c_int = 10;
 pub const RM_INFO_JIT_FROM_CACHE: c_int = 11;
+/// 1 when the last march launch ran the kernel compiled without the per-lane range guards (the host proved the ranges).
+pub const RM_INFO_RANGE_PROOF: c_int = 12;
 
 // enum rm_program_fact: indices into the array rm_program_info fills
 pub const RM_PROGRAM_RECORDS: usize = 0;

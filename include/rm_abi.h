@@ -176,8 +176,13 @@ enum rm_info {
                                     LDS), 3 the tree loop (reference node types in any arrangement: one dispatch per record), 4 the tree loop over the
                                     records wave-level culling leaves (exact; trees of a dozen leaves or more and at most 128 records, staged in LDS), 5 the
                                     general record machine over the units of a blending chain that wave-level culling names (exact; eight leaves or more) */
-    RM_INFO_JIT_FROM_CACHE = 11  /* 1 when the current program's kernel was read from the disk cache of compiled structures
+    RM_INFO_JIT_FROM_CACHE = 11, /* 1 when the current program's kernel was read from the disk cache of compiled structures
                                   * (RM_JIT_CACHE_DIR; default: jit_cache next to the library) instead of being compiled */
+    RM_INFO_RANGE_PROOF = 12     /* 1 when the last march launch ran the specialised kernel compiled WITHOUT the range guards that facts of
+                                  * the program make unnecessary (every box half-extent at least 2^-23 in magnitude and finite, no material
+                                  * table, a pruned min / max program; DESIGN.md section 5 "Range proofs"); 0 when it ran the guarded
+                                  * kernel -- a program without those facts, RM_JIT_RANGE_PROOF=0 in the environment -- or an interpreter
+                                  * kernel.  The frames are the same bit for bit.  (Additive: RM_ABI_VERSION stays 2.) */
 };
 
 int rm_abi_version(void);
@@ -1069,6 +1074,8 @@ int rm_read_wave_stats(rm_ctx* ctx, void* dst, uint64_t cap_bytes, uint64_t* out
  *                 compilation fails (log receives the reason).  Nothing is cached or loaded.
  * rm_jit_log: compiler / loader messages for the context's current program (empty string if none). */
 #define RM_JIT_PRUNE 0x100 /* OR into waves_per_tile: generate the RM_OPT_PRUNE = 1 form of the kernel */
+#define RM_JIT_RANGE_PROVED 0x200 /* OR into waves_per_tile, with RM_JIT_PRUNE: the variant without the range guards
+                                     (RM_INFO_RANGE_PROOF); ignored for programs that get no such variant */
 int rm_jit_source(uint32_t cmd_count, const uint32_t* words, uint32_t n_words, int waves_per_tile, char* buf, size_t cap,
                   size_t* needed);
 int rm_jit_compile(uint32_t cmd_count, const uint32_t* words, uint32_t n_words, int waves_per_tile, double* compile_ms,

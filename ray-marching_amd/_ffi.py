@@ -35,12 +35,13 @@ RM_OPT_BALANCE, RM_OPT_WAVE_STATS, RM_OPT_WAVES_PER_TILE, RM_OPT_SPECIALIZE, RM_
 RM_KERNEL_DEFAULT, RM_KERNEL_PIXEL = 0, 1      # 2..11: the retired v2-v4 variants of ABI version 1
 RM_KERNEL_V5, RM_KERNEL_V5_LDS = 12, 13
 RM_JIT_PRUNE = 0x100
+RM_JIT_RANGE_PROVED = 0x200
 RM_STREAM_OWN = (1 << 64) - 1   # (void*)-1: the context's own stream
 RM_OPT_OUTPUT_FORMAT = 10
 RM_FORMAT_RGBA32F, RM_FORMAT_RGBA8_UNORM, RM_FORMAT_BGRA8_UNORM = 0, 1, 2
 RM_INFO_KERNEL_MS, RM_INFO_PROGRAM_COMMANDS, RM_INFO_PROGRAM_WORDS, RM_INFO_PROGRAM_DEPTH = 0, 1, 2, 3
 RM_INFO_DEVICE, RM_INFO_CU_COUNT, RM_INFO_SPECIALIZED, RM_INFO_JIT_STATE, RM_INFO_JIT_COMPILE_MS = 4, 5, 6, 7, 8
-RM_INFO_PRUNED, RM_INFO_INTERPRETER_LOOP, RM_INFO_JIT_FROM_CACHE = 9, 10, 11
+RM_INFO_PRUNED, RM_INFO_INTERPRETER_LOOP, RM_INFO_JIT_FROM_CACHE, RM_INFO_RANGE_PROOF = 9, 10, 11, 12
 # scene queries (rm_query_points / rm_cast_rays / rm_camera_rays)
 RM_NO_ID = 0xFFFFFFFF
 RM_HIT_NONE, RM_HIT_SURFACE, RM_HIT_FLOOR = 0, 1, 2

@@ -275,7 +275,9 @@ struct rm_ctx {
     int spec_wpt = 0;
     int spec_pruned = 0;            // rmjit::PRUNE_* of the requested kernel
     bool spec_stats = false;        // ... and whether it keeps the counters of RM_OPT_WAVE_STATS
+    bool spec_range = false;        // ... and whether it is the variant without the range guards (rmjit::KERNEL_RANGE_PROVED)
     bool last_specialized = false;  // the last march launch ran a specialised kernel
+    bool last_range_proof = false;  // ... the variant without the range guards (RM_INFO_RANGE_PROOF)
     int last_loop = 0;              // RM_INFO_INTERPRETER_LOOP of the last march launch
     // stream-ordered uploads (program records, bounds, batch uniforms): four pinned staging buffers, see upload()
     struct Staging { void* host = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool pending = false; };
@@ -388,18 +390,32 @@ int prune_kind(const RmDecoded& d, int option) {
     return rmjit::PRUNE_NONE;
 }
 
+// Whether the march launches of the current program may run the kernel compiled without the range guards its facts make
+// unnecessary (rm_interp.h "Range proofs"): every box half-extent at least 2^-23 in magnitude and finite (the lower side of the boxes'
+// guard), no material table (the gamma roots), and a kernel that has the variant at all -- a pruned lattice program
+// (rmjit::range_variant).  Nothing here depends on the camera, the limits or where the uniforms live: a batch of frames qualifies.
+// RM_JIT_RANGE_PROOF=0 in the environment (read at every launch) keeps the guarded kernel, for comparisons and tests.
+bool range_facts_hold(const rm_ctx* c) {
+    if (rmjit::jit_knob("RM_JIT_RANGE_PROOF", 1) == 0) return false;
+    const RmDecoded& d = c->decoded;
+    return d.box_sizes_normal && rmjit::range_variant(prune_kind(d, c->prune) | rmjit::KERNEL_RANGE_PROVED, !d.mrec.empty());
+}
+
 // The specialised march kernel for the current program and WPT waves per tile on this device, or
 // nullptr: specialisation off, not possible, still compiling (mode 1) or failed -- the caller then
 // launches the interpreter kernel.  Never an error.
-hipFunction_t specialised_kernel(rm_ctx* c, int wpt) {
+// range_proved: the variant without the range guards the program's facts make unnecessary (range_facts_hold above).
+hipFunction_t specialised_kernel(rm_ctx* c, int wpt, bool range_proved) {
     if (!c->specialize || !rmjit::can_specialise(c->decoded.rec)) return nullptr;
-    if (c->spec_gen != c->prog_gen || c->spec_wpt != wpt || c->spec_stats != c->wave_stats) {
+    if (c->spec_gen != c->prog_gen || c->spec_wpt != wpt || c->spec_stats != c->wave_stats || c->spec_range != range_proved) {
         // same structure as before (parameters moved): the key lookup finds the same entry
         const int prune = prune_kind(c->decoded, c->prune);
         // (the per-wave counters of RM_OPT_WAVE_STATS are compiled into a kernel of their own: the default one does without)
-        c->spec = rmjit::Cache::get().request(c->decoded.rec, c->decoded.mrec, wpt, prune | (c->wave_stats ? rmjit::KERNEL_WITH_STATS : 0));
+        c->spec = rmjit::Cache::get().request(c->decoded.rec, c->decoded.mrec, wpt, prune | (c->wave_stats ? rmjit::KERNEL_WITH_STATS : 0) |
+                                                                                      (range_proved ? rmjit::KERNEL_RANGE_PROVED : 0));
         c->spec_pruned = prune;
         c->spec_stats = c->wave_stats;
+        c->spec_range = range_proved;
         c->spec_gen = c->prog_gen;
         c->spec_wpt = wpt;
     }
@@ -520,7 +536,8 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
     c->last_loop = loop;
     const uint32_t n_tiles = ((L.W + 7u) / 8u) * ((L.rows + 7u) / 8u);
     // structure-specialised kernel (values live in registers: no LDS spill stack)
-    hipFunction_t spec_fn = lds ? specialised_kernel(c, WPT) : nullptr;
+    const bool range_proved = lds && range_facts_hold(c);
+    hipFunction_t spec_fn = lds ? specialised_kernel(c, WPT, range_proved) : nullptr;
     if (spec_fn) { L.spill_depth = 0u; L.n_tree = 0u; }
     // the material evaluation of a tagged program borrows the spill area: (distance, index) pairs + saved positions
     // (a specialised kernel with the generated material walk keeps those pairs in registers too)
@@ -572,6 +589,7 @@ int launch_v5_w(rm_ctx* c, const RmLaunch& L_in, bool lds, uint32_t n_frames, hi
     // which has the general record loop
     const bool ext = d.has_extensions || !d.is_tree;
     c->last_specialized = spec_fn != nullptr;
+    c->last_range_proof = spec_fn != nullptr && range_proved;
     // When a wave takes new rays.  With far-primitive pruning every evaluation tests which primitives are near for ANY lane:
     // lanes at unrelated march depths (a lane refilled the moment it retires) keep most of them near, while 64 rays started
     // together stay in step -- far from everything at first, then close to one or two primitives each -- and the union shrinks
@@ -3428,6 +3446,7 @@ RM_EXPORT int rm_get_info(rm_ctx* c, int key, double* out) {
     case RM_INFO_DEVICE: *out = c->device; return RM_OK;
     case RM_INFO_CU_COUNT: *out = c->cu_count; return RM_OK;
     case RM_INFO_SPECIALIZED: *out = c->last_specialized ? 1.0 : 0.0; return RM_OK;
+    case RM_INFO_RANGE_PROOF: *out = c->last_range_proof ? 1.0 : 0.0; return RM_OK;
     case RM_INFO_INTERPRETER_LOOP: *out = c->last_specialized ? 0.0 : (double)c->last_loop; return RM_OK;
     case RM_INFO_PRUNED: *out = c->spec && c->spec_gen == c->prog_gen && !c->cmd_dirty ? (double)c->spec_pruned : 0.0; return RM_OK;
     case RM_INFO_JIT_STATE:
@@ -3726,12 +3745,15 @@ RM_EXPORT int rm_measure_write_bandwidth(rm_ctx* c, uint64_t bytes, int iters, d
 }
 
 namespace {
-int jit_decode(uint32_t cmd_count, const uint32_t* words, uint32_t n_words, int wpt, bool prune, std::string* src, std::string* capped = nullptr) {
+int jit_decode(uint32_t cmd_count, const uint32_t* words, uint32_t n_words, int waves_per_tile, std::string* src, std::string* capped = nullptr) {
+    const int wpt = waves_per_tile & 0xFF;
+    const bool prune = (waves_per_tile & RM_JIT_PRUNE) != 0;
     if (wpt != 1 && wpt != 2 && wpt != 4 && wpt != 8) return RM_ERR_ARG;
     RmDecoded d;
     int rc = rm_decode_program(cmd_count, words, n_words, &d);
     if (rc != RM_OK) return rc;
-    const int kind = !prune ? rmjit::PRUNE_NONE : d.unit_mode == RM_UNITS_LATTICE ? rmjit::PRUNE_LATTICE : d.unit_mode == RM_UNITS_BLEND ? rmjit::PRUNE_BLEND : rmjit::PRUNE_NONE;
+    int kind = !prune ? rmjit::PRUNE_NONE : d.unit_mode == RM_UNITS_LATTICE ? rmjit::PRUNE_LATTICE : d.unit_mode == RM_UNITS_BLEND ? rmjit::PRUNE_BLEND : rmjit::PRUNE_NONE;
+    if ((waves_per_tile & RM_JIT_RANGE_PROVED) != 0) kind |= rmjit::KERNEL_RANGE_PROVED;  // (taken by the programs that have the variant)
     if (!rmjit::can_specialise(d.rec) || !rmjit::generate_source(d.rec, d.mrec, wpt, kind, src, nullptr, nullptr, capped)) return RM_ERR_ARG;
     return RM_OK;
 }
@@ -3746,7 +3768,7 @@ void copy_out(const std::string& s, char* buf, size_t cap) {
 RM_EXPORT int rm_jit_source(uint32_t cmd_count, const uint32_t* words, uint32_t n_words, int waves_per_tile, char* buf,
                             size_t cap, size_t* needed) {
     std::string src;
-    int rc = jit_decode(cmd_count, words, n_words, waves_per_tile & 0xFF, (waves_per_tile & RM_JIT_PRUNE) != 0, &src);
+    int rc = jit_decode(cmd_count, words, n_words, waves_per_tile, &src);
     if (rc != RM_OK) return rc;
     if (needed) *needed = src.size() + 1;
     copy_out(src, buf, cap);
@@ -3756,7 +3778,7 @@ RM_EXPORT int rm_jit_source(uint32_t cmd_count, const uint32_t* words, uint32_t 
 RM_EXPORT int rm_jit_compile(uint32_t cmd_count, const uint32_t* words, uint32_t n_words, int waves_per_tile,
                              double* compile_ms, size_t* code_bytes, char* log, size_t log_cap) {
     std::string src, capped, msg;
-    int rc = jit_decode(cmd_count, words, n_words, waves_per_tile & 0xFF, (waves_per_tile & RM_JIT_PRUNE) != 0, &src, &capped);
+    int rc = jit_decode(cmd_count, words, n_words, waves_per_tile, &src, &capped);
     if (rc != RM_OK) return rc;
     std::vector<char> code;
     double ms = 0.0;

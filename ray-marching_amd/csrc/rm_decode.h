@@ -36,6 +36,9 @@ struct RmDecoded {
     // 1-Lipschitz leaf or a min/max operator; scene_scale = 1 + max over primitives of |centre|_1 + |size|_1
     bool prunable = true;
     float scene_scale = 1.0f;
+    // Every half-extent r of every box has 2^-23 <= |r| < inf: the radicand of a box leaf is then 0 or at least 2^-92, whatever
+    // the position, and a kernel compiled with the range proofs does not guard its lower side (rm_interp.h "Range proofs")
+    bool box_sizes_normal = true;
     // Chain program: record 0 pushes a sphere / box, every later record is a sphere / box fused with a Union / Subtraction
     // (RM_OP_FASTCLASS): the interpreter kernels run such programs through map_scene_chain (rm_interp.h)
     bool is_chain = false;
@@ -438,6 +441,10 @@ static inline int rm_decode_core(uint32_t cmd_count, const uint32_t* words, uint
         sharper = sharper || (RM_OP_KIND(r.op) == RM_KIND_PLANE && !(r.op & RM_OP_NOCULL)) || RM_OP_MODE(r.op) == RM_MODE_INTER;
     d.bound_walk = ((d.smooth_slack > 0.0 && d.smooth_slack < 1.0e30) || (sharper && d.smooth_slack == 0.0)) && !d.has_xforms &&
                    d.spill_depth <= 1u && d.scene_scale < 1.0e12f;
+    for (const RmRecord& r : d.rec)  // the records as the kernels read them
+        if (RM_OP_KIND(r.op) == RM_KIND_BOX)
+            for (uint32_t k = 3; k < 6; k++)
+                if (!(std::fabs(r.p[k]) >= 0x1p-23f && std::fabs(r.p[k]) < INFINITY)) d.box_sizes_normal = false;  // (also takes a NaN)
     d.n_words = ptr;
     *out = std::move(d);
     return RM_OK;

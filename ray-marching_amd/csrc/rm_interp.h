@@ -49,6 +49,14 @@ struct SqrtGuard {
     }
     static constexpr uint32_t kLoBits = 0x0F800000u - 1u;  // bits(2^-96) - 1
 };
+// What a generated kernel compiled with RM_JIT_RANGE_PROOF leaves unguarded ("Range proofs" below; rm_jit.h writes the definition
+// in front of the translation unit of a program whose facts hold -- rm_abi.hip range_facts_hold; the library's own kernels guard everything)
+#if defined(RM_JIT_RANGE_PROOF)
+constexpr bool kBoxGuardLo = false, kRangeProved = true;
+#else
+constexpr bool kBoxGuardLo = true, kRangeProved = false;
+#endif
+constexpr bool kNumeratorHi = !kRangeProved;  // DivGuard::a_hi: see the lemma at normalize3_guard
 RM_DEV float vmax(float a, float b) {  // direct v_max_f32, see vmin
     float r;
     asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -61,12 +69,31 @@ RM_DEV float sqrt_rn_fast(float x) {
     return __builtin_fmaf(__builtin_fmaf(-g, g, x), h, g);
 }
 
-template <bool FAST, bool ZERO_OK = false>
+// Range proofs (a generated kernel compiled with RM_JIT_RANGE_PROOF; DESIGN.md section 5 "Range proofs").  Both sides of the
+// guard cost vector instructions at every use, and on a sane program neither ever fires: where a fact about the whole PROGRAM
+// excludes a side, the host establishes it once (when the program is decoded) and the kernel is compiled without that side -- GUARD_LO /
+// GUARD_HI = false below.
+//   Lower side, boxes.  m_i = max(fl(t - r_i), 0) with t = |p_i - c_i| >= 0.  With 2^-23 <= |r_i| < inf (RmDecoded::
+//   box_sizes_normal): r_i < 0 gives fl(t + |r_i|) >= |r_i| >= 2^-23.  r_i > 0: m_i > 0 only for t > r_i; for t <= 2 r_i the
+//   difference is exact (Sterbenz) and a positive multiple of ulp(r_i) >= 2^-46 (t >= r_i is a multiple of ulp(r_i)); beyond,
+//   t - r_i > r_i and rounding is monotone: fl(t - r_i) >= r_i >= 2^-23.  A NaN t gives m_i = 0 (fmax_ drops it).  So m_i is 0
+//   or >= 2^-46, its square 0 or >= 2^-92 (the rounded square of a number >= 2^-46 is >= the exactly representable 2^-92), and
+//   the radicand, a rounded sum of non-negative terms, 0 or >= 2^-92 > 2^-96 -- or +inf, which is the upper side's business:
+//   inside sqrt_rn_fast<true>'s range from below, and the clamp of the v_rsq input stays for the zero.  Spheres keep their lower
+//   guard (a point exactly at a centre is possible), and so do cylinders (their inner root lies on no such grid).
+//   Upper side, leaves: kept.  No fact of the program excludes a non-finite radicand (the camera and the limits decide it), and a
+//   kernel without this side, sent to the generic root by a test of the culling mask, executes no vector instruction less -- the
+//   per-leaf v_max_u32 are folded two to a v_max3_u32 -- and 3.4 M scalar instructions and 1.4 M branches more per frame
+//   (profiles/r30_range_proofs_ab.txt, "upper side").
+//   A walk class made of boxes alone (rm_jit.h "Single-unit steps") still pays the guard's two v_mov, two v_cmp and the s_or_b64 of
+//   any_bad(): the test stands behind the call, in eval_scene, where the class is not known; left as it is.
+//   Gamma roots (rm_kernel_v5.h, the resolve): the lower side, and the upper side on two of three channels.
+template <bool FAST, bool ZERO_OK = false, bool GUARD_LO = true, bool GUARD_HI = true>
 RM_DEV float sqrt_sel(float x, SqrtGuard& guard) {
     if constexpr (FAST) {
         // x >= +0 or NaN here (sums of squares).  ZERO_OK: (bits - 1) wraps 0 to the top, so only 0 < x < 2^-96 is low.
-        guard.lo = min(guard.lo, ZERO_OK ? __float_as_uint(x) - 1u : __float_as_uint(x));
-        guard.hi = max(guard.hi, __float_as_uint(x));
+        if constexpr (GUARD_LO) guard.lo = min(guard.lo, ZERO_OK ? __float_as_uint(x) - 1u : __float_as_uint(x));
+        if constexpr (GUARD_HI) guard.hi = max(guard.hi, __float_as_uint(x));
         return sqrt_rn_fast<ZERO_OK>(x);
     } else {
         return __builtin_sqrtf(x);
@@ -108,7 +135,7 @@ struct DivGuard {
     RM_DEV void numerator(float a) {
         const uint32_t ua = __float_as_uint(a) & 0x7FFFFFFFu;
         a_lo = min(a_lo, ua - 1u);
-        a_hi = max(a_hi, ua);
+        if constexpr (kNumeratorHi) a_hi = max(a_hi, ua);
     }
     RM_DEV bool bad() const { return d_hi > kBSpan || m_hi >= kMant || a_lo < kALo - 1u || a_hi >= kAHi; }
     RM_DEV bool any_bad() const {  // any lane of the wave, combined on the scalar side like SqrtGuard::any_bad
@@ -130,6 +157,13 @@ RM_DEV float div_rn_fast(float a, float b, float r) {  // r = rcp_rn_fast(b)
 // one exact reciprocal, three short quotients; a wave with any lane outside the DivGuard's range takes the generic form.
 // The guard of one normalisation: the radicand s, its short root b and the three numerators (rm_selftest_normalise reads a
 // lane's verdict from the same function).
+// Lemma (numerators): every numerator a of a normalisation is a number whose square is a term of the radicand s -- the
+// contract forms s = fl(fl(fl(x x) + fl(y y)) + fl(z z)), the ray's with a fourth square added -- and all terms are >= 0, so
+// by the monotonicity of rounding s >= fl(a a) >= a^2 (1 - 2^-24) unless a a underflows (|a| < 2^-63).  Once root_of has let
+// s through, s <= 2^88 (1 + 2^-23): |a| <= sqrt(s) (1 + 2^-24) < 2^44 * 1.000001 < 2^78.  An infinite or NaN numerator makes s
+// non-finite, which root_of rejects.  So a_hi never decides a verdict that root_of has not decided already, and a kernel
+// compiled with the range proofs (kNumeratorHi = false) drops its v_max3_u32 and its compare; a_lo stays (a numerator may
+// well be a nonzero number below 2^-79).
 RM_DEV DivGuard normalize3_guard(float s, float b, float x, float y, float z) {
     DivGuard g;
     g.root_of(s, b);
@@ -177,13 +211,14 @@ RM_DEV float sdf_sphere_t(float px, float py, float pz, const float (&p)[7], Sqr
     const float dx = px - p[0], dy = py - p[1], dz = pz - p[2];
     return sqrt_sel<FAST>((dx * dx + dy * dy) + dz * dz, tiny) - p[3];
 }
-template <bool FAST>
+// BOX_LO: whether the caller's kernel still guards the lower side of a box ("Range proofs" above; spec_box in rm_kernel_v5.h)
+template <bool FAST, bool BOX_LO = true>
 RM_DEV float sdf_box_t(float px, float py, float pz, const float (&p)[7], SqrtGuard& tiny) {
     const float qx = __builtin_fabsf(px - p[0]) - p[3];
     const float qy = __builtin_fabsf(py - p[1]) - p[4];
     const float qz = __builtin_fabsf(pz - p[2]) - p[5];
     const float mx = fmax_(qx, 0.0f), my = fmax_(qy, 0.0f), mz = fmax_(qz, 0.0f);
-    return sqrt_sel<FAST, true>((mx * mx + my * my) + mz * mz, tiny) + fmin_(fmax_(qx, fmax_(qy, qz)), 0.0f);
+    return sqrt_sel<FAST, true, BOX_LO>((mx * mx + my * my) + mz * mz, tiny) + fmin_(fmax_(qx, fmax_(qy, qz)), 0.0f);
 }
 
 template <bool FAST>

@@ -135,7 +135,14 @@ inline int jit_knob(const char* name, int dflt) {
 enum : int { PRUNE_NONE = 0, PRUNE_LATTICE = 1, PRUNE_BLEND = 2 };
 // ... | KERNEL_WITH_STATS: the kernel keeps the per-wave counters of RM_OPT_WAVE_STATS (iterations, live lanes).  A kernel without
 // them -- the default -- saves five scalar instructions per march step (rm_kernel_v5.h, RM_NO_WAVE_STATS)
-enum : int { KERNEL_WITH_STATS = 0x100, PRUNE_KIND_MASK = 0xFF };
+// ... | KERNEL_RANGE_PROVED: the kernel is compiled without the range guards that facts of the program make unnecessary
+// (RM_JIT_RANGE_PROOF in front of the translation unit; rm_interp.h "Range proofs").  Only the kernel of a pruned lattice program
+// without a material phase has such a variant (the kernels the cache is warmed with and the measurements were made on):
+// range_variant() says whether the flag is taken.
+enum : int { KERNEL_WITH_STATS = 0x100, KERNEL_RANGE_PROVED = 0x200, PRUNE_KIND_MASK = 0xFF };
+inline bool range_variant(int prune, bool materials) {
+    return (prune & KERNEL_RANGE_PROVED) != 0 && (prune & PRUNE_KIND_MASK) == PRUNE_LATTICE && !materials;
+}
 
 // Straight-line code for `rec`, mirroring exec_command (rm_interp.h) record by record with the value stack resolved at
 // generation time: the accumulator and every spilled value become named values, no opcode decode, no loop; parameters are
@@ -721,6 +728,7 @@ inline bool generate_source(const std::vector<RmRecord>& rec, const std::vector<
                             bool* walk_generated = nullptr, bool* taps4_generated = nullptr, std::string* capped_out = nullptr) {
     const bool materials = !mrec.empty();
     const bool with_stats = (prune_kind & KERNEL_WITH_STATS) != 0;
+    const bool range_proved = range_variant(prune_kind, materials);
     prune_kind &= PRUNE_KIND_MASK;
     std::string body, taps, walk, unit_walk;
     if (!generate_scene_code(rec, prune_kind, 1, &body, &unit_walk)) return false;
@@ -741,6 +749,7 @@ inline bool generate_source(const std::vector<RmRecord>& rec, const std::vector<
     if (walk_spec) s += "#define RM_JIT_MATERIAL_WALK 1\n";
     if (structure_allows_bound_walk(rec)) s += "#define RM_JIT_BOUND_WALK 1\n";
     if (!with_stats) s += "#define RM_NO_WAVE_STATS 1\n";
+    if (range_proved) s += "#define RM_JIT_RANGE_PROOF 1\n";  // (the functions below are the same text either way: the headers take it)
     if (!unit_walk.empty()) s += "#define RM_JIT_UNIT_WALK 1\n";
     if (prune_kind && jit_knob("RM_JIT_PRUNE_STATS", 0) == 5) s += "#define RM_JIT_WALK_COUNTER 1\n";
     s += "#include \"rm_kernel_v5.h\"\n";
@@ -1027,7 +1036,7 @@ public:
         for (const char* name : knobs)
             if (const char* v = std::getenv(name)) knob_key += std::string("|") + name + "=" + v;
         const std::string key = std::to_string(wpt) + ((prune & PRUNE_KIND_MASK) == PRUNE_LATTICE ? "p" : (prune & PRUNE_KIND_MASK) == PRUNE_BLEND ? "b" : "") +
-                                ((prune & KERNEL_WITH_STATS) ? "s" : "") + ":" + structure_key(rec) +
+                                ((prune & KERNEL_WITH_STATS) ? "s" : "") + (range_variant(prune, !mrec.empty()) ? "r" : "") + ":" + structure_key(rec) +
                                 (mrec.empty() ? "" : "|m:" + structure_key(mrec)) + knob_key;
         std::unique_lock<std::mutex> lk(m_);
         auto it = entries_.find(key);

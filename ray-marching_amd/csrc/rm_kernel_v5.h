@@ -520,10 +520,11 @@ RM_DEV SpecBox spec_box_a(LdsF r, float px, float py, float pz) {
 }
 template <bool FAST>
 RM_DEV float spec_box_v(const SpecBox& b, SqrtGuard& tiny) {
-    return sqrt_sel<FAST, true>(b.a, tiny) + fmin_(fmax_(b.qx, fmax_(b.qy, b.qz)), 0.0f);
+    return sqrt_sel<FAST, true, kBoxGuardLo>(b.a, tiny) + fmin_(fmax_(b.qx, fmax_(b.qy, b.qz)), 0.0f);
 }
 // Leaves and the one operator with a parameter, as the generated code calls them: `r` points at the
-// record's parameters in LDS (wave-uniform address, constant offset: a broadcast read).
+// record's parameters in LDS (wave-uniform address, constant offset: a broadcast read).  A box guards the lower
+// side of its root only where the kernel still has to (kBoxGuardLo: rm_interp.h "Range proofs").
 template <bool FAST>
 RM_DEV float spec_sphere(LdsF r, float qx, float qy, float qz, SqrtGuard& tiny) {
     const lds_f4 c = lds_load4(r);
@@ -535,7 +536,7 @@ RM_DEV float spec_box(LdsF r, float qx, float qy, float qz, SqrtGuard& tiny) {
     const lds_f4 c = lds_load4(r);
     const lds_f2 h = lds_load2(r + 4);
     const float p[7] = {c.x, c.y, c.z, c.w, h.x, h.y, 0.0f};
-    return sdf_box_t<FAST>(qx, qy, qz, p, tiny);
+    return sdf_box_t<FAST, kBoxGuardLo>(qx, qy, qz, p, tiny);
 }
 template <bool FAST>
 RM_DEV float spec_cylinder(LdsF r, float qx, float qy, float qz, SqrtGuard& tiny) {
@@ -1435,8 +1436,15 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
         const uint32_t px = tile_x * 8u + (p & 7u), py = tile_y * 8u + (p >> 3);
         if (px < L.W && py < L.rows) {
             // the 48 gamma square roots of a pixel (wgsl:68) take the short form of the leaves' sqrt (rm_interp.h sqrt_rn_fast:
-            // the same bits for every argument its guard lets through); a colour it does not -- negative, NaN, infinite: only a
-            // material table can produce one -- sends the pixel through the generic form
+            // the same bits for every argument its guard lets through); a colour it does not -- negative or NaN from a material
+            // table, infinite from a table or from a degenerate normal (below) -- sends the pixel through the generic form.
+            // Without a table (kernels compiled with the range proofs have none; rm_interp.h "Range proofs") a colour is 0.4 / 0.7 /
+            // 0.1 times a code that is max(0.02, dot) -- a NaN dot is dropped by the maximum --, or 0.1 / 0.2 plus 0 or 0.2 for the
+            // floor, or 0: never negative, never NaN, and zero or at least 2e-3, so the LOWER side is not guarded.  The UPPER side
+            // is, on one channel: shade_hit divides by a zero root when the three squares of a normal underflow (tap values that
+            // differ by less than 2^-75: radii that small around a camera inside the solid reach it), the dot may then be +inf, and
+            // the three colours are infinite together (0.7 code does not overflow for a finite code): the green one speaks for all.
+            constexpr bool kGammaLo = MAT || !kRangeProved, kGammaHiAll = kGammaLo;
             auto sum_samples = [&](auto fast_tag, float& tr, float& tg, float& tb, SqrtGuard& guard) {
                 constexpr bool FAST = decltype(fast_tag)::value;
                 tr = 0.0f; tg = 0.0f; tb = 0.0f;
@@ -1458,9 +1466,9 @@ RM_DEV void rm_render_v5_body(const RmLaunch& L, const V5Work& work, uint32_t n_
                     } else {
                         cr = 0.0f; cg = 0.0f; cb = 0.0f;  // wgsl:130
                     }
-                    tr += sqrt_sel<FAST, true>(cr, guard);
-                    tg += sqrt_sel<FAST, true>(cg, guard);
-                    tb += sqrt_sel<FAST, true>(cb, guard);
+                    tr += sqrt_sel<FAST, true, kGammaLo, kGammaHiAll>(cr, guard);
+                    tg += sqrt_sel<FAST, true, kGammaLo, true>(cg, guard);
+                    tb += sqrt_sel<FAST, true, kGammaLo, kGammaHiAll>(cb, guard);
                 }
             };
             float tr, tg, tb;

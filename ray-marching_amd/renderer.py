@@ -1656,14 +1656,15 @@ def jit_source(cmd_count, words, waves_per_tile=4, prune=False, env=None):
     return buf.value.decode()
 
 
-def jit_compile(cmd_count, words, waves_per_tile=4, prune=False):
+def jit_compile(cmd_count, words, waves_per_tile=4, prune=False, range_proved=False):
     """rm_jit_compile: compile the specialised kernel for gfx950 with hipRTC, without loading it (no GPU needed).
+    range_proved: the variant without the per-lane range guards (RM_INFO_RANGE_PROOF), for the programs that get one.
     Returns (status, compile_ms, code_bytes, log)."""
     w = np.ascontiguousarray(np.asarray(words, dtype=np.uint32))
     ptr = w.ctypes.data_as(C.POINTER(C.c_uint32)) if w.size else None
     ms, nbytes = C.c_double(0.0), C.c_size_t(0)
     log = C.create_string_buffer(1 << 16)
-    waves_per_tile = int(waves_per_tile) | (_ffi.RM_JIT_PRUNE if prune else 0)
+    waves_per_tile = int(waves_per_tile) | (_ffi.RM_JIT_PRUNE if prune else 0) | (_ffi.RM_JIT_RANGE_PROVED if range_proved else 0)
     rc = _ffi.hip_lib().rm_jit_compile(int(cmd_count), ptr, int(w.size), int(waves_per_tile), C.byref(ms),
                                        C.byref(nbytes), log, len(log))
     return rc, ms.value, nbytes.value, log.value.decode(errors="replace")

@@ -42,14 +42,14 @@ def demangle(n):
         return n
 
 
-def jit_kernel(scene, prune):
+def jit_kernel(scene, prune, range_proved=False):
     from ray_marching_amd import csg, renderer
     cc, words = csg.serialize(csg.scene(scene))
     with tempfile.TemporaryDirectory() as d:
         os.environ["RM_JIT_DUMP_DIR"] = d
         old_cache = os.environ.get("RM_JIT_CACHE_DIR")
         os.environ["RM_JIT_CACHE_DIR"] = "off"       # (a kernel read from the disk cache is not dumped)
-        rc, ms, nbytes, log = renderer.jit_compile(cc, words, prune=prune)
+        rc, ms, nbytes, log = renderer.jit_compile(cc, words, prune=prune, range_proved=range_proved)
         del os.environ["RM_JIT_DUMP_DIR"]
         if old_cache is None:
             del os.environ["RM_JIT_CACHE_DIR"]
@@ -88,13 +88,14 @@ def main():
             r.get("LDS Size [bytes/block]", "?"), r.get("ScratchSize [bytes/lane]", "?")))
     print("\n## specialised march kernel rm_render_v5_spec (hipRTC, per scene structure)")
     for scene in (sys.argv[1:] or ["g8", "g32", "g64", "g32s", "xform_mix", "mat_mix"]):
-        for prune in (False, True):
-            m = jit_kernel(scene, prune)
+        # ("proved": the variant without the per-lane range guards; a program without one compiles to its pruned kernel again)
+        for prune, proved in ((False, False), (True, False), (True, True)):
+            m = jit_kernel(scene, prune, proved)
             if not m:
                 continue
             w, alloc = waves_per_simd(m.get("vgpr_count", 0))
             print("%-10s %-7s VGPRs %3d (alloc %3d -> %d waves/SIMD)  SGPRs %3d  spills s/v %d/%d  static LDS %d B  scratch %d B  kernarg %d B" % (
-                scene, "pruned" if prune else "plain", m.get("vgpr_count", 0), alloc, w, m.get("sgpr_count", 0),
+                scene, "proved" if proved else "pruned" if prune else "plain", m.get("vgpr_count", 0), alloc, w, m.get("sgpr_count", 0),
                 m.get("sgpr_spill_count", 0), m.get("vgpr_spill_count", 0), m.get("group_segment_fixed_size", 0),
                 m.get("private_segment_fixed_size", 0), m.get("kernarg_segment_size", 0)))
 
