@@ -404,6 +404,24 @@ pub const RM_SLICE_POINTS: c_int = 0;
 pub const RM_SLICE_CONTOURS: c_int = 1;
 pub const RM_SLICE_COUNTS: c_int = 2;
 
+// Mesh slicing (rm_slice_mesh; read with rm_read_slices).
+// enum rm_mslicecount: indices into the counts of rm_slice_mesh; RM_MSLICE_COUNTS is their number
+pub const RM_MSLICE_TRIANGLES: c_int = 0;
+pub const RM_MSLICE_REJECTED: c_int = 1;
+pub const RM_MSLICE_PAIRED_EDGES: c_int = 2;
+pub const RM_MSLICE_BORDER_EDGES: c_int = 3;
+pub const RM_MSLICE_BRANCH_EDGES: c_int = 4;
+pub const RM_MSLICE_SEGMENTS: c_int = 5;
+pub const RM_MSLICE_POINTS: c_int = 6;
+pub const RM_MSLICE_CONTOURS: c_int = 7;
+pub const RM_MSLICE_OPEN_CONTOURS: c_int = 8;
+pub const RM_MSLICE_COUNTS: c_int = 9;
+// enum rm_mslicestat: indices into the statistics of rm_slice_mesh; RM_MSLICE_STATS is their number
+pub const RM_MSLICE_STAT_SORT_PASSES: c_int = 0;
+pub const RM_MSLICE_STAT_RANK_ROUNDS: c_int = 1;
+pub const RM_MSLICE_STAT_SCRATCH_BYTES: c_int = 2;
+pub const RM_MSLICE_STATS: c_int = 3;
+
 // Lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit).
 // enum rm_light: indices into the parameter array; RM_LIGHT_PARAMS is its length
 pub const RM_LIGHT_POS_X: c_int = 0;
@@ -541,6 +559,9 @@ extern "C" {
                            out_stats: *mut u64, n_stats: u32) -> c_int;
     pub fn rm_read_class_mesh(ctx: *mut rm_ctx, out_vertices: *mut f32, out_triangles: *mut u32, out_ids: *mut u32, is_device: c_int,
                               stream: *mut c_void) -> c_int;
+    pub fn rm_slice_mesh(ctx: *mut rm_ctx, xyz: *const f32, n_vertices: u32, triangles: *const u32, n_triangles: u32, is_device: c_int,
+                         stream: *mut c_void, origin: *const f32, step: *const f32, axis: u32, heights: *const f32, n_layers: u32,
+                         flags: u32, out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
     pub fn rm_slice_contours(ctx: *mut rm_ctx, axis: u32, origin_uv: *const f32, step_uv: *const f32, nu: u32, nv: u32,
                              heights: *const f32, n_layers: u32, level: f32, flags: u32, out_counts: *mut u64,
                              n_counts: u32) -> c_int;
@@ -567,6 +588,8 @@ extern "C" {
     pub fn rm_selftest_div(ctx: *mut rm_ctx, a: *const f32, b: *const f32, n: u32, seed: u32, n_seeded: u32, out: *mut u64) -> c_int;
     pub fn rm_selftest_normalise(ctx: *mut rm_ctx, input: *const f32, n: u32, mode: c_int, out: *mut u32) -> c_int;
     pub fn rm_selftest_wave(ctx: *mut rm_ctx, input: *const f32, n_waves: u32, out: *mut f32) -> c_int;
+    pub fn rm_selftest_sort(ctx: *mut rm_ctx, keys: *const u64, values: *const u32, n: u32, bits: u32, out_keys: *mut u64,
+                            out_values: *mut u32) -> c_int;
     pub fn rm_selftest_cull_rays(ctx: *mut rm_ctx, origin: *const f32, dirs: *const f32, n: u32, out_flags: *mut u32, out_bound: *mut f32) -> c_int;
     pub fn rm_selftest_cull_pixels(ctx: *mut rm_ctx, w: u32, h: u32, xy: *const u32, n: u32, out: *mut f32) -> c_int;
     pub fn rm_selftest_cull_tiles(ctx: *mut rm_ctx, w: u32, h: u32, xy: *const u32, n: u32, out: *mut f32) -> c_int;
@@ -1368,6 +1391,29 @@ impl RayMarchingResources {
                               level, flags, counts.as_mut_ptr(), RM_SLICE_COUNTS as u32)
         })?;
         let (p, c) = (counts[RM_SLICE_POINTS as usize], counts[RM_SLICE_CONTOURS as usize]);
+        self.slices.set(Some((p, c, heights.len() as u32)));
+        Ok((p, c))
+    }
+
+    /// The outlines of an indexed triangle mesh in host memory in the planes `heights` (strictly increasing) across `axis`
+    /// (`rm_slice_mesh`): `xyz` three floats per vertex, `triangles` three vertex indices per triangle; `origin` and `step` are the
+    /// resolution frame the vertices are snapped in (1 / 64 of a step, as `voxelize_mesh` snaps them).  Fills `out_counts` (at least
+    /// `RM_MSLICE_COUNTS` entries indexed by `RM_MSLICE_*`) and `out_stats` (at least `RM_MSLICE_STATS`, indexed by
+    /// `RM_MSLICE_STAT_*`).  Returns (points, contours); `read_slices` copies points, contours and layer_first out (normals and ids
+    /// are `RM_ERR_ARG`).  A call that fails leaves the previous slices readable.
+    pub fn slice_mesh(&self, xyz: &[f32], triangles: &[u32], origin: [f32; 3], step: [f32; 3], axis: u32, heights: &[f32],
+                      out_counts: &mut [u64], out_stats: &mut [u64]) -> Result<(u64, u64), RmError> {
+        assert!(xyz.len() % 3 == 0 && xyz.len() / 3 <= u32::MAX as usize, "slice_mesh: xyz holds three floats per vertex");
+        assert!(triangles.len() % 3 == 0 && triangles.len() / 3 <= u32::MAX as usize, "slice_mesh: triangles holds three indices per triangle");
+        assert!(heights.len() <= u32::MAX as usize, "slice_mesh: too many heights");
+        assert!(out_counts.len() >= RM_MSLICE_COUNTS as usize, "slice_mesh: out_counts is shorter than RM_MSLICE_COUNTS entries");
+        assert!(out_stats.len() >= RM_MSLICE_STATS as usize, "slice_mesh: out_stats is shorter than RM_MSLICE_STATS entries");
+        self.check(unsafe {
+            rm_slice_mesh(self.ctx, xyz.as_ptr(), (xyz.len() / 3) as u32, triangles.as_ptr(), (triangles.len() / 3) as u32, 0,
+                          std::ptr::null_mut(), origin.as_ptr(), step.as_ptr(), axis, heights.as_ptr(), heights.len() as u32, 0,
+                          out_counts.as_mut_ptr(), RM_MSLICE_COUNTS as u32, out_stats.as_mut_ptr(), RM_MSLICE_STATS as u32)
+        })?;
+        let (p, c) = (out_counts[RM_MSLICE_POINTS as usize], out_counts[RM_MSLICE_CONTOURS as usize]);
         self.slices.set(Some((p, c, heights.len() as u32)));
         Ok((p, c))
     }

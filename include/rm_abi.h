@@ -909,6 +909,42 @@ int rm_read_slices(rm_ctx* ctx, float* out_points, uint32_t* out_contours, uint3
  * around each inside corner.  RM_ERR_ARG when n_out < 80. */
 int rm_slice_case_table(uint32_t* out, uint32_t n_out);
 
+/* Mesh slicing (extension; DESIGN.md section 30 is the contract): the outlines of an INDEXED triangle mesh in a stack of planes,
+ * as the ordered polylines of rm_slice_contours, retained in the same slot and read with rm_read_slices (points, contours,
+ * layer_first; asking for normals or ids is RM_ERR_ARG).  Needs no scene.  xyz: n_vertices x 3 floats, triangles: n_triangles x
+ * 3 u32 (required); host arrays, or with is_device != 0 device arrays (4-byte aligned), read after the work queued on `stream`
+ * (RM_STREAM_OWN: the context's own).  origin and step (host, 3 floats, finite, step > 0) are a resolution frame, not a lattice:
+ * a vertex is snapped exactly as rm_voxelize_mesh snaps it, q = rint(((double)v - o) / s * 64) per axis, valid iff finite and
+ * |q| <= 2^17.  axis = w (0, 1, 2), u = (w + 1) % 3, v = (w + 2) % 3.  heights: a HOST array of n_layers finite floats;
+ * r_k = ((double)h_k - o_w) / s_w * 64 and the plane sits at P2_k = 2 floor(r_k) + 1 in units of 1 / 128 of a step: at most
+ * 1 / 128 of a step from the height asked for, and never through a vertex.  P2 must be strictly increasing.
+ * A triangle with an index >= n_vertices, two equal indices or an invalid corner is REJECTED: counted, and contributes nothing.
+ * Half-edge h = 3 t + s runs from triangles[3 t + s] to triangles[3 t + (s + 1) % 3].  The half-edges of accepted triangles are
+ * grouped by their unordered index pair: two of opposite direction are a PAIRED edge (canonical half-edge: the lower h), one is
+ * a BORDER edge, anything else a BRANCH edge; every half-edge of a border or branch group is its own canonical half-edge.  A
+ * canonical half-edge carries one vertex for each plane strictly between its ends; vertices are ordered by (plane, canonical
+ * half-edge).  A plane that meets an accepted triangle crosses two of its half-edges; the segment runs from the vertex of the one
+ * going down the axis to the vertex of the one going up, so that for triangles wound counter-clockwise seen from outside the
+ * inside is on the left seen from +w: outer boundaries counter-clockwise, holes clockwise.  Segments chain into contours exactly
+ * as rm_slice_contours': a closed one starts at its lowest vertex, an open one at the vertex no segment ends at; ordered by
+ * layer, then first vertex.  The point of the edge A -> B (A_w < B_w, snapped) in plane P2: on a = u, v
+ * g_a = (double)A_a + (double)((B_a - A_a) (P2 - 2 A_w)) / (double)(2 (B_w - A_w)), on w g_w = (double)P2 / 2; the world
+ * coordinate is (float)((double)o_a + g_a / 64 * (double)s_a); no fma.  All outputs are identical from run to run; permuting the
+ * triangles or rotating a triangle's corners changes only where loops start and their order within a layer.
+ * out_counts (enum rm_mslicecount, n_counts >= RM_MSLICE_COUNTS), out_stats (enum rm_mslicestat, n_stats >= RM_MSLICE_STATS).
+ * Refusals, in this order: RM_ERR_NULL for a NULL array; RM_ERR_ARG for n_counts or n_stats too small, flags != 0, axis > 2, an
+ * origin or step that is not finite or a step <= 0, n_vertices = 0; RM_ERR_RANGE for n_layers outside 1..65536 or n_triangles
+ * outside 1..2^28; RM_ERR_ARG for a height that is not finite; RM_ERR_RANGE for |r_k| > 2^18; RM_ERR_ARG when P2 is not strictly
+ * increasing or a device array is misaligned; RM_ERR_RANGE when POINTS does not fit 32 bits; RM_ERR_DEVICE when device memory runs
+ * out.  Every one of them leaves the previous slices readable.  Synchronous; touches no other family's result and no draw state. */
+enum rm_mslicecount { RM_MSLICE_TRIANGLES = 0, RM_MSLICE_REJECTED = 1, RM_MSLICE_PAIRED_EDGES = 2, RM_MSLICE_BORDER_EDGES = 3,
+                      RM_MSLICE_BRANCH_EDGES = 4, RM_MSLICE_SEGMENTS = 5, RM_MSLICE_POINTS = 6, RM_MSLICE_CONTOURS = 7,
+                      RM_MSLICE_OPEN_CONTOURS = 8, RM_MSLICE_COUNTS = 9 };
+enum rm_mslicestat { RM_MSLICE_STAT_SORT_PASSES = 0, RM_MSLICE_STAT_RANK_ROUNDS = 1, RM_MSLICE_STAT_SCRATCH_BYTES = 2, RM_MSLICE_STATS = 3 };
+int rm_slice_mesh(rm_ctx* ctx, const float* xyz, uint32_t n_vertices, const uint32_t* triangles, uint32_t n_triangles, int is_device,
+                  void* stream, const float* origin, const float* step, uint32_t axis, const float* heights, uint32_t n_layers,
+                  uint32_t flags, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats);
+
 /* Lit rendering (extension): rm_draw with soft shadows and ambient occlusion marched through the same distance field
  * (DESIGN.md section 13 is the contract, to the last bit).  The reference has one fixed light and max(0.02, n.l)
  * (wgsl:98-105); with RM_LIGHT_SHADOW = 0 and RM_LIGHT_AO = 0 rm_draw_lit writes rm_draw's image bit for bit.
@@ -1025,6 +1061,12 @@ int rm_selftest_normalise(rm_ctx* ctx, const float* in, uint32_t n, int mode, ui
  * NaN): out[i] = the largest value of input i's wave (by bit pattern: a NaN wins), out[64 n_waves + i] = the minimum over the
  * inputs of the LOWER lanes of its wave (+inf for lane 0; a NaN is skipped).  tests/test_gpu_arithmetic.py compares with numpy. */
 int rm_selftest_wave(rm_ctx* ctx, const float* in, uint32_t n_waves, float* out);
+/* The device sort (csrc/rm_sort.h) on the caller's pairs: host arrays keys[n] (u64) and values[n] (u32), n >= 1, bits in 1..64.
+ * out_keys / out_values: the pairs ordered by the low `bits` bits of their keys, equal ones in input order (stable); key bits above
+ * `bits` travel with their pair and are not compared.  RM_ERR_ARG for n = 0 or bits outside 1..64.  tests/test_gpu_sort.py compares
+ * with numpy's stable argsort. */
+int rm_selftest_sort(rm_ctx* ctx, const uint64_t* keys, const uint32_t* values, uint32_t n, uint32_t bits, uint64_t* out_keys,
+                     uint32_t* out_values);
 /* The culling decisions of the march on inputs the caller chooses (tests/test_gpu_cull_bounds.py compares them with binary64
  * geometry): the device functions of a draw, on the context's current program, limits and options, with the launch a draw would
  * fill and the tables staged as the kernels stage them.  Host arrays only; they wait for the result.

@@ -144,6 +144,15 @@ def RM_SURF_PAIR(a, b, nu):
 
 # slicing (rm_slice_contours / rm_read_slices / rm_slice_case_table): enum rm_slicecount, the indices of out_counts
 RM_SLICE_POINTS, RM_SLICE_CONTOURS, RM_SLICE_COUNTS = 0, 1, 2
+# mesh slicing (rm_slice_mesh; read with rm_read_slices): enum rm_mslicecount, enum rm_mslicestat
+(RM_MSLICE_TRIANGLES, RM_MSLICE_REJECTED, RM_MSLICE_PAIRED_EDGES, RM_MSLICE_BORDER_EDGES, RM_MSLICE_BRANCH_EDGES, RM_MSLICE_SEGMENTS,
+ RM_MSLICE_POINTS, RM_MSLICE_CONTOURS, RM_MSLICE_OPEN_CONTOURS, RM_MSLICE_COUNTS) = range(10)
+MSLICE_COUNT_NAMES = ("triangles", "rejected", "paired_edges", "border_edges", "branch_edges", "segments", "points", "contours",
+                      "open_contours")
+(RM_MSLICE_STAT_SORT_PASSES, RM_MSLICE_STAT_RANK_ROUNDS, RM_MSLICE_STAT_SCRATCH_BYTES, RM_MSLICE_STATS) = range(4)
+MSLICE_STAT_NAMES = ("sort_passes", "rank_rounds", "scratch_bytes")
+# the device sort (csrc/rm_sort.h, rm_selftest_sort): rml::kSortTile, the pairs one workgroup ranks
+SORT_TILE = 1024
 # lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit): enum rm_light, the parameter names in index order
 RM_LIGHT_PARAMS = 13
 LIGHT_NAMES = ("pos_x", "pos_y", "pos_z", "shadow", "shadow_softness", "bias", "shadow_max_t", "shadow_steps", "ao", "ao_step",
@@ -237,6 +246,8 @@ def hip_lib():
         L.rm_selftest_normalise.restype = C.c_int
         L.rm_selftest_wave.argtypes = [vp, vp, u32, vp]
         L.rm_selftest_wave.restype = C.c_int
+        L.rm_selftest_sort.argtypes = [vp, vp, vp, u32, u32, vp, vp]
+        L.rm_selftest_sort.restype = C.c_int
         L.rm_selftest_cull_rays.argtypes = [vp, vp, vp, u32, vp, vp]
         L.rm_selftest_cull_rays.restype = C.c_int
         L.rm_selftest_cull_pixels.argtypes = [vp, u32, u32, vp, u32, vp]
@@ -328,6 +339,8 @@ def hip_lib():
         L.rm_read_slices.restype = C.c_int
         L.rm_slice_case_table.argtypes = [vp, u32]
         L.rm_slice_case_table.restype = C.c_int
+        L.rm_slice_mesh.argtypes = [vp, vp, u32, vp, u32, C.c_int, vp, f3, f3, u32, f3, u32, u32, C.POINTER(u64), u32, C.POINTER(u64), u32]
+        L.rm_slice_mesh.restype = C.c_int
         L.rm_program_lipschitz.argtypes = [u32, C.POINTER(u32), u32, C.POINTER(C.c_double)]
         L.rm_program_lipschitz.restype = C.c_int
         L.rm_lighting_defaults.argtypes = [f3, u32]

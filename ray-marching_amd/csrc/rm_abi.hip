@@ -41,6 +41,8 @@
 #include "rm_lattice.h"
 #include "rm_class_mesh.h"
 #include "rm_slice.h"
+#include "rm_sort.h"
+#include "rm_mesh_slice.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
 
@@ -3374,6 +3376,202 @@ RM_EXPORT int rm_slice_case_table(uint32_t* out, uint32_t n_out) {
     return RM_OK;
 }
 
+// ---- mesh slicing (rm_mesh_slice.h) ----
+namespace {
+
+static_assert(RM_MSLICE_STAT_SCRATCH_BYTES == RM_MSLICE_STATS - 1, "the scratch size last");
+constexpr double kMsliceMaxR = 262144.0;  // |r_k| <= 2^18
+
+// Room for `need` bytes of a retained result WITHOUT touching the buffer that holds the previous one: nothing when it is large
+// enough, else a fresh allocation for the caller to move in once the previous result is dropped.
+int reserve_beside(rm_ctx* c, const DevBuf<char>& current, size_t need, DevBuf<char>& fresh) {
+    return need <= current.cap ? RM_OK : fresh.reserve(c, need, "slices");
+}
+void move_in(DevBuf<char>& current, DevBuf<char>& fresh) {
+    if (fresh.p) current = std::move(fresh);  // (the old buffer goes with `fresh`)
+}
+
+}  // namespace
+
+RM_EXPORT int rm_slice_mesh(rm_ctx* c, const float* xyz, uint32_t n_vertices, const uint32_t* triangles, uint32_t n_triangles, int is_device,
+                            void* stream, const float* origin, const float* step, uint32_t axis, const float* heights, uint32_t n_layers,
+                            uint32_t flags, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
+    const char* fn = "rm_slice_mesh";
+    if (!c) return RM_ERR_NULL;
+    if (!xyz || !triangles || !heights || !out_counts || !out_stats || !origin || !step)
+        return fail(c, RM_ERR_NULL, "%s: xyz, triangles, origin, step, heights, out_counts or out_stats is NULL", fn);
+    if (n_counts < (uint32_t)RM_MSLICE_COUNTS) return fail(c, RM_ERR_ARG, "%s: n_counts %u < RM_MSLICE_COUNTS", fn, n_counts);
+    if (n_stats < (uint32_t)RM_MSLICE_STATS) return fail(c, RM_ERR_ARG, "%s: n_stats %u < RM_MSLICE_STATS", fn, n_stats);
+    if (flags != 0u) return fail(c, RM_ERR_ARG, "%s: flags 0x%x: must be 0", fn, flags);
+    if (axis > 2u) return fail(c, RM_ERR_ARG, "%s: axis %u is not 0, 1 or 2", fn, axis);
+    if (int rc = check_lattice(c, fn, origin, step)) return rc;
+    if (n_vertices == 0u) return fail(c, RM_ERR_ARG, "%s: no vertices", fn);
+    if (n_layers < 1u || n_layers > kMaxDim || n_triangles < 1u || n_triangles > (1u << 28))
+        return fail(c, RM_ERR_RANGE, "%s: %u layers, %u triangles: 1..65536 layers, 1..2^28 triangles", fn, n_layers, n_triangles);
+    // the planes, before the first launch
+    std::vector<int32_t> p2(n_layers);
+    for (uint32_t k = 0; k < n_layers; k++) {
+        if (!std::isfinite(heights[k])) return fail(c, RM_ERR_ARG, "%s: heights[%u] = %g is not finite", fn, k, (double)heights[k]);
+        const double r = ((double)heights[k] - (double)origin[axis]) / (double)step[axis] * 64.0;
+        if (!(std::fabs(r) <= kMsliceMaxR)) return fail(c, RM_ERR_RANGE, "%s: heights[%u] = %g lies more than 4096 steps from the origin", fn, k, (double)heights[k]);
+        p2[k] = 2 * (int32_t)std::floor(r) + 1;
+    }
+    for (uint32_t k = 1; k < n_layers; k++)
+        if (!(p2[k] > p2[k - 1u]))
+            return fail(c, RM_ERR_ARG, "%s: heights[%u] = %g does not lie in a plane above heights[%u] = %g: planes must be strictly increasing", fn, k,
+                        (double)heights[k], k - 1u, (double)heights[k - 1u]);
+    if (is_device && (misaligned(xyz, 4) || misaligned(triangles, 4))) return fail(c, RM_ERR_ARG, "%s: device xyz and triangles need 4-byte alignment", fn);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    order_with_previous(c, s);  // after a device read of the previous slices, too
+    const uint32_t H = 3u * n_triangles;
+    const rml::MeshSliceScratch S(n_vertices, n_triangles, n_layers, is_device ? 0u : n_vertices, is_device ? 0u : n_triangles);
+    int rc = c->d_mscratch.reserve(c, S.bytes);
+    if (rc != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    const float* d_xyz = xyz;
+    const uint32_t* d_tri = triangles;
+    if (is_device) {
+        // the caller's arrays are ready when the work queued on its stream is done; the call is synchronous anyway
+        const hipStream_t su = user_stream(c, stream);
+        if (su != s) HIP_TRY(c, hipStreamSynchronize(su));
+    } else {
+        HIP_TRY(c, hipMemcpyAsync(S.xyz.at(sc), xyz, S.xyz.bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(S.idx.at(sc), triangles, S.idx.bytes, hipMemcpyHostToDevice, s));
+        d_xyz = S.xyz.at(sc);
+        d_tri = S.idx.at(sc);
+    }
+    HIP_TRY(c, hipMemcpyAsync(S.p2.at(sc), p2.data(), (size_t)n_layers * 4u, hipMemcpyHostToDevice, s));
+    rmk::MsliceFrame f{};
+    for (int a = 0; a < 3; a++) f.o[a] = (double)origin[a], f.s[a] = (double)step[a];
+    f.axis = axis, f.n_layers = n_layers;
+    int32_t* vq = S.vq.at(sc);
+    const int32_t* d_p2 = S.p2.at(sc);
+    uint32_t* mate = S.mate.at(sc);
+    uint32_t* estart = S.estart.at(sc);
+    uint32_t* k0 = S.k0.at(sc);
+    // edges: b = the bit length of n_vertices - 1, keys of 2 b bits
+    uint32_t b = 0;
+    while (b < 32u && ((uint64_t)(n_vertices - 1u) >> b) != 0u) b++;
+    const uint32_t edge_bits = std::max(1u, 2u * b), hb = blocks_of(H, 256u), hsb = blocks_of(H, rmk::kSliceBlock);
+    hipLaunchKernelGGL(rmk::rm_mslice_snap_kernel, dim3(blocks_of(n_vertices, 256u)), dim3(256), 0, s, f, n_vertices, d_xyz, vq);
+    hipLaunchKernelGGL(rmk::rm_mslice_keys_kernel, dim3(hb), dim3(256), 0, s, n_vertices, H, b, d_tri, vq, S.hkeys.at(sc), S.hvals.at(sc));
+    const rml::SortedPairs E = rml::sort_pairs(s, S.hkeys.at(sc), S.hvals.at(sc), H, edge_bits, sc + S.sort);
+    hipLaunchKernelGGL(rmk::rm_mslice_groups_kernel, dim3(hb), dim3(256), 0, s, H, d_tri, E.keys, E.values, mate, S.rows.at(sc));
+    hipLaunchKernelGGL(rmk::rm_mslice_count_kernel, dim3(hsb), dim3(256), 0, s, f, n_vertices, H, d_tri, vq, d_p2, mate, estart, k0, S.bsums.at(sc));
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = scan_launch(c, s, S.bsums.at(sc), hsb, S.btot.at(sc))) != RM_OK) return rc;
+    unsigned long long erow[RM_MOMENTS];
+    uint64_t tot[2];
+    if ((rc = reduce_rows(c, s, S.rows.at(sc), hb, S.folded.at(sc), S.result.at(sc), erow, {tot, S.btot.at(sc), sizeof tot})) != RM_OK) return rc;
+    if (tot[0] > 0xFFFFFFFFull) return fail(c, RM_ERR_RANGE, "%s: %llu points: more than 2^32 - 1", fn, (unsigned long long)tot[0]);
+    const uint32_t N = (uint32_t)tot[0];
+    const rml::SliceLayerTables T(n_layers);
+    uint32_t Cb = 0, rounds = 0, item_passes = 0;
+    uint64_t open = 0;
+    size_t scratch_bytes = S.bytes;
+    DevBuf<char> f_points, f_contours, f_layers;
+    if (N == 0u) {
+        if ((rc = reserve_beside(c, c->slices.layers, T.bytes, f_layers)) != RM_OK) return rc;
+        // the last check that can refuse is past: the previous slices go
+        c->slices.drop();
+        move_in(c->slices.layers, f_layers);
+        HIP_TRY(c, hipMemsetAsync(T.layer_first.at(c->slices.layers.p), 0, T.layer_first.bytes, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+    } else {
+        const rml::MeshSliceItems I(N, n_layers);
+        if ((rc = c->d_mbricks.reserve(c, I.bytes)) != RM_OK) return rc;
+        char* ic = c->d_mbricks.p;
+        uint32_t layer_bits = 1;
+        while (layer_bits < 32u && ((n_layers - 1u) >> layer_bits) != 0u) layer_bits++;
+        const uint32_t vb = blocks_of(N, 256u), vsb = blocks_of(N, rmk::kSliceBlock), c_max = N / 2u + 1u;
+        hipLaunchKernelGGL(rmk::rm_mslice_scan_kernel, dim3(hsb), dim3(256), 0, s, H, S.bsums.at(sc), estart);
+        hipLaunchKernelGGL(rmk::rm_mslice_items_kernel, dim3(vb), dim3(256), 0, s, N, H, estart, k0, I.ikeys.at(ic), I.ivals.at(ic));
+        const rml::SortedPairs V = rml::sort_pairs(s, I.ikeys.at(ic), I.ivals.at(ic), N, layer_bits, ic + I.sort);
+        item_passes = V.passes;
+        uint32_t* inv = I.inv.at(ic);
+        uint32_t* vh = I.vh.at(ic);
+        uint32_t* d_base = I.layer_base.at(ic);
+        uint32_t* d_totals = I.totals.at(ic);
+        hipLaunchKernelGGL(rmk::rm_mslice_ids_kernel, dim3(vb), dim3(256), 0, s, N, H, n_layers, estart, V.keys, V.values, inv, vh, d_base);
+        HIP_TRY(c, hipGetLastError());
+        std::vector<uint32_t> base((size_t)n_layers + 1u);
+        HIP_TRY(c, hipMemcpyAsync(base.data(), d_base, base.size() * 4u, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        // ranking rounds: 2^rounds >= the vertices of the fullest layer >= the longest chain
+        uint32_t v_layer = 0;
+        for (uint32_t l = 0; l < n_layers; l++) v_layer = std::max(v_layer, base[l + 1u] - base[l]);
+        while ((1ull << rounds) < v_layer) rounds++;
+        const rml::SliceVertexScratch<uint2> Wk(N, vsb, c_max);
+        if ((rc = c->d_swork.reserve(c, Wk.bytes)) != RM_OK) return rc;
+        scratch_bytes += I.bytes + Wk.bytes;
+        char* wk = c->d_swork.p;
+        uint32_t* next = Wk.next.at(wk);
+        uint32_t* prev = Wk.prev.at(wk);
+        uint2* st_a = Wk.state0.at(wk);
+        uint2* st_b = Wk.state1.at(wk);
+        uint32_t* start = Wk.start.at(wk);
+        uint32_t* vsums = Wk.vsums.at(wk);
+        uint32_t* length = Wk.length.at(wk);
+        uint32_t* first_point = Wk.first_point.at(wk);
+        HIP_TRY(c, hipMemsetAsync(wk, 0xFF, Wk.state0.offset, s));  // next and prev: kSliceNil
+        hipLaunchKernelGGL(rmk::rm_mslice_link_kernel, dim3(vb), dim3(256), 0, s, f, N, d_tri, vq, d_p2, mate, estart, k0, V.keys, vh, inv, next, prev);
+        hipLaunchKernelGGL(rmk::rm_slice_low_init_kernel, dim3(vb), dim3(256), 0, s, next, N, st_a);
+        for (uint32_t r = 0; r < rounds; r++) {
+            hipLaunchKernelGGL(rmk::rm_slice_low_round_kernel, dim3(vb), dim3(256), 0, s, st_a, N, st_b);
+            std::swap(st_a, st_b);
+        }
+        hipLaunchKernelGGL(rmk::rm_slice_cut_kernel, dim3(vb), dim3(256), 0, s, st_a, prev, N, start, st_b);
+        std::swap(st_a, st_b);
+        for (uint32_t r = 0; r < rounds; r++) {
+            hipLaunchKernelGGL(rmk::rm_slice_rank_round_kernel, dim3(vb), dim3(256), 0, s, st_a, N, st_b);
+            std::swap(st_a, st_b);
+        }
+        hipLaunchKernelGGL(rmk::rm_slice_start_count_kernel, dim3(vsb), dim3(256), 0, s, start, N, vsums);
+        hipLaunchKernelGGL(rmk::rm_slice_scan_kernel, dim3(1), dim3(1024), 0, s, vsums, vsb, d_totals + 1);
+        hipLaunchKernelGGL(rmk::rm_slice_start_scan_kernel, dim3(vsb), dim3(256), 0, s, start, N, vsums);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(&Cb, d_totals + 1, 4u, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        if (Cb > c_max) return fail(c, RM_ERR_DEVICE, "%s: %u contours from %u vertices", fn, Cb, N);
+        // every size is known: room for the result beside the previous one, which goes only when nothing can refuse any more
+        if ((rc = reserve_beside(c, c->slices.points, (size_t)N * 12u, f_points)) != RM_OK) return rc;
+        if ((rc = reserve_beside(c, c->slices.contours, (size_t)Cb * 16u, f_contours)) != RM_OK) return rc;
+        if ((rc = reserve_beside(c, c->slices.layers, T.bytes, f_layers)) != RM_OK) return rc;
+        c->slices.drop();
+        move_in(c->slices.points, f_points);
+        move_in(c->slices.contours, f_contours);
+        move_in(c->slices.layers, f_layers);
+        const uint32_t cb = blocks_of(Cb, rmk::kSliceBlock);
+        hipLaunchKernelGGL(rmk::rm_slice_length_kernel, dim3(vb), dim3(256), 0, s, st_a, next, start, N, length);
+        hipLaunchKernelGGL(rmk::rm_slice_length_count_kernel, dim3(cb), dim3(256), 0, s, length, Cb, vsums);
+        hipLaunchKernelGGL(rmk::rm_slice_scan_kernel, dim3(1), dim3(1024), 0, s, vsums, cb, d_totals + 2);
+        hipLaunchKernelGGL(rmk::rm_slice_length_scan_kernel, dim3(cb), dim3(256), 0, s, length, Cb, vsums, first_point);
+        hipLaunchKernelGGL(rmk::rm_slice_layer_first_kernel, dim3(blocks_of(n_layers + 1u, 256u)), dim3(256), 0, s, d_base, n_layers, N, start, Cb, 0u,
+                           T.layer_first.at(c->slices.layers.p));
+        hipLaunchKernelGGL(rmk::rm_mslice_emit_kernel, dim3(vb), dim3(256), 0, s, f, N, d_tri, vq, d_p2, V.keys, vh, prev, st_a, start, length, first_point,
+                           c->slices.points.as<float>(), c->slices.contours.as<uint4>(), I.rows.at(ic));
+        HIP_TRY(c, hipGetLastError());
+        unsigned long long vrow[RM_MOMENTS];
+        if ((rc = reduce_rows(c, s, I.rows.at(ic), vb, I.folded.at(ic), I.result.at(ic), vrow)) != RM_OK) return rc;
+        open = vrow[0];
+    }
+    out_counts[RM_MSLICE_TRIANGLES] = n_triangles;
+    out_counts[RM_MSLICE_REJECTED] = erow[3];
+    out_counts[RM_MSLICE_PAIRED_EDGES] = erow[0];
+    out_counts[RM_MSLICE_BORDER_EDGES] = erow[1];
+    out_counts[RM_MSLICE_BRANCH_EDGES] = erow[2];
+    out_counts[RM_MSLICE_SEGMENTS] = (uint64_t)N - open;  // a closed contour has a segment per point, an open one one fewer
+    out_counts[RM_MSLICE_POINTS] = N;
+    out_counts[RM_MSLICE_CONTOURS] = Cb;
+    out_counts[RM_MSLICE_OPEN_CONTOURS] = open;
+    out_stats[RM_MSLICE_STAT_SORT_PASSES] = E.passes + item_passes;
+    out_stats[RM_MSLICE_STAT_RANK_ROUNDS] = rounds;
+    out_stats[RM_MSLICE_STAT_SCRATCH_BYTES] = scratch_bytes;
+    c->slices.commit(N, Cb, n_layers, 0u);
+    return RM_OK;
+}
+
 RM_EXPORT int rm_sync_context(rm_ctx* c) {
     if (!c) return RM_ERR_NULL;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -3584,6 +3782,31 @@ RM_EXPORT int rm_selftest_wave(rm_ctx* c, const float* in, uint32_t n_waves, flo
     }
     if (e == hipSuccess) e = hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(c, RM_ERR_DEVICE, "rm_selftest_wave: %s", hipGetErrorString(e));
+    return RM_OK;
+}
+
+RM_EXPORT int rm_selftest_sort(rm_ctx* c, const uint64_t* keys, const uint32_t* values, uint32_t n, uint32_t bits, uint64_t* out_keys,
+                               uint32_t* out_values) {
+    if (!c) return RM_ERR_NULL;
+    if (!keys || !values || !out_keys || !out_values) return fail(c, RM_ERR_NULL, "rm_selftest_sort: NULL argument");
+    if (n == 0u || bits < 1u || bits > 64u) return fail(c, RM_ERR_ARG, "rm_selftest_sort: n = %u, bits = %u: n >= 1, bits in 1..64", n, bits);
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<unsigned long long> dk;
+    DevBuf<uint32_t> dv;
+    DevBuf<char> scratch;
+    if (int rc = dk.reserve(c, n)) return rc;
+    if (int rc = dv.reserve(c, n)) return rc;
+    if (int rc = scratch.reserve(c, rml::SortScratch(n).bytes)) return rc;
+    hipError_t e = hipMemcpy(dk.p, keys, (size_t)n * 8u, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dv.p, values, (size_t)n * 4u, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const rml::SortedPairs r = rml::sort_pairs(c->stream, dk.p, dv.p, n, bits, scratch.p);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(out_keys, r.keys, (size_t)n * 8u, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out_values, r.values, (size_t)n * 4u, hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) return fail(c, RM_ERR_DEVICE, "rm_selftest_sort: %s", hipGetErrorString(e));
     return RM_OK;
 }
 

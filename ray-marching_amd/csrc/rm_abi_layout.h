@@ -367,6 +367,69 @@ struct SliceAttributes {
         : normals(a.take<float>(with_normals ? P * 3u : 0u)), ids(a.take<uint32_t>(with_ids ? P * 2u : 0u)), bytes(a.total) {}
 };
 
+// rml::sort_pairs (rm_sort.h), for n pairs in sort_tiles(n) tiles of kSortTile: the second buffer of each ping-pong pair (keys 8 B,
+// values 4 B), the table of digit counts [kSortDigits][tiles] (4 B each; scanned in place into output positions), per kSortTile
+// table entries a block sum (scanned in place) and the two totals.
+constexpr uint32_t kSortTile = 1024u, kSortDigits = 256u;
+constexpr uint32_t sort_tiles(uint32_t n) { return (uint32_t)(((uint64_t)n + kSortTile - 1u) / kSortTile); }
+constexpr uint32_t sort_passes(uint32_t bits) { return (bits + 7u) / 8u; }
+constexpr uint32_t sort_table_blocks(uint32_t n) { return (uint32_t)(((uint64_t)sort_tiles(n) * kSortDigits + kSortTile - 1u) / kSortTile); }
+struct SortScratch {
+    Carver a;
+    Region<unsigned long long> keys;
+    Region<uint32_t> values, table;
+    Region<unsigned long long> bsums, btot;
+    size_t bytes;
+    explicit SortScratch(uint32_t n)
+        : keys(a.take<unsigned long long>(n)), values(a.take<uint32_t>(n)), table(a.take<uint32_t>((size_t)sort_tiles(n) * kSortDigits)),
+          bsums(a.take<unsigned long long>(sort_table_blocks(n))), btot(a.take<unsigned long long>(2)), bytes(a.total) {}
+};
+
+// rm_slice_mesh, for a mesh of n_vertices vertices and n_triangles triangles (H = 3 n_triangles half-edges) cut by n_layers planes:
+// per vertex its snapped coordinates (3 i32; the first is kMsliceBad for a vertex that does not snap); per plane its doubled
+// position P2 (i32); per half-edge its sort key (8 B) and number (4 B), its mate (4 B), the vertices before its own in edge-major
+// order (H + 1 entries: the last is their number) and its first plane (4 B); per kSortTile half-edges a block sum, the totals;
+// one row of 16 counts per 256 half-edges, per 256 rows a folded row, the reduced row; the edge sort's scratch; and the copies of a
+// caller's host arrays (empty for device inputs).
+constexpr int32_t kMsliceBad = 0x7FFFFFFF;
+struct MeshSliceScratch {
+    Carver a;
+    Region<int32_t> vq, p2;
+    Region<unsigned long long> hkeys;
+    Region<uint32_t> hvals, mate, estart, k0;
+    Region<unsigned long long> bsums, btot, rows, folded, result;
+    Region<float> xyz;
+    Region<uint32_t> idx;
+    size_t sort, bytes;  // sort: where the SortScratch of the half-edges begins
+    MeshSliceScratch(uint32_t n_vertices, uint32_t n_triangles, uint32_t n_layers, uint64_t host_vertices, uint64_t host_triangles)
+        : vq(a.take<int32_t>((size_t)n_vertices * 3u)), p2(a.take<int32_t>(n_layers)), hkeys(a.take<unsigned long long>((size_t)n_triangles * 3u)),
+          hvals(a.take<uint32_t>((size_t)n_triangles * 3u)), mate(a.take<uint32_t>((size_t)n_triangles * 3u)),
+          estart(a.take<uint32_t>((size_t)n_triangles * 3u + 1u)), k0(a.take<uint32_t>((size_t)n_triangles * 3u)),
+          bsums(a.take<unsigned long long>(sort_tiles(n_triangles * 3u))), btot(a.take<unsigned long long>(2)),
+          rows(a.take<unsigned long long>((size_t)((n_triangles * 3u + 255u) / 256u) * 16u)),
+          folded(a.take<unsigned long long>((size_t)(((n_triangles * 3u + 255u) / 256u + 255u) / 256u) * 16u)),
+          result(a.take<unsigned long long>(16)), xyz(a.take<float>(host_vertices * 3u)), idx(a.take<uint32_t>(host_triangles * 3u)),
+          sort(a.total), bytes(a.total + SortScratch(n_triangles * 3u).bytes) {}
+};
+
+// ... and per vertex of the slices (N of them; an ITEM is a vertex in edge-major order, its ID its place in layer-major order):
+// the item's sort key (its plane, 8 B) and number (4 B), the id of each item and the canonical half-edge of each id (4 B each), the
+// first id of each layer (n_layers + 1 entries), the ranking scans' totals, one row of 16 counts per 256 vertices with their
+// folded rows and the reduced row, and the item sort's scratch.
+struct MeshSliceItems {
+    Carver a;
+    Region<unsigned long long> ikeys;
+    Region<uint32_t> ivals, inv, vh, layer_base, totals;
+    Region<unsigned long long> rows, folded, result;
+    size_t sort, bytes;
+    MeshSliceItems(uint32_t N, uint32_t n_layers)
+        : ikeys(a.take<unsigned long long>(N)), ivals(a.take<uint32_t>(N)), inv(a.take<uint32_t>(N)), vh(a.take<uint32_t>(N)),
+          layer_base(a.take<uint32_t>((size_t)n_layers + 1u)), totals(a.take<uint32_t>(4)),
+          rows(a.take<unsigned long long>(((size_t)N + 255u) / 256u * 16u)),
+          folded(a.take<unsigned long long>((((size_t)N + 255u) / 256u + 255u) / 256u * 16u)), result(a.take<unsigned long long>(16)),
+          sort(a.total), bytes(a.total + SortScratch(N).bytes) {}
+};
+
 // rm_trace_rays' scratch of the attribute pass over n rays (nb workgroups of 256) with K event slots each: the stored count
 // per ray, the workgroups' sums (scanned in place into offsets), the total (2 of 4 words), the compact (ray, slot) list -- K
 // entries per ray at most -- and, only when the caller takes no event records, a copy of them for the positions.  Pair is the

@@ -200,4 +200,16 @@ struct VoxFillLds {
     RM_LDS_FN VoxFillLds() : raw(0u), prefix((raw + kVoxFillMaxWords * 4u + 15u) & ~15u), bytes(prefix + kVoxFillMaxWords * 4u) {}
 };
 
+// ---- Device sort (rm_sort.h rm_sort_count_kernel, rm_sort_scatter_kernel) -----------------------------------------------------
+// STATIC LDS of a workgroup of kSortWaves waves working one tile of kSortRounds * 64 pairs.  ROUND r = it * kSortWaves + wave holds
+// the 64 pairs the wave loads in its pass `it` over the tile, and the rounds in this order are the tile in input order.  One row
+// of kSortLdsDigits words per round, digit d of round r at word r * kSortLdsDigits + d: first the round's count of the digit,
+// then (the scatter) the output position of the round's first pair with it.  Every word has one writer between two barriers.
+// (The tile itself is rml::kSortTile in rm_abi_layout.h, which sizes the global tables from it.)
+constexpr uint32_t kSortWaves = 4u, kSortRounds = 16u, kSortLdsDigits = 256u;
+struct SortLds {
+    uint32_t rows, bytes;
+    RM_LDS_FN SortLds() : rows(0u), bytes(rows + kSortRounds * kSortLdsDigits * 4u) {}
+};
+
 }  // namespace rml

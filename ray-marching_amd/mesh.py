@@ -54,6 +54,26 @@ class Mesh:
         return bool(np.array_equal(fwd, rev) and np.array_equal(nf, nr))
 
 
+def weld(mesh):
+    """The mesh with vertices of identical binary32 coordinates (-0 folded into +0) united and the triangles re-indexed: what a
+    soup (read_stl) needs before RayMarchingResources.slice_mesh, which pairs edges by vertex index.  On the host.  A vertex keeps
+    the place of its first occurrence; a NaN coordinate unites only with the same bit pattern; per-vertex attributes are dropped
+    (the united vertices need not agree on them)."""
+    m = mesh.numpy()
+    v = np.ascontiguousarray(np.asarray(m.vertices, dtype=np.float32).reshape(-1, 3)) + np.float32(0.0)   # (-0 + 0 = +0)
+    if len(v) == 0:
+        return Mesh(v, np.asarray(m.triangles).astype(np.uint32).reshape(-1, 3))
+    bits = v.view(np.uint32).reshape(-1, 3)
+    _, first, inverse = np.unique(bits, axis=0, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")                 # the united vertices by first occurrence
+    place = np.empty(len(order), dtype=np.int64)
+    place[order] = np.arange(len(order))
+    t = np.asarray(m.triangles).astype(np.int64).reshape(-1, 3)
+    inside = t < len(v)
+    new = np.where(inside, place[inverse.reshape(-1)][np.where(inside, t, 0)], 0xFFFFFFFF)      # (an index out of range stays out of range)
+    return Mesh(v[first[order]], new.astype(np.uint32))
+
+
 def write_obj(mesh, path):
     """Wavefront OBJ: v, vn (when the mesh has normals) and f lines, 1-based."""
     m = mesh.numpy()

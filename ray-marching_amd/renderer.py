@@ -1014,6 +1014,7 @@ class RayMarchingResources:
         counts = (C.c_uint64 * _ffi.RM_SLICE_COUNTS)()
         self._check(self._L.rm_slice_contours(self._h, axis, fp(o), fp(s), nu, nv, fp(h), len(h), float(level), flags, counts,
                                               _ffi.RM_SLICE_COUNTS))
+        self._advance(self._L.rm_slice_contours, "slices")
         return self._read_slices(int(counts[_ffi.RM_SLICE_POINTS]), int(counts[_ffi.RM_SLICE_CONTOURS]), axis, h, (o, s, (nu, nv)),
                                  normals, ids, device)
 
@@ -1024,6 +1025,72 @@ class RayMarchingResources:
                                                                          ((len(heights) + 1,), *_U32, True), ((P, 3), *_F32, normals),
                                                                          ((P, 2), *_U32, ids)], device)
         return _slicer.Slices(pts, con, lf, heights, axis, nrm, idv[:, 0] if ids else None, idv[:, 1] if ids else None, lattice)
+
+    # -- mesh slicing (rm_slice_mesh; the slices are read with rm_read_slices) -------------------------------------------------------
+    @staticmethod
+    def _mesh_extent(vertices):
+        """(lo, hi) float64 (3,) over the finite coordinates of (n, 3) vertices (numpy, or a torch tensor)."""
+        v = vertices.vertices if hasattr(vertices, "vertices") else vertices
+        if type(v).__module__.split(".")[0] == "torch":
+            import torch
+            finite = torch.where(torch.isfinite(v), v, torch.full_like(v, float("nan")))
+            lo = torch.nan_to_num(finite, nan=float("inf")).amin(dim=0).cpu().numpy().astype(np.float64)
+            hi = torch.nan_to_num(finite, nan=float("-inf")).amax(dim=0).cpu().numpy().astype(np.float64)
+        else:
+            a = np.asarray(v, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+            a = np.where(np.isfinite(a), a, np.nan)
+            with np.errstate(all="ignore"):
+                lo, hi = np.nanmin(a, axis=0), np.nanmax(a, axis=0)
+        if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.max(hi - lo) > 0):
+            raise ValueError("the mesh has no finite extent")
+        return lo, hi
+
+    def slice_mesh(self, vertices, triangles=None, origin=(0.0, 0.0, 0.0), step=(1.0, 1.0, 1.0), axis=2, heights=None, layer_height=None,
+                   device=False):
+        """rm_slice_mesh: the outlines of an indexed triangle mesh in planes across `axis` (0, 1, 2 or "x", "y", "z"): a
+        slicer.Slices with lattice None, and with `counts` and `stats` (dicts: _ffi.MSLICE_COUNT_NAMES, MSLICE_STAT_NAMES).
+        vertices (n, 3) float32 and triangles (m, 3) indices as numpy arrays, or contiguous torch tensors on this context's GPU
+        (indices int32), or a mesh.Mesh in place of both; a soup (mesh.read of an STL) goes through mesh.weld first.  origin and
+        step are the resolution frame: vertices are snapped to 1 / 64 of a step from origin, as voxelize_mesh snaps them, and a
+        plane lies within 1 / 128 of a step of its height.  Give either `heights` (strictly increasing planes) or `layer_height`:
+        mid-layer heights over the mesh's extent on the axis.  Needs no scene.  device=True: torch tensors on the GPU."""
+        if (heights is None) == (layer_height is None):
+            raise ValueError("give either heights or layer_height")
+        axis = self._slice_axis(axis)
+        nv, xyz, nt, idx, is_device, stream, keep = self._mesh_arg(vertices, triangles)
+        if keep[1] is None:
+            raise ValueError("slice_mesh takes an indexed mesh: triangles are required (mesh.weld makes a soup one)")
+        o = np.array(origin, dtype=np.float32, copy=True).reshape(-1)
+        st = np.array(step, dtype=np.float32, copy=True).reshape(-1)
+        if o.shape != (3,) or st.shape != (3,):
+            raise ValueError("origin and step must have 3 entries each")
+        if heights is None:
+            lo, hi = self._mesh_extent(vertices)
+            heights = self._layer_heights(lo[axis], hi[axis], layer_height)
+        h = np.array(heights, dtype=np.float32, copy=True).reshape(-1)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        counts, stats = (C.c_uint64 * _ffi.RM_MSLICE_COUNTS)(), (C.c_uint64 * _ffi.RM_MSLICE_STATS)()
+        fn = self._L.rm_slice_mesh
+        self._check(fn(self._h, xyz, nv, idx, nt, is_device, stream, fp(o), fp(st), axis, fp(h), len(h), 0, counts, _ffi.RM_MSLICE_COUNTS,
+                       stats, _ffi.RM_MSLICE_STATS))
+        self._advance(fn, "slices")
+        del keep
+        s = self._read_slices(int(counts[_ffi.RM_MSLICE_POINTS]), int(counts[_ffi.RM_MSLICE_CONTOURS]), axis, h, None, False, False, device)
+        s.counts, s.stats = _named(counts, _ffi.MSLICE_COUNT_NAMES), _named(stats, _ffi.MSLICE_STAT_NAMES)
+        return s
+
+    def slice_mesh_box(self, vertices, triangles=None, axis=2, layer_height=None, resolution=1024, device=False):
+        """slice_mesh in a resolution frame chosen from the mesh's bounding box (over its finite coordinates), as voxelize_mesh_box
+        chooses its lattice: origin at the box's lower corner, one step for all three axes, `resolution` points along the longest
+        one.  Layers at the mid-layer heights lo_w + (k + 0.5) * layer_height while below hi_w."""
+        resolution = int(resolution)
+        if resolution < 2 or resolution > 2048:
+            raise ValueError("resolution %d: 2..2048 points along the longest axis" % resolution)
+        if layer_height is None:
+            raise ValueError("slice_mesh_box needs a layer_height")
+        lo, hi = self._mesh_extent(vertices)
+        step = float(np.max(hi - lo)) / (resolution - 1)
+        return self.slice_mesh(vertices, triangles, lo, (step, step, step), axis, layer_height=layer_height, device=device)
 
     def read_slices_device(self, points_ptr=0, contours_ptr=0, layer_first_ptr=0, normals_ptr=0, ids_ptr=0, stream=None):
         """rm_read_slices of the last slice call into device memory (integer addresses; 0 = not wanted), asynchronous."""
@@ -1060,7 +1127,7 @@ class RayMarchingCallback:
 
 # The outputs of the lattice analyses (RayMarchingResources._solid_grid_call): the families of retained results a call replaces
 # (a new distance volume has no mask), how many counts and statistics, and their names.
-_FAMILIES = ("topology", "distance", "distance_mask", "support", "islands", "voxels", "lattice", "class_mesh")
+_FAMILIES = ("topology", "distance", "distance_mask", "support", "islands", "voxels", "lattice", "class_mesh", "slices")
 _TOPO_OUTPUTS = (("topology",), _ffi.RM_TOPO_COUNTS, _ffi.RM_TOPO_STATS, _ffi.TOPO_COUNT_NAMES, _ffi.TOPO_STAT_NAMES)
 _DIST_OUTPUTS = (("distance", "distance_mask"), _ffi.RM_DIST_COUNTS, _ffi.RM_DIST_STATS, _ffi.DIST_COUNT_NAMES, _ffi.DIST_STAT_NAMES)
 _SUP_OUTPUTS = (("support",), _ffi.RM_SUP_COUNTS, _ffi.RM_SUP_STATS, _ffi.SUP_COUNT_NAMES, _ffi.SUP_STAT_NAMES)

@@ -4,6 +4,11 @@ polylines -- and their files: SVG (section drawings) and an ASCII layer file in 
   python -m ray_marching_amd.slicer --scene g8 --axis y --lo -2 --hi 2 --res 1024 --layer-height 0.05 out.svg
 
 slices a named scene (csg.scene) on the GPU and writes the layers; the format follows the file's extension (.svg, .cli).
+
+  python -m ray_marching_amd.slicer --mesh part.stl --axis z --layer-height 0.2 out.svg
+
+slices a mesh file (mesh.read: STL, OBJ, PLY; welded first) instead, prints its counts as one JSON object, and with
+--fail-on "open_contours>0,branch_edges>0,border_edges>0" exits with status 2 when a gate trips.
 Seen from the positive end of the slicing axis, outer boundaries run counter-clockwise and holes clockwise.  A contour is
 open where the outline leaves the box [lo, hi]."""
 import argparse
@@ -29,6 +34,8 @@ class Slices:
     u = (w + 1) % 3 and v = (w + 2) % 3; per point, when computed: normals (P, 3), leaf and material (P,) (rm_query_points
     at the points), else None.  lattice: (origin_uv, step_uv, (nu, nv)) of the layers, or None."""
 
+    counts = stats = None     # of a mesh slicing (RayMarchingResources.slice_mesh): dicts, else None
+
     def __init__(self, points, contours, layer_first, heights, axis, normals=None, leaf=None, material=None, lattice=None):
         self.points, self.contours, self.layer_first = points, contours, layer_first
         self.heights, self.axis = np.asarray(heights, dtype=np.float32), int(axis)
@@ -39,8 +46,10 @@ class Slices:
 
     def numpy(self):
         """These slices with numpy arrays (contours and layer_first as uint32)."""
-        return Slices(_numpy(self.points), _unsigned(_numpy(self.contours)), _unsigned(_numpy(self.layer_first)), self.heights,
-                      self.axis, _numpy(self.normals), _unsigned(_numpy(self.leaf)), _unsigned(_numpy(self.material)), self.lattice)
+        s = Slices(_numpy(self.points), _unsigned(_numpy(self.contours)), _unsigned(_numpy(self.layer_first)), self.heights,
+                   self.axis, _numpy(self.normals), _unsigned(_numpy(self.leaf)), _unsigned(_numpy(self.material)), self.lattice)
+        s.counts, s.stats = self.counts, self.stats
+        return s
 
     @property
     def in_plane_axes(self):
@@ -153,9 +162,60 @@ def _values(text, kind, name, counts):
     return v
 
 
+_GATE_OPS = {">=": lambda a, b: a >= b, "<=": lambda a, b: a <= b, "==": lambda a, b: a == b, "!=": lambda a, b: a != b,
+             ">": lambda a, b: a > b, "<": lambda a, b: a < b}
+
+
+def parse_gates(text, names):
+    """'open_contours>0,branch_edges>0' -> [(name, op, value)]; names: the counts a gate may test."""
+    gates = []
+    for term in (t.strip() for t in text.split(",") if t.strip()):
+        for op in (">=", "<=", "==", "!=", ">", "<"):
+            if op in term:
+                name, value = (x.strip() for x in term.split(op, 1))
+                break
+        else:
+            raise SystemExit("--fail-on: %r has no comparison (>, >=, <, <=, ==, !=)" % term)
+        if name not in names:
+            raise SystemExit("--fail-on: %r is not one of %s" % (name, ", ".join(names)))
+        try:
+            gates.append((name, op, int(value)))
+        except ValueError:
+            raise SystemExit("--fail-on: %r is not an integer" % value)
+    return gates
+
+
+def tripped_gates(gates, counts):
+    """The gates of parse_gates that hold for `counts`, as text."""
+    return ["%s%s%d" % (n, op, v) for n, op, v in gates if _GATE_OPS[op](int(counts[n]), v)]
+
+
+def _main_mesh(a):
+    import json
+    from . import _ffi, mesh as _mesh, renderer
+    gates = parse_gates(a.fail_on, _ffi.MSLICE_COUNT_NAMES) if a.fail_on else []
+    if a.layer_height is None:
+        raise SystemExit("--mesh needs --layer-height")
+    m = _mesh.weld(_mesh.read(a.mesh))
+    res = renderer.RayMarchingResources(a.device)
+    try:
+        s = res.slice_mesh_box(m, axis=a.axis, layer_height=a.layer_height, resolution=int(_values(a.res, int, "--res", (2,))[0]))
+    finally:
+        res.close()
+    write(s, a.out)
+    print(json.dumps(dict(s.counts, layers=len(s.heights), out=a.out)))
+    bad = tripped_gates(gates, s.counts)
+    if bad:
+        print("gate tripped: %s" % ", ".join(bad), file=sys.stderr)
+        return 2
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m ray_marching_amd.slicer", description=__doc__.split("\n\n")[0])
     ap.add_argument("--scene", default="g32", help="a csg.scene name (g1, g8, g32, g32_balanced, mat_mix, ...)")
+    ap.add_argument("--mesh", default=None, help="slice this mesh file (.stl, .obj, .ply) instead of a scene; takes --axis, --layer-height, --res")
+    ap.add_argument("--fail-on", default=None, help='with --mesh: gates on the counts, e.g. "open_contours>0,branch_edges>0,border_edges>0"; exit 2 when one trips')
     ap.add_argument("--axis", default="y", help="the slicing axis: x, y or z (default y: the floor's up axis)")
     ap.add_argument("--lo", default="-3", help="lower box corner: one value for all axes, or x,y,z")
     ap.add_argument("--hi", default="3", help="upper box corner: one value, or x,y,z")
@@ -168,6 +228,10 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.axis not in ("x", "y", "z"):
         raise SystemExit("--axis takes x, y or z, not %r" % a.axis)
+    if a.mesh is not None:
+        return _main_mesh(a)
+    if a.fail_on is not None:
+        raise SystemExit("--fail-on goes with --mesh")
     if (a.heights is None) == (a.layer_height is None):
         raise SystemExit("give either --layer-height or --heights")
     heights = None
