@@ -421,6 +421,20 @@ pub const RM_MSLICE_STAT_SORT_PASSES: c_int = 0;
 pub const RM_MSLICE_STAT_RANK_ROUNDS: c_int = 1;
 pub const RM_MSLICE_STAT_SCRATCH_BYTES: c_int = 2;
 pub const RM_MSLICE_STATS: c_int = 3;
+// Hatching (rm_hatch_slices / rm_read_hatch).
+// enum rm_hatchflag
+pub const RM_HATCH_ZIGZAG: c_int = 1;
+// enum rm_hatchcount: indices into the counts of rm_hatch_slices; RM_HATCH_COUNTS is their number
+pub const RM_HATCH_SEGMENTS_IN: c_int = 0;
+pub const RM_HATCH_CROSSINGS: c_int = 1;
+pub const RM_HATCH_SEGMENTS: c_int = 2;
+pub const RM_HATCH_LINES_HIT: c_int = 3;
+pub const RM_HATCH_ODD_LINES: c_int = 4;
+pub const RM_HATCH_COUNTS: c_int = 5;
+// enum rm_hatchstat: indices into the statistics of rm_hatch_slices; RM_HATCH_STATS is their number
+pub const RM_HATCH_STAT_SORT_PASSES: c_int = 0;
+pub const RM_HATCH_STAT_SCRATCH_BYTES: c_int = 1;
+pub const RM_HATCH_STATS: c_int = 2;
 
 // Lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit).
 // enum rm_light: indices into the parameter array; RM_LIGHT_PARAMS is its length
@@ -562,6 +576,10 @@ extern "C" {
     pub fn rm_slice_mesh(ctx: *mut rm_ctx, xyz: *const f32, n_vertices: u32, triangles: *const u32, n_triangles: u32, is_device: c_int,
                          stream: *mut c_void, origin: *const f32, step: *const f32, axis: u32, heights: *const f32, n_layers: u32,
                          flags: u32, out_counts: *mut u64, n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_hatch_slices(ctx: *mut rm_ctx, lines: *const f32, n_layers: u32, n_lines: u32, flags: u32, out_counts: *mut u64,
+                           n_counts: u32, out_stats: *mut u64, n_stats: u32) -> c_int;
+    pub fn rm_read_hatch(ctx: *mut rm_ctx, out_segments: *mut f32, out_line: *mut u32, out_layer_first: *mut u32, is_device: c_int,
+                         stream: *mut c_void) -> c_int;
     pub fn rm_slice_contours(ctx: *mut rm_ctx, axis: u32, origin_uv: *const f32, step_uv: *const f32, nu: u32, nv: u32,
                              heights: *const f32, n_layers: u32, level: f32, flags: u32, out_counts: *mut u64,
                              n_counts: u32) -> c_int;
@@ -701,6 +719,7 @@ pub struct RayMarchingResources {
     /// (points, contours, layers) of the slices the context holds since the last successful `slice_contours`: what
     /// `read_slices` writes, so what its slices must hold
     slices: Cell<Option<(u64, u64, u32)>>,
+    hatch: Cell<Option<(u64, u32)>>,  // (segments, layers) of the last hatch of the current slices
     /// (bodies, cavities, lattice points) of the last successful labelling call: what `read_topology` writes
     topology: Cell<Option<(u64, u64, u64)>>,
     /// (lattice points, whether a features call has made a mask) of the last successful distance call: what `read_distance` writes
@@ -726,7 +745,7 @@ impl RayMarchingResources {
             let msg = unsafe { CStr::from_ptr(rm_last_error(std::ptr::null_mut())) };
             return Err(RmError { status: rc, message: msg.to_string_lossy().into_owned() });
         }
-        Ok(Self { ctx, mesh: Cell::new(None), slices: Cell::new(None), topology: Cell::new(None), distance: Cell::new(None),
+        Ok(Self { ctx, mesh: Cell::new(None), slices: Cell::new(None), hatch: Cell::new(None), topology: Cell::new(None), distance: Cell::new(None),
                   support: Cell::new(None), islands: Cell::new(None), voxels: Cell::new(None),
                   class_mesh: Cell::new(None) })
     }
@@ -1386,6 +1405,7 @@ impl RayMarchingResources {
         assert!(heights.len() <= u32::MAX as usize, "slice_contours: too many heights");
         let mut counts = [0u64; RM_SLICE_COUNTS as usize];
         self.slices.set(None);  // a failed call may have released the previous slices
+        self.hatch.set(None);  // ... and a hatch is of the slices it was made of
         self.check(unsafe {
             rm_slice_contours(self.ctx, axis, origin_uv.as_ptr(), step_uv.as_ptr(), nu, nv, heights.as_ptr(), heights.len() as u32,
                               level, flags, counts.as_mut_ptr(), RM_SLICE_COUNTS as u32)
@@ -1415,6 +1435,7 @@ impl RayMarchingResources {
         })?;
         let (p, c) = (out_counts[RM_MSLICE_POINTS as usize], out_counts[RM_MSLICE_CONTOURS as usize]);
         self.slices.set(Some((p, c, heights.len() as u32)));
+        self.hatch.set(None);
         Ok((p, c))
     }
 
@@ -1440,6 +1461,41 @@ impl RayMarchingResources {
         let pn = out_normals.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
         let pi = out_ids.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
         self.check(unsafe { rm_read_slices(self.ctx, pp, pc, pl, pn, pi, 0, std::ptr::null_mut()) })
+    }
+
+    /// The retained slices filled with parallel lines under the even-odd rule (`rm_hatch_slices`): `lines` holds
+    /// (dx, dy, offset, spacing) per layer of the slices, `n_lines` lines per layer; `flags`: `RM_HATCH_ZIGZAG` or 0.  Fills
+    /// `out_counts` (at least `RM_HATCH_COUNTS` entries indexed by `RM_HATCH_*`) and `out_stats` (at least `RM_HATCH_STATS`).
+    /// Returns the number of hatch segments; `read_hatch` copies them out.  A call that fails leaves the previous hatch readable.
+    pub fn hatch_slices(&self, lines: &[f32], n_lines: u32, flags: u32, out_counts: &mut [u64], out_stats: &mut [u64]) -> Result<u64, RmError> {
+        assert!(lines.len() % 4 == 0 && lines.len() / 4 <= u32::MAX as usize, "hatch_slices: lines holds four floats per layer");
+        assert!(out_counts.len() >= RM_HATCH_COUNTS as usize, "hatch_slices: out_counts is shorter than RM_HATCH_COUNTS entries");
+        assert!(out_stats.len() >= RM_HATCH_STATS as usize, "hatch_slices: out_stats is shorter than RM_HATCH_STATS entries");
+        self.check(unsafe {
+            rm_hatch_slices(self.ctx, lines.as_ptr(), (lines.len() / 4) as u32, n_lines, flags, out_counts.as_mut_ptr(),
+                            RM_HATCH_COUNTS as u32, out_stats.as_mut_ptr(), RM_HATCH_STATS as u32)
+        })?;
+        let h = out_counts[RM_HATCH_SEGMENTS as usize];
+        self.hatch.set(Some((h, (lines.len() / 4) as u32)));
+        Ok(h)
+    }
+
+    /// The hatch of the last successful `hatch_slices`: segments (u, v of the first end, u, v of the second; four per segment),
+    /// line (layer * n_lines + j; one per segment), layer_first (layers + 1 entries).  `None` skips that output.  `RM_ERR_ARG`
+    /// without a hatch of the current slices.
+    pub fn read_hatch(&self, out_segments: Option<&mut [f32]>, out_line: Option<&mut [u32]>,
+                      out_layer_first: Option<&mut [u32]>) -> Result<(), RmError> {
+        let (h, l) = match self.hatch.get() {
+            Some((h, l)) => (h as usize, l as usize),
+            None => return Err(RmError { status: RM_ERR_ARG, message: "read_hatch: no hatch of the current slices".to_string() }),
+        };
+        assert!(out_segments.as_ref().map_or(true, |s| s.len() >= 4 * h), "read_hatch: out_segments is shorter than {} segments", h);
+        assert!(out_line.as_ref().map_or(true, |s| s.len() >= h), "read_hatch: out_line is shorter than {} segments", h);
+        assert!(out_layer_first.as_ref().map_or(true, |s| s.len() >= l + 1), "read_hatch: out_layer_first is shorter than {} entries", l + 1);
+        let ps = out_segments.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pl = out_line.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        let pf = out_layer_first.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr());
+        self.check(unsafe { rm_read_hatch(self.ctx, ps, pl, pf, 0, std::ptr::null_mut()) })
     }
 }
 

@@ -945,6 +945,42 @@ int rm_slice_mesh(rm_ctx* ctx, const float* xyz, uint32_t n_vertices, const uint
                   void* stream, const float* origin, const float* step, uint32_t axis, const float* heights, uint32_t n_layers,
                   uint32_t flags, uint64_t* out_counts, uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats);
 
+/* Hatching (extension; DESIGN.md section 31 is the contract, to the last bit): the retained slices -- of rm_slice_contours or of
+ * rm_slice_mesh -- filled layer by layer with parallel lines under the even-odd rule: infill, scan vectors, section hatching.  The
+ * slices are read on the device and never changed.  lines: a HOST array of n_layers x 4 floats (dx, dy, offset, spacing) per
+ * layer, n_layers the slices' own layer count; n_lines lines per layer (1..2^24, n_layers * n_lines <= 2^32).
+ * Frame: w the slices' axis, u = (w + 1) % 3, v = (w + 2) % 3.  The normal coordinate of a point is
+ * s(P) = (double)P_v (double)dx - (double)P_u (double)dy (exact products, one rounded difference; the direction need not be a unit
+ * vector: offset and spacing are in units of s).  Line j of a layer lies at c_j = (double)offset + (double)j (double)spacing.
+ * Point i of a contour with first point f and n points is the tail of the segment to f + (i - f + 1) % n -- the last point of an
+ * open contour of none --, and the segment's id is i.  With A its end of the smaller s and B the other, the segment CROSSES line
+ * j iff sA <= c_j < sB; sA == sB or a value that is not finite crosses nothing.  The crossing's point, in binary64 without fma:
+ * t = (c_j - sA) / (sB - sA), X_a = (float)((double)A_a + t ((double)B_a - (double)A_a)) on a = u, v; its place along the line
+ * r = (float)((double)X_u (double)dx + (double)X_v (double)dy), as key32 = bits(r) ^ (sign ? 0xFFFFFFFF : 0x80000000).  Crossings
+ * are enumerated by (segment id, j) and sorted stably by L * 2^32 + key32, L = layer * n_lines + j: equal keys keep the enumeration's
+ * order.  On each line the crossings of ranks 2 i and 2 i + 1 are one hatch segment; a line with an odd number -- open contours
+ * alone cause one -- drops its last and counts in ODD_LINES; zero-length segments are kept.  Segments are ordered by L, then rank;
+ * with RM_HATCH_ZIGZAG the segments of a line with odd j come in reverse order with their ends swapped.
+ * Results (rm_read_hatch): segments H x 4 floats (u, v of the first end, u, v of the second), line H u32 (L), layer_first
+ * n_layers + 1 u32 (the segment each layer starts at; the last entry is H).  Identical from run to run.
+ * out_counts (enum rm_hatchcount, n_counts >= RM_HATCH_COUNTS): SEGMENTS_IN the contour segments looked at, CROSSINGS, SEGMENTS = H,
+ * LINES_HIT the lines with a crossing, ODD_LINES.  out_stats (enum rm_hatchstat, n_stats >= RM_HATCH_STATS).
+ * Refusals, in this order: RM_ERR_NULL for lines, out_counts or out_stats NULL; RM_ERR_ARG for n_counts or n_stats too small,
+ * unknown flags, no valid slices, n_layers other than the slices', a value of lines that is not finite, spacing <= 0,
+ * dx = dy = 0; RM_ERR_RANGE for n_lines outside 1..2^24, n_layers * n_lines > 2^32, 2^32 crossings or more; RM_ERR_DEVICE when
+ * device memory runs out.  Every one of them leaves the previous hatch and the slices readable.  The hatch lives in buffers of its
+ * own until the next rm_hatch_slices, rm_destroy, or any call that replaces the slices (rm_slice_contours, rm_slice_mesh): from
+ * there on rm_read_hatch is RM_ERR_ARG until the next hatch.  Synchronous; touches no other family's result and no draw state. */
+enum rm_hatchflag { RM_HATCH_ZIGZAG = 1 };
+enum rm_hatchcount { RM_HATCH_SEGMENTS_IN = 0, RM_HATCH_CROSSINGS = 1, RM_HATCH_SEGMENTS = 2, RM_HATCH_LINES_HIT = 3, RM_HATCH_ODD_LINES = 4,
+                     RM_HATCH_COUNTS = 5 };
+enum rm_hatchstat { RM_HATCH_STAT_SORT_PASSES = 0, RM_HATCH_STAT_SCRATCH_BYTES = 1, RM_HATCH_STATS = 2 };
+int rm_hatch_slices(rm_ctx* ctx, const float* lines, uint32_t n_layers, uint32_t n_lines, uint32_t flags, uint64_t* out_counts,
+                    uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats);
+/* Copies the last hatch out; any output may be NULL.  RM_ERR_ARG without a valid hatch.  is_device and stream as for
+ * rm_read_slices (device arrays: out_segments 16-byte aligned, the others 4-byte). */
+int rm_read_hatch(rm_ctx* ctx, float* out_segments, uint32_t* out_line, uint32_t* out_layer_first, int is_device, void* stream);
+
 /* Lit rendering (extension): rm_draw with soft shadows and ambient occlusion marched through the same distance field
  * (DESIGN.md section 13 is the contract, to the last bit).  The reference has one fixed light and max(0.02, n.l)
  * (wgsl:98-105); with RM_LIGHT_SHADOW = 0 and RM_LIGHT_AO = 0 rm_draw_lit writes rm_draw's image bit for bit.

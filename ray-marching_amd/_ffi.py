@@ -151,6 +151,12 @@ MSLICE_COUNT_NAMES = ("triangles", "rejected", "paired_edges", "border_edges", "
                       "open_contours")
 (RM_MSLICE_STAT_SORT_PASSES, RM_MSLICE_STAT_RANK_ROUNDS, RM_MSLICE_STAT_SCRATCH_BYTES, RM_MSLICE_STATS) = range(4)
 MSLICE_STAT_NAMES = ("sort_passes", "rank_rounds", "scratch_bytes")
+# hatching (rm_hatch_slices / rm_read_hatch): enum rm_hatchflag, enum rm_hatchcount, enum rm_hatchstat
+RM_HATCH_ZIGZAG = 1
+(RM_HATCH_SEGMENTS_IN, RM_HATCH_CROSSINGS, RM_HATCH_SEGMENTS, RM_HATCH_LINES_HIT, RM_HATCH_ODD_LINES, RM_HATCH_COUNTS) = range(6)
+HATCH_COUNT_NAMES = ("segments_in", "crossings", "segments", "lines_hit", "odd_lines")
+(RM_HATCH_STAT_SORT_PASSES, RM_HATCH_STAT_SCRATCH_BYTES, RM_HATCH_STATS) = range(3)
+HATCH_STAT_NAMES = ("sort_passes", "scratch_bytes")
 # the device sort (csrc/rm_sort.h, rm_selftest_sort): rml::kSortTile, the pairs one workgroup ranks
 SORT_TILE = 1024
 # lit rendering (rm_lighting_defaults / rm_set_lighting / rm_draw_lit): enum rm_light, the parameter names in index order
@@ -341,6 +347,10 @@ def hip_lib():
         L.rm_slice_case_table.restype = C.c_int
         L.rm_slice_mesh.argtypes = [vp, vp, u32, vp, u32, C.c_int, vp, f3, f3, u32, f3, u32, u32, C.POINTER(u64), u32, C.POINTER(u64), u32]
         L.rm_slice_mesh.restype = C.c_int
+        L.rm_hatch_slices.argtypes = [vp, f3, u32, u32, u32, C.POINTER(u64), u32, C.POINTER(u64), u32]
+        L.rm_hatch_slices.restype = C.c_int
+        L.rm_read_hatch.argtypes = [vp, vp, vp, vp, C.c_int, vp]
+        L.rm_read_hatch.restype = C.c_int
         L.rm_program_lipschitz.argtypes = [u32, C.POINTER(u32), u32, C.POINTER(C.c_double)]
         L.rm_program_lipschitz.restype = C.c_int
         L.rm_lighting_defaults.argtypes = [f3, u32]

@@ -43,6 +43,7 @@
 #include "rm_slice.h"
 #include "rm_sort.h"
 #include "rm_mesh_slice.h"
+#include "rm_hatch.h"
 #include "rm_light.h"
 #include "rm_gbuffer.h"
 
@@ -178,10 +179,22 @@ struct rm_ctx {
         DevBuf<char> points, contours, attr, layers;  // layers (rml::SliceLayerTables) also holds the call's small scratch
         bool valid = false;
         uint64_t p = 0, c = 0;
-        uint32_t n_layers = 0, flags = 0;
+        uint32_t n_layers = 0, flags = 0, axis = 0;
         void drop() { valid = false; }
-        void commit(uint64_t p_, uint64_t c_, uint32_t n_layers_, uint32_t flags_) { p = p_, c = c_, n_layers = n_layers_, flags = flags_, valid = true; }
+        void commit(uint64_t p_, uint64_t c_, uint32_t n_layers_, uint32_t flags_, uint32_t axis_) {
+            p = p_, c = c_, n_layers = n_layers_, flags = flags_, axis = axis_, valid = true;
+        }
     } slices;
+    struct Hatch {  // rm_hatch_slices: the arrays of rml::HatchSlot(h, n_layers) in buf; of the slices as they were at the call
+        DevBuf<char> buf;
+        bool valid = false;
+        uint64_t h = 0;
+        uint32_t n_layers = 0;
+        void drop() { valid = false; }
+        void commit(uint64_t h_, uint32_t n_layers_) { h = h_, n_layers = n_layers_, valid = true; }
+    } hatch;
+    // A call that replaces the slices: their hatch is no longer of slices that exist.
+    void drop_slices() { slices.drop(), hatch.drop(); }
     DevBuf<char> d_swork;  // slicing (rm_slice.h): the per-vertex scratch of a batch of layers
     struct Labels {  // rm_label_*: the label volume of n points and the rows (rml::TopoRows) of b bodies and c cavities
         DevBuf<char> labels, rows;
@@ -3250,7 +3263,7 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
     QueryCall q;
     int rc = q.begin(c, s, (flags & RM_MESH_IDS) != 0, false);  // after a device read of the previous slices, too
     if (rc != RM_OK) return rc;
-    c->slices.drop();
+    c->drop_slices();
     const uint32_t n2 = (uint32_t)n2_64, per = std::min(n_layers, std::max(1u, rmk::kSliceBatchPoints / n2));
     const uint32_t n_max = per * n2, nb_max = blocks_of(n_max, rmk::kSliceBlock);
     const rml::SliceLayerTables T(n_layers, per);
@@ -3351,7 +3364,7 @@ RM_EXPORT int rm_slice_contours(rm_ctx* c, uint32_t axis, const float* origin_uv
     HIP_TRY(c, hipStreamSynchronize(s));
     out_counts[RM_SLICE_POINTS] = P;
     out_counts[RM_SLICE_CONTOURS] = Cn;
-    c->slices.commit(P, Cn, n_layers, flags);
+    c->slices.commit(P, Cn, n_layers, flags, axis);
     return RM_OK;
 }
 
@@ -3474,7 +3487,7 @@ RM_EXPORT int rm_slice_mesh(rm_ctx* c, const float* xyz, uint32_t n_vertices, co
     if (N == 0u) {
         if ((rc = reserve_beside(c, c->slices.layers, T.bytes, f_layers)) != RM_OK) return rc;
         // the last check that can refuse is past: the previous slices go
-        c->slices.drop();
+        c->drop_slices();
         move_in(c->slices.layers, f_layers);
         HIP_TRY(c, hipMemsetAsync(T.layer_first.at(c->slices.layers.p), 0, T.layer_first.bytes, s));
         HIP_TRY(c, hipStreamSynchronize(s));
@@ -3538,7 +3551,7 @@ RM_EXPORT int rm_slice_mesh(rm_ctx* c, const float* xyz, uint32_t n_vertices, co
         if ((rc = reserve_beside(c, c->slices.points, (size_t)N * 12u, f_points)) != RM_OK) return rc;
         if ((rc = reserve_beside(c, c->slices.contours, (size_t)Cb * 16u, f_contours)) != RM_OK) return rc;
         if ((rc = reserve_beside(c, c->slices.layers, T.bytes, f_layers)) != RM_OK) return rc;
-        c->slices.drop();
+        c->drop_slices();
         move_in(c->slices.points, f_points);
         move_in(c->slices.contours, f_contours);
         move_in(c->slices.layers, f_layers);
@@ -3568,8 +3581,123 @@ RM_EXPORT int rm_slice_mesh(rm_ctx* c, const float* xyz, uint32_t n_vertices, co
     out_stats[RM_MSLICE_STAT_SORT_PASSES] = E.passes + item_passes;
     out_stats[RM_MSLICE_STAT_RANK_ROUNDS] = rounds;
     out_stats[RM_MSLICE_STAT_SCRATCH_BYTES] = scratch_bytes;
-    c->slices.commit(N, Cb, n_layers, 0u);
+    c->slices.commit(N, Cb, n_layers, 0u, axis);
     return RM_OK;
+}
+
+// ---- hatching (rm_hatch.h) ----
+static_assert(RM_HATCH_STAT_SCRATCH_BYTES == RM_HATCH_STATS - 1, "the scratch size last");
+
+RM_EXPORT int rm_hatch_slices(rm_ctx* c, const float* lines, uint32_t n_layers, uint32_t n_lines, uint32_t flags, uint64_t* out_counts,
+                              uint32_t n_counts, uint64_t* out_stats, uint32_t n_stats) {
+    const char* fn = "rm_hatch_slices";
+    if (!c) return RM_ERR_NULL;
+    if (!lines || !out_counts || !out_stats) return fail(c, RM_ERR_NULL, "%s: lines, out_counts or out_stats is NULL", fn);
+    if (n_counts < (uint32_t)RM_HATCH_COUNTS) return fail(c, RM_ERR_ARG, "%s: n_counts %u < RM_HATCH_COUNTS", fn, n_counts);
+    if (n_stats < (uint32_t)RM_HATCH_STATS) return fail(c, RM_ERR_ARG, "%s: n_stats %u < RM_HATCH_STATS", fn, n_stats);
+    if ((flags & ~(uint32_t)RM_HATCH_ZIGZAG) != 0u) return fail(c, RM_ERR_ARG, "%s: flags 0x%x: RM_HATCH_ZIGZAG or 0", fn, flags);
+    const rm_ctx::Slices& sl = c->slices;
+    if (!sl.valid) return fail(c, RM_ERR_ARG, "%s: nothing has been sliced", fn);
+    if (n_layers != sl.n_layers) return fail(c, RM_ERR_ARG, "%s: %u line sets for slices of %u layers", fn, n_layers, sl.n_layers);
+    for (uint32_t k = 0; k < n_layers; k++) {
+        const float* l = lines + (size_t)k * 4u;
+        if (!std::isfinite(l[0]) || !std::isfinite(l[1]) || !std::isfinite(l[2]) || !std::isfinite(l[3]))
+            return fail(c, RM_ERR_ARG, "%s: lines[%u] = (%g, %g, %g, %g) is not finite", fn, k, (double)l[0], (double)l[1], (double)l[2], (double)l[3]);
+        if (!(l[3] > 0.0f)) return fail(c, RM_ERR_ARG, "%s: lines[%u]: spacing %g must be > 0", fn, k, (double)l[3]);
+        if (l[0] == 0.0f && l[1] == 0.0f) return fail(c, RM_ERR_ARG, "%s: lines[%u]: the direction is (0, 0)", fn, k);
+    }
+    if (n_lines < 1u || n_lines > rml::kHatchMaxLines) return fail(c, RM_ERR_RANGE, "%s: %u lines per layer: 1..2^24", fn, n_lines);
+    const uint64_t all_lines = (uint64_t)n_layers * n_lines;
+    if (all_lines > (1ull << 32)) return fail(c, RM_ERR_RANGE, "%s: %u layers of %u lines: more than 2^32 lines", fn, n_layers, n_lines);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const hipStream_t s = c->stream;
+    order_with_previous(c, s);  // after a device read of the slices or of the previous hatch, too
+    const uint32_t P = (uint32_t)sl.p, pb = blocks_of(P, rmk::kSliceBlock);
+    const rml::HatchScratch S(P, n_layers);
+    int rc = c->d_mscratch.reserve(c, S.bytes);
+    if (rc != RM_OK) return rc;
+    char* sc = c->d_mscratch.p;
+    size_t scratch_bytes = S.bytes;
+    uint32_t N = 0, passes = 0;
+    uint64_t H = 0;
+    unsigned long long crow[RM_MOMENTS] = {}, prow[RM_MOMENTS] = {};
+    rmk::HatchFrame f{};
+    f.u = sl.axis == 2u ? 0u : sl.axis + 1u, f.v = f.u == 2u ? 0u : f.u + 1u;
+    f.n_points = P, f.n_contours = (uint32_t)sl.c, f.n_lines = n_lines;
+    const float* points = sl.points.as<const float>();
+    const uint4* contours = sl.contours.as<const uint4>();
+    const float4* d_lines = reinterpret_cast<const float4*>(S.lines.at(sc));
+    uint32_t* cstart = S.cstart.at(sc);
+    uint32_t* j0 = S.j0.at(sc);
+    if (P > 0u) {
+        HIP_TRY(c, hipMemcpyAsync(S.lines.at(sc), lines, (size_t)n_layers * 16u, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(rmk::rm_hatch_count_kernel, dim3(pb), dim3(256), 0, s, f, points, contours, d_lines, cstart, j0, S.bsums.at(sc), S.rows.at(sc));
+        HIP_TRY(c, hipGetLastError());
+        if ((rc = scan_launch(c, s, S.bsums.at(sc), pb, S.btot.at(sc))) != RM_OK) return rc;
+        uint64_t tot[2];
+        if ((rc = reduce_rows(c, s, S.rows.at(sc), pb, S.folded.at(sc), S.result.at(sc), crow, {tot, S.btot.at(sc), sizeof tot})) != RM_OK) return rc;
+        if (!rml::hatch_crossings_fit(tot[0], tot[1])) return fail(c, RM_ERR_RANGE, "%s: 2^32 crossings or more", fn);
+        N = (uint32_t)tot[0];
+    }
+    DevBuf<char> fresh;
+    if (N == 0u) {
+        const rml::HatchSlot T(0u, n_layers);
+        if ((rc = reserve_beside(c, c->hatch.buf, T.bytes, fresh)) != RM_OK) return rc;
+        // the last check that can refuse is past: the previous hatch goes
+        c->hatch.drop();
+        move_in(c->hatch.buf, fresh);
+        HIP_TRY(c, hipMemsetAsync(T.layer_first.at(c->hatch.buf.p), 0, T.layer_first.bytes, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+    } else {
+        const rml::HatchItems I(N);
+        if ((rc = c->d_mbricks.reserve(c, I.bytes)) != RM_OK) return rc;
+        scratch_bytes += I.bytes;
+        char* ic = c->d_mbricks.p;
+        const uint32_t nb = blocks_of(N, rmk::kSliceBlock);
+        float2* xs = reinterpret_cast<float2*>(I.xs.at(ic));
+        uint32_t* hstart = I.hstart.at(ic);
+        hipLaunchKernelGGL(rmk::rm_mslice_scan_kernel, dim3(pb), dim3(256), 0, s, P, S.bsums.at(sc), cstart);
+        hipLaunchKernelGGL(rmk::rm_hatch_items_kernel, dim3(blocks_of(N, 256u)), dim3(256), 0, s, f, N, points, contours, d_lines, cstart, j0,
+                           I.ikeys.at(ic), I.ivals.at(ic), xs);
+        const rml::SortedPairs V = rml::sort_pairs(s, I.ikeys.at(ic), I.ivals.at(ic), N, rml::hatch_key_bits(all_lines), ic + I.sort);
+        passes = V.passes;
+        hipLaunchKernelGGL(rmk::rm_hatch_pair_kernel, dim3(nb), dim3(256), 0, s, N, V.keys, hstart, I.bsums.at(ic), I.rows.at(ic));
+        HIP_TRY(c, hipGetLastError());
+        if ((rc = scan_launch(c, s, I.bsums.at(ic), nb, I.btot.at(ic))) != RM_OK) return rc;
+        uint64_t htot[2];
+        if ((rc = reduce_rows(c, s, I.rows.at(ic), nb, I.folded.at(ic), I.result.at(ic), prow, {htot, I.btot.at(ic), sizeof htot})) != RM_OK) return rc;
+        H = htot[0];  // (at most N / 2)
+        // every size is known: room for the result beside the previous one, which goes only when nothing can refuse any more
+        const rml::HatchSlot T(H, n_layers);
+        if ((rc = reserve_beside(c, c->hatch.buf, T.bytes, fresh)) != RM_OK) return rc;
+        c->hatch.drop();
+        move_in(c->hatch.buf, fresh);
+        char* hb = c->hatch.buf.p;
+        hipLaunchKernelGGL(rmk::rm_mslice_scan_kernel, dim3(nb), dim3(256), 0, s, N, I.bsums.at(ic), hstart);
+        hipLaunchKernelGGL(rmk::rm_hatch_emit_kernel, dim3(blocks_of(std::max(N, n_layers + 1u), 256u)), dim3(256), 0, s, N, n_layers, n_lines,
+                           flags & (uint32_t)RM_HATCH_ZIGZAG, V.keys, V.values, xs, hstart, reinterpret_cast<float4*>(T.segments.at(hb)),
+                           T.line.at(hb), T.layer_first.at(hb));
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(s));
+    }
+    out_counts[RM_HATCH_SEGMENTS_IN] = crow[0];
+    out_counts[RM_HATCH_CROSSINGS] = N;
+    out_counts[RM_HATCH_SEGMENTS] = H;
+    out_counts[RM_HATCH_LINES_HIT] = prow[0];
+    out_counts[RM_HATCH_ODD_LINES] = prow[1];
+    out_stats[RM_HATCH_STAT_SORT_PASSES] = passes;
+    out_stats[RM_HATCH_STAT_SCRATCH_BYTES] = scratch_bytes;
+    c->hatch.commit(H, n_layers);
+    return RM_OK;
+}
+
+RM_EXPORT int rm_read_hatch(rm_ctx* c, float* out_segments, uint32_t* out_line, uint32_t* out_layer_first, int is_device, void* stream) {
+    if (!c) return RM_ERR_NULL;
+    const rm_ctx::Hatch& r = c->hatch;
+    if (!r.valid) return fail(c, RM_ERR_ARG, "rm_read_hatch: no hatch of the current slices");
+    const rml::HatchSlot T(r.h, r.n_layers);
+    return read_back(c, is_device, stream, "rm_read_hatch: device arrays need 4-byte alignment (out_segments: 16-byte)",
+                     {{out_segments, T.segments, r.buf.p, 16}, {out_line, T.line, r.buf.p, 4}, {out_layer_first, T.layer_first, r.buf.p, 4}});
 }
 
 RM_EXPORT int rm_sync_context(rm_ctx* c) {

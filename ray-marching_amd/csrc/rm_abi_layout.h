@@ -430,6 +430,65 @@ struct MeshSliceItems {
           sort(a.total), bytes(a.total + SortScratch(N).bytes) {}
 };
 
+// rm_hatch_slices, for slices of P points in n_layers layers: per layer its line set (4 floats: dx, dy, offset, spacing); per point
+// (= per contour segment, numbered by its tail) the crossings before its own (P + 1 entries: the last is their number) and its first
+// line (4 B each); per kSortTile points a block sum (scanned in place) and the totals; one row of 16 counts per kSortTile points,
+// per 256 rows a folded row, the reduced row.
+constexpr uint32_t kHatchMaxLines = 1u << 24;
+struct HatchScratch {
+    Carver a;
+    Region<float> lines;
+    Region<uint32_t> cstart, j0;
+    Region<unsigned long long> bsums, btot, rows, folded, result;
+    size_t bytes;
+    HatchScratch(uint32_t P, uint32_t n_layers)
+        : lines(a.take<float>((size_t)n_layers * 4u)), cstart(a.take<uint32_t>((size_t)P + 1u)), j0(a.take<uint32_t>(P)),
+          bsums(a.take<unsigned long long>(sort_tiles(P))), btot(a.take<unsigned long long>(2)),
+          rows(a.take<unsigned long long>((size_t)sort_tiles(P) * 16u)),
+          folded(a.take<unsigned long long>((size_t)((sort_tiles(P) + 255u) / 256u) * 16u)), result(a.take<unsigned long long>(16)),
+          bytes(a.total) {}
+};
+
+// ... and per crossing (N of them; an ITEM is a crossing in the order (segment, line)): the item's sort key (8 B) and number (4 B),
+// its point (u, v: 8 B), the hatch segments before its own in sorted order (N + 1 entries: the last is H); the block sums, rows
+// and totals as above; and the sort's scratch.
+struct HatchItems {
+    Carver a;
+    Region<unsigned long long> ikeys;
+    Region<uint32_t> ivals;
+    Region<float> xs;
+    Region<uint32_t> hstart;
+    Region<unsigned long long> bsums, btot, rows, folded, result;
+    size_t sort, bytes;
+    explicit HatchItems(uint32_t N)
+        : ikeys(a.take<unsigned long long>(N)), ivals(a.take<uint32_t>(N)), xs(a.take<float>((size_t)N * 2u)),
+          hstart(a.take<uint32_t>((size_t)N + 1u)), bsums(a.take<unsigned long long>(sort_tiles(N))), btot(a.take<unsigned long long>(2)),
+          rows(a.take<unsigned long long>((size_t)sort_tiles(N) * 16u)),
+          folded(a.take<unsigned long long>((size_t)((sort_tiles(N) + 255u) / 256u) * 16u)), result(a.take<unsigned long long>(16)),
+          sort(a.total), bytes(a.total + SortScratch(N).bytes) {}
+};
+
+// ... and the retained slot of H hatch segments in n_layers layers: the segments (4 floats: u, v of one end, u, v of the other),
+// their lines (4 B) and layer_first (n_layers + 1 entries).
+struct HatchSlot {
+    Carver a;
+    Region<float> segments;
+    Region<uint32_t> line, layer_first;
+    size_t bytes;
+    HatchSlot(uint64_t H, uint32_t n_layers)
+        : segments(a.take<float>(H * 4u)), line(a.take<uint32_t>(H)), layer_first(a.take<uint32_t>((size_t)n_layers + 1u)), bytes(a.total) {}
+};
+
+// The count pass's block sums are 64-bit numbers that rm_block_scan_kernel adds up half by half: lo = the sum of the low halves,
+// hi = that of the high ones.  The crossings fit 32 bits iff no block sum has a high half and the low halves' sum is below 2^32.
+constexpr bool hatch_crossings_fit(uint64_t lo, uint64_t hi) { return hi == 0u && lo < (1ull << 32); }
+// The bits of the sort key L << 32 | key32 for all_lines = n_layers * n_lines lines (1..2^32): 32 + the bit length of all_lines - 1.
+constexpr uint32_t hatch_key_bits(uint64_t all_lines) {
+    uint32_t b = 0;
+    while (b < 32u && ((all_lines - 1u) >> b) != 0u) b++;
+    return 32u + b;
+}
+
 // rm_trace_rays' scratch of the attribute pass over n rays (nb workgroups of 256) with K event slots each: the stored count
 // per ray, the workgroups' sums (scanned in place into offsets), the total (2 of 4 words), the compact (ray, slot) list -- K
 // entries per ray at most -- and, only when the caller takes no event records, a copy of them for the positions.  Pair is the

@@ -1096,6 +1096,29 @@ class RayMarchingResources:
         """rm_read_slices of the last slice call into device memory (integer addresses; 0 = not wanted), asynchronous."""
         self._read_into(self._L.rm_read_slices, (points_ptr, contours_ptr, layer_first_ptr, normals_ptr, ids_ptr), True, stream)
 
+    # -- hatching (rm_hatch_slices / rm_read_hatch) -------------------------------------------------------------------------------
+    def hatch_slices(self, lines, n_lines, zigzag=False, device=False):
+        """rm_hatch_slices: the slices this context retains -- of the last slice_contours or slice_mesh -- filled with parallel
+        lines under the even-odd rule: a slicer.Hatch.  lines: (n_layers, 4) float32, (dx, dy, offset, spacing) per layer, in the
+        slices' in-plane frame (u, v); n_lines lines per layer, line j at offset + j * spacing of the normal coordinate
+        s = v dx - u dy (slicer.hatch_lines chooses both from an angle and a spacing).  zigzag: the segments of every other line
+        reversed.  device=True: torch tensors on the GPU."""
+        from . import slicer as _slicer
+        l = np.array(lines, dtype=np.float32, copy=True)
+        if l.ndim != 2 or l.shape[1] != 4:
+            raise ValueError("lines must be (n_layers, 4): dx, dy, offset, spacing per layer")
+        l = np.ascontiguousarray(l)
+        counts, stats = (C.c_uint64 * _ffi.RM_HATCH_COUNTS)(), (C.c_uint64 * _ffi.RM_HATCH_STATS)()
+        self._check(self._L.rm_hatch_slices(self._h, l.ctypes.data_as(C.POINTER(C.c_float)), len(l), int(n_lines),
+                                            _ffi.RM_HATCH_ZIGZAG if zigzag else 0, counts, _ffi.RM_HATCH_COUNTS, stats, _ffi.RM_HATCH_STATS))
+        H = int(counts[_ffi.RM_HATCH_SEGMENTS])
+        seg, line, lf = self._read_new(self._L.rm_read_hatch, [((H, 4), *_F32, True), ((H,), *_U32, True), ((len(l) + 1,), *_U32, True)], device)
+        return _slicer.Hatch(seg, line, lf, l, int(n_lines), _named(counts, _ffi.HATCH_COUNT_NAMES), _named(stats, _ffi.HATCH_STAT_NAMES))
+
+    def read_hatch_device(self, segments_ptr=0, line_ptr=0, layer_first_ptr=0, stream=None):
+        """rm_read_hatch of the last hatch into device memory (integer addresses; 0 = not wanted), asynchronous."""
+        self._read_into(self._L.rm_read_hatch, (segments_ptr, line_ptr, layer_first_ptr), True, stream)
+
 
 class RayMarchingCallback:
     """Per-frame value object (renderer.rs:177-193) with the reference's prepare/paint split."""
